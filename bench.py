@@ -23,7 +23,7 @@ bytes, so that figure is not a fraction of anything.  traffic = measured HBM byt
 passes of tools/profile.sh, taken from profiles/traffic.json ONLY if that file was measured on this very
 sk_device.hip + sk_dev_*.hip.h (sha256 stamp), else null.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--no-cpu] [--dump-outputs DIR]
   N > 1, either way:
     python bench.py --gpus N ...                       (no WORLD_SIZE in the environment: this process starts the N ranks itself --
                                                         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -374,6 +374,30 @@ def strain_detect_leg(device, oracle_sample_reads=20_000, repeat=10):
     return out
 
 
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET_BYTES = 60 << 20           # (under 64 MB however counted, the .npy headers included)
+DUMP_SAMPLE_SEED = 0x5EED31
+
+
+def dump_outputs(where, arrays):
+    """write each array as where/<name>.npy in float64 (exact for the u32 counts).  Over DUMP_BUDGET_BYTES in all, every array
+    is cut to the same fixed, seeded sample of its rows, and the sampled row indices go beside it as where/<name>_rows.npy"""
+    os.makedirs(where, exist_ok=True)
+    total = sum(8 * a.size for a in arrays.values())
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.size * DUMP_BUDGET_BYTES / total) // 2)       # (values + row indices, both float64)
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False))
+            a = a[rows]
+            out[name + "_rows"] = rows.astype(np.float64)
+        out[name] = a.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(where, name + ".npy"), a)
+    return {name: int(a.size) for name, a in out.items()}
+
+
 # ----------------------------------------------------------------------------- N > 1 from the plain command
 def launch_ranks(gpus, argv):
     """`python bench.py --gpus N` with no launcher around it (the driver's own command): start the N ranks as a
@@ -438,7 +462,13 @@ def main():
     ap.add_argument("--grid-kib", type=int, default=None, help="size of the grid kernel's level-1 filter in KiB (default: automatic)")
     ap.add_argument("--text-stage", type=int, default=None, help="0 = stage 2 without the strain's text (A/B)")
     ap.add_argument("--ablate", type=int, default=0, help="timing experiments: 1 = no filter/table memory, 2 = no table probes (counts are wrong)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the -B column's per-k-mer count vector of one step "
+                         "(all ranks' sum when N > 1), in the key set's row order -- as DIR/counts_per_step.npy (float64, at most 64 MB: "
+                         "a fixed, seeded sample of the rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:        # the plain command: be the launcher (no GPU, no torch in this process)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -569,6 +599,12 @@ def main():
         parity = {"facts": "tests/golden/cfg2_facts.json", "checked": True, "producer": facts.get("producer"),
                   "what": "counts of the timed passes / steps == the reference's metagenome_count column (sum, non-zero rows, md5)"
                           if world == 1 else "reduced total == sum of the ranks' reference sums; every rank's own stream re-scanned once and md5-checked"}
+    if args.dump_outputs and rank == 0:
+        # every timed step adds the same vector to the column (checked above, unless --ablate: the counts are K x one pass), so the
+        # column / K is exactly what the last step computed
+        written = dump_outputs(args.dump_outputs, {"counts_per_step": counts // args.steps})
+        print("bench.py: wrote %s to %s" % (", ".join("%s.npy (%d values)" % kv for kv in written.items()), args.dump_outputs),
+              file=sys.stderr, flush=True)
 
     # PCIe-inclusive rate (host buffer -> pinned staging -> H2D -> scan), reported beside `value`,
     # never as it: 2 passes of sk_scan_stream over the same record stream

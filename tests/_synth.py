@@ -39,6 +39,93 @@ def fuzz_stream(rng: random.Random, strain: bytes, nreads: int, junk=b"NnRYKMUu-
     return b"\n".join(out) + b"\n"
 
 
+def oracle_fuzz_world(seed: int, d) -> list:
+    """Random FASTA/FASTQ soup (junk bytes, CRLF, blank lines, multi-line, '>'/'@'/'+' traps) for one kmer_scrub_count
+    job, written into directory `d`; returns the job's argv (paths relative to `d`).  What the reference printed for
+    it is in tests/golden/fuzz_facts.json (tests/golden/make_fuzz_facts.py)."""
+    rng = random.Random(seed)
+    strain = rand_dna(rng, 3000)
+    lines = [b">s1 c\n"]
+    for i in range(0, len(strain), 70):
+        lines.append(strain[i:i + 70] + b"\n")
+    with open(os.path.join(d, "strain.fa"), "wb") as f:
+        f.write(b"".join(lines))
+    files = []
+    for fi in range(3):
+        recs = fuzz_stream(rng, strain, 200, p_junk=0.01, min_len=0, max_len=160).split(b"\n")[:-1]
+        body = bytearray()
+        for i, r in enumerate(recs):
+            style = rng.randrange(5)
+            r = r.replace(b"\r", b"A")
+            if style == 0:
+                body += b">r%d\n" % i + r + b"\n"
+            elif style == 1:
+                w = rng.choice([20, 50, 61])
+                body += b">r%d desc\r\n" % i + b"\r\n".join(r[j:j + w] for j in range(0, len(r), w)) + b"\r\n"
+            elif style == 2:
+                q = bytes(rng.choice(b"@+>IJK#") for _ in r)
+                body += b"@q%d\n" % i + r + b"\n+\n" + q + b"\n"
+            elif style == 3:
+                body += b">r%d\n\n" % i + r[:len(r) // 2] + b"\n\n" + r[len(r) // 2:] + b"\n"
+            else:
+                body += b"junk before header\n>r%d\t x\n" % i + r + b"\n"
+        name = "m%d.fx" % fi
+        with open(os.path.join(d, name), "wb") as f:
+            f.write(bytes(body))
+        files.append(name)
+    with open(os.path.join(d, "A.txt"), "w") as f:
+        f.write(files[0] + "\n")
+    with open(os.path.join(d, "B.txt"), "w") as f:
+        f.write("\n".join(files[1:]) + "\n")
+    return ["-r", "strain.fa", "-A", "A.txt", "-B", "B.txt"]
+
+
+def reader_soup(seed: int, d):
+    """A file thrown together from header, sequence, '+', quality and blank lines in every order -- equal and unequal
+    quality lengths, wrapped sequences, CR line ends, '@' and '>' opening quality lines, a missing last newline, plain
+    or gzipped, perhaps cut short -- written into directory `d`; returns (the strain its sequence comes from, the path)."""
+    import gzip
+    rng = random.Random(9000 + seed)
+    nl = rng.choice([b"\n", b"\n", b"\r\n"])
+    strain = rand_dna(rng, 3000)
+    out = []
+    for _ in range(rng.randrange(1, 400)):
+        kind = rng.random()
+        n = rng.choice([0, 1, 2, 30, 31, 40, 150, 151])
+        a = rng.randrange(0, len(strain) - n)
+        seq = strain[a:a + n]                              # (pieces of the strain: which bytes count as sequence shows in the table)
+        if seed % 3 == 0:                                  # every third soup is mostly one-line FASTA: the parser's other whole-record shortcut
+            kind = 0.6 if kind < 0.6 else kind
+        if kind < 0.55:                                    # a well-formed four-line record (now and then not quite)
+            q = bytes(rng.choice(b"FFFF:,#@>+I") for _ in range(n if rng.random() < 0.9 else rng.choice([0, 1, max(0, n - 1), n + 1])))
+            out += [b"@r%d some text" % len(out), seq, b"+" + (b"r" if rng.random() < 0.2 else b""), q]
+        elif kind < 0.62:                                  # FASTA, the sequence on one line, '>' or '@' header
+            out += [(b">" if rng.random() < 0.8 else b"@") + b"o%d len=%d" % (len(out), n), seq]
+        elif kind < 0.7:                                   # FASTA, wrapped
+            out += [b">c%d" % len(out)] + [seq[i:i + 60] for i in range(0, n, 60)]
+        elif kind < 0.8:                                   # FASTQ with wrapped sequence and quality
+            q = b"I" * n
+            out += [b"@w%d" % len(out)] + [seq[i:i + 50] for i in range(0, n, 50)] + [b"+"] + [q[i:i + 70] for i in range(0, n, 70)]
+        else:                                              # loose lines
+            out.append(rng.choice([b"", b"+", b"@", b">", b"\r", seq, b"@" + seq, b"+" + seq, b" ", b"\t@x"]))
+    text = nl.join(out) + (nl if rng.random() < 0.8 else b"")
+    if rng.random() < 0.3:
+        text = text[:rng.randrange(len(text) + 1)]
+    path = os.path.join(d, "soup.fq.gz" if seed % 2 else "soup.fq")
+    with open(path, "wb") as f:
+        f.write(gzip.compress(text, 6, mtime=0) if seed % 2 else text)
+    return strain, path
+
+
+def soup_job(strain: bytes, soup: str, d) -> list:
+    """the kmer_scrub_count job that scans a reader soup against its strain (-A and -B both name the soup)"""
+    with open(os.path.join(d, "strain.fa"), "wb") as f:
+        f.write(b">s\n" + strain + b"\n")
+    with open(os.path.join(d, "A.txt"), "w") as f:
+        f.write(soup + "\n")
+    return ["-r", os.path.join(d, "strain.fa"), "-A", os.path.join(d, "A.txt"), "-B", os.path.join(d, "A.txt")]
+
+
 
 def two_expansions_strain(golden, tmp_path):
     """the 9.2 Mbp strain of tests/golden/make_two_expansions_facts.py, written again by that script's own function; None if this

@@ -53,3 +53,37 @@ def test_under_a_launcher_the_world_must_match():
     e = dict(os.environ, WORLD_SIZE="3", RANK="0", SK_BENCH_RANK_SCRIPT=STUB)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--no-cpu"], env=e, capture_output=True, timeout=120)
     assert p.returncode != 0 and b"must be the same" in p.stderr
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_writes_exact_float64_and_samples_over_budget(tmp_path, monkeypatch):
+    """--dump-outputs DIR: each array as DIR/<name>.npy in float64 (u32 counts exactly); over the byte budget every array is cut
+    to the same seeded sample of rows, the row indices beside it, and two dumps of the same arrays are the same files"""
+    import numpy as np
+    bench = _bench_module()
+    counts = np.random.default_rng(1).integers(0, 2**32, size=1000, dtype=np.uint64).astype(np.uint32)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"counts_per_step": counts}) == {"counts_per_step": 1000}
+    got = np.load(tmp_path / "a" / "counts_per_step.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), counts)
+    assert sorted(os.listdir(tmp_path / "a")) == ["counts_per_step.npy"]
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    for d in ("b", "c"):
+        written = bench.dump_outputs(str(tmp_path / d), {"counts_per_step": counts})
+        assert 8 * sum(written.values()) <= 4000 and written["counts_per_step"] == written["counts_per_step_rows"] > 0
+    rows = np.load(tmp_path / "b" / "counts_per_step_rows.npy").astype(np.int64)
+    assert np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "counts_per_step.npy").astype(np.uint32), counts[rows])
+    for name in ("counts_per_step.npy", "counts_per_step_rows.npy"):
+        assert (tmp_path / "b" / name).read_bytes() == (tmp_path / "c" / name).read_bytes()
+
+
+def test_steps_below_one_is_refused_before_anything_starts():
+    p = _run(["--gpus", "2", "--steps", "0", "--backend", "gloo"])
+    assert p.returncode != 0 and p.stdout == b"" and b"--steps must be at least 1" in p.stderr

@@ -1,9 +1,8 @@
 """The oracle against the golden vectors (all produced by the unmodified reference binary,
-see tests/golden/make_golden.py) and, where oracle/_ref is present, against that binary live."""
+see tests/golden/make_golden.py and make_fuzz_facts.py) and, where oracle/_ref is present, against that binary live."""
 import hashlib
 import json
 import os
-import random
 
 import pytest
 
@@ -55,46 +54,23 @@ def test_oracle_bundled_example_md5(golden):
     assert hashlib.md5(p.stdout).hexdigest() == facts["stdout_md5"] == "75989a9bc31ef0b6f53a5112a60920bd"
 
 
-@pytest.mark.skipif(not _oracle.have_reference(), reason="oracle/_ref not built (GPU box)")
 @pytest.mark.parametrize("seed", [1, 2, 3])
-def test_oracle_equals_live_reference_on_fuzz(seed, tmp_path):
-    """Random FASTA/FASTQ soup (junk bytes, CRLF, blank lines, multi-line, '>'/'@'/'+' traps)."""
-    rng = random.Random(seed)
-    strain = _synth.rand_dna(rng, 3000)
-    lines = [b">s1 c\n"]
-    for i in range(0, len(strain), 70):
-        lines.append(strain[i:i + 70] + b"\n")
-    (tmp_path / "strain.fa").write_bytes(b"".join(lines))
-    files = []
-    for fi in range(3):
-        recs = _synth.fuzz_stream(rng, strain, 200, p_junk=0.01, min_len=0, max_len=160).split(b"\n")[:-1]
-        body = bytearray()
-        for i, r in enumerate(recs):
-            style = rng.randrange(5)
-            r = r.replace(b"\r", b"A")
-            if style == 0:
-                body += b">r%d\n" % i + r + b"\n"
-            elif style == 1:
-                w = rng.choice([20, 50, 61])
-                body += b">r%d desc\r\n" % i + b"\r\n".join(r[j:j + w] for j in range(0, len(r), w)) + b"\r\n"
-            elif style == 2:
-                q = bytes(rng.choice(b"@+>IJK#") for _ in r)
-                body += b"@q%d\n" % i + r + b"\n+\n" + q + b"\n"
-            elif style == 3:
-                body += b">r%d\n\n" % i + r[:len(r) // 2] + b"\n\n" + r[len(r) // 2:] + b"\n"
-            else:
-                body += b"junk before header\n>r%d\t x\n" % i + r + b"\n"
-        name = "m%d.fx" % fi
-        (tmp_path / name).write_bytes(bytes(body))
-        files.append(name)
-    (tmp_path / "A.txt").write_text(files[0] + "\n")
-    (tmp_path / "B.txt").write_text("\n".join(files[1:]) + "\n")
-    argv = ["-r", "strain.fa", "-A", "A.txt", "-B", "B.txt"]
-    ref = _oracle.run_reference_cli(argv, str(tmp_path))
+def test_oracle_equals_live_reference_on_fuzz(seed, golden, tmp_path):
+    """Random FASTA/FASTQ soup (junk bytes, CRLF, blank lines, multi-line, '>'/'@'/'+' traps): the oracle program against
+    what the reference printed for it (tests/golden/fuzz_facts.json, made by tests/golden/make_fuzz_facts.py) and, where
+    oracle/_ref is present, against that binary live."""
+    argv = _synth.oracle_fuzz_world(seed, str(tmp_path))
+    with open(os.path.join(golden, "fuzz_facts.json")) as f:
+        want = json.load(f)["oracle_fuzz"][str(seed)]
     ora = _oracle.run_oracle_cli(argv, str(tmp_path))
-    assert ref.returncode == ora.returncode == 0
-    assert ref.stdout == ora.stdout
-    assert ref.stderr == ora.stderr
+    assert want["argv"] == argv and want["returncode"] == ora.returncode == 0
+    assert (hashlib.md5(ora.stdout).hexdigest(), len(ora.stdout)) == (want["stdout_md5"], want["stdout_bytes"])
+    assert ora.stderr.decode("latin-1") == want["stderr"]
+    if _oracle.have_reference():
+        ref = _oracle.run_reference_cli(argv, str(tmp_path))
+        assert ref.returncode == ora.returncode == 0
+        assert ref.stdout == ora.stdout
+        assert ref.stderr == ora.stderr
 
 
 def test_oracle_on_the_cfg3_shaped_job(golden, tmp_path):
