@@ -209,6 +209,19 @@ int  sk_union_scan_timing(sk_union *u, double *total_ms, uint64_t *launches, int
 const char *sk_union_last_error(const sk_union *u);          /* of launch/collect */
 uint32_t sk_union_members(const sk_union *u);
 uint32_t sk_union_rows(const sk_union *u);                   /* the members' rows added up */
+/* COUNT on a union (kmer_scrub_count -S: many strains counted over ONE pass of the -A/-B/-C lists).  sk_union_count_enable gives
+ * the union's context ncols (1..16) zeroed count columns of sk_union_rows() u32 each, the difference array the scan needs and the
+ * map of every global row (base of member s + the member's counter index) to the row of its key's slot; calling it again with
+ * the same ncols does nothing.  sk_union_context: that context (owned by the union: never destroy it), on which
+ * sk_scan_stream / sk_scan_pinned[_packed] / sk_scan_device[_packed], skh_scan_file and skh_scan_list count into a union column;
+ * without count columns they refuse it with SK_E_STATE.  sk_union_counts_fold: union column `ucol` is folded into column
+ * `member_col` of every member whose bit is set in member_mask (subtract != 0: taken off, u32 wrapping -- a file counted
+ * for all members is taken back from some), then zeroed; synchronous.  Afterwards each such member's column has changed
+ * exactly as if the same batches had been scanned into it directly.  Replaces GEN_all_kmer_counts[_skip_file]()
+ * (src/genome_compare.c:149-177,115-146) run once per strain process (src/kmer_scrub_count.c:87-99). */
+int  sk_union_count_enable(sk_union *u, uint32_t ncols);
+sk_ctx *sk_union_context(sk_union *u);
+int  sk_union_counts_fold(sk_union *u, uint32_t ucol, uint32_t member_col, uint32_t member_mask, int subtract);
 
 /* Wait for all queued work of the context. */
 int sk_sync(sk_ctx *ctx);
@@ -351,6 +364,14 @@ int skh_print_counts(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug
 /* The whole program with the reference's argv contract (src/kmer_scrub_count.c:29-131).
  * Extra environment: SK_DEVICE (default 0).  Returns the process exit status. */
 int skh_kmer_scrub_count_main(int argc, char **argv, FILE *out, FILE *err);
+/* kmer_scrub_count -S <strains file> -A <list> -B <list> [-C <list>] [-p <progress>] (no -r; new): every line of the strains
+ * file is  <reference genome> TAB <outfile>  (empty lines and lines starting with '#' are skipped), and every outfile gets
+ * exactly what `kmer_scrub_count -r <genome> -A .. -B .. [-C ..]` writes on stdout (gzip when its name ends in .gz).  Up to
+ * SK_UNION_MAX strains share one union table and one pass over the lists (sk_union_count_enable / sk_union_counts_fold);
+ * a -C line equal to a strain's genome is taken back from that strain alone.  Environment: SK_SCRUB_GROUP=1..32 (strains
+ * per union), SK_SCRUB_NO_UNION=1 (a pass per strain); with WORLD_SIZE/RANK the strain lines are dealt to the ranks
+ * round-robin (no collective).  Returns the exit status. */
+int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err);
 
 /* The whole strain_detect program with the reference's argv contract (src/strain_detect.c:61-158):
  * -r -a -o and one of -b [-c] [-t SE|PE|PEI] / -B, optional -g.  Messages the reference prints on

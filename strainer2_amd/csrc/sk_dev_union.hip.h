@@ -217,3 +217,52 @@ __global__ void sk_union_ship(const unsigned long long *__restrict__ cnt, unsign
         cnt_next[0] = 0ull; cnt_next[1] = 0ull; cnt_next[2] = 0ull; cnt_next[3] = 0ull;
     }
 }
+
+// ---- COUNT on a union (kmer_scrub_count -S).  A scan into the union's column counts a window at the global row it was found
+// at: the key's slot row when a probe found it, base[s] + the member's counter index when it was verified against member s's
+// text.  Every row of a key names the same slot row ("canon", as in sk_union_mask_a); the fold adds the other rows' counts
+// there and gives every member, for each of its counter indices, the count of the key's slot row.  Integer adds: bit-exact in
+// any order, u32 wrap included.
+__global__ void sk_union_canon_rows(const sk_u4 *__restrict__ mslots, uint64_t nslots, uint32_t base,
+                                    const sk_u4 *__restrict__ slots, uint32_t mask, uint32_t *__restrict__ canon)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += stride) {
+        const sk_u4 e = mslots[i];
+        const uint64_t k = sk_slot_key(e);
+        if (k == SK_EMPTY64) continue;
+        uint32_t slot = sk_slot0(sk_khash(k), mask), w = 0xFFFFFFFFu;
+        for (;;) {
+            const sk_u4 u = slots[slot];
+            const uint64_t uk = sk_slot_key(u);
+            if (uk == k) { w = u.z; break; }
+            if (uk == SK_EMPTY64) break;                   // (cannot happen: every key was inserted)
+            slot = (slot + 1u) & mask;
+        }
+        const uint32_t g = base + e.z;
+        canon[g] = w == 0xFFFFFFFFu ? g : w;
+    }
+}
+
+// every row that is not its key's slot row adds its count there (slot rows are never read here after they were written:
+// canon[w] == w, so no row both gives and takes)
+__global__ void sk_union_fold_canon(uint32_t *ucol, const uint32_t *__restrict__ canon, uint32_t n)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const uint32_t w = canon[g];
+    if (w != g && w < n) {
+        const uint32_t v = ucol[g];
+        if (v) atomicAdd(&ucol[w], v);
+    }
+}
+
+// member column[i] +/-= the count of the slot row of global row base + i (i = the member's counter index)
+__global__ void sk_union_fold_member(uint32_t *__restrict__ dst, const uint32_t *__restrict__ ucol, const uint32_t *__restrict__ canon,
+                                     uint32_t base, uint32_t n, uint32_t subtract)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = ucol[canon[base + i]];
+    dst[i] = subtract ? dst[i] - v : dst[i] + v;
+}

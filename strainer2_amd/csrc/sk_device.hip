@@ -1021,6 +1021,10 @@ struct sk_union {
     uint64_t *d_ukeys;               // [rows] key of every global row
     uint2    *d_umask;               // [rows]
     sk_union_member *d_members;
+    // COUNT on the union (sk_union_count_enable): the members and their first global rows, and every row's key slot row
+    std::vector<sk_ctx *> mem;
+    std::vector<uint32_t> base;
+    uint32_t *d_canon;               // [rows] NULL until count columns were set up
 };
 
 extern "C" void sk_union_destroy(sk_union *u)
@@ -1030,7 +1034,7 @@ extern "C" void sk_union_destroy(sk_union *u)
         hipSetDevice(u->uc->device);
         hipStreamSynchronize(u->uc->stream);
         hipFree(u->d_ukeys); hipFree(u->d_umask); hipFree(u->d_members);
-        hipFree(u->d_tally); hipFree(u->d_flag); hipFree(u->d_raw); hipFree(u->d_cnt);
+        hipFree(u->d_tally); hipFree(u->d_flag); hipFree(u->d_raw); hipFree(u->d_cnt); hipFree(u->d_canon);
         sk_ctx_destroy(u->uc);
     }
     delete u;
@@ -1060,7 +1064,7 @@ extern "C" int sk_union_create(sk_ctx *const *members, uint32_t n, uint32_t type
     sk_union *u = new (std::nothrow) sk_union();
     if (!u) return SK_E_NOMEM;
     u->uc = NULL; u->n = n; u->d_ukeys = NULL; u->d_umask = NULL; u->d_members = NULL;
-    u->d_tally = u->d_flag = u->d_raw = NULL; u->tally_cap = u->flag_cap = u->raw_cap = 0; u->d_cnt = NULL;
+    u->d_tally = u->d_flag = u->d_raw = NULL; u->tally_cap = u->flag_cap = u->raw_cap = 0; u->d_cnt = NULL; u->d_canon = NULL;
     int rc = sk_ctx_create(&u->uc, first->device);
     if (rc != SK_OK) { delete u; return rc; }
     sk_ctx *c = u->uc;
@@ -1101,6 +1105,8 @@ extern "C" int sk_union_create(sk_ctx *const *members, uint32_t n, uint32_t type
         hipLaunchKernelGGL(sk_union_rank_copy, dim3((ndst + 255) / 256), dim3(256), 0, c->stream, c->d_rank + tbase / 64u, (const sk_u4 *)m->d_rank,
                            nsrc < ndst ? nsrc : ndst, ndst, base, base + m->nrows);
         hm[s].slots = m->d_keys; hm[s].mask = (uint32_t)(mslots - 1); hm[s].inv = m->d_inv;
+        u->mem.push_back(m);
+        u->base.push_back(base);
         base += m->nrows;
         tbase += span;
     }
@@ -1274,6 +1280,68 @@ extern "C" int sk_union_sync(sk_union *u)
     return SK_OK;
 }
 
+// ---- COUNT on a union (kmer_scrub_count -S): the union's context is scanned like one big strain into a count column of global rows;
+// sk_union_counts_fold then moves each key's count to its slot row and hands it to the members' own columns.
+extern "C" int sk_union_count_enable(sk_union *u, uint32_t ncols)
+{
+    if (!u || ncols < 1 || ncols > 16) return SK_E_ARG;
+    sk_ctx *c = u->uc;
+    if (c->d_counts) return ncols == c->ncols ? SK_OK : sk_fail(c, SK_E_STATE, "the union already has %u count column(s)", c->ncols);
+    SK_HIP(c, hipSetDevice(c->device));
+    const uint32_t nrows = c->nrows;
+    const uint64_t uslots = (uint64_t)1 << c->slots_log2;
+    SK_HIP(c, hipMalloc((void **)&u->d_canon, (size_t)nrows * 4));
+    for (uint32_t s = 0; s < u->n; s++) {                      // (sk_union_create's own canon[] went with its masks)
+        const sk_ctx *m = u->mem[s];
+        hipLaunchKernelGGL(sk_union_canon_rows, dim3(4096), dim3(256), 0, c->stream, (const sk_u4 *)m->d_keys, (uint64_t)1 << m->slots_log2,
+                           u->base[s], (const sk_u4 *)c->d_keys, (uint32_t)(uslots - 1), u->d_canon);
+    }
+    const size_t cbytes = (size_t)nrows * ncols * 4;
+    SK_HIP(c, hipMalloc((void **)&c->d_counts, cbytes));
+    SK_HIP(c, hipMemsetAsync(c->d_counts, 0, cbytes, c->stream));
+    SK_HIP(c, hipMalloc((void **)&c->d_diff, ((size_t)nrows + 2) * 4));
+    SK_HIP(c, hipMalloc((void **)&c->d_diff_sums, ((size_t)nrows / SK_DIFF_PER_BLOCK + 2) * 4));
+    SK_HIP(c, hipMemsetAsync(c->d_diff, 0, ((size_t)nrows + 2) * 4, c->stream));
+    c->diff_col = -1;
+    c->ncols = ncols;
+    SK_HIP(c, hipGetLastError());
+    SK_HIP(c, hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+extern "C" sk_ctx *sk_union_context(sk_union *u) { return u ? u->uc : NULL; }
+
+extern "C" int sk_union_counts_fold(sk_union *u, uint32_t ucol, uint32_t member_col, uint32_t member_mask, int subtract)
+{
+    if (!u) return SK_E_ARG;
+    sk_ctx *c = u->uc;
+    if (!c->d_counts || !u->d_canon) return sk_fail(c, SK_E_STATE, "the union has no count columns (sk_union_count_enable)");
+    if (ucol >= c->ncols) return sk_fail(c, SK_E_ARG, "union column %u out of range", ucol);
+    if (u->n < 32u && (member_mask >> u->n) != 0u) return sk_fail(c, SK_E_ARG, "member mask 0x%x names no member of %u", member_mask, u->n);
+    for (uint32_t s = 0; s < u->n; s++)
+        if (((member_mask >> s) & 1u) && (!u->mem[s]->d_counts || member_col >= u->mem[s]->ncols))
+            return sk_fail(c, SK_E_ARG, "member %u has no column %u", s, member_col);
+    SK_HIP(c, hipSetDevice(c->device));
+    { int rc = sk_diff_flush(c); if (rc) return rc; }
+    const uint32_t nrows = c->nrows;
+    uint32_t *const uc = c->d_counts + (size_t)ucol * nrows;
+    if (nrows) hipLaunchKernelGGL(sk_union_fold_canon, dim3((nrows + 255) / 256), dim3(256), 0, c->stream, uc, (const uint32_t *)u->d_canon, nrows);
+    for (uint32_t s = 0; s < u->n; s++) {
+        if (!((member_mask >> s) & 1u)) continue;
+        sk_ctx *m = u->mem[s];
+        { int rc = sk_diff_flush(m); if (rc) return rc; }
+        SK_HIP(c, hipStreamSynchronize(m->stream));            // (the member's own work on its column is done)
+        m->infbits_ok = false;
+        if (m->nrows)
+            hipLaunchKernelGGL(sk_union_fold_member, dim3((m->nrows + 255) / 256), dim3(256), 0, c->stream, m->d_counts + (size_t)member_col * m->nrows,
+                               (const uint32_t *)uc, (const uint32_t *)u->d_canon, u->base[s], m->nrows, (uint32_t)(subtract != 0));
+    }
+    SK_HIP(c, hipMemsetAsync(uc, 0, (size_t)nrows * 4, c->stream));
+    SK_HIP(c, hipGetLastError());
+    SK_HIP(c, hipStreamSynchronize(c->stream));               // (the members' streams may use their columns from here on)
+    return SK_OK;
+}
+
 extern "C" int sk_union_scan_timing(sk_union *u, double *total_ms, uint64_t *launches, int reset)
 {
     return u ? sk_scan_timing(u->uc, total_ms, launches, reset) : SK_E_ARG;
@@ -1286,6 +1354,7 @@ extern "C" int sk_scan_device(sk_ctx *c, const void *dev_stream, uint64_t nbytes
 {
     if (!c || (!dev_stream && nbytes)) return SK_E_ARG;
     if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
     if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
     if (((uintptr_t)dev_stream & 15u) != 0) return sk_fail(c, SK_E_ARG, "device stream must be 16-byte aligned");
     SK_HIP(c, hipSetDevice(c->device));
@@ -1298,6 +1367,7 @@ extern "C" int sk_scan_device_packed(sk_ctx *c, const void *dev_packed, uint64_t
 {
     if (!c || (!dev_packed && nbytes)) return SK_E_ARG;
     if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
     if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
     if (((uintptr_t)dev_packed & 3u) != 0) return sk_fail(c, SK_E_ARG, "device batch must be 4-byte aligned");
     SK_HIP(c, hipSetDevice(c->device));
@@ -1321,6 +1391,7 @@ extern "C" int sk_scan_stream(sk_ctx *c, const uint8_t *stream, uint64_t nbytes,
 {
     if (!c || (!stream && nbytes)) return SK_E_ARG;
     if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
     if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
     SK_HIP(c, hipSetDevice(c->device));
     int rc = sk_stage_init(c);
@@ -1395,6 +1466,7 @@ extern "C" int sk_scan_pinned(sk_ctx *c, const uint8_t *pinned, uint64_t nbytes,
 {
     if (!c || (!pinned && nbytes) || !ticket) return SK_E_ARG;
     if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
     if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
     if (nbytes > SK_STAGE_BYTES - 64) return sk_fail(c, SK_E_ARG, "pinned batch larger than the staging buffer");
     SK_HIP(c, hipSetDevice(c->device));
@@ -1430,6 +1502,7 @@ extern "C" int sk_scan_pinned_packed(sk_ctx *c, const void *packed, uint64_t nby
 {
     if (!c || (!packed && nbytes) || !ticket) return SK_E_ARG;
     if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
     if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
     const uint64_t nch = (nbytes + 15u) >> 4;
     if (nch * 6u > SK_STAGE_BYTES) return sk_fail(c, SK_E_ARG, "packed batch larger than the staging buffer");

@@ -1,0 +1,377 @@
+/* sk_host_scrub_multi.c -- kmer_scrub_count -S: step 1 of the workflow for many strains over ONE pass of the -A/-B/-C lists.
+ *
+ * The reference counts one strain per process (src/kmer_scrub_count.c:29-131); a drug with 8-32 strains re-reads, re-decodes
+ * and re-uploads the same lists once per strain.  Here up to SK_UNION_MAX strains are resident at once and share one union table
+ * (sk_union_*): each list is scanned once into the union's count column, and sk_union_counts_fold hands the counts to every
+ * member's own column.  The -C rule (a line equal to the run's -r is not counted: src/genome_compare.c:115-146) is per strain:
+ * the whole -C list goes to every member, then each line equal to a member's genome is scanned alone and taken back from the
+ * members it names (u32 wrap makes -= after += exact).  A strain the union cannot hold (byte-string keys, no text stage) gets a
+ * pass of its own through its own context, as the single-strain program would run it.
+ *
+ * Kept in a translation unit of its own: the host tests link sk_host.c, sk_host_sd.c and sk_host_cov.c against a device
+ * double that has none of the union's COUNT entry points. */
+#define _GNU_SOURCE
+#include <pthread.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+#include <unistd.h>
+#include "../../include/strainer_kmer.h"
+#include "sk_cpus.h"
+#include "sk_gzout.h"
+
+typedef struct {
+    char      *genome, *outfile;
+    FILE      *fp;                 /* the outfile (plain) ...                                    */
+    skzo_file *zo;                 /* ... or its gzip writer (a name ending in .gz)              */
+    skh_keyset ks;
+    sk_ctx    *ctx;
+    int        rc_keys, rc_ctx, rc_load;
+    int        print_rc;
+} sm_strain;
+
+typedef struct {
+    sm_strain *st;
+    uint32_t   n;
+    int        device, with_drug;
+    uint32_t   next;               /* pool: the next strain to take */
+    pthread_mutex_t mu;
+} sm_job;
+
+static double sm_now(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+
+static int sm_env_int(const char *a, const char *b, const char *c3, int dflt)
+{
+    const char *v = getenv(a);
+    if (!v && b) v = getenv(b);
+    if (!v && c3) v = getenv(c3);
+    return v ? atoi(v) : dflt;
+}
+
+static int sm_threads(void)
+{
+    const char *e = getenv("SK_THREADS");
+    long n = e ? atol(e) : sk_cpu_budget();
+    return n < 1 ? 1 : n > 16 ? 16 : (int)n;
+}
+
+/* run fn on every strain, `nth` threads taking the next one */
+static void sm_pool_run(sm_job *j, int nth, void *(*worker)(void *))
+{
+    pthread_t th[16];
+    int k, started = 0;
+    j->next = 0;
+    pthread_mutex_init(&j->mu, NULL);
+    if (nth > (int)j->n) nth = (int)j->n;
+    for (k = 0; k < nth; k++) if (pthread_create(&th[started], NULL, worker, j) == 0) started++;
+    if (!started) worker(j);
+    for (k = 0; k < started; k++) pthread_join(th[k], NULL);
+    pthread_mutex_destroy(&j->mu);
+}
+
+static sm_strain *sm_take(sm_job *j)
+{
+    sm_strain *s = NULL;
+    pthread_mutex_lock(&j->mu);
+    if (j->next < j->n) s = &j->st[j->next++];
+    pthread_mutex_unlock(&j->mu);
+    return s;
+}
+
+/* a strain opened start to finish on one worker: host key set in the reference's row order, context, table load */
+static void *sm_open_worker(void *arg)
+{
+    sm_job *j = (sm_job *)arg;
+    sm_strain *s;
+    while ((s = sm_take(j)) != NULL) {
+        s->rc_keys = skh_keyset_from_file(&s->ks, s->genome, SK_REF_TABLE_SLOTS, 1, 1);
+        if (s->rc_keys != SK_OK) continue;
+        s->rc_ctx = sk_ctx_create(&s->ctx, j->device);
+        if (s->rc_ctx != SK_OK) { s->ctx = NULL; continue; }
+        s->rc_load = skh_keyset_load(s->ctx, &s->ks, 4);
+    }
+    return NULL;
+}
+
+static ssize_t sm_gz_write(void *cookie, const char *buf, size_t n)
+{
+    skzo_append((skzo_file *)cookie, buf, n);
+    return (ssize_t)n;
+}
+
+static void *sm_print_worker(void *arg)
+{
+    sm_job *j = (sm_job *)arg;
+    sm_strain *s;
+    while ((s = sm_take(j)) != NULL) {
+        FILE *f = s->fp;
+        if (s->zo) {
+            cookie_io_functions_t io = {NULL, sm_gz_write, NULL, NULL};
+            f = fopencookie(s->zo, "w", io);
+            if (!f) { s->print_rc = SK_E_NOMEM; continue; }
+        }
+        setvbuf(f, NULL, _IOFBF, 1 << 20);
+        s->print_rc = skh_print_counts(s->ctx, &s->ks, f, j->with_drug);
+        if (s->zo) { if (fclose(f) != 0 && s->print_rc == SK_OK) s->print_rc = SK_E_OPEN; }
+        else if (fflush(f) != 0 && s->print_rc == SK_OK) s->print_rc = SK_E_OPEN;
+    }
+    return NULL;
+}
+
+/* one strain, its own pass: what the single-strain program does (src/kmer_scrub_count.c:87-99) */
+static int sm_single_pass(sm_strain *s, const char *A, const char *B, const char *C, FILE *progress, FILE *err)
+{
+    if (skh_scan_list(s->ctx, A, NULL, 1, progress, err, 0, 1, NULL) != SK_OK) return 1;
+    if (skh_scan_list(s->ctx, B, NULL, 2, progress, err, 0, 1, NULL) != SK_OK) return 1;
+    if (C && skh_scan_list(s->ctx, C, s->genome, 3, progress, err, 0, 1, NULL) != SK_OK) return 1;
+    return 0;
+}
+
+#define SM_FALLBACK 2
+
+static int sm_fold(sk_union *u, uint32_t col, uint32_t mask, int subtract, FILE *err)
+{
+    const int rc = sk_union_counts_fold(u, 0, col, mask, subtract);
+    if (rc != SK_OK) fprintf(err, "kmer_scrub_count: union fold failed: %s (%s)\n", sk_strerror(rc), sk_union_last_error(u));
+    return rc;
+}
+
+/* up to SK_UNION_MAX strains, one pass over the lists through their union table.  SM_FALLBACK: the union could not be made
+ * (SK_E_STATE: a member it cannot hold) -- nothing was scanned, the caller runs the strains one by one */
+static int sm_union_pass(sm_strain **g, uint32_t n, const char *A, const char *B, const char *C, FILE *progress, FILE *err,
+                         double *fold_ms)
+{
+    sk_ctx *m[SK_UNION_MAX];
+    sk_union *u = NULL;
+    sk_ctx *uc;
+    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u;
+    uint32_t k;
+    int rc, status = 1;
+    double t;
+    for (k = 0; k < n; k++) m[k] = g[k]->ctx;
+    rc = sk_union_create(m, n, 0, 0, &u);
+    if (rc == SK_E_STATE) return SM_FALLBACK;
+    if (rc != SK_OK) { fprintf(err, "kmer_scrub_count: union table failed: %s (%s)\n", sk_strerror(rc), sk_last_error(m[0])); return 1; }
+    if ((rc = sk_union_count_enable(u, 1)) != SK_OK) {
+        fprintf(err, "kmer_scrub_count: union count column failed: %s (%s)\n", sk_strerror(rc), sk_union_last_error(u));
+        goto out;
+    }
+    uc = sk_union_context(u);
+    if (skh_scan_list(uc, A, NULL, 0, progress, err, 0, 1, NULL) != SK_OK) goto out;
+    t = sm_now();
+    if (sm_fold(u, 1, all, 0, err) != SK_OK) goto out;
+    *fold_ms += 1e3 * (sm_now() - t);
+    if (skh_scan_list(uc, B, NULL, 0, progress, err, 0, 1, NULL) != SK_OK) goto out;
+    t = sm_now();
+    if (sm_fold(u, 2, all, 0, err) != SK_OK) goto out;
+    *fold_ms += 1e3 * (sm_now() - t);
+    if (C) {
+        FILE *fp;
+        char *line = NULL, *nl;
+        size_t cap = 0;
+        if (skh_scan_list(uc, C, NULL, 0, progress, err, 0, 1, NULL) != SK_OK) goto out;
+        if (sm_fold(u, 3, all, 0, err) != SK_OK) goto out;
+        /* the -C lines a member would have skipped: scanned alone and taken back from that member (a line may come several times) */
+        if (!(fp = fopen(C, "r"))) { fprintf(err, "could not read file %s in GEN_all_kmer_counts()\n", C); goto out; }
+        rc = SK_OK;
+        while (rc == SK_OK && getline(&line, &cap, fp) != -1) {
+            uint32_t mask = 0;
+            if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
+            for (k = 0; k < n; k++) if (strcmp(g[k]->genome, line) == 0) mask |= 1u << k;
+            if (!mask) continue;
+            rc = skh_scan_file(uc, line, 0, NULL);
+            if (rc == SK_E_OPEN) fprintf(err, "could not read file %s in GEN_calculate_kmer_count()\n", line);
+            else if (rc != SK_OK) fprintf(err, "kmer_scrub_count: device error while scanning %s: %s (%s)\n", line, sk_strerror(rc), sk_last_error(uc));
+            if (rc == SK_OK) rc = sm_fold(u, 3, mask, 1, err);
+            for (k = 0; rc == SK_OK && k < n; k++) if ((mask >> k) & 1u) fprintf(err, "skipping %s (identical match)\n", line);
+        }
+        free(line);
+        fclose(fp);
+        if (rc != SK_OK) goto out;
+    }
+    status = 0;
+out:
+    sk_union_destroy(u);
+    return status;
+}
+
+static int sm_is_gz(const char *p)
+{
+    const size_t l = strlen(p);
+    return l >= 3 && strcmp(p + l - 3, ".gz") == 0;
+}
+
+int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
+{
+    const char *A = NULL, *B = NULL, *C = NULL, *P = NULL, *S = NULL, *env;
+    const int world = sm_env_int("SK_WORLD_SIZE", "WORLD_SIZE", "OMPI_COMM_WORLD_SIZE", 1);
+    const int rank = sm_env_int("SK_RANK", "RANK", "OMPI_COMM_WORLD_RANK", 0);
+    int device = sm_env_int("SK_LOCAL_RANK", "LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", 0);
+    uint32_t group = SK_UNION_MAX, ns = 0, k, nunion = 0, nsingle = 0;
+    sm_strain *st = NULL;
+    FILE *progress = NULL;
+    skzo_pool zpool;
+    int zpool_on = 0, status = 1, c, any_gz = 0, created = 0;
+    double t0 = sm_now(), t1 = 0, t2 = 0, t3 = 0, fold_ms = 0;
+    (void)out;
+
+    for (c = 1; c < argc; c++)
+        if (!strncmp(argv[c], "--scrub", 7) || !strcmp(argv[c], "--detect") || !strcmp(argv[c], "--independent")) {
+            fprintf(err, "kmer_scrub_count: -S does not go with --scrub/--detect (run the strains one by one for those)\n");
+            return 1;
+        }
+    optind = 1;
+    while ((c = getopt(argc, argv, "A:B:C:S:p:Hhud")) != -1) {
+        switch (c) {
+        case 'A': A = optarg; break;
+        case 'B': B = optarg; break;
+        case 'C': C = optarg; break;
+        case 'S': S = optarg; break;
+        case 'p': P = optarg; break;
+        case 'd': break;
+        default:
+            fputs("Usage: kmer_scrub_count -S <strains file: genome TAB outfile per line> -A <file with multiple genome filenames> "
+                  "-B <file with multiple metagenome filenames> -C <(optional) file with multiple genome filenames of drug strains> "
+                  "-p [progress output file, optional]\n", err);
+            break;
+        }
+    }
+    if (!S || !A || !B) {
+        fputs("Usage: kmer_scrub_count -S <strains file: genome TAB outfile per line> -A <file with multiple genome filenames> "
+              "-B <file with multiple metagenome filenames> -C <(optional) file with multiple genome filenames of drug strains> "
+              "-p [progress output file, optional]\n", err);
+        return 1;
+    }
+    if (world < 1 || rank < 0 || rank >= world) { fprintf(err, "kmer_scrub_count: bad rank %d of %d\n", rank, world); return 1; }
+    if ((env = getenv("SK_DEVICE")) != NULL) device = atoi(env);
+    if ((env = getenv("SK_SCRUB_GROUP")) != NULL && atoi(env) >= 1 && atoi(env) <= SK_UNION_MAX) group = (uint32_t)atoi(env);
+
+    {   /* the strains file: <genome> TAB <outfile>; this rank's lines (round-robin over the strain lines) */
+        FILE *fp = fopen(S, "r");
+        char *line = NULL, *nl;
+        size_t cap = 0;
+        unsigned lineno = 0;
+        if (!fp) { fprintf(err, "kmer_scrub_count: could not read the strain list %s\n", S); return 1; }
+        while (getline(&line, &cap, fp) != -1) {
+            char *fr, *fo, *rest;
+            if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
+            if (line[0] == '#' || line[0] == '\0') continue;
+            fr = strtok(line, "\t"); fo = strtok(NULL, "\t"); rest = strtok(NULL, "\t");
+            if (!fr || !fo || rest) {
+                fprintf(err, "kmer_scrub_count: %s: a line needs <reference genome> TAB <outfile>\n", S);
+                free(line); fclose(fp);
+                goto done;
+            }
+            if (world > 1 && (int)(lineno++ % (unsigned)world) != rank) continue;     /* strains are dealt to the ranks; no collective */
+            st = (sm_strain *)realloc(st, ((size_t)ns + 1) * sizeof *st);
+            memset(&st[ns], 0, sizeof st[ns]);
+            st[ns].genome = strdup(fr);
+            st[ns].outfile = strdup(fo);
+            ns++;
+        }
+        free(line);
+        fclose(fp);
+    }
+    /* every outfile is created before anything is scanned: a run that cannot write its results does not start */
+    for (k = 0; k < ns; k++) any_gz |= sm_is_gz(st[k].outfile);
+    if (any_gz) { skzo_pool_start(&zpool, sm_threads()); zpool_on = 1; }
+    for (k = 0; k < ns; k++) {
+        if (sm_is_gz(st[k].outfile)) st[k].zo = skzo_open(&zpool, st[k].outfile);
+        else st[k].fp = fopen(st[k].outfile, "w");
+        if (!st[k].zo && !st[k].fp) { fprintf(err, "kmer_scrub_count: cannot write %s\n", st[k].outfile); goto done; }
+        created = (int)k + 1;
+    }
+    if (P && rank == 0) {
+        progress = fopen(P, "w");
+        if (!progress) { fprintf(err, "could not open progress file %s\n", P); goto done; }
+        fputs("adding kmer counts for:\n", progress);
+    }
+
+    {   /* the strains are opened on worker threads; what went wrong is said here, in list order, up to the first failure */
+        sm_job j;
+        memset(&j, 0, sizeof j);
+        j.st = st; j.n = ns; j.device = device;
+        sm_pool_run(&j, sm_threads(), sm_open_worker);
+        for (k = 0; k < ns; k++) {
+            sm_strain *s = &st[k];
+            if (s->rc_keys == SK_E_OPEN) { fprintf(err, "could not read file %s GEN_hash_sequences_set_count_vec()\n", s->genome); goto done; }
+            if (s->rc_keys != SK_OK) { fprintf(err, "kmer_scrub_count: %s\n", sk_strerror(s->rc_keys)); goto done; }
+            if (s->ks.short_records && rank == 0)
+                fprintf(err, "kmer_scrub_count: skipped %llu reference record(s) shorter than %d bases "
+                             "(the original program crashes on these)\n", (unsigned long long)s->ks.short_records, SK_K - 1);
+            if (s->rc_ctx != SK_OK) { fprintf(err, "kmer_scrub_count: cannot use HIP device %d: %s\n", device, sk_strerror(s->rc_ctx)); goto done; }
+            if (s->rc_load != SK_OK) { fprintf(err, "kmer_scrub_count: table load failed: %s (%s)\n", sk_strerror(s->rc_load), sk_last_error(s->ctx)); goto done; }
+        }
+    }
+    t1 = sm_now();
+
+    {   /* the passes: unions of up to `group` strains, then every strain a union cannot hold on its own.  Only the first pass
+         * writes the progress file (every pass walks the same lists). */
+        sm_strain **uni = (sm_strain **)malloc(((size_t)ns + 1) * sizeof *uni), **solo = (sm_strain **)malloc(((size_t)ns + 1) * sizeof *solo);
+        uint32_t nu = 0, nsolo = 0, a;
+        const int no_union = getenv("SK_SCRUB_NO_UNION") != NULL && getenv("SK_SCRUB_NO_UNION")[0] == '1';
+        int rc = 0;
+        for (k = 0; k < ns; k++) {
+            const skh_keyset *ks = &st[k].ks;
+            /* what sk_union_create takes: packed keys only, the text stage, fewer rows than the hit log can name */
+            const int fits = !no_union && ks->nrows && !ks->nwide && ks->text2 && ks->text_bases && !getenv("SK_NO_TEXT") &&
+                             ks->nrows < (1u << SK_UNION_ROW_BITS) - 1u;
+            if (fits) uni[nu++] = &st[k]; else solo[nsolo++] = &st[k];
+        }
+        for (a = 0; rc == 0 && a < nu; a += group) {
+            const uint32_t n = nu - a < group ? nu - a : group;
+            rc = sm_union_pass(uni + a, n, A, B, C, progress, err, &fold_ms);
+            if (rc == SM_FALLBACK) {                           /* (nothing was scanned) */
+                for (k = 0; k < n; k++) solo[nsolo++] = uni[a + k];
+                rc = 0;
+                continue;
+            }
+            nunion++;
+            if (progress) { fclose(progress); progress = NULL; }
+        }
+        for (k = 0; rc == 0 && k < nsolo; k++) {
+            rc = sm_single_pass(solo[k], A, B, C, progress, err);
+            nsingle++;
+            if (progress) { fclose(progress); progress = NULL; }
+        }
+        free(uni);
+        free(solo);
+        if (rc != 0) goto done;
+    }
+    t2 = sm_now();
+
+    {   /* the tables, printed on worker threads (a 5 Mbp strain's table is ~250 MB of text) */
+        sm_job j;
+        memset(&j, 0, sizeof j);
+        j.st = st; j.n = ns; j.with_drug = C != NULL;
+        sm_pool_run(&j, sm_threads(), sm_print_worker);
+        for (k = 0; k < ns; k++) {
+            int wrc = st[k].print_rc;
+            if (st[k].zo) { if (skzo_close(st[k].zo) && wrc == SK_OK) wrc = SK_E_OPEN; st[k].zo = NULL; }
+            if (st[k].fp) { if (fclose(st[k].fp) != 0 && wrc == SK_OK) wrc = SK_E_OPEN; st[k].fp = NULL; }
+            if (wrc == SK_E_OPEN) { fprintf(err, "kmer_scrub_count: error writing %s\n", st[k].outfile); goto done; }
+            if (wrc != SK_OK) { fprintf(err, "kmer_scrub_count: %s (%s)\n", sk_strerror(wrc), sk_last_error(st[k].ctx)); goto done; }
+        }
+    }
+    t3 = sm_now();
+    status = 0;
+done:
+    if (getenv("SK_TIMING") && t3 > 0)
+        fprintf(err, "kmer_scrub_count -S timing: %u strain(s) opened in %.2f s, %u union pass(es) + %u single pass(es) %.2f s "
+                     "(folds %.1f ms), print %.2f s\n", ns, t1 - t0, nunion, nsingle, t2 - t1, fold_ms, t3 - t2);
+    for (k = 0; k < ns; k++) {
+        if (st[k].zo) skzo_close(st[k].zo);
+        if (st[k].fp) fclose(st[k].fp);
+        if (status != 0 && (int)k < created) unlink(st[k].outfile);     /* no outfile of a failed run looks complete */
+        if (st[k].ctx) sk_ctx_destroy(st[k].ctx);
+        skh_keyset_free(&st[k].ks);
+        free(st[k].genome);
+        free(st[k].outfile);
+    }
+    free(st);
+    if (progress) fclose(progress);
+    if (zpool_on) skzo_pool_stop(&zpool);
+    return status;
+}

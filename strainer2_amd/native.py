@@ -55,7 +55,8 @@ ABI_SYMBOLS = [
     "sk_distinct_count", "sk_first_seen_count", "skh_coverage_depth_main",
     "sk_batch_create", "sk_batch_destroy", "sk_batch_sync", "sk_batch_fill", "sk_batch_fill_packed", "sk_tally_launch", "sk_tally_collect", "sk_tally_collect_sparse",
     "sk_union_create", "sk_union_destroy", "sk_union_tally_launch", "sk_union_tally_collect", "sk_union_last_error", "sk_union_scan_timing", "sk_union_sync",
-    "sk_union_members", "sk_union_rows",
+    "sk_union_members", "sk_union_rows", "sk_union_count_enable", "sk_union_context", "sk_union_counts_fold",
+    "skh_kmer_scrub_count_multi_main",
 ]
 
 
@@ -164,6 +165,10 @@ lib.sk_union_tally_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
 lib.sk_union_tally_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
 lib.sk_union_last_error.argtypes = [C.c_void_p]
 lib.sk_union_last_error.restype = C.c_char_p
+lib.sk_union_count_enable.argtypes = [C.c_void_p, C.c_uint32]
+lib.sk_union_context.argtypes = [C.c_void_p]
+lib.sk_union_context.restype = C.c_void_p
+lib.sk_union_counts_fold.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
 lib.sk_union_members.argtypes = [C.c_void_p]
 lib.sk_union_members.restype = C.c_uint32
 lib.sk_union_rows.argtypes = [C.c_void_p]
@@ -489,6 +494,37 @@ class KmerUnion:
         out = np.stack([hits[:, 1] >> 27, hits[:, 0], hits[:, 1] & ((1 << 27) - 1)], axis=1) if len(hits) else np.zeros((0, 3), dtype=np.uint32)
         order = np.lexsort((out[:, 2], out[:, 1], out[:, 0]))
         return tally.reshape(nrec, n, 2), out[order]
+
+    # ---- COUNT on the union (sk_union_count_enable / sk_union_context / sk_union_counts_fold)
+    def _uck(self, rc):
+        if rc:
+            raise SKError(rc, lib.sk_union_last_error(self._h).decode())
+
+    def count_enable(self, ncols=1):
+        """give the union's context ncols zeroed count columns of global rows (needed before scan_stream / fold_counts)"""
+        self._uck(lib.sk_union_count_enable(self._h, ncols))
+
+    def scan_stream(self, stream, col=0):
+        """count a host record stream into union column `col` (sk_scan_stream on the union's context)"""
+        ctx = lib.sk_union_context(self._h)
+        if isinstance(stream, np.ndarray):
+            stream = np.ascontiguousarray(stream, dtype=np.uint8)
+            self._uck(lib.sk_scan_stream(ctx, stream.ctypes.data, stream.size, col))
+        else:
+            self._uck(lib.sk_scan_stream(ctx, stream, len(stream), col))
+
+    def fold_counts(self, ucol, member_col, member_mask=None, subtract=False):
+        """fold union column `ucol` into column `member_col` of the members in member_mask (default: all), then zero it"""
+        if member_mask is None:
+            member_mask = (1 << len(self._members)) - 1
+        self._uck(lib.sk_union_counts_fold(self._h, ucol, member_col, member_mask & 0xFFFFFFFF, int(bool(subtract))))
+
+    def scan_timing(self, reset=False):
+        """(milliseconds, launches) of the union's scan kernels since the last reset, from HIP events"""
+        ms = C.c_double(0)
+        n = C.c_uint64(0)
+        self._uck(lib.sk_union_scan_timing(self._h, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
 
     def close(self):
         if getattr(self, "_batch", None):
