@@ -98,6 +98,7 @@ lib.sk_tally_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C
 lib.sk_sync.argtypes = [C.c_void_p]
 lib.sk_counts_fetch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_counts_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+lib.sk_counts_set_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
 lib.sk_counts_zero.argtypes = [C.c_void_p, C.c_uint32]
 lib.sk_counts_device_ptr.argtypes = [C.c_void_p]
 lib.sk_counts_device_ptr.restype = C.c_void_p
@@ -294,6 +295,31 @@ class KmerContext:
         hits = hits[: nh.value]
         return tally, hits[np.argsort(hits[:, 0], kind="stable")]
 
+    def tally_launch(self, batch, type_col=0, informative_value=2, hits_cap=None):
+        """sk_tally_launch on a filled TallyBatch (returns at once; hits_cap default: one entry per byte of the batch)"""
+        cap = max(batch.nbytes, 16) if hits_cap is None else hits_cap
+        self._ck(lib.sk_tally_launch(self._h, batch._h, type_col, informative_value, cap))
+        self._inflight = (batch.nrec, cap)
+
+    def tally_collect(self):
+        """sk_tally_collect of the launch in flight: (tally[nrec, 2], hits[min(n, cap), 2] as stored, n = the true count)"""
+        nrec, cap = self._inflight
+        tally = np.zeros((nrec, 2), dtype=np.uint32)
+        hits = np.zeros((max(cap, 1), 2), dtype=np.uint32)
+        nh = C.c_uint64(0)
+        self._ck(lib.sk_tally_collect(self._h, tally.ctypes.data, hits.ctypes.data, C.byref(nh)))
+        return tally, hits[: min(nh.value, cap)], nh.value
+
+    def tally_collect_sparse(self):
+        """sk_tally_collect_sparse of the launch in flight: (recs[m, 3] = (record, all, informative) as stored, hits, n)"""
+        nrec, cap = self._inflight
+        recs = np.zeros((max(nrec, 1), 3), dtype=np.uint32)
+        hits = np.zeros((max(cap, 1), 2), dtype=np.uint32)
+        nr, nh = C.c_uint64(0), C.c_uint64(0)
+        self._ck(lib.sk_tally_collect_sparse(self._h, recs.ctypes.data, nrec, C.byref(nr), hits.ctypes.data, C.byref(nh)))
+        assert nr.value <= nrec
+        return recs[: nr.value], hits[: min(nh.value, cap)], nh.value
+
     def pinned_alloc(self, nbytes):
         """A pinned host buffer as a writable numpy uint8 array (free with pinned_free(arr))."""
         p = C.c_void_p()
@@ -377,6 +403,11 @@ class KmerContext:
         assert values.size == self.nrows
         self._ck(lib.sk_counts_set(self._h, col, values.ctypes.data))
 
+    def set_counts_rows(self, col, rows, value):
+        """counts[col][rows[i]] = value (sk_counts_set_rows)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        self._ck(lib.sk_counts_set_rows(self._h, col, rows.ctypes.data, rows.size, value))
+
     def zero_counts(self, col):
         self._ck(lib.sk_counts_zero(self._h, col))
 
@@ -446,6 +477,44 @@ class KmerContext:
         self.close()
 
 
+class TallyBatch:
+    """A batch of records resident on a context's device (sk_batch_*), to be tallied against one or more tables."""
+
+    def __init__(self, ctx: KmerContext):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        ctx._ck(lib.sk_batch_create(ctx._h, C.byref(self._h)))
+        self.nbytes = self.nrec = 0
+
+    def fill(self, stream: bytes, rec_start, packed=False):
+        """upload a record stream (packed: in sk_pack_stream's form, which must hold no odd byte); rec_start as in tally_batch"""
+        rec_start = np.ascontiguousarray(rec_start, dtype=np.uint32)
+        if packed:
+            buf, odd = pack_stream(stream)
+            assert not odd, "a packed batch holds only A/C/G/T, N and newlines"
+            rc = lib.sk_batch_fill_packed(self._h, buf.ctypes.data, len(stream), rec_start.ctypes.data, len(rec_start))
+        else:
+            buf = np.frombuffer(stream, dtype=np.uint8) if isinstance(stream, (bytes, bytearray)) else np.ascontiguousarray(stream, dtype=np.uint8)
+            rc = lib.sk_batch_fill(self._h, buf.ctypes.data, buf.size, rec_start.ctypes.data, len(rec_start))
+        self._ctx._ck(rc)
+        self._ctx._ck(lib.sk_batch_sync(self._h))        # (the upload is done: buf may go)
+        self.nbytes, self.nrec = len(stream), len(rec_start)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.sk_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class KmerUnion:
     """One table for several resident strains (sk_union_*): a batch is tallied against all of them in one launch."""
 
@@ -466,11 +535,21 @@ class KmerUnion:
     def rows(self):
         return lib.sk_union_rows(self._h)
 
-    def tally_batch(self, stream: bytes, rec_start, hits_cap=None):
-        """returns (tally[nrec, members, 2], hits[n, 3] = (member, window-end offset, the member's row) sorted)"""
+    def set_option(self, name, value):
+        """sk_set_option on the union's own context (e.g. "odd_list_cap" for its scans)"""
+        self._uck(lib.sk_set_option(lib.sk_union_context(self._h), name.encode(), value))
+
+    def tally_batch(self, stream: bytes, rec_start, hits_cap=None, packed=False):
+        """returns (tally[nrec, members, 2], hits[n, 3] = (member, window-end offset, the member's row) sorted);
+        packed: the batch goes up in sk_pack_stream's form (it must hold no odd byte)"""
         rec_start = np.ascontiguousarray(rec_start, dtype=np.uint32)
         nrec, n = len(rec_start), len(self._members)
-        rc = lib.sk_batch_fill(self._batch, stream, len(stream), rec_start.ctypes.data, nrec)
+        if packed:
+            pk, odd = pack_stream(stream)
+            assert not odd, "a packed batch holds only A/C/G/T, N and newlines"
+            rc = lib.sk_batch_fill_packed(self._batch, pk.ctypes.data, len(stream), rec_start.ctypes.data, nrec)
+        else:
+            rc = lib.sk_batch_fill(self._batch, stream, len(stream), rec_start.ctypes.data, nrec)
         if rc:
             raise SKError(rc, lib.sk_last_error(self._members[0]._h).decode())
         cap = hits_cap if hits_cap is not None else max(len(stream) * 2, 16)

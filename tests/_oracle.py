@@ -80,6 +80,14 @@ class OracleTable:
         klist = [raw[i * (K + 1): i * (K + 1) + K].split(b"\0")[0] for i in range(n)]
         return klist, counts[:n]
 
+    def counts(self):
+        """the counter matrix [rows, ncols] alone, in row order (rows() without decoding the keys)"""
+        n = self.size
+        keys = C.create_string_buffer(max(n, 1) * (K + 1))
+        counts = np.zeros((max(n, 1), self.ncols), dtype=np.uint32)
+        L.kso_table_rows(self.h, K, keys, counts.ctypes.data)
+        return counts[:n]
+
     def close(self):
         if self.h:
             L.kso_table_free(self.h)

@@ -141,3 +141,94 @@ def two_expansions_strain(golden, tmp_path):
     if hashlib.md5(open(path, "rb").read()).hexdigest() != facts["strain"]["md5"]:
         return None, facts
     return path, facts
+
+
+# ---- TALLY worlds (tests/test_tally_forms_gpu.py, tests/test_tally_ref.py) ------------------------------------------
+def mutate(rng: random.Random, seq: bytes, rate: float) -> bytes:
+    b = bytearray(seq)
+    for i in range(len(b)):
+        if rng.random() < rate:
+            b[i] = rng.choice(b"ACGT")
+    return bytes(b)
+
+
+def u_window(rng: random.Random, strain: bytes):
+    """(a 31-byte window holding U or u that hits `strain` for certain, the strain k-mer it hits), or None.  A strain
+    k-mer w that is its own canonical form (w > revcomp(w)) is reverse-complemented and a T behind the first base where
+    the two differ becomes U: the window's reverse complement is then w again and the larger of the two, so the key
+    looked up is pure A/C/G/T -- the byte-string kernel's one way to a table hit on such a window"""
+    for _ in range(200):
+        a = rng.randrange(len(strain) - 30)
+        w = strain[a:a + 31].upper()
+        if set(w) - set(b"ACGT"):
+            continue
+        r = revcomp(w)
+        if w <= r:
+            continue
+        d = next(i for i in range(31) if w[i] != r[i])
+        ts = [i for i in range(d + 1, 31) if r[i] == ord("T")]
+        if ts:
+            i = rng.choice(ts)
+            return r[:i] + rng.choice([b"U", b"u"]) + r[i + 1:], w
+    return None
+
+
+def tally_strains(rng: random.Random, kind: int, n: int, sizes=(400, 3000, 12000)) -> list:
+    """n strains that share keys: the same strain again, diverged copies, unrelated ones, the other strand of a part,
+    a repeated segment (with an N)"""
+    base = rand_dna(rng, rng.choice(sizes))
+    out = []
+    for s in range(n):
+        pick = (s + kind) % 5
+        if pick == 0:
+            g = base
+        elif pick == 1:
+            g = mutate(rng, base, rng.choice([0.002, 0.01, 0.05]))
+        elif pick == 2:
+            g = rand_dna(rng, rng.choice([200, 5000, 9000]))
+        elif pick == 3:
+            g = revcomp(base[len(base) // 3:]) + rand_dna(rng, 500)
+        else:
+            cut = len(base) // 2
+            g = base[:cut] + base[cut // 2:cut] + base[cut:]
+            g = g[:50] + b"N" + g[51:]
+        out.append(g)
+    return out
+
+
+def tally_reads(rng: random.Random, strains: list, nreads: int, junk: bool) -> tuple:
+    """(records, the strain k-mers that U windows were made from).  Pieces of the strains (either strand, some
+    mutated), random reads, reads shorter than k and empty ones, lower case; junk: also U windows that hit for
+    certain (u_window), and IUPAC letters, U and '\\r' sprinkled in.  Without junk the bytes are A/C/G/T, N and lower case."""
+    recs, uk = [], []
+    for _ in range(nreads):
+        x = rng.random()
+        if x < 0.04:
+            recs.append(b"")
+            continue
+        if x < 0.1:
+            recs.append(rand_dna(rng, rng.randrange(1, 31)))
+            continue
+        ln = rng.choice([31, 32, 47, 64, 100, 150, 151, 250, 700])
+        g = strains[rng.randrange(len(strains))]
+        if rng.random() < 0.75 and len(g) > ln:
+            a = rng.randrange(len(g) - ln)
+            seq = mutate(rng, g[a:a + ln], rng.choice([0.0, 0.0, 0.01, 0.05]))
+            if rng.random() < 0.5:
+                seq = revcomp(seq)
+        else:
+            seq = rand_dna(rng, ln)
+        if junk and rng.random() < 0.15:
+            u = u_window(rng, g)
+            if u:
+                cut = rng.randrange(len(seq) + 1)
+                seq = seq[:cut] + u[0] + seq[cut:]
+                uk.append(u[1])
+        b = bytearray(seq)
+        if rng.random() < 0.1:
+            for _ in range(rng.randrange(1, 3)):
+                b[rng.randrange(len(b))] = rng.choice(b"RYKMSWBDHVUu\r" if junk else b"Nn")
+        if rng.random() < 0.05:
+            b = b.lower()
+        recs.append(bytes(b))
+    return recs, uk

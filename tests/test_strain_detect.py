@@ -224,11 +224,13 @@ def _canon(k):
     return k if k >= r else r
 
 
-def _make_multi_inputs(tmp_path, nstrains=3, strain_len=60_000, nreads=320_000, related=False):
+def _make_multi_inputs(tmp_path, nstrains=3, strain_len=60_000, nreads=320_000, related=False, u_windows=False, mates=(60_000, 50_001)):
     """nstrains synthetic strains with their informative lists, and a -B list with an SE (.gz), a PE pair and
     an interleaved file whose decoded size spans more than one 32 MiB chunk; short reads mixed in.  related: the
     strains are diverged copies of three ancestors (0.5-3 % substitutions, every seventh an exact copy): most k-mers
-    are shared by several strains, and a k-mer informative in one strain is plain in another."""
+    are shared by several strains, and a k-mer informative in one strain is plain in another.  u_windows: one read in
+    fifty of the interleaved file holds a window with U that hits an informative k-mer (_synth.u_window), the other
+    files none.  mates: the reads of each PE file and of the interleaved one."""
     rng = random.Random(4242)
     if related:
         anc = [_synth.rand_dna(rng, strain_len) for _ in range(3)]
@@ -265,17 +267,26 @@ def _make_multi_inputs(tmp_path, nstrains=3, strain_len=60_000, nreads=320_000, 
                 rd = _synth.rand_dna(r, 150)
             if r.random() < 0.01:
                 rd = rd[:r.randrange(0, 31)]                  # shorter than k: inherits the previous read's tallies
+            if u_windows and seed == 4 and ur.random() < 0.02:
+                g = strains[ur.randrange(nstrains)]
+                for _ in range(60):
+                    u = _synth.u_window(ur, g)
+                    if u and g.find(u[1]) % 17 == 0:           # (a k-mer of the informative list)
+                        cut = ur.randrange(len(rd) + 1)
+                        rd = rd[:cut] + u[0] + rd[cut:]
+                        break
             out.append(rd)
         return out
 
     def fasta(rs):
         return b"".join(b">r%d\n%s\n" % (i, x) for i, x in enumerate(rs))
 
+    ur = random.Random(77)
     with gzip.open(tmp_path / "se.fa.gz", "wb", compresslevel=1) as f:
         f.write(fasta(reads(nreads, 1)))
-    (tmp_path / "pe_1.fa").write_bytes(fasta(reads(60_000, 2)))
-    (tmp_path / "pe_2.fa").write_bytes(fasta(reads(60_000, 3)))
-    (tmp_path / "il.fa").write_bytes(fasta(reads(50_001, 4)))          # odd count: the last mate is missing
+    (tmp_path / "pe_1.fa").write_bytes(fasta(reads(mates[0], 2)))
+    (tmp_path / "pe_2.fa").write_bytes(fasta(reads(mates[0], 3)))
+    (tmp_path / "il.fa").write_bytes(fasta(reads(mates[1], 4)))          # odd count: the last mate is missing
     (tmp_path / "B.txt").write_text(f"SE\t{tmp_path}/se.fa.gz\n#comment\nPE\t{tmp_path}/pe_1.fa\t{tmp_path}/pe_2.fa\n"
                                     f"XX\tnope\nPEI\t{tmp_path}/il.fa\n")
     return nstrains
@@ -486,3 +497,47 @@ def test_sd_union_leaves_a_giant_record_to_the_members(tmp_path):
         outs[union] = [gzip.open(tmp_path / f"out{s}.gz", "rb").read() for s in range(3)]
     assert outs[True] == outs[False]
     assert sum(o.count(b"\n") for o in outs[True]) > 300
+
+
+@pytest.mark.gpu
+def test_sd_related_strains_packed_chunks_against_oracle_runs(tmp_path):
+    """-S with SK_SD_PACK=1: four related strains tallied through sk_scan_grid<TALLY, UNION, PACKED> (the chunks of these
+    files hold only A/C/G/T and newlines, so every one goes up packed); every strain's file equals the CPU oracle program's
+    run on that strain alone"""
+    n = _make_multi_inputs(tmp_path, nstrains=4, strain_len=12_000, nreads=30_000, related=True, mates=(10_000, 8_001))
+    env = dict(os.environ, SK_SD_PACK="1", SK_SD_TIMING="1", SK_SD_CHUNK_BYTES="400000")
+    multi = subprocess.run([sk.cli_path("strain_detect"), "-S", str(tmp_path / "strains.txt"), "-B", str(tmp_path / "B.txt")],
+                           capture_output=True, env=env)
+    assert multi.returncode == 0, multi.stderr.decode()[-500:]
+    assert b"union table(s) for 4 strains" in multi.stderr
+    total = 0
+    for s, want in enumerate(_oracle_runs(tmp_path, n)):
+        assert gzip.open(tmp_path / f"multi{s}.gz", "rb").read() == want, s
+        total += want.count(b"\n")
+    assert total > 4 * 100
+
+
+@pytest.mark.gpu
+def test_sd_u_windows_through_the_union_against_oracle_runs(tmp_path):
+    """-S on -B files whose interleaved file holds reads with U windows that hit informative k-mers (the union's byte-string
+    kernel, sk_scan_wide<TALLY, UNION>, is their only way to a hit).  With SK_SD_PACK=1 and small chunks the chunks holding U
+    go up as bytes and the others packed.  Every strain's file equals the CPU oracle program's run on it alone, and what
+    SK_SD_NO_UNION=1 (strain by strain) writes."""
+    n = _make_multi_inputs(tmp_path, nstrains=3, strain_len=12_000, nreads=20_000, u_windows=True, mates=(8_000, 12_001))
+    il = (tmp_path / "il.fa").read_bytes()
+    assert il.count(b"U") + il.count(b"u") > 150
+    outs = {}
+    for union in (True, False):
+        env = dict(os.environ, SK_SD_PACK="1", SK_SD_TIMING="1", SK_SD_CHUNK_BYTES="200000")
+        if not union:
+            env["SK_SD_NO_UNION"] = "1"
+        p = subprocess.run([sk.cli_path("strain_detect"), "-S", str(tmp_path / "strains.txt"), "-B", str(tmp_path / "B.txt")],
+                           capture_output=True, env=env)
+        assert p.returncode == 0, p.stderr.decode()[-500:]
+        assert (b"union table(s) for 3 strains" in p.stderr) == union
+        outs[union] = [gzip.open(tmp_path / f"multi{s}.gz", "rb").read() for s in range(n)]
+    assert outs[True] == outs[False]
+    wants = _oracle_runs(tmp_path, n)
+    for s in range(n):
+        assert outs[True][s] == wants[s], s
+    assert sum(w.count(b"\n") for w in wants) > 3 * 100
