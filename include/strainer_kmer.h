@@ -370,7 +370,10 @@ int skh_kmer_scrub_count_main(int argc, char **argv, FILE *out, FILE *err);
  * SK_UNION_MAX strains share one union table and one pass over the lists (sk_union_count_enable / sk_union_counts_fold);
  * a -C line equal to a strain's genome is taken back from that strain alone.  Environment: SK_SCRUB_GROUP=1..32 (strains
  * per union), SK_SCRUB_NO_UNION=1 (a pass per strain); with WORLD_SIZE/RANK the strain lines are dealt to the ranks
- * round-robin (no collective).  Returns the exit status. */
+ * round-robin (no collective).  With "--scrub <min_fraction> [--independent] --detect <strain_detect arguments>" a line is
+ * <genome> TAB <informative outfile> TAB <hits outfile> [TAB <-g list>]: the informative outfile gets what `-r <genome> ...
+ * --scrub f [--independent]` prints (step 2 on the resident counts), and the strains go on into step 3 (and 4) together through
+ * skh_strain_detect_resident_many.  --scrub without --detect is refused.  Returns the exit status. */
 int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err);
 
 /* The whole strain_detect program with the reference's argv contract (src/strain_detect.c:61-158):
@@ -384,6 +387,14 @@ int skh_strain_detect_main(int argc, char **argv, FILE *out, FILE *err);
  * ignored; -r and -a are implied.  `kmer_scrub_count ... --scrub m --detect <those arguments>` runs the reference's
  * steps 1 to 3 (4 with --coverage-depth) in one process this way. */
 int skh_strain_detect_resident(sk_ctx *ctx, skh_keyset *ks, const char *informative_path, int argc, char **argv, FILE *out, FILE *err);
+/* The same for n strains at once, as strain_detect -S runs them (one decode of the targets, union tables, SK_SD_GROUP):
+ * ctx[i] and ks[i] are strain i's, loaded with at least 6 columns (all are taken over and released by the call, whatever
+ * happens); informative[i], hits[i], glist[i] are what its -a, -o, -g would name (glist, or glist[i], NULL: no -g).  argv =
+ * strain_detect's command line WITHOUT -r, -a, -o, -S, -g (-B/-b/-c/-t, --coverage-depth with no file name, --min-kmer-hits),
+ * argv[0] ignored.  hits == NULL: n is 1 and -o, -g come from argv -- skh_strain_detect_resident is that case.  Used by
+ * `kmer_scrub_count -S <strains> ... --scrub m --detect <those arguments>`. */
+int skh_strain_detect_resident_many(uint32_t n, sk_ctx **ctx, skh_keyset *ks, const char *const *informative, const char *const *hits,
+                                    const char *const *glist, int argc, char **argv, FILE *out, FILE *err);
 
 /* Record reader exposed for tests: decode `path` into the record stream, calling `sink` with
  * successive chunks (records separated by '\n'; a long record may be cut with a k-1 overlap).

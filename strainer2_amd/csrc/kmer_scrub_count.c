@@ -2,7 +2,8 @@
  * (src/kmer_scrub_count.c:29-131): same flags (-r -A -B -C -p, and -d -h -u -H accepted), same
  * stdout TSV in the same row order, same progress file, same stderr texts and exit status.
  * Extension: -S <strains file> WITHOUT -r counts many strains over one pass of the lists
- * (skh_kmer_scrub_count_multi_main); with -r, -S is what the reference makes of it (usage, ignored).
+ * (skh_kmer_scrub_count_multi_main), and with --scrub .. --detect takes them on through steps 2-3 (and 4); with -r, -S is what
+ * the reference makes of it (usage, ignored).
  * All of the work happens in libstrainer_kmer.so (host layer in C, scan in HIP on gfx950). */
 #include <stdio.h>
 #include <string.h>
@@ -16,8 +17,8 @@ static int has_opt(int argc, char **argv, char opt)
     for (i = 1; i < argc; i++) {
         const char *a = argv[i];
         if (a[0] != '-' || a[1] == '\0') continue;
-        if (!strcmp(a, "--")) break;
-        if (a[1] == '-') continue;                     /* (--scrub, --detect ...: their values are skipped by the program) */
+        if (!strcmp(a, "--") || !strcmp(a, "--detect")) break;      /* (what follows --detect is strain_detect's command line) */
+        if (a[1] == '-') continue;                     /* (--scrub ...: its value is skipped by the program) */
         for (a++; *a; a++) {
             if (*a == opt) return 1;
             if (strchr("ABCrpS", *a)) { if (a[1] == '\0') i++; break; }

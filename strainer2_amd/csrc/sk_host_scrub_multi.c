@@ -8,6 +8,12 @@
  * members it names (u32 wrap makes -= after += exact).  A strain the union cannot hold (byte-string keys, no text stage) gets a
  * pass of its own through its own context, as the single-strain program would run it.
  *
+ * With --scrub <min_fraction> [--independent] --detect <strain_detect arguments> each strain goes on into step 2 on its resident
+ * counts (skh_scrub_filter_resident, sk_filter on the device) and its line names an informative outfile and a hit list instead of
+ * a count table; then the strains go on together into step 3 (and 4) on the same resident tables: skh_strain_detect_resident_many,
+ * strain_detect -S's machinery with the tables of step 1 taken over instead of rebuilt.  --scrub without --detect stays refused,
+ * as before this mode existed (run the strains one by one for the informative lists alone).
+ *
  * Kept in a translation unit of its own: the host tests link sk_host.c, sk_host_sd.c and sk_host_cov.c against a device
  * double that has none of the union's COUNT entry points. */
 #define _GNU_SOURCE
@@ -23,19 +29,25 @@
 #include "sk_gzout.h"
 
 typedef struct {
-    char      *genome, *outfile;
+    char      *genome, *outfile;   /* outfile: the count table, or with --scrub the informative list                        */
+    char      *hits, *glist, *cov; /* --detect: the hit list, the -g list (or NULL), the --coverage-depth table (or NULL)    */
     FILE      *fp;                 /* the outfile (plain) ...                                    */
     skzo_file *zo;                 /* ... or its gzip writer (a name ending in .gz)              */
     skh_keyset ks;
     sk_ctx    *ctx;
     int        rc_keys, rc_ctx, rc_load;
     int        print_rc;
+    char      *err_buf;            /* --scrub: what the filter said, replayed in list order */
+    size_t     err_len;
+    unsigned   made;               /* the files this run created: 1 outfile, 2 hits, 4 coverage table */
 } sm_strain;
 
 typedef struct {
     sm_strain *st;
     uint32_t   n;
-    int        device, with_drug;
+    int        device, with_drug, ncols;
+    double     scrub_fraction;     /* >= 0: step 2 instead of the table */
+    int        independent;
     uint32_t   next;               /* pool: the next strain to take */
     pthread_mutex_t mu;
 } sm_job;
@@ -90,10 +102,12 @@ static void *sm_open_worker(void *arg)
         if (s->rc_keys != SK_OK) continue;
         s->rc_ctx = sk_ctx_create(&s->ctx, j->device);
         if (s->rc_ctx != SK_OK) { s->ctx = NULL; continue; }
-        s->rc_load = skh_keyset_load(s->ctx, &s->ks, 4);
+        s->rc_load = skh_keyset_load(s->ctx, &s->ks, (uint32_t)j->ncols);     /* (strain_detect's table has six columns) */
     }
     return NULL;
 }
+
+#define SM_FILTER_FAILED 1          /* (print_rc of a strain whose filter said why itself) */
 
 static ssize_t sm_gz_write(void *cookie, const char *buf, size_t n)
 {
@@ -113,7 +127,12 @@ static void *sm_print_worker(void *arg)
             if (!f) { s->print_rc = SK_E_NOMEM; continue; }
         }
         setvbuf(f, NULL, _IOFBF, 1 << 20);
-        s->print_rc = skh_print_counts(s->ctx, &s->ks, f, j->with_drug);
+        if (j->scrub_fraction >= 0.0) {              /* step 2: the informative list, as `-r <genome> ... --scrub f` prints it */
+            FILE *me = open_memstream(&s->err_buf, &s->err_len);
+            s->print_rc = skh_scrub_filter_resident(s->ctx, &s->ks, j->with_drug, j->scrub_fraction, j->independent, f, me ? me : stderr)
+                              ? SM_FILTER_FAILED : SK_OK;
+            if (me) fclose(me);
+        } else s->print_rc = skh_print_counts(s->ctx, &s->ks, f, j->with_drug);
         if (s->zo) { if (fclose(f) != 0 && s->print_rc == SK_OK) s->print_rc = SK_E_OPEN; }
         else if (fflush(f) != 0 && s->print_rc == SK_OK) s->print_rc = SK_E_OPEN;
     }
@@ -203,6 +222,60 @@ static int sm_is_gz(const char *p)
     return l >= 3 && strcmp(p + l - 3, ".gz") == 0;
 }
 
+static void sm_usage(FILE *err)
+{
+    fputs("Usage: kmer_scrub_count -S <strains file: genome TAB outfile per line> -A <file with multiple genome filenames> "
+          "-B <file with multiple metagenome filenames> -C <(optional) file with multiple genome filenames of drug strains> "
+          "-p [progress output file, optional]\n", err);
+    fputs("  with --scrub <min_fraction> [--independent] --detect <strain_detect arguments: -B list | -b -c -t, --coverage-depth, "
+          "--min-kmer-hits>: a line is genome TAB informative outfile TAB hits outfile [TAB -g list] (steps 1-3, 4)\n", err);
+}
+
+/* where strain_detect --coverage-depth puts a strain's table: its hit list's name, ".kmer_hits.gz" replaced by ".coverage_depth" */
+static char *sm_cov_path(const char *hits)
+{
+    const size_t n = strlen(hits);
+    char *c = (char *)malloc(n + 32);
+    strcpy(c, hits);
+    if (n >= 13 && !strcmp(c + n - 13, ".kmer_hits.gz")) c[n - 13] = 0;
+    strcat(c, ".coverage_depth");
+    return c;
+}
+
+/* the arguments behind --detect, checked before anything is opened: strain_detect's own letters, less the ones every strain's
+ * line gives (-r -a -o -g) and -S; --coverage-depth without a file name (one name cannot serve many strains) */
+static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
+{
+    char **v = (char **)malloc(((size_t)argc + 1) * sizeof *v);
+    int c, n = 0, bad = 0, saved = opterr;
+    if (!v) return 1;
+    for (c = 0; c < argc; c++) {
+        if (c > 0 && !strncmp(argv[c], "--coverage-depth", 16) && (argv[c][16] == 0 || argv[c][16] == '=')) {
+            if (argv[c][16] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-depth takes no file name (each strain's table goes next to its hit list)\n");
+                free(v);
+                return 1;
+            }
+            *want_cov = 1;
+            continue;
+        }
+        if (c > 0 && !strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { c++; continue; }
+        v[n++] = argv[c];
+    }
+    v[n] = NULL;
+    opterr = 0;                                      /* (strain_detect itself reports unknown letters later) */
+    optind = 1;
+    while (!bad && (c = getopt(n, v, "g:r:a:A:b:c:B:S:M:o:t:Hhuspn")) != -1)
+        if (c == 'r' || c == 'a' || c == 'o' || c == 'S' || c == 'g') {
+            fprintf(err, "kmer_scrub_count: with -S, each strain's line gives strain_detect's -%c (not after --detect)\n", c);
+            bad = 1;
+        }
+    opterr = saved;
+    optind = 1;
+    free(v);
+    return bad;
+}
+
 int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
 {
     const char *A = NULL, *B = NULL, *C = NULL, *P = NULL, *S = NULL, *env;
@@ -213,15 +286,41 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
     sm_strain *st = NULL;
     FILE *progress = NULL;
     skzo_pool zpool;
-    int zpool_on = 0, status = 1, c, any_gz = 0, created = 0;
-    double t0 = sm_now(), t1 = 0, t2 = 0, t3 = 0, fold_ms = 0;
-    (void)out;
+    int zpool_on = 0, status = 1, c, j, any_gz = 0, want_cov = 0;
+    double t0 = sm_now(), t1 = 0, t2 = 0, t3 = 0, t4 = 0, fold_ms = 0;
+    double scrub_fraction = -1.0;                    /* >= 0: step 2 on the resident counts instead of the table */
+    int independent = 0, detect_argc = 0;
+    char **detect_argv = NULL;                       /* --detect ...: strain_detect's arguments (step 3 for all the strains) */
 
+    /* the words of the single-strain program's extensions (skh_kmer_scrub_count_main): everything behind --detect is
+     * strain_detect's command line; --scrub and --independent are taken out of argv before getopt.  Without --detect, -S does
+     * not take them: the informative lists alone are the single-strain program's */
     for (c = 1; c < argc; c++)
-        if (!strncmp(argv[c], "--scrub", 7) || !strcmp(argv[c], "--detect") || !strcmp(argv[c], "--independent")) {
+        if (!strcmp(argv[c], "--detect")) { detect_argv = argv + c; detect_argc = argc - c; argc = c; break; }
+    for (c = 1; !detect_argv && c < argc; c++)
+        if (!strncmp(argv[c], "--scrub", 7) || !strcmp(argv[c], "--independent")) {
             fprintf(err, "kmer_scrub_count: -S does not go with --scrub/--detect (run the strains one by one for those)\n");
             return 1;
         }
+    for (c = 1, j = 1; c < argc; c++) {
+        if (!strcmp(argv[c], "--independent")) { independent = 1; continue; }
+        if (!strncmp(argv[c], "--scrub-out", 11)) {
+            fprintf(err, "kmer_scrub_count: with -S the strains file names each informative outfile (no --scrub-out)\n");
+            return 1;
+        }
+        if (!strncmp(argv[c], "--scrub", 7) && (argv[c][7] == 0 || argv[c][7] == '=')) {
+            const char *v = argv[c][7] ? argv[c] + 8 : (c + 1 < argc ? argv[++c] : "");
+            char *e;
+            scrub_fraction = strtod(v, &e);
+            if (e == v || *e || scrub_fraction < 0.0 || scrub_fraction > 1.0) {
+                fprintf(err, "kmer_scrub_count: --scrub needs a fraction between 0.0 and 1.0\n");
+                return 1;
+            }
+            continue;
+        }
+        argv[j++] = argv[c];
+    }
+    argc = j;
     optind = 1;
     while ((c = getopt(argc, argv, "A:B:C:S:p:Hhud")) != -1) {
         switch (c) {
@@ -232,35 +331,46 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
         case 'p': P = optarg; break;
         case 'd': break;
         default:
-            fputs("Usage: kmer_scrub_count -S <strains file: genome TAB outfile per line> -A <file with multiple genome filenames> "
-                  "-B <file with multiple metagenome filenames> -C <(optional) file with multiple genome filenames of drug strains> "
-                  "-p [progress output file, optional]\n", err);
+            sm_usage(err);
             break;
         }
     }
     if (!S || !A || !B) {
-        fputs("Usage: kmer_scrub_count -S <strains file: genome TAB outfile per line> -A <file with multiple genome filenames> "
-              "-B <file with multiple metagenome filenames> -C <(optional) file with multiple genome filenames of drug strains> "
-              "-p [progress output file, optional]\n", err);
+        sm_usage(err);
         return 1;
     }
+    if (detect_argv && scrub_fraction < 0.0) {
+        fprintf(err, "kmer_scrub_count: --detect needs --scrub <min_fraction> and a single process\n");
+        return 1;
+    }
+    if (detect_argv && sm_check_detect(detect_argc, detect_argv, &want_cov, err)) return 1;
     if (world < 1 || rank < 0 || rank >= world) { fprintf(err, "kmer_scrub_count: bad rank %d of %d\n", rank, world); return 1; }
+    if (detect_argv && (env = getenv("SK_DEVICES")) != NULL && *env) {
+        fprintf(err, "kmer_scrub_count: -S --detect keeps every strain on the device that counted it (SK_DEVICES is not for this run)\n");
+        return 1;
+    }
     if ((env = getenv("SK_DEVICE")) != NULL) device = atoi(env);
     if ((env = getenv("SK_SCRUB_GROUP")) != NULL && atoi(env) >= 1 && atoi(env) <= SK_UNION_MAX) group = (uint32_t)atoi(env);
 
-    {   /* the strains file: <genome> TAB <outfile>; this rank's lines (round-robin over the strain lines) */
+    {   /* the strains file: <genome> TAB <outfile> (with --detect: <genome> TAB <informative> TAB <hits> [TAB <-g list>]);
+         * this rank's lines (round-robin over the strain lines) */
         FILE *fp = fopen(S, "r");
         char *line = NULL, *nl;
         size_t cap = 0;
         unsigned lineno = 0;
         if (!fp) { fprintf(err, "kmer_scrub_count: could not read the strain list %s\n", S); return 1; }
         while (getline(&line, &cap, fp) != -1) {
-            char *fr, *fo, *rest;
+            char *fr, *fo, *fh = NULL, *fg = NULL, *rest;
             if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
             if (line[0] == '#' || line[0] == '\0') continue;
-            fr = strtok(line, "\t"); fo = strtok(NULL, "\t"); rest = strtok(NULL, "\t");
-            if (!fr || !fo || rest) {
-                fprintf(err, "kmer_scrub_count: %s: a line needs <reference genome> TAB <outfile>\n", S);
+            fr = strtok(line, "\t"); fo = strtok(NULL, "\t");
+            if (detect_argv) { fh = strtok(NULL, "\t"); fg = strtok(NULL, "\t"); }
+            rest = strtok(NULL, "\t");
+            if (!fr || !fo || rest || (detect_argv && !fh)) {
+                if (detect_argv)
+                    fprintf(err, "kmer_scrub_count: %s: a line needs <reference genome> TAB <informative outfile> TAB <hits outfile> "
+                                 "[TAB <-g list>]\n", S);
+                else fprintf(err, "kmer_scrub_count: %s: a line needs <reference genome> TAB <outfile>\n", S);
                 free(line); fclose(fp);
                 goto done;
             }
@@ -269,19 +379,33 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
             memset(&st[ns], 0, sizeof st[ns]);
             st[ns].genome = strdup(fr);
             st[ns].outfile = strdup(fo);
+            if (fh) st[ns].hits = strdup(fh);
+            if (fg) st[ns].glist = strdup(fg);
+            if (fh && want_cov) st[ns].cov = sm_cov_path(fh);
             ns++;
         }
         free(line);
         fclose(fp);
     }
-    /* every outfile is created before anything is scanned: a run that cannot write its results does not start */
+    /* every outfile is created before anything is scanned: a run that cannot write its results does not start (the hit lists
+     * and coverage tables are written by step 3, which opens them again) */
     for (k = 0; k < ns; k++) any_gz |= sm_is_gz(st[k].outfile);
     if (any_gz) { skzo_pool_start(&zpool, sm_threads()); zpool_on = 1; }
     for (k = 0; k < ns; k++) {
+        const char *more[2];
+        int m;
         if (sm_is_gz(st[k].outfile)) st[k].zo = skzo_open(&zpool, st[k].outfile);
         else st[k].fp = fopen(st[k].outfile, "w");
         if (!st[k].zo && !st[k].fp) { fprintf(err, "kmer_scrub_count: cannot write %s\n", st[k].outfile); goto done; }
-        created = (int)k + 1;
+        st[k].made |= 1u;
+        more[0] = st[k].hits; more[1] = st[k].cov;
+        for (m = 0; m < 2; m++) {
+            FILE *f;
+            if (!more[m]) continue;
+            if (!(f = fopen(more[m], "w"))) { fprintf(err, "kmer_scrub_count: cannot write %s\n", more[m]); goto done; }
+            fclose(f);
+            st[k].made |= 2u << m;
+        }
     }
     if (P && rank == 0) {
         progress = fopen(P, "w");
@@ -292,7 +416,7 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
     {   /* the strains are opened on worker threads; what went wrong is said here, in list order, up to the first failure */
         sm_job j;
         memset(&j, 0, sizeof j);
-        j.st = st; j.n = ns; j.device = device;
+        j.st = st; j.n = ns; j.device = device; j.ncols = detect_argv ? 6 : 4;
         sm_pool_run(&j, sm_threads(), sm_open_worker);
         for (k = 0; k < ns; k++) {
             sm_strain *s = &st[k];
@@ -342,13 +466,16 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
     }
     t2 = sm_now();
 
-    {   /* the tables, printed on worker threads (a 5 Mbp strain's table is ~250 MB of text) */
+    {   /* the tables, printed on worker threads (a 5 Mbp strain's table is ~250 MB of text), or with --scrub the informative
+         * lists (sk_filter on each strain's device table); what the filters said is replayed here in list order */
         sm_job j;
         memset(&j, 0, sizeof j);
-        j.st = st; j.n = ns; j.with_drug = C != NULL;
+        j.st = st; j.n = ns; j.with_drug = C != NULL; j.scrub_fraction = scrub_fraction; j.independent = independent;
         sm_pool_run(&j, sm_threads(), sm_print_worker);
         for (k = 0; k < ns; k++) {
             int wrc = st[k].print_rc;
+            if (st[k].err_buf && st[k].err_len) fwrite(st[k].err_buf, 1, st[k].err_len, err);
+            if (wrc == SM_FILTER_FAILED) goto done;
             if (st[k].zo) { if (skzo_close(st[k].zo) && wrc == SK_OK) wrc = SK_E_OPEN; st[k].zo = NULL; }
             if (st[k].fp) { if (fclose(st[k].fp) != 0 && wrc == SK_OK) wrc = SK_E_OPEN; st[k].fp = NULL; }
             if (wrc == SK_E_OPEN) { fprintf(err, "kmer_scrub_count: error writing %s\n", st[k].outfile); goto done; }
@@ -356,19 +483,50 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
         }
     }
     t3 = sm_now();
+    if (detect_argv && ns) {   /* step 3 (and 4) for all of this rank's strains, on the tables of step 1: taken over by the call */
+        sk_ctx **ctxs = (sk_ctx **)calloc(ns, sizeof *ctxs);
+        skh_keyset *kss = (skh_keyset *)calloc(ns, sizeof *kss);
+        const char **inf = (const char **)calloc(ns, sizeof *inf), **hits = (const char **)calloc(ns, sizeof *hits);
+        const char **gl = (const char **)calloc(ns, sizeof *gl);
+        int rc;
+        if (!ctxs || !kss || !inf || !hits || !gl) {
+            fprintf(err, "kmer_scrub_count: out of memory\n");
+            free(ctxs); free(kss); free(inf); free(hits); free(gl);
+            goto done;
+        }
+        for (k = 0; k < ns; k++) {
+            ctxs[k] = st[k].ctx; kss[k] = st[k].ks;
+            st[k].ctx = NULL; memset(&st[k].ks, 0, sizeof st[k].ks);
+            inf[k] = st[k].outfile; hits[k] = st[k].hits; gl[k] = st[k].glist;
+        }
+        rc = skh_strain_detect_resident_many(ns, ctxs, kss, inf, hits, gl, detect_argc, detect_argv, out, err);
+        free(ctxs); free(kss); free(inf); free(hits); free(gl);
+        if (rc != 0) goto done;
+    }
+    t4 = sm_now();
     status = 0;
 done:
-    if (getenv("SK_TIMING") && t3 > 0)
+    if (getenv("SK_TIMING") && t3 > 0 && scrub_fraction < 0.0)
         fprintf(err, "kmer_scrub_count -S timing: %u strain(s) opened in %.2f s, %u union pass(es) + %u single pass(es) %.2f s "
                      "(folds %.1f ms), print %.2f s\n", ns, t1 - t0, nunion, nsingle, t2 - t1, fold_ms, t3 - t2);
+    if (getenv("SK_TIMING") && t3 > 0 && scrub_fraction >= 0.0)
+        fprintf(err, "kmer_scrub_count -S timing: %u strain(s) opened in %.2f s, %u union pass(es) + %u single pass(es) %.2f s "
+                     "(folds %.1f ms), filter %.2f s, detect %.2f s\n", ns, t1 - t0, nunion, nsingle, t2 - t1, fold_ms, t3 - t2,
+                t4 > 0 ? t4 - t3 : 0.0);
     for (k = 0; k < ns; k++) {
         if (st[k].zo) skzo_close(st[k].zo);
         if (st[k].fp) fclose(st[k].fp);
-        if (status != 0 && (int)k < created) unlink(st[k].outfile);     /* no outfile of a failed run looks complete */
+        if (status != 0) {                                              /* no outfile of a failed run looks complete */
+            if (st[k].made & 1u) unlink(st[k].outfile);
+            if (st[k].made & 2u) unlink(st[k].hits);
+            if (st[k].made & 4u) unlink(st[k].cov);
+        }
         if (st[k].ctx) sk_ctx_destroy(st[k].ctx);
         skh_keyset_free(&st[k].ks);
         free(st[k].genome);
         free(st[k].outfile);
+        free(st[k].hits); free(st[k].glist); free(st[k].cov);
+        free(st[k].err_buf);
     }
     free(st);
     if (progress) fclose(progress);

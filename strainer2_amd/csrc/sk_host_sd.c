@@ -1765,12 +1765,14 @@ static skzo_pool *sd_zpool;             /* compressors of every -o file of the r
  * main thread in list order. */
 typedef struct {
     sd_prog *p; const char *r, *a, *g, *o; int device, failed, done;
+    int adopted;                          /* the strain is resident already (its context and key set were taken over): sd_strain_adopted */
     char *out_buf, *err_buf; size_t out_len, err_len;
     sk_ctxjob *cj;                        /* the first strain takes the context that was opened while the key sets were built */
 } ks_job;
 typedef struct { ks_job *jobs; uint32_t njobs, next; pthread_mutex_t mu; pthread_cond_t cv; } ks_pool;
 
 static int sd_strain_finish(sd_prog *p, int ks_rc, const char *r, const char *a, const char *g, const char *o, int device);
+static int sd_strain_adopted(sd_prog *p, const char *a, const char *g, const char *o);
 
 /* A strain's key set.  Round 3: built ON THE DEVICE from the strain's text (skh_keyset_build_on_device: the host only parses the
  * file and packs the bases; no hash table of 5 M keys on the host, no 140 MB of keys, permutations and columns over PCIe) -- the
@@ -1802,12 +1804,12 @@ static void *sd_keyset_pool_thread(void *arg)
         if (k >= kp->njobs) return NULL;
         j = &kp->jobs[k];
         if (j->cj) j->p->ctx_rc = sk_ctxjob_join(j->cj, &j->p->ctx);
-        rc = sd_keyset(j->p, j->r, j->device);
+        rc = j->adopted ? SK_OK : sd_keyset(j->p, j->r, j->device);
         real_out = j->p->out; real_err = j->p->err;
         mo = open_memstream(&j->out_buf, &j->out_len);
         me = open_memstream(&j->err_buf, &j->err_len);
         if (mo && me) { j->p->out = mo; j->p->err = me; }
-        j->failed = sd_strain_finish(j->p, rc, j->r, j->a, j->g, j->o, j->device);
+        j->failed = j->adopted ? sd_strain_adopted(j->p, j->a, j->g, j->o) : sd_strain_finish(j->p, rc, j->r, j->a, j->g, j->o, j->device);
         if (mo) fclose(mo);
         if (me) fclose(me);
         j->p->out = real_out; j->p->err = real_err;
@@ -1868,17 +1870,25 @@ static int sd_strain_finish(sd_prog *p, int ks_rc, const char *r, const char *a,
     }
 }
 
-/* The strain of a kmer_scrub_count run that goes on into strain_detect in the same process (key set, row
+/* The strains of a kmer_scrub_count run that goes on into strain_detect in the same process (key set, row
  * order, device table, filters and text are built ONCE for steps 1 and 3; src/strain_detect.c:137-146 rebuilds what
- * src/kmer_scrub_count.c:87-89 built).  Takes over ctx and *ks (the caller's copy is cleared); the table must have been
- * loaded with at least SD_NCOLS columns.  Every column goes back to what a fresh strain_detect start has. */
-static int sd_strain_adopt(sd_prog *p, sk_ctx *ctx, skh_keyset *ks, const char *a, const char *g, const char *o, FILE *out, FILE *err)
+ * src/kmer_scrub_count.c:87-89 built).  sd_strain_adopt takes over ctx and *ks (the caller's copy is cleared), before anything
+ * can fail: from then on the strain is closed with the others.  sd_strain_adopted then checks the table (loaded with at least
+ * SD_NCOLS columns), puts every column back to what a fresh strain_detect start has, and flags the strain. */
+static void sd_strain_adopt(sd_prog *p, sk_ctx *ctx, skh_keyset *ks, FILE *out, FILE *err)
 {
-    uint32_t col;
-    int rc = SK_OK;
     memset(p, 0, sizeof *p);
     p->out = out; p->err = err; p->ctx = ctx; p->ks = *ks;
     memset(ks, 0, sizeof *ks);
+}
+
+static int sd_strain_adopted(sd_prog *p, const char *a, const char *g, const char *o)
+{
+    sk_ctx *ctx = p->ctx;
+    FILE *err = p->err;
+    uint32_t col;
+    int rc = SK_OK;
+    if (!ctx) { fprintf(err, "strain_detect: no resident table\n"); return 1; }
     if (sk_table_cols(ctx) < SD_NCOLS || sk_table_rows(ctx) != p->ks.nrows) { fprintf(err, "strain_detect: the resident table does not fit (columns/rows)\n"); return 1; }
     for (col = 0; col < SD_NCOLS && rc == SK_OK; col++) rc = sk_counts_zero(ctx, col);
     if (rc == SK_OK && p->ks.nrows) {
@@ -1988,20 +1998,114 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     return bad;
 }
 
-static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, sk_ctx *adopt_ctx, skh_keyset *adopt_ks, const char *adopt_a);
+/* strains that are already resident (kmer_scrub_count ... --scrub f --detect ...): n contexts and key sets, taken over */
+typedef struct {
+    uint32_t n;
+    sk_ctx **ctx;
+    skh_keyset *ks;
+    const char *const *a, *const *o, *const *g;      /* o == NULL: ONE strain whose -o and -g are on the command line */
+} sd_adoption;
 
-int skh_strain_detect_main(int argc, char **argv, FILE *out, FILE *err) { return sd_main_impl(argc, argv, out, err, NULL, NULL, NULL); }
+static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_adoption *ad);
+
+int skh_strain_detect_main(int argc, char **argv, FILE *out, FILE *err) { return sd_main_impl(argc, argv, out, err, NULL); }
 
 /* strain_detect on a strain that is already resident: ctx holds its table (>= 6 columns), *ks its key set -- both are
  * taken over and released here -- and informative_path names the informative k-mer list (what -a would name).  argv: the
- * rest of a strain_detect command line (-B/-b/-c/-t/-g/-o, --coverage-depth ...), argv[0] ignored; -r and -a are implied. */
+ * rest of a strain_detect command line (-B/-b/-c/-t/-g/-o, --coverage-depth ...), argv[0] ignored; -r and -a are implied.
+ * The n = 1 case of skh_strain_detect_resident_many, with -o and -g taken from argv. */
 int skh_strain_detect_resident(sk_ctx *ctx, skh_keyset *ks, const char *informative_path, int argc, char **argv, FILE *out, FILE *err)
 {
-    if (!ctx || !ks || !informative_path) return 1;
-    return sd_main_impl(argc, argv, out, err, ctx, ks, informative_path);
+    return skh_strain_detect_resident_many(1, &ctx, ks, &informative_path, NULL, NULL, argc, argv, out, err);
 }
 
-static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, sk_ctx *adopt_ctx, skh_keyset *adopt_ks, const char *adopt_a)
+/* strain_detect -S on n strains that are already resident: ctx[s] holds strain s's table (>= 6 columns), ks[s] its key set --
+ * all are taken over and released here, whatever happens -- informative[s] names its informative k-mer list (-a), hits[s]
+ * its outfile (-o) and glist[s] (NULL, or glist itself NULL) its -g list.  argv: strain_detect's command line without -r, -a,
+ * -o, -S, -g (-B/-b/-c/-t, --coverage-depth, --min-kmer-hits), argv[0] ignored.  The strains share the -S machinery: one decode
+ * of the targets, union tables of SK_SD_GROUP strains, each --coverage-depth table at its strain's default path.  hits == NULL:
+ * n must be 1, and -o (and -g) come from argv, as in skh_strain_detect_resident. */
+int skh_strain_detect_resident_many(uint32_t n, sk_ctx **ctx, skh_keyset *ks, const char *const *informative, const char *const *hits,
+                                    const char *const *glist, int argc, char **argv, FILE *out, FILE *err)
+{
+    sd_adoption ad;
+    uint32_t s;
+    int bad = !ctx || !ks || !informative || n == 0 || (!hits && n != 1);
+    for (s = 0; !bad && s < n; s++) bad = !ctx[s] || !informative[s] || (hits && !hits[s]);
+    if (bad) {
+        for (s = 0; ctx && ks && s < n; s++) {           /* (taken over all the same: nothing is left to the caller) */
+            if (ctx[s]) sk_ctx_destroy(ctx[s]);
+            ctx[s] = NULL;
+            skh_keyset_free(&ks[s]);
+        }
+        fprintf(err, "strain_detect: no resident strains to adopt\n");
+        return 1;
+    }
+    ad.n = n; ad.ctx = ctx; ad.ks = ks; ad.a = informative; ad.o = hits; ad.g = glist;
+    return sd_main_impl(argc, argv, out, err, &ad);
+}
+
+/* the strains of a -S list (or the adopted ones), opened by worker threads, each strain start to finish on one of them;
+ * their messages are replayed here in list order, up to the first failure (SK_THREADS, default: the usable CPUs, at most
+ * 16).  paths: r, a, o, g of every strain.  Returns non-zero when a strain failed. */
+static int sd_open_strains(sd_prog *p, uint32_t ns, char **paths, int adopted, FILE *out, FILE *err)
+{
+    long ncpu = sk_cpu_budget();
+    int nth = getenv("SK_THREADS") ? atoi(getenv("SK_THREADS")) : (int)(ncpu < 1 ? 1 : ncpu > 16 ? 16 : ncpu), t;
+    ks_pool kp;
+    pthread_t th[16];
+    uint32_t k, failed = 0;
+    sk_ctxjob cj;
+    /* the HIP runtime comes up (0.25-3 s) while the first key sets are built: the context opened here becomes the first
+     * strain's -- every other sk_ctx_create then finds the runtime ready instead of all workers queueing up behind it */
+    if (ns && !adopted) sk_ctxjob_start(&cj, sd_dev.phys[0]);
+    memset(&kp, 0, sizeof kp);
+    kp.jobs = (ks_job *)calloc(ns ? ns : 1, sizeof *kp.jobs);
+    kp.njobs = ns;
+    pthread_mutex_init(&kp.mu, NULL);
+    pthread_cond_init(&kp.cv, NULL);
+    for (k = 0; k < ns; k++) {
+        ks_job *j = &kp.jobs[k];
+        j->p = &p[k]; j->r = paths[4 * k]; j->a = paths[4 * k + 1]; j->o = paths[4 * k + 2]; j->g = paths[4 * k + 3];
+        j->device = sd_dev.phys[sd_dev_of_strain(k)];
+        j->cj = k == 0 && !adopted ? &cj : NULL;
+        j->adopted = adopted;
+    }
+    if (nth > 16) nth = 16;
+    if (nth < 1) nth = 1;
+    if ((uint32_t)nth > ns) nth = (int)ns;
+    for (t = 0; t < nth; t++) if (pthread_create(&th[t], NULL, sd_keyset_pool_thread, &kp)) break;
+    nth = t;
+    if (nth == 0) sd_keyset_pool_thread(&kp);     /* no thread could be started: open them here */
+    for (k = 0; k < ns; k++) {
+        ks_job *j = &kp.jobs[k];
+        pthread_mutex_lock(&kp.mu);
+        while (!j->done) pthread_cond_wait(&kp.cv, &kp.mu);
+        pthread_mutex_unlock(&kp.mu);
+        if (!failed) {
+            if (j->out_buf && j->out_len) fwrite(j->out_buf, 1, j->out_len, out);
+            if (j->err_buf && j->err_len) fwrite(j->err_buf, 1, j->err_len, err);
+            failed = (uint32_t)j->failed;
+        }
+        free(j->out_buf); free(j->err_buf);
+    }
+    for (t = 0; t < nth; t++) pthread_join(th[t], NULL);
+    pthread_mutex_destroy(&kp.mu);
+    pthread_cond_destroy(&kp.cv);
+    free(kp.jobs);
+    return failed != 0;
+}
+
+/* a run that ends before its strains were opened: the adopted ones are released all the same */
+static int sd_drop(sd_prog *p, uint32_t ns)
+{
+    uint32_t s;
+    for (s = 0; p && s < ns; s++) sd_strain_close(&p[s]);
+    free(p);
+    return 1;
+}
+
+static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_adoption *ad)
 {
     const char *a = NULL, *r = NULL, *b = NULL, *b2 = NULL, *B = NULL, *tt = NULL, *g = NULL, *o = NULL, *S = NULL, *env;
     int c, j, mode = SD_SE, status = 1, device = 0, n_S = 0, want_cov = 0;
@@ -2012,6 +2116,14 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, sk_ctx *ado
     sd_prog *p = NULL;
     char **paths = NULL;
     uint32_t ns = 0, s;
+
+    if (ad) {                                            /* the resident strains are ours from here, whatever happens */
+        p = (sd_prog *)calloc(ad->n, sizeof *p);
+        if (!p) { fprintf(err, "strain_detect: out of memory\n"); return 1; }
+        for (s = 0; s < ad->n; s++) sd_strain_adopt(&p[s], ad->ctx[s], &ad->ks[s], out, err);
+        for (s = 0; s < ad->n; s++) ad->ctx[s] = NULL;
+        ns = ad->n;
+    }
 
     /* Extension (not in the reference): "--coverage-depth[=FILE]" also writes the table that
      * scripts/coverage_depth.py -k <outfile> [-m N] would print (step 4 of the workflow), collected while the
@@ -2049,26 +2161,31 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, sk_ctx *ado
      * line of the file is  <reference genome> TAB <informative k-mer file> TAB <outfile> [TAB <-g list>];
      * every outfile gets exactly what a separate run with that line's -r/-a/-o[/-g] would write.  All
      * tables stay resident on the device; each metagenome is decoded and uploaded once. */
-    if (adopt_ctx) { a = adopt_a; r = "(resident)"; S = NULL; }
+    if (ad && ad->o) {                                   /* many strains: their -r/-a/-o/-g are not on the command line */
+        if (r || a || o || S || g) { fputs("strain_detect: the resident strains bring their own -r, -a, -o and -g\n", err); return sd_drop(p, ns); }
+        if (cov_file) { fputs("strain_detect: --coverage-depth=FILE names one file; the resident strains each have their own\n", err); return sd_drop(p, ns); }
+        o = ad->o[0];
+    }
+    if (ad) { a = ad->a[0]; r = "(resident)"; S = NULL; }
     if (S && !a && !o && !r) {
-        if (!b && !B) { usage(err); return 1; }
+        if (!b && !B) { usage(err); return sd_drop(p, ns); }
     } else {
         S = NULL;
         while (n_S-- > 0) usage(err);
-        if (!a || !o || !r) { usage(err); return 1; }
-        if (!b && !B) { usage(err); return 1; }
+        if (!a || !o || !r) { usage(err); return sd_drop(p, ns); }
+        if (!b && !B) { usage(err); return sd_drop(p, ns); }
     }
     if (tt) {
         mode = file_type(tt);
-        if (mode == SD_UNKNOWN) { fputs("unknown filetype specification. allowed are SE, PE, PEI\n\n", out); usage(err); return 1; }
+        if (mode == SD_UNKNOWN) { fputs("unknown filetype specification. allowed are SE, PE, PEI\n\n", out); usage(err); return sd_drop(p, ns); }
     }
     if (b && mode == SD_PE && !b2) {
-        fputs("commandline PE mapping requires two files (-b [file1] and -c [file2])\n\n", out); usage(err); return 1;
+        fputs("commandline PE mapping requires two files (-b [file1] and -c [file2])\n\n", out); usage(err); return sd_drop(p, ns);
     }
     if (b && B) {
         fputs("cannot have -B flag and -b flag\nEither have a file with metagenomics files to be detect the strain in or "
               "specify one metagenomic file to detect the strain in\n", out);
-        usage(err); return 1;
+        usage(err); return sd_drop(p, ns);
     }
     if ((env = getenv("SK_DEVICE")) != NULL) device = atoi(env);
     sd_dev.n = 1; sd_dev.phys[0] = device;
@@ -2125,62 +2242,24 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, sk_ctx *ado
         }
         free(line);
         fclose(fp);
-        {   /* the strains are opened by worker threads, each strain start to finish on
-             * one of them; their messages are replayed here in list order, up to the first failure
-             * (SK_THREADS, default: the usable CPUs, at most 16) */
-            long ncpu = sk_cpu_budget();
-            int nth = getenv("SK_THREADS") ? atoi(getenv("SK_THREADS")) : (int)(ncpu < 1 ? 1 : ncpu > 16 ? 16 : ncpu), t;
-            ks_pool kp;
-            pthread_t th[16];
-            uint32_t k, failed = 0;
-            sk_ctxjob cj;
-            /* the HIP runtime comes up (0.25-3 s) while the first key sets are built: the context opened here becomes the first
-             * strain's -- every other sk_ctx_create then finds the runtime ready instead of all workers queueing up behind it */
-            {   /* no more devices than there are groups of strains */
-                const uint32_t ng = (ns + sd_group - 1) / sd_group;
-                if ((uint32_t)sd_dev.n > ng) sd_dev.n = ng ? (int)ng : 1;
-            }
-            if (ns) sk_ctxjob_start(&cj, sd_dev.phys[0]);
-            memset(&kp, 0, sizeof kp);
-            kp.jobs = (ks_job *)calloc(ns ? ns : 1, sizeof *kp.jobs);
-            kp.njobs = ns;
-            pthread_mutex_init(&kp.mu, NULL);
-            pthread_cond_init(&kp.cv, NULL);
-            for (k = 0; k < ns; k++) {
-                ks_job *j = &kp.jobs[k];
-                j->p = &p[k]; j->r = paths[4 * k]; j->a = paths[4 * k + 1]; j->o = paths[4 * k + 2]; j->g = paths[4 * k + 3];
-                j->device = sd_dev.phys[sd_dev_of_strain(k)];
-                j->cj = k == 0 ? &cj : NULL;
-            }
-            if (nth > 16) nth = 16;
-            if (nth < 1) nth = 1;
-            if ((uint32_t)nth > ns) nth = (int)ns;
-            for (t = 0; t < nth; t++) if (pthread_create(&th[t], NULL, sd_keyset_pool_thread, &kp)) break;
-            nth = t;
-            if (nth == 0) sd_keyset_pool_thread(&kp);     /* no thread could be started: open them here */
-            for (k = 0; k < ns; k++) {
-                ks_job *j = &kp.jobs[k];
-                pthread_mutex_lock(&kp.mu);
-                while (!j->done) pthread_cond_wait(&kp.cv, &kp.mu);
-                pthread_mutex_unlock(&kp.mu);
-                if (!failed) {
-                    if (j->out_buf && j->out_len) fwrite(j->out_buf, 1, j->out_len, out);
-                    if (j->err_buf && j->err_len) fwrite(j->err_buf, 1, j->err_len, err);
-                    failed = (uint32_t)j->failed;
-                }
-                free(j->out_buf); free(j->err_buf);
-            }
-            for (t = 0; t < nth; t++) pthread_join(th[t], NULL);
-            pthread_mutex_destroy(&kp.mu);
-            pthread_cond_destroy(&kp.cv);
-            free(kp.jobs);
-            if (failed) goto done;
+        {   /* no more devices than there are groups of strains */
+            const uint32_t ng = (ns + sd_group - 1) / sd_group;
+            if ((uint32_t)sd_dev.n > ng) sd_dev.n = ng ? (int)ng : 1;
         }
+        if (sd_open_strains(p, ns, paths, 0, out, err)) goto done;
         if (ns == 0) { status = 0; goto done; }          /* nothing dealt to this rank */
+    } else if (ad) {                                     /* (sd_dev: one device, the one the strains are on) */
+        paths = (char **)calloc((size_t)ns * 4, sizeof *paths);
+        for (s = 0; s < ns; s++) {
+            paths[4 * s + 1] = strdup(ad->a[s]);
+            paths[4 * s + 2] = strdup(ad->o ? ad->o[s] : o);
+            paths[4 * s + 3] = ad->o ? (ad->g && ad->g[s] ? strdup(ad->g[s]) : NULL) : (g ? strdup(g) : NULL);
+        }
+        if (sd_open_strains(p, ns, paths, 1, out, err)) goto done;
     } else {
         p = (sd_prog *)malloc(sizeof *p);
         ns = 1;
-        if (adopt_ctx ? sd_strain_adopt(&p[0], adopt_ctx, adopt_ks, a, g, o, out, err) : sd_strain_open(&p[0], r, a, g, o, device, out, err)) goto done;
+        if (sd_strain_open(&p[0], r, a, g, o, device, out, err)) goto done;
     }
     t_setup = now_s() - t_begin;
     for (s = ns; s-- > 0; ) sd_dev.ctx[sd_dev_of_strain(s)] = p[s].ctx;       /* a context on every device (its first strain's): owner of the device's batches */

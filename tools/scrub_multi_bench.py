@@ -9,10 +9,18 @@
   (c) end to end: `kmer_scrub_count -S` with E2E_STRAINS strains over a plain FASTQ -B list of the same reads, against the
       sum of the E2E_STRAINS single-strain runs, outputs compared byte for byte (md5).
 
-Prints one JSON line.  Environment: READS (10,000,000), E2E_STRAINS (8), WORK (/tmp/sk_scrub_multi_bench)."""
+  (d) with --workflow, instead of (a)-(c): steps 1 to 3 for WORKFLOW_STRAINS cfg5 strains (8; "8,32" for both sizes) over a
+      plain FASTQ -B list, fused -- `kmer_scrub_count -S .. --scrub 0.01 --detect -B <targets>` -- against the chain of
+      three programs: `kmer_scrub_count -S` (gz count tables), `kmer_scrub_filter -l` once per strain, `strain_detect -S`.
+      Every informative list and hit list (decompressed) is compared by md5 in the same run.  Each program runs under its own
+      `timeout -k 10`; the first failure ends the run.
+
+Prints one JSON line.  Environment: READS (10,000,000), E2E_STRAINS (8), WORK (/tmp/sk_scrub_multi_bench), and for (d)
+WORKFLOW_STRAINS (8), TARGET_READS (2,000,000: the -B list of strain_detect, one plain FASTQ)."""
 import hashlib
 import json
 import os
+import shutil
 import subprocess
 import sys
 import time
@@ -39,6 +47,123 @@ def md5(path):
         for blk in iter(lambda: f.read(1 << 24), b""):
             h.update(blk)
     return h.hexdigest()
+
+
+def write_fastq(path, reads):
+    """a record stream of 150 bp reads (151 bytes per record) as a plain FASTQ file"""
+    r2 = reads.reshape(-1, 151)[:, :150]
+    with open(path, "wb") as f:
+        for a in range(0, r2.shape[0], 500_000):
+            blk = r2[a:a + 500_000]
+            rec = np.empty((blk.shape[0], 4 + 151 + 2 + 151), dtype=np.uint8)
+            rec[:, 0:4] = np.frombuffer(b"@rd\n", dtype=np.uint8)
+            rec[:, 4:154] = blk
+            rec[:, 154] = 10
+            rec[:, 155:157] = np.frombuffer(b"+\n", dtype=np.uint8)
+            rec[:, 157:307] = ord("I")
+            rec[:, 307] = 10
+            f.write(rec.tobytes())
+
+
+def md5_any(path):
+    """md5 of the decompressed bytes (gzip by its magic)"""
+    import gzip
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    h = hashlib.md5()
+    with (gzip.open if gz else open)(path, "rb") as f:
+        for blk in iter(lambda: f.read(1 << 24), b""):
+            h.update(blk)
+    return h.hexdigest()
+
+
+def timed(argv, limit_s, what, **kw):
+    """one program under its own time limit; a failure ends the bench (nothing more is started)"""
+    t = time.time()
+    kw.setdefault("stdout", subprocess.PIPE)
+    p = subprocess.run(["timeout", "-k", "10", str(limit_s)] + argv, stderr=subprocess.PIPE, text=True, **kw)
+    if p.returncode != 0:
+        sys.stderr.write(f"{what} failed with status {p.returncode}:\n{p.stderr[-3000:]}\n")
+        sys.exit(1)
+    return time.time() - t, p
+
+
+def workflow():
+    """(d): the fused job against the chain of three programs, outputs compared"""
+    os.makedirs(WORK, exist_ok=True)
+    sizes = [int(x) for x in os.environ.get("WORKFLOW_STRAINS", "8").split(",")]
+    target_reads = int(os.environ.get("TARGET_READS", "2000000"))
+    res = {"reads": READS, "target_reads": target_reads, "read_len": 150, "min_fraction": "0.01", "runs": []}
+    t0 = time.time()
+    genomes = [cfg5.strain(s) for s in range(max(sizes))]
+    reads, bases = synth.make_reads(genomes, READS)
+    fq = os.path.join(WORK, "reads.fq")
+    write_fastq(fq, reads)
+    del reads
+    treads, tbases = synth.make_reads(genomes, target_reads, seed=synth.SEED + 7)
+    tq = os.path.join(WORK, "targets.fq")
+    write_fastq(tq, treads)
+    del treads
+    paths = []
+    for s in range(max(sizes)):
+        p = os.path.join(WORK, f"s{s}.fa")
+        with open(p, "wb") as f:
+            f.write(b">s%d\n" % s + genomes[s].tobytes() + b"\n")
+        paths.append(p)
+    res["setup_s"] = round(time.time() - t0, 1)
+    res["list_gbase"] = round(bases / 1e9, 3)
+    res["target_gbase"] = round(tbases / 1e9, 3)
+    with open(os.path.join(WORK, "A.txt"), "w") as f:
+        f.write(paths[-1] + "\n")
+    with open(os.path.join(WORK, "B.txt"), "w") as f:
+        f.write(fq + "\n")
+    with open(os.path.join(WORK, "T.txt"), "w") as f:
+        f.write(f"SE\t{tq}\n")
+    exe, flt, sd = sk.cli_path(), sk.cli_path("kmer_scrub_filter"), sk.cli_path("strain_detect")
+    lists = ["-A", os.path.join(WORK, "A.txt"), "-B", os.path.join(WORK, "B.txt")]
+    env = dict(os.environ, SK_TIMING="1")
+    for n in sizes:
+        w = os.path.join(WORK, f"n{n}")
+        os.makedirs(w, exist_ok=True)
+        fused_s, chain_s = os.path.join(w, "fused.txt"), os.path.join(w, "chain.txt")
+        with open(fused_s, "w") as f:
+            for s in range(n):
+                f.write(f"{paths[s]}\t{w}/fused{s}.inf\t{w}/fused{s}.kmer_hits.gz\n")
+        with open(chain_s, "w") as f:
+            for s in range(n):
+                f.write(f"{paths[s]}\t{w}/counts{s}.tsv.gz\n")
+        run = {"strains": n}
+        # the fused job: steps 1-3 in one process, the tables of step 1 resident to the end
+        run["fused_s"], p = timed([exe, "-S", fused_s] + lists + ["--scrub", "0.01", "--detect", "-B", os.path.join(WORK, "T.txt")],
+                                  900, "fused -S", env=env)
+        run["fused_timing"] = [l for l in p.stderr.splitlines() if "timing" in l]
+        # the chain: -S count tables (gz), the filter per strain, strain_detect -S
+        run["chain_count_s"], p = timed([exe, "-S", chain_s] + lists, 900, "-S count tables", env=env)
+        run["count_tables_gz_bytes"] = sum(os.path.getsize(f"{w}/counts{s}.tsv.gz") for s in range(n))
+        run["chain_filter_s"] = 0.0
+        for s in range(n):
+            with open(f"{w}/list{s}.txt", "w") as f:
+                f.write(f"{w}/counts{s}.tsv.gz\n")
+            with open(f"{w}/chain{s}.inf", "w") as out:
+                dt, _ = timed([flt, "-l", f"{w}/list{s}.txt", "-m", "0.01"], 600, f"kmer_scrub_filter strain {s}", stdout=out)
+            run["chain_filter_s"] += dt
+        with open(os.path.join(w, "sd.txt"), "w") as f:
+            for s in range(n):
+                f.write(f"{paths[s]}\t{w}/chain{s}.inf\t{w}/chain{s}.kmer_hits.gz\n")
+        run["chain_detect_s"], _ = timed([sd, "-S", os.path.join(w, "sd.txt"), "-B", os.path.join(WORK, "T.txt")], 900, "strain_detect -S")
+        run["chain_s"] = round(run["chain_count_s"] + run["chain_filter_s"] + run["chain_detect_s"], 2)
+        for k in ("fused_s", "chain_count_s", "chain_filter_s", "chain_detect_s"):
+            run[k] = round(run[k], 2)
+        run["speedup"] = round(run["chain_s"] / run["fused_s"], 2)
+        same_inf = all(md5_any(f"{w}/fused{s}.inf") == md5_any(f"{w}/chain{s}.inf") for s in range(n))
+        same_hits = all(md5_any(f"{w}/fused{s}.kmer_hits.gz") == md5_any(f"{w}/chain{s}.kmer_hits.gz") for s in range(n))
+        run["informative_identical"], run["hits_identical"] = same_inf, same_hits
+        run["informative_kmers"] = sum(sum(1 for _ in open(f"{w}/fused{s}.inf")) for s in range(n))
+        res["runs"].append(run)
+        shutil.rmtree(w)
+    os.unlink(fq)
+    os.unlink(tq)
+    print(json.dumps(res))
 
 
 def main():
@@ -143,4 +268,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--workflow" in sys.argv[1:]:
+        workflow()
+    else:
+        main()
