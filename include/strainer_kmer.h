@@ -151,6 +151,17 @@ uint64_t sk_packed_bytes(uint64_t nbytes);
 int sk_pack_stream(const uint8_t *stream, uint64_t nbytes, void *packed, int *odd);
 int sk_scan_pinned_packed(sk_ctx *ctx, const void *packed, uint64_t nbytes, uint32_t col, uint64_t *ticket);
 int sk_scan_device_packed(sk_ctx *ctx, const void *dev_packed, uint64_t nbytes, uint32_t col);   /* the packed batch already in device memory (4-byte aligned) */
+/* ONE upload, n COUNT scans (new: several union tables fed by one decode of the lists, kmer_scrub_count -S).  The batch crosses
+ * the link once, into ctx[0]'s staging ring under ctx[0]'s ticket; then every ctx[i] (a strain's context or a union's,
+ * sk_union_context) scans it into its own column `col`, as sk_scan_pinned[_packed] would.  The staging buffer is reused only
+ * after all n scans have read it, so sk_sync(ctx[0]), sk_pinned_free(ctx[0], ..) and sk_ticket_wait(ctx[0], *ticket) speak for
+ * the whole group.  Counts equal n separate sk_scan_pinned[_packed] calls, bit for bit.  Refused (errors in ctx[0]): contexts
+ * on different devices, a context without a table or count columns, `col` out of range for any of them.  One caller at a time
+ * for the whole group. */
+int sk_scan_pinned_many(sk_ctx *const *ctx, uint32_t n, const uint8_t *pinned, uint64_t nbytes, uint32_t col, uint64_t *ticket);
+int sk_scan_pinned_packed_many(sk_ctx *const *ctx, uint32_t n, const void *packed, uint64_t nbytes, uint32_t col, uint64_t *ticket);
+/* Free and total HBM of the context's device (hipMemGetInfo). */
+int sk_device_memory(sk_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 
 /* Same, for a batch already resident in HBM (device pointer). */
 int sk_scan_device(sk_ctx *ctx, const void *dev_stream, uint64_t nbytes, uint32_t col);
@@ -346,6 +357,13 @@ int skh_scan_list(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t
  * scan_list_sharded).  skh_scan_list_uncut = skh_scan_list over the plan without byte-range pieces (SK_NO_SPLIT=1). */
 int skh_scan_list_uncut(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col,
                         FILE *progress, FILE *err, uint32_t rank, uint32_t world, uint64_t *bases);
+/* skh_scan_list into n contexts on one device over ONE decode of the list (new: kmer_scrub_count -S feeds every resident union
+ * from one walk): each chunk goes up once and is scanned into column `col` of every ctx[i] (sk_scan_pinned[_packed]_many; packed
+ * or bytes is decided once per chunk, for all of them).  A cut that does not hold puts back the column of EVERY context before the
+ * uncut rescan.  Progress lines, messages and *bases are written once; the communicator (world > 1) is ctx[0]'s.  n = 1 is
+ * skh_scan_list. */
+int skh_scan_list_many(sk_ctx *const *ctx, uint32_t n, const char *list_path, const char *skip, uint32_t col,
+                       FILE *progress, FILE *err, uint32_t rank, uint32_t world, uint64_t *bases);
 /* Hash of the work plan skh_scan_list(list, skip, .., world) follows (items, byte ranges, file sizes, owners): a function
  * of the list, the files and `world` (and of SK_SPLIT_BYTES / SK_NO_SPLIT) only, never of a rank's thread count.  With the
  * library's own communicator skh_scan_list compares it across ranks itself (SK_E_PLAN); a caller that reduces the counters
@@ -367,10 +385,11 @@ int skh_kmer_scrub_count_main(int argc, char **argv, FILE *out, FILE *err);
 /* kmer_scrub_count -S <strains file> -A <list> -B <list> [-C <list>] [-p <progress>] (no -r; new): every line of the strains
  * file is  <reference genome> TAB <outfile>  (empty lines and lines starting with '#' are skipped), and every outfile gets
  * exactly what `kmer_scrub_count -r <genome> -A .. -B .. [-C ..]` writes on stdout (gzip when its name ends in .gz).  Up to
- * SK_UNION_MAX strains share one union table and one pass over the lists (sk_union_count_enable / sk_union_counts_fold);
- * a -C line equal to a strain's genome is taken back from that strain alone.  Environment: SK_SCRUB_GROUP=1..32 (strains
- * per union), SK_SCRUB_NO_UNION=1 (a pass per strain); with WORLD_SIZE/RANK the strain lines are dealt to the ranks
- * round-robin (no collective).  With "--scrub <min_fraction> [--independent] --detect <strain_detect arguments>" a line is
+ * SK_UNION_MAX strains share one union table (sk_union_count_enable / sk_union_counts_fold), and all the unions that fit in
+ * HBM are fed by ONE decode of the lists (skh_scan_list_many); a -C line equal to a strain's genome is taken back from that
+ * strain alone.  Environment: SK_SCRUB_GROUP=1..32 (strains per union), SK_SCRUB_UNIONS=n (at most n unions per decode; 1 =
+ * a decode per union), SK_SCRUB_HBM_MB=m (the free HBM the residency plan assumes), SK_SCRUB_NO_UNION=1 (a pass per strain);
+ * with WORLD_SIZE/RANK the strain lines are dealt to the ranks round-robin (no collective).  With "--scrub <min_fraction> [--independent] --detect <strain_detect arguments>" a line is
  * <genome> TAB <informative outfile> TAB <hits outfile> [TAB <-g list>]: the informative outfile gets what `-r <genome> ...
  * --scrub f [--independent]` prints (step 2 on the resident counts), and the strains go on into step 3 (and 4) together through
  * skh_strain_detect_resident_many.  --scrub without --detect is refused.  Returns the exit status. */

@@ -97,6 +97,7 @@ struct sk_ctx {
     int          stage_next;
     hipStream_t  copy_stream;          // sk_scan_pinned's uploads: the next chunk's copy runs while this chunk is scanned
     hipEvent_t   copied[64];           // ring of "host buffer of ticket t has been read" events
+    hipEvent_t   read_done;            // sk_scan_pinned_many: this context's scan of another context's staging buffer is done
     uint64_t     tickets;              // tickets issued so far
     // flags: [0] wide windows seen in the current batch, [1] table build errors
     uint32_t    *d_flags;
@@ -259,6 +260,7 @@ extern "C" void sk_ctx_destroy(sk_ctx *c)
     for (hipEvent_t e : c->ev) hipEventDestroy(e);
     for (hipEvent_t e : c->ev_free) hipEventDestroy(e);
     for (int i = 0; i < 64; i++) if (c->copied[i]) hipEventDestroy(c->copied[i]);
+    if (c->read_done) hipEventDestroy(c->read_done);
     if (c->own_batch) sk_batch_destroy(c->own_batch);
     hipFree(c->t_tally); hipFree(c->t_hits); hipFree(c->t_compact);
     hipFree(c->p_bins); hipFree(c->p_binn); hipFree(c->p_cand);
@@ -1068,7 +1070,7 @@ extern "C" int sk_union_create(sk_ctx *const *members, uint32_t n, uint32_t type
     int rc = sk_ctx_create(&u->uc, first->device);
     if (rc != SK_OK) { delete u; return rc; }
     sk_ctx *c = u->uc;
-#define SK_U(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { sk_fail(first, SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); sk_union_destroy(u); return SK_E_HIP; } } while (0)
+#define SK_U(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { sk_fail(first, SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); (void)hipGetLastError(); sk_union_destroy(u); return SK_E_HIP; } } while (0)
     const uint32_t nrows = (uint32_t)rows;
     uint32_t lg = 10;
     while (((uint64_t)1 << lg) * (uint64_t)first->table_load_pct < rows * 100ull && lg < 31) lg++;
@@ -1282,6 +1284,10 @@ extern "C" int sk_union_sync(sk_union *u)
 
 // ---- COUNT on a union (kmer_scrub_count -S): the union's context is scanned like one big strain into a count column of global rows;
 // sk_union_counts_fold then moves each key's count to its slot row and hands it to the members' own columns.
+// (an allocation that fails must not leave its error behind for a later hipGetLastError: kmer_scrub_count -S plans with it -- the
+// union is destroyed and the lists are decoded for the unions made so far)
+#define SK_UNION_MALLOC(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (void)hipGetLastError(); \
+    return sk_fail((ctx), SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
 extern "C" int sk_union_count_enable(sk_union *u, uint32_t ncols)
 {
     if (!u || ncols < 1 || ncols > 16) return SK_E_ARG;
@@ -1290,17 +1296,17 @@ extern "C" int sk_union_count_enable(sk_union *u, uint32_t ncols)
     SK_HIP(c, hipSetDevice(c->device));
     const uint32_t nrows = c->nrows;
     const uint64_t uslots = (uint64_t)1 << c->slots_log2;
-    SK_HIP(c, hipMalloc((void **)&u->d_canon, (size_t)nrows * 4));
+    SK_UNION_MALLOC(c, hipMalloc((void **)&u->d_canon, (size_t)nrows * 4));
     for (uint32_t s = 0; s < u->n; s++) {                      // (sk_union_create's own canon[] went with its masks)
         const sk_ctx *m = u->mem[s];
         hipLaunchKernelGGL(sk_union_canon_rows, dim3(4096), dim3(256), 0, c->stream, (const sk_u4 *)m->d_keys, (uint64_t)1 << m->slots_log2,
                            u->base[s], (const sk_u4 *)c->d_keys, (uint32_t)(uslots - 1), u->d_canon);
     }
     const size_t cbytes = (size_t)nrows * ncols * 4;
-    SK_HIP(c, hipMalloc((void **)&c->d_counts, cbytes));
+    SK_UNION_MALLOC(c, hipMalloc((void **)&c->d_counts, cbytes));
     SK_HIP(c, hipMemsetAsync(c->d_counts, 0, cbytes, c->stream));
-    SK_HIP(c, hipMalloc((void **)&c->d_diff, ((size_t)nrows + 2) * 4));
-    SK_HIP(c, hipMalloc((void **)&c->d_diff_sums, ((size_t)nrows / SK_DIFF_PER_BLOCK + 2) * 4));
+    SK_UNION_MALLOC(c, hipMalloc((void **)&c->d_diff, ((size_t)nrows + 2) * 4));
+    SK_UNION_MALLOC(c, hipMalloc((void **)&c->d_diff_sums, ((size_t)nrows / SK_DIFF_PER_BLOCK + 2) * 4));
     SK_HIP(c, hipMemsetAsync(c->d_diff, 0, ((size_t)nrows + 2) * 4, c->stream));
     c->diff_col = -1;
     c->ncols = ncols;
@@ -1460,15 +1466,15 @@ extern "C" int sk_pinned_free(sk_ctx *c, void *p)
     return rc;
 }
 
-// Like sk_scan_stream, but `pinned` (from sk_pinned_alloc, at most 64 MiB - 64 bytes) is DMA-read in
-// place: the caller must leave it alone until sk_ticket_wait(*ticket) returns.
-extern "C" int sk_scan_pinned(sk_ctx *c, const uint8_t *pinned, uint64_t nbytes, uint32_t col, uint64_t *ticket)
+// One upload, n scans: `src` (copy_bytes of it) goes up ONCE, on cs[0]'s copy stream into cs[0]'s staging ring, and every context
+// scans that device buffer on its own stream into its column `col` (packed: the batch is in sk_pack_stream's form, nbytes the length of
+// the byte stream).  The buffer may be rewritten only after ALL n scans have read it, so cs[0]'s stream waits for each other context's
+// scan before it records stage_done[b]: sk_sync / sk_pinned_free / sk_ticket_wait on cs[0] then stand for the whole group.  Callers
+// have checked the contexts (same device, a table, count columns, col in range).
+static int sk_scan_pinned_n(sk_ctx *const *cs, uint32_t n, const void *src, uint64_t nbytes, uint64_t copy_bytes, bool packed,
+                            uint32_t col, uint64_t *ticket)
 {
-    if (!c || (!pinned && nbytes) || !ticket) return SK_E_ARG;
-    if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
-    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
-    if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
-    if (nbytes > SK_STAGE_BYTES - 64) return sk_fail(c, SK_E_ARG, "pinned batch larger than the staging buffer");
+    sk_ctx *const c = cs[0];
     SK_HIP(c, hipSetDevice(c->device));
     int rc = sk_stage_init(c);
     if (rc) return rc;
@@ -1483,14 +1489,36 @@ extern "C" int sk_scan_pinned(sk_ctx *c, const uint8_t *pinned, uint64_t nbytes,
     // not wait for the device at all -- its back-pressure is the ticket of its own two buffers.  (Round 4: copy and scan took
     // turns on one stream, 0.65 + 0.05 ms a chunk, and the submit waited on the host for the buffer two chunks back.)
     SK_HIP(c, hipStreamWaitEvent(c->copy_stream, c->stage_done[b], 0));       // (never recorded yet = done)
-    if (nbytes) SK_HIP(c, hipMemcpyAsync(c->d_stage[b], pinned, nbytes, hipMemcpyHostToDevice, c->copy_stream));
+    if (copy_bytes) SK_HIP(c, hipMemcpyAsync(c->d_stage[b], src, copy_bytes, hipMemcpyHostToDevice, c->copy_stream));
     SK_HIP(c, hipEventRecord(ev, c->copy_stream));
-    SK_HIP(c, hipStreamWaitEvent(c->stream, ev, 0));                          // (before anything else: sk_sync / sk_pinned_free wait on c->stream alone)
-    rc = sk_launch_scan(c, c->d_stage[b], nbytes, 0, col);
-    if (rc) return rc;
+    const uint8_t *const d = c->d_stage[b];
+    const void *const inv = packed ? d + ((nbytes + 15u) >> 4) * 4u : NULL;
+    for (uint32_t i = 0; i < n; i++) {
+        sk_ctx *const m = cs[i];
+        SK_HIP(c, hipStreamWaitEvent(m->stream, ev, 0));                       // (before anything else: sk_sync / sk_pinned_free wait on the stream alone)
+        rc = sk_launch_scan(m, d, nbytes, 0, col, NULL, inv);
+        if (rc) return m == c ? rc : sk_fail(c, rc, "context %u: %s", i, m->err);
+        if (m != c) {                                                          // (cs[0]'s own scan is on its stream already)
+            if (!m->read_done) SK_HIP(c, hipEventCreateWithFlags(&m->read_done, hipEventDisableTiming));
+            SK_HIP(c, hipEventRecord(m->read_done, m->stream));
+            SK_HIP(c, hipStreamWaitEvent(c->stream, m->read_done, 0));
+        }
+    }
     SK_HIP(c, hipEventRecord(c->stage_done[b], c->stream));
     *ticket = t;
     return SK_OK;
+}
+
+// Like sk_scan_stream, but `pinned` (from sk_pinned_alloc, at most 64 MiB - 64 bytes) is DMA-read in
+// place: the caller must leave it alone until sk_ticket_wait(*ticket) returns.
+extern "C" int sk_scan_pinned(sk_ctx *c, const uint8_t *pinned, uint64_t nbytes, uint32_t col, uint64_t *ticket)
+{
+    if (!c || (!pinned && nbytes) || !ticket) return SK_E_ARG;
+    if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
+    if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
+    if (nbytes > SK_STAGE_BYTES - 64) return sk_fail(c, SK_E_ARG, "pinned batch larger than the staging buffer");
+    return sk_scan_pinned_n(&c, 1, pinned, nbytes, nbytes, false, col, ticket);
 }
 
 // The same for a batch the host has PACKED (sk_pack_stream, sk_host.c: per 16-byte chunk of the byte stream the 32-bit code word and
@@ -1506,23 +1534,51 @@ extern "C" int sk_scan_pinned_packed(sk_ctx *c, const void *packed, uint64_t nby
     if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
     const uint64_t nch = (nbytes + 15u) >> 4;
     if (nch * 6u > SK_STAGE_BYTES) return sk_fail(c, SK_E_ARG, "packed batch larger than the staging buffer");
+    return sk_scan_pinned_n(&c, 1, packed, nbytes, nch * 6u, true, col, ticket);
+}
+
+// ONE upload scanned into n contexts (several unions fed by one decode of the lists: kmer_scrub_count -S).  Errors go to ctx[0].
+static int sk_many_check(sk_ctx *const *cs, uint32_t n, uint32_t col)
+{
+    sk_ctx *const c = cs[0];
+    for (uint32_t i = 0; i < n; i++) {
+        const sk_ctx *m = cs[i];
+        if (!m) return sk_fail(c, SK_E_ARG, "context %u is NULL", i);
+        if (m->device != c->device) return sk_fail(c, SK_E_ARG, "context %u is on device %d, context 0 on %d: one upload serves one device", i, m->device, c->device);
+        if (!m->d_keys) return sk_fail(c, SK_E_STATE, "context %u: no table loaded", i);
+        if (!m->d_counts) return sk_fail(c, SK_E_STATE, "context %u: no count columns (a union's context needs sk_union_count_enable)", i);
+        if (col >= m->ncols) return sk_fail(c, SK_E_ARG, "context %u: column %u out of range", i, col);
+    }
+    return SK_OK;
+}
+
+extern "C" int sk_scan_pinned_many(sk_ctx *const *ctx, uint32_t n, const uint8_t *pinned, uint64_t nbytes, uint32_t col, uint64_t *ticket)
+{
+    if (!ctx || n < 1 || !ctx[0] || (!pinned && nbytes) || !ticket) return SK_E_ARG;
+    int rc = sk_many_check(ctx, n, col);
+    if (rc) return rc;
+    if (nbytes > SK_STAGE_BYTES - 64) return sk_fail(ctx[0], SK_E_ARG, "pinned batch larger than the staging buffer");
+    return sk_scan_pinned_n(ctx, n, pinned, nbytes, nbytes, false, col, ticket);
+}
+
+extern "C" int sk_scan_pinned_packed_many(sk_ctx *const *ctx, uint32_t n, const void *packed, uint64_t nbytes, uint32_t col, uint64_t *ticket)
+{
+    if (!ctx || n < 1 || !ctx[0] || (!packed && nbytes) || !ticket) return SK_E_ARG;
+    int rc = sk_many_check(ctx, n, col);
+    if (rc) return rc;
+    const uint64_t nch = (nbytes + 15u) >> 4;
+    if (nch * 6u > SK_STAGE_BYTES) return sk_fail(ctx[0], SK_E_ARG, "packed batch larger than the staging buffer");
+    return sk_scan_pinned_n(ctx, n, packed, nbytes, nch * 6u, true, col, ticket);
+}
+
+// free and total HBM of the context's device (kmer_scrub_count -S plans how many unions one decode of the lists can feed)
+extern "C" int sk_device_memory(sk_ctx *c, uint64_t *free_bytes, uint64_t *total_bytes)
+{
+    if (!c || !free_bytes || !total_bytes) return SK_E_ARG;
+    size_t f = 0, t = 0;
     SK_HIP(c, hipSetDevice(c->device));
-    int rc = sk_stage_init(c);
-    if (rc) return rc;
-    const uint64_t t = c->tickets++;
-    hipEvent_t &ev = c->copied[t & 63u];
-    if (!ev) SK_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming | (getenv("SK_SYNC") ? hipEventBlockingSync : 0u)));
-    else SK_HIP(c, hipEventSynchronize(ev));                     // ring slot of ticket t-64
-    const int b = c->stage_next;
-    c->stage_next = (b + 1) % SK_NSTAGE;
-    SK_HIP(c, hipStreamWaitEvent(c->copy_stream, c->stage_done[b], 0));
-    if (nch) SK_HIP(c, hipMemcpyAsync(c->d_stage[b], packed, nch * 6u, hipMemcpyHostToDevice, c->copy_stream));
-    SK_HIP(c, hipEventRecord(ev, c->copy_stream));
-    SK_HIP(c, hipStreamWaitEvent(c->stream, ev, 0));
-    rc = sk_launch_scan(c, c->d_stage[b], nbytes, 0, col, NULL, c->d_stage[b] + nch * 4u);
-    if (rc) return rc;
-    SK_HIP(c, hipEventRecord(c->stage_done[b], c->stream));
-    *ticket = t;
+    SK_HIP(c, hipMemGetInfo(&f, &t));
+    *free_bytes = f; *total_bytes = t;
     return SK_OK;
 }
 

@@ -850,12 +850,14 @@ typedef struct { char *path; uint64_t a, b, size; uint32_t line; int ranged; } s
 typedef struct { char *text; int skipped; long end; } list_line;
 
 typedef struct {
-    sk_ctx         *ctx;
+    sk_ctx         *ctx;               /* the context whose staging ring, tickets and page-locked buffers the walk uses: ctxs[0] ... */
+    sk_ctx *const  *ctxs;              /* ... and every context a chunk is scanned into (skh_scan_list_many: one upload, nctx scans) */
+    uint32_t        nctx;
     uint32_t        col;
     int             pipe;              /* fewer files than cores: each file's inflate gets a helper thread (> 1: that many) */
     int             gpu_inflate;       /* SK_GPU_INFLATE=1: .gz items go through the device-side decoder first (experimental) */
     int             dev_workers, worker_ids;   /* ... on this many EXTRA threads (SK_GPU_INFLATE_WORKERS, default 4), which mostly wait for the device */
-    pthread_mutex_t submit_mu;         /* sk_scan_stream is one-caller-at-a-time per context */
+    pthread_mutex_t submit_mu;         /* sk_scan_stream is one-caller-at-a-time per context (per group of contexts: sk_scan_pinned_many) */
     pthread_mutex_t queue_mu;
     scan_item      *item;              /* work list of this call (what this rank scans), in list order */
     uint32_t        nitem, next;
@@ -912,6 +914,20 @@ static uint64_t pool_chunk_bytes(void)
 }
 #define POOL_CHUNK pool_chunk_bytes()
 
+/* The host-only test builds link this file against device doubles that have no many-context scans; in the library they are
+ * always there (sk_device.hip), and a walk into several contexts is refused without them (skh_scan_list_many). */
+#pragma weak sk_scan_pinned_many
+#pragma weak sk_scan_pinned_packed_many
+
+/* a chunk to every context of the walk, under submit_mu: with several, it goes up once and is scanned into each of them */
+static int pool_submit(scan_pool *p, const void *buf, uint64_t nbytes, int packed, uint64_t *ticket)
+{
+    if (p->nctx > 1)
+        return packed ? sk_scan_pinned_packed_many(p->ctxs, p->nctx, buf, nbytes, p->col, ticket)
+                      : sk_scan_pinned_many(p->ctxs, p->nctx, (const uint8_t *)buf, nbytes, p->col, ticket);
+    return packed ? sk_scan_pinned_packed(p->ctx, buf, nbytes, p->col, ticket) : sk_scan_pinned(p->ctx, (const uint8_t *)buf, nbytes, p->col, ticket);
+}
+
 static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
 {
     scan_worker *w = (scan_worker *)user;
@@ -933,7 +949,7 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
             if (!odd) {
                 pthread_mutex_lock(&w->pool->submit_mu);
                 t1 = w->pool->timing ? now_s() : 0.0;
-                rc = sk_scan_pinned_packed(w->pool->ctx, w->pk[i], nbytes, w->pool->col, &w->pk_ticket[i]);
+                rc = pool_submit(w->pool, w->pk[i], nbytes, 1, &w->pk_ticket[i]);
                 pthread_mutex_unlock(&w->pool->submit_mu);
                 if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; w->npacked++; }
                 w->pk_used[i] = rc == SK_OK;
@@ -944,7 +960,7 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
     }
     pthread_mutex_lock(&w->pool->submit_mu);
     t1 = w->pool->timing ? now_s() : 0.0;
-    rc = sk_scan_pinned(w->pool->ctx, chunk, nbytes, w->pool->col, &w->ticket[w->cur]);
+    rc = pool_submit(w->pool, chunk, nbytes, 0, &w->ticket[w->cur]);
     pthread_mutex_unlock(&w->pool->submit_mu);
     if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; }
     w->used[w->cur] = 1;
@@ -1435,15 +1451,16 @@ typedef struct { uint64_t *hash; uint32_t *owner; uint32_t cap, *nlines; } plan_
  * set-up for this list failed") and ONE after (first unreadable line, "a cut failed", "a device error"), each a max
  * all-reduce of a few words (sk_comm_max_u64), and every rank returns the SAME status, so the callers' decisions
  * (skip the remaining lists, go to the big all-reduce) are the same everywhere. */
-typedef struct { uint32_t *snap; long prog_at; int armed; } split_guard;
+typedef struct { uint32_t **snap; uint32_t nsnap; long prog_at; int armed; } split_guard;     /* snap[i]: ctxs[i]'s column */
 
 #define LIST_FAIL_OPEN  1u    /* agreement before the scan: this rank could not read the list itself */
 #define LIST_FAIL_GUARD 2u    /*                            ... could not copy its column (no memory, device error) */
 
-static int scan_list_once(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
+static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                           FILE *err, uint32_t rank, uint32_t world, uint64_t *bases, int plan_only, const plan_report *report,
                           int no_split, split_guard *guard)
 {
+    sk_ctx *const ctx = ctxs ? ctxs[0] : NULL;       /* (plan only: no context) */
     FILE *fp = fopen(list_path, "r");
     char *line = NULL, *nl;
     size_t cap = 0;
@@ -1470,6 +1487,8 @@ static int scan_list_once(sk_ctx *ctx, const char *list_path, const char *skip, 
     pool.timing = getenv("SK_TIMING") != NULL;
     { const char *e = getenv("SK_LIST_PACK"); pool.pack = e && e[0] == '0' ? 0 : e && e[0] == '2' ? 2 : 1; }      /* (0: never, 2: always -- tests --, default: plain-text items' chunks once the scan is bound by the link) */
     pool.ctx = ctx;
+    pool.ctxs = ctxs;
+    pool.nctx = ctxs ? nctx : 0;
     pool.col = col;
     pthread_mutex_init(&pool.submit_mu, NULL);
     pthread_mutex_init(&pool.queue_mu, NULL);
@@ -1565,13 +1584,24 @@ static int scan_list_once(sk_ctx *ctx, const char *list_path, const char *skip, 
             }
     }
     for (i = 0; i < nall; i++) any_ranged |= all[i].ranged;
-    if (guard && ctx && !plan_only && !no_split && coordinated && any_ranged && sk_table_rows(ctx)) {
-        /* pieces ahead (somewhere in the plan: on every rank, then): keep what a failed cut would spoil */
-        guard->snap = (uint32_t *)malloc((size_t)sk_table_rows(ctx) * sizeof(uint32_t));
-        if (guard->snap && sk_counts_fetch(ctx, col, guard->snap) == SK_OK) {
-            guard->prog_at = progress ? (fflush(progress), ftell(progress)) : -1;
-            guard->armed = 1;
-        } else local_fail |= LIST_FAIL_GUARD;
+    {
+        uint32_t rows_any = 0, c;
+        for (c = 0; ctx && c < nctx; c++) rows_any |= sk_table_rows(ctxs[c]);
+        if (guard && ctx && !plan_only && !no_split && coordinated && any_ranged && rows_any) {
+            /* pieces ahead (somewhere in the plan: on every rank, then): keep what a failed cut would spoil -- the column of
+             * every context the chunks go to */
+            int ok = (guard->snap = (uint32_t **)calloc(nctx, sizeof *guard->snap)) != NULL;
+            if (ok) guard->nsnap = nctx;
+            for (c = 0; ok && c < nctx; c++) {
+                if (!sk_table_rows(ctxs[c])) continue;
+                guard->snap[c] = (uint32_t *)malloc((size_t)sk_table_rows(ctxs[c]) * sizeof(uint32_t));
+                ok = guard->snap[c] && sk_counts_fetch(ctxs[c], col, guard->snap[c]) == SK_OK;
+            }
+            if (ok) {
+                guard->prog_at = progress ? (fflush(progress), ftell(progress)) : -1;
+                guard->armed = 1;
+            } else local_fail |= LIST_FAIL_GUARD;
+        }
     }
     if (ctx && !plan_only) {                            /* (a world of one with a communicator -- SK_FORCE_COMM -- takes the same road: tests) */
         /* The agreement before the scan.  Local settings that change the plan (SK_SPLIT_BYTES, SK_NO_SPLIT) or a file whose
@@ -1724,20 +1754,24 @@ static int scan_list_once(sk_ctx *ctx, const char *list_path, const char *skip, 
     return pool.rc;
 }
 
-static int scan_list_impl(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
+static int scan_list_impl(sk_ctx *const *ctxs, uint32_t nctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                           FILE *err, uint32_t rank, uint32_t world, uint64_t *bases, int plan_only, const plan_report *report, int no_split)
 {
-    split_guard guard = {NULL, -1, 0};
-    int rc = scan_list_once(ctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, no_split, &guard);
+    split_guard guard = {NULL, 0, -1, 0};
+    uint32_t c;
+    int rc = scan_list_once(ctxs, nctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, no_split, &guard);
     if (rc == SK_E_SPLIT && guard.armed) {               /* (armed on every rank of a coordinated run, or on none) */
-        rc = sk_counts_set(ctx, col, guard.snap);
+        rc = SK_OK;
+        for (c = 0; rc == SK_OK && c < guard.nsnap; c++)  /* every context's column back */
+            if (guard.snap[c] && (rc = sk_counts_set(ctxs[c], col, guard.snap[c])) != SK_OK && err)
+                fprintf(err, "kmer_scrub_count: could not put the counters back: %s (%s)\n", sk_strerror(rc), sk_last_error(ctxs[c]));
         if (rc == SK_OK && progress && guard.prog_at >= 0 && fflush(progress) == 0 && ftruncate(fileno(progress), (off_t)guard.prog_at) == 0)
             fseek(progress, guard.prog_at, SEEK_SET);
-        if (rc != SK_OK && err) fprintf(err, "kmer_scrub_count: could not put the counters back: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx));
         if (getenv("SK_TIMING") && err && rc == SK_OK) fprintf(err, "kmer_scrub_count timing: a cut of %s did not hold; the list is scanned again uncut\n", list_path);
         /* the second scan opens with an agreement too: a rank whose restore failed says so there and everybody leaves */
-        rc = scan_list_once(ctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, rc == SK_OK ? 1 : 2, NULL);
+        rc = scan_list_once(ctxs, nctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, rc == SK_OK ? 1 : 2, NULL);
     }
+    for (c = 0; c < guard.nsnap; c++) free(guard.snap[c]);
     free(guard.snap);
     return rc;
 }
@@ -1745,27 +1779,35 @@ static int scan_list_impl(sk_ctx *ctx, const char *list_path, const char *skip, 
 int skh_scan_list(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                   FILE *err, uint32_t rank, uint32_t world, uint64_t *bases)
 {
-    return scan_list_impl(ctx, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 0);
+    return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 0);
+}
+
+int skh_scan_list_many(sk_ctx *const *ctx, uint32_t n, const char *list_path, const char *skip, uint32_t col, FILE *progress,
+                       FILE *err, uint32_t rank, uint32_t world, uint64_t *bases)
+{
+    if (!ctx || n < 1) return SK_E_ARG;
+    if (n > 1 && (!sk_scan_pinned_many || !sk_scan_pinned_packed_many)) return SK_E_STATE;
+    return scan_list_impl(ctx, n, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 0);
 }
 
 int skh_scan_list_uncut(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                         FILE *err, uint32_t rank, uint32_t world, uint64_t *bases)
 {
-    return scan_list_impl(ctx, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 1);
+    return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 1);
 }
 
 int skh_list_plan_hash(const char *list_path, const char *skip, uint32_t world, uint64_t *hash)
 {
     plan_report rp = {hash, NULL, 0, NULL};
     if (!list_path || !hash) return SK_E_ARG;
-    return scan_list_impl(NULL, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0);
+    return scan_list_impl(NULL, 0, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0);
 }
 
 int skh_list_plan_owners(const char *list_path, const char *skip, uint32_t world, uint32_t *owner, uint32_t cap, uint32_t *nlines)
 {
     plan_report rp = {NULL, owner, cap, nlines};
     if (!list_path || !nlines || (cap && !owner)) return SK_E_ARG;
-    return scan_list_impl(NULL, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0);
+    return scan_list_impl(NULL, 0, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0);
 }
 
 /* =========================================================================================

@@ -8,6 +8,14 @@
  * members it names (u32 wrap makes -= after += exact).  A strain the union cannot hold (byte-string keys, no text stage) gets a
  * pass of its own through its own context, as the single-strain program would run it.
  *
+ * More strains than one union holds make several unions, and the lists are decoded ONCE for all of them: every union is made
+ * first, as many as fit in HBM next to the strains' own tables (an estimate of each union's bytes against the free memory less a
+ * reserve; SK_SCRUB_HBM_MB stands in for the free memory, SK_SCRUB_UNIONS caps the unions per decode, 1 = one decode per union
+ * as before), then one walk of -A, -B and -C (skh_scan_list_many) uploads each chunk once and scans it into every union, and
+ * each union folds after each list.  A union that cannot be made next to the others closes the set -- nothing has been scanned
+ * into it yet -- and the remaining groups get a decode of their own.  Outfiles, stderr and the progress file are what one pass
+ * per union wrote; the -C "skipping" lines come union by union as before.
+ *
  * With --scrub <min_fraction> [--independent] --detect <strain_detect arguments> each strain goes on into step 2 on its resident
  * counts (skh_scrub_filter_resident, sk_filter on the device) and its line names an informative outfile and a hit list instead of
  * a count table; then the strains go on together into step 3 (and 4) on the same resident tables: skh_strain_detect_resident_many,
@@ -140,15 +148,16 @@ static void *sm_print_worker(void *arg)
 }
 
 /* one strain, its own pass: what the single-strain program does (src/kmer_scrub_count.c:87-99) */
-static int sm_single_pass(sm_strain *s, const char *A, const char *B, const char *C, FILE *progress, FILE *err)
+static int sm_single_pass(sm_strain *s, const char *A, const char *B, const char *C, FILE *progress, FILE *err, uint64_t *bases)
 {
-    if (skh_scan_list(s->ctx, A, NULL, 1, progress, err, 0, 1, NULL) != SK_OK) return 1;
-    if (skh_scan_list(s->ctx, B, NULL, 2, progress, err, 0, 1, NULL) != SK_OK) return 1;
-    if (C && skh_scan_list(s->ctx, C, s->genome, 3, progress, err, 0, 1, NULL) != SK_OK) return 1;
+    if (skh_scan_list(s->ctx, A, NULL, 1, progress, err, 0, 1, bases) != SK_OK) return 1;
+    if (skh_scan_list(s->ctx, B, NULL, 2, progress, err, 0, 1, bases) != SK_OK) return 1;
+    if (C && skh_scan_list(s->ctx, C, s->genome, 3, progress, err, 0, 1, bases) != SK_OK) return 1;
     return 0;
 }
 
 #define SM_FALLBACK 2
+#define SM_LATER    3
 
 static int sm_fold(sk_union *u, uint32_t col, uint32_t mask, int subtract, FILE *err)
 {
@@ -157,63 +166,100 @@ static int sm_fold(sk_union *u, uint32_t col, uint32_t mask, int subtract, FILE 
     return rc;
 }
 
-/* up to SK_UNION_MAX strains, one pass over the lists through their union table.  SM_FALLBACK: the union could not be made
- * (SK_E_STATE: a member it cannot hold) -- nothing was scanned, the caller runs the strains one by one */
-static int sm_union_pass(sm_strain **g, uint32_t n, const char *A, const char *B, const char *C, FILE *progress, FILE *err,
-                         double *fold_ms)
+/* a union of up to SK_UNION_MAX strains with its count column, resident while one decode of the lists feeds it */
+typedef struct { sk_union *u; sm_strain **g; uint32_t n; } sm_union;
+
+static uint32_t sm_all(uint32_t n) { return n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u; }
+
+/* What a union of these strains will hold in HBM (sk_union_create + sk_union_count_enable): slots at half
+ * load, keys, masks, the row map, the count column and its difference array, the two filter levels, the texts and their rank maps,
+ * and the staging ring of its -C rescans.  An estimate from the layout, not a measurement. */
+static uint64_t sm_union_bytes(sm_strain *const *g, uint32_t n)
+{
+    uint64_t rows = 0, bases = 0, slots = 1024, g2 = 4096;
+    uint32_t k;
+    for (k = 0; k < n; k++) { rows += g[k]->ks.nrows; bases += ((uint64_t)g[k]->ks.text_bases + 63u) / 64u * 64u + 64u; }
+    while (slots < 2 * rows) slots <<= 1;
+    while (g2 < rows * 32) g2 <<= 1;
+    return slots * 16 + rows * 33 + g2 / 8 + bases / 2 + (128ull << 20);
+}
+
+/* the union of one group with its count column.  SM_FALLBACK: a member it cannot hold (SK_E_STATE) -- the caller runs the strains
+ * one by one.  SM_LATER: it did not fit next to the unions already made (`others`): nothing is lost, no list has been scanned into
+ * them yet -- the caller decodes the lists for those and makes this one again afterwards */
+static int sm_union_make(sm_strain **g, uint32_t n, int others, sk_union **out, FILE *err)
 {
     sk_ctx *m[SK_UNION_MAX];
     sk_union *u = NULL;
-    sk_ctx *uc;
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u;
     uint32_t k;
-    int rc, status = 1;
-    double t;
+    int rc;
+    *out = NULL;
     for (k = 0; k < n; k++) m[k] = g[k]->ctx;
     rc = sk_union_create(m, n, 0, 0, &u);
     if (rc == SK_E_STATE) return SM_FALLBACK;
-    if (rc != SK_OK) { fprintf(err, "kmer_scrub_count: union table failed: %s (%s)\n", sk_strerror(rc), sk_last_error(m[0])); return 1; }
+    if (rc != SK_OK) {
+        if (others) return SM_LATER;
+        fprintf(err, "kmer_scrub_count: union table failed: %s (%s)\n", sk_strerror(rc), sk_last_error(m[0]));
+        return 1;
+    }
     if ((rc = sk_union_count_enable(u, 1)) != SK_OK) {
-        fprintf(err, "kmer_scrub_count: union count column failed: %s (%s)\n", sk_strerror(rc), sk_union_last_error(u));
-        goto out;
+        if (!others) fprintf(err, "kmer_scrub_count: union count column failed: %s (%s)\n", sk_strerror(rc), sk_union_last_error(u));
+        sk_union_destroy(u);
+        return others ? SM_LATER : 1;
     }
-    uc = sk_union_context(u);
-    if (skh_scan_list(uc, A, NULL, 0, progress, err, 0, 1, NULL) != SK_OK) goto out;
-    t = sm_now();
-    if (sm_fold(u, 1, all, 0, err) != SK_OK) goto out;
-    *fold_ms += 1e3 * (sm_now() - t);
-    if (skh_scan_list(uc, B, NULL, 0, progress, err, 0, 1, NULL) != SK_OK) goto out;
-    t = sm_now();
-    if (sm_fold(u, 2, all, 0, err) != SK_OK) goto out;
-    *fold_ms += 1e3 * (sm_now() - t);
-    if (C) {
-        FILE *fp;
-        char *line = NULL, *nl;
-        size_t cap = 0;
-        if (skh_scan_list(uc, C, NULL, 0, progress, err, 0, 1, NULL) != SK_OK) goto out;
-        if (sm_fold(u, 3, all, 0, err) != SK_OK) goto out;
-        /* the -C lines a member would have skipped: scanned alone and taken back from that member (a line may come several times) */
-        if (!(fp = fopen(C, "r"))) { fprintf(err, "could not read file %s in GEN_all_kmer_counts()\n", C); goto out; }
-        rc = SK_OK;
-        while (rc == SK_OK && getline(&line, &cap, fp) != -1) {
-            uint32_t mask = 0;
-            if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
-            for (k = 0; k < n; k++) if (strcmp(g[k]->genome, line) == 0) mask |= 1u << k;
-            if (!mask) continue;
-            rc = skh_scan_file(uc, line, 0, NULL);
-            if (rc == SK_E_OPEN) fprintf(err, "could not read file %s in GEN_calculate_kmer_count()\n", line);
-            else if (rc != SK_OK) fprintf(err, "kmer_scrub_count: device error while scanning %s: %s (%s)\n", line, sk_strerror(rc), sk_last_error(uc));
-            if (rc == SK_OK) rc = sm_fold(u, 3, mask, 1, err);
-            for (k = 0; rc == SK_OK && k < n; k++) if ((mask >> k) & 1u) fprintf(err, "skipping %s (identical match)\n", line);
-        }
-        free(line);
-        fclose(fp);
-        if (rc != SK_OK) goto out;
+    *out = u;
+    return 0;
+}
+
+/* the -C lines a union's member would have skipped: scanned alone and taken back from that member (a line may come several times) */
+static int sm_union_skips(const sm_union *r, const char *C, FILE *err)
+{
+    sk_ctx *uc = sk_union_context(r->u);
+    FILE *fp;
+    char *line = NULL, *nl;
+    size_t cap = 0;
+    uint32_t k;
+    int rc = SK_OK;
+    if (!(fp = fopen(C, "r"))) { fprintf(err, "could not read file %s in GEN_all_kmer_counts()\n", C); return 1; }
+    while (rc == SK_OK && getline(&line, &cap, fp) != -1) {
+        uint32_t mask = 0;
+        if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
+        for (k = 0; k < r->n; k++) if (strcmp(r->g[k]->genome, line) == 0) mask |= 1u << k;
+        if (!mask) continue;
+        rc = skh_scan_file(uc, line, 0, NULL);
+        if (rc == SK_E_OPEN) fprintf(err, "could not read file %s in GEN_calculate_kmer_count()\n", line);
+        else if (rc != SK_OK) fprintf(err, "kmer_scrub_count: device error while scanning %s: %s (%s)\n", line, sk_strerror(rc), sk_last_error(uc));
+        if (rc == SK_OK) rc = sm_fold(r->u, 3, mask, 1, err);
+        for (k = 0; rc == SK_OK && k < r->n; k++) if ((mask >> k) & 1u) fprintf(err, "skipping %s (identical match)\n", line);
     }
-    status = 0;
-out:
-    sk_union_destroy(u);
-    return status;
+    free(line);
+    fclose(fp);
+    return rc != SK_OK;
+}
+
+/* ONE decode of the lists for every resident union: each chunk goes up once and is scanned into every union's column 0
+ * (skh_scan_list_many), and after each list every union folds it into its members' column.  Then the -C lines equal to a member,
+ * union by union in group order -- the order in which one pass per group said its "skipping" lines. */
+static int sm_decode(const sm_union *r, uint32_t nr, const char *A, const char *B, const char *C, FILE *progress, FILE *err,
+                     double *fold_ms, uint64_t *bases)
+{
+    sk_ctx **uc = (sk_ctx **)malloc((size_t)nr * sizeof *uc);
+    const char *list[3] = {A, B, C};
+    uint32_t i, l;
+    double t;
+    if (!uc) { fprintf(err, "kmer_scrub_count: out of memory\n"); return 1; }
+    for (i = 0; i < nr; i++) uc[i] = sk_union_context(r[i].u);
+    for (l = 0; l < 3 && list[l]; l++) {
+        if (skh_scan_list_many(uc, nr, list[l], NULL, 0, progress, err, 0, 1, bases) != SK_OK) break;
+        t = sm_now();
+        for (i = 0; i < nr; i++) if (sm_fold(r[i].u, l + 1, sm_all(r[i].n), 0, err) != SK_OK) break;
+        if (i < nr) break;
+        if (l < 2) *fold_ms += 1e3 * (sm_now() - t);
+    }
+    free(uc);
+    if (l < 3 && list[l]) return 1;
+    for (i = 0; C && i < nr; i++) if (sm_union_skips(&r[i], C, err)) return 1;
+    return 0;
 }
 
 static int sm_is_gz(const char *p)
@@ -282,7 +328,8 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
     const int world = sm_env_int("SK_WORLD_SIZE", "WORLD_SIZE", "OMPI_COMM_WORLD_SIZE", 1);
     const int rank = sm_env_int("SK_RANK", "RANK", "OMPI_COMM_WORLD_RANK", 0);
     int device = sm_env_int("SK_LOCAL_RANK", "LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", 0);
-    uint32_t group = SK_UNION_MAX, ns = 0, k, nunion = 0, nsingle = 0;
+    uint32_t group = SK_UNION_MAX, ns = 0, k, nunion = 0, nsingle = 0, ndecode = 0, max_unions = UINT32_MAX;
+    uint64_t hbm_mb = 0, list_bases = 0;
     sm_strain *st = NULL;
     FILE *progress = NULL;
     skzo_pool zpool;
@@ -351,6 +398,8 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
     }
     if ((env = getenv("SK_DEVICE")) != NULL) device = atoi(env);
     if ((env = getenv("SK_SCRUB_GROUP")) != NULL && atoi(env) >= 1 && atoi(env) <= SK_UNION_MAX) group = (uint32_t)atoi(env);
+    if ((env = getenv("SK_SCRUB_UNIONS")) != NULL && atol(env) >= 1) max_unions = atol(env) > UINT32_MAX ? UINT32_MAX : (uint32_t)atol(env);
+    if ((env = getenv("SK_SCRUB_HBM_MB")) != NULL && atoll(env) >= 1) hbm_mb = (uint64_t)atoll(env);
 
     {   /* the strains file: <genome> TAB <outfile> (with --detect: <genome> TAB <informative> TAB <hits> [TAB <-g list>]);
          * this rank's lines (round-robin over the strain lines) */
@@ -431,12 +480,16 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
     }
     t1 = sm_now();
 
-    {   /* the passes: unions of up to `group` strains, then every strain a union cannot hold on its own.  Only the first pass
-         * writes the progress file (every pass walks the same lists). */
+    {   /* the passes: unions of up to `group` strains, as many resident at once as fit (SK_SCRUB_UNIONS at most), every list
+         * decoded ONCE for all of them; then every strain a union cannot hold on its own.  Only the first decode writes the progress
+         * file (every decode walks the same lists). */
         sm_strain **uni = (sm_strain **)malloc(((size_t)ns + 1) * sizeof *uni), **solo = (sm_strain **)malloc(((size_t)ns + 1) * sizeof *solo);
-        uint32_t nu = 0, nsolo = 0, a;
+        sm_union *res = (sm_union *)calloc((size_t)ns + 1, sizeof *res);
+        uint32_t nu = 0, nsolo = 0, a = 0;
         const int no_union = getenv("SK_SCRUB_NO_UNION") != NULL && getenv("SK_SCRUB_NO_UNION")[0] == '1';
+        uint64_t budget = 0;
         int rc = 0;
+        if (!uni || !solo || !res) { fprintf(err, "kmer_scrub_count: out of memory\n"); free(uni); free(solo); free(res); goto done; }
         for (k = 0; k < ns; k++) {
             const skh_keyset *ks = &st[k].ks;
             /* what sk_union_create takes: packed keys only, the text stage, fewer rows than the hit log can name */
@@ -444,24 +497,48 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
                              ks->nrows < (1u << SK_UNION_ROW_BITS) - 1u;
             if (fits) uni[nu++] = &st[k]; else solo[nsolo++] = &st[k];
         }
-        for (a = 0; rc == 0 && a < nu; a += group) {
-            const uint32_t n = nu - a < group ? nu - a : group;
-            rc = sm_union_pass(uni + a, n, A, B, C, progress, err, &fold_ms);
-            if (rc == SM_FALLBACK) {                           /* (nothing was scanned) */
-                for (k = 0; k < n; k++) solo[nsolo++] = uni[a + k];
-                rc = 0;
-                continue;
+        if (nu) {   /* room for unions: free HBM (or SK_SCRUB_HBM_MB) less a reserve for scratch and staging */
+            uint64_t fr = 0, tot = 0;
+            if (hbm_mb) fr = hbm_mb << 20;
+            else if (sk_device_memory(uni[0]->ctx, &fr, &tot) != SK_OK) fr = 0;
+            budget = fr > (1ull << 30) + fr / 32 ? fr - (1ull << 30) - fr / 32 : 0;
+        }
+        while (rc == 0 && a < nu) {
+            uint32_t nr = 0;
+            uint64_t used = 0;
+            while (a < nu && nr < max_unions) {                /* make this decode's unions */
+                const uint32_t n = nu - a < group ? nu - a : group;
+                const uint64_t est = sm_union_bytes(uni + a, n);
+                if (nr && used + est > budget) break;
+                rc = sm_union_make(uni + a, n, nr > 0, &res[nr].u, err);
+                if (rc == SM_FALLBACK) {                       /* (nothing was scanned) */
+                    for (k = 0; k < n; k++) solo[nsolo++] = uni[a + k];
+                    a += n;
+                    rc = 0;
+                    continue;
+                }
+                if (rc == SM_LATER) { rc = 0; break; }         /* (made again for the next decode) */
+                if (rc != 0) break;
+                res[nr].g = uni + a; res[nr].n = n;
+                nr++; used += est; a += n;
             }
-            nunion++;
-            if (progress) { fclose(progress); progress = NULL; }
+            if (rc == 0 && nr) {
+                rc = sm_decode(res, nr, A, B, C, progress, err, &fold_ms, &list_bases);
+                ndecode++;
+                if (rc == 0) nunion += nr;
+                if (progress) { fclose(progress); progress = NULL; }
+            }
+            for (k = 0; k < nr; k++) { sk_union_destroy(res[k].u); res[k].u = NULL; }
         }
         for (k = 0; rc == 0 && k < nsolo; k++) {
-            rc = sm_single_pass(solo[k], A, B, C, progress, err);
+            rc = sm_single_pass(solo[k], A, B, C, progress, err, &list_bases);
             nsingle++;
+            ndecode++;
             if (progress) { fclose(progress); progress = NULL; }
         }
         free(uni);
         free(solo);
+        free(res);
         if (rc != 0) goto done;
     }
     t2 = sm_now();
@@ -508,11 +585,12 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
 done:
     if (getenv("SK_TIMING") && t3 > 0 && scrub_fraction < 0.0)
         fprintf(err, "kmer_scrub_count -S timing: %u strain(s) opened in %.2f s, %u union pass(es) + %u single pass(es) %.2f s "
-                     "(folds %.1f ms), print %.2f s\n", ns, t1 - t0, nunion, nsingle, t2 - t1, fold_ms, t3 - t2);
+                     "(folds %.1f ms), print %.2f s, lists decoded %u time(s) (%llu bases)\n", ns, t1 - t0, nunion, nsingle, t2 - t1,
+                fold_ms, t3 - t2, ndecode, (unsigned long long)list_bases);
     if (getenv("SK_TIMING") && t3 > 0 && scrub_fraction >= 0.0)
         fprintf(err, "kmer_scrub_count -S timing: %u strain(s) opened in %.2f s, %u union pass(es) + %u single pass(es) %.2f s "
-                     "(folds %.1f ms), filter %.2f s, detect %.2f s\n", ns, t1 - t0, nunion, nsingle, t2 - t1, fold_ms, t3 - t2,
-                t4 > 0 ? t4 - t3 : 0.0);
+                     "(folds %.1f ms), filter %.2f s, detect %.2f s, lists decoded %u time(s) (%llu bases)\n", ns, t1 - t0, nunion, nsingle,
+                t2 - t1, fold_ms, t3 - t2, t4 > 0 ? t4 - t3 : 0.0, ndecode, (unsigned long long)list_bases);
     for (k = 0; k < ns; k++) {
         if (st[k].zo) skzo_close(st[k].zo);
         if (st[k].fp) fclose(st[k].fp);

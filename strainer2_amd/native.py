@@ -42,13 +42,13 @@ SK_E_PLAN = -10
 # every symbol include/strainer_kmer.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
     "sk_ctx_create", "sk_ctx_destroy", "sk_last_error", "sk_strerror", "sk_table_load", "sk_table_load_ex",
-    "sk_table_load_wide", "sk_table_load_text", "sk_table_build_from_text", "sk_table_export_keys", "sk_table_export_keys_of", "sk_scan_stream", "sk_scan_device", "sk_pinned_alloc", "sk_pinned_free", "sk_scan_pinned", "sk_scan_pinned_packed", "sk_scan_device_packed", "sk_pack_stream", "sk_packed_bytes",
+    "sk_table_load_wide", "sk_table_load_text", "sk_table_build_from_text", "sk_table_export_keys", "sk_table_export_keys_of", "sk_scan_stream", "sk_scan_device", "sk_pinned_alloc", "sk_pinned_free", "sk_scan_pinned", "sk_scan_pinned_packed", "sk_scan_pinned_many", "sk_scan_pinned_packed_many", "sk_device_memory", "sk_scan_device_packed", "sk_pack_stream", "sk_packed_bytes",
     "sk_ticket_wait", "sk_tally_batch", "sk_sync", "sk_counts_fetch",
     "sk_counts_set", "sk_counts_set_rows", "sk_counts_zero", "sk_counts_device_ptr", "sk_table_rows", "sk_table_cols",
     "sk_counts_allreduce", "sk_comm_init", "sk_comm_init_ex", "sk_rendezvous_exchange", "sk_comm_destroy", "sk_comm_sum_u32", "sk_comm_agree_u64", "sk_comm_max_u64", "sk_comm_world", "sk_scan_timing", "sk_set_option", "sk_dev_alloc", "sk_dev_free",
     "sk_dev_upload", "sk_dev_download",
     "skh_keyset_from_file", "skh_keyset_from_stream", "skh_keyset_free", "skh_keyset_key",
-    "skh_keyset_load", "skh_scan_file", "skh_scan_list", "skh_scan_list_uncut", "skh_list_plan_hash", "skh_list_plan_owners", "skh_print_counts",
+    "skh_keyset_load", "skh_scan_file", "skh_scan_list", "skh_scan_list_many", "skh_scan_list_uncut", "skh_list_plan_hash", "skh_list_plan_owners", "skh_print_counts",
     "skh_kmer_scrub_count_main", "skh_strain_detect_main", "skh_strain_detect_resident", "skh_strain_detect_resident_many", "skh_decode_file",
     "sk_filter_create", "sk_filter_destroy", "sk_filter_load", "sk_filter_load_counts", "sk_filter_sums",
     "sk_filter_hist", "sk_filter_joint", "sk_filter_above", "skh_scrub_filter_main", "skh_scrub_filter_resident",
@@ -89,6 +89,9 @@ lib.sk_pinned_free.argtypes = [C.c_void_p, C.c_void_p]
 lib.sk_scan_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
 lib.sk_ticket_wait.argtypes = [C.c_void_p, C.c_uint64]
 lib.sk_scan_pinned_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+lib.sk_scan_pinned_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+lib.sk_scan_pinned_packed_many.argtypes = lib.sk_scan_pinned_many.argtypes
+lib.sk_device_memory.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
 lib.sk_scan_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
 lib.sk_pack_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int)]
 lib.sk_packed_bytes.argtypes = [C.c_uint64]
@@ -129,6 +132,7 @@ lib.skh_list_plan_owners.restype = C.c_int
 lib.skh_scan_list.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p,
                               C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
 lib.skh_scan_list_uncut.argtypes = lib.skh_scan_list.argtypes
+lib.skh_scan_list_many.argtypes = [C.c_void_p, C.c_uint32] + lib.skh_scan_list.argtypes[1:]
 lib.skh_print_counts.argtypes = [C.c_void_p, C.POINTER(_KeysetStruct), C.c_void_p, C.c_int]
 lib.skh_kmer_scrub_count_main.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
 lib.skh_decode_file.argtypes = [C.c_char_p, C.c_uint64, _SINK, C.c_void_p, C.POINTER(C.c_uint64)]
@@ -346,6 +350,32 @@ class KmerContext:
         self._ck(lib.sk_scan_pinned_packed(self._h, packed_arr.ctypes.data, nbytes, col, C.byref(t)))
         return t.value
 
+    def _many(self, others):
+        """self's handle, then those of `others` (KmerContext or KmerUnion: the union's own context), as a C array"""
+        hs = [self._h] + [o.context_handle if isinstance(o, KmerUnion) else o._h for o in others]
+        return (C.c_void_p * len(hs))(*hs), len(hs)
+
+    def scan_pinned_many(self, others, arr, nbytes, col, offset=0):
+        """sk_scan_pinned_many: one upload of a pinned batch (this context's staging ring and ticket), scanned into column `col` of
+        this context and of every one in `others`; returns the ticket (ticket_wait on this context)"""
+        t = C.c_uint64(0)
+        hs, n = self._many(others)
+        self._ck(lib.sk_scan_pinned_many(hs, n, arr.ctypes.data + offset, nbytes, col, C.byref(t)))
+        return t.value
+
+    def scan_pinned_packed_many(self, others, packed_arr, nbytes, col):
+        """sk_scan_pinned_packed_many: scan_pinned_many for a batch packed by pack_stream() into page-locked memory"""
+        t = C.c_uint64(0)
+        hs, n = self._many(others)
+        self._ck(lib.sk_scan_pinned_packed_many(hs, n, packed_arr.ctypes.data, nbytes, col, C.byref(t)))
+        return t.value
+
+    def device_memory(self):
+        """(free, total) bytes of HBM on this context's device"""
+        f, t = C.c_uint64(0), C.c_uint64(0)
+        self._ck(lib.sk_device_memory(self._h, C.byref(f), C.byref(t)))
+        return f.value, t.value
+
     def ticket_wait(self, ticket):
         self._ck(lib.sk_ticket_wait(self._h, ticket))
 
@@ -365,6 +395,15 @@ class KmerContext:
         fn = lib.skh_scan_list_uncut if uncut else lib.skh_scan_list
         self._ck(fn(self._h, os.fsencode(list_path), None if skip is None else os.fsencode(skip),
                     col, None, None, rank, world, C.byref(bases)))
+        return bases.value
+
+    def scan_list_many(self, others, list_path, col, skip=None):
+        """skh_scan_list_many: one decode of the list into column `col` of this context and of every one in `others`; returns the
+        bases decoded"""
+        bases = C.c_uint64(0)
+        hs, n = self._many(others)
+        self._ck(lib.skh_scan_list_many(hs, n, os.fsencode(list_path), None if skip is None else os.fsencode(skip),
+                                        col, None, None, 0, 1, C.byref(bases)))
         return bases.value
 
     @staticmethod
@@ -534,6 +573,17 @@ class KmerUnion:
     @property
     def rows(self):
         return lib.sk_union_rows(self._h)
+
+    @property
+    def context_handle(self):
+        """the union's own context (sk_union_context): what the COUNT scans take"""
+        return lib.sk_union_context(self._h)
+
+    def counts(self, col=0):
+        """union column `col` in global-row order (sk_counts_fetch on the union's context)"""
+        out = np.zeros(self.rows, dtype=np.uint32)
+        self._uck(lib.sk_counts_fetch(lib.sk_union_context(self._h), col, out.ctypes.data))
+        return out
 
     def set_option(self, name, value):
         """sk_set_option on the union's own context (e.g. "odd_list_cap" for its scans)"""

@@ -15,11 +15,19 @@
       Every informative list and hit list (decompressed) is compared by md5 in the same run.  Each program runs under its own
       `timeout -k 10`; the first failure ends the run.
 
-Prints one JSON line.  Environment: READS (10,000,000), E2E_STRAINS (8), WORK (/tmp/sk_scrub_multi_bench), and for (d)
-WORKFLOW_STRAINS (8), TARGET_READS (2,000,000: the -B list of strain_detect, one plain FASTQ)."""
+  (e) with --onepass, instead: `kmer_scrub_count -S` for G x 32 cfg5 strains (ONEPASS_G, "2,8": 64 and 256 strains) over a -B
+      list of one plain FASTQ of ONEPASS_READS reads, then over its .gz copy, with the default (every union that fits fed by
+      one decode of the lists) and with SK_SCRUB_UNIONS=1 (one decode per union, as before).  Every outfile is compared by md5
+      in the same run; reported: wall time, the list phase from SK_TIMING, decodes, unions per decode.  Each run under its
+      own `timeout -k 10`; the first failure ends the tool.
+
+Prints one JSON line.  Environment: READS (10,000,000), E2E_STRAINS (8), WORK (/tmp/sk_scrub_multi_bench), for (d)
+WORKFLOW_STRAINS (8), TARGET_READS (2,000,000: the -B list of strain_detect, one plain FASTQ), for (e) ONEPASS_G ("2,8"),
+ONEPASS_READS (4,000,000)."""
 import hashlib
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -166,6 +174,77 @@ def workflow():
     print(json.dumps(res))
 
 
+def onepass():
+    """(e): G unions fed by one decode against one decode per union, plain and .gz -B list, outputs compared"""
+    os.makedirs(WORK, exist_ok=True)
+    gs = [int(x) for x in os.environ.get("ONEPASS_G", "2,8").split(",")]
+    nreads = int(os.environ.get("ONEPASS_READS", "4000000"))
+    res = {"reads": nreads, "read_len": 150, "runs": []}
+    t0 = time.time()
+    genomes = [cfg5.strain(s) for s in range(32 * max(gs))]
+    reads, bases = synth.make_reads(genomes[:32], nreads)
+    fq = os.path.join(WORK, "reads.fq")
+    write_fastq(fq, reads)
+    del reads
+    timed(["sh", "-c", f"gzip -1 -c {fq} > {fq}.gz"], 600, "gzip of the -B file")
+    paths = []
+    for s in range(len(genomes)):
+        p = os.path.join(WORK, f"s{s}.fa")
+        with open(p, "wb") as f:
+            f.write(b">s%d\n" % s + genomes[s].tobytes() + b"\n")
+        paths.append(p)
+    del genomes
+    res["setup_s"] = round(time.time() - t0, 1)
+    res["list_gbase"] = round(bases / 1e9, 3)
+    res["fastq_bytes"], res["fastq_gz_bytes"] = os.path.getsize(fq), os.path.getsize(fq + ".gz")
+    with open(os.path.join(WORK, "A.txt"), "w") as f:
+        f.write(paths[-1] + "\n")
+    exe = sk.cli_path()
+    pat = re.compile(r"(\d+) union pass\(es\) \+ (\d+) single pass\(es\) ([0-9.]+) s .*lists decoded (\d+) time\(s\) \((\d+) bases\)")
+    for g in gs:
+        n = 32 * g
+        w = os.path.join(WORK, f"g{g}")
+        os.makedirs(w, exist_ok=True)
+        with open(os.path.join(w, "S.txt"), "w") as f:
+            for s in range(n):
+                f.write(f"{paths[s]}\t{w}/o{s}.tsv\n")
+        for form, path in (("plain", fq), ("gz", fq + ".gz")):
+            with open(os.path.join(w, "B.txt"), "w") as f:
+                f.write(path + "\n")
+            run = {"strains": n, "list": form}
+            sums = {}
+            for mode, extra in (("onepass", {}), ("per_union", {"SK_SCRUB_UNIONS": "1"})):
+                env = dict(os.environ, SK_TIMING="1", **extra)
+                wall, p = timed([exe, "-S", os.path.join(w, "S.txt"), "-A", os.path.join(WORK, "A.txt"), "-B", os.path.join(w, "B.txt")],
+                                1800, f"-S {n} strains ({form}, {mode})", env=env)
+                m = pat.search(p.stderr)
+                if not m:
+                    sys.stderr.write(f"no SK_TIMING line in:\n{p.stderr[-3000:]}\n")
+                    sys.exit(1)
+                unions, singles, list_s, decodes, dbases = int(m[1]), int(m[2]), float(m[3]), int(m[4]), int(m[5])
+                run[mode] = {"wall_s": round(wall, 2), "list_phase_s": list_s, "unions": unions, "single_passes": singles,
+                             "decodes": decodes, "unions_per_decode": round(unions / max(decodes - singles, 1), 2),
+                             "bases_decoded": dbases}
+                with ThreadPoolExecutor(16) as ex:
+                    sums[mode] = list(ex.map(md5, [f"{w}/o{s}.tsv" for s in range(n)]))
+                for s in range(n):
+                    os.unlink(f"{w}/o{s}.tsv")
+            run["outputs_identical"] = sums["onepass"] == sums["per_union"]
+            run["list_phase_speedup"] = round(run["per_union"]["list_phase_s"] / max(run["onepass"]["list_phase_s"], 1e-9), 2)
+            run["wall_speedup"] = round(run["per_union"]["wall_s"] / run["onepass"]["wall_s"], 2)
+            res["runs"].append(run)
+            if not run["outputs_identical"]:
+                print(json.dumps(res))
+                sys.stderr.write("outfiles differ between the two modes\n")
+                sys.exit(1)
+        shutil.rmtree(w)
+    for p in paths:
+        os.unlink(p)
+    os.unlink(fq)
+    os.unlink(fq + ".gz")
+    print(json.dumps(res))
+
+
 def main():
     os.makedirs(WORK, exist_ok=True)
     res = {"reads": READS, "read_len": 150}
@@ -270,5 +349,7 @@ def main():
 if __name__ == "__main__":
     if "--workflow" in sys.argv[1:]:
         workflow()
+    elif "--onepass" in sys.argv[1:]:
+        onepass()
     else:
         main()
