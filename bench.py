@@ -9,7 +9,12 @@ scan over that batch (sk_scan_device -> sk_scan_grid [+ sk_scan_wide early-exit]
 K timed steps the per-k-mer count vector of the scanned (-B) column is summed across ranks with one
 RCCL all-reduce (inside the timed region when N > 1).  value = bases all ranks scanned / max-over-ranks time.
 
-Bit-exactness is checked in the run that is timed: the counts of the K timed passes, divided by K, must be
+A plain run does only what `value` needs: set-up, preheat + W warmup steps, the K timed steps, --dump-outputs, the line.
+--full adds the rest, none of it inside the timed steps: the CPU baselines (before the GPU is touched), the reference check below,
+the PCIe-inclusive, packed-input and file-fed rates and the strain_detect leg; --no-cpu, --no-host-rate, --file-reads 0 and
+--no-sd leave single legs out of a --full run.
+
+Bit-exactness (--full) is checked in the run that is timed: the counts of the K timed passes, divided by K, must be
 the vector the UNMODIFIED reference program produced for the same stream (tests/golden/cfg2_facts.json:
 sum, non-zero rows and md5 of the u32 column in the reference's row order, made by
 tests/golden/make_cfg2_facts.py); for N > 1 the reduced total must be the sum of the ranks' facts and every
@@ -23,7 +28,7 @@ bytes, so that figure is not a fraction of anything.  traffic = measured HBM byt
 passes of tools/profile.sh, taken from profiles/traffic.json ONLY if that file was measured on this very
 sk_device.hip + sk_dev_*.hip.h (sha256 stamp), else null.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--no-cpu] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR] [--full [--no-cpu] [--no-sd] ...]
   N > 1, either way:
     python bench.py --gpus N ...                       (no WORLD_SIZE in the environment: this process starts the N ranks itself --
                                                         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -453,11 +458,15 @@ def main():
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--strain-bp", type=int, default=5_000_000, help="size of the synthetic strain (cfg 2: 5 Mbp); other sizes are for sweeps, not for `value`")
     ap.add_argument("--hit-frac", type=float, default=0.02, help="fraction of reads drawn from the strain (cfg 2: 0.02)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-sd", action="store_true", help="skip the strain_detect (TALLY/UNION kernel) side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what `value` does not need: cpu_baseline (the reference program and the oracle on the "
+                         "host's CPUs), the timed counts against the reference's facts, the PCIe-inclusive and packed-input rates, the "
+                         "file-fed rate and the strain_detect leg (a minute or more beyond the timed steps)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-sd", action="store_true", help="with --full: skip the strain_detect (TALLY/UNION kernel) side measurement")
     ap.add_argument("--sd-only", action="store_true", help="only the strain_detect side leg (for tools/profile.sh --sd): prints its object, no `value`")
-    ap.add_argument("--no-host-rate", action="store_true", help="skip the PCIe-inclusive host-buffer passes (keeps profiles clean)")
-    ap.add_argument("--file-reads", type=int, default=1_000_000, help="reads per FASTQ file of the file-fed, rank-sharded side measurement (0 = skip it)")
+    ap.add_argument("--no-host-rate", action="store_true", help="with --full: skip the PCIe-inclusive host-buffer passes")
+    ap.add_argument("--file-reads", type=int, default=1_000_000, help="with --full: reads per FASTQ file of the file-fed, rank-sharded side measurement (0 = skip it)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--grid-kib", type=int, default=None, help="size of the grid kernel's level-1 filter in KiB (default: automatic)")
     ap.add_argument("--text-stage", type=int, default=None, help="0 = stage 2 without the strain's text (A/B)")
@@ -492,7 +501,7 @@ def main():
 
     # CPU baseline first: it forks, and must do so before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline_reference(contigs, reads, args.read_len)
         port = cpu_baseline(sstream, reads, args.read_len, target_seconds=1.0 if cpu else 12.0)
         if cpu is None:
@@ -567,7 +576,7 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    # bit-exactness inside the same run: the K timed passes' counts / K must be the reference program's vector
+    # bit-exactness inside the same run (--full): the K timed passes' counts / K must be the reference program's vector
     # for this very stream (tests/golden/cfg2_facts.json); for N > 1 the reduced total must be the ranks' sum
     counts = ctx.counts(2)
     if world > 1:                                   # every rank must hold the same reduced table
@@ -580,7 +589,7 @@ def main():
     hits_per_pass = int(counts.astype(np.uint64).sum()) // args.steps
     parity = {"facts": None, "checked": False}
     facts = load_cfg2_facts(args)
-    if facts is not None and not args.ablate:
+    if args.full and facts is not None and not args.ablate:
         def fact_of(vec):
             return {"sum": int(vec.astype(np.uint64).sum()), "nonzero_rows": int(np.count_nonzero(vec)),
                     "md5_u32_le": hashlib.md5(vec.astype("<u4").tobytes()).hexdigest()}
@@ -609,7 +618,7 @@ def main():
     # PCIe-inclusive rate (host buffer -> pinned staging -> H2D -> scan), reported beside `value`,
     # never as it: 2 passes of sk_scan_stream over the same record stream
     host_rate = pinned_rate = packed_resident = None
-    if world == 1 and not args.ablate and not args.no_host_rate:
+    if args.full and world == 1 and not args.ablate and not args.no_host_rate:
         ctx.scan_stream(reads[: 64 << 20], 3)
         ctx.sync()
         t1 = time.perf_counter()
@@ -657,7 +666,7 @@ def main():
     # that list through the product's list walk (skh_scan_list: items dealt by size, the big file cut at checked record
     # boundaries, decode threads -> pinned buffers -> H2D -> kernel).  This is where N ranks share the host's cores.
     file_fed = None
-    if args.file_reads > 0 and not args.ablate:
+    if args.full and args.file_reads > 0 and not args.ablate:
         import shutil
         import tempfile
         base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
@@ -747,7 +756,7 @@ def main():
             shutil.rmtree(root, ignore_errors=True)
 
     sd_leg = None
-    if rank == 0 and world == 1 and not args.no_sd and not args.ablate:
+    if args.full and rank == 0 and world == 1 and not args.no_sd and not args.ablate:
         ctx.dev_free(dev)                                   # (the 1.5 GB stream is no longer needed)
         try:
             sd_leg = strain_detect_leg(device)
@@ -767,7 +776,7 @@ def main():
         traffic, traffic_note = measured_traffic(args, kernel_name)
         line = {
             "metric": "metagenome bases/sec scanned at k=31", "value": value, "unit": "bases/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "preheat_ms": args.preheat_ms, "preheat_launches": preheat_launches,
+            "n_gpus": world, "full": args.full, "steps": args.steps, "warmup": args.warmup, "preheat_ms": args.preheat_ms, "preheat_launches": preheat_launches,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u64", "data": "synthetic",
             "config": {"workload": "configs[1]: 5 Mbp synthetic strain (-r) vs %d x %d bp synthetic reads (-B) per GPU, k=31, "

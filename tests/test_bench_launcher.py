@@ -9,6 +9,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = os.path.join(REPO, "tests", "native", "bench_rank_stub.py")
 
@@ -87,3 +89,29 @@ def test_dump_outputs_writes_exact_float64_and_samples_over_budget(tmp_path, mon
 def test_steps_below_one_is_refused_before_anything_starts():
     p = _run(["--gpus", "2", "--steps", "0", "--backend", "gloo"])
     assert p.returncode != 0 and p.stdout == b"" and b"--steps must be at least 1" in p.stderr
+
+
+@pytest.mark.gpu
+def test_a_plain_run_does_only_the_headline_and_full_adds_the_side_legs(tmp_path):
+    """a plain `bench.py --gpus 1` sets up, times its steps, dumps and prints the line with no side leg in it; --full brings the
+    CPU baseline, the PCIe-inclusive, packed-input and file-fed rates back (the strain_detect leg is left out here for time)"""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "SK_BENCH_RANK_SCRIPT"):
+        env.pop(k, None)
+    argv = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "200000"]
+    p = subprocess.run(argv + ["--dump-outputs", str(tmp_path)], env=env, capture_output=True, timeout=300)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    plain = json.loads(p.stdout.decode())
+    assert plain["full"] is False and plain["steps"] == 3 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["cpu_baseline"] is None and plain["strain_detect"] is None and plain["parity"]["checked"] is False
+    cfg = plain["config"]
+    assert cfg["pcie_inclusive_bases_per_s_host_buffers"] is None and cfg["packed_input_resident"] is None and cfg["file_fed_rank_sharded"] is None
+    assert sorted(os.listdir(tmp_path)) == ["counts_per_step.npy"]
+    p = subprocess.run(argv + ["--full", "--no-sd"], env=env, capture_output=True, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    full = json.loads(p.stdout.decode())
+    assert full["full"] is True and full["cpu_baseline"]["value"] > 0 and full["strain_detect"] is None
+    cfg = full["config"]
+    assert cfg["pcie_inclusive_bases_per_s_host_buffers"] > 0 and cfg["packed_input_resident"]["bases_per_s"] > 0
+    assert cfg["file_fed_rank_sharded"]["bases_per_s"] > 0
+    assert full["config"]["hits_per_pass_rank0_or_sum"] == plain["config"]["hits_per_pass_rank0_or_sum"] > 0

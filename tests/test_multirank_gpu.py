@@ -25,7 +25,7 @@ def test_plain_bench_command_at_two_ranks_is_parity_checked():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--backend", "gloo",
-                        "--no-cpu", "--no-sd"], env=env, capture_output=True, timeout=840)
+                        "--full", "--no-cpu", "--no-sd"], env=env, capture_output=True, timeout=840)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = p.stdout.decode().splitlines()
     assert len(lines) == 1
