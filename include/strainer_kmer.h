@@ -279,15 +279,21 @@ int  sk_comm_max_u64(sk_ctx *ctx, uint64_t *vals, uint32_t n);
 int  sk_comm_world(const sk_ctx *ctx);
 int  sk_counts_allreduce(sk_ctx *ctx, void *rccl_comm);
 
-/* Device-side timing of the scan kernel, from HIP events recorded on the context's stream
- * around every scan kernel since the last reset: total milliseconds and launch count. */
+/* Device-side timing of the scan kernel, from HIP events recorded around every scan kernel since the last
+ * reset: launch count, and the milliseconds the scan kernels kept the card busy.  Count scans of resident
+ * batches run on two lanes ("scan_lanes") and overlap at their edges; such time is counted once (the length
+ * of the union of the launches' intervals), so total_ms / launches is the time a launch ADDS, not how long
+ * one kernel took from its first workgroup to its last.  With one lane the two are the same. */
 int sk_scan_timing(sk_ctx *ctx, double *total_ms, uint64_t *launches, int reset);
 
 /* Tunables (before sk_table_load).  name: "table_load_pct" (max load factor in percent), "grid_kib" (size of
  * the level-1 filter in KiB, -1 = automatic), "text_stage" (0 = stage 2 probes every window on its own even
  * when the strain's text is resident; for A/B runs and tests), "pipeline" (2 = the partitioned pipeline sk_bin ->
  * sk_lds_probe -> candidates-only scan, an experiment that measured slower than the default single kernel: DESIGN.md
- * section 4), "odd_list_cap" (tests), "dev_alloc_uncached" (experiment: no effect), "ablate" (timing
+ * section 4), "odd_list_cap" (tests), "scan_lanes" (may be set at any time; 2, the default: back-to-back sk_scan_device /
+ * sk_scan_device_packed calls take two streams in turn, so that a launch starts while the one before it drains -- every
+ * other call of the context waits for both, results are the same; 1 = all of them on the context's one stream, for A/B
+ * runs and tests; the environment variable SK_SCAN_LANES=1 does the same for programs that set no options), "dev_alloc_uncached" (experiment: no effect), "ablate" (timing
  * experiments only: kernel variants that skip memory stages and give WRONG counts).
  * Unknown name -> SK_E_ARG. */
 int sk_set_option(sk_ctx *ctx, const char *name, long value);

@@ -17,11 +17,12 @@ template <bool TALLY, bool UNION = false>
 __global__ __launch_bounds__(256)
 void sk_scan_wide(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t emit_begin,
                   sk_table_view table, sk_wide_view wide, sk_sink sink,
-                  const uint32_t *__restrict__ flags, uint32_t *__restrict__ next_flags)
+                  uint32_t *flags)
 {
-    // the NEXT launch's flag words (the context alternates between two sets) are zeroed here, behind this launch's scan kernel and
-    // before the next one's: a memset per scan less on the stream
-    if (blockIdx.x == 0u && threadIdx.x < 4u) next_flags[threadIdx.x] = 0u;
+    // The flag words are the lane's own (a context's count scans take two lanes in turn, each with its words and its list), and this
+    // kernel leaves them zero for the lane's next launch: a memset per scan less on the stream.  With no odd byte in the batch they
+    // are zero as they stand; else the workgroup that finishes last (flags[1] counts them) zeroes them -- every workgroup has read
+    // what it needs of them by then.
     if (flags[0] == 0u) return;                        // no window with a non-ACGT byte in this batch
     // Work list: phase 1 of the scan kernel noted every 16-byte chunk that holds such a byte (flags[2] of them).
     // A window that needs this kernel contains one; it is handled from the chunk that holds its LAST non-ACGT
@@ -81,6 +82,15 @@ void sk_scan_wide(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
                 if (same) { sk_on_hit<TALLY, false, UNION>(sink, wide.rows[e - 1u], (uint32_t)p); break; }
                 slot = (slot + 1u) & wide.wmask;
             }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        __threadfence();
+        if (atomicAdd(&flags[1], 1u) == gridDim.x - 1u) {
+            flags[0] = 0u; flags[2] = 0u; flags[3] = 0u;
+            __threadfence();
+            flags[1] = 0u;
         }
     }
 }

@@ -35,6 +35,7 @@
 #include <new>
 #include <string>
 #include <vector>
+#include <algorithm>
 #include <unistd.h>
 #include <pthread.h>
 #include <errno.h>
@@ -56,6 +57,16 @@
 #define SK_NSTAGE        2
 
 struct sk_pin { void *p; size_t n; bool used; bool registered; };    // registered: malloc'd + hipHostRegister; else hipHostMalloc
+#define SK_LANES 2
+struct sk_span { double b, e; };
+struct sk_lane {
+    hipStream_t  stream;
+    uint32_t    *d_flags;             // this lane's four scan flag words (inside the context's flag block)
+    uint32_t    *d_oddlist;           // chunks with a byte for the byte-string kernel (SK_ODDCAP entries)
+    bool         flags_ready;         // the flag words are zero (false after anything but a scan wrote to the flag block)
+    std::vector<hipEvent_t> ev;       // begin/end pairs of this lane's launches not yet added up: a ring of at most SK_EV_PAIRS
+    std::vector<uint64_t> seq;        // ... and the number of each of those launches among the context's launches
+};
 
 struct sk_ctx {
     int          device;
@@ -99,16 +110,25 @@ struct sk_ctx {
     hipEvent_t   copied[64];           // ring of "host buffer of ticket t has been read" events
     hipEvent_t   read_done;            // sk_scan_pinned_many: this context's scan of another context's staging buffer is done
     uint64_t     tickets;              // tickets issued so far
-    // flags: [0] wide windows seen in the current batch, [1] table build errors
+    // flags: words 0..3 lane 0's scan flags, 4..7 lane 1's ([0] wide windows seen in the batch, [1] byte-string kernel's finished
+    // workgroups, [2] listed chunks); word 1 also counts table build errors
     uint32_t    *d_flags;
-    uint32_t     flag_set;            // which of the two sets of scan flags (words 0..3 / 4..7) the launch in hand uses
-    bool         flags_ready;         // both sets are zero (false after anything else wrote to the flag block)
-    uint32_t    *d_oddlist;           // chunks with a byte for the byte-string kernel (SK_ODDCAP entries)
+    // Count scans of resident batches (sk_scan_device, sk_scan_device_packed) take turns on two lanes, so that the next launch's
+    // workgroups fill the CUs while this launch's last ones drain.  Lane 0 is the context's stream; lane 1 has a stream, flag words
+    // and an odd-chunk list of its own, made when it is first used.  No event links the lanes; sk_lanes_join is where they meet.
+    sk_lane      lane[SK_LANES];
+    long         scan_lanes;          // option: 2 (default) or 1 = everything on the context's stream
+    uint32_t     lane_next;           // the lane the next count scan takes
+    bool         lane1_busy;          // lane 1 has scans the context's stream has not waited for
+    bool         lane1_behind;        // the context's stream has work lane 1's next scan must wait for
+    hipEvent_t   lane_done, lane_go;  // "lane 1 up to here" for the context's stream / "the context's stream up to here" for lane 1
     // timing
-    std::vector<hipEvent_t> ev;        // begin/end pairs of launches not yet added up: a ring of at most SK_EV_PAIRS
-    std::vector<hipEvent_t> ev_free;   // pairs that have been added up, for the next launches
+    std::vector<hipEvent_t> ev_free;   // event pairs that have been added up, for the next launches
+    hipEvent_t   ev_base;              // the launches' begin and end are placed on one time axis from here (recorded when the context is made)
+    std::vector<sk_span> busy;         // ... the stretches of it already counted into timed_ms (ms after ev_base), the newest few
     double       timed_ms;
     uint64_t     timed_launches;
+    uint64_t     launch_seq;           // launches made so far
     // options
     long         table_load_pct;
     long         ablate;              // timing experiments: kernel variants that skip memory stages
@@ -192,8 +212,21 @@ extern "C" int sk_ctx_create(sk_ctx **out, int device)
     c->err[0] = 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return SK_E_NODEVICE; }
     if (hipMalloc((void **)&c->d_flags, 32 * sizeof(uint32_t)) != hipSuccess) { delete c; return SK_E_NOMEM; }   // (words 16..31: scratch of the small collectives)
-    if (hipMalloc((void **)&c->d_oddlist, (size_t)SK_ODDCAP * sizeof(uint32_t)) != hipSuccess) { hipFree(c->d_flags); delete c; return SK_E_NOMEM; }
+    if (hipMalloc((void **)&c->lane[0].d_oddlist, (size_t)SK_ODDCAP * sizeof(uint32_t)) != hipSuccess) { hipFree(c->d_flags); delete c; return SK_E_NOMEM; }
     hipMemsetAsync(c->d_flags, 0, 32 * sizeof(uint32_t), c->stream);
+    c->lane[0].stream = c->stream;
+    for (uint32_t l = 0; l < SK_LANES; l++) c->lane[l].d_flags = c->d_flags + 4u * l;
+    c->scan_lanes = SK_LANES;
+    {   // (A/B runs of programs that set no options, like SK_SYNC above: SK_SCAN_LANES=1 is the option "scan_lanes" = 1)
+        const char *e = getenv("SK_SCAN_LANES");
+        if (e && !strcmp(e, "1")) c->scan_lanes = 1;
+    }
+    c->lane1_behind = true;
+    // the base of the timing's one time axis: recorded here, ahead of every launch of either lane, so that it is complete whenever a
+    // launch that is over is measured against it
+    if (hipEventCreate(&c->ev_base) != hipSuccess || hipEventRecord(c->ev_base, c->stream) != hipSuccess) {
+        hipFree(c->d_flags); hipFree(c->lane[0].d_oddlist); hipStreamDestroy(c->stream); delete c; return SK_E_NODEVICE;
+    }
     {   // the complement map goes to the device once per process and device, not once per context: the copy to a symbol
         // waits for the device, and 32 strains opened at once (strain_detect -S) spent 0.19 s each in here
         static pthread_mutex_t once_mu = PTHREAD_MUTEX_INITIALIZER;
@@ -211,6 +244,88 @@ extern "C" int sk_ctx_create(sk_ctx **out, int device)
         if (e != hipSuccess) { delete c; return SK_E_NODEVICE; }
     }
     *out = c;
+    return SK_OK;
+}
+
+// Where the two scan lanes meet.  Everything that enqueues on the context's stream, waits for it, or reads or frees what a count scan
+// touches calls this first -- everything, that is, but a count scan that takes a lane: the context's stream waits for what lane 1
+// has in flight (a wait on the device, not on the host), so that work on the stream and a hipStreamSynchronize of it stand for both
+// lanes as they did for the one; and lane 1's next scan will wait for what the caller is about to put on the stream.
+static int sk_lanes_join(sk_ctx *c)
+{
+    c->lane1_behind = true;
+    if (!c->lane1_busy) return SK_OK;
+    SK_HIP(c, hipEventRecord(c->lane_done, c->lane[1].stream));
+    SK_HIP(c, hipStreamWaitEvent(c->stream, c->lane_done, 0));
+    c->lane1_busy = false;
+    return SK_OK;
+}
+
+// lane 1's own things, the first time a scan takes it (most contexts never do: TALLY, UNION and the file-fed paths stay on the stream)
+static int sk_lane1_init(sk_ctx *c)
+{
+    sk_lane &L = c->lane[1];
+    if (L.stream) return SK_OK;
+    if (!L.d_oddlist) SK_HIP(c, hipMalloc((void **)&L.d_oddlist, (size_t)SK_ODDCAP * sizeof(uint32_t)));
+    if (!c->lane_done) SK_HIP(c, hipEventCreateWithFlags(&c->lane_done, hipEventDisableTiming));
+    if (!c->lane_go) SK_HIP(c, hipEventCreateWithFlags(&c->lane_go, hipEventDisableTiming));
+    SK_HIP(c, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    L.flags_ready = false;
+    return SK_OK;
+}
+
+// One finished launch, begin e0 and end e1, goes into the totals.  timed_ms is the time the scan kernels kept the card busy.
+// With one lane that is the sum of the launches' durations.  With two, launches overlap, so the length of the UNION of their
+// intervals is added up: each interval is placed on one time axis (ms after ev_base; hipEventElapsedTime works across
+// streams) and only the part of it that no counted stretch covers is added.  c->busy holds the counted stretches, disjoint
+// and ascending; the newest SK_BUSY_KEEP are kept, which is exact as long as a launch does not begin before stretches
+// older than those -- launches are added in the order they were made, so it reaches back by a launch or two.
+// The base moves along to the begin of a launch that is done: offsets are floats of ms (0.06 us at 1 s).
+#define SK_BUSY_KEEP 16u
+static void sk_timing_merge(sk_ctx *c, double b, double e)
+{
+    double add = e - b, mb = b, me = e;
+    std::vector<sk_span> keep;
+    for (const sk_span &s : c->busy) {
+        if (s.e < b || s.b > e) { keep.push_back(s); continue; }
+        add -= (e < s.e ? e : s.e) - (b > s.b ? b : s.b);            // (the stretches are disjoint: so are these overlaps)
+        if (s.b < mb) mb = s.b;
+        if (s.e > me) me = s.e;
+    }
+    if (add > 0.0) c->timed_ms += add;
+    size_t at = keep.size();
+    while (at > 0 && keep[at - 1].b > mb) at--;
+    keep.insert(keep.begin() + at, (sk_span){mb, me});
+    if (keep.size() > SK_BUSY_KEEP) keep.erase(keep.begin(), keep.end() - SK_BUSY_KEEP);
+    c->busy.swap(keep);
+}
+static void sk_timing_rebase(sk_ctx *c, hipEvent_t &e0, double at)      // e0, `at` ms after the base, becomes the base
+{
+    std::swap(c->ev_base, e0);
+    for (sk_span &s : c->busy) { s.b -= at; s.e -= at; }
+}
+static int sk_timing_add(sk_ctx *c, hipEvent_t &e0, hipEvent_t e1)
+{
+    float ms = 0.f, at = 0.f;
+    SK_HIP(c, hipEventElapsedTime(&ms, e0, e1));
+    c->timed_launches++;
+    if (!c->lane[1].stream) { c->timed_ms += ms; return SK_OK; }     // (lane 1 never used: what it always was)
+    SK_HIP(c, hipEventElapsedTime(&at, c->ev_base, e0));
+    sk_timing_merge(c, (double)at, (double)at + (double)ms);
+    if (at > 1000.f) sk_timing_rebase(c, e0, (double)at);
+    return SK_OK;
+}
+
+// a lane's oldest pending launch goes into the totals (waits for it: it is SK_EV_PAIRS launches old, or older than one that is)
+static int sk_timing_retire(sk_ctx *c, sk_lane &L)
+{
+    SK_HIP(c, hipEventSynchronize(L.ev[1]));
+    int trc = sk_timing_add(c, L.ev[0], L.ev[1]);
+    if (trc) return trc;
+    c->ev_free.push_back(L.ev[0]);
+    c->ev_free.push_back(L.ev[1]);
+    L.ev.erase(L.ev.begin(), L.ev.begin() + 2);
+    L.seq.erase(L.seq.begin());
     return SK_OK;
 }
 
@@ -248,7 +363,9 @@ extern "C" void sk_ctx_destroy(sk_ctx *c)
 {
     if (!c) return;
     hipSetDevice(c->device);
+    (void)sk_lanes_join(c);
     hipStreamSynchronize(c->stream);
+    if (c->lane[1].stream) { hipStreamSynchronize(c->lane[1].stream); hipStreamDestroy(c->lane[1].stream); }
     sk_comm_destroy(c);
     sk_table_release(c);
     for (int i = 0; i < SK_NSTAGE; i++) {
@@ -257,8 +374,11 @@ extern "C" void sk_ctx_destroy(sk_ctx *c)
         if (c->stage_done[i]) hipEventDestroy(c->stage_done[i]);
     }
     if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
-    for (hipEvent_t e : c->ev) hipEventDestroy(e);
+    for (sk_lane &L : c->lane) for (hipEvent_t e : L.ev) hipEventDestroy(e);
     for (hipEvent_t e : c->ev_free) hipEventDestroy(e);
+    if (c->ev_base) hipEventDestroy(c->ev_base);
+    if (c->lane_done) hipEventDestroy(c->lane_done);
+    if (c->lane_go) hipEventDestroy(c->lane_go);
     for (int i = 0; i < 64; i++) if (c->copied[i]) hipEventDestroy(c->copied[i]);
     if (c->read_done) hipEventDestroy(c->read_done);
     if (c->own_batch) sk_batch_destroy(c->own_batch);
@@ -268,7 +388,7 @@ extern "C" void sk_ctx_destroy(sk_ctx *c)
     for (sk_pin &q : c->pins) { if (q.registered) { hipHostUnregister(q.p); free(q.p); } else hipHostFree(q.p); }
     pthread_mutex_destroy(&c->pin_mu);
     hipFree(c->d_flags);
-    hipFree(c->d_oddlist);
+    for (sk_lane &L : c->lane) hipFree(L.d_oddlist);
     hipStreamDestroy(c->stream);
     delete c;
 }
@@ -282,6 +402,13 @@ extern "C" int sk_set_option(sk_ctx *c, const char *name, long value)
     if (!strcmp(name, "dev_alloc_uncached")) { c->dev_uncached = value != 0; return SK_OK; }
     if (!strcmp(name, "text_stage")) { c->no_text = value == 0; return SK_OK; }
     if (!strcmp(name, "pipeline")) { if (value < 0 || value > 2) return SK_E_ARG; c->pipeline = value; return SK_OK; }
+    if (!strcmp(name, "scan_lanes")) {
+        if (value < 1 || value > SK_LANES) return SK_E_ARG;
+        if (value == 1 && c->lane1_busy) { SK_HIP(c, hipSetDevice(c->device)); int rc = sk_lanes_join(c); if (rc) return rc; }
+        c->scan_lanes = value;
+        c->lane_next = 0;
+        return SK_OK;
+    }
 #ifdef SK_EXPERIMENTS
     if (!strcmp(name, "ablate")) { c->ablate = value; return SK_OK; }
 #else
@@ -309,6 +436,7 @@ extern "C" int sk_table_load_ex(sk_ctx *c, const uint64_t *keys, uint32_t nrows,
         }
     }
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
     sk_table_release(c);
 
@@ -322,7 +450,7 @@ extern "C" int sk_table_load_ex(sk_ctx *c, const uint64_t *keys, uint32_t nrows,
     SK_HIP(c, hipMemsetAsync(c->d_counts, 0, cbytes, c->stream));
     hipLaunchKernelGGL(sk_fill64, dim3(2048), dim3(256), 0, c->stream, (uint64_t *)c->d_keys, 2 * slots, SK_EMPTY64);
     SK_HIP(c, hipMemsetAsync(c->d_flags, 0, 16 * sizeof(uint32_t), c->stream));
-    c->flags_ready = false;
+    for (sk_lane &L : c->lane) L.flags_ready = false;
     if (nrows) {
         uint64_t *d_in = NULL;
         SK_HIP(c, hipMalloc((void **)&d_in, (size_t)nrows * sizeof(uint64_t)));
@@ -434,6 +562,7 @@ extern "C" int sk_table_load_text(sk_ctx *c, const uint32_t *text2, uint32_t nba
     uint32_t run = 0;
     for (size_t b = 0; b < nblk; b++) { rank[b].x = run; run += (uint32_t)__builtin_popcount(rank[b].y) + (uint32_t)__builtin_popcount(rank[b].z); }
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
     hipFree(c->d_text2); c->d_text2 = NULL;
     hipFree(c->d_rank); c->d_rank = NULL;
@@ -477,6 +606,7 @@ extern "C" int sk_table_build_from_text(sk_ctx *c, const uint32_t *text2, const 
     if (!c || !text2 || !startok || !nrows_out || ncols == 0 || ncols > 16) return SK_E_ARG;
     if (nbases < SK_K || nbases > 0x7FFFFF00u) return sk_fail(c, SK_E_ARG, "text of %u bases (a table slot holds 31 bits of position)", nbases);
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
     sk_table_release(c);
     // a build that fails midway (out of memory with many strains on one device) must leave neither its scratch nor half a table
@@ -511,7 +641,7 @@ static int sk_table_build_from_text_steps(sk_ctx *c, const uint32_t *text2, cons
     SK_HIP(c, hipMemsetAsync(c->d_text2, 0, words * 4, c->stream));
     SK_HIP(c, hipMemsetAsync(c->d_rank, 0, nblk * sizeof(sk_u4), c->stream));
     SK_HIP(c, hipMemsetAsync(c->d_flags, 0, 16 * sizeof(uint32_t), c->stream));
-    c->flags_ready = false;
+    for (sk_lane &L : c->lane) L.flags_ready = false;
     SK_HIP(c, hipMemcpyAsync(c->d_text2, text2, have * 4, hipMemcpyHostToDevice, c->stream));
     SK_HIP(c, hipMemcpyAsync(d_ok, startok, bwords * 4, hipMemcpyHostToDevice, c->stream));
     const dim3 grid((nbases + 255) / 256), block(256);
@@ -584,6 +714,7 @@ extern "C" int sk_table_export_keys_of(sk_ctx *c, const uint32_t *rows, uint32_t
     if (!c->d_keys_by_row) return sk_fail(c, SK_E_STATE, "no key list to export (sk_table_build_from_text first)");
     for (uint32_t i = 0; i < n; i++) if (rows[i] >= c->nrows) return sk_fail(c, SK_E_ARG, "row %u out of range", rows[i]);
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     void *d = NULL;
     SK_HIP(c, hipMalloc(&d, (size_t)n * 12));
     uint64_t *d_out = (uint64_t *)d;
@@ -614,6 +745,7 @@ static int sk_grid_ensure(sk_ctx *c)
 // reads or writes the counters calls this first; scans into another column do too.
 static int sk_diff_flush(sk_ctx *c)
 {
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }       // (both lanes add to the array and to the column)
     if (c->diff_col < 0 || !c->d_diff) { c->diff_col = -1; return SK_OK; }
     const uint32_t n = c->nrows + 1u, nb = (n + SK_DIFF_PER_BLOCK - 1u) / SK_DIFF_PER_BLOCK;
     hipLaunchKernelGGL(sk_diff_block_sums, dim3(nb), dim3(256), 0, c->stream, c->d_diff, n, c->d_diff_sums);
@@ -630,7 +762,7 @@ static int sk_scratch(sk_ctx *c, void **p, size_t *cap, size_t need);
 // launch main + wide kernels over one device-resident batch
 // packed_inv: the batch is in the host-packed form (sk_pack_stream) -- d_stream points at its code words, packed_inv at its masks
 static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, uint64_t emit_begin, uint32_t col,
-                          const sk_sink *tally_sink = NULL, const void *packed_inv = NULL)
+                          const sk_sink *tally_sink = NULL, const void *packed_inv = NULL, bool lane_scan = false)
 {
     if (nbytes <= emit_begin || c->nrows == 0) return SK_OK;        // (an empty key set: nothing can be counted)
     const uint64_t ntiles = (nbytes + SK_TILE - 1) / SK_TILE;
@@ -639,7 +771,7 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
     tv.nrows = c->nrows;
     tv.text2 = c->no_text ? NULL : c->d_text2; tv.rank = c->d_rank; tv.text_bases = c->text_bases;
     tv.slots = c->d_keys; tv.mask = (uint32_t)(((uint64_t)1 << c->slots_log2) - 1);
-    tv.oddlist = c->d_oddlist; tv.oddcap = c->odd_cap ? (uint32_t)c->odd_cap : SK_ODDCAP;
+    tv.oddcap = c->odd_cap ? (uint32_t)c->odd_cap : SK_ODDCAP;
     tv.grid1 = c->d_grid1; tv.grid2 = c->d_grid2;
     tv.grid1_blocks = c->grid1_blocks; tv.grid2_shift = 32u - c->grid2_blocks_log2;
     sk_wide_view wv;
@@ -660,30 +792,46 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
     }
     const dim3 grid((uint32_t)ntiles), block(SK_THREADS);
     if (!c->d_grid1) return sk_fail(c, SK_E_STATE, "no table loaded");
-    { int grc = sk_grid_ensure(c); if (grc) return grc; }
-
-    // [0] odd bytes seen, [2] listed chunks: two sets of four words taking turns -- this launch's byte-string kernel zeroes the other set
-    // for the next launch (both sets are zero after a table load)
-    if (!c->flags_ready) {                                    // (the first scan after a table was built: its kernels used the same words)
-        SK_HIP(c, hipMemsetAsync(c->d_flags, 0, 8 * sizeof(uint32_t), c->stream));
-        c->flags_ready = true;
+    // A count scan of a resident batch takes the lanes in turn; everything else runs on the context's stream (lane 0) behind both.
+    uint32_t li = 0;
+    if (lane_scan && !tally_sink && c->scan_lanes > 1 && !c->ablate && c->pipeline != 2 && !SK_PHASE_CLOCK) {     // (phase clocks are summed in lane 0's list)
+        if (c->grid_pending) { int jrc = sk_lanes_join(c); if (jrc) return jrc; }      // (the filters are filled on the context's stream)
+        li = c->lane_next;
+        c->lane_next ^= 1u;
+    } else {
+        int jrc = sk_lanes_join(c);
+        if (jrc) return jrc;
     }
-    c->flag_set ^= 1u;
-    uint32_t *const d_fl = c->d_flags + 4u * c->flag_set, *const d_fl_next = c->d_flags + 4u * (c->flag_set ^ 1u);
-    // timing: a begin/end event pair per launch from a small ring -- the oldest pair is added to the totals (its launch is
-    // long over, SK_EV_PAIRS launches later) and used again, so a program that never asks for the timing holds 128 events,
-    // not two per launch
+    { int grc = sk_grid_ensure(c); if (grc) return grc; }
+    if (li) {
+        int lrc = sk_lane1_init(c);
+        if (lrc) return lrc;
+        if (c->lane1_behind) {                                // the first scan on lane 1 after anything else on the context's stream
+            SK_HIP(c, hipEventRecord(c->lane_go, c->stream));
+            SK_HIP(c, hipStreamWaitEvent(c->lane[1].stream, c->lane_go, 0));
+            c->lane1_behind = false;
+        }
+        c->lane1_busy = true;
+    }
+    sk_lane &L = c->lane[li];
+    const hipStream_t st = L.stream;
+    tv.oddlist = L.d_oddlist;
+    // [0] odd bytes seen, [2] listed chunks: the lane's own four words -- its byte-string kernel leaves them zero for the lane's next launch
+    if (!L.flags_ready) {                                     // (the first scan after a table was built: its kernels used the same words)
+        SK_HIP(c, hipMemsetAsync(L.d_flags, 0, 4 * sizeof(uint32_t), st));
+        L.flags_ready = true;
+    }
+    uint32_t *const d_fl = L.d_flags;
+    // timing: a begin/end event pair per launch from a small ring per lane -- the lane's oldest pair is added to the totals (its
+    // launch is long over, SK_EV_PAIRS launches of this lane later: the wait below is never for the other lane's newest) and used
+    // again, so a program that never asks for the timing holds 128 events a lane, not two per launch
     hipEvent_t e0 = NULL, e1 = NULL;
     const bool timed = true;
-    if (c->ev.size() >= 2 * SK_EV_PAIRS) {
-        float ms = 0.f;
-        SK_HIP(c, hipEventSynchronize(c->ev[1]));
-        SK_HIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        c->timed_ms += ms;
-        c->timed_launches++;
-        c->ev_free.push_back(c->ev[0]);
-        c->ev_free.push_back(c->ev[1]);
-        c->ev.erase(c->ev.begin(), c->ev.begin() + 2);
+    if (L.ev.size() >= 2 * SK_EV_PAIRS) {                     // (launches are added up in the order they were made, whichever lane took them)
+        sk_lane &O = c->lane[li ^ 1u];
+        while (!O.seq.empty() && O.seq[0] < L.seq[0]) { int trc = sk_timing_retire(c, O); if (trc) return trc; }
+        int trc = sk_timing_retire(c, L);
+        if (trc) return trc;
     }
     if (c->ev_free.size() >= 2) {
         e1 = c->ev_free.back(); c->ev_free.pop_back();
@@ -692,7 +840,7 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
         SK_HIP(c, hipEventCreate(&e0));
         SK_HIP(c, hipEventCreate(&e1));
     }
-    SK_HIP(c, hipEventRecord(e0, c->stream));
+    SK_HIP(c, hipEventRecord(e0, st));
     // The partitioned pipeline (the level-1 question answered from LDS) is an experiment kept selectable (option
     // "pipeline" = 2; parity-tested): as measured it LOSES to the single kernel (0.43 against 0.34 ms per 0.6 Gbase at
     // 2 % strain reads; profiles/r02_lds_pipeline.txt) -- its one full pass over the stream plus the
@@ -706,8 +854,8 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
         const size_t b3 = (size_t)SK_BIN_P * SK_BIN_WORDS * 4;
         const uint64_t nslots = (uint64_t)1 << c->slots_log2;
         SK_HIP(c, hipMalloc((void **)&c->d_grid3, b3));
-        SK_HIP(c, hipMemsetAsync(c->d_grid3, 0, b3, c->stream));
-        hipLaunchKernelGGL(sk_grid3_insert, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, c->stream, (const sk_u4 *)c->d_keys, nslots, c->d_grid3);
+        SK_HIP(c, hipMemsetAsync(c->d_grid3, 0, b3, st));
+        hipLaunchKernelGGL(sk_grid3_insert, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, st, (const sk_u4 *)c->d_keys, nslots, c->d_grid3);
     }
     if (piped) {
         const uint64_t ntiles_bin = (nbytes + SK_BIN_TILE - 1) / SK_BIN_TILE;
@@ -715,8 +863,8 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
         if ((rc = sk_scratch(c, &c->p_bins, &c->p_bins_cap, (size_t)ntiles_bin * SK_BIN_P * SK_BIN_CAP * 4)) != SK_OK) return rc;
         if ((rc = sk_scratch(c, &c->p_binn, &c->p_binn_cap, (size_t)ntiles_bin * SK_BIN_P)) != SK_OK) return rc;
         if ((rc = sk_scratch(c, &c->p_cand, &c->p_cand_cap, (size_t)ntiles_bin * SK_BIN_CH + 64)) != SK_OK) return rc;
-        SK_HIP(c, hipMemsetAsync(c->p_cand, 0, (size_t)ntiles_bin * SK_BIN_CH + 64, c->stream));
-        hipLaunchKernelGGL(sk_bin, dim3((uint32_t)ntiles_bin), dim3(256), 0, c->stream, d_stream, nbytes, tv,
+        SK_HIP(c, hipMemsetAsync(c->p_cand, 0, (size_t)ntiles_bin * SK_BIN_CH + 64, st));
+        hipLaunchKernelGGL(sk_bin, dim3((uint32_t)ntiles_bin), dim3(256), 0, st, d_stream, nbytes, tv,
                            (uint32_t *)c->p_bins, (uint8_t *)c->p_binn, (uint32_t)ntiles_bin, (uint8_t *)c->p_cand, d_fl);
         // one workgroup per CU at a time (128 KiB of LDS each): a few shares per partition keep all 256 CUs busy
         uint32_t splits = ntiles_bin >= 4096 ? 4u : ntiles_bin >= 1024 ? 2u : 1u;
@@ -725,23 +873,23 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
             SK_HIP(c, hipFuncSetAttribute((const void *)sk_lds_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SK_BIN_WORDS * 4)));
             lds_attr = true;
         }
-        hipLaunchKernelGGL(sk_lds_probe, dim3(SK_BIN_P * splits), dim3(1024), SK_BIN_WORDS * 4, c->stream, (const uint32_t *)c->d_grid3,
+        hipLaunchKernelGGL(sk_lds_probe, dim3(SK_BIN_P * splits), dim3(1024), SK_BIN_WORDS * 4, st, (const uint32_t *)c->d_grid3,
                            (const uint32_t *)c->p_bins, (const uint8_t *)c->p_binn, (uint32_t)ntiles_bin, splits, (uint8_t *)c->p_cand);
         d_cand = (const uint8_t *)c->p_cand;
     }
-#define SK_LAUNCH_GRID(T, A, C) hipLaunchKernelGGL((sk_scan_grid<T, A, C>), grid, block, 0, c->stream, \
+#define SK_LAUNCH_GRID(T, A, C) hipLaunchKernelGGL((sk_scan_grid<T, A, C>), grid, block, 0, st, \
                                                    d_stream, nbytes, emit_begin, tv, sink, d_fl, d_cand)
     if (packed_inv) {
         if (c->ablate) return sk_fail(c, SK_E_UNSUPPORTED, "no ablations on packed batches");
         if (tally_sink && tally_sink->ns)
-            hipLaunchKernelGGL((sk_scan_grid<true, 0, false, true, true>), grid, block, 0, c->stream, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
+            hipLaunchKernelGGL((sk_scan_grid<true, 0, false, true, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
         else if (tally_sink)
-            hipLaunchKernelGGL((sk_scan_grid<true, 0, false, false, true>), grid, block, 0, c->stream, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
+            hipLaunchKernelGGL((sk_scan_grid<true, 0, false, false, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
         else
-            hipLaunchKernelGGL((sk_scan_grid<false, 0, false, false, true>), grid, block, 0, c->stream, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
+            hipLaunchKernelGGL((sk_scan_grid<false, 0, false, false, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
     }
     else if (tally_sink && tally_sink->ns)
-        hipLaunchKernelGGL((sk_scan_grid<true, 0, false, true>), grid, block, 0, c->stream, d_stream, nbytes, emit_begin, tv, sink, d_fl, d_cand);
+        hipLaunchKernelGGL((sk_scan_grid<true, 0, false, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, d_cand);
     else if (piped && tally_sink) SK_LAUNCH_GRID(true, 0, true);
 #ifdef SK_EXPERIMENTS
     else if (piped && c->ablate == 7) SK_LAUNCH_GRID(false, 7, true);
@@ -762,22 +910,23 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
     else                     SK_LAUNCH_GRID(false, 0, false);
 #undef SK_LAUNCH_GRID
     if (timed) {
-        SK_HIP(c, hipEventRecord(e1, c->stream));
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
+        SK_HIP(c, hipEventRecord(e1, st));
+        L.ev.push_back(e0);
+        L.ev.push_back(e1);
+        L.seq.push_back(c->launch_seq++);
     }
     uint64_t wblocks = (nbytes - emit_begin + 255) / 256;
     if (wblocks > 2048) wblocks = 2048;                        // (grid-stride: eight workgroups per CU; with nothing to do -- the usual case -- the launch is over in 3 us)
-    if (wblocks == 0) { wblocks = 1; }                        // (the kernel also readies the next launch's flag words)
+    if (wblocks == 0) { wblocks = 1; }
     if (tally_sink && tally_sink->ns)
-        hipLaunchKernelGGL((sk_scan_wide<true, true>), dim3((uint32_t)wblocks), dim3(256), 0, c->stream,
-                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl, d_fl_next);
+        hipLaunchKernelGGL((sk_scan_wide<true, true>), dim3((uint32_t)wblocks), dim3(256), 0, st,
+                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl);
     else if (tally_sink)
-        hipLaunchKernelGGL(sk_scan_wide<true>, dim3((uint32_t)wblocks), dim3(256), 0, c->stream,
-                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl, d_fl_next);
+        hipLaunchKernelGGL(sk_scan_wide<true>, dim3((uint32_t)wblocks), dim3(256), 0, st,
+                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl);
     else
-        hipLaunchKernelGGL(sk_scan_wide<false>, dim3((uint32_t)wblocks), dim3(256), 0, c->stream,
-                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl, d_fl_next);
+        hipLaunchKernelGGL(sk_scan_wide<false>, dim3((uint32_t)wblocks), dim3(256), 0, st,
+                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl);
     SK_HIP(c, hipGetLastError());
     return SK_OK;
 }
@@ -1277,6 +1426,7 @@ extern "C" int sk_union_sync(sk_union *u)
     if (!u) return SK_E_ARG;
     sk_ctx *c = u->uc;
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
     c->t_inflight_nrec = 0;
     return SK_OK;
@@ -1364,7 +1514,7 @@ extern "C" int sk_scan_device(sk_ctx *c, const void *dev_stream, uint64_t nbytes
     if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
     if (((uintptr_t)dev_stream & 15u) != 0) return sk_fail(c, SK_E_ARG, "device stream must be 16-byte aligned");
     SK_HIP(c, hipSetDevice(c->device));
-    return sk_launch_scan(c, (const uint8_t *)dev_stream, nbytes, 0, col);
+    return sk_launch_scan(c, (const uint8_t *)dev_stream, nbytes, 0, col, NULL, NULL, true);
 }
 
 // sk_scan_device for a batch that lies in device memory in the PACKED form (sk_pack_stream's layout: the code words, then the masks;
@@ -1378,7 +1528,7 @@ extern "C" int sk_scan_device_packed(sk_ctx *c, const void *dev_packed, uint64_t
     if (((uintptr_t)dev_packed & 3u) != 0) return sk_fail(c, SK_E_ARG, "device batch must be 4-byte aligned");
     SK_HIP(c, hipSetDevice(c->device));
     const uint64_t nch = (nbytes + 15u) >> 4;
-    return sk_launch_scan(c, (const uint8_t *)dev_packed, nbytes, 0, col, NULL, (const uint8_t *)dev_packed + nch * 4u);
+    return sk_launch_scan(c, (const uint8_t *)dev_packed, nbytes, 0, col, NULL, (const uint8_t *)dev_packed + nch * 4u, true);
 }
 
 static int sk_stage_init(sk_ctx *c)
@@ -1458,7 +1608,7 @@ extern "C" int sk_pinned_free(sk_ctx *c, void *p)
 {
     if (!c) return SK_E_ARG;
     if (!p) return SK_OK;
-    if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return SK_E_HIP;   // (nothing reads it any more)
+    if (hipSetDevice(c->device) != hipSuccess || sk_lanes_join(c) != SK_OK || hipStreamSynchronize(c->stream) != hipSuccess) return SK_E_HIP;   // (nothing reads it any more)
     int rc = SK_E_ARG;
     pthread_mutex_lock(&c->pin_mu);
     for (sk_pin &q : c->pins) if (q.p == p && q.used) { q.used = false; rc = SK_OK; break; }
@@ -1595,6 +1745,7 @@ extern "C" int sk_sync(sk_ctx *c)
 {
     if (!c) return SK_E_ARG;
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
     return SK_OK;
 }
@@ -1709,16 +1860,26 @@ extern "C" int sk_scan_timing(sk_ctx *c, double *total_ms, uint64_t *launches, i
 {
     if (!c) return SK_E_ARG;
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i + 1 < c->ev.size(); i += 2) {
-        float ms = 0.f;
-        SK_HIP(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
-        c->timed_ms += ms;
-        c->timed_launches++;
-        c->ev_free.push_back(c->ev[i]);
-        c->ev_free.push_back(c->ev[i + 1]);
+    if (!c->lane[1].stream) {
+        for (size_t i = 0; i + 1 < c->lane[0].ev.size(); i += 2) { int trc = sk_timing_add(c, c->lane[0].ev[i], c->lane[0].ev[i + 1]); if (trc) return trc; }
+    } else {                                                  // both lanes' pending launches, merged in the order they began
+        struct span { double b, e; hipEvent_t *e0; };
+        std::vector<span> sp;
+        for (sk_lane &L : c->lane)
+            for (size_t i = 0; i + 1 < L.ev.size(); i += 2) {
+                float ms = 0.f, at = 0.f;
+                SK_HIP(c, hipEventElapsedTime(&ms, L.ev[i], L.ev[i + 1]));
+                SK_HIP(c, hipEventElapsedTime(&at, c->ev_base, L.ev[i]));
+                sp.push_back((span){(double)at, (double)at + (double)ms, &L.ev[i]});
+            }
+        std::sort(sp.begin(), sp.end(), [](const span &x, const span &y) { return x.b < y.b; });
+        for (const span &x : sp) { sk_timing_merge(c, x.b, x.e); c->timed_launches++; }
+        if (!sp.empty() && sp.back().b > 1000.0) sk_timing_rebase(c, *sp.back().e0, sp.back().b);
     }
-    c->ev.clear();
+    for (sk_lane &L : c->lane) { c->ev_free.insert(c->ev_free.end(), L.ev.begin(), L.ev.end()); }
+    for (sk_lane &L : c->lane) { L.ev.clear(); L.seq.clear(); }
     if (total_ms) *total_ms = c->timed_ms;
     if (launches) *launches = c->timed_launches;
     if (reset) { c->timed_ms = 0; c->timed_launches = 0; }
@@ -1902,6 +2063,7 @@ extern "C" int sk_dev_free(sk_ctx *c, void *dev)
 {
     if (!c) return SK_E_ARG;
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }       // (a lane may still read it)
     SK_HIP(c, hipStreamSynchronize(c->stream));
     SK_HIP(c, hipFree(dev));
     return SK_OK;
@@ -1911,6 +2073,7 @@ extern "C" int sk_dev_upload(sk_ctx *c, void *dev, const void *host, uint64_t nb
 {
     if (!c || !dev || !host) return SK_E_ARG;
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }       // (a lane may still read it)
     SK_HIP(c, hipMemcpyAsync(dev, host, nbytes, hipMemcpyHostToDevice, c->stream));
     SK_HIP(c, hipStreamSynchronize(c->stream));
     return SK_OK;
@@ -1920,6 +2083,7 @@ extern "C" int sk_dev_download(sk_ctx *c, void *host, const void *dev, uint64_t 
 {
     if (!c || !dev || !host) return SK_E_ARG;
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipMemcpyAsync(host, dev, nbytes, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(c, hipStreamSynchronize(c->stream));
     return SK_OK;
@@ -1931,8 +2095,9 @@ extern "C" int sk_debug_phase_clock(sk_ctx *c, unsigned long long out[8])
 {
     if (!c || !out) return SK_E_ARG;
     SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
-    unsigned long long *d = (unsigned long long *)(c->d_oddlist + (c->odd_cap ? c->odd_cap : SK_ODDCAP) - 1024u), h[512];
+    unsigned long long *d = (unsigned long long *)(c->lane[0].d_oddlist + (c->odd_cap ? c->odd_cap : SK_ODDCAP) - 1024u), h[512];
     SK_HIP(c, hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost));
     SK_HIP(c, hipMemset(d, 0, sizeof h));
     for (int k = 0; k < 8; k++) { out[k] = 0; for (int s = 0; s < 64; s++) out[k] += h[s * 8 + k]; }
