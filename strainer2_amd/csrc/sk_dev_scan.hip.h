@@ -318,6 +318,9 @@ __device__ __forceinline__ void sk_decode4o(uint32_t w, uint32_t &codes8, uint32
 // bit 7 of the BYTE instead of bit 7 of u ^ e (one instruction less: where e = 0xFF the low seven bits already differ -- a byte
 // whose low seven bits are all ones selects 'G' --, and where e is a letter its bit 7 is clear), with the ANDs and ORs folded into
 // three-input bit operations (v_bitop3_b32); (3) the case fold is two instructions, the odd-byte word two per input word.
+// Tested over all 256 byte values at every position of the chunk, and over pairs of foreign bytes in one word, in COUNT, TALLY and
+// union form: tests/test_byte_alphabet_gpu.py (sk_decode4 through "pipeline" = 2, the host's pre-pack in tests/test_byte_alphabet_host.py).
+// Any rewrite of this function must keep that module green.
 __device__ __forceinline__ void sk_decode16(const sk_u4 v, uint32_t &code32, uint32_t &inv16, uint32_t &oddw)
 {
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};

@@ -232,3 +232,101 @@ def tally_reads(rng: random.Random, strains: list, nreads: int, junk: bool) -> t
             b = b.lower()
         recs.append(bytes(b))
     return recs, uk
+
+
+# ---- byte-alphabet worlds (tests/test_byte_alphabet_gpu.py, tests/test_byte_alphabet_host.py) -----------------------
+# Every decision the scan makes about a byte (base, hard breaker, or a byte for the byte-string kernel) is a function of the byte:
+# these worlds hand it all 256 values, at every position of the 16-byte chunk and next to every kind of neighbour.
+ALPHABET_READ = 93                     # bases of a read: 46, the foreign byte, 46 -- 16 windows end before it, 31 hold it, 16 start behind it
+ALPHABET_AT = 46
+# World B's representative bytes, one per hazard: the separator and NUL, N, bases and U in both cases, IUPAC letters, symbols of the
+# complement map, '*' ('\n' + bit 5), bytes one bit from a letter or from NUL, the ends of the letter ranges, 0x7F, and bytes at or
+# above 0x80 that equal '\n', 'A', 'N' or nothing in their low seven bits
+ALPHABET_PAIR_SET = bytes([0x00, 0x0A]) + b"NnAcGtUuRK.-*" + bytes([0x01, 0x21, 0x40, 0x60, 0x5B, 0x7B, 0x49, 0x51, 0x7F,
+                                                                   0x80, 0x8A, 0xC1, 0xCE, 0xE3, 0xFF])
+
+
+def _alphabet_piece(rng: random.Random, strain: bytes, want=None) -> bytes:
+    """ALPHABET_READ bases of the strain, either strand; want: the base at ALPHABET_AT must be this one"""
+    while True:
+        a = rng.randrange(len(strain) - ALPHABET_READ + 1)
+        r = strain[a:a + ALPHABET_READ]
+        if rng.random() < 0.5:
+            r = revcomp(r)
+        if want is None or r[ALPHABET_AT] == want:
+            return r
+
+
+def _alphabet_place(rng: random.Random, recs: list, off: int, read: bytes, mod16: int) -> int:
+    """append `read` behind a filler record of 1..16 random bases (too short for a window) sized so that the read's byte
+    ALPHABET_AT lands on a stream offset that is mod16 modulo 16; returns the offset behind the read's newline"""
+    f = (mod16 - off - 1 - ALPHABET_AT) % 16 or 16
+    recs += [rand_dna(rng, f), read]
+    return off + f + 1 + len(read) + 1
+
+
+def alphabet_world_a(seed=4601, phases=range(16), leave_out=b""):
+    """World A: one foreign byte, every value, every chunk phase.  Returns (strain, records, cases): the strain is 600 random
+    bases; for every byte b (but those in leave_out) and every phase j of `phases` one read of 93 strain bases (either strand)
+    with b at index 46, placed so that b's offset in b"\\n".join(records) + b"\\n" is j modulo 16; cases[i] = (b, j, index of
+    the read in records, the base b replaced).  The U and u reads replace a T, so that some of their windows can hit; at the even
+    phases a base replaces itself (either case: all windows hit), and a byte that equals a base in its low seven bits and for the
+    case bit replaces that base (taken for the base, it would make 31 windows hit that must not)."""
+    rng = random.Random(seed)
+    strain = rand_dna(rng, 600)
+    recs, cases, off = [], [], 0
+    for b in range(256):
+        if b in leave_out:
+            continue
+        for j in phases:
+            want = None
+            if b in b"Uu":
+                want = ord("T")
+            elif j % 2 == 0 and b & 0x5F in b"ACGT":                # a base, or a byte that equals one in its low seven bits with the case folded
+                want = b & 0x5F
+            r = bytearray(_alphabet_piece(rng, strain, want))
+            was = r[ALPHABET_AT]
+            r[ALPHABET_AT] = b
+            off = _alphabet_place(rng, recs, off, bytes(r), j)
+            cases.append((b, j, len(recs) - 1, was))
+    return strain, recs, cases
+
+
+def alphabet_world_b(seed=4602):
+    """World B: two foreign bytes side by side, every ordered pair of ALPHABET_PAIR_SET at indices 46 and 47 of a read, the first
+    on every byte of its 32-bit word (the fourth: the second byte opens the next word, for every fourth pair the next chunk).
+    Returns (strain, records, cases) with cases[i] = (b1, b2, offset of b1 modulo 16)."""
+    rng = random.Random(seed)
+    strain = rand_dna(rng, 600)
+    recs, cases, off, n = [], [], 0, 0
+    for b1 in ALPHABET_PAIR_SET:
+        for b2 in ALPHABET_PAIR_SET:
+            for w in range(4):
+                r = bytearray(_alphabet_piece(rng, strain))
+                r[ALPHABET_AT], r[ALPHABET_AT + 1] = b1, b2
+                mod16 = w + 4 * (n % 4)
+                n += w == 3
+                off = _alphabet_place(rng, recs, off, bytes(r), mod16)
+                cases.append((b1, b2, mod16))
+    return strain, recs, cases
+
+
+def alphabet_world_c(seed=4603):
+    """World C, the strain's side: for every byte b but NUL and the separator one strain record of 45 random bases, b, 45 random
+    bases.  Returns [(b, record)]."""
+    rng = random.Random(seed)
+    return [(b, rand_dna(rng, 45) + bytes([b]) + rand_dna(rng, 45)) for b in range(1, 256) if b != 0x0A]
+
+
+def alphabet_world_c_reads(records, reverse: bool, cs=range(256)) -> bytes:
+    """World C's reads: every record of alphabet_world_c with its byte 45 replaced by every c of `cs`; reverse: the record
+    reversed and its A/C/G/T complemented first (45 is its own mirror image in 91 bytes).  One read a line, record after
+    record, c ascending."""
+    import numpy as np
+    cs = np.array(list(cs), dtype=np.uint8)
+    out = np.empty((len(records), len(cs), 92), dtype=np.uint8)
+    for i, (_b, rec) in enumerate(records):
+        out[i, :, :91] = np.frombuffer(revcomp(rec) if reverse else rec, dtype=np.uint8)
+    out[:, :, 45] = cs
+    out[:, :, 91] = 0x0A
+    return out.tobytes()

@@ -35,8 +35,10 @@ def starts_of(recs):
 class OracleStrain:
     """one strain's key set in the oracle (rows in the order the product numbers them: callers assert it)"""
 
-    def __init__(self, sstream):
-        self.t = _oracle.OracleTable(ncols=3)
+    def __init__(self, sstream, capacity=8000000):
+        """capacity: the table's first size (the product's initial_slots: the row order follows it); a small one makes the
+        per-record passes over the table cheap"""
+        self.t = _oracle.OracleTable(capacity=capacity, ncols=3)
         assert self.t.build_stream(sstream, default=1, incr=0, short_policy=1) == 0
         self.keys = self.t.rows()[0]
         self.nrows = len(self.keys)
