@@ -293,8 +293,8 @@ int sk_scan_timing(sk_ctx *ctx, double *total_ms, uint64_t *launches, int reset)
  * section 4), "odd_list_cap" (tests), "scan_lanes" (may be set at any time; 2, the default: back-to-back sk_scan_device /
  * sk_scan_device_packed calls take two streams in turn, so that a launch starts while the one before it drains -- every
  * other call of the context waits for both, results are the same; 1 = all of them on the context's one stream, for A/B
- * runs and tests; the environment variable SK_SCAN_LANES=1 does the same for programs that set no options), "dev_alloc_uncached" (experiment: no effect), "ablate" (timing
- * experiments only: kernel variants that skip memory stages and give WRONG counts).
+ * runs and tests; the environment variable SK_SCAN_LANES=1 does the same for programs that set no options), "dev_alloc_uncached" (experiment:
+ * non-zero = sk_dev_alloc hands out memory the L2 does not keep), "ablate" (accepted as 0 only: the kernel variants it chose were retired).
  * Unknown name -> SK_E_ARG. */
 int sk_set_option(sk_ctx *ctx, const char *name, long value);
 

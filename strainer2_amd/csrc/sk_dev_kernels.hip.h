@@ -70,7 +70,7 @@ void sk_scan_wide(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
         if (opure) {                                   // e.g. a window with U whose revcomp wins
             uint64_t key = 0;
             for (int i = 0; i < SK_K; i++) key = (key << 2) | sk_code((uint8_t)o[i]);
-            sk_probe<TALLY, false, UNION>(key, table, sink, (uint32_t)p);
+            sk_probe<TALLY, UNION>(key, table, sink, (uint32_t)p);
         } else if (wide.nwide) {
             uint32_t slot = sk_hash_wide(o) & wide.wmask;
             for (;;) {
@@ -79,7 +79,7 @@ void sk_scan_wide(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
                 const char *cand = wide.keys31 + (size_t)(e - 1u) * 32u;
                 bool same = true;
                 for (int i = 0; i < SK_K; i++) same &= (cand[i] == o[i]);
-                if (same) { sk_on_hit<TALLY, false, UNION>(sink, wide.rows[e - 1u], (uint32_t)p); break; }
+                if (same) { sk_on_hit<TALLY, UNION>(sink, wide.rows[e - 1u], (uint32_t)p); break; }
                 slot = (slot + 1u) & wide.wmask;
             }
         }

@@ -15,24 +15,17 @@ static_assert(SK_THREADS <= 256 && SK_THREADS % 64 == 0, "a tile's window number
 #define SK_REC_DW       12                  // per record: 8 code words (u32) + 8 invalid masks (u16) = 48 B;
                                             // 12-dword lane stride keeps ds_read_b128 conflict-free
 #define SK_NCHUNK       (SK_NREC * SK_SPAN_CH)
-#ifndef SK_STREAM_POLICY
-#define SK_STREAM_POLICY 0
-#endif
-#define SK_NCHUNK_GRID  (SK_NCHUNK + 1)
+#define SK_NCHUNK_GRID  (SK_NCHUNK + 1)    // grid kernel: plus the chunk after the tile
 #ifndef SK_AGG_LOG2
 #define SK_AGG_LOG2     8
 #endif
 #define SK_AGG          (1u << SK_AGG_LOG2) // per-workgroup table of rows already counted in the tile
 #define SK_UNION_EAGER  16384u              // union tally: records and log entries that travel back with the counters (320 KiB of page-locked memory)
 #define SK_EV_PAIRS     64u                 // launches whose timing events are kept before they are added up
-#define SK_ODDCAP       (1u << 20)          // list of chunks with odd bytes; beyond it the byte-string kernel scans everything     // grid kernel: plus the chunk after the tile
-#ifndef SK_CHUNK_REJECT
-#define SK_CHUNK_REJECT 1                   // stage 2: three filter questions per differing base before its ~31 windows go one by one
-#endif
+#define SK_ODDCAP       (1u << 20)          // list of chunks with odd bytes; beyond it the byte-string kernel scans everything
 #ifndef SK_ANCHOR_CH
 #define SK_ANCHOR_CH    8u                  // stage 2: one table probe per this many consecutive surviving chunks (and the first); 2: -10 %, 4: -1 %
 #endif
-//                 // stage 2: one hash probe per this many consecutive windows
 
 typedef uint32_t sk_u4 __attribute__((ext_vector_type(4)));
 
@@ -161,10 +154,9 @@ __device__ __forceinline__ uint32_t sk_record_of(const sk_sink &k, uint32_t pos)
     return lo;
 }
 
-template <bool TALLY, bool NOATOMIC = false, bool UNION = false>
+template <bool TALLY, bool UNION = false>
 __device__ __forceinline__ void sk_on_hit(const sk_sink &k, uint32_t row, uint32_t pos)
 {
-    if (NOATOMIC) { if (row == 0x7FFFFFFFu) k.counts[0] = pos; return; }      // timing experiment only
     if (!TALLY) { atomicAdd(&k.counts[row], 1u); return; }
     const uint32_t lo = sk_record_of(k, pos);
     if (UNION) {                                                    // (lane by lane: only sk_scan_wide comes this way)
@@ -257,14 +249,14 @@ __device__ __forceinline__ uint32_t sk_find(uint64_t canon, const sk_table_view 
 }
 
 // stage 2 for one window: slot from the k-mer hash, linear probing, 62-bit compare
-template <bool TALLY, bool NOATOMIC = false, bool UNION = false>
+template <bool TALLY, bool UNION = false>
 __device__ __forceinline__ void sk_probe(uint64_t canon, const sk_table_view &t, const sk_sink &k, uint32_t pos)
 {
     uint32_t slot = sk_slot0(sk_khash(canon), t.mask);
     for (;;) {
         const sk_u4 e = t.slots[slot];
         const uint64_t key = sk_slot_key(e);
-        if (key == canon) { sk_on_hit<TALLY, NOATOMIC, UNION>(k, e.z, pos); return; }
+        if (key == canon) { sk_on_hit<TALLY, UNION>(k, e.z, pos); return; }
         if (key == SK_EMPTY64) return;
         slot = (slot + 1u) & t.mask;
     }
@@ -360,23 +352,6 @@ __device__ __forceinline__ uint32_t sk_chunk_has_odd_byte(const sk_u4 v, uint32_
     return odd;
 }
 
-#ifndef SK_PRIO_BASE
-#define SK_PRIO_BASE 0                       // ... the decode section's priority
-#endif
-#ifndef SK_PRIO_P2
-#define SK_PRIO_P2 SK_PRIO_BASE              // ... phase 2's (records read, hashes, the eight lookups issued)
-#endif
-#ifndef SK_PRIO_TAIL
-#define SK_PRIO_TAIL SK_PRIO_P2              // ... everything behind that
-#endif
-#ifndef SK_PRIO_LVL
-#define SK_PRIO_LVL 3
-#endif
-#ifndef SK_PRIO
-#define SK_PRIO 1                            // wave priority (s_setprio): 1 = raised to SK_PRIO_LVL while a wave issues phase 1's stream loads, back to SK_PRIO_BASE
-                                             // for the decode; 4 = kept up until the barrier.  A wave that starts a tile gets its nine loads out at once instead of
-                                             // taking turns with the waves that decode: 0.724 -> 0.645 ms at cfg 2 (profiles/r03_kernel_experiments.txt, item 14)
-#endif
 #ifndef SK_SEED2_MIN
 #define SK_SEED2_MIN 128                    // stage 2: in a wave with at least this many surviving chunks (of 512: a stretch of strain reads) a stretch without a seed
                                             // tries one more window before its windows go one by one; 0 = never, 1 = always.  Round 3 measured the compile-time
@@ -385,19 +360,9 @@ __device__ __forceinline__ uint32_t sk_chunk_has_odd_byte(const sk_u4 v, uint32_
 #endif
 #ifndef SK_RUN_PASS
 #define SK_RUN_PASS 5                      // phase 2: this many level-1 survivors in a row (two more in a union table) go to stage 2 unquestioned;
-                                           // 0 = never.  Measured (profiles/r03_kernel_experiments.txt, item 10): 3 costs 6.5 % with no strain reads (runs of three
+                                           // at least 1.  Measured (profiles/r03_kernel_experiments.txt, item 10): 3 costs 6.5 % with no strain reads (runs of three
                                            // false positives are frequent enough to send a wave in six down stage 2's slow path), 5 costs nothing there
                                            // and saves 3 % when every read is a strain read, 0.3 % at cfg 2
-#endif
-#ifndef SK_PHASE_CLOCK
-#define SK_PHASE_CLOCK 0                    // experiment: wave-cycles per phase of the scan kernel, summed into the last words of the odd list (sk_debug_phase_clock)
-#endif
-#if SK_PHASE_CLOCK
-#define SK_PHASE(k) do { if (!TALLY && !CAND) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        if (lane == 0u) atomicAdd((unsigned long long *)(table.oddlist + table.oddcap - 1024u) + (((blockIdx.x * SK_WAVES + (tid >> 6)) & 63u) * 8u + (k)), now_ - pc_last); \
-        pc_last = __builtin_amdgcn_s_memtime(); } } while (0)
-#else
-#define SK_PHASE(k) do { } while (0)
 #endif
 __device__ __forceinline__ uint32_t sk_revcomp32(uint32_t x)              // 16 packed bases
 {
@@ -524,15 +489,7 @@ __device__ __forceinline__ uint32_t sk_chunk_inv(const uint32_t *rec, uint32_t c
 // the read bases are touched once: keep them from pushing the filter out of the L2
 __device__ __forceinline__ sk_u4 sk_stream_load(const sk_u4 *p)
 {
-#if SK_STREAM_POLICY == 0
     return __builtin_nontemporal_load(p);
-#elif SK_STREAM_POLICY == 1
-    return *p;
-#else
-    sk_u4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1 nt\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-    return v;
-#endif
 }
 
 // the first `keep` (< 16) bytes of a chunk, '\n' behind them
@@ -565,13 +522,10 @@ __device__ __forceinline__ sk_u4 sk_load_chunk(const uint8_t *__restrict__ strea
 // batch, non-zero for the chunks the LDS-resident filter slices could not rule out; only those chunks (and the lines
 // around them) are read and looked at.
 // Scalar registers decide how many workgroups a CU admits: <= 80 -> 8 of these 256-thread groups, 81..96 -> 7, 97..112 -> 6
-// (MI355X_MICROARCH.md, "Residency").  The COUNT kernel is held at 80, the TALLY kernels at 96 (round 3: 100 and 94 = 6 and 7 groups).
-template <bool TALLY, int ABLATE, bool CAND, bool UNION = false, bool PACKED = false>
-#if defined(SK_NO_SGPR_CAP)                                       // (A/B builds: round 3's register budget -- TALLY 100 scalar registers = 6 groups per CU, UNION 94 = 7)
-__global__ __launch_bounds__(SK_THREADS)
-#else
+// (MI355X_MICROARCH.md, "Residency").  Every form, COUNT and TALLY alike, is held at 80 (uncapped, round 3's TALLY kernel took 100 and
+// its union form 94: 6 and 7 groups).
+template <bool TALLY, bool CAND, bool UNION = false, bool PACKED = false>
 __global__ __launch_bounds__(SK_THREADS) __attribute__((amdgpu_num_sgpr(80)))
-#endif
 void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t emit_begin,
                   sk_table_view table, sk_sink sink, uint32_t *__restrict__ flags, const uint8_t *__restrict__ cand)
 {
@@ -585,9 +539,6 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
-#if SK_PHASE_CLOCK
-    unsigned long long pc_last = __builtin_amdgcn_s_memtime();
-#endif
     __shared__ uint32_t hl_n[2];                                  // TALLY: the hit log's LDS share (agg is free in that mode)
     if (!TALLY)
         for (uint32_t i = tid; i < SK_AGG; i += SK_THREADS) agg[i] = make_uint2(0xFFFFFFFFu, 0u);   // (visible after phase 1's barrier)
@@ -601,14 +552,13 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
 
     // A tile's stream loads: all of a thread's 16-byte loads are issued together (nine HBM latencies in flight instead of one
     // after the other), at raised wave priority -- a wave that starts a tile must not take turns, instruction by instruction, with
-    // the waves that decode or hash (round 3).  Tiles at the ends of the batch mask what lies outside it.
+    // the waves that decode or hash: priority 3 while the loads are issued, back to 0 for the decode, 0.724 -> 0.645 ms at cfg 2
+    // (round 3; profiles/r03_kernel_experiments.txt, item 14).  Tiles at the ends of the batch mask what lies outside it.
     constexpr int NIT = CAND ? 1 : (SK_NCHUNK_GRID + SK_THREADS - 1) / SK_THREADS;
     sk_u4 vv[NIT];
     auto issue_loads = [&](uint64_t t0) {
         const bool inside = t0 >= SK_SPAN && t0 + SK_TILE + 16u <= nbytes;      // (workgroup-uniform)
-#if SK_PRIO & 1
-        __builtin_amdgcn_s_setprio(SK_PRIO_LVL);
-#endif
+        __builtin_amdgcn_s_setprio(3);
         if (inside) {
     #pragma unroll
             for (int it = 0; it < NIT; it++) {
@@ -633,9 +583,7 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
                 vv[it] = v;
             }
         }
-#if (SK_PRIO & 5) == 1
-        __builtin_amdgcn_s_setprio(SK_PRIO_BASE);
-#endif
+        __builtin_amdgcn_s_setprio(0);
     };
     if (!CAND && !PACKED) issue_loads(tile0);
 
@@ -669,7 +617,6 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
         }
     } else
     if (!CAND) {
-        SK_PHASE(0);                                                 // start -> the tile's loads issued
     #pragma unroll
         for (int it = 0; it < NIT; it++) {
             const uint32_t c = tid + (uint32_t)it * SK_THREADS;
@@ -700,7 +647,6 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
         own = (own | (own >> 1) | (own >> 2) | (own >> 4)) & 0x0101010101010101ull;          // (any non-zero byte value of 1..0x17)
         candm = (uint32_t)((own * 0x0102040810204080ull) >> 56);
         const uint32_t before = c8 > 0 && c8 - 1u < nch ? cand[c8 - 1u] : 0u, after = c8 + SK_SPAN_CH < nch ? cand[c8 + SK_SPAN_CH] : 0u;
-        if (ABLATE == 7) { if (own == 0x123456789ull && before + after == 77u) flags[3] = 1u; return; }    // timing: the candidate map alone
         // only the chunks next to a candidate are read (a candidate needs itself and its two neighbours)
         const int64_t off0 = (int64_t)tile0 + (int64_t)tid * SK_SPAN;
         const uint32_t needm = (candm | (candm << 1) | (candm >> 1) | (before ? 1u : 0u) | (after ? 0x80u : 0u)) & 0xFFu;
@@ -743,18 +689,9 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
             ((uint16_t *)rec)[r * (2 * SK_REC_DW) + 16 + sl] = (uint16_t)(i0 | (i1 << 4) | (i2 << 8) | (i3 << 12));
         }
     }
-    SK_PHASE(1);                                                     // waiting for the loads + decode
-#if (SK_PRIO & 5) == 5
-    __builtin_amdgcn_s_setprio(SK_PRIO_BASE);
-#endif
     __syncthreads();
-    SK_PHASE(2);                                                     // the barrier
-    if (ABLATE == 8) { if (rec[tid] == 0x12345u && candm == 0x77u) flags[3] = 1u; return; }               // timing: phase 1 alone
 
     // ================= phase 2: one filter lookup per chunk ======================================
-#if SK_PRIO_P2 != SK_PRIO_BASE
-    __builtin_amdgcn_s_setprio(SK_PRIO_P2);
-#endif
     uint16_t *const wq = wq_all[tid >> 6];
     uint16_t *const cq = cq_all[tid >> 6];                        // the wave's list of chunks: phase 2's questions first, stage 2's survivors then
     uint32_t qw = 0;                                              // queue fill (wave-uniform)
@@ -776,29 +713,21 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
         g[i] = sk_gmix(cw < rc ? cw : rc);
         okm |= (uint32_t)(inv == 0u && (!CAND || ((candm >> i) & 1u))) << i;
         b1[i] = make_uint2(0u, 0u);
-        if (ABLATE == 4) { if (inv == 0u) b1[i] = table.grid1[sk_grid1_block(g[i], table.grid1_blocks) & 131071u]; }  // timing: all lookups in 1 MiB (L2 hits)
-        else if (ABLATE == 6) { if (inv == 0u) b1[i] = table.grid1[sk_grid1_block(g[i], table.grid1_blocks) & 2047u]; } // timing: all lookups in 16 KiB (L1 hits)
-        else if (ABLATE == 10) { if (inv == 0u) b1[i] = table.grid1[sk_grid1_block(g[i], table.grid1_blocks)]; }         // timing: the real level-1 lookups, verdicts dropped (no level 2, no stage 2)
-        else if (ABLATE != 1 && ((okm >> i) & 1u)) b1[i] = table.grid1[sk_grid1_block(g[i], table.grid1_blocks)];
+        if ((okm >> i) & 1u) b1[i] = table.grid1[sk_grid1_block(g[i], table.grid1_blocks)];
     }
-    SK_PHASE(3);                                                     // records read, hashes, lookups issued
-#if SK_PRIO_TAIL != SK_PRIO_P2
-    __builtin_amdgcn_s_setprio(SK_PRIO_TAIL);
-#endif
+    // (the records are read, the hashes made and the eight lookups issued: what follows waits for them)
     uint32_t m = 0;                                               // chunks that may be in the strain
 #pragma unroll
     for (int i = 0; i < SK_SPAN_CH; i++)
-        m |= (uint32_t)(((okm >> i) & 1u) != 0u && sk_grid_test(b1[i], sk_grid1_bits(g[i])) &&
-                        ((ABLATE != 4 && ABLATE != 6 && ABLATE != 10) || g[i] == 0x9E3779B9u)) << i;     // (ablations: loads kept alive, verdicts dropped)
-    SK_PHASE(4);                                                     // waiting for the lookups + their verdicts
-#if SK_RUN_PASS
+        m |= (uint32_t)(((okm >> i) & 1u) != 0u && sk_grid_test(b1[i], sk_grid1_bits(g[i]))) << i;
     // SK_RUN_PASS level-1 survivors in a row (two more in a union table, where one chunk in seven passes level 1 by chance) are a read of
     // the strain: the run goes to stage 2 unquestioned, without the round trips to the L2 and to HBM that the questions below cost a
     // wave whose strain read waits for them.  Pruning less is always exact.  The neighbouring lanes' verdicts carry a run over the
     // edge of a thread's eight chunks (a 150-base read is nine chunks: with own chunks only, one of its two threads still asks).
     uint32_t runpass = 0u;
-    if (!CAND && ABLATE != 5) {
+    if (!CAND) {
         constexpr uint32_t RUN = UNION ? SK_RUN_PASS + 2u : SK_RUN_PASS, MARGIN = RUN - 1u;
+        static_assert(SK_RUN_PASS >= 1, "a run that passes unquestioned is at least one chunk long");
         static_assert(MARGIN <= 8u, "a run longer than nine chunks needs more than the two neighbouring lanes");
         const uint32_t mu = (uint32_t)__shfl_up((int)m, 1), md = (uint32_t)__shfl_down((int)m, 1);
         const uint32_t wide = (lane > 0u ? mu >> (8u - MARGIN) : 0u) | (m << MARGIN) | (lane < 63u ? (md & ((1u << MARGIN) - 1u)) << (8u + MARGIN) : 0u);
@@ -809,18 +738,14 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
         for (uint32_t k = 0; k < RUN; k++) members |= sr << k;
         runpass = (members >> MARGIN) & m;
     }
-#endif
     // Level 2, a CHUNK PER LANE (round 3, when the kernel had become bound by vector instructions).  The false positives of level 1 are
     // 7 % of the chunks: nearly every thread-wise loop over "my survivors" runs in every wave (some lane always has one), one or two
     // rounds of ~220 instructions for two or three busy lanes.  Here the chunks to be asked (level-1 survivors outside the runs that pass
     // unquestioned) are compacted over the wave -- 36 of 512 on average: ONE round with half the lanes busy -- each lane asks about one
     // chunk (the two half-shifted 16-mers, then the 24-mer of a side that passed), and the verdicts go back to the owners as bits of a
     // word in LDS.  Every asked chunk stands for itself (no "right behind a chunk that passed"): strain reads are the runs.
-    if (ABLATE != 5 && !CAND) {
-        uint32_t ask = m;
-#if SK_RUN_PASS
-        ask &= ~runpass;
-#endif
+    if (!CAND) {
+        uint32_t ask = m & ~runpass;
         const unsigned long long anyask = __ballot(ask != 0u);
         uint32_t m2 = m & ~ask;
         if (anyask) {                                             // (wave-uniform)
@@ -876,8 +801,6 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
         m = m2;
     }
 
-    SK_PHASE(5);                                                     // the second and third questions
-    if (ABLATE == 9) { if (m == 0x77u && tid == 100u) flags[3] = 1u; return; }                            // timing: phases 1 and 2 alone
 
     // ================= stage 2: the windows of the surviving chunks ==============================
     // Seed and verify, a CHUNK per lane (16 windows at a time, 64 chunks = up to 1024 windows per round).
@@ -898,13 +821,13 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
     //   rest    windows the diagonal does not explain (a read error, a repeat, no seed hit) are queued one by one,
     //           asked about in the L2-resident level-1 filter (first and last 16-mer: they cover all 31 bases)
     //           and only then probed in the table.
-    auto count_row = [&](uint32_t row, uint32_t pos) { sk_on_hit<false, ABLATE == 3>(sink, row, pos); };
+    auto count_row = [&](uint32_t row, uint32_t pos) { sk_on_hit<false>(sink, row, pos); };
     // difference-array update through the workgroup's table of indices already touched in this tile
     auto diff_add = [&](uint32_t idx, uint32_t delta) {
         const uint32_t a = (idx * 0x9E3779B1u) >> (32 - SK_AGG_LOG2);
         const uint32_t old = atomicCAS(&agg[a].x, 0xFFFFFFFFu, idx);
         if (old == idx) atomicAdd(&agg[a].y, delta);
-        else if (ABLATE != 3) atomicAdd(&sink.diff[idx], delta);
+        else atomicAdd(&sink.diff[idx], delta);
     };
 
     auto probe_windows = [&](uint32_t n) {
@@ -931,7 +854,6 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
             q0[s2] = q1[s2] = make_uint2(0u, 0u);
             if (act[s2]) { q0[s2] = table.grid1[sk_grid1_block(g0[s2], table.grid1_blocks)]; q1[s2] = table.grid1[sk_grid1_block(g1[s2], table.grid1_blocks)]; }
         }
-        if (ABLATE == 2) { __builtin_amdgcn_wave_barrier(); return; }
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++)
             if (act[s2] && sk_grid_test(q0[s2], sk_grid1_bits(g0[s2])) && sk_grid_test(q1[s2], sk_grid1_bits(g1[s2]))) {
@@ -1082,7 +1004,7 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
                 hits = asc & bits16;
                 const uint32_t dups = asc & ~bits16;                           // a k-mer of the strain, but its row is elsewhere
                 uint32_t un = live & ~ver16;                                   // live windows the diagonal does not explain
-                if (un && SK_CHUNK_REJECT) {
+                if (un) {
                     // Mostly a base that differs from the strain (a read error, a diverged genome): ~31 windows in a row hold
                     // it.  Before they go to the one-by-one path (two filter questions each), three questions for all of
                     // them: the 16-mers that start 15 and 8 bases before the differing base and at it.  Every window that
@@ -1271,15 +1193,13 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     if (qw) probe_windows(qw);
-    SK_PHASE(6);                                                     // stage 2
     if (bad) atomicAdd(&flags[0], 1u);
     if (!TALLY) {                                                 // the repeats of this tile, one atomic per index
         __syncthreads();
         for (uint32_t i = tid; i < SK_AGG; i += SK_THREADS) {
             const uint2 e = agg[i];
-            if (e.y != 0u && ABLATE != 3) atomicAdd(&sink.diff[e.x], e.y);
+            if (e.y != 0u) atomicAdd(&sink.diff[e.x], e.y);
         }
-        SK_PHASE(7);                                                 // the closing barrier + flush
     } else {                                                      // the tile's share of the hit log: one atomic, one copy
         __syncthreads();
         const uint32_t nl = hl_n[0] < hl_n[1] ? hl_n[0] : hl_n[1];

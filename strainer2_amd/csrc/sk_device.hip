@@ -131,7 +131,6 @@ struct sk_ctx {
     uint64_t     launch_seq;           // launches made so far
     // options
     long         table_load_pct;
-    long         ablate;              // timing experiments: kernel variants that skip memory stages
     long         dev_uncached;        // experiment: sk_dev_alloc hands out memory the L2 does not keep
     uint32_t    *d_grid3;             // partitioned pipeline: the SK_BIN_P filter slices (bitmaps) of sk_lds_probe
     void        *p_bins, *p_binn, *p_cand;    // its grow-only scratch: segments, segment fills, candidate bytes
@@ -409,13 +408,9 @@ extern "C" int sk_set_option(sk_ctx *c, const char *name, long value)
         c->lane_next = 0;
         return SK_OK;
     }
-#ifdef SK_EXPERIMENTS
-    if (!strcmp(name, "ablate")) { c->ablate = value; return SK_OK; }
-#else
-    // the timing variants of the hot kernel that leave memory stages out (some of them count wrongly) are compiled
-    // only into an experiments build (make EXPERIMENTS=1): the product library has no switch that changes a count
-    if (!strcmp(name, "ablate")) return value == 0 ? SK_OK : sk_fail(c, SK_E_ARG, "option \"ablate\" needs a library built with make EXPERIMENTS=1");
-#endif
+    // the timing variants of the hot kernel that left memory stages out (some of them counted wrongly) are retired: the
+    // option is kept for its callers and takes 0 only -- the library has no switch that changes a count
+    if (!strcmp(name, "ablate")) return value == 0 ? SK_OK : sk_fail(c, SK_E_ARG, "the scan kernel's timing variants were retired (their results: profiles/); this option takes 0 only");
     return sk_fail(c, SK_E_ARG, "unknown option %s", name);
 }
 
@@ -759,6 +754,28 @@ static int sk_diff_flush(sk_ctx *c)
 
 static int sk_scratch(sk_ctx *c, void **p, size_t *cap, size_t need);
 
+// The forms of the two scan kernels that exist, by the facts of the launch: the hit goes to the per-record tallies (`tally`) or to
+// the column's counters, the table is a union of strains (`un`: TALLY only -- a sink with strains IS a tally sink), the stream is
+// read through the partitioned pipeline's candidate map (`cand`) or came packed by the host (`packed`).  Eight forms of the grid
+// kernel and three of the byte-string kernel are built, no others.  The combinations left out cannot be asked for: sk_launch_scan
+// makes `un` only from a tally sink, never sets `cand` for a packed batch or a union table, and these are the only callers.
+typedef void (*sk_grid_fn)(const uint8_t *, uint64_t, uint64_t, sk_table_view, sk_sink, uint32_t *, const uint8_t *);
+static sk_grid_fn sk_grid_form(bool tally, bool un, bool cand, bool packed)
+{
+    //                                    <TALLY, CAND, UNION, PACKED>
+    if (packed && un)  return sk_scan_grid<true,  false, true,  true>;
+    if (packed)        return tally ? sk_scan_grid<true,  false, false, true> : sk_scan_grid<false, false, false, true>;
+    if (un)            return sk_scan_grid<true,  false, true>;
+    if (cand)          return tally ? sk_scan_grid<true,  true> : sk_scan_grid<false, true>;
+    return tally ? sk_scan_grid<true,  false> : sk_scan_grid<false, false>;
+}
+typedef void (*sk_wide_fn)(const uint8_t *, uint64_t, uint64_t, sk_table_view, sk_wide_view, sk_sink, uint32_t *);
+static sk_wide_fn sk_wide_form(bool tally, bool un)
+{
+    if (un) return sk_scan_wide<true, true>;
+    return tally ? sk_scan_wide<true> : sk_scan_wide<false>;
+}
+
 // launch main + wide kernels over one device-resident batch
 // packed_inv: the batch is in the host-packed form (sk_pack_stream) -- d_stream points at its code words, packed_inv at its masks
 static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, uint64_t emit_begin, uint32_t col,
@@ -794,7 +811,7 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
     if (!c->d_grid1) return sk_fail(c, SK_E_STATE, "no table loaded");
     // A count scan of a resident batch takes the lanes in turn; everything else runs on the context's stream (lane 0) behind both.
     uint32_t li = 0;
-    if (lane_scan && !tally_sink && c->scan_lanes > 1 && !c->ablate && c->pipeline != 2 && !SK_PHASE_CLOCK) {     // (phase clocks are summed in lane 0's list)
+    if (lane_scan && !tally_sink && c->scan_lanes > 1 && c->pipeline != 2) {
         if (c->grid_pending) { int jrc = sk_lanes_join(c); if (jrc) return jrc; }      // (the filters are filled on the context's stream)
         li = c->lane_next;
         c->lane_next ^= 1u;
@@ -826,7 +843,6 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
     // launch is long over, SK_EV_PAIRS launches of this lane later: the wait below is never for the other lane's newest) and used
     // again, so a program that never asks for the timing holds 128 events a lane, not two per launch
     hipEvent_t e0 = NULL, e1 = NULL;
-    const bool timed = true;
     if (L.ev.size() >= 2 * SK_EV_PAIRS) {                     // (launches are added up in the order they were made, whichever lane took them)
         sk_lane &O = c->lane[li ^ 1u];
         while (!O.seq.empty() && O.seq[0] < L.seq[0]) { int trc = sk_timing_retire(c, O); if (trc) return trc; }
@@ -846,7 +862,7 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
     // 2 % strain reads; profiles/r02_lds_pipeline.txt) -- its one full pass over the stream plus the
     // bin write already costs half of the single kernel's time, and the re-read of the candidates' neighbourhoods pays
     // the fabric's random-line rate.  The default is the single kernel for every batch size.
-    const bool piped = !packed_inv && (!c->ablate || c->ablate >= 7) && c->pipeline == 2;        // (ablations 7-9 exist for both forms)
+    const bool piped = !packed_inv && c->pipeline == 2;
     const uint8_t *d_cand = NULL;
     if (piped && !c->d_grid3) {
         // the partitioned pipeline's filter slices, built from the resident table the first time they are wanted:
@@ -877,56 +893,18 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
                            (const uint32_t *)c->p_bins, (const uint8_t *)c->p_binn, (uint32_t)ntiles_bin, splits, (uint8_t *)c->p_cand);
         d_cand = (const uint8_t *)c->p_cand;
     }
-#define SK_LAUNCH_GRID(T, A, C) hipLaunchKernelGGL((sk_scan_grid<T, A, C>), grid, block, 0, st, \
-                                                   d_stream, nbytes, emit_begin, tv, sink, d_fl, d_cand)
-    if (packed_inv) {
-        if (c->ablate) return sk_fail(c, SK_E_UNSUPPORTED, "no ablations on packed batches");
-        if (tally_sink && tally_sink->ns)
-            hipLaunchKernelGGL((sk_scan_grid<true, 0, false, true, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
-        else if (tally_sink)
-            hipLaunchKernelGGL((sk_scan_grid<true, 0, false, false, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
-        else
-            hipLaunchKernelGGL((sk_scan_grid<false, 0, false, false, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, (const uint8_t *)packed_inv);
-    }
-    else if (tally_sink && tally_sink->ns)
-        hipLaunchKernelGGL((sk_scan_grid<true, 0, false, true>), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, d_cand);
-    else if (piped && tally_sink) SK_LAUNCH_GRID(true, 0, true);
-#ifdef SK_EXPERIMENTS
-    else if (piped && c->ablate == 7) SK_LAUNCH_GRID(false, 7, true);
-    else if (piped && c->ablate == 8) SK_LAUNCH_GRID(false, 8, true);
-    else if (piped && c->ablate == 9) SK_LAUNCH_GRID(false, 9, true);
-#endif
-    else if (piped)          SK_LAUNCH_GRID(false, 0, true);
-    else if (tally_sink)     SK_LAUNCH_GRID(true, 0, false);
-#ifdef SK_EXPERIMENTS
-    else if (c->ablate == 1) SK_LAUNCH_GRID(false, 1, false);
-    else if (c->ablate == 2) SK_LAUNCH_GRID(false, 2, false);
-    else if (c->ablate == 3) SK_LAUNCH_GRID(false, 3, false);
-    else if (c->ablate == 4) SK_LAUNCH_GRID(false, 4, false);
-    else if (c->ablate == 5) SK_LAUNCH_GRID(false, 5, false);
-    else if (c->ablate == 6) SK_LAUNCH_GRID(false, 6, false);
-    else if (c->ablate == 10) SK_LAUNCH_GRID(false, 10, false);
-#endif
-    else                     SK_LAUNCH_GRID(false, 0, false);
-#undef SK_LAUNCH_GRID
-    if (timed) {
-        SK_HIP(c, hipEventRecord(e1, st));
-        L.ev.push_back(e0);
-        L.ev.push_back(e1);
-        L.seq.push_back(c->launch_seq++);
-    }
+    // (a union table has no candidate form: its scan is the single kernel whatever "pipeline" says)
+    const bool tally = tally_sink != NULL, un = tally && tally_sink->ns != 0;
+    const uint8_t *const last = packed_inv ? (const uint8_t *)packed_inv : d_cand;
+    hipLaunchKernelGGL(sk_grid_form(tally, un, piped && !un, packed_inv != NULL), grid, block, 0, st, d_stream, nbytes, emit_begin, tv, sink, d_fl, last);
+    SK_HIP(c, hipEventRecord(e1, st));
+    L.ev.push_back(e0);
+    L.ev.push_back(e1);
+    L.seq.push_back(c->launch_seq++);
     uint64_t wblocks = (nbytes - emit_begin + 255) / 256;
     if (wblocks > 2048) wblocks = 2048;                        // (grid-stride: eight workgroups per CU; with nothing to do -- the usual case -- the launch is over in 3 us)
     if (wblocks == 0) { wblocks = 1; }
-    if (tally_sink && tally_sink->ns)
-        hipLaunchKernelGGL((sk_scan_wide<true, true>), dim3((uint32_t)wblocks), dim3(256), 0, st,
-                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl);
-    else if (tally_sink)
-        hipLaunchKernelGGL(sk_scan_wide<true>, dim3((uint32_t)wblocks), dim3(256), 0, st,
-                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl);
-    else
-        hipLaunchKernelGGL(sk_scan_wide<false>, dim3((uint32_t)wblocks), dim3(256), 0, st,
-                           d_stream, nbytes, emit_begin, tv, wv, sink, d_fl);
+    hipLaunchKernelGGL(sk_wide_form(tally, un), dim3((uint32_t)wblocks), dim3(256), 0, st, d_stream, nbytes, emit_begin, tv, wv, sink, d_fl);
     SK_HIP(c, hipGetLastError());
     return SK_OK;
 }
@@ -2088,19 +2066,3 @@ extern "C" int sk_dev_download(sk_ctx *c, void *host, const void *dev, uint64_t 
     SK_HIP(c, hipStreamSynchronize(c->stream));
     return SK_OK;
 }
-
-#if SK_PHASE_CLOCK
-// experiment builds only: the eight phase sums (wave-cycles of s_memtime) since the last call, then zeroed
-extern "C" int sk_debug_phase_clock(sk_ctx *c, unsigned long long out[8])
-{
-    if (!c || !out) return SK_E_ARG;
-    SK_HIP(c, hipSetDevice(c->device));
-    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
-    SK_HIP(c, hipStreamSynchronize(c->stream));
-    unsigned long long *d = (unsigned long long *)(c->lane[0].d_oddlist + (c->odd_cap ? c->odd_cap : SK_ODDCAP) - 1024u), h[512];
-    SK_HIP(c, hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost));
-    SK_HIP(c, hipMemset(d, 0, sizeof h));
-    for (int k = 0; k < 8; k++) { out[k] = 0; for (int s = 0; s < 64; s++) out[k] += h[s * 8 + k]; }
-    return SK_OK;
-}
-#endif

@@ -207,6 +207,20 @@ def test_byte_string_path_list_and_overflow(cap):
     assert np.array_equal(got, ocounts[:, 1]) and got.sum() > 5_000
 
 
+def test_option_ablate_takes_zero_only():
+    """the benchmark passes its --ablate argument on as this option: 0 is accepted, every other value is a bad argument
+    (the kernel variants it once chose are retired), and so is a name the library does not know -- on a fresh context"""
+    SK_E_ARG = -3
+    with sk.KmerContext(0) as c:
+        c.set_option("ablate", 0)
+        with pytest.raises(sk.SKError) as e:
+            c.set_option("ablate", 1)
+        assert e.value.code == SK_E_ARG
+        with pytest.raises(sk.SKError) as e:
+            c.set_option("no_such_option", 0)
+        assert e.value.code == SK_E_ARG
+
+
 def test_scan_device_equals_scan_stream_and_tile_edges(ctx):
     """Device-resident entry point; stream lengths around tile (32768) and chunk (16) edges."""
     rng = random.Random(7)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/exp_grid.py -- one process, many variants of the scan kernel (options, ablations, strain-read fractions).
+"""tools/exp_grid.py -- one process, many variants of the scan kernel (options, strain-read fractions).
 
 Prints, per variant, the average launch time of the scan kernel (HIP events on the library's stream).  Under
 `rocprofv3 --kernel-trace --pmc ...` the launches come out in the order of the variants, LAUNCHES per variant
@@ -21,13 +21,6 @@ sys.path.insert(0, REPO)
 VARIANTS = {
     "base_h0":      (0.0,  {}, False),
     "base_h2":      (0.02, {}, False),
-    "nol2_h0":      (0.0,  {"ablate": 5}, False),
-    "nol2_h2":      (0.02, {"ablate": 5}, False),
-    "l2hit_h2":     (0.02, {"ablate": 4}, False),
-    "l1hit_h2":     (0.02, {"ablate": 6}, False),
-    "nofilt_h2":    (0.02, {"ablate": 1}, False),
-    "l1only_h0":    (0.0,  {"ablate": 10}, False),
-    "l1only_h2":    (0.02, {"ablate": 10}, False),
     "g2048_h0":     (0.0,  {"grid_kib": 2048}, False),
     "g2048_h2":     (0.02, {"grid_kib": 2048}, False),
     "g1536_h2":     (0.02, {"grid_kib": 1536}, False),
@@ -39,32 +32,21 @@ VARIANTS = {
     "unc_g2048_h2": (0.02, {"grid_kib": 2048}, True),
     "notext_h2":    (0.02, {"text_stage": 0}, False),
     "notext_h100":  (1.0,  {"text_stage": 0}, False),
-    "pipe7_h2":     (0.02, {"ablate": 7}, False),
-    "pipe8_h2":     (0.02, {"ablate": 8}, False),
-    "pipe9_h2":     (0.02, {"ablate": 9}, False),
-    "abl8_h2":      (0.02, {"ablate": 8}, False),
-    "abl9_h2":      (0.02, {"ablate": 9}, False),
     "single_h0":    (0.0,  {"pipeline": 1}, False),
     "single_h2":    (0.02, {"pipeline": 1}, False),
     "single_h30":   (0.3,  {"pipeline": 1}, False),
     "single_h100":  (1.0,  {"pipeline": 1}, False),
     "exact_h100":   (1.0,  {}, False, 0.0),
     "exact_h30":    (0.3,  {}, False, 0.0),
-    "exact_noprobe_h30": (0.3, {"ablate": 2}, False, 0.0),
-    "noatom_h30":   (0.3,  {"ablate": 3}, False),
-    "noprobe_h30":  (0.3,  {"ablate": 2}, False),
     "notext_h30":   (0.3,  {"text_stage": 0}, False),
     "div1_h100":    (1.0,  {}, False, 0.01),
     "div3_h100":    (1.0,  {}, False, 0.03),
     "base_h30":     (0.3,  {}, False),
     "base_h100":    (1.0,  {}, False),
-    # where a launch of the dense regimes goes (round 4: both run at ~3.2 TB/s of L2 misses): no counter atomics, no table probes, smaller filter
-    "noatom_h100":  (1.0,  {"ablate": 3}, False),
-    "noprobe_h100": (1.0,  {"ablate": 2}, False),
+    # the dense regimes with a smaller filter (round 4: both run at ~3.2 TB/s of L2 misses; the kernel variants without counter atomics and
+    # without table probes that were measured beside these are retired: profiles/r04_dense_regime.txt)
     "g2048_h100":   (1.0,  {"grid_kib": 2048}, False),
     "g1024_h100":   (1.0,  {"grid_kib": 1024}, False),
-    "noatom_div3":  (1.0,  {"ablate": 3}, False, 0.03),
-    "noprobe_div3": (1.0,  {"ablate": 2}, False, 0.03),
     "g2048_div3":   (1.0,  {"grid_kib": 2048}, False, 0.03),
     "g1024_div3":   (1.0,  {"grid_kib": 1024}, False, 0.03),
 }

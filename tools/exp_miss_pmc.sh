@@ -1,7 +1,7 @@
 # usage (GPU box): bash tools/exp_miss_pmc.sh [NAME]   -- NAME = a variant built by tools/exp_variant_build.sh into build_exp/libsk_NAME.so
 #                                                       (default: the library that ships)
 export TMPDIR=/tmp
-V=base_h0,l2hit_h2,nofilt_h2,base_h2
+V=base_h0,base_h2
 OUT=gpurun_out/exp_miss
 mkdir -p $OUT
 if [ -n "$1" ]; then
