@@ -166,6 +166,60 @@ int sk_device_memory(sk_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 /* Same, for a batch already resident in HBM (device pointer). */
 int sk_scan_device(sk_ctx *ctx, const void *dev_stream, uint64_t nbytes, uint32_t col);
 
+/* Plain FASTA/FASTQ text parsed ON THE DEVICE (new; opt-in for the list scan: option "device_parse", SK_DEVICE_PARSE=1).  Replaces the
+ * reference's reader, src/kseq.h:171-211 (which the host layer restates in C), for text that is already in HBM: a line classifier and a
+ * compaction instead of a CPU thread walking every byte.
+ *   dev_text (16-byte aligned, at most 256 MiB: SK_E_ARG above, so offsets are 32-bit) begins at a record boundary: the start of a
+ *   file, or `consumed` of the piece before it.  With status SK_TEXT_OK, dev_stream[0..stream_bytes) is byte for byte the record stream
+ *   the reference's parser yields for text[0..consumed): every record's sequence followed by one '\n', records shorter than k and empty
+ *   records included (the scan ignores them), case untouched, every byte value that is not line structure passed through;
+ *   dev_rec_start[r] (NULL, or room for nrec_cap) = record r's offset in it.  is_eof == 0: a record counts as whole only if the piece
+ *   itself shows its end -- FASTQ: all four lines with their '\n'; FASTA: the next record's header character at a line start inside
+ *   the piece -- so consumed may be 0 (no progress: send a longer piece).  is_eof != 0: consumed == nbytes.
+ *   SK_TEXT_DECLINED is not an error: the piece holds something the two device forms do not cover; consumed is 0, nothing was scanned,
+ *   nothing in dev_stream may be used, and the caller parses from the piece's start on the host.
+ * The forms, each exact by induction over verified records:
+ *   SK_TEXT_FASTQ4  the piece starts with '@' and its third line with '+'.  Line i has kind i mod 4 (a quality line may start with
+ *                   @, > or +); every record: line 0 starts with '@', line 1 is non-empty and starts with none of > @ +, line 2 starts
+ *                   with '+', line 3 has line 1's length after the CR rule (src/kseq.h:136).  A record that fails declines the piece.
+ *   SK_TEXT_FASTA   otherwise, when the piece starts with '>' or '@': a line starting with > or @ is a header, a line starting with
+ *                   '+' declines (the reference reads quality from there), empty lines are skipped, every other line is sequence
+ *                   with its '\n' dropped; a line of one CR is dropped after a sequence line and declines elsewhere.
+ *   Anything else declines; so do a header cut by the end of the file and a FASTQ record cut by it.
+ * sk_scan_text_pinned: `pinned_text` (sk_pinned_alloc) goes up, is parsed, and the stream is counted into column col as by
+ * sk_scan_device; on return the buffer has been read (the scan itself may still run: sk_sync).  _many: one upload and one parse, the
+ * stream scanned into every ctx[i] (one device); scratch, errors and sk_text_stats are ctx[0]'s.  The parser's scratch is made when a
+ * context first parses, sized for that piece, and grows only for a longer one; sk_text_release frees it (before sk_ctx_destroy).
+ * sk_text_stats: pieces sk_scan_text_pinned[_many] took since the last reset, and how many of them declined.
+ * sk_text_option: the list scan's switch "device_parse" (0 default, 1 on, may be set at any time; a context that was never told follows
+ * the environment variable SK_DEVICE_PARSE=1): whole plain-text items of skh_scan_file and skh_scan_list[_many] then go up as text, in
+ * pieces (32 MiB; SK_TEXT_PIECE_BYTES), and a piece the device declines hands the rest of its file to the host parser.  It is a call of
+ * its own because sk_set_option lives with the scan kernel, which this path leaves untouched.  sk_text_enabled: what holds for ctx. */
+#define SK_TEXT_TILE      16384u        /* text bytes per workgroup of the line passes (tests aim at its boundaries) */
+#define SK_TEXT_OK        0u
+#define SK_TEXT_DECLINED  1u
+#define SK_TEXT_FASTA     1u
+#define SK_TEXT_FASTQ4    2u
+typedef struct sk_text_info {
+    uint32_t status;        /* SK_TEXT_OK | SK_TEXT_DECLINED */
+    uint32_t form;          /* SK_TEXT_FASTA | SK_TEXT_FASTQ4 */
+    uint64_t consumed;      /* bytes of text that are whole records; text[consumed..) is the caller's to send again */
+    uint64_t stream_bytes;  /* bytes written to dev_stream */
+    uint64_t nrecords;      /* records in it */
+    uint64_t bases;         /* sum of their lengths, short and empty ones included */
+} sk_text_info;
+int sk_text_parse_device(sk_ctx *ctx, const void *dev_text, uint64_t nbytes, int is_eof,
+                         void *dev_stream /* nbytes + 1 bytes */, uint32_t *dev_rec_start /* NULL or nrec_cap */,
+                         uint64_t nrec_cap, sk_text_info *info);
+int sk_scan_text_pinned(sk_ctx *ctx, const uint8_t *pinned_text, uint64_t nbytes, int is_eof, uint32_t col, sk_text_info *info);
+int sk_scan_text_pinned_many(sk_ctx *const *ctx, uint32_t n, const uint8_t *pinned_text, uint64_t nbytes, int is_eof, uint32_t col,
+                             sk_text_info *info);
+int sk_text_stats(sk_ctx *ctx, uint64_t *pieces, uint64_t *declined, int reset);
+void sk_text_release(sk_ctx *ctx);
+int sk_text_option(sk_ctx *ctx, int on);
+int sk_text_enabled(sk_ctx *ctx);
+int sk_text_timing(sk_ctx *ctx, double *last_ms);   /* device time of the context's last parse (HIP events around its passes) */
+
 /* strain_detect's per-READ view of the same scan (src/strain_detect.c:443-541): one batch of the
  * record stream whose records start at rec_start[0..nrec) (byte offsets into `stream`, ascending;
  * a record ends at the next start).  For record r: out_tally[2r] = windows that hit any key,

@@ -816,6 +816,128 @@ int skh_keyset_load(sk_ctx *ctx, const skh_keyset *ks, uint32_t ncols)
  * scan phase
  * ======================================================================================= */
 
+/* ---- plain text parsed on the device (opt-in: option "device_parse" through sk_text_option, or SK_DEVICE_PARSE=1) -------------
+ * A whole plain-text item is read in pieces into a page-locked buffer and every piece goes up as it lies in the file
+ * (sk_scan_text_pinned[_many]: upload, device parse, scan); the next piece begins with text[consumed..) of the one before, so every
+ * piece starts at a record boundary that the device VERIFIED.  A piece the device declines, or one that shows no whole record even
+ * at the 256 MiB cap, hands the rest of the file -- from that piece's start, a true record boundary -- to the host parser below,
+ * which also finds the record that ends the file for the reference (a quality string of the wrong length, src/kseq.h:205-209)
+ * where the reference finds it.  The host-only test builds link this file without the device layer: the entry points are weak,
+ * and without them the host path is taken. */
+#pragma weak sk_scan_text_pinned_many
+#pragma weak sk_text_enabled
+
+#define TEXT_NOT_TAKEN   (-100)
+#define TEXT_WHOLE       UINT64_MAX
+#define TEXT_PIECE_MAX   (256ull << 20)
+
+static int text_wanted(sk_ctx *ctx, int timing)
+{
+    const char *e;
+    static int said = 0;
+    if (sk_text_enabled && sk_scan_text_pinned_many) return ctx ? sk_text_enabled(ctx) : 0;
+    e = getenv("SK_DEVICE_PARSE");
+    if (e && e[0] == '1' && timing && !__atomic_exchange_n(&said, 1, __ATOMIC_RELAXED))
+        fprintf(stderr, "kmer_scrub_count timing: SK_DEVICE_PARSE=1, but this build has no device parser: the host parses\n");
+    return 0;
+}
+
+static uint64_t text_piece_bytes(void)
+{
+    const char *e = getenv("SK_TEXT_PIECE_BYTES");
+    const long long v = e ? atoll(e) : 0;
+    return v >= 64 && (uint64_t)v <= TEXT_PIECE_MAX ? (uint64_t)v : 32ull << 20;
+}
+
+/* the rest of a plain-text file from byte `off`, a record boundary, through the host parser */
+static int parse_from(const char *path, uint64_t off, rec_fn fn, void *user, int64_t *nrecords)
+{
+    enum { BLK = 4 << 20 };
+    const int fd = open(path, O_RDONLY);
+    unsigned char *rb;
+    parser ps;
+    if (fd < 0) return SK_E_OPEN;
+    if (!(rb = (unsigned char *)malloc(BLK))) { close(fd); return SK_E_NOMEM; }
+    parser_init(&ps, fn, user);
+    tl_plain_text = 0;                                   /* (an item that began on the device never packs) */
+    while (ps.state != P_STOP) {
+        const ssize_t r = pread(fd, rb, BLK, (off_t)off);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) break;
+        parser_feed(&ps, rb, (size_t)r);
+        off += (uint64_t)r;
+    }
+    free(rb);
+    close(fd);
+    if (ps.state != P_STOP) parser_eof(&ps);
+    if (nrecords) *nrecords += ps.nrecords;
+    parser_free(&ps);
+    return SK_OK;
+}
+
+/* SK_OK: *resume = TEXT_WHOLE (the whole file was counted on the device), or the offset from which the host goes on (everything
+ * before it was counted); TEXT_NOT_TAKEN: not a plain regular file with text in it -- the ordinary way, which also reports a file
+ * that cannot be opened; a negative SK_E_*: a device error.  `mu` (may be NULL) is held around every device call.  *tbuf / *tcap: the
+ * caller's text buffer (NULL at first; made here, grown here when a piece must grow; the caller gives it back with sk_pinned_free when
+ * its walk is over -- that call drains the context, so it is not made per file). */
+static int text_scan(sk_ctx *const *ctxs, uint32_t nctx, pthread_mutex_t *mu, const char *path, uint32_t col, uint64_t *bases,
+                     int64_t *nrecords, uint64_t *resume, uint8_t **tbuf, uint64_t *tcap)
+{
+    sk_ctx *const ctx = ctxs[0];
+    const int fd = open(path, O_RDONLY);
+    struct stat st;
+    uint8_t *buf = *tbuf;                                  /* the caller's page-locked text buffer, kept from file to file */
+    uint64_t cap = *tbuf ? *tcap : text_piece_bytes(), off = 0, have = 0;
+    int rc = SK_OK, eof = 0;
+    *resume = TEXT_WHOLE;
+    if (fd < 0) return TEXT_NOT_TAKEN;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 2) { close(fd); return TEXT_NOT_TAKEN; }
+    {
+        unsigned char magic[2];
+        if (pread(fd, magic, 2, 0) != 2 || (magic[0] == 0x1f && magic[1] == 0x8b)) { close(fd); return TEXT_NOT_TAKEN; }
+    }
+    if (!buf) {
+        if (sk_pinned_alloc(ctx, (void **)&buf, cap) != SK_OK) { close(fd); return TEXT_NOT_TAKEN; }
+        *tbuf = buf; *tcap = cap;
+    }
+    for (;;) {
+        sk_text_info info;
+        while (!eof && have < cap) {
+            const ssize_t r = pread(fd, buf + have, (size_t)(cap - have), (off_t)(off + have));
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) { eof = 1; break; }
+            have += (uint64_t)r;
+        }
+        if (off + have >= (uint64_t)st.st_size) eof = 1;
+        if (!have) break;
+        if (mu) pthread_mutex_lock(mu);
+        rc = sk_scan_text_pinned_many(ctxs, nctx, buf, have, eof, col, &info);
+        if (mu) pthread_mutex_unlock(mu);
+        if (rc != SK_OK) break;
+        if (info.status != SK_TEXT_OK) { *resume = off; break; }
+        *bases += info.bases;
+        *nrecords += (int64_t)info.nrecords;
+        if (eof) break;
+        if (info.consumed == 0) {                            /* no whole record in the piece: a longer one, up to the cap */
+            uint8_t *nb = NULL;
+            const uint64_t ncap = cap * 2 > TEXT_PIECE_MAX ? TEXT_PIECE_MAX : cap * 2;
+            if (cap >= TEXT_PIECE_MAX || sk_pinned_alloc(ctx, (void **)&nb, ncap) != SK_OK) { *resume = off; break; }
+            memcpy(nb, buf, (size_t)have);
+            if (mu) pthread_mutex_lock(mu);
+            sk_pinned_free(ctx, buf);
+            if (mu) pthread_mutex_unlock(mu);
+            buf = nb; cap = ncap;
+            *tbuf = buf; *tcap = cap;
+        } else {
+            memmove(buf, buf + info.consumed, (size_t)(have - info.consumed));
+            off += info.consumed;
+            have -= info.consumed;
+        }
+    }
+    close(fd);
+    return rc;
+}
+
 typedef struct { sk_ctx *ctx; uint32_t col; } scan_sink;
 
 static int scan_sink_fn(void *user, const uint8_t *chunk, uint64_t nbytes)
@@ -829,6 +951,30 @@ int skh_scan_file(sk_ctx *ctx, const char *path, uint32_t col, uint64_t *bases)
     scan_sink s;
     int64_t rc;
     s.ctx = ctx; s.col = col;
+    if (ctx && text_wanted(ctx, getenv("SK_TIMING") != NULL)) {
+        uint64_t resume = TEXT_WHOLE, b = 0, tcap = 0;
+        uint8_t *tbuf = NULL;
+        int64_t nrec = 0;
+        int trc = text_scan(&ctx, 1, NULL, path, col, &b, &nrec, &resume, &tbuf, &tcap);
+        if (tbuf) sk_pinned_free(ctx, tbuf);
+        if (trc != TEXT_NOT_TAKEN) {
+            if (trc == SK_OK && resume != TEXT_WHOLE) {
+                stream_writer w;
+                memset(&w, 0, sizeof w);
+                w.cap = 32u << 20;
+                if (!(w.buf = (uint8_t *)malloc(w.cap))) return SK_E_NOMEM;
+                w.sink = scan_sink_fn;
+                w.user = &s;
+                trc = parse_from(path, resume, writer_record, &w, &nrec);
+                if (trc == SK_OK) writer_flush(&w);
+                b += w.bases;
+                free(w.buf);
+                if (trc == SK_OK) trc = w.rc;
+            }
+            if (bases) *bases += b;
+            return trc;
+        }
+    }
     rc = skh_decode_file(path, 32u << 20, scan_sink_fn, &s, bases);
     return rc < 0 ? (int)rc : SK_OK;
 }
@@ -873,6 +1019,7 @@ typedef struct {
     int             pack;              /* SK_LIST_PACK: 1 (default) = the chunks of plain-text items go up packed (6 bytes per 16 bases) once the scan has shown
                                         * itself bound by the link; 0 = never; 2 = always, .gz items' too (tests) */
     int             link_bound;        /* a decode thread has spent a tenth of its time waiting for uploads (atomic) */
+    int             text;              /* whole plain-text items go up as text and are parsed on the device (option "device_parse", SK_DEVICE_PARSE=1) */
 } scan_pool;
 
 /* The progress file gets a list line when a decode thread TAKES the line's (first) item, and every line before it that is
@@ -903,6 +1050,7 @@ typedef struct {
     uint64_t   pk_ticket[2];           /* ... each rewritten only after the upload that read it */
     int        pk_used[2], pk_cur;
     double     t_begin, t_wait_all;    /* since this worker began: time spent waiting for its buffers' uploads */
+    uint8_t   *tbuf; uint64_t tcap;    /* device_parse: the page-locked buffer its items' text is read into */
 } scan_worker;
 
 /* size of a worker's chunk buffer: SK_CHUNK_BYTES (4096 .. 63 MiB; tests use small ones: many flushes per file), default 32 MiB */
@@ -1014,6 +1162,7 @@ static void worker_done(scan_worker *w)
     if (w->pinned[1]) sk_pinned_free(w->pool->ctx, w->pinned[1]);
     if (w->pk[0]) sk_pinned_free(w->pool->ctx, w->pk[0]);
     if (w->pk[1]) sk_pinned_free(w->pool->ctx, w->pk[1]);
+    if (w->tbuf) sk_pinned_free(w->pool->ctx, w->tbuf);
     pthread_mutex_unlock(&w->pool->submit_mu);
 }
 
@@ -1319,6 +1468,21 @@ static int64_t worker_item(scan_worker *w, const scan_item *it, uint64_t *bases)
         if (r != -100) return r;
     }
 #endif
+    if (!it->ranged && w->pool->text) {
+        uint64_t resume = TEXT_WHOLE;
+        rc = text_scan(w->pool->ctxs, w->pool->nctx, &w->pool->submit_mu, it->path, w->pool->col, bases, &nrec, &resume, &w->tbuf, &w->tcap);
+        if (rc != TEXT_NOT_TAKEN) {
+            if (rc != SK_OK) return rc;
+            if (resume == TEXT_WHOLE) return nrec;
+            memset(&sw, 0, sizeof sw);
+            sw.cap = POOL_CHUNK; sw.sink = worker_sink; sw.user = w; sw.next_buf = worker_next_buf;
+            rc = parse_from(it->path, resume, writer_record, &sw, &nrec);
+            if (rc == SK_OK) writer_flush(&sw);
+            *bases += sw.bases;
+            if (rc != SK_OK) return rc;
+            return sw.rc ? (int64_t)sw.rc : nrec;
+        }
+    }
     if (!it->ranged && w->pool->pipe > 1 && !getenv("SK_NO_SPLIT") && !getenv("SK_ZLIB")) {
         const int64_t r = parse_gz_split(w, it, bases);
         if (r != -100) return r;
@@ -1490,6 +1654,7 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
     pool.ctxs = ctxs;
     pool.nctx = ctxs ? nctx : 0;
     pool.col = col;
+    pool.text = ctx && !plan_only ? text_wanted(ctx, pool.timing) : (getenv("SK_DEVICE_PARSE") && getenv("SK_DEVICE_PARSE")[0] == '1' && sk_scan_text_pinned_many != NULL);
     pthread_mutex_init(&pool.submit_mu, NULL);
     pthread_mutex_init(&pool.queue_mu, NULL);
     if (env) nthreads = atoi(env);
@@ -1546,7 +1711,7 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
             size_t total_items = 0;
             for (i = 0; i < n0; i++) {
                 uint64_t np = 1;
-                if (lanes > 1 && !gz[i] && !no_split && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target) np = (all[i].size + target - 1) / target;
+                if (lanes > 1 && !gz[i] && !no_split && !(pool.text && world <= 1) && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target) np = (all[i].size + target - 1) / target;
                 total_items += np > 256 ? 256 : (size_t)np;
             }
             cut = (scan_item *)malloc((total_items + 1) * sizeof *cut);
@@ -1554,7 +1719,7 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
         }
         for (i = 0; i < n0; i++) {
             uint32_t np = 1, k;
-            if (lanes > 1 && !gz[i] && !no_split && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target) {
+            if (lanes > 1 && !gz[i] && !no_split && !(pool.text && world <= 1) && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target) {
                 np = (uint32_t)((all[i].size + target - 1) / target > 256 ? 256 : (all[i].size + target - 1) / target);
             }
             for (k = 0; k < np; k++) {

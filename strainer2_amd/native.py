@@ -41,6 +41,8 @@ SK_E_PLAN = -10
 
 # every symbol include/strainer_kmer.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
+    "sk_text_parse_device", "sk_scan_text_pinned", "sk_scan_text_pinned_many", "sk_text_stats", "sk_text_release", "sk_text_option",
+    "sk_text_enabled", "sk_text_timing",
     "sk_ctx_create", "sk_ctx_destroy", "sk_last_error", "sk_strerror", "sk_table_load", "sk_table_load_ex",
     "sk_table_load_wide", "sk_table_load_text", "sk_table_build_from_text", "sk_table_export_keys", "sk_table_export_keys_of", "sk_scan_stream", "sk_scan_device", "sk_pinned_alloc", "sk_pinned_free", "sk_scan_pinned", "sk_scan_pinned_packed", "sk_scan_pinned_many", "sk_scan_pinned_packed_many", "sk_device_memory", "sk_scan_device_packed", "sk_pack_stream", "sk_packed_bytes",
     "sk_ticket_wait", "sk_tally_batch", "sk_sync", "sk_counts_fetch",
@@ -99,6 +101,25 @@ lib.sk_packed_bytes.restype = C.c_uint64
 lib.sk_tally_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
 lib.sk_sync.argtypes = [C.c_void_p]
+
+
+class TextInfo(C.Structure):
+    """sk_text_info"""
+    _fields_ = [("status", C.c_uint32), ("form", C.c_uint32), ("consumed", C.c_uint64), ("stream_bytes", C.c_uint64),
+                ("nrecords", C.c_uint64), ("bases", C.c_uint64)]
+
+
+SK_TEXT_OK, SK_TEXT_DECLINED = 0, 1
+SK_TEXT_FASTA, SK_TEXT_FASTQ4 = 1, 2
+SK_TEXT_TILE = 16384
+lib.sk_text_parse_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TextInfo)]
+lib.sk_scan_text_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(TextInfo)]
+lib.sk_text_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
+lib.sk_text_release.argtypes = [C.c_void_p]
+lib.sk_text_release.restype = None
+lib.sk_text_option.argtypes = [C.c_void_p, C.c_int]
+lib.sk_text_enabled.argtypes = [C.c_void_p]
+lib.sk_text_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 lib.sk_counts_fetch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_counts_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_counts_set_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -270,7 +291,46 @@ class KmerContext:
             raise SKError(rc, lib.sk_last_error(self._h).decode())
 
     def set_option(self, name, value):
+        if name == "device_parse":          # the list scan's switch for plain text parsed on the device (sk_text_option)
+            self._ck(lib.sk_text_option(self._h, int(value)))
+            return
         self._ck(lib.sk_set_option(self._h, name.encode(), value))
+
+    def parse_text_device(self, dev_text, nbytes, is_eof, want_rec_start=False):
+        """sk_text_parse_device on text resident at device pointer dev_text: returns (info, dev_stream, dev_rec_start) -- device
+        buffers of this context (dev_free), nbytes + 1 bytes and, with want_rec_start, room for nbytes // 2 + 1 record starts
+        (else None).  info.status == SK_TEXT_DECLINED: nothing in them may be used."""
+        info = TextInfo()
+        out = self.dev_alloc(nbytes + 16)
+        cap = nbytes // 2 + 1 if want_rec_start else 0
+        rs = self.dev_alloc(cap * 4) if want_rec_start else None
+        self._ck(lib.sk_text_parse_device(self._h, dev_text, nbytes, int(bool(is_eof)), out, rs, cap, C.byref(info)))
+        return info, out, rs
+
+    def scan_text(self, data, col, is_eof=True):
+        """sk_scan_text_pinned: plain FASTA/FASTQ text (bytes or a uint8 array) goes up as it is, is parsed on the device and counted
+        into column `col`; returns the sk_text_info (status DECLINED: nothing was counted)."""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        info = TextInfo()
+        buf = self.pinned_alloc(max(data.size, 16))
+        try:
+            buf[: data.size] = data
+            self._ck(lib.sk_scan_text_pinned(self._h, buf.ctypes.data, data.size, int(bool(is_eof)), col, C.byref(info)))
+        finally:
+            self.pinned_free(buf)
+        return info
+
+    def text_timing(self):
+        """device milliseconds of this context's last text parse (sk_text_timing)"""
+        ms = C.c_double(0)
+        self._ck(lib.sk_text_timing(self._h, C.byref(ms)))
+        return ms.value
+
+    def text_stats(self, reset=False):
+        """(pieces parsed on the device, pieces it declined) since the last reset (sk_text_stats)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._ck(lib.sk_text_stats(self._h, C.byref(a), C.byref(b), int(reset)))
+        return a.value, b.value
 
     def load_keyset(self, ks: Keyset, ncols=4):
         self._ck(lib.skh_keyset_load(self._h, C.byref(ks._s), ncols))
@@ -387,14 +447,21 @@ class KmerContext:
         self._ck(lib.skh_scan_file(self._h, os.fsencode(path), col, C.byref(bases)))
         return bases.value
 
-    def scan_list(self, list_path, col, skip=None, rank=0, world=1, uncut=False):
+    def scan_list(self, list_path, col, skip=None, rank=0, world=1, uncut=False, progress_path=None, err_path=None):
         """skh_scan_list; uncut=True: the whole-file plan (skh_scan_list_uncut).  With world > 1 and no in-library communicator
         a cut that does not hold raises SKError(SK_E_SPLIT): use strainer2_amd.dist.scan_list_sharded, which agrees across
         the ranks and scans again uncut."""
         bases = C.c_uint64(0)
         fn = lib.skh_scan_list_uncut if uncut else lib.skh_scan_list
-        self._ck(fn(self._h, os.fsencode(list_path), None if skip is None else os.fsencode(skip),
-                    col, None, None, rank, world, C.byref(bases)))
+        prog = _libc.fopen(os.fsencode(progress_path), b"w") if progress_path is not None else None
+        err = _libc.fopen(os.fsencode(err_path), b"w") if err_path is not None else None
+        try:
+            self._ck(fn(self._h, os.fsencode(list_path), None if skip is None else os.fsencode(skip),
+                        col, prog, err, rank, world, C.byref(bases)))
+        finally:
+            for f in (prog, err):
+                if f:
+                    _libc.fclose(f)
         return bases.value
 
     def scan_list_many(self, others, list_path, col, skip=None):
@@ -503,6 +570,7 @@ class KmerContext:
             for p in list(self._bufs):
                 lib.sk_dev_free(self._h, p)
             self._bufs = []
+            lib.sk_text_release(self._h)
             lib.sk_ctx_destroy(self._h)
             self._h = None
 
