@@ -742,7 +742,7 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
     // 7 % of the chunks: nearly every thread-wise loop over "my survivors" runs in every wave (some lane always has one), one or two
     // rounds of ~220 instructions for two or three busy lanes.  Here the chunks to be asked (level-1 survivors outside the runs that pass
     // unquestioned) are compacted over the wave -- 36 of 512 on average: ONE round with half the lanes busy -- each lane asks about one
-    // chunk (the two half-shifted 16-mers, then the 24-mer of a side that passed), and the verdicts go back to the owners as bits of a
+    // chunk (the two half-shifted 16-mers, the quarter-shifted one of a side that passed, then the 24-mer of a side still left), and the verdicts go back to the owners as bits of a
     // word in LDS.  Every asked chunk stands for itself (no "right behind a chunk that passed"): strain reads are the runs.
     if (!CAND) {
         uint32_t ask = m & ~runpass;
@@ -779,9 +779,28 @@ void sk_scan_grid(const uint8_t *__restrict__ stream, uint64_t nbytes, uint64_t 
                     uint2 bl = make_uint2(0u, 0u), br = make_uint2(0u, 0u);                  // (both lookups in flight together)
                     if (lv_ok) bl = table.grid1[sk_grid1_block(gl, table.grid1_blocks)];
                     if (rv_ok) br = table.grid1[sk_grid1_block(gr, table.grid1_blocks)];
-                    const bool al = lv_ok && sk_grid_test(bl, sk_grid1_bits(gl)), ar = rv_ok && sk_grid_test(br, sk_grid1_bits(gr));
+                    bool al = lv_ok && sk_grid_test(bl, sk_grid1_bits(gl)), ar = rv_ok && sk_grid_test(br, sk_grid1_bits(gr));
+                    if (!UNION && (al | ar)) {
+                        // The quarter-shifted 16-mers, one more question in the L2-resident level 1 before the trip to HBM.  The chunk's
+                        // windows with >= 8 bases to its left (the ones `al` stands for) all hold the 16-mer at shift -4 as well, those with
+                        // <= 7 (`ar`) the one at shift +4: a side whose quarter-shifted 16-mer is no 16-mer of the strain has no window left.
+                        // Each passes by chance 7 % of the time, so of the chunks that got here by chance one in fourteen goes on to level 2,
+                        // whose answer comes from HBM: at cfg 2 the kernel's misses fall by a ninth and the launch by 2 %; a chunk of a
+                        // strain read pays one more trip to the L2 instead (profiles/quarter_shift.txt).  (Not in a
+                        // union table: its level 1 is saturated with true 16-mers.)
+                        const uint32_t wl4 = __builtin_amdgcn_alignbit(cwp, cw, 8), wr4 = __builtin_amdgcn_alignbit(cw, cwn, 24);
+                        const uint32_t rl4 = sk_revcomp32(wl4), rr4 = sk_revcomp32(wr4);
+                        const uint32_t gl4 = sk_gmix(wl4 < rl4 ? wl4 : rl4), gr4 = sk_gmix(wr4 < rr4 ? wr4 : rr4);
+                        uint2 bl4 = make_uint2(0u, 0u), br4 = make_uint2(0u, 0u);            // (both lookups in flight together)
+                        if (al) bl4 = table.grid1[sk_grid1_block(gl4, table.grid1_blocks)];
+                        if (ar) br4 = table.grid1[sk_grid1_block(gr4, table.grid1_blocks)];
+                        al = al && sk_grid_test(bl4, sk_grid1_bits(gl4));                    // (the 4 borrowed bases are among the 8 that lv_ok / rv_ok vouch for)
+                        ar = ar && sk_grid_test(br4, sk_grid1_bits(gr4));
+                    }
                     bool pass = false;
-                    if (al | ar) {                                // level 2: the 24-mer of a side that passed, the other side's only if that one is no 24-mer of the strain
+                    // (wave-uniform: behind the quarter-shifted questions most waves of an unrelated metagenome have no lane left to ask
+                    // level 2, and those neither issue its load nor wait for it)
+                    if ((UNION || __ballot(al | ar) != 0ull) && (al | ar)) {   // level 2: the 24-mer of a side that passed, the other side's only if that one is no 24-mer of the strain
                         const uint64_t l24 = ((uint64_t)(cwp & 0xFFFFu) << 32) | cw, r24 = ((uint64_t)cw << 16) | (cwn >> 16);
                         uint64_t c24 = sk_canon24(al ? l24 : r24);
                         pass = sk_grid_test(table.grid2[sk_grid2_block(sk_h24_block(c24), table.grid2_shift)], sk_grid2_bits(sk_h24_bits(c24)));

@@ -62,7 +62,7 @@ t = {"kernel": [n for n in s["kernels"] if "sk_scan_grid" in n][0].split("<")[0]
      "sk_device_hip_sha256": device_source_sha(),
      "correction": "FETCH_SIZE raw + half of the record stream's bytes (gfx950: 128-B streaming requests are tallied at 64 B; "
                    "applied to the streaming share only, random lookups as counted) + WRITE_SIZE (exact). Separate --pmc passes (tools/profile.sh).",
-     "source": f"profiles/{tag}_summary.txt", "run": src}
+     "source": f"profiles/{tag}_summary.txt", "run": os.path.basename(src)}
 json.dump(t, open("profiles/traffic.json", "w"), indent=1)
 k = [v for n, v in s["kernels"].items() if "sk_scan_grid" in n][0]
 print(f"{tag}: kernel-trace avg {k['avg_ns'] / 1e6:.3f} ms over {k['calls']} calls; bench events avg "
