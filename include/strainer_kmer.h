@@ -242,6 +242,26 @@ void sk_batch_destroy(sk_batch *b);
 int  sk_batch_sync(sk_batch *b);                               /* its uploads are done: the host memory it was filled from may be reused, the batch kept for the next file */
 int  sk_batch_fill(sk_batch *b, const uint8_t *stream, uint64_t nbytes, const uint32_t *rec_start, uint32_t nrec);
 int  sk_batch_fill_packed(sk_batch *b, const void *packed, uint64_t nbytes, const uint32_t *rec_start, uint32_t nrec);   /* the batch in sk_pack_stream's form (nbytes, rec_start: of the byte stream it was packed from) */
+/* A batch filled from plain TEXT, parsed on the device (new; opt-in for strain_detect: option "device_parse", SK_DEVICE_PARSE=1): what
+ * sk_batch_fill does with a record stream the host made, for a piece of FASTA/FASTQ text as it lies in the file.
+ *   A piece is pinned_text[0..nbytes) (sk_pinned_alloc; at most 256 MiB), beginning at a record boundary as for sk_text_parse_device.
+ *   is_eof == 0: a piece before the file's last; give it ONE byte of look-ahead -- the first byte of the piece that follows, inside
+ *   nbytes -- so that both forms count its last record, and accept it only if consumed == nbytes - 1.  is_eof != 0: the last piece.
+ *   sk_batch_fill_text enqueues on the batch's stream and returns at once: the upload, the parser's passes writing the record stream
+ *   and every record's start into the batch, the tile index the TALLY scan reads (made on the device: only it knows the number of
+ *   records), and the copies home.  The text must stay as it is until sk_batch_text_finish.  Every tally launched on the batch's
+ *   previous contents must have been collected, as for sk_batch_fill.
+ *   sk_batch_text_finish waits and fills *info (status, form, consumed, stream_bytes, nrecords, bases); *rec_start (may be NULL) points
+ *   at the nrecords record starts in the batch's page-locked staging, valid until the batch is filled again: record i has
+ *   (i + 1 < nrecords ? rec_start[i + 1] : stream_bytes) - rec_start[i] - 1 bases.  The batch holds EVERY record of the piece, in file
+ *   order, records shorter than k and empty ones included: they have no window, so they tally 0 and log nothing, and a record's
+ *   index in the tallies is its index in the piece.  The results equal those of sk_batch_fill with the host-made stream of the same
+ *   records.
+ *   The decline rule: SK_TEXT_DECLINED (not an error) for whatever the two device forms do not cover, and for a piece with more than
+ *   2^22 records.  A declined piece, and one without records, leaves the batch unusable: a launch on it fails with SK_E_STATE until
+ *   it is filled again.  The caller parses from the piece's start on the host. */
+int  sk_batch_fill_text(sk_batch *b, const uint8_t *pinned_text, uint64_t nbytes, int is_eof);
+int  sk_batch_text_finish(sk_batch *b, sk_text_info *info, const uint32_t **rec_start);
 int  sk_tally_launch(sk_ctx *ctx, const sk_batch *b, uint32_t type_col, uint32_t informative_value, uint64_t hits_cap);
 int  sk_tally_collect(sk_ctx *ctx, uint32_t *out_tally /* 2*nrec */, sk_hit *out_hits /* hits_cap */, uint64_t *out_nhits);
 /* The same collection, sparse: only records with at least one hit, compacted on the device, as {record, all hits,

@@ -934,6 +934,8 @@ struct sk_batch {
     bool         packed;                // d_stream holds the host-packed form (sk_pack_stream) of nbytes bytes
     uint32_t    *h_rec;                 // page-locked staging of rec_start[nrec] + tile_first[ntiles + 2]: ONE copy from pinned memory instead of
     size_t       h_rec_cap;             // two from the caller's pageable arrays (which the runtime stages, chunk by chunk, on its own threads)
+    void        *text;                  // sk_text.hip's state of a batch filled from text (sk_batch_fill_text), freed through text_free
+    void       (*text_free)(void *);
 };
 
 extern "C" int sk_batch_create(sk_ctx *c, sk_batch **out)
@@ -946,6 +948,7 @@ extern "C" int sk_batch_create(sk_ctx *c, sk_batch **out)
     b->owner = c;
     b->d_stream = b->d_rec = NULL; b->stream_cap = b->rec_cap = 0; b->nbytes = 0; b->nrec = b->ntiles = 0;
     b->h_rec = NULL; b->h_rec_cap = 0; b->packed = false;
+    b->text = NULL; b->text_free = NULL;
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { delete b; return sk_fail(c, SK_E_HIP, "stream"); }
     if (hipEventCreateWithFlags(&b->ready, hipEventDisableTiming) != hipSuccess) { hipStreamDestroy(b->stream); delete b; return sk_fail(c, SK_E_HIP, "event"); }
     *out = b;
@@ -966,11 +969,62 @@ extern "C" void sk_batch_destroy(sk_batch *b)
     if (!b) return;
     hipSetDevice(b->owner->device);
     hipStreamSynchronize(b->stream);
+    if (b->text && b->text_free) b->text_free(b->text);
     hipFree(b->d_stream); hipFree(b->d_rec);
     if (b->h_rec) hipHostFree(b->h_rec);
     hipEventDestroy(b->ready);
     hipStreamDestroy(b->stream);
     delete b;
+}
+
+// Room for a stream of nbytes (+ 16 of slack) and rec_need bytes of record starts and tile index, on the device and in the page-locked
+// staging; waits for the batch's stream, so the staging of the previous upload is free again.
+static int sk_batch_room(sk_batch *b, uint64_t nbytes, size_t rec_need)
+{
+    sk_ctx *c = b->owner;
+    if (nbytes + 16 > b->stream_cap) {
+        SK_HIP(c, hipStreamSynchronize(b->stream));
+        (void)hipFree(b->d_stream); b->d_stream = NULL; b->stream_cap = 0;
+        const size_t want = nbytes + nbytes / 4 + 4096;
+        SK_HIP(c, hipMalloc(&b->d_stream, want));
+        b->stream_cap = want;
+    }
+    if (rec_need > b->rec_cap) {
+        SK_HIP(c, hipStreamSynchronize(b->stream));
+        (void)hipFree(b->d_rec); b->d_rec = NULL; b->rec_cap = 0;
+        const size_t want = rec_need + rec_need / 4 + 4096;
+        SK_HIP(c, hipMalloc(&b->d_rec, want));
+        b->rec_cap = want;
+    }
+    SK_HIP(c, hipStreamSynchronize(b->stream));            // the staging of the previous upload is free again
+    if (rec_need > b->h_rec_cap) {
+        if (b->h_rec) (void)hipHostFree(b->h_rec);
+        b->h_rec = NULL; b->h_rec_cap = 0;
+        const size_t want = rec_need + rec_need / 4 + 4096;
+        SK_HIP(c, hipHostMalloc((void **)&b->h_rec, want, hipHostMallocDefault));
+        b->h_rec_cap = want;
+    }
+    return SK_OK;
+}
+
+// The text parser's way to a batch (sk_text.hip: sk_batch_fill_text): room as above, then where its buffers are.
+extern "C" int sk_batch_hook_(sk_batch *b, uint64_t stream_bytes, uint64_t rec_words, sk_batch_hook *out)
+{
+    if (!b || !out) return SK_E_ARG;
+    if (stream_bytes > 0xFFFFFFF0ull) return sk_fail(b->owner, SK_E_ARG, "bad batch size");
+    SK_HIP(b->owner, hipSetDevice(b->owner->device));
+    const int rc = sk_batch_room(b, stream_bytes, (size_t)rec_words * 4);
+    if (rc != SK_OK) return rc;
+    out->owner = b->owner; out->stream = (void *)b->stream; out->ready = (void *)b->ready;
+    out->d_stream = b->d_stream; out->d_rec = (uint32_t *)b->d_rec; out->h_rec = b->h_rec;
+    out->text = &b->text; out->text_free = &b->text_free;
+    return SK_OK;
+}
+
+// ... and what the batch holds once the parse is known (nrec 0: nothing a tally may be launched on)
+extern "C" void sk_batch_contents_(sk_batch *b, uint64_t nbytes, uint32_t nrec)
+{
+    b->nbytes = nbytes; b->nrec = nrec; b->ntiles = (uint32_t)((nbytes + 32767u) >> 15); b->packed = false;
 }
 
 // Upload new contents.  Every tally launched on the previous contents must have been collected.
@@ -992,29 +1046,8 @@ static int sk_batch_fill_any(sk_batch *b, const uint8_t *stream, uint64_t nbytes
     if (nbytes == 0 || nrec == 0 || nbytes > 0xFFFFFFF0ull) return sk_fail(c, SK_E_ARG, "bad batch size");
     SK_HIP(c, hipSetDevice(c->device));
     const uint32_t ntiles = (uint32_t)((nbytes + 32767u) >> 15);
-    if (nbytes + 16 > b->stream_cap) {
-        SK_HIP(c, hipStreamSynchronize(b->stream));
-        (void)hipFree(b->d_stream); b->d_stream = NULL; b->stream_cap = 0;
-        const size_t want = nbytes + nbytes / 4 + 4096;
-        SK_HIP(c, hipMalloc(&b->d_stream, want));
-        b->stream_cap = want;
-    }
     const size_t rec_need = ((size_t)nrec + ntiles + 2) * 4;
-    if (rec_need > b->rec_cap) {
-        SK_HIP(c, hipStreamSynchronize(b->stream));
-        (void)hipFree(b->d_rec); b->d_rec = NULL; b->rec_cap = 0;
-        const size_t want = rec_need + rec_need / 4 + 4096;
-        SK_HIP(c, hipMalloc(&b->d_rec, want));
-        b->rec_cap = want;
-    }
-    SK_HIP(c, hipStreamSynchronize(b->stream));            // the staging of the previous upload is free again
-    if (rec_need > b->h_rec_cap) {
-        if (b->h_rec) (void)hipHostFree(b->h_rec);
-        b->h_rec = NULL; b->h_rec_cap = 0;
-        const size_t want = rec_need + rec_need / 4 + 4096;
-        SK_HIP(c, hipHostMalloc((void **)&b->h_rec, want, hipHostMallocDefault));
-        b->h_rec_cap = want;
-    }
+    { const int rc = sk_batch_room(b, nbytes, rec_need); if (rc != SK_OK) return rc; }
     memcpy(b->h_rec, rec_start, (size_t)nrec * 4);
     uint32_t *const tile_first = b->h_rec + nrec;
     for (uint32_t t = 0, r = 0; t < ntiles + 2; t++) {     // first record starting at or after the tile's first byte

@@ -112,7 +112,14 @@ typedef struct sd_chunk {
      * res_recs[res_off[s] .. res_off[s + 1]), its log entries res_hits[res_hoff[s] .. res_hoff[s + 1]) */
     sk_tally_rec *res_recs; sk_hit *res_hits; uint64_t *res_off, *res_hoff;
     int       refs;                          /* holders: the stream (queue, current chunk), every lane job that names it */
+    /* a piece of plain text for the device's parser (sd_text_read): buf holds text[toff .. toff + tlen) of the file and tla bytes of
+     * look-ahead; the arrays above are filled from the device's record starts once the piece is accepted (sd_text_resolve) */
+    int       text;                          /* SD_TEXT_*: 0 = a chunk the host parsed */
+    int       t_eof, tla;                    /* the file's last piece; bytes of look-ahead behind the piece (0 or 1) */
+    uint64_t  toff, tlen;
+    uint64_t  t_reads, t_eval;               /* accepted: records of k bases or more, and their windows */
 } sd_chunk;
+enum { SD_TEXT_PENDING = 1, SD_TEXT_ACCEPTED = 2, SD_TEXT_DECLINED = 3 };   /* (DECLINED before it went up: the reader found no piece to send) */
 typedef struct sd_sp { uint32_t n; uint32_t *rec, *all, *inf, *hbeg /* n + 1 */, *rows; } sd_sp;
 
 typedef struct {
@@ -134,6 +141,10 @@ typedef struct {
     int         split_failed;                /* a segment did not end between two records */
     int         cancel_segments;             /* the file is over for the reader (truncated record): later segments are dropped */
     int         in_mode;                     /* SD_IN_*: how the parser threads get at the bytes of a mapped plain file's segments */
+    /* plain text parsed on the device (sd_text_read): the reader sends pieces of text until the main thread's verdict */
+    int         text_mode;                   /* the option is on and the entry points are there */
+    int         text_verdict;                /* 0 none yet, SD_VERDICT_DONE the last piece was accepted, SD_VERDICT_HOST the piece at text_off declined */
+    uint64_t    text_off;
     /* consumer */
     sd_chunk   *c; uint32_t ci;
     int         eof, end_kind; size_t end_len;
@@ -216,8 +227,8 @@ static void chunk_free(sd_chunk *c)
 static void stream_push(sd_stream *st, sd_chunk *c)
 {
     pthread_mutex_lock(&st->mu);
-    while (st->qn == 3 && !st->cancel) pthread_cond_wait(&st->cv, &st->mu);
-    if (st->cancel) { pthread_mutex_unlock(&st->mu); chunk_free(c); return; }
+    while (st->qn == 3 && !st->cancel && !(c->text && st->text_verdict)) pthread_cond_wait(&st->cv, &st->mu);
+    if (st->cancel || (c->text && st->text_verdict)) { pthread_mutex_unlock(&st->mu); chunk_free(c); return; }   /* (text read ahead beyond a declined piece) */
     st->q[st->qn++] = c;
     pthread_cond_broadcast(&st->cv);
     pthread_mutex_unlock(&st->mu);
@@ -450,6 +461,101 @@ static void sd_seg_dispatch(sd_stream *st, sd_seg *sg)
     pthread_mutex_unlock(&st->pmu);
 }
 
+/* ---- plain text parsed on the device (opt-in: option "device_parse" through sk_text_option, or SK_DEVICE_PARSE=1) -------------
+ * With the switch on, a mapped plain file is not parsed here at all: the reader thread copies it, piece by piece, into page-locked
+ * buffers and queues the pieces AS TEXT; the main thread sends each up (sk_batch_fill_text, ahead of its turn like any chunk) and the
+ * device parses it straight into the batch the TALLY scan reads (sk_text.hip).  A piece starts at a verified record boundary -- the
+ * file's start, or the end of an accepted piece -- and ends at a GUESSED one (parser_guess_start, as the segments below): nothing
+ * is trusted from the guess, the device must consume exactly the piece.  A piece before the last goes up with one byte of
+ * look-ahead, the next piece's first byte, so that both device forms count its last record (FASTQ4: four whole lines; FASTA: the
+ * next header's character at a line start).  Whatever the device does not take -- a declined piece, another `consumed`, too many
+ * records, no cut within one buffer, a last piece without its final '\n' (whose ending the host parser tells apart) -- hands the
+ * REST of the file, from that piece's start, to the host path below (segments and parser threads, started at that offset); pieces
+ * read ahead beyond it are dropped.  The entry points are weak: the host-only test builds link this file without them, and without
+ * them the switch is the host path. */
+#pragma weak sk_text_enabled
+#pragma weak sk_batch_fill_text
+#pragma weak sk_batch_text_finish
+enum { SD_VERDICT_DONE = 1, SD_VERDICT_HOST = 2 };
+#define SD_TEXT_PIECE_MAX (256ull << 20)               /* the device parser's offsets are 32-bit */
+static unsigned long n_text_taken, n_text_declined;    /* SK_SD_TIMING: pieces the device parsed, pieces handed to the host */
+
+static int sd_text_wanted(void)
+{
+    if (!sk_text_enabled || !sk_batch_fill_text || !sk_batch_text_finish || !sd_dev.ctx[0]) return 0;
+    return sk_text_enabled(sd_dev.ctx[0]);
+}
+
+/* Where the piece t[0 .. ) of a text of n > cap bytes ends: a guessed record start g with g + 1 <= cap (the piece and its byte of look-ahead
+ * fit one buffer), or 0 when there is none.  Looked for in the buffer's last `tail` bytes first, so that pieces are about a buffer
+ * long; when that search overshoots (records longer than the tail: contigs, genomes) from ever earlier places -- half way, a quarter,
+ * ... the first line -- so any record start inside the buffer is found.  Never more than cap + tail bytes are looked at. */
+static size_t sd_text_cut(const unsigned char *t, size_t n, size_t cap, size_t tail)
+{
+    const size_t lim = n < cap + tail ? n : cap + tail;
+    size_t x = cap - tail;
+    for (;;) {
+        const size_t g = (size_t)parser_guess_start(t, lim, x, lim == n);
+        if (g + 1 <= cap) return g;
+        if (x <= 1) return 0;
+        x /= 2;
+    }
+}
+
+/* the reader's side.  1: the file is done (every piece accepted, or the stream cancelled); 0: the host path takes over at *from */
+static int sd_text_read(sd_stream *st, const unsigned char *map, size_t mlen, int fd, size_t *from)
+{
+    const size_t room = st->chunk_bytes < sd_pin.bytes ? st->chunk_bytes : sd_pin.bytes;
+    const size_t cap = room < SD_TEXT_PIECE_MAX ? room : (size_t)SD_TEXT_PIECE_MAX;      /* piece + look-ahead */
+    const size_t tail = cap / 2 < (64u << 10) ? cap / 2 : (64u << 10);                   /* a cut is looked for in the buffer's last bytes */
+    size_t at = 0;
+    int verdict = 0;
+    sd_chunk *spare = chunk_new();                         /* the marker that ends the text, should a chunk not be had later */
+    if (!spare) { *from = 0; return 0; }                   /* (nothing is queued yet: the host path takes the whole file) */
+    while (at < mlen && !verdict) {
+        sd_chunk *c;
+        size_t cut = mlen;
+        pthread_mutex_lock(&st->mu);
+        verdict = st->cancel ? SD_VERDICT_DONE : st->text_verdict;
+        pthread_mutex_unlock(&st->mu);
+        if (verdict) break;
+        if (mlen - at > cap) cut = at + sd_text_cut(map + at, mlen - at, cap, tail);
+        if ((c = chunk_new()) == NULL) { c = spare; spare = NULL; cut = at; }      /* (no memory: the host path from here, not a wait for a verdict nobody gives) */
+        c->toff = at;
+        if (cut == at || (cut == mlen && map[mlen - 1] != '\n')) c->text = SD_TEXT_DECLINED;      /* no cut within one buffer; a last line without its '\n' */
+        else {
+            size_t have = 0;
+            c->text = SD_TEXT_PENDING;
+            c->tlen = cut - at;
+            c->tla = cut < mlen;
+            c->t_eof = cut == mlen;
+            if ((c->buf = (uint8_t *)sd_pin_get()) != NULL) c->pinned = 1;
+            else { c->buf = (uint8_t *)malloc(cap); __atomic_add_fetch(&n_unpinned_chunks, 1, __ATOMIC_RELAXED); }
+            if (!c->buf) { c->text = SD_TEXT_DECLINED; c->tlen = 0; }
+            while (c->buf && fd >= 0 && have < c->tlen + (size_t)c->tla) {
+                const ssize_t r = pread(fd, c->buf + have, c->tlen + (size_t)c->tla - have, (off_t)(at + have));
+                if (r < 0 && errno == EINTR) continue;
+                if (r <= 0) break;
+                have += (size_t)r;
+            }
+            if (c->buf && have < c->tlen + (size_t)c->tla) memcpy(c->buf + have, map + at + have, c->tlen + (size_t)c->tla - have);   /* (a failed read: out of the mapping) */
+        }
+        {
+            const int stop = c->text == SD_TEXT_DECLINED;
+            stream_push(st, c);
+            if (stop) break;
+        }
+        at = cut;
+    }
+    chunk_free(spare);
+    pthread_mutex_lock(&st->mu);
+    while (!st->cancel && !st->text_verdict) pthread_cond_wait(&st->cv, &st->mu);
+    verdict = st->cancel ? SD_VERDICT_DONE : st->text_verdict;
+    *from = (size_t)st->text_off;
+    pthread_mutex_unlock(&st->mu);
+    return verdict != SD_VERDICT_HOST;
+}
+
 static void *sd_decode_thread(void *arg)
 {
     enum { BLK = 1 << 20 };
@@ -464,6 +570,7 @@ static void *sd_decode_thread(void *arg)
     const unsigned char *map = NULL;
     size_t mlen = 0;
     int map_fd = -1;
+    size_t map_from = 0;                                  /* where the host path starts in a mapped file: behind the text the device took */
     if (!own && !getenv("SK_ZLIB")) {
         const int fd = open(st->path, O_RDONLY);
         struct stat sb;
@@ -474,6 +581,9 @@ static void *sd_decode_thread(void *arg)
         if (fd >= 0 && map) map_fd = fd; else if (fd >= 0) close(fd);       /* (kept open for the parser threads' pread, should they go that way) */
         if (map && mlen >= 2 && map[0] == 0x1f && map[1] == 0x8b) { munmap((void *)map, mlen); map = NULL; }   /* (gzip after all: zlib) */
     }
+    if (map && st->text_mode && sd_text_read(st, map, mlen, map_fd, &map_from)) {
+        /* (every piece of the text went to the device, or the stream was cancelled) */
+    } else
     if (st->par > 1 && (own || map)) {
         /* a .gz file inflated by several threads delivers text faster than one thread parses it (measured, 3 Gbase of FASTA,
          * 16 inflate threads: waiting for the decode side 0.73 s with one parser, 0.47 s with four), and so does a mapped
@@ -492,7 +602,7 @@ static void *sd_decode_thread(void *arg)
             for (i = 0; i < npar && i < SD_PARSERS_MAX; i++) if (pthread_create(&wk[nw], NULL, sd_parse_worker, st) == 0) nw++;
         }
         if (map) {
-            size_t at = 0;
+            size_t at = map_from;
             while (at < mlen && nw) {
                 size_t cut = mlen;
                 int over;
@@ -582,7 +692,7 @@ static void *sd_decode_thread(void *arg)
             while (ps.state != P_STOP && !st->cancel && (n = skzp_next(&zp, &data)) > 0) parser_feed(&ps, data, n);
         } else {
             if (map) {
-                size_t at = 0;
+                size_t at = map_from;
                 while (ps.state != P_STOP && !st->cancel && at < mlen) {
                     const size_t n = mlen - at < (4u << 20) ? mlen - at : (4u << 20);
                     parser_feed(&ps, map + at, n);
@@ -596,7 +706,7 @@ static void *sd_decode_thread(void *arg)
         b.cur = NULL;
         c->last = 1;
         c->end_kind = ps.end_kind;
-        c->end_len = ps.end_len;
+        c->end_len = !ps.nrecords && ps.end_kind == SKP_END_STALE ? st->carry_last_len : ps.end_len;   /* ("the previous record" may lie in text the device took: 0 otherwise, as end_len) */
         stream_push(st, c);
         parser_free(&ps);
     }
@@ -638,6 +748,7 @@ static int stream_open(sd_stream *st, const char *path, int gz_threads)
         if (getenv("SK_NO_SPLIT") || st->par < 2) st->par = 1;
         if (st->par > SD_PARSERS_MAX) st->par = SD_PARSERS_MAX;
     }
+    st->text_mode = sd_text_wanted();
     pthread_mutex_init(&st->pmu, NULL);
     pthread_cond_init(&st->pcv, NULL);
     st->g = gzopen(path, "r");
@@ -1146,10 +1257,12 @@ static void sd_prefetch(sd_stream *st)
     pthread_mutex_lock(&st->mu);
     if (st->qn > 0) n = st->q[0];                          /* (only this thread takes chunks off the queue: n stays) */
     pthread_mutex_unlock(&st->mu);
-    if (!n || n == st->pre || !n->np) return;
+    if (!n || n == st->pre || (n->text ? n->text != SD_TEXT_PENDING : !n->np)) return;
     for (d = 0; d < sd_dev.n && ok; d++) {
         sk_batch **b = &st->bat[st->bcur ^ 1][d];
         if (!*b && sd_batch_get(d, b) != SK_OK) { *b = NULL; ok = 0; break; }
+        if (n->text) ok = sk_batch_fill_text(*b, n->buf, n->tlen + (uint64_t)n->tla, n->t_eof) == SK_OK;     /* (a piece of text: upload + parse, enqueued) */
+        else
         ok = (n->packed ? sk_batch_fill_packed(*b, n->buf, n->blen, n->pstart, n->np) : sk_batch_fill(*b, n->buf, n->blen, n->pstart, n->np)) == SK_OK;
     }
     if (ok) st->pre = n;                                   /* (all devices or none: a chunk that is not everywhere goes up again) */
@@ -1260,6 +1373,74 @@ static int sd_collect(sd_prog *p, uint32_t ns, sk_batch **batches, sd_chunk *c)
     return SK_OK;
 }
 
+/* A piece of text whose turn has come (or whose scan is to be started ahead): wait for the device's parse in `batches` (begun: it was
+ * sent up ahead) and, if the device took exactly the piece, fill in what the host walk needs from the record starts -- the batch
+ * holds EVERY record, short and empty ones included, so the records of the scan are the records of the file (prec is the
+ * identity) and len[i] is the distance of two starts less the '\n'.  A record shorter than k has no window: it tallies nothing.
+ * 1 accepted, 0 declined (c->text says so), < 0 device error. */
+static int sd_text_resolve(sd_stream *st, sd_chunk *c, sk_batch **batches, int begun)
+{
+    sk_text_info info[SD_MAX_DEV];
+    const uint32_t *starts = NULL;
+    int d, rc = SK_OK, ok = 1;
+    uint32_t i, n;
+    if (c->text != SD_TEXT_PENDING) return c->text == SD_TEXT_ACCEPTED;
+    pthread_mutex_lock(&sd_dev_mu);
+    for (d = 0; d < sd_dev.n && !begun && rc == SK_OK; d++) rc = sk_batch_fill_text(batches[d], c->buf, c->tlen + (uint64_t)c->tla, c->t_eof);
+    for (d = 0; d < sd_dev.n && rc == SK_OK; d++) rc = sk_batch_text_finish(batches[d], &info[d], d == 0 ? &starts : NULL);
+    pthread_mutex_unlock(&sd_dev_mu);
+    if (rc != SK_OK) return rc;
+    for (d = 0; d < sd_dev.n; d++)
+        ok = ok && info[d].status == SK_TEXT_OK && info[d].consumed == c->tlen && info[d].nrecords <= (1u << 22) && info[d].nrecords == info[0].nrecords &&
+             info[d].stream_bytes == info[0].stream_bytes;
+    if (c->pinned) sd_pin_put(c->buf); else free(c->buf);      /* (the text is on the device, or nobody wants it) */
+    c->buf = NULL; c->pinned = 0;
+    if (!ok) { c->text = SD_TEXT_DECLINED; return 0; }
+    n = (uint32_t)info[0].nrecords;
+    c->len = (uint64_t *)malloc(((size_t)n + 1) * sizeof *c->len);
+    c->pstart = (uint32_t *)malloc(((size_t)n + 1) * sizeof *c->pstart);
+    c->prec = (uint32_t *)malloc(((size_t)n + 1) * sizeof *c->prec);
+    if (!c->len || !c->pstart || !c->prec) return SK_E_NOMEM;
+    if (n) memcpy(c->pstart, starts, (size_t)n * sizeof *c->pstart);
+    for (i = 0; i < n; i++) {
+        const uint64_t l = (i + 1 < n ? (uint64_t)c->pstart[i + 1] : info[0].stream_bytes) - c->pstart[i] - 1;
+        c->len[i] = l;
+        c->prec[i] = i;
+        if (l >= SK_K) { c->t_reads++; c->t_eval += l - (SK_K - 1); }
+    }
+    c->nrec = c->np = n;
+    c->blen = info[0].stream_bytes;
+    c->text = SD_TEXT_ACCEPTED;
+    n_text_taken++;
+    if (n) st->carry_last_len = (size_t)c->len[n - 1];
+    if (c->t_eof) {
+        /* the file ends behind a whole record and its '\\n': the host parser would stand in P_SEEK after a FASTQ record (END_STALE, the
+         * last record's length) and at a line start in FASTA (END_RESET) -- sk_parser.h: parser_eof */
+        c->last = 1;
+        c->end_kind = info[0].form == SK_TEXT_FASTQ4 ? SKP_END_STALE : SKP_END_RESET;
+        c->end_len = info[0].form == SK_TEXT_FASTQ4 ? st->carry_last_len : 0;
+        pthread_mutex_lock(&st->mu);
+        st->text_verdict = SD_VERDICT_DONE;
+        pthread_cond_broadcast(&st->cv);
+        pthread_mutex_unlock(&st->mu);
+    }
+    return 1;
+}
+
+/* the piece `c` declined: the reader's host path takes the file from c's start, and the text read ahead beyond it goes */
+static void sd_text_decline(sd_stream *st, sd_chunk *c)
+{
+    int i;
+    n_text_declined++;                                           /* (no other piece is on its way up: the next one goes when this one's scan runs) */
+    pthread_mutex_lock(&st->mu);
+    st->text_verdict = SD_VERDICT_HOST;
+    st->text_off = c->toff;
+    for (i = 0; i < st->qn; i++) chunk_free(st->q[i]);          /* (all of them text: the host path has not begun) */
+    st->qn = 0;
+    pthread_cond_broadcast(&st->cv);
+    pthread_mutex_unlock(&st->mu);
+}
+
 /* One chunk against every strain.  uploaded: its bytes are in `batches` already (prefetched while the chunk before it was scanned);
  * launched: its scans are in flight as well (started while the chunk before it was being replayed: sd_launch_ahead). */
 static int sd_tally_chunk(sd_prog *p, uint32_t ns, sk_batch **batches, sd_pool *pool, sd_chunk *c, int uploaded, int launched, sd_stream *st)
@@ -1298,6 +1479,7 @@ static void sd_launch_ahead(sd_stream *st, sd_prog *p, uint32_t ns)
 {
     const double t0 = now_s();
     if (!st->solo || !st->pre || st->ahead || getenv("SK_SD_NO_AHEAD")) return;
+    if (st->pre->text && (sd_text_resolve(st, st->pre, st->bat[st->bcur ^ 1], 1) != 1 || !st->pre->np)) return;   /* (its turn will tell: a decline or an error is dealt with there) */
     pthread_mutex_lock(&sd_dev_mu);
     if (sd_launch(p, ns, st->bat[st->bcur ^ 1]) == SK_OK) st->ahead = st->pre;
     else sd_drain_scans();
@@ -1338,7 +1520,7 @@ static int stream_fill(sd_stream *st, sd_prog *p, uint32_t ns, sk_batch *batch, 
         pthread_mutex_unlock(&st->mu);
         {
             const double t0 = now_s();
-            const int uploaded = st->pre == c;             /* its bytes went up while the chunk before it was scanned */
+            int uploaded = st->pre == c;                   /* its bytes went up while the chunk before it was scanned */
             const int launched = uploaded && st->ahead == c;   /* ... and its scans were started while that chunk was replayed */
             (void)batch;
             if (uploaded) st->bcur ^= 1;
@@ -1346,6 +1528,12 @@ static int stream_fill(sd_stream *st, sd_prog *p, uint32_t ns, sk_batch *batch, 
             st->ahead = NULL;
             for (i = 0; i < sd_dev.n; i++)
                 if (!st->bat[st->bcur][i] && (rc = sd_batch_get(i, &st->bat[st->bcur][i])) != SK_OK) { st->bat[st->bcur][i] = NULL; chunk_free(c); return rc; }
+            if (c->text) {                                 /* a piece of text: what the device made of it */
+                rc = sd_text_resolve(st, c, st->bat[st->bcur], uploaded);
+                if (rc < 0) { chunk_free(c); return rc; }
+                if (rc == 0) { sd_text_decline(st, c); chunk_free(c); t_tally += now_s() - t0; continue; }      /* the host parser's chunks follow */
+                uploaded = 1;                              /* (the batch holds it) */
+            }
             rc = sd_tally_chunk(p, ns, st->bat[st->bcur], pool, c, uploaded, launched, st);
             if (rc == SK_OK) sd_launch_ahead(st, p, ns);
             t_tally += now_s() - t0;
@@ -1553,8 +1741,11 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
         if (!cb && astep == 1 && a0 == 0 && n == ca->nrec) {
             /* a whole chunk of single reads (the usual case): its builder counted the records of k bases or more (np) and laid their
              * bases end to end with a '\n' after each (blen) -- the sums without a walk over 200,000 lengths per chunk */
+            if (ca->text) { reads += ca->t_reads; evaluated += ca->t_eval; }     /* (a batch made from text holds the short records too: summed when it was accepted) */
+            else {
             reads += ca->np;
             evaluated += (ca->blen - ca->np) - (uint64_t)(SK_K - 1) * ca->np;
+            }
         } else
         for (j = 0; j < n; j++) {
             const uint64_t la = ca->len[a0 + j * astep];
@@ -2193,6 +2384,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     if ((env = getenv("SK_SD_GROUP")) != NULL && atoi(env) >= 1 && atoi(env) <= SK_UNION_MAX) sd_group = (uint32_t)atoi(env);
     memset(sd_dev.ctx, 0, sizeof sd_dev.ctx);
     t_begin = now_s();
+    n_text_taken = n_text_declined = 0;                  /* (per run: the library entry points may be called again in one process) */
     {
         const long ncpu = sk_cpu_budget();
         skzo_pool_start(&zpool, getenv("SK_THREADS") ? atoi(getenv("SK_THREADS")) : (int)(ncpu > 16 ? 16 : ncpu < 1 ? 1 : ncpu));
@@ -2323,6 +2515,8 @@ done:
     if (getenv("SK_SD_TIMING"))
         fprintf(err, "strain_detect timing: page-locked chunk buffers: %d of at most %d made (%zu bytes each), %lu chunks had to do without one\n",
                 sd_pin.total, SD_PIN_MAX, sd_pin.bytes, n_unpinned_chunks);
+    if (getenv("SK_SD_TIMING") && (n_text_taken || n_text_declined || sd_text_wanted()))
+        fprintf(err, "strain_detect timing: text pieces parsed on the device: %lu taken, %lu declined (the host parsed the rest of their files)\n", n_text_taken, n_text_declined);
     if (getenv("SK_SD_TIMING") && t_pw_parse > 0)
         fprintf(err, "strain_detect timing: parser threads, summed: parsing %.2f s, waiting for a segment %.2f s, for their turn to hand chunks on %.2f s, for room in the queue %.2f s\n",
                 t_pw_parse, t_pw_seg, t_pw_turn, t_pw_push);

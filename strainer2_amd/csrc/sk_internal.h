@@ -35,6 +35,18 @@ void sk_inflater_destroy(sk_inflater *f);
 const char *sk_inflater_error(const sk_inflater *f);
 uint64_t sk_inflate_gz_size(const uint8_t *gz, uint64_t n);
 int  sk_inflate_gz(sk_inflater *f, const uint8_t *gz, uint64_t n, uint8_t *host_text, uint64_t host_cap, uint64_t *text_len, uint32_t *trailer_crc);
+/* A batch's buffers, for the text parser that fills it on the device (sk_text.hip: sk_batch_fill_text).  sk_batch_hook_ makes room for
+ * a stream of stream_bytes and rec_words u32 of record starts + tile index (device and page-locked staging), waits for the batch's
+ * stream and says where they are; `text`/`text_free`: the parser's own state of this batch, freed by sk_batch_destroy.
+ * sk_batch_contents_: what the batch holds now (nrec 0: nothing to launch on). */
+typedef struct sk_batch_hook {
+    sk_ctx *owner;
+    void *stream, *ready;              /* hipStream_t, hipEvent_t */
+    void *d_stream; uint32_t *d_rec, *h_rec;
+    void **text; void (**text_free)(void *);
+} sk_batch_hook;
+int  sk_batch_hook_(sk_batch *b, uint64_t stream_bytes, uint64_t rec_words, sk_batch_hook *out);
+void sk_batch_contents_(sk_batch *b, uint64_t nbytes, uint32_t nrec);
 #ifdef __cplusplus
 }
 #endif

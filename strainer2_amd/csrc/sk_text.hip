@@ -17,6 +17,8 @@
 //   sk_text_emit     a wave takes 64 consecutive lines, whose kept bytes are ONE contiguous range of the output: every lane
 //                    writes aligned words of it and finds each byte's line by a search over the wave's 64 offsets in LDS --
 //                    coalesced for 150-byte reads and for a 5 Mbp record of 60-column lines alike
+//   sk_text_batch_close  (strain_detect's batches, sk_batch_fill_text) the tile index the TALLY scan reads behind the record starts, by
+//                    a lower-bound search per 32 KiB tile, and the starts copied home, 16 bytes per lane
 // Ordinary vector loads and stores throughout; the flags are plain atomics.
 #include <hip/hip_runtime.h>
 #include <pthread.h>
@@ -357,11 +359,36 @@ __global__ void __launch_bounds__(TX_THREADS) sk_text_emit(const uint8_t *__rest
     }
 }
 
+// A batch filled from text is finished on the device: nrec and the stream's length are known only here.  (a) tile_first[t], for the
+// ntiles + 2 entries the TALLY scan reads behind rec_start[nrec]: the first record starting at or after byte t << 15 -- one lane per
+// tile, a lower-bound search of the starts (ascending, all different: an empty record's start is one byte before the next one's).
+// (b) the starts go home: 16 bytes per lane into the batch's page-locked staging, from which the host derives every record's length.
+// More records than there is room for (a piece the host treats as declined): nothing is written.
+__global__ void __launch_bounds__(TX_THREADS) sk_text_batch_close(const tx_head *__restrict__ h, uint32_t *__restrict__ rec, uint32_t nrec_cap,
+                                                                    uint4 *__restrict__ host_rec)
+{
+    if (h->decline) return;
+    const uint64_t nrec64 = h->info.nrecords;
+    if (!nrec64 || nrec64 > nrec_cap) return;
+    const uint32_t nrec = (uint32_t)nrec64;
+    const uint32_t ntiles = (uint32_t)((h->info.stream_bytes + 32767u) >> 15);
+    const uint32_t gid = blockIdx.x * TX_THREADS + threadIdx.x, gsz = gridDim.x * TX_THREADS;
+    for (uint32_t t = gid; t < ntiles + 2u; t += gsz) {
+        const uint64_t edge = (uint64_t)t << 15;
+        uint32_t lo = 0, hi = nrec;                               // the first r in [0, nrec] with rec[r] >= edge
+        while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (rec[mid] < edge) lo = mid + 1u; else hi = mid; }
+        rec[nrec + t] = lo;
+    }
+    const uint4 *const rec16 = (const uint4 *)rec;                // (whole 16-byte groups: the last one may take in tile entries, for which both sides have room)
+    for (uint32_t i = gid; i < (nrec + 3u) / 4u; i += gsz) host_rec[i] = rec16[i];
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 // The scratch of a context: made when the context first parses, sized for the piece at hand (the list scan's pieces have one
 // size; a piece that grew makes it grow once more), kept until sk_text_release or the end of the process.
-struct tx_state {
-    int          device = 0;
+// what one parse works in: a stream, the scratch of the passes, the head block and where it lands.  A context has one (tx_state), and so
+// has every batch that is filled from text (tx_batch: two batches of one context are parsed side by side).
+struct tx_work {
     hipStream_t  stream = NULL;
     uint64_t     cap = 0;             // text bytes the scratch serves
     uint32_t     line_cap = 0;
@@ -371,6 +398,10 @@ struct tx_state {
     unsigned long long *d_blk = NULL; // per block of TX_LB lines {records << 32 | bytes}, then its prefix
     tx_head     *d_head = NULL;
     tx_head     *h_head = NULL;       // page-locked landing place
+    hipEvent_t   ev0 = NULL, ev1 = NULL;  // around the passes of the last parse (sk_text_timing); NULL: not timed
+};
+struct tx_state : tx_work {
+    int          device = 0;
     // sk_scan_text_pinned: the text as uploaded, two record-stream buffers taking turns; readers[b]: the contexts whose scans
     // of d_out[b] have not been waited for -- they are, before a parse writes that buffer again
     uint64_t     up_cap = 0;
@@ -378,7 +409,6 @@ struct tx_state {
     std::vector<sk_ctx *> readers[2];
     int          cur = 0;
     uint64_t     pieces = 0, declined = 0;
-    hipEvent_t   ev0 = NULL, ev1 = NULL;  // around the passes of the last parse (sk_text_timing)
     int          opt = -1;            // sk_text_option: 0 off, 1 on, -1 not set (SK_DEVICE_PARSE decides)
 };
 static pthread_mutex_t tx_mu = PTHREAD_MUTEX_INITIALIZER;
@@ -386,7 +416,7 @@ static std::map<sk_ctx *, tx_state *> tx_states;
 
 #define TX_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sk_fail_(ctx, SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 
-static void tx_free_scratch(tx_state *s)
+static void tx_free_scratch(tx_work *s)
 {
     (void)hipFree(s->d_tiles); (void)hipFree(s->d_nl); (void)hipFree(s->d_lineval); (void)hipFree(s->d_blk);
     s->d_tiles = NULL; s->d_nl = NULL; s->d_lineval = NULL; s->d_blk = NULL; s->cap = 0;
@@ -457,7 +487,7 @@ extern "C" void sk_text_release(sk_ctx *ctx)
     delete s;
 }
 
-static int tx_scratch(sk_ctx *ctx, tx_state *s, uint64_t nbytes)
+static int tx_scratch(sk_ctx *ctx, tx_work *s, uint64_t nbytes)
 {
     if (nbytes <= s->cap) return SK_OK;
     TX_HIP(hipStreamSynchronize(s->stream));
@@ -473,15 +503,15 @@ static int tx_scratch(sk_ctx *ctx, tx_state *s, uint64_t nbytes)
     return SK_OK;
 }
 
-// the passes, on s->stream; the info lands in s->h_head (valid after the stream is synchronised)
-static int tx_enqueue(sk_ctx *ctx, tx_state *s, const void *dev_text, uint64_t nbytes, int is_eof, void *dev_stream, uint32_t *dev_rec_start, uint64_t nrec_cap)
+// the passes, on s->stream (enqueued only: nothing here waits); the info lands in s->h_head (valid after the stream is synchronised)
+static int tx_enqueue(sk_ctx *ctx, tx_work *s, const void *dev_text, uint64_t nbytes, int is_eof, void *dev_stream, uint32_t *dev_rec_start, uint64_t nrec_cap)
 {
     const uint32_t ntiles = (uint32_t)((nbytes + TX_TILE - 1u) / TX_TILE);
     uint64_t max_lines = nbytes + 1u;
     if (max_lines > s->line_cap) max_lines = s->line_cap;
     const uint32_t nblk = (uint32_t)(max_lines / TX_LB + 1u);
     const uint8_t *text = (const uint8_t *)dev_text;
-    TX_HIP(hipEventRecord(s->ev0, s->stream));
+    if (s->ev0) TX_HIP(hipEventRecord(s->ev0, s->stream));
     TX_HIP(hipMemsetAsync(s->d_head, 0, sizeof(tx_head), s->stream));
     hipLaunchKernelGGL(sk_text_mark, dim3(ntiles), dim3(TX_THREADS), 0, s->stream, (const uint4 *)dev_text, nbytes, s->d_tiles);
     hipLaunchKernelGGL(sk_text_scan, dim3(1), dim3(1024), 0, s->stream, s->d_tiles, ntiles, 1, s->d_head, text, nbytes,
@@ -495,12 +525,12 @@ static int tx_enqueue(sk_ctx *ctx, tx_state *s, const void *dev_text, uint64_t n
     hipLaunchKernelGGL(sk_text_emit, dim3(nblk), dim3(TX_THREADS), 0, s->stream, text, nbytes, (const uint32_t *)s->d_nl, (const tx_head *)s->d_head,
                        (const uint32_t *)s->d_lineval, (const unsigned long long *)s->d_blk, (uint8_t *)dev_stream, dev_rec_start, nrec_cap);
     TX_HIP(hipGetLastError());
-    TX_HIP(hipEventRecord(s->ev1, s->stream));
+    if (s->ev1) TX_HIP(hipEventRecord(s->ev1, s->stream));
     TX_HIP(hipMemcpyAsync(s->h_head, s->d_head, sizeof(tx_head), hipMemcpyDeviceToHost, s->stream));
     return SK_OK;
 }
 
-static void tx_result(const tx_state *s, sk_text_info *info)
+static void tx_result(const tx_work *s, sk_text_info *info)
 {
     memset(info, 0, sizeof *info);
     if (s->h_head->decline) { info->status = SK_TEXT_DECLINED; info->form = s->h_head->form; }
@@ -612,6 +642,93 @@ extern "C" int sk_scan_text_pinned_many(sk_ctx *const *ctxs, uint32_t nctx, cons
 extern "C" int sk_scan_text_pinned(sk_ctx *ctx, const uint8_t *pinned_text, uint64_t nbytes, int is_eof, uint32_t col, sk_text_info *info)
 {
     return sk_scan_text_pinned_many(&ctx, 1, pinned_text, nbytes, is_eof, col, info);
+}
+
+// ---- a strain_detect batch filled from text (sk_batch_fill_text / sk_batch_text_finish) ---------------------------------------
+// Begin enqueues, on the batch's own stream: the upload of the text, the passes above writing the record stream and every record's
+// start straight into the batch's buffers, sk_text_batch_close, and the copy home of the info; the batch's `ready` event follows
+// them.  Nothing waits, so strain_detect's upload-ahead stays what it is.  Finish waits and says what the batch holds.  Every batch
+// has its own scratch and head block: the two batches of a stream, and those of two streams (PE), are parsed side by side.
+#define TX_BATCH_RECS (1u << 22)          // records in one piece at most (the host path's cap per chunk); more declines
+
+struct tx_batch : tx_work {
+    uint8_t *d_text = NULL;
+    uint64_t text_cap = 0;
+    uint32_t nrec_cap = 0;
+    bool     pending = false;
+};
+
+static void tx_batch_free(void *p)        // (sk_batch_destroy: the device is set and the batch's stream has run dry)
+{
+    tx_batch *t = (tx_batch *)p;
+    tx_free_scratch(t);
+    (void)hipFree(t->d_text);
+    (void)hipFree(t->d_head);
+    if (t->h_head) (void)hipHostFree(t->h_head);
+    delete t;
+}
+
+extern "C" int sk_batch_fill_text(sk_batch *b, const uint8_t *pinned_text, uint64_t nbytes, int is_eof)
+{
+    if (!b || !pinned_text || !nbytes || nbytes > TX_MAX) return SK_E_ARG;
+    // a record takes two bytes of text at least (a header character and its '\n'), and the stream is shorter than the text
+    const uint32_t nrec_cap = nbytes / 2u + 1u < TX_BATCH_RECS ? (uint32_t)(nbytes / 2u + 1u) : TX_BATCH_RECS;
+    const uint32_t tiles_max = (uint32_t)((nbytes + 32767u) >> 15) + 2u;
+    sk_batch_hook hk;
+    int rc = sk_batch_hook_(b, nbytes, (uint64_t)nrec_cap + tiles_max + 4u, &hk);
+    if (rc != SK_OK) return rc;
+    sk_ctx *const ctx = hk.owner;
+    sk_batch_contents_(b, 0, 0);                                  // (nothing to launch on until sk_batch_text_finish says so)
+    tx_batch *t = (tx_batch *)*hk.text;
+    if (!t) {
+        if ((t = new (std::nothrow) tx_batch()) == NULL) return SK_E_NOMEM;
+        t->stream = (hipStream_t)hk.stream;
+        if (hipMalloc((void **)&t->d_head, sizeof(tx_head)) != hipSuccess || hipHostMalloc((void **)&t->h_head, sizeof(tx_head), hipHostMallocDefault) != hipSuccess) {
+            tx_batch_free(t);
+            return sk_fail_(ctx, SK_E_HIP, "no memory for the batch's text parser");
+        }
+        *hk.text = t;
+        *hk.text_free = tx_batch_free;
+    }
+    t->pending = false;
+    if ((rc = tx_scratch(ctx, t, nbytes)) != SK_OK) return rc;
+    if (t->cap > t->text_cap) {
+        (void)hipFree(t->d_text); t->d_text = NULL; t->text_cap = 0;
+        TX_HIP(hipMalloc((void **)&t->d_text, t->cap + 64u));
+        t->text_cap = t->cap;
+    }
+    uint4 *host_rec = NULL;
+    TX_HIP(hipHostGetDevicePointer((void **)&host_rec, hk.h_rec, 0));
+    TX_HIP(hipMemcpyAsync(t->d_text, pinned_text, nbytes, hipMemcpyHostToDevice, t->stream));
+    if ((rc = tx_enqueue(ctx, t, t->d_text, nbytes, is_eof, hk.d_stream, hk.d_rec, nrec_cap)) != SK_OK) return rc;
+    uint32_t work = nrec_cap / 4u + 1u > tiles_max ? nrec_cap / 4u + 1u : tiles_max, blocks = (work + TX_THREADS - 1u) / TX_THREADS;
+    if (blocks > 1024u) blocks = 1024u;
+    hipLaunchKernelGGL(sk_text_batch_close, dim3(blocks), dim3(TX_THREADS), 0, t->stream, (const tx_head *)t->d_head, hk.d_rec, nrec_cap, host_rec);
+    TX_HIP(hipGetLastError());
+    TX_HIP(hipEventRecord((hipEvent_t)hk.ready, t->stream));
+    t->nrec_cap = nrec_cap;
+    t->pending = true;
+    return SK_OK;
+}
+
+extern "C" int sk_batch_text_finish(sk_batch *b, sk_text_info *info, const uint32_t **rec_start)
+{
+    if (!b || !info) return SK_E_ARG;
+    sk_batch_hook hk;
+    const int rc = sk_batch_hook_(b, 0, 0, &hk);                  // (waits for the batch's stream)
+    if (rc != SK_OK) return rc;
+    tx_batch *const t = (tx_batch *)*hk.text;
+    if (!t || !t->pending) return sk_fail_(hk.owner, SK_E_STATE, "no text in flight for this batch");
+    t->pending = false;
+    tx_result(t, info);
+    if (info->status == SK_TEXT_OK && info->nrecords > t->nrec_cap) {     // too many records for one batch: the host takes the piece
+        const uint32_t form = info->form;
+        memset(info, 0, sizeof *info);
+        info->status = SK_TEXT_DECLINED; info->form = form;
+    }
+    if (info->status == SK_TEXT_OK && info->nrecords) sk_batch_contents_(b, info->stream_bytes, (uint32_t)info->nrecords);
+    if (rec_start) *rec_start = hk.h_rec;
+    return SK_OK;
 }
 
 extern "C" int sk_text_stats(sk_ctx *ctx, uint64_t *pieces, uint64_t *declined, int reset)

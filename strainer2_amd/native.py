@@ -55,7 +55,7 @@ ABI_SYMBOLS = [
     "sk_filter_create", "sk_filter_destroy", "sk_filter_load", "sk_filter_load_counts", "sk_filter_sums",
     "sk_filter_hist", "sk_filter_joint", "sk_filter_above", "skh_scrub_filter_main", "skh_scrub_filter_resident",
     "sk_distinct_count", "sk_first_seen_count", "skh_coverage_depth_main",
-    "sk_batch_create", "sk_batch_destroy", "sk_batch_sync", "sk_batch_fill", "sk_batch_fill_packed", "sk_tally_launch", "sk_tally_collect", "sk_tally_collect_sparse",
+    "sk_batch_create", "sk_batch_destroy", "sk_batch_sync", "sk_batch_fill", "sk_batch_fill_packed", "sk_batch_fill_text", "sk_batch_text_finish", "sk_tally_launch", "sk_tally_collect", "sk_tally_collect_sparse",
     "sk_union_create", "sk_union_destroy", "sk_union_tally_launch", "sk_union_tally_collect", "sk_union_last_error", "sk_union_scan_timing", "sk_union_sync",
     "sk_union_members", "sk_union_rows", "sk_union_count_enable", "sk_union_context", "sk_union_counts_fold",
     "skh_kmer_scrub_count_multi_main",
@@ -180,6 +180,8 @@ lib.sk_batch_destroy.argtypes = [C.c_void_p]
 lib.sk_batch_destroy.restype = None
 lib.sk_batch_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
 lib.sk_batch_fill_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+lib.sk_batch_fill_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+lib.sk_batch_text_finish.argtypes = [C.c_void_p, C.POINTER(TextInfo), C.POINTER(C.POINTER(C.c_uint32))]
 lib.sk_tally_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]
 lib.sk_tally_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
 lib.sk_tally_collect_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
@@ -291,7 +293,8 @@ class KmerContext:
             raise SKError(rc, lib.sk_last_error(self._h).decode())
 
     def set_option(self, name, value):
-        if name == "device_parse":          # the list scan's switch for plain text parsed on the device (sk_text_option)
+        if name == "device_parse":          # plain text parsed on the device (sk_text_option): the list scan's items, and the targets of
+            # strain_detect run on this context (strain_detect_resident: the streams follow the context that owns the device's batches)
             self._ck(lib.sk_text_option(self._h, int(value)))
             return
         self._ck(lib.sk_set_option(self._h, name.encode(), value))
@@ -607,6 +610,26 @@ class TallyBatch:
         self._ctx._ck(lib.sk_batch_sync(self._h))        # (the upload is done: buf may go)
         self.nbytes, self.nrec = len(stream), len(rec_start)
 
+    def fill_text(self, text, is_eof=True, lookahead=b""):
+        """sk_batch_fill_text + sk_batch_text_finish: a piece of plain FASTA/FASTQ text goes up as it is and the device parses it into
+        this batch.  is_eof False: `lookahead` is the one byte that follows the piece in its file.  Returns (TextInfo, rec_start) --
+        the starts of EVERY record of the piece, short and empty ones included; with status DECLINED (or no records) the batch
+        cannot be launched on."""
+        data = np.frombuffer(bytes(text) + (b"" if is_eof else bytes(lookahead)), dtype=np.uint8)
+        buf = self._ctx.pinned_alloc(max(data.size, 16))
+        info = TextInfo()
+        rs = C.POINTER(C.c_uint32)()
+        try:
+            buf[: data.size] = data
+            self._ctx._ck(lib.sk_batch_fill_text(self._h, buf.ctypes.data, data.size, int(bool(is_eof))))
+            self._ctx._ck(lib.sk_batch_text_finish(self._h, C.byref(info), C.byref(rs)))
+        finally:
+            self._ctx.pinned_free(buf)
+        ok = info.status == 0 and info.nrecords > 0
+        starts = np.ctypeslib.as_array(rs, shape=(int(info.nrecords),)).copy() if ok else np.zeros(0, dtype=np.uint32)
+        self.nbytes, self.nrec = (int(info.stream_bytes), int(info.nrecords)) if ok else (0, 0)
+        return info, starts
+
     def close(self):
         if getattr(self, "_h", None):
             lib.sk_batch_destroy(self._h)
@@ -670,9 +693,17 @@ class KmerUnion:
             rc = lib.sk_batch_fill(self._batch, stream, len(stream), rec_start.ctypes.data, nrec)
         if rc:
             raise SKError(rc, lib.sk_last_error(self._members[0]._h).decode())
-        cap = hits_cap if hits_cap is not None else max(len(stream) * 2, 16)
+        return self._tally(self._batch, nrec, len(stream), hits_cap)
+
+    def tally_filled(self, batch, hits_cap=None):
+        """tally_batch for a TallyBatch that is filled already (fill or fill_text) on this union's device"""
+        return self._tally(batch._h, batch.nrec, batch.nbytes, hits_cap)
+
+    def _tally(self, batch_h, nrec, nbytes, hits_cap):
+        n = len(self._members)
+        cap = hits_cap if hits_cap is not None else max(nbytes * 2, 16)
         while True:
-            rc = lib.sk_union_tally_launch(self._h, self._batch, cap)
+            rc = lib.sk_union_tally_launch(self._h, batch_h, cap)
             if rc:
                 raise SKError(rc, lib.sk_union_last_error(self._h).decode())
             recs = np.zeros((nrec * n + 1, 3), dtype=np.uint32)
