@@ -62,6 +62,9 @@ extern "C" {
 #define SK_E_RCCL       -8
 #define SK_E_SPLIT      -9   /* a big text file could not be cut at record boundaries: the run fails rather than count something else */
 #define SK_E_PLAN       -10  /* the ranks of a multi-GPU run computed different work plans for a list: every rank leaves */
+#define SK_E_CACHE      -11  /* a packed input cache file failed its checksum after chunks of it were counted: the run fails.  (Host
+                              * layer only: sk_strerror, which lives with the device layer, has no text of its own for it -- the line on
+                              * `err` that names the file is the explanation; the Python binding supplies one.) */
 
 typedef struct sk_ctx sk_ctx;
 
@@ -160,6 +163,20 @@ int sk_scan_device_packed(sk_ctx *ctx, const void *dev_packed, uint64_t nbytes, 
  * for the whole group. */
 int sk_scan_pinned_many(sk_ctx *const *ctx, uint32_t n, const uint8_t *pinned, uint64_t nbytes, uint32_t col, uint64_t *ticket);
 int sk_scan_pinned_packed_many(sk_ctx *const *ctx, uint32_t n, const void *packed, uint64_t nbytes, uint32_t col, uint64_t *ticket);
+/* The same pack made ON THE DEVICE (new; sk_packdev.hip -- the list scan's packed input cache keeps a chunk that went up as bytes in
+ * its packed form without spending a decode thread on it; the reference has no counterpart: it moves bytes through memory only,
+ * src/kseq.h:90-141).  sk_pack_device: dev_stream[0..nbytes) (16-byte aligned) into dev_packed (8-byte aligned, sk_packed_bytes(nbytes)
+ * bytes), byte for byte what sk_pack_stream writes, *odd as there; nothing at or beyond nbytes is read.  Synchronous.
+ * sk_scan_pinned_pack_many: ONE upload of `pinned` (sk_pinned_alloc, at most 64 MiB - 64 bytes), n COUNT scans as sk_scan_pinned_many
+ * does (counts equal it bit for bit), and the pack of the same device bytes; on return `pinned` has been read, and the packed form and
+ * the flag (one u32, non-zero = odd) are in pinned_packed_out / pinned_odd_out (page-locked) once sk_pack_ticket_wait(ctx[0], *ticket)
+ * has returned -- a ticket of this entry's own, not one for sk_ticket_wait.  Buffers and errors are ctx[0]'s; one caller at a time for
+ * the whole group.  sk_pack_release frees a context's buffers (before sk_ctx_destroy). */
+int sk_pack_device(sk_ctx *ctx, const void *dev_stream, uint64_t nbytes, void *dev_packed, int *odd);
+int sk_scan_pinned_pack_many(sk_ctx *const *ctx, uint32_t n, const uint8_t *pinned, uint64_t nbytes, uint32_t col,
+                             void *pinned_packed_out, uint32_t *pinned_odd_out, uint64_t *ticket);
+int sk_pack_ticket_wait(sk_ctx *ctx, uint64_t ticket);
+void sk_pack_release(sk_ctx *ctx);
 /* Free and total HBM of the context's device (hipMemGetInfo). */
 int sk_device_memory(sk_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 
@@ -444,6 +461,24 @@ int skh_scan_list_uncut(sk_ctx *ctx, const char *list_path, const char *skip, ui
  * skh_scan_list. */
 int skh_scan_list_many(sk_ctx *const *ctx, uint32_t n, const char *list_path, const char *skip, uint32_t col,
                        FILE *progress, FILE *err, uint32_t rank, uint32_t world, uint64_t *bases);
+/* The list scan's packed input cache (new, opt-in; the reference decodes every list item in every run, src/genome_compare.c:179-236).
+ * With a directory set, skh_scan_file and skh_scan_list[_uncut|_many] keep for every list item what its decode handed to the device
+ * -- the chunks of the record stream in sk_pack_stream's form, DIR/<basename>.<hash of the realpath>.skp (strainer2_amd/csrc/
+ * sk_pcache.h has the format) -- and a later run whose item has the same size and mtime reads that file instead of inflating, parsing
+ * and packing the source.  Every byte a run prints is the same with the cache off, filled or served.  mode "rw" (default, NULL) writes
+ * what is missing or stale, "ro" only reads.  An empty dir switches it off for ctx; dir and mode both NULL make ctx follow the
+ * process-wide default again (and forget its counters: call it before sk_ctx_destroy, as the programs do -- settings and counters are
+ * kept by the context's address); ctx NULL sets that default, which is SK_PACK_CACHE / SK_PACK_CACHE_MODE until somebody sets it and
+ * again after skh_pack_cache_set(NULL, NULL, NULL) (kmer_scrub_count --pack-cache DIR sets it for the length of that call).  A
+ * source that is missing, or that this process cannot open for reading, is scanned -- and fails -- exactly as without the cache,
+ * whatever the directory holds for it.  Not cached (and counted so):
+ * items the plan cuts into byte ranges, items the device text parser takes, any run with world > 1 (the option is ignored there).
+ * A directory that cannot be used gives one warning on `err` and the scan goes on uncached; a cache file whose payload fails its
+ * checksum fails the run (SK_E_CACHE, the file named on `err`): chunks before it were counted already.
+ * skh_pack_cache_stats: list items since the last reset that were served from the cache, written to it, found stale (or cut short,
+ * or of another version), and scanned without being cached; each may be NULL. */
+int skh_pack_cache_set(sk_ctx *ctx, const char *dir, const char *mode);
+int skh_pack_cache_stats(sk_ctx *ctx, uint64_t *served, uint64_t *written, uint64_t *stale, uint64_t *not_cached, int reset);
 /* Hash of the work plan skh_scan_list(list, skip, .., world) follows (items, byte ranges, file sizes, owners): a function
  * of the list, the files and `world` (and of SK_SPLIT_BYTES / SK_NO_SPLIT) only, never of a rank's thread count.  With the
  * library's own communicator skh_scan_list compares it across ranks itself (SK_E_PLAN); a caller that reduces the counters

@@ -33,6 +33,7 @@
 
 #include "sk_parser.h"
 #include "sk_pack.h"
+#include "sk_pcache.h"
 #include "sk_ctxjob.h"
 #include "sk_gzpipe.h"
 #include "sk_cpus.h"
@@ -938,6 +939,117 @@ static int text_scan(sk_ctx *const *ctxs, uint32_t nctx, pthread_mutex_t *mu, co
     return rc;
 }
 
+/* ---- the packed input cache (opt-in; sk_pcache.h has the file format, its writer and its reader) -----------------------------
+ * Who wants it: a context that was told (skh_pack_cache_set), else the process-wide default (the programs' --pack-cache), else
+ * SK_PACK_CACHE / SK_PACK_CACHE_MODE.  The contexts' settings and counters live here, by address: the context itself belongs to the
+ * device layer, which this path leaves untouched. */
+typedef struct { const sk_ctx *ctx; char *dir; int mode, set; uint64_t served, written, stale, not_cached; } pc_conf;
+static pthread_mutex_t pc_mu = PTHREAD_MUTEX_INITIALIZER;
+static pc_conf *pc_confs, pc_default;
+static uint32_t pc_n, pc_cap;
+static int pc_warned;
+
+static pc_conf *pc_find(const sk_ctx *ctx, int create)          /* (under pc_mu) */
+{
+    uint32_t i;
+    for (i = 0; i < pc_n; i++) if (pc_confs[i].ctx == ctx) return &pc_confs[i];
+    if (!create) return NULL;
+    if (pc_n == pc_cap) {
+        pc_conf *nc = (pc_conf *)realloc(pc_confs, (size_t)(pc_cap ? pc_cap * 2 : 16) * sizeof *nc);
+        if (!nc) return NULL;
+        pc_confs = nc; pc_cap = pc_cap ? pc_cap * 2 : 16;
+    }
+    memset(&pc_confs[pc_n], 0, sizeof pc_confs[pc_n]);
+    pc_confs[pc_n].ctx = ctx;
+    return &pc_confs[pc_n++];
+}
+
+int skh_pack_cache_set(sk_ctx *ctx, const char *dir, const char *mode)
+{
+    pc_conf *c;
+    int m = SKPC_RW, rc = SK_OK;
+    if (mode && !strcmp(mode, "ro")) m = SKPC_RO;
+    else if (mode && strcmp(mode, "rw") != 0) return SK_E_ARG;
+    pthread_mutex_lock(&pc_mu);
+    if (!dir && !mode) {                                 /* forget the context: its setting and its counters (NULL: the default) */
+        if (!ctx) { free(pc_default.dir); memset(&pc_default, 0, sizeof pc_default); }
+        else if ((c = pc_find(ctx, 0)) != NULL) { free(c->dir); *c = pc_confs[--pc_n]; }
+    } else if ((c = ctx ? pc_find(ctx, 1) : &pc_default) == NULL) rc = SK_E_NOMEM;
+    else {
+        char *d = dir && dir[0] ? strdup(dir) : NULL;
+        if (dir && dir[0] && !d) rc = SK_E_NOMEM;
+        else { free(c->dir); c->dir = d; c->mode = m; c->set = 1; }
+    }
+    pthread_mutex_unlock(&pc_mu);
+    return rc;
+}
+
+int skh_pack_cache_stats(sk_ctx *ctx, uint64_t *served, uint64_t *written, uint64_t *stale, uint64_t *not_cached, int reset)
+{
+    pc_conf *c;
+    if (!ctx) return SK_E_ARG;
+    pthread_mutex_lock(&pc_mu);
+    c = pc_find(ctx, 0);
+    if (served) *served = c ? c->served : 0;
+    if (written) *written = c ? c->written : 0;
+    if (stale) *stale = c ? c->stale : 0;
+    if (not_cached) *not_cached = c ? c->not_cached : 0;
+    if (c && reset) c->served = c->written = c->stale = c->not_cached = 0;
+    pthread_mutex_unlock(&pc_mu);
+    return SK_OK;
+}
+
+/* the directory that holds for ctx (malloc'd) and its mode, or NULL: no cache */
+static char *pc_effective(const sk_ctx *ctx, int *mode)
+{
+    const pc_conf *c;
+    char *dir = NULL;
+    pthread_mutex_lock(&pc_mu);
+    c = pc_find(ctx, 0);
+    if (!c || !c->set) c = pc_default.set ? &pc_default : NULL;
+    if (c) { dir = c->dir ? strdup(c->dir) : NULL; *mode = c->mode; }
+    pthread_mutex_unlock(&pc_mu);
+    if (!c) {
+        const char *e = getenv("SK_PACK_CACHE"), *m = getenv("SK_PACK_CACHE_MODE");
+        dir = e && e[0] ? strdup(e) : NULL;
+        *mode = m && !strcmp(m, "ro") ? SKPC_RO : SKPC_RW;
+    }
+    return dir;
+}
+
+static void pc_count(const sk_ctx *ctx, uint64_t served, uint64_t written, uint64_t stale, uint64_t not_cached)
+{
+    pc_conf *c;
+    pthread_mutex_lock(&pc_mu);
+    if ((c = pc_find(ctx, 1)) != NULL) { c->served += served; c->written += written; c->stale += stale; c->not_cached += not_cached; }
+    pthread_mutex_unlock(&pc_mu);
+}
+
+/* can the directory be used?  "rw" makes it when only its last component is missing.  One warning per process when it cannot. */
+static int pc_dir_usable(const char *dir, int mode, FILE *err)
+{
+    struct stat st;
+    int ok;
+    if (mode == SKPC_RW && stat(dir, &st) != 0 && errno == ENOENT) (void)mkdir(dir, 0777);
+    ok = stat(dir, &st) == 0 && (S_ISDIR(st.st_mode) || (errno = ENOTDIR, 0)) && access(dir, mode == SKPC_RW ? R_OK | W_OK | X_OK : R_OK | X_OK) == 0;
+    if (!ok && !__atomic_exchange_n(&pc_warned, 1, __ATOMIC_RELAXED))
+        fprintf(err ? err : stderr, "libstrainer_kmer: the pack cache directory %s cannot be used (%s): scanning without it\n", dir, strerror(errno));
+    return ok;
+}
+
+/* Can the source be opened for reading, as the parser would open it?  A cache file never stands in for a source this process may not
+ * read (mode 000, an ACL, a root-squashed mount): such an item takes the old path and fails where it failed before.  *st: the open
+ * file's own stat. */
+static int pc_source_readable(const char *path, struct stat *st)
+{
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    int ok;
+    if (fd < 0) return 0;
+    ok = fstat(fd, st) == 0 && S_ISREG(st->st_mode);
+    close(fd);
+    return ok;
+}
+
 typedef struct { sk_ctx *ctx; uint32_t col; } scan_sink;
 
 static int scan_sink_fn(void *user, const uint8_t *chunk, uint64_t nbytes)
@@ -946,11 +1058,22 @@ static int scan_sink_fn(void *user, const uint8_t *chunk, uint64_t nbytes)
     return sk_scan_stream(s->ctx, chunk, nbytes, s->col);
 }
 
+static int scan_file_cached(sk_ctx *ctx, const char *path, uint32_t col, uint64_t *bases, const char *dir, int mode, int *handled);
+
 int skh_scan_file(sk_ctx *ctx, const char *path, uint32_t col, uint64_t *bases)
 {
     scan_sink s;
     int64_t rc;
     s.ctx = ctx; s.col = col;
+    if (ctx && path) {                                   /* the packed input cache (opt-in): the file served from it, or written to it */
+        int mode = SKPC_RW, handled = 0;
+        char *dir = pc_effective(ctx, &mode);
+        if (dir) {
+            const int crc = scan_file_cached(ctx, path, col, bases, dir, mode, &handled);
+            free(dir);
+            if (handled) return crc;
+        }
+    }
     if (ctx && text_wanted(ctx, getenv("SK_TIMING") != NULL)) {
         uint64_t resume = TEXT_WHOLE, b = 0, tcap = 0;
         uint8_t *tbuf = NULL;
@@ -989,7 +1112,15 @@ int skh_scan_file(sk_ctx *ctx, const char *path, uint32_t col, uint64_t *bases)
  * rank the decode threads take them from a queue.  The counters are sums (src/genome_compare.c:220-223), so neither
  * the dealing nor the cutting changes a count -- provided every piece really starts at a record boundary, which is
  * CHECKED, not assumed (parse_range). */
-typedef struct { char *path; uint64_t a, b, size; uint32_t line; int ranged; } scan_item;
+typedef struct {
+    char *path; uint64_t a, b, size; uint32_t line; int ranged;
+    /* the packed input cache: 0 not for this item, PC_SERVE a valid cache file was found when the list was planned, PC_FILL one is to
+     * be written; cpath: the cache file; reg/mtime: the source is a regular file, its mtime in nanoseconds (with size: what the
+     * cache file's header is compared with) */
+    int cache, reg; char *cpath; int64_t mtime;
+} scan_item;
+#define PC_SERVE 1
+#define PC_FILL  2
 
 /* one line of the list as the reference reports it: "<line>\t<time>" in the progress file just before the file is opened
  * (src/genome_compare.c:133-136,167-170), "skipping ..." on stderr for the -C line that equals -r (:138-141) */
@@ -1020,6 +1151,11 @@ typedef struct {
                                         * itself bound by the link; 0 = never; 2 = always, .gz items' too (tests) */
     int             link_bound;        /* a decode thread has spent a tenth of its time waiting for uploads (atomic) */
     int             text;              /* whole plain-text items go up as text and are parsed on the device (option "device_parse", SK_DEVICE_PARSE=1) */
+    FILE           *err;               /* where a damaged cache file is named */
+    uint64_t        pc_served, pc_written, pc_stale, pc_not;       /* the packed input cache: items (under queue_mu) ... */
+    double          pc_t_sum, pc_t_read, pc_t_write;               /* ... seconds summed over the threads: checksums, reading, writing */
+    uint64_t        pc_bytes;                                      /* ... cache bytes read or written */
+    int             pc_rw;                                         /* ... the directory may be written */
 } scan_pool;
 
 /* The progress file gets a list line when a decode thread TAKES the line's (first) item, and every line before it that is
@@ -1051,6 +1187,14 @@ typedef struct {
     int        pk_used[2], pk_cur;
     double     t_begin, t_wait_all;    /* since this worker began: time spent waiting for its buffers' uploads */
     uint8_t   *tbuf; uint64_t tcap;    /* device_parse: the page-locked buffer its items' text is read into */
+    /* the packed input cache: the file this worker's chunks are written to (NULL: none; the helpers of a split .gz item share their
+     * item's), the item that wants one once the host parser takes it, and the chunk whose packed form the device is still sending home */
+    skpc_writer *fill; const scan_item *fill_item;
+    int        pk_kind[2];             /* pk_ticket[i] is sk_scan_pinned_pack_many's (1) or the context's (0) */
+    uint32_t  *pkodd;                  /* page-locked: the device pack's odd flags, one per pk buffer */
+    uint8_t   *fill_tmp;               /* the host's pack of a chunk that went up as bytes (builds without the device pack) */
+    int        pend, pend_i; const uint8_t *pend_chunk; uint64_t pend_n;
+    double     t_pc_sum, t_pc_read; uint64_t pc_bytes;
 } scan_worker;
 
 /* size of a worker's chunk buffer: SK_CHUNK_BYTES (4096 .. 63 MiB; tests use small ones: many flushes per file), default 32 MiB */
@@ -1066,6 +1210,11 @@ static uint64_t pool_chunk_bytes(void)
  * always there (sk_device.hip), and a walk into several contexts is refused without them (skh_scan_list_many). */
 #pragma weak sk_scan_pinned_many
 #pragma weak sk_scan_pinned_packed_many
+/* ... nor the device-side pack (sk_packdev.hip): without it a chunk that went up as bytes is packed for the cache file by
+ * sk_pack_stream on the decode thread */
+#pragma weak sk_scan_pinned_pack_many
+#pragma weak sk_pack_ticket_wait
+#pragma weak sk_pack_release
 
 /* a chunk to every context of the walk, under submit_mu: with several, it goes up once and is scanned into each of them */
 static int pool_submit(scan_pool *p, const void *buf, uint64_t nbytes, int packed, uint64_t *ticket)
@@ -1076,12 +1225,35 @@ static int pool_submit(scan_pool *p, const void *buf, uint64_t nbytes, int packe
     return packed ? sk_scan_pinned_packed(p->ctx, buf, nbytes, p->col, ticket) : sk_scan_pinned(p->ctx, (const uint8_t *)buf, nbytes, p->col, ticket);
 }
 
+/* a pk buffer is free again once the transfer that used it last is over: the upload of a packed chunk, or the device pack's copy home */
+static int worker_pk_wait(scan_worker *w, int i)
+{
+    int rc = SK_OK;
+    if (w->pk_used[i]) rc = w->pk_kind[i] ? sk_pack_ticket_wait(w->pool->ctx, w->pk_ticket[i]) : sk_ticket_wait(w->pool->ctx, w->pk_ticket[i]);
+    w->pk_used[i] = 0;
+    return rc;
+}
+
+/* the chunk before this one went through the device pack: its packed form (or, odd, its bytes -- the writer has not been given that
+ * buffer again) goes into the cache file now */
+static int worker_fill_flush(scan_worker *w)
+{
+    int rc;
+    if (!w->pend) return SK_OK;
+    w->pend = 0;
+    if ((rc = worker_pk_wait(w, w->pend_i)) != SK_OK) return rc;
+    if (w->pkodd[w->pend_i]) skpc_append(w->fill, SKPC_BYTES, w->pend_n, w->pend_chunk);
+    else skpc_append(w->fill, SKPC_PACKED, w->pend_n, w->pk[w->pend_i]);
+    return SK_OK;
+}
+
 static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
 {
     scan_worker *w = (scan_worker *)user;
-    int rc;
+    int rc, known_odd = 0;
     double t0 = w->pool->timing ? now_s() : 0.0;
     double t1;
+    if (w->fill && (rc = worker_fill_flush(w)) != SK_OK) return rc;
     if (w->pool->pack > 1 || (w->pool->pack && tl_plain_text && __atomic_load_n(&w->pool->link_bound, __ATOMIC_RELAXED))) {
         /* The chunk goes up PACKED: what the scan kernel's first phase would make of its bytes is made here (sk_pack.h), 6 bytes per
          * 16 bases over the link instead of 16 -- the list scan of plain text was bound by the link, not by these threads.  A chunk
@@ -1090,9 +1262,10 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
         if (!w->pk[i] && sk_pinned_alloc(w->pool->ctx, (void **)&w->pk[i], sk_packed_bytes(POOL_CHUNK)) != SK_OK) w->pk[i] = NULL;
         if (w->pk[i]) {
             int odd = 0;
-            if (w->pk_used[i]) { sk_ticket_wait(w->pool->ctx, w->pk_ticket[i]); w->pk_used[i] = 0; }
+            worker_pk_wait(w, i);
             if (w->pool->timing) { t1 = now_s(); w->t_ticket += t1 - t0; t0 = t1; }
             sk_pack_stream(chunk, nbytes, w->pk[i], &odd);
+            known_odd = odd;
             if (w->pool->timing) { t1 = now_s(); w->t_pack += t1 - t0; t0 = t1; }
             if (!odd) {
                 pthread_mutex_lock(&w->pool->submit_mu);
@@ -1101,9 +1274,32 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
                 pthread_mutex_unlock(&w->pool->submit_mu);
                 if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; w->npacked++; }
                 w->pk_used[i] = rc == SK_OK;
+                w->pk_kind[i] = 0;
                 w->used[w->cur] = 0;                    /* (the bytes were read by this thread alone: their buffer is free at once) */
+                if (w->fill && rc == SK_OK) skpc_append(w->fill, SKPC_PACKED, nbytes, w->pk[i]);     /* (it lies packed in page-locked memory: written out) */
                 return rc;
             }
+        }
+    }
+    if (w->fill && !known_odd && sk_scan_pinned_pack_many && sk_pack_ticket_wait) {
+        /* A chunk that goes up as bytes, for a cache file: the device packs it beside its scan (sk_packdev.hip) -- a .gz item's decode
+         * thread has no cycles for that -- and sends the packed form home; it is written when the next chunk comes (worker_fill_flush). */
+        const int i = w->pk_cur ^= 1;
+        if (!w->pk[i] && sk_pinned_alloc(w->pool->ctx, (void **)&w->pk[i], sk_packed_bytes(POOL_CHUNK)) != SK_OK) w->pk[i] = NULL;
+        if (!w->pkodd && sk_pinned_alloc(w->pool->ctx, (void **)&w->pkodd, 4096) != SK_OK) w->pkodd = NULL;
+        if (w->pk[i] && w->pkodd) {
+            if ((rc = worker_pk_wait(w, i)) != SK_OK) return rc;
+            if (w->pool->timing) { t1 = now_s(); w->t_ticket += t1 - t0; t0 = t1; }
+            pthread_mutex_lock(&w->pool->submit_mu);
+            t1 = w->pool->timing ? now_s() : 0.0;
+            rc = sk_scan_pinned_pack_many(w->pool->ctxs, w->pool->nctx, chunk, nbytes, w->pool->col, w->pk[i], &w->pkodd[i], &w->pk_ticket[i]);
+            pthread_mutex_unlock(&w->pool->submit_mu);
+            if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; }
+            w->pk_used[i] = rc == SK_OK;
+            w->pk_kind[i] = 1;
+            w->used[w->cur] = 0;                        /* (on return the bytes have been read) */
+            if (rc == SK_OK) { w->pend = 1; w->pend_i = i; w->pend_chunk = chunk; w->pend_n = nbytes; }
+            return rc;
         }
     }
     pthread_mutex_lock(&w->pool->submit_mu);
@@ -1112,6 +1308,13 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
     pthread_mutex_unlock(&w->pool->submit_mu);
     if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; }
     w->used[w->cur] = 1;
+    if (w->fill && rc == SK_OK) {
+        int odd = known_odd;
+        if (!odd && !w->fill_tmp) w->fill_tmp = (uint8_t *)malloc((size_t)sk_packed_bytes(POOL_CHUNK) + 8u);
+        if (!odd && w->fill_tmp) sk_pack_stream(chunk, nbytes, w->fill_tmp, &odd);
+        if (odd || !w->fill_tmp) skpc_append(w->fill, SKPC_BYTES, nbytes, chunk);
+        else skpc_append(w->fill, SKPC_PACKED, nbytes, w->fill_tmp);
+    }
     return rc;
 }
 
@@ -1153,6 +1356,8 @@ static int worker_init(scan_worker *w, scan_pool *p)
 
 static void worker_done(scan_worker *w)
 {
+    int i;
+    for (i = 0; i < 2; i++) if (w->pk_used[i] && w->pk_kind[i]) worker_pk_wait(w, i);     /* (a device pack still on its way home after a failure) */
 #ifdef SK_EXPERIMENTS
     if (w->inf) sk_inflater_destroy(w->inf);
 #endif
@@ -1163,7 +1368,9 @@ static void worker_done(scan_worker *w)
     if (w->pk[0]) sk_pinned_free(w->pool->ctx, w->pk[0]);
     if (w->pk[1]) sk_pinned_free(w->pool->ctx, w->pk[1]);
     if (w->tbuf) sk_pinned_free(w->pool->ctx, w->tbuf);
+    if (w->pkodd) sk_pinned_free(w->pool->ctx, w->pkodd);
     pthread_mutex_unlock(&w->pool->submit_mu);
+    free(w->fill_tmp);
 }
 
 /* One piece [a, b) of a plain-text file: the records that START in it.  The piece's own start s(a) and end s(b) come from
@@ -1258,6 +1465,7 @@ typedef struct {
     gz_seg *head, *tail;
     int nq, done, stop, rc;
     uint64_t bases; int64_t nrec;
+    skpc_writer *fill;                 /* the item's cache file being written (or NULL): every helper's chunks go there */
 } gz_split;
 
 static void *gz_split_worker(void *arg)
@@ -1265,6 +1473,7 @@ static void *gz_split_worker(void *arg)
     gz_split *g = (gz_split *)arg;
     scan_worker w;
     worker_init(&w, g->pool);
+    w.fill = g->fill;
     for (;;) {
         gz_seg *sg;
         int stop;
@@ -1292,6 +1501,7 @@ static void *gz_split_worker(void *arg)
             }
             if (ps.state != P_STOP) parser_eof(&ps);
             writer_flush(&sw);
+            if (w.fill && !sw.rc) sw.rc = worker_fill_flush(&w);
             pthread_mutex_lock(&g->mu);
             g->bases += sw.bases;
             g->nrec += ps.nrecords;
@@ -1338,6 +1548,7 @@ static int64_t parse_gz_split(scan_worker *w, const scan_item *it, uint64_t *bas
     if (skzp_open_threads(&zp, it->path, w->pool->pipe) != SKZ_OK) return -100;
     memset(&g, 0, sizeof g);
     g.pool = w->pool;
+    g.fill = w->fill;
     pthread_mutex_init(&g.mu, NULL);
     pthread_cond_init(&g.cv, NULL);
     for (i = 0; i < npar; i++) if (pthread_create(&th[nth], NULL, gz_split_worker, &g) == 0) nth++;
@@ -1456,8 +1667,19 @@ static int64_t parse_gz_on_device(scan_worker *w, const scan_item *it, uint64_t 
 
 #endif
 
+/* the item's cache file is begun: from here on worker_sink writes every chunk to it as well */
+static void worker_fill_begin(scan_worker *w, const scan_item *it)
+{
+    struct stat src;
+    memset(&src, 0, sizeof src);
+    src.st_size = (off_t)it->size;
+    src.st_mtim.tv_sec = (time_t)(it->mtime / 1000000000ll);
+    src.st_mtim.tv_nsec = (long)(it->mtime % 1000000000ll);
+    w->fill = skpc_begin(it->cpath, &src, POOL_CHUNK);
+}
+
 /* decode one item into the worker's pinned buffers; returns records or a negative SK_E_* */
-static int64_t worker_item(scan_worker *w, const scan_item *it, uint64_t *bases)
+static int64_t worker_item_parse(scan_worker *w, const scan_item *it, uint64_t *bases)
 {
     stream_writer sw;
     int64_t nrec = 0;
@@ -1483,6 +1705,7 @@ static int64_t worker_item(scan_worker *w, const scan_item *it, uint64_t *bases)
             return sw.rc ? (int64_t)sw.rc : nrec;
         }
     }
+    if (w->fill_item == it) worker_fill_begin(w, it);       /* (the host parser has the whole item) */
     if (!it->ranged && w->pool->pipe > 1 && !getenv("SK_NO_SPLIT") && !getenv("SK_ZLIB")) {
         const int64_t r = parse_gz_split(w, it, bases);
         if (r != -100) return r;
@@ -1499,6 +1722,151 @@ static int64_t worker_item(scan_worker *w, const scan_item *it, uint64_t *bases)
     if (rc != SK_OK) return rc;
     if (sw.rc) return sw.rc;
     return nrec;
+}
+
+/* A cached item: every segment of its file read into this worker's page-locked buffers and submitted as the chunk it was when a decode
+ * thread first made it; the stored bases and records are the item's.  -100: the source or the file changed since the list was planned
+ * and nothing was counted yet -- the caller parses the source as if there were no cache.  A segment that fails its checksum may come
+ * after others were counted: the run fails (SK_E_CACHE) and says which file. */
+static int64_t worker_serve(scan_worker *w, const scan_item *it, uint64_t *bases)
+{
+    scan_pool *const p = w->pool;
+    skpc_reader rd;
+    skpc_seg sg;
+    struct stat st;
+    int r, rc = SK_OK;
+    const char *why = NULL;
+    if (!pc_source_readable(it->path, &st) || skpc_open(&rd, it->cpath, &st, POOL_CHUNK) != SKPC_OK) return -100;
+    while (rc == SK_OK && (r = skpc_next(&rd, &sg)) == SKPC_OK) {
+        const double t0 = p->timing ? now_s() : 0.0;
+        double t1, tsum = 0.0;
+        if (sg.kind == SKPC_PACKED) {
+            const int i = w->pk_cur ^= 1;
+            if (!w->pk[i] && sk_pinned_alloc(p->ctx, (void **)&w->pk[i], sk_packed_bytes(POOL_CHUNK)) != SK_OK) { w->pk[i] = NULL; rc = SK_E_NOMEM; break; }
+            if ((rc = worker_pk_wait(w, i)) != SK_OK) break;
+            t1 = p->timing ? now_s() : 0.0;
+            if ((r = skpc_payload(&rd, &sg, w->pk[i], p->timing ? &tsum : NULL)) != SKPC_OK) break;
+            w->pc_bytes += sg.payload_len;
+            if (p->timing) { w->t_pc_read += now_s() - t1 - tsum; w->t_pc_sum += tsum; w->t_ticket += t1 - t0; t1 = now_s(); }
+            pthread_mutex_lock(&p->submit_mu);
+            {
+                const double t2 = p->timing ? now_s() : 0.0;
+                rc = pool_submit(p, w->pk[i], sg.stream_len, 1, &w->pk_ticket[i]);
+                pthread_mutex_unlock(&p->submit_mu);
+                if (p->timing) { w->t_submit_wait += t2 - t1; w->t_submit += now_s() - t2; w->nchunks++; w->npacked++; }
+            }
+            w->pk_used[i] = rc == SK_OK;
+            w->pk_kind[i] = 0;
+        } else {
+            uint8_t *buf = worker_next_buf(w);
+            if (!buf) { rc = SK_E_NOMEM; break; }
+            t1 = p->timing ? now_s() : 0.0;
+            if ((r = skpc_payload(&rd, &sg, buf, p->timing ? &tsum : NULL)) != SKPC_OK) break;
+            w->pc_bytes += sg.payload_len;
+            if (p->timing) { w->t_pc_read += now_s() - t1 - tsum; w->t_pc_sum += tsum; t1 = now_s(); }
+            pthread_mutex_lock(&p->submit_mu);
+            {
+                const double t2 = p->timing ? now_s() : 0.0;
+                rc = pool_submit(p, buf, sg.stream_len, 0, &w->ticket[w->cur]);
+                pthread_mutex_unlock(&p->submit_mu);
+                if (p->timing) { w->t_submit_wait += t2 - t1; w->t_submit += now_s() - t2; w->nchunks++; }
+            }
+            w->used[w->cur] = rc == SK_OK;
+        }
+    }
+    if (rc == SK_OK && r != SKPC_MISS) why = r == SKPC_IO ? "it cannot be read" : "a segment does not match its checksum";
+    if (why) {
+        fprintf(p->err ? p->err : stderr, "libstrainer_kmer: the pack cache file %s is damaged (%s) and part of it may have been counted: "
+                                          "nothing is reported; remove the file and run again\n", it->cpath, why);
+        rc = SK_E_CACHE;
+    }
+    if (rc == SK_OK) *bases += rd.h.bases;
+    r = rc == SK_OK;
+    {
+        const int64_t nrec = (int64_t)rd.h.records;
+        skpc_close(&rd);
+        return r ? nrec : (int64_t)rc;
+    }
+}
+
+/* one item: served from its cache file, or parsed -- and then, where the plan says so, written to one */
+static int64_t worker_item(scan_worker *w, const scan_item *it, uint64_t *bases)
+{
+    scan_pool *const p = w->pool;
+    uint64_t served = 0, written = 0, stale = 0, not_cached = 0;
+    const uint64_t b0 = *bases;
+    double tsum = 0.0, twrite = 0.0;
+    int64_t r = -100;
+    if (it->cache == PC_SERVE && (r = worker_serve(w, it, bases)) != -100) served = r >= 0;
+    else {
+        if (it->cache == PC_SERVE) stale = 1;              /* (changed since the plan: parsed, and in rw mode written anew) */
+        w->fill_item = it->cache == PC_FILL || (it->cache == PC_SERVE && p->pc_rw) ? it : NULL;
+        r = worker_item_parse(w, it, bases);
+        w->fill_item = NULL;
+        if (w->fill) {
+            const int frc = worker_fill_flush(w);
+            tsum = w->fill->t_sum; twrite = w->fill->t_write;
+            w->pc_bytes += w->fill->h.payload_bytes;
+            written = (uint64_t)skpc_end(w->fill, r >= 0 && frc == SK_OK, r >= 0 ? (uint64_t)r : 0, *bases - b0);
+            w->fill = NULL;
+            w->pend = 0;
+            if (r >= 0 && frc != SK_OK) r = frc;
+            not_cached = !written && r >= 0;
+        } else if (it->cache && r >= 0) not_cached = 1;     /* (the device text parser took it, ro mode, or the file could not be begun) */
+    }
+    if (it->cache) {
+        pthread_mutex_lock(&p->queue_mu);
+        p->pc_served += served; p->pc_written += written; p->pc_stale += stale; p->pc_not += not_cached;
+        p->pc_t_sum += tsum + w->t_pc_sum; p->pc_t_read += w->t_pc_read; p->pc_t_write += twrite; p->pc_bytes += w->pc_bytes;
+        pthread_mutex_unlock(&p->queue_mu);
+        w->t_pc_sum = w->t_pc_read = 0.0; w->pc_bytes = 0;
+    }
+    return r;
+}
+
+/* skh_scan_file with the cache on: the file as a list of one item (the list walk's worker serves or fills it).  *handled = 0: not a
+ * regular file, no usable directory, nothing to serve and nothing to write -- the caller scans it as before. */
+static int scan_file_cached(sk_ctx *ctx, const char *path, uint32_t col, uint64_t *bases, const char *dir, int mode, int *handled)
+{
+    scan_pool pool;
+    scan_worker w;
+    scan_item it;
+    skpc_reader rd;
+    struct stat st;
+    sk_ctx *one = ctx;
+    uint64_t b = 0, stale = 0;
+    int64_t r;
+    int o;
+    const char *e = getenv("SK_LIST_PACK");
+    *handled = 0;
+    if (!pc_source_readable(path, &st) || !pc_dir_usable(dir, mode, stderr)) return SK_OK;     /* (missing, unreadable: as without the cache) */
+    memset(&it, 0, sizeof it);
+    if (!(it.cpath = skpc_path(dir, path))) return SK_OK;
+    o = skpc_open(&rd, it.cpath, &st, POOL_CHUNK);
+    if (o == SKPC_OK) { skpc_close(&rd); it.cache = PC_SERVE; }
+    else {
+        stale = o == SKPC_INVALID;
+        if (mode == SKPC_RW && !text_wanted(ctx, 0)) it.cache = PC_FILL;
+    }
+    if (!it.cache) { pc_count(ctx, 0, 0, stale, 1); free(it.cpath); return SK_OK; }
+    it.path = (char *)(uintptr_t)path; it.size = (uint64_t)st.st_size; it.mtime = skpc_mtime_ns(&st); it.reg = 1;
+    memset(&pool, 0, sizeof pool);
+    pool.ctx = ctx; pool.ctxs = &one; pool.nctx = 1; pool.col = col;
+    pool.pack = e && e[0] == '0' ? 0 : e && e[0] == '2' ? 2 : 1;
+    pool.err = stderr;
+    pool.pc_rw = mode == SKPC_RW;
+    pthread_mutex_init(&pool.submit_mu, NULL);
+    pthread_mutex_init(&pool.queue_mu, NULL);
+    worker_init(&w, &pool);
+    r = worker_item(&w, &it, &b);
+    worker_done(&w);
+    pc_count(ctx, pool.pc_served, pool.pc_written, pool.pc_stale + stale, pool.pc_not);
+    pthread_mutex_destroy(&pool.submit_mu);
+    pthread_mutex_destroy(&pool.queue_mu);
+    free(it.cpath);
+    if (bases) *bases += b;
+    *handled = 1;
+    return r < 0 ? (int)r : SK_OK;
 }
 
 static void *pool_worker(void *arg)
@@ -1638,6 +2006,8 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
     uint64_t local_fail = 0;
     uint32_t open_line = UINT32_MAX;            /* the first list line whose file some rank could not open */
     int any_ranged = 0, coordinated, by_other = 0;
+    char *pc_dir = NULL;                        /* the packed input cache's directory for this scan (NULL: none) */
+    int pc_mode = SKPC_RW, pc_asked = 0;
     if (world == 0) world = 1;
     /* several ranks act together only when all of them are in the library's communicator */
     coordinated = world <= 1 || (ctx && (uint32_t)sk_comm_world(ctx) == world);
@@ -1654,6 +2024,7 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
     pool.ctxs = ctxs;
     pool.nctx = ctxs ? nctx : 0;
     pool.col = col;
+    pool.err = err;
     pool.text = ctx && !plan_only ? text_wanted(ctx, pool.timing) : (getenv("SK_DEVICE_PARSE") && getenv("SK_DEVICE_PARSE")[0] == '1' && sk_scan_text_pinned_many != NULL);
     pthread_mutex_init(&pool.submit_mu, NULL);
     pthread_mutex_init(&pool.queue_mu, NULL);
@@ -1677,13 +2048,45 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
         memset(&all[nall], 0, sizeof all[nall]);
         all[nall].path = strdup(line);
         all[nall].line = nline++;
-        all[nall].size = stat(line, &st) == 0 && S_ISREG(st.st_mode) ? (uint64_t)st.st_size : 0;
+        all[nall].reg = stat(line, &st) == 0 && S_ISREG(st.st_mode);
+        all[nall].size = all[nall].reg ? (uint64_t)st.st_size : 0;
+        all[nall].mtime = all[nall].reg ? skpc_mtime_ns(&st) : 0;
         nall++;
     }
     free(line);
     if (fp) fclose(fp);
     pool.nll = nline;
     pool.progress = rank == 0 ? progress : NULL;
+
+    /* The packed input cache (opt-in).  Which items a cache file serves is decided HERE, with the plan: the source must be a regular
+     * file whose size and mtime are the header's, the file of this version and k and exactly as long as its header implies.  Such an
+     * item stays whole -- never cut into ranges, never sent to the device text parser.  A source that is missing is none of the
+     * cache's business: it fails where it failed before.  With several ranks the option is ignored (the items count as not cached). */
+    if (ctx && !plan_only && (pc_dir = pc_effective(ctx, &pc_mode)) != NULL) {
+        pc_asked = 1;
+        if (world > 1 || !pc_dir_usable(pc_dir, pc_mode, err)) { free(pc_dir); pc_dir = NULL; }
+        pool.pc_rw = pc_dir && pc_mode == SKPC_RW;
+    }
+    for (i = 0; pc_dir && i < nall; i++) {
+        skpc_reader rd;
+        struct stat st;
+        int o;
+        if (!all[i].reg || !(all[i].cpath = skpc_path(pc_dir, all[i].path))) continue;
+        memset(&st, 0, sizeof st);
+        st.st_size = (off_t)all[i].size;
+        st.st_mtim.tv_sec = (time_t)(all[i].mtime / 1000000000ll); st.st_mtim.tv_nsec = (long)(all[i].mtime % 1000000000ll);
+        o = skpc_open(&rd, all[i].cpath, &st, POOL_CHUNK);
+        if (o == SKPC_OK) {
+            struct stat now;
+            skpc_close(&rd);
+            /* a source that cannot be opened is not served: it goes the old way and fails there, as it does without the cache */
+            if (pc_source_readable(all[i].path, &now)) all[i].cache = PC_SERVE;
+            else { free(all[i].cpath); all[i].cpath = NULL; }
+        } else {
+            pool.pc_stale += o == SKPC_INVALID;
+            if (pc_mode == SKPC_RW) all[i].cache = PC_FILL; else pool.pc_not++;
+        }
+    }
 
     /* cut big plain-text files into pieces (never with one thread and one rank: that is the reference's strict sequence).
      * With several ranks the plan must be the SAME on every rank, so it is a function of the list, the files' sizes and
@@ -1711,7 +2114,7 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
             size_t total_items = 0;
             for (i = 0; i < n0; i++) {
                 uint64_t np = 1;
-                if (lanes > 1 && !gz[i] && !no_split && !(pool.text && world <= 1) && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target) np = (all[i].size + target - 1) / target;
+                if (lanes > 1 && !gz[i] && !no_split && !(pool.text && world <= 1) && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target && all[i].cache != PC_SERVE) np = (all[i].size + target - 1) / target;
                 total_items += np > 256 ? 256 : (size_t)np;
             }
             cut = (scan_item *)malloc((total_items + 1) * sizeof *cut);
@@ -1719,9 +2122,11 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
         }
         for (i = 0; i < n0; i++) {
             uint32_t np = 1, k;
-            if (lanes > 1 && !gz[i] && !no_split && !(pool.text && world <= 1) && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target) {
+            if (lanes > 1 && !gz[i] && !no_split && !(pool.text && world <= 1) && !getenv("SK_NO_SPLIT") && all[i].size >= 2 * target && all[i].cache != PC_SERVE) {
                 np = (uint32_t)((all[i].size + target - 1) / target > 256 ? 256 : (all[i].size + target - 1) / target);
             }
+            if (np > 1 && all[i].cache) { all[i].cache = 0; pool.pc_not++; }      /* (an item in byte ranges is not written in this version) */
+            if (np > 1) { free(all[i].cpath); all[i].cpath = NULL; }
             for (k = 0; k < np; k++) {
                 cut[out] = all[i];
                 if (k) cut[out].path = strdup(all[i].path);
@@ -1798,8 +2203,9 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
     pool.item = (scan_item *)malloc(((size_t)nall + 1) * sizeof *pool.item);
     for (i = 0; i < nall; i++) {
         if (owner[i] == rank) pool.item[pool.nitem++] = all[i];
-        else free(all[i].path);
+        else { free(all[i].path); free(all[i].cpath); }
     }
+    if (pc_asked && world > 1 && !plan_only) pool.pc_not += pool.nitem;
     free(all); free(est); free(owner);
 
     {   /* with fewer files than half the cores, a file's inflate and its record parsing take a core each; with
@@ -1899,6 +2305,8 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
         /* (said above or by the rank it happened to, or nothing to say) */
     } else if (pool.rc == SK_E_OPEN) {
         if (err) fprintf(err, "could not read file %s in GEN_calculate_kmer_count()\n", pool.item[pool.rc_index].path);
+    } else if (pool.rc == SK_E_CACHE) {
+        /* (the worker that found the damaged cache file has named it) */
     } else if (pool.rc == SK_E_SPLIT && guard && guard->armed) {
         /* (said nothing: the caller scans the list again, uncut) */
     } else if (pool.rc == SK_E_SPLIT) {
@@ -1909,7 +2317,16 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
         if (err) fprintf(err, "kmer_scrub_count: device error while scanning %s: %s (%s)\n", pool.item[pool.rc_index].path,
                          sk_strerror(pool.rc), sk_last_error(ctx));
     }
-    for (i = 0; i < pool.nitem; i++) free(pool.item[i].path);
+    if (pc_asked && ctx) {
+        pc_count(ctx, pool.pc_served, pool.pc_written, pool.pc_stale, pool.pc_not);
+        if (pool.timing && err && pc_dir)
+            fprintf(err, "kmer_scrub_count timing: pack cache: %s: %llu items served, %llu written, %llu stale, %llu not cached; %.1f MB of cache files; "
+                         "summed over the threads: checksums %.3f s, reading %.3f s, writing %.3f s\n", list_path, (unsigned long long)pool.pc_served,
+                    (unsigned long long)pool.pc_written, (unsigned long long)pool.pc_stale, (unsigned long long)pool.pc_not, 1e-6 * (double)pool.pc_bytes,
+                    pool.pc_t_sum, pool.pc_t_read, pool.pc_t_write);
+    }
+    free(pc_dir);
+    for (i = 0; i < pool.nitem; i++) { free(pool.item[i].path); free(pool.item[i].cpath); }
     free(pool.item);
     for (i = 0; i < pool.nll; i++) free(pool.ll[i].text);
     free(pool.ll);
@@ -2065,7 +2482,18 @@ static int env_int(const char *a, const char *b, const char *c3, int dflt)
  * compared before anyone scans (SK_E_PLAN) --, every rank's counters are summed with one RCCL all-reduce, rank 0 alone
  * writes stdout, the progress file and the skip/progress messages.  The sequence of collectives is the same on every rank
  * whatever fails where: set-up (in the rendezvous), table load (one sum), per list scan two agreements, one sum, the all-reduce. */
+static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_word_out);
+
+/* (--pack-cache DIR sets the process-wide default of the packed input cache: taken back when the call ends, however it ends) */
 int skh_kmer_scrub_count_main(int argc, char **argv, FILE *out, FILE *err)
+{
+    int word = 0;
+    const int status = ksc_main(argc, argv, out, err, &word);
+    if (word) skh_pack_cache_set(NULL, NULL, NULL);
+    return status;
+}
+
+static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_word_out)
 {
     const char *A = NULL, *B = NULL, *C = NULL, *R = NULL, *P = NULL, *env;
     FILE *progress = NULL;
@@ -2104,6 +2532,14 @@ int skh_kmer_scrub_count_main(int argc, char **argv, FILE *out, FILE *err)
     for (c = 1, j = 1; c < argc; c++) {
         if (!strcmp(argv[c], "--independent")) { scrub_independent = 1; continue; }
         if (!strcmp(argv[c], "--scrub-out") && c + 1 < argc) { scrub_out = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--pack-cache", 12) && (argv[c][12] == 0 || argv[c][12] == '=')) {     /* the packed input cache's directory (SK_PACK_CACHE) */
+            const char *m = getenv("SK_PACK_CACHE_MODE");
+            const char *dir = argv[c][12] ? argv[c] + 13 : (c + 1 < argc ? argv[++c] : "");
+            if (!dir[0]) { fprintf(err, "kmer_scrub_count: --pack-cache needs a directory\n"); return 1; }
+            skh_pack_cache_set(NULL, dir, m && !strcmp(m, "ro") ? "ro" : "rw");
+            *pack_cache_word_out = 1;
+            continue;
+        }
         if (!strncmp(argv[c], "--scrub", 7) && (argv[c][7] == 0 || argv[c][7] == '=')) {
             const char *v = argv[c][7] ? argv[c] + 8 : (c + 1 < argc ? argv[++c] : "");
             char *e;
@@ -2242,6 +2678,7 @@ int skh_kmer_scrub_count_main(int argc, char **argv, FILE *out, FILE *err)
         if (status == 0 && detect_argv) {
             sk_ctx *c2 = ctx;
             ctx = NULL;                               /* ctx and ks now belong to strain_detect, which releases them */
+            skh_pack_cache_set(c2, NULL, NULL);       /* (step 1's counters end here; strain_detect forgets the context when it lets it go) */
             status = skh_strain_detect_resident(c2, &ks, list_path, detect_argc, detect_argv, out, err);
         }
         if (tmp_path[0]) unlink(tmp_path);
@@ -2257,6 +2694,8 @@ done:
     if (getenv("SK_TIMING") && t5 > 0)
         fprintf(err, "kmer_scrub_count timing: key set %.2f s (+%.2f s more for the HIP context), table load %.2f s, scans %.2f s, "
                      "%s %.2f s\n", t1 - t0, t2 - t1, t3 - t2, t4 - t3, scrub_fraction >= 0.0 ? "filter + print" : "print", t5 - t4);
+    if (ctx) skh_pack_cache_set(ctx, NULL, NULL);    /* (the context's address may be another context's later) */
+    if (ctx && sk_pack_release) sk_pack_release(ctx);
     if (ctx) sk_ctx_destroy(ctx);
     skh_keyset_free(&ks);
     if (progress) fclose(progress);

@@ -322,7 +322,18 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
     return bad;
 }
 
+static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_word_out);
+
+/* (--pack-cache DIR sets the process-wide default of the packed input cache: taken back when the call ends, however it ends) */
 int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
+{
+    int word = 0;
+    const int status = sm_main(argc, argv, out, err, &word);
+    if (word) skh_pack_cache_set(NULL, NULL, NULL);
+    return status;
+}
+
+static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_word_out)
 {
     const char *A = NULL, *B = NULL, *C = NULL, *P = NULL, *S = NULL, *env;
     const int world = sm_env_int("SK_WORLD_SIZE", "WORLD_SIZE", "OMPI_COMM_WORLD_SIZE", 1);
@@ -351,6 +362,14 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
         }
     for (c = 1, j = 1; c < argc; c++) {
         if (!strcmp(argv[c], "--independent")) { independent = 1; continue; }
+        if (!strncmp(argv[c], "--pack-cache", 12) && (argv[c][12] == 0 || argv[c][12] == '=')) {     /* the packed input cache's directory (SK_PACK_CACHE) */
+            const char *m = getenv("SK_PACK_CACHE_MODE");
+            const char *dir = argv[c][12] ? argv[c] + 13 : (c + 1 < argc ? argv[++c] : "");
+            if (!dir[0]) { fprintf(err, "kmer_scrub_count: --pack-cache needs a directory\n"); return 1; }
+            skh_pack_cache_set(NULL, dir, m && !strcmp(m, "ro") ? "ro" : "rw");
+            *pack_cache_word_out = 1;
+            continue;
+        }
         if (!strncmp(argv[c], "--scrub-out", 11)) {
             fprintf(err, "kmer_scrub_count: with -S the strains file names each informative outfile (no --scrub-out)\n");
             return 1;
@@ -528,7 +547,7 @@ int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err)
                 if (rc == 0) nunion += nr;
                 if (progress) { fclose(progress); progress = NULL; }
             }
-            for (k = 0; k < nr; k++) { sk_union_destroy(res[k].u); res[k].u = NULL; }
+            for (k = 0; k < nr; k++) { skh_pack_cache_set(sk_union_context(res[k].u), NULL, NULL); sk_union_destroy(res[k].u); res[k].u = NULL; }
         }
         for (k = 0; rc == 0 && k < nsolo; k++) {
             rc = sm_single_pass(solo[k], A, B, C, progress, err, &list_bases);
@@ -599,7 +618,7 @@ done:
             if (st[k].made & 2u) unlink(st[k].hits);
             if (st[k].made & 4u) unlink(st[k].cov);
         }
-        if (st[k].ctx) sk_ctx_destroy(st[k].ctx);
+        if (st[k].ctx) { skh_pack_cache_set(st[k].ctx, NULL, NULL); sk_ctx_destroy(st[k].ctx); }
         skh_keyset_free(&st[k].ks);
         free(st[k].genome);
         free(st[k].outfile);

@@ -2137,7 +2137,7 @@ static void sd_strain_close(sd_prog *p)
     /* SK_LEAK_AT_EXIT=1 (set by bin/strain_detect, whose process ends right after): the result file is complete; taking 32
      * device contexts and key sets apart one hipFree at a time (0.3-0.7 s for 32 strains) is left to the end of the process */
     if (getenv("SK_LEAK_AT_EXIT") && strcmp(getenv("SK_LEAK_AT_EXIT"), "0")) { memset(p, 0, sizeof *p); return; }
-    if (p->ctx) sk_ctx_destroy(p->ctx);
+    if (p->ctx) { skh_pack_cache_set(p->ctx, NULL, NULL); sk_ctx_destroy(p->ctx); }
     skh_keyset_free(&p->ks);
     free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path);
     skc_destroy(p->cov);
@@ -2225,7 +2225,7 @@ int skh_strain_detect_resident_many(uint32_t n, sk_ctx **ctx, skh_keyset *ks, co
     for (s = 0; !bad && s < n; s++) bad = !ctx[s] || !informative[s] || (hits && !hits[s]);
     if (bad) {
         for (s = 0; ctx && ks && s < n; s++) {           /* (taken over all the same: nothing is left to the caller) */
-            if (ctx[s]) sk_ctx_destroy(ctx[s]);
+            if (ctx[s]) { skh_pack_cache_set(ctx[s], NULL, NULL); sk_ctx_destroy(ctx[s]); }
             ctx[s] = NULL;
             skh_keyset_free(&ks[s]);
         }

@@ -38,6 +38,7 @@ SK_E_NODEVICE = -1
 SK_E_OPEN = -5
 SK_E_SPLIT = -9
 SK_E_PLAN = -10
+SK_E_CACHE = -11
 
 # every symbol include/strainer_kmer.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
@@ -59,6 +60,7 @@ ABI_SYMBOLS = [
     "sk_union_create", "sk_union_destroy", "sk_union_tally_launch", "sk_union_tally_collect", "sk_union_last_error", "sk_union_scan_timing", "sk_union_sync",
     "sk_union_members", "sk_union_rows", "sk_union_count_enable", "sk_union_context", "sk_union_counts_fold",
     "skh_kmer_scrub_count_multi_main",
+    "sk_pack_device", "sk_scan_pinned_pack_many", "sk_pack_ticket_wait", "sk_pack_release", "skh_pack_cache_set", "skh_pack_cache_stats",
 ]
 
 
@@ -98,6 +100,13 @@ lib.sk_scan_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_ui
 lib.sk_pack_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int)]
 lib.sk_packed_bytes.argtypes = [C.c_uint64]
 lib.sk_packed_bytes.restype = C.c_uint64
+lib.sk_pack_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int)]
+lib.sk_scan_pinned_pack_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+lib.sk_pack_ticket_wait.argtypes = [C.c_void_p, C.c_uint64]
+lib.sk_pack_release.argtypes = [C.c_void_p]
+lib.sk_pack_release.restype = None
+lib.skh_pack_cache_set.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+lib.skh_pack_cache_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4 + [C.c_int]
 lib.sk_tally_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
 lib.sk_sync.argtypes = [C.c_void_p]
@@ -289,6 +298,8 @@ class KmerContext:
         self._bufs = []
 
     def _ck(self, rc):
+        if rc == SK_E_CACHE:            # (a host-layer code: the device layer's texts do not know it)
+            raise SKError(rc, "a packed input cache file is damaged (stderr names it); part of it may have been counted")
         if rc:
             raise SKError(rc, lib.sk_last_error(self._h).decode())
 
@@ -433,6 +444,38 @@ class KmerContext:
         self._ck(lib.sk_scan_pinned_packed_many(hs, n, packed_arr.ctypes.data, nbytes, col, C.byref(t)))
         return t.value
 
+    def pack_device(self, dev_stream, nbytes, dev_packed):
+        """sk_pack_device: the record stream at device pointer dev_stream packed into dev_packed (packed_bytes(nbytes) bytes, 8-byte
+        aligned) as pack_stream() packs it on the host; returns the odd flag"""
+        odd = C.c_int(0)
+        self._ck(lib.sk_pack_device(self._h, dev_stream, nbytes, dev_packed, C.byref(odd)))
+        return bool(odd.value)
+
+    def scan_pinned_pack_many(self, others, arr, nbytes, col, packed_out, odd_out):
+        """sk_scan_pinned_pack_many: scan_pinned_many plus the device's pack of the same bytes, sent home into packed_out (pinned uint8
+        array, packed_bytes(nbytes)) and odd_out (pinned, 4 bytes: a u32); returns the ticket for pack_ticket_wait"""
+        t = C.c_uint64(0)
+        hs, n = self._many(others)
+        self._ck(lib.sk_scan_pinned_pack_many(hs, n, arr.ctypes.data, nbytes, col, packed_out.ctypes.data, odd_out.ctypes.data, C.byref(t)))
+        return t.value
+
+    def pack_ticket_wait(self, ticket):
+        self._ck(lib.sk_pack_ticket_wait(self._h, ticket))
+
+    def pack_cache(self, directory, mode="rw"):
+        """skh_pack_cache_set: the packed input cache of scan_file / scan_list[_many] on this context; None: follow the process-wide
+        default (SK_PACK_CACHE) again, "": off for this context"""
+        if directory is None:
+            self._ck(lib.skh_pack_cache_set(self._h, None, None))
+        else:
+            self._ck(lib.skh_pack_cache_set(self._h, os.fsencode(directory), mode.encode()))
+
+    def pack_cache_stats(self, reset=False):
+        """list items (served, written, stale, not_cached) since the last reset"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._ck(lib.skh_pack_cache_stats(self._h, *[C.byref(x) for x in v], int(reset)))
+        return tuple(x.value for x in v)
+
     def device_memory(self):
         """(free, total) bytes of HBM on this context's device"""
         f, t = C.c_uint64(0), C.c_uint64(0)
@@ -574,6 +617,8 @@ class KmerContext:
                 lib.sk_dev_free(self._h, p)
             self._bufs = []
             lib.sk_text_release(self._h)
+            lib.sk_pack_release(self._h)
+            lib.skh_pack_cache_set(self._h, None, None)
             lib.sk_ctx_destroy(self._h)
             self._h = None
 
