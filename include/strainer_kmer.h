@@ -386,7 +386,10 @@ int sk_scan_timing(sk_ctx *ctx, double *total_ms, uint64_t *launches, int reset)
  * other call of the context waits for both, results are the same; 1 = all of them on the context's one stream, for A/B
  * runs and tests; the environment variable SK_SCAN_LANES=1 does the same for programs that set no options), "dev_alloc_uncached" (experiment:
  * non-zero = sk_dev_alloc hands out memory the L2 does not keep), "ablate" (accepted as 0 only: the kernel variants it chose were retired).
- * Unknown name -> SK_E_ARG. */
+ * Unknown name -> SK_E_ARG.  Ranges: "table_load_pct" 5..90 (default 50); "grid_kib" -1 or 1..4194304 (the filter is never
+ * smaller than 4 KiB); a value outside them -> SK_E_ARG and the option keeps what it had.  A union (sk_union_create) takes both from its
+ * first member: its table is sized to that member's "table_load_pct", its level-1 filter to that member's "grid_kib" times the
+ * number of members. */
 int sk_set_option(sk_ctx *ctx, const char *name, long value);
 
 /* Device buffer helpers so that FFI callers need no HIP binding of their own. */

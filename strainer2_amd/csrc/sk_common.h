@@ -100,6 +100,12 @@ SK_HD uint32_t sk_grid1_bits(uint32_t g) { return g * 0x85EBCA77u; }
 SK_HD uint32_t sk_grid2_block(uint32_t g, uint32_t shift) { return (g * 0xC2B2AE3Du) >> shift; }
 SK_HD uint32_t sk_grid2_bits(uint32_t g) { return g * 0x27D4EB2Fu; }
 
+/* the partitioned pipeline's bins (sk_dev_pipeline.hip.h): partition (7 bits) and in-partition key (20 bits) of a canonical
+ * 16-mer's mix; multiplier of its own, so that the slices' false positives are not the L2 filter's */
+SK_HD uint32_t sk_grid3_hash(uint32_t g) { return (g ^ (g >> 13)) * 0x5BD1E995u; }
+SK_HD uint32_t sk_grid3_part(uint32_t h) { return h >> 25; }
+SK_HD uint32_t sk_grid3_key(uint32_t h) { return (h >> 5) & 0xFFFFFu; }
+
 /* reverse complement of a packed 31-mer */
 SK_HD uint64_t sk_revcomp62(uint64_t key)
 {

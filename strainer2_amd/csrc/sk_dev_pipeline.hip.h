@@ -20,9 +20,8 @@
 #define SK_BIN_CAP    40u                          // entries per (partition, tile): mean 28.5 clean chunks, +2 sigma; the rest go straight to the candidates
 #define SK_BIN_WORDS  32768u                       // 2^20 bits per partition slice
 
-// partition (7 bits) and in-partition key (20 bits) of a canonical 16-mer's mix; multiplier of its own, so that the slices'
-// false positives are not the L2 filter's
-__device__ __forceinline__ uint32_t sk_grid3_hash(uint32_t g) { return (g ^ (g >> 13)) * 0x5BD1E995u; }
+// partition (7 bits) and in-partition key (20 bits) of a canonical 16-mer's mix: sk_grid3_hash, sk_grid3_part and sk_grid3_key
+// (sk_common.h, where the tests' key search can call them)
 
 __global__ void sk_grid3_insert(const sk_u4 *__restrict__ slots, uint64_t nslots, uint32_t *__restrict__ w3)
 {
@@ -34,8 +33,8 @@ __global__ void sk_grid3_insert(const sk_u4 *__restrict__ slots, uint64_t nslots
         const uint32_t f = (uint32_t)(k >> (2 * (15 - off)));
         const uint32_t r = sk_revcomp16(f);
         const uint32_t h = sk_grid3_hash(sk_gmix(f < r ? f : r));
-        const uint32_t key = (h >> 5) & 0xFFFFFu;
-        uint32_t *w = w3 + (size_t)(h >> 25) * SK_BIN_WORDS + (key >> 5);
+        const uint32_t key = sk_grid3_key(h);
+        uint32_t *w = w3 + (size_t)sk_grid3_part(h) * SK_BIN_WORDS + (key >> 5);
         const uint32_t bit = 1u << (key & 31u);
         if (!(__builtin_nontemporal_load(w) & bit)) atomicOr(w, bit);
     }
@@ -85,8 +84,8 @@ void sk_bin(const uint8_t *__restrict__ stream, uint64_t nbytes, sk_table_view t
             const uint32_t cw = (c0 << 24) | (c1 << 16) | (c2 << 8) | c3;
             const uint32_t rc = sk_revcomp32(cw);
             const uint32_t h = sk_grid3_hash(sk_gmix(cw < rc ? cw : rc));
-            const uint32_t p = h >> 25;
-            const uint32_t ent = (c << 20) | ((h >> 5) & 0xFFFFFu);
+            const uint32_t p = sk_grid3_part(h);
+            const uint32_t ent = (c << 20) | sk_grid3_key(h);
             const uint32_t r = ent != 0xFFFFFFFFu ? atomicAdd(&cnt[p], 1u) : SK_BIN_CAP;
             if (r < SK_BIN_CAP) stage[p * SK_BIN_CAP + r] = ent;
             else cand[(tile0 >> 4) + c] = 1u;                     // no room in the segment: a candidate without being asked

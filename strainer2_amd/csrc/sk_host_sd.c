@@ -797,8 +797,10 @@ static void sd_unmap_wait(void)
 }
 static void sd_unmap_later(void *p, size_t n)
 {
-    sd_unmap_wait();
+    /* wait for the one before and start this one under ONE hold of the lock: with the lock let go in between, two decode threads
+     * could both find nobody to wait for, and the second would overwrite what the first one's thread is about to unmap */
     pthread_mutex_lock(&sd_unmapper_mu);
+    if (sd_unmapper.live) { pthread_join(sd_unmapper.th, NULL); sd_unmapper.live = 0; }
     sd_unmapper.p = p; sd_unmapper.n = n;
     if (pthread_create(&sd_unmapper.th, NULL, sd_unmap_thread, NULL) == 0) sd_unmapper.live = 1;
     else munmap(p, n);

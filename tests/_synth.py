@@ -160,17 +160,27 @@ def u_window(rng: random.Random, strain: bytes):
     for _ in range(200):
         a = rng.randrange(len(strain) - 30)
         w = strain[a:a + 31].upper()
-        if set(w) - set(b"ACGT"):
-            continue
-        r = revcomp(w)
-        if w <= r:
-            continue
-        d = next(i for i in range(31) if w[i] != r[i])
-        ts = [i for i in range(d + 1, 31) if r[i] == ord("T")]
-        if ts:
-            i = rng.choice(ts)
-            return r[:i] + rng.choice([b"U", b"u"]) + r[i + 1:], w
+        u = u_window_of(rng, w)
+        if u:
+            return u, w
     return None
+
+
+def u_window_of(rng: random.Random, w: bytes):
+    """u_window for one given k-mer w (31 upper-case bytes), in the table or not: the window holding U or u through which the
+    byte-string kernel looks w up, or None where w has none (a byte that is no base, w <= revcomp(w), or no T behind the first
+    base where the two differ)"""
+    if len(w) != 31 or set(w) - set(b"ACGT"):
+        return None
+    r = revcomp(w)
+    if w <= r:
+        return None
+    d = next(i for i in range(31) if w[i] != r[i])
+    ts = [i for i in range(d + 1, 31) if r[i] == ord("T")]
+    if not ts:
+        return None
+    i = rng.choice(ts)
+    return r[:i] + rng.choice([b"U", b"u"]) + r[i + 1:]
 
 
 def tally_strains(rng: random.Random, kind: int, n: int, sizes=(400, 3000, 12000)) -> list:
