@@ -259,6 +259,12 @@ void sk_batch_destroy(sk_batch *b);
 int  sk_batch_sync(sk_batch *b);                               /* its uploads are done: the host memory it was filled from may be reused, the batch kept for the next file */
 int  sk_batch_fill(sk_batch *b, const uint8_t *stream, uint64_t nbytes, const uint32_t *rec_start, uint32_t nrec);
 int  sk_batch_fill_packed(sk_batch *b, const void *packed, uint64_t nbytes, const uint32_t *rec_start, uint32_t nrec);   /* the batch in sk_pack_stream's form (nbytes, rec_start: of the byte stream it was packed from) */
+/* The bytes the batch holds (sk_batch_fill), packed on the device into sk_pack_stream's form and copied home -- strain_detect's target
+ * cache.  Enqueued on the batch's own stream behind the upload: no tally waits for it.  sk_packed_bytes(nbytes) bytes go to
+ * pinned_packed_out (nothing behind them is written) and one u32, non-zero = odd, to pinned_odd_out; both are there once
+ * sk_batch_pack_wait has returned.  SK_E_STATE: the batch is packed already, was parsed from text, or is empty. */
+int  sk_batch_pack_home(sk_batch *b, void *pinned_packed_out, uint32_t *pinned_odd_out);
+int  sk_batch_pack_wait(sk_batch *b);
 /* A batch filled from plain TEXT, parsed on the device (new; opt-in for strain_detect: option "device_parse", SK_DEVICE_PARSE=1): what
  * sk_batch_fill does with a record stream the host made, for a piece of FASTA/FASTQ text as it lies in the file.
  *   A piece is pinned_text[0..nbytes) (sk_pinned_alloc; at most 256 MiB), beginning at a record boundary as for sk_text_parse_device.
@@ -482,6 +488,17 @@ int skh_scan_list_many(sk_ctx *const *ctx, uint32_t n, const char *list_path, co
  * or of another version), and scanned without being cached; each may be NULL. */
 int skh_pack_cache_set(sk_ctx *ctx, const char *dir, const char *mode);
 int skh_pack_cache_stats(sk_ctx *ctx, uint64_t *served, uint64_t *written, uint64_t *stale, uint64_t *not_cached, int reset);
+/* strain_detect's target cache (new, opt-in: strain_detect --target-cache DIR, also behind --detect; or SK_TARGET_CACHE=DIR;
+ * SK_TARGET_CACHE_MODE=rw|ro).  The metagenomes strain_detect reads (-b/-c, -B) are kept, one file per target, as the chunks its
+ * decode side handed on: the record stream in sk_pack_stream's form, packed on the device beside the scans, and every record's length
+ * -- DIR/<basename>.<hash of the realpath>.skt (sk_pcache.h, version 2).  A later run whose target has the same size and mtime is
+ * served from that file by one thread: no inflate, no parser threads.  Every byte a run prints or writes is the same with the cache
+ * off, filled or served.  A switch of its own: SK_PACK_CACHE goes on meaning the -g list only, and both may name one directory.  A
+ * directory that cannot be used gives one warning and the run goes on uncached; a stale, mis-sized or other-version file is a miss
+ * (replaced in rw mode); a file that fails a checksum or a structure check fails the run with SK_E_CACHE, the file named on `err`.
+ * Not written: targets the device text parser may take, a target with a record of 2^32 bases or more, one that was not read to its
+ * end.  skh_target_cache_stats: the process's targets since the last reset (the programs own their contexts, so there is no ctx). */
+int skh_target_cache_stats(uint64_t *served, uint64_t *written, uint64_t *stale, uint64_t *not_cached, int reset);
 /* Hash of the work plan skh_scan_list(list, skip, .., world) follows (items, byte ranges, file sizes, owners): a function
  * of the list, the files and `world` (and of SK_SPLIT_BYTES / SK_NO_SPLIT) only, never of a rank's thread count.  With the
  * library's own communicator skh_scan_list compares it across ranks itself (SK_E_PLAN); a caller that reduces the counters

@@ -936,6 +936,10 @@ struct sk_batch {
     size_t       h_rec_cap;             // two from the caller's pageable arrays (which the runtime stages, chunk by chunk, on its own threads)
     void        *text;                  // sk_text.hip's state of a batch filled from text (sk_batch_fill_text), freed through text_free
     void       (*text_free)(void *);
+    bool         from_text;             // the current contents were parsed on the device (or a parse is in flight)
+    void        *d_pack;                // sk_batch_pack_home (sk_packdev.hip): the packed form of the resident bytes, and behind it the odd flag
+    size_t       pack_cap;              // stream bytes d_pack has room for (follows stream_cap)
+    hipEvent_t   home;                  // ... and its copy home
 };
 
 extern "C" int sk_batch_create(sk_ctx *c, sk_batch **out)
@@ -949,6 +953,7 @@ extern "C" int sk_batch_create(sk_ctx *c, sk_batch **out)
     b->d_stream = b->d_rec = NULL; b->stream_cap = b->rec_cap = 0; b->nbytes = 0; b->nrec = b->ntiles = 0;
     b->h_rec = NULL; b->h_rec_cap = 0; b->packed = false;
     b->text = NULL; b->text_free = NULL;
+    b->from_text = false; b->d_pack = NULL; b->pack_cap = 0; b->home = NULL;
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { delete b; return sk_fail(c, SK_E_HIP, "stream"); }
     if (hipEventCreateWithFlags(&b->ready, hipEventDisableTiming) != hipSuccess) { hipStreamDestroy(b->stream); delete b; return sk_fail(c, SK_E_HIP, "event"); }
     *out = b;
@@ -972,6 +977,8 @@ extern "C" void sk_batch_destroy(sk_batch *b)
     if (b->text && b->text_free) b->text_free(b->text);
     hipFree(b->d_stream); hipFree(b->d_rec);
     if (b->h_rec) hipHostFree(b->h_rec);
+    hipFree(b->d_pack);
+    if (b->home) hipEventDestroy(b->home);
     hipEventDestroy(b->ready);
     hipStreamDestroy(b->stream);
     delete b;
@@ -1025,6 +1032,33 @@ extern "C" int sk_batch_hook_(sk_batch *b, uint64_t stream_bytes, uint64_t rec_w
 extern "C" void sk_batch_contents_(sk_batch *b, uint64_t nbytes, uint32_t nrec)
 {
     b->nbytes = nbytes; b->nrec = nrec; b->ntiles = (uint32_t)((nbytes + 32767u) >> 15); b->packed = false;
+    b->from_text = true;
+}
+
+// The device pack's way to a batch (sk_packdev.hip: sk_batch_pack_home, sk_batch_pack_wait).  want_room: the contents must be bytes that
+// came up as bytes (SK_E_STATE otherwise: packed already, parsed from text, empty), and the batch's own buffer for their packed form
+// has room for whatever d_stream can hold -- it grows with stream_cap, so a refill that fits d_stream never grows it.  The batch's
+// stream is NOT waited for (unlike sk_batch_hook_): the caller enqueues behind the upload.  !want_room: only where things are (home
+// is NULL while nothing was ever packed).
+extern "C" int sk_batch_pack_hook_(sk_batch *b, int want_room, sk_batch_pack_hook *out)
+{
+    if (!b || !out) return SK_E_ARG;
+    sk_ctx *c = b->owner;
+    SK_HIP(c, hipSetDevice(c->device));
+    if (want_room) {
+        if (b->packed || b->from_text || !b->nrec || !b->nbytes) return sk_fail(c, SK_E_STATE, "the batch holds no bytes to pack (packed already, parsed from text, or empty)");
+        if (!b->home) SK_HIP(c, hipEventCreateWithFlags(&b->home, hipEventDisableTiming));
+        if (b->pack_cap < b->stream_cap) {
+            SK_HIP(c, hipStreamSynchronize(b->stream));            // (a copy home of the old buffer may be in flight)
+            (void)hipFree(b->d_pack); b->d_pack = NULL; b->pack_cap = 0;
+            SK_HIP(c, hipMalloc(&b->d_pack, (((size_t)b->stream_cap + 15u) >> 4) * 6u + 64u));
+            b->pack_cap = b->stream_cap;
+        }
+    }
+    out->owner = c; out->stream = (void *)b->stream; out->home = (void *)b->home;
+    out->d_stream = b->d_stream; out->nbytes = b->nbytes; out->d_pack = b->d_pack;
+    out->d_odd = b->d_pack ? (uint32_t *)((uint8_t *)b->d_pack + (((((size_t)b->pack_cap + 15u) >> 4) * 6u + 15u) & ~(size_t)15u)) : NULL;
+    return SK_OK;
 }
 
 // Upload new contents.  Every tally launched on the previous contents must have been collected.
@@ -1059,7 +1093,7 @@ static int sk_batch_fill_any(sk_batch *b, const uint8_t *stream, uint64_t nbytes
     b->packed = packed;
     SK_HIP(c, hipMemcpyAsync(b->d_rec, b->h_rec, ((size_t)nrec + ntiles + 2) * 4, hipMemcpyHostToDevice, b->stream));
     SK_HIP(c, hipEventRecord(b->ready, b->stream));
-    b->nbytes = nbytes; b->nrec = nrec; b->ntiles = ntiles;
+    b->nbytes = nbytes; b->nrec = nrec; b->ntiles = ntiles; b->from_text = false;
     return SK_OK;
 }
 

@@ -37,6 +37,7 @@
 #include "sk_gzpipe.h"
 #include "sk_cpus.h"
 #include "sk_gzout.h"
+#include "sk_pcache.h"
 
 
 enum { SD_TYPE = 0, SD_BACKGROUND = 5, SD_INFORMATIVE = 2, SD_PLAIN = 1, SD_NCOLS = 6 };
@@ -118,6 +119,8 @@ typedef struct sd_chunk {
     int       t_eof, tla;                    /* the file's last piece; bytes of look-ahead behind the piece (0 or 1) */
     uint64_t  toff, tlen;
     uint64_t  t_reads, t_eval;               /* accepted: records of k bases or more, and their windows */
+    int       tc_handed;                     /* the target cache's writer has been given this chunk */
+    int       cache_err;                     /* the serving thread's marker: its cache file failed a check here (SKPC_*) */
 } sd_chunk;
 enum { SD_TEXT_PENDING = 1, SD_TEXT_ACCEPTED = 2, SD_TEXT_DECLINED = 3 };   /* (DECLINED before it went up: the reader found no piece to send) */
 typedef struct sd_sp { uint32_t n; uint32_t *rec, *all, *inf, *hbeg /* n + 1 */, *rows; } sd_sp;
@@ -154,6 +157,11 @@ typedef struct {
     sd_chunk   *pre;                         /* the queued chunk whose bytes are already in bat[bcur ^ 1] */
     sd_chunk   *ahead;                       /* ... and whose scan has been launched as well (solo streams: see sd_launch_ahead) */
     int         solo;                        /* the only stream that uses the tables now (SE, PEI): its next chunk may be scanned while this one is replayed */
+    /* the target cache (sd_tc): a file that is served has a serving thread in the decode thread's place; one that is filled has a writer */
+    int         serving, cache_failed;
+    skpc_reader tcr;
+    char       *tc_path;
+    struct sd_tcw *tcw;
 } sd_stream;
 
 /* Page-locked chunk buffers, recycled.  The upload of a chunk from ordinary memory goes through the runtime's
@@ -718,6 +726,290 @@ static void *sd_decode_thread(void *arg)
     return NULL;
 }
 
+
+/* ---- the target cache (opt-in: --target-cache DIR or SK_TARGET_CACHE=DIR; SK_TARGET_CACHE_MODE=rw|ro) -----------------------------
+ * The same metagenomes are tracked again for every new strain, drug or donor, and each run inflates and parses them from scratch.
+ * With the switch on, what the decode side hands to the main thread for one target file -- its chunks: the record stream and the
+ * length of every record -- is kept in DIR, one file per target (sk_pcache.h, version 2, .skt), the stream in sk_pack_stream's form,
+ * and a later run is SERVED from it: one thread per file reads segment after segment into a pool buffer, checks its sum, rebuilds
+ * len/pstart/prec by sd_on_record's rule and queues the chunk -- no inflate, no parser threads, no segments; the chunks go up through
+ * sk_batch_fill_packed as SK_SD_PACK=1 chunks do.
+ * FILLING costs the decode threads nothing: a chunk goes up as bytes as ever, the DEVICE packs it where it lies in the batch, behind
+ * its upload and beside its scans (sk_batch_pack_home), and one writer thread per stream waits for the packed form and appends it --
+ * or the chunk's bytes, when it holds a byte for the byte-string kernel.  The main thread hands the chunk on (with a reference) and
+ * goes on; the writer's queue holds four chunks, so memory stays bounded and the appends come in the file's order -- a writer that
+ * falls four chunks behind is waited for.  Without the device entry points (the host-only builds) the writer packs with
+ * sk_pack_stream.  A file takes its name only when the chunk with `last` set was appended and nothing failed: a cancelled stream, a
+ * failed split, a PE1 abandoned because PE2 ended first leave nothing.  Pieces of text for the device's parser are not written.
+ * A served file that fails a sum or a structure check FAILS the run (SK_E_CACHE, the file named): hit lines of earlier chunks are
+ * out already. */
+#pragma weak sk_batch_pack_home
+#pragma weak sk_batch_pack_wait
+typedef struct { uint64_t served, written, stale, not_cached; double t_sum, t_read, t_write, t_pack; } sd_tc_counts;
+static struct { char *dir; int ro; } sd_tc;
+static sd_tc_counts sd_tc_run, sd_tc_all;             /* this run's; the process's (skh_target_cache_stats) */
+static pthread_mutex_t sd_tc_mu = PTHREAD_MUTEX_INITIALIZER;
+
+int skh_target_cache_stats(uint64_t *served, uint64_t *written, uint64_t *stale, uint64_t *not_cached, int reset)
+{
+    pthread_mutex_lock(&sd_tc_mu);
+    if (served) *served = sd_tc_all.served;
+    if (written) *written = sd_tc_all.written;
+    if (stale) *stale = sd_tc_all.stale;
+    if (not_cached) *not_cached = sd_tc_all.not_cached;
+    if (reset) memset(&sd_tc_all, 0, sizeof sd_tc_all);
+    pthread_mutex_unlock(&sd_tc_mu);
+    return SK_OK;
+}
+
+#define SD_TCW_QUEUE 4
+typedef struct sd_tcw {
+    skpc_writer *w;
+    pthread_t th;
+    pthread_mutex_t mu; pthread_cond_t cv;
+    struct { sd_chunk *c; sk_batch *b; uint8_t *pk; } q[SD_TCW_QUEUE];      /* b, pk: the batch that packs the chunk and where its packed form lands (or none) */
+    int qn, closing;
+    int failed, saw_last;                    /* (the writer thread's own until it is joined) */
+    uint64_t records, bases;
+    double t_pack;
+} sd_tcw;
+
+/* where the device's odd flag lands in a pool buffer: its last aligned u32 */
+static uint32_t *sd_tc_flag(uint8_t *pk) { return (uint32_t *)(pk + ((sd_pin.bytes - 4u) & ~(size_t)3u)); }
+
+/* one chunk into the file */
+static void sd_tcw_append(sd_tcw *w, sd_chunk *c, uint8_t *pk, int pk_ok)
+{
+    uint32_t kind = SKPC_PACKED, i;
+    const uint8_t *src = NULL;
+    uint8_t *own = NULL, *dst;
+    uint64_t raw = 0, part, plen, bases = 0;
+    if (c->np) {
+        if (pk_ok && !*sd_tc_flag(pk)) src = pk;
+        else if (c->packed) src = c->buf;
+        else if (pk_ok) { kind = SKPC_BYTES; src = c->buf; }                  /* (the device saw a byte for the byte-string kernel) */
+        else {
+            int odd = 0;
+            own = (uint8_t *)malloc((size_t)skpt_payload_len(SKPC_PACKED, c->blen, c->nrec) + 8u);
+            if (!own || sk_pack_stream(c->buf, c->blen, own, &odd) != SK_OK) { free(own); w->failed = 1; return; }
+            if (odd) { free(own); own = NULL; kind = SKPC_BYTES; src = c->buf; } else src = own;
+        }
+        raw = kind == SKPC_PACKED ? skpc_packed_bytes(c->blen) : c->blen;
+    }
+    for (i = 0; i < c->nrec; i++) {
+        if (c->len[i] > 0xFFFFFFFFull) { free(own); w->failed = 1; return; }   /* a record of 2^32 bases or more: this target is not cached */
+        bases += c->len[i];
+    }
+    part = skpt_stream_part(kind, c->blen);
+    plen = skpt_payload_len(kind, c->blen, c->nrec);
+    if (src && src == own) dst = own;
+    else if (pk && plen <= sd_pin.bytes) dst = pk;
+    else dst = own = (uint8_t *)malloc((size_t)plen + 8u);
+    if (!dst) { w->failed = 1; return; }
+    if (src && src != dst) memcpy(dst, src, (size_t)raw);
+    memset(dst + raw, 0, (size_t)(part - raw));
+    for (i = 0; i < c->nrec; i++) skpc_put32(dst + part + 4u * (size_t)i, (uint32_t)c->len[i]);
+    skpt_append(w->w, kind, c->blen, c->nrec, c->np, c->last, (uint32_t)c->end_kind, (uint64_t)c->end_len, dst);
+    w->records += c->nrec; w->bases += bases;
+    if (c->last) w->saw_last = 1;
+    free(own);
+}
+
+static void *sd_tcw_thread(void *arg)
+{
+    sd_tcw *w = (sd_tcw *)arg;
+    pthread_setname_np(pthread_self(), "sk-tcache");
+    for (;;) {
+        sd_chunk *c; sk_batch *b; uint8_t *pk;
+        int i, pk_ok = 0;
+        pthread_mutex_lock(&w->mu);
+        while (w->qn == 0 && !w->closing) pthread_cond_wait(&w->cv, &w->mu);
+        if (w->qn == 0) { pthread_mutex_unlock(&w->mu); return NULL; }
+        c = w->q[0].c; b = w->q[0].b; pk = w->q[0].pk;
+        for (i = 1; i < w->qn; i++) w->q[i - 1] = w->q[i];
+        w->qn--;
+        pthread_cond_broadcast(&w->cv);
+        pthread_mutex_unlock(&w->mu);
+        if (b) {                                           /* (always waited for: the copy home must have landed before the buffer goes back to the pool) */
+            const double t0 = now_s();
+            pk_ok = sk_batch_pack_wait(b) == SK_OK;
+            w->t_pack += now_s() - t0;
+            if (!pk_ok) { w->failed = 1; pk = NULL; }      /* (a device error: the buffer is not reused) */
+        }
+        if (!w->failed) sd_tcw_append(w, c, pk, pk_ok);
+        if (pk) sd_pin_put(pk);
+        chunk_free(c);
+    }
+}
+
+/* the main thread's side: chunk c, whose bytes device 0's batch b0 has just been sent (NULL: a chunk without a record of k bases), is
+ * the next of its stream's file */
+static void sd_tc_hand(sd_stream *st, sd_chunk *c, sk_batch *b0)
+{
+    sd_tcw *w = st ? st->tcw : NULL;
+    uint8_t *pk = NULL;
+    sk_batch *pb = NULL;
+    if (!w || c->tc_handed || c->text) return;
+    c->tc_handed = 1;
+    if (b0 && c->np && !c->packed && sk_batch_pack_home && sk_batch_pack_wait && skpc_pad8(skpc_packed_bytes(c->blen)) + 8u <= sd_pin.bytes &&
+        (pk = (uint8_t *)sd_pin_get()) != NULL) {
+        if (sk_batch_pack_home(b0, pk, sd_tc_flag(pk)) == SK_OK) pb = b0;
+        else { sd_pin_put(pk); pk = NULL; }                /* (the writer packs it) */
+    }
+    chunk_ref(c);
+    pthread_mutex_lock(&w->mu);
+    while (w->qn == SD_TCW_QUEUE) pthread_cond_wait(&w->cv, &w->mu);
+    w->q[w->qn].c = c; w->q[w->qn].b = pb; w->q[w->qn].pk = pk;
+    w->qn++;
+    pthread_cond_broadcast(&w->cv);
+    pthread_mutex_unlock(&w->mu);
+}
+
+/* the stream is over (its batches are still there): the writer runs dry, and the file is kept if it holds the whole target */
+static void sd_tc_finish(sd_stream *st)
+{
+    sd_tcw *w = st->tcw;
+    int kept;
+    if (!w) return;
+    pthread_mutex_lock(&w->mu);
+    w->closing = 1;
+    pthread_cond_broadcast(&w->cv);
+    pthread_mutex_unlock(&w->mu);
+    pthread_join(w->th, NULL);
+    pthread_mutex_lock(&sd_tc_mu);
+    sd_tc_run.t_sum += w->w->t_sum; sd_tc_run.t_write += w->w->t_write; sd_tc_run.t_pack += w->t_pack;
+    pthread_mutex_unlock(&sd_tc_mu);
+    kept = skpc_end(w->w, w->saw_last && !w->failed && !st->split_failed, w->records, w->bases);
+    pthread_mutex_lock(&sd_tc_mu);
+    if (kept) sd_tc_run.written++; else sd_tc_run.not_cached++;
+    pthread_mutex_unlock(&sd_tc_mu);
+    pthread_mutex_destroy(&w->mu);
+    pthread_cond_destroy(&w->cv);
+    free(w);
+    st->tcw = NULL;
+}
+
+/* the serving thread: the decode thread's place for a file whose cache holds */
+static void *sd_serve_thread(void *arg)
+{
+    sd_stream *st = (sd_stream *)arg;
+    double t_sum = 0, t_read = 0;
+    int rc;
+    pthread_setname_np(pthread_self(), "sk-tserve");
+    for (;;) {
+        skpt_seg sg;
+        sd_chunk *c;
+        const uint8_t *tab;
+        uint64_t at = 0;
+        uint32_t i, np = 0;
+        pthread_mutex_lock(&st->mu);
+        i = (uint32_t)st->cancel;
+        pthread_mutex_unlock(&st->mu);
+        if (i) { rc = SKPC_OK; break; }
+        if ((rc = skpt_next(&st->tcr, &sg)) != SKPC_OK) { if (rc == SKPC_MISS) rc = SKPC_OK; break; }     /* (behind the last segment) */
+        if ((c = chunk_new()) == NULL) { rc = SKPC_IO; break; }
+        if (sg.payload_len <= sd_pin.bytes && (c->buf = (uint8_t *)sd_pin_get()) != NULL) { c->pinned = 1; c->bcap = sd_pin.bytes; }
+        else {                                             /* a chunk longer than a pool buffer: ordinary memory, as the builder does */
+            c->buf = (uint8_t *)malloc((size_t)sg.payload_len + 8u);
+            c->bcap = sg.payload_len + 8u;
+            if (sg.np) __atomic_add_fetch(&n_unpinned_chunks, 1, __ATOMIC_RELAXED);
+        }
+        c->len = (uint64_t *)malloc(((size_t)sg.nrec + 1) * sizeof *c->len);
+        c->pstart = (uint32_t *)malloc(((size_t)sg.np + 1) * sizeof *c->pstart);
+        c->prec = (uint32_t *)malloc(((size_t)sg.np + 1) * sizeof *c->prec);
+        if (!c->buf || !c->len || !c->pstart || !c->prec) { chunk_free(c); rc = SKPC_IO; break; }
+        if ((rc = skpt_payload(&st->tcr, &sg, c->buf, &t_sum, &t_read)) != SKPC_OK || (rc = skpt_lengths(&sg, c->buf)) != SKPC_OK) { chunk_free(c); break; }
+        tab = skpt_table(&sg, c->buf);
+        for (i = 0; i < sg.nrec; i++) {                    /* sd_on_record's rule */
+            const uint32_t l = skpc_le32(tab + 4u * (size_t)i);
+            c->len[i] = l;
+            if (l >= SK_K) { c->pstart[np] = (uint32_t)at; c->prec[np++] = i; at += (uint64_t)l + 1u; }
+        }
+        c->nrec = c->rcap = sg.nrec; c->np = np; c->pcap = sg.np + 1;
+        c->blen = sg.stream_len;
+        c->packed = sg.kind == SKPC_PACKED && sg.np;
+        c->last = (sg.flags & SKPT_LAST) != 0; c->end_kind = (int)sg.end_kind; c->end_len = (size_t)sg.end_len;
+        stream_push(st, c);
+    }
+    if (rc != SKPC_OK) {                                   /* the main thread fails the run when it comes to this marker */
+        sd_chunk *c = chunk_new();
+        if (c) { c->last = 1; c->cache_err = rc; c->end_kind = SKP_END_RESET; stream_push(st, c); }
+    }
+    pthread_mutex_lock(&sd_tc_mu);
+    sd_tc_run.t_sum += t_sum; sd_tc_run.t_read += t_read;
+    pthread_mutex_unlock(&sd_tc_mu);
+    pthread_mutex_lock(&t_pw_mu); cpu_readers += thread_cpu_s(); pthread_mutex_unlock(&t_pw_mu);
+    return NULL;
+}
+
+/* stream_open's part: is the file served, and if not, is it filled?  (Decided before the device's text parser gets a say: a file that
+ * is served is not text for it; one it may take is not written.) */
+static void sd_tc_stream(sd_stream *st)
+{
+    struct stat sb;
+    int rc;
+    if (!sd_tc.dir) return;
+    if (stat(st->path, &sb) != 0 || !S_ISREG(sb.st_mode) || (st->tc_path = skpt_path(sd_tc.dir, st->path)) == NULL) {
+        pthread_mutex_lock(&sd_tc_mu); sd_tc_run.not_cached++; pthread_mutex_unlock(&sd_tc_mu);
+        return;
+    }
+    rc = skpt_open(&st->tcr, st->tc_path, &sb);
+    if (rc == SKPC_OK) {
+        st->serving = 1;
+        st->text_mode = 0;
+        pthread_mutex_lock(&sd_tc_mu); sd_tc_run.served++; pthread_mutex_unlock(&sd_tc_mu);
+        return;
+    }
+    if (rc == SKPC_INVALID) { pthread_mutex_lock(&sd_tc_mu); sd_tc_run.stale++; pthread_mutex_unlock(&sd_tc_mu); }
+    if (sd_tc.ro) return;
+    if (st->text_mode) { pthread_mutex_lock(&sd_tc_mu); sd_tc_run.not_cached++; pthread_mutex_unlock(&sd_tc_mu); return; }
+    {
+        sd_tcw *w = (sd_tcw *)calloc(1, sizeof *w);
+        if (w && (w->w = skpt_begin(st->tc_path, &sb)) != NULL) {
+            pthread_mutex_init(&w->mu, NULL);
+            pthread_cond_init(&w->cv, NULL);
+            if (pthread_create(&w->th, NULL, sd_tcw_thread, w) == 0) { st->tcw = w; return; }
+            pthread_mutex_destroy(&w->mu);
+            pthread_cond_destroy(&w->cv);
+            skpc_end(w->w, 0, 0, 0);
+        }
+        free(w);
+        pthread_mutex_lock(&sd_tc_mu); sd_tc_run.not_cached++; pthread_mutex_unlock(&sd_tc_mu);
+    }
+}
+
+/* the run's switch: DIR from the command line or SK_TARGET_CACHE; a directory that cannot be used is said once and the run goes on
+ * uncached */
+static void sd_tc_open(const char *dir, FILE *err)
+{
+    const char *m = getenv("SK_TARGET_CACHE_MODE");
+    struct stat sb;
+    memset(&sd_tc_run, 0, sizeof sd_tc_run);
+    sd_tc.dir = NULL;
+    if (!dir || !*dir) dir = getenv("SK_TARGET_CACHE");
+    if (!dir || !*dir) return;
+    sd_tc.ro = m && !strcmp(m, "ro");
+    if (stat(dir, &sb) != 0 || !S_ISDIR(sb.st_mode) || access(dir, sd_tc.ro ? R_OK | X_OK : R_OK | W_OK | X_OK) != 0) {
+        fprintf(err, "strain_detect: the target cache directory %s cannot be used (%s): going on without it\n", dir, sb.st_mode && !S_ISDIR(sb.st_mode) ? "not a directory" : strerror(errno));
+        return;
+    }
+    sd_tc.dir = strdup(dir);
+}
+
+static void sd_tc_close(FILE *err)
+{
+    if (sd_tc.dir && (getenv("SK_SD_TIMING") || getenv("SK_TIMING")))
+        fprintf(err, "target cache: %s: %llu files served, %llu written, %llu stale, %llu not cached; checksums %.2f s, reading %.2f s, writing %.2f s, "
+                     "waiting for the device pack %.2f s\n", sd_tc.dir, (unsigned long long)sd_tc_run.served, (unsigned long long)sd_tc_run.written,
+                (unsigned long long)sd_tc_run.stale, (unsigned long long)sd_tc_run.not_cached, sd_tc_run.t_sum, sd_tc_run.t_read, sd_tc_run.t_write, sd_tc_run.t_pack);
+    pthread_mutex_lock(&sd_tc_mu);
+    sd_tc_all.served += sd_tc_run.served; sd_tc_all.written += sd_tc_run.written; sd_tc_all.stale += sd_tc_run.stale; sd_tc_all.not_cached += sd_tc_run.not_cached;
+    memset(&sd_tc_run, 0, sizeof sd_tc_run);
+    pthread_mutex_unlock(&sd_tc_mu);
+    free(sd_tc.dir);
+    sd_tc.dir = NULL;
+}
+
 /* how many threads may inflate each of the `nfiles` files read at the same time: SK_GZ_THREADS, or the host
  * thread budget (SK_THREADS, default min(16, usable CPUs)) shared out -- used when it leaves three or more per
  * file, below that the one helper thread of sk_gzpipe.h does as well */
@@ -756,7 +1048,13 @@ static int stream_open(sd_stream *st, const char *path, int gz_threads)
     gzbuffer(st->g, 1 << 18);
     pthread_mutex_init(&st->mu, NULL);
     pthread_cond_init(&st->cv, NULL);
-    if (pthread_create(&st->th, NULL, sd_decode_thread, st)) { gzclose(st->g); st->g = NULL; return SK_E_NOMEM; }
+    sd_tc_stream(st);
+    if (pthread_create(&st->th, NULL, st->serving ? sd_serve_thread : sd_decode_thread, st)) {
+        if (st->serving) skpc_close(&st->tcr);
+        if (st->tcw) { st->split_failed = 1; sd_tc_finish(st); }
+        free(st->tc_path);
+        gzclose(st->g); st->g = NULL; return SK_E_NOMEM;
+    }
     st->started = 1;
     return SK_OK;
 }
@@ -826,6 +1124,9 @@ static void stream_close(sd_stream *st)
         pthread_mutex_destroy(&st->pmu);
         pthread_cond_destroy(&st->pcv);
     }
+    sd_tc_finish(st);                                   /* (before the batches go: the writer waits for their packs) */
+    if (st->serving) skpc_close(&st->tcr);
+    free(st->tc_path);
     for (i = 0; i < SD_MAX_DEV; i++) {
         sd_batch_put(i, st->bat[0][i]);                 /* (waits for an upload in flight before the chunks go) */
         sd_batch_put(i, st->bat[1][i]);
@@ -1266,6 +1567,7 @@ static void sd_prefetch(sd_stream *st)
         if (n->text) ok = sk_batch_fill_text(*b, n->buf, n->tlen + (uint64_t)n->tla, n->t_eof) == SK_OK;     /* (a piece of text: upload + parse, enqueued) */
         else
         ok = (n->packed ? sk_batch_fill_packed(*b, n->buf, n->blen, n->pstart, n->np) : sk_batch_fill(*b, n->buf, n->blen, n->pstart, n->np)) == SK_OK;
+        if (ok && d == 0) sd_tc_hand(st, n, *b);           /* (the target cache: packed behind this upload) */
     }
     if (ok) st->pre = n;                                   /* (all devices or none: a chunk that is not everywhere goes up again) */
     t_fill += now_s() - t0;
@@ -1456,8 +1758,10 @@ static int sd_tally_chunk(sd_prog *p, uint32_t ns, sk_batch **batches, sd_pool *
         int d;
         pthread_mutex_lock(&sd_dev_mu);
         rc = SK_OK;
-        for (d = 0; d < sd_dev.n && !uploaded && rc == SK_OK; d++)  /* (asynchronous copies from page-locked memory: the devices' uploads overlap) */
+        for (d = 0; d < sd_dev.n && !uploaded && rc == SK_OK; d++) { /* (asynchronous copies from page-locked memory: the devices' uploads overlap) */
             rc = c->packed ? sk_batch_fill_packed(batches[d], c->buf, c->blen, c->pstart, c->np) : sk_batch_fill(batches[d], c->buf, c->blen, c->pstart, c->np);
+            if (rc == SK_OK && d == 0) sd_tc_hand(st, c, batches[0]);
+        }
         t1 = now_s(); t_fill += t1 - t0; t0 = t1;
         if (rc == SK_OK && !launched) rc = sd_launch(p, ns, batches);
         if (rc == SK_OK) {
@@ -1468,6 +1772,7 @@ static int sd_tally_chunk(sd_prog *p, uint32_t ns, sk_batch **batches, sd_pool *
         if (rc != SK_OK) return rc;
         t1 = now_s(); t_launch += t1 - t0; t0 = t1;
     }
+    else sd_tc_hand(st, c, NULL);                                /* (nothing went up: the target cache still wants its records' lengths) */
     lanes_post(job_new(SD_JOB_TALLY, c, NULL));                  /* sort + spread, strain by strain, behind the main thread's back */
     t_post += now_s() - t0;
     return SK_OK;
@@ -1520,6 +1825,7 @@ static int stream_fill(sd_stream *st, sd_prog *p, uint32_t ns, sk_batch *batch, 
         st->qn--;
         pthread_cond_broadcast(&st->cv);
         pthread_mutex_unlock(&st->mu);
+        if (c->cache_err) { chunk_free(c); st->cache_failed = 1; st->eof = 1; return SK_E_CACHE; }
         {
             const double t0 = now_s();
             int uploaded = st->pre == c;                   /* its bytes went up while the chunk before it was scanned */
@@ -1778,6 +2084,13 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
     if (got == SK_E_SPLIT) {
         fprintf(err, "strain_detect: %s could not be cut at record boundaries for parsing on several threads: nothing from it is reported; "
                      "run again with SK_NO_SPLIT=1\n", A.split_failed || !f2 ? f1 : f2);
+        goto done;
+    }
+    if (got == SK_E_CACHE) {
+        const sd_stream *bad = A.cache_failed ? &A : &B;
+        fprintf(err, "strain_detect: the target cache file %s of %s failed its checks (a checksum, or lengths that do not give its stream): "
+                     "hits of earlier chunks may be out already, the run fails; remove the file and run again\n", bad->tc_path ? bad->tc_path : "?", bad->path);
+        status = SK_E_CACHE;
         goto done;
     }
     if (got < 0) {
@@ -2303,7 +2616,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     const char *a = NULL, *r = NULL, *b = NULL, *b2 = NULL, *B = NULL, *tt = NULL, *g = NULL, *o = NULL, *S = NULL, *env;
     int c, j, mode = SD_SE, status = 1, device = 0, n_S = 0, want_cov = 0;
     skzo_pool zpool;
-    const char *cov_file = NULL;
+    const char *cov_file = NULL, *tc_dir = NULL;
     long long cov_min = 1;
     double t_begin = 0;
     sd_prog *p = NULL;
@@ -2329,6 +2642,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             continue;
         }
         if (!strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { cov_min = atoll(argv[++c]); continue; }
+        if (!strcmp(argv[c], "--target-cache") && c + 1 < argc) { tc_dir = argv[++c]; continue; }       /* (extension: the target cache, see sd_tc) */
+        if (!strncmp(argv[c], "--target-cache=", 15)) { tc_dir = argv[c] + 15; continue; }
         argv[j++] = argv[c];
     }
     argc = j;
@@ -2386,6 +2701,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     if ((env = getenv("SK_SD_GROUP")) != NULL && atoi(env) >= 1 && atoi(env) <= SK_UNION_MAX) sd_group = (uint32_t)atoi(env);
     memset(sd_dev.ctx, 0, sizeof sd_dev.ctx);
     t_begin = now_s();
+    sd_tc_open(tc_dir, err);
     n_text_taken = n_text_declined = 0;                  /* (per run: the library entry points may be called again in one process) */
     {
         const long ncpu = sk_cpu_budget();
@@ -2460,7 +2776,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     if (getenv("SK_SD_TIMING") && sd_dev.n > 1) fprintf(err, "strain_detect timing: %u strains on %d devices, one decode pipeline\n", ns, sd_dev.n);
     for (s = 0; want_cov && s < ns; s++)
         if (sd_coverage_open(&p[s], S ? NULL : cov_file, cov_min)) goto done;
-    if (sd_run(p, ns, B, b, b2, mode, out, err)) goto done;
+    if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
     for (s = 0; s < ns; s++)
         if (sd_coverage_write(&p[s])) goto done;
     status = 0;
@@ -2522,6 +2838,7 @@ done:
     if (getenv("SK_SD_TIMING") && t_pw_parse > 0)
         fprintf(err, "strain_detect timing: parser threads, summed: parsing %.2f s, waiting for a segment %.2f s, for their turn to hand chunks on %.2f s, for room in the queue %.2f s\n",
                 t_pw_parse, t_pw_seg, t_pw_turn, t_pw_push);
+    sd_tc_close(err);
     sd_pin_close();
     {   /* closing a strain = finishing its gz output, freeing its device context and tables: strain by strain on threads */
         sd_pool cp;

@@ -47,6 +47,16 @@ typedef struct sk_batch_hook {
 } sk_batch_hook;
 int  sk_batch_hook_(sk_batch *b, uint64_t stream_bytes, uint64_t rec_words, sk_batch_hook *out);
 void sk_batch_contents_(sk_batch *b, uint64_t nbytes, uint32_t nrec);
+/* ... and for the device pack of a batch's resident bytes (sk_packdev.hip: sk_batch_pack_home).  want_room != 0: SK_E_STATE unless the
+ * batch holds bytes that came up as bytes; d_pack (batch-owned, 8-byte aligned) holds sk_packed_bytes(nbytes), d_odd one u32, `home` is
+ * the event of the copy home.  The batch's stream is not waited for. */
+typedef struct sk_batch_pack_hook {
+    sk_ctx *owner;
+    void *stream, *home;               /* hipStream_t, hipEvent_t */
+    const void *d_stream; uint64_t nbytes;
+    void *d_pack; uint32_t *d_odd;
+} sk_batch_pack_hook;
+int  sk_batch_pack_hook_(sk_batch *b, int want_room, sk_batch_pack_hook *out);
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,45 @@ extern "C" int sk_scan_pinned_pack_many(sk_ctx *const *ctxs, uint32_t nctx, cons
     return rc;
 }
 
+// strain_detect's target cache: the bytes a batch holds, packed where they lie.  Enqueued on the batch's OWN stream, so behind the
+// upload of the current contents and behind its `ready` event -- the tallies wait for that event only, never for this -- and ahead of
+// the next fill, which is what may overwrite the bytes.  The kernel is sk_pack_chunks as above: whole 16-byte chunks below nbytes by
+// one load, the chunk the stream's end cuts byte by byte, so neither the batch's 16 bytes of slack nor what an earlier, longer fill
+// left beyond nbytes is read.  Into the batch's own buffer (it grows with the batch's stream buffer), then sk_packed_bytes(nbytes)
+// bytes and the flag (one u32: non-zero = odd) home; they are there once sk_batch_pack_wait has returned.
+extern "C" int sk_batch_pack_home(sk_batch *b, void *pinned_packed_out, uint32_t *pinned_odd_out)
+{
+    if (!b || !pinned_packed_out || !pinned_odd_out) return SK_E_ARG;
+    sk_batch_pack_hook hk;
+    const int rc = sk_batch_pack_hook_(b, 1, &hk);
+    if (rc != SK_OK) return rc;
+    sk_ctx *const ctx = hk.owner;
+    hipStream_t st = (hipStream_t)hk.stream;
+    const uint64_t nch = (hk.nbytes + 15u) >> 4, npair = (nch + 1u) >> 1;
+    uint64_t blocks = (npair + PK_THREADS - 1u) / PK_THREADS;
+    if (blocks > 2048u) blocks = 2048u;
+    PK_HIP(hipMemsetAsync(hk.d_odd, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(sk_pack_chunks, dim3((uint32_t)blocks), dim3(PK_THREADS), 0, st, (const uint8_t *)hk.d_stream, hk.nbytes,
+                       (uint32_t *)hk.d_pack, (uint16_t *)((uint8_t *)hk.d_pack + nch * 4u), hk.d_odd);
+    PK_HIP(hipGetLastError());
+    PK_HIP(hipMemcpyAsync(pinned_packed_out, hk.d_pack, nch * 6u, hipMemcpyDeviceToHost, st));
+    PK_HIP(hipMemcpyAsync(pinned_odd_out, hk.d_odd, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PK_HIP(hipEventRecord((hipEvent_t)hk.home, st));
+    return SK_OK;
+}
+
+extern "C" int sk_batch_pack_wait(sk_batch *b)
+{
+    if (!b) return SK_E_ARG;
+    sk_batch_pack_hook hk;
+    const int rc = sk_batch_pack_hook_(b, 0, &hk);
+    if (rc != SK_OK) return rc;
+    sk_ctx *const ctx = hk.owner;
+    if (!hk.home) return sk_fail_(ctx, SK_E_STATE, "no pack was asked of this batch");
+    PK_HIP(hipEventSynchronize((hipEvent_t)hk.home));
+    return SK_OK;
+}
+
 extern "C" int sk_pack_ticket_wait(sk_ctx *ctx, uint64_t ticket)
 {
     if (!ctx) return SK_E_ARG;

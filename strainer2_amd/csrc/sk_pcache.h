@@ -18,7 +18,8 @@
  *   payload}, the payload, zero padding to a multiple of 8.  A packed payload is sk_pack_stream's layout for the stream length (the
  *   code words, then the masks); a chunk with a byte for the byte-string kernel (IUPAC, U, CR: *odd) is kept as its bytes.
  *   The file's size is 128 + 32 * segments + payload bytes, exactly: anything else is not a cache file.
- * Version 1 holds chunks for the COUNT scan only; strain_detect's targets need every record's start (a later version).
+ * Version 1 holds chunks for the COUNT scan only; strain_detect's targets need every record's length: version 2, in files of their own
+ * (.skt), at the end of this header.  The version-1 format, its reader and its writer are as they were.
  * A file is written under a temporary name (<name>.tmp.<pid>.<n>) and renamed once its item was parsed to the end; an item that fails
  * leaves nothing, and the temporary of a process that was killed is removed by the next fill of the same item. */
 #ifndef SK_PCACHE_H
@@ -346,5 +347,157 @@ static inline int skpc_end(skpc_writer *w, int commit, uint64_t records, uint64_
     pthread_mutex_destroy(&w->mu);
     free(w->tmp); free(w->final); free(w);
     return ok;
+}
+
+/* ---- version 2: strain_detect's targets (DIR/<basename>.<the same 16 hex digits>.skt) ------------------------------------------
+ * The same header (version 2; the chunk cap is the largest stream length that was written, known at the end), other segments: one
+ * segment is one chunk of sk_host_sd.c as its consumer sees it -- WHOLE records, and the length of EVERY record, the ones shorter
+ * than k included (the replay of the reference's read-after-read bookkeeping needs them).
+ *   per segment: 64 bytes { 0 u32 kind (1 packed, 2 bytes)   4 u32 flags (bit 0: the file's last chunk)   8 u64 stream length
+ *       16 u64 payload length   24 u64 skpc_sum64 of the payload   32 u32 records   36 u32 records of k bases or more
+ *       40 u32 how the parser ended (last chunk only)   44 zero   48 u64 the ending's length (last chunk only)   56 zero },
+ *   the payload -- the stream (packed, or its bytes), zero padding to a multiple of 8, then one little-endian u32 length per record
+ *   -- and zero padding to a multiple of 8.  ONE sum covers stream, padding and lengths.
+ * The stream is what sd_on_record lays down: every record of k bases or more, in order, its bases and a '\n'; so the lengths must
+ * reproduce the segment's second record count and its stream length exactly (skpt_lengths), a record of 2^32 bases or more cannot be
+ * written, and a segment whose records are all shorter than k has an EMPTY stream (version 1 forbids that; here it is the rule for
+ * such a chunk).  The last segment, and only it, carries the last flag; a file without it was never committed.
+ * A version-1 reader rejects a .skt and this reader a .skp by the header's version field. */
+#define SKPT_VERSION     2u
+#define SKPT_SEG_HEADER  64u
+#define SKPT_LAST        1u
+
+typedef struct { uint32_t kind, flags, nrec, np, end_kind; uint64_t stream_len, payload_len, sum, end_len, payload_off; } skpt_seg;
+
+static inline uint64_t skpt_stream_part(uint32_t kind, uint64_t stream_len) { return skpc_pad8(kind == SKPC_PACKED ? skpc_packed_bytes(stream_len) : stream_len); }
+static inline uint64_t skpt_payload_len(uint32_t kind, uint64_t stream_len, uint32_t nrec) { return skpt_stream_part(kind, stream_len) + 4u * (uint64_t)nrec; }
+
+static inline char *skpt_path(const char *dir, const char *item)
+{
+    char *out = skpc_path(dir, item);
+    if (out) out[strlen(out) - 1] = 't';
+    return out;
+}
+
+/* skpc_open for a target's file: SKPC_OK, SKPC_MISS or SKPC_INVALID (another version -- a .skp under this name --, another k,
+ * source size or mtime, a size that is not what the header implies) */
+static inline int skpt_open(skpc_reader *r, const char *path, const struct stat *src)
+{
+    uint8_t hb[SKPC_HEADER];
+    struct stat st;
+    memset(r, 0, sizeof *r);
+    r->fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (r->fd < 0) return errno == ENOENT ? SKPC_MISS : SKPC_INVALID;
+    if (fstat(r->fd, &st) != 0 || !S_ISREG(st.st_mode) || (uint64_t)st.st_size < SKPC_HEADER || skpc_read_all(r->fd, hb, SKPC_HEADER, 0) != 0 ||
+        skpc_header_get(hb, &r->h) != 0 || r->h.version != SKPT_VERSION || r->h.k != SKPC_K ||
+        r->h.src_size != (uint64_t)src->st_size || r->h.src_mtime != skpc_mtime_ns(src) || r->h.segments == 0 ||
+        r->h.segments > ((uint64_t)st.st_size - SKPC_HEADER) / SKPT_SEG_HEADER ||
+        (uint64_t)st.st_size != SKPC_HEADER + r->h.segments * SKPT_SEG_HEADER + r->h.payload_bytes) {
+        close(r->fd);
+        r->fd = -1;
+        return SKPC_INVALID;
+    }
+    r->size = (uint64_t)st.st_size;
+    r->off = SKPC_HEADER;
+    return SKPC_OK;
+}
+
+/* the next segment's header: SKPC_OK, SKPC_MISS after the last one, SKPC_CORRUPT for a header that cannot be, SKPC_IO */
+static inline int skpt_next(skpc_reader *r, skpt_seg *s)
+{
+    uint8_t sb[SKPT_SEG_HEADER];
+    if (r->seg >= r->h.segments) return r->off == r->size ? SKPC_MISS : SKPC_CORRUPT;
+    if (r->off + SKPT_SEG_HEADER > r->size) return SKPC_CORRUPT;
+    if (skpc_read_all(r->fd, sb, SKPT_SEG_HEADER, r->off) != 0) return SKPC_IO;
+    s->kind = skpc_le32(sb); s->flags = skpc_le32(sb + 4); s->stream_len = skpc_le64(sb + 8); s->payload_len = skpc_le64(sb + 16); s->sum = skpc_le64(sb + 24);
+    s->nrec = skpc_le32(sb + 32); s->np = skpc_le32(sb + 36); s->end_kind = skpc_le32(sb + 40); s->end_len = skpc_le64(sb + 48);
+    s->payload_off = r->off + SKPT_SEG_HEADER;
+    if ((s->kind != SKPC_PACKED && s->kind != SKPC_BYTES) || (s->flags & ~SKPT_LAST) || skpc_le32(sb + 44) != 0 || skpc_le64(sb + 56) != 0 ||
+        s->stream_len > r->h.chunk_cap || s->stream_len > 0xFFFFFFF0ull || s->np > s->nrec || (s->np == 0) != (s->stream_len == 0) ||
+        ((s->flags & SKPT_LAST) != 0) != (r->seg + 1 == r->h.segments) || (!(s->flags & SKPT_LAST) && (s->end_kind || s->end_len)) ||
+        s->payload_len != skpt_payload_len(s->kind, s->stream_len, s->nrec) || skpc_pad8(s->payload_len) > r->size - s->payload_off)
+        return SKPC_CORRUPT;
+    r->off = s->payload_off + skpc_pad8(s->payload_len);
+    r->seg++;
+    return SKPC_OK;
+}
+
+/* the payload into buf (room for payload_len), its sum checked: SKPC_OK, SKPC_IO, SKPC_CORRUPT */
+static inline int skpt_payload(const skpc_reader *r, const skpt_seg *s, void *buf, double *t_sum, double *t_read)
+{
+    double t0 = skpc_now(), t1;
+    uint64_t sum;
+    if (s->payload_len && skpc_read_all(r->fd, buf, s->payload_len, s->payload_off) != 0) return SKPC_IO;
+    t1 = skpc_now();
+    sum = skpc_sum64(buf, s->payload_len);
+    if (t_read) *t_read += t1 - t0;
+    if (t_sum) *t_sum += skpc_now() - t1;
+    return sum == s->sum ? SKPC_OK : SKPC_CORRUPT;
+}
+
+/* where the segment's length table lies in its payload */
+static inline const uint8_t *skpt_table(const skpt_seg *s, const void *payload) { return (const uint8_t *)payload + skpt_stream_part(s->kind, s->stream_len); }
+
+/* the structure behind a sum that held: the lengths must reproduce the stream -- every record of k bases or more takes its length
+ * and a '\n' -- and the count of such records.  SKPC_OK or SKPC_CORRUPT. */
+static inline int skpt_lengths(const skpt_seg *s, const void *payload)
+{
+    const uint8_t *t = skpt_table(s, payload);
+    uint64_t at = 0;
+    uint32_t i, np = 0;
+    for (i = 0; i < s->nrec; i++) {
+        const uint32_t l = skpc_le32(t + 4u * (size_t)i);
+        if (l >= SKPC_K) { at += (uint64_t)l + 1u; np++; }
+    }
+    return at == s->stream_len && np == s->np ? SKPC_OK : SKPC_CORRUPT;
+}
+
+/* the writer: skpc_begin's temporary file, sweep and rename, skpc_end's commit; the header says version 2 and its chunk cap grows
+ * with what is appended */
+static inline skpc_writer *skpt_begin(const char *final_path, const struct stat *src)
+{
+    skpc_writer *w = skpc_begin(final_path, src, 0);
+    if (w) w->h.version = SKPT_VERSION;
+    return w;
+}
+
+/* one chunk: `payload` is the stream part (packed or bytes, padded to 8 with zeros) with the nrec u32 lengths behind it, in one
+ * piece of skpt_payload_len(kind, stream_len, nrec) bytes.  From one thread per file, in the file's order. */
+static inline void skpt_append(skpc_writer *w, uint32_t kind, uint64_t stream_len, uint32_t nrec, uint32_t np, int last, uint32_t end_kind, uint64_t end_len,
+                               const void *payload)
+{
+    static const uint8_t pad[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint64_t plen = skpt_payload_len(kind, stream_len, nrec), padded = skpc_pad8(plen);
+    uint8_t sb[SKPT_SEG_HEADER];
+    struct iovec iov[3];
+    double t0 = skpc_now(), t1;
+    uint64_t done = 0, total = SKPT_SEG_HEADER + padded;
+    int niov = 3, first = 0;
+    memset(sb, 0, sizeof sb);
+    skpc_put32(sb, kind); skpc_put32(sb + 4, last ? SKPT_LAST : 0u); skpc_put64(sb + 8, stream_len); skpc_put64(sb + 16, plen);
+    skpc_put64(sb + 24, skpc_sum64(payload, plen));
+    skpc_put32(sb + 32, nrec); skpc_put32(sb + 36, np); skpc_put32(sb + 40, last ? end_kind : 0u); skpc_put64(sb + 48, last ? end_len : 0u);
+    t1 = skpc_now();
+    iov[0].iov_base = sb; iov[0].iov_len = sizeof sb;
+    iov[1].iov_base = (void *)(uintptr_t)payload; iov[1].iov_len = (size_t)plen;
+    iov[2].iov_base = (void *)(uintptr_t)pad; iov[2].iov_len = (size_t)(padded - plen);
+    pthread_mutex_lock(&w->mu);
+    w->t_sum += t1 - t0;
+    while (!w->err && done < total) {
+        const ssize_t r = writev(w->fd, iov + first, niov - first);
+        uint64_t got;
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) { w->err = 1; break; }
+        done += (uint64_t)r;
+        for (got = (uint64_t)r; first < niov && got; ) {
+            if (got >= iov[first].iov_len) { got -= iov[first].iov_len; first++; }
+            else { iov[first].iov_base = (uint8_t *)iov[first].iov_base + got; iov[first].iov_len -= (size_t)got; got = 0; }
+        }
+    }
+    w->h.segments++;
+    w->h.payload_bytes += padded;
+    if (stream_len > w->h.chunk_cap) w->h.chunk_cap = stream_len;
+    w->t_write += skpc_now() - t1;
+    pthread_mutex_unlock(&w->mu);
 }
 #endif

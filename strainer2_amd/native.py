@@ -36,6 +36,7 @@ SK_KEY_NONE = 0xFFFFFFFFFFFFFFFF
 SK_OK = 0
 SK_E_NODEVICE = -1
 SK_E_OPEN = -5
+SK_E_STATE = -7
 SK_E_SPLIT = -9
 SK_E_PLAN = -10
 SK_E_CACHE = -11
@@ -61,6 +62,7 @@ ABI_SYMBOLS = [
     "sk_union_members", "sk_union_rows", "sk_union_count_enable", "sk_union_context", "sk_union_counts_fold",
     "skh_kmer_scrub_count_multi_main",
     "sk_pack_device", "sk_scan_pinned_pack_many", "sk_pack_ticket_wait", "sk_pack_release", "skh_pack_cache_set", "skh_pack_cache_stats",
+    "sk_batch_pack_home", "sk_batch_pack_wait", "skh_target_cache_stats",
 ]
 
 
@@ -107,6 +109,9 @@ lib.sk_pack_release.argtypes = [C.c_void_p]
 lib.sk_pack_release.restype = None
 lib.skh_pack_cache_set.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
 lib.skh_pack_cache_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4 + [C.c_int]
+lib.skh_target_cache_stats.argtypes = [C.POINTER(C.c_uint64)] * 4 + [C.c_int]
+lib.sk_batch_pack_home.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sk_batch_pack_wait.argtypes = [C.c_void_p]
 lib.sk_tally_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
 lib.sk_sync.argtypes = [C.c_void_p]
@@ -632,6 +637,13 @@ class KmerContext:
         self.close()
 
 
+def target_cache_stats(reset=False):
+    """skh_target_cache_stats: (served, written, stale, not cached) targets of strain_detect runs in this process"""
+    v = [C.c_uint64(0) for _ in range(4)]
+    lib.skh_target_cache_stats(*[C.byref(x) for x in v], int(reset))
+    return tuple(int(x.value) for x in v)
+
+
 class TallyBatch:
     """A batch of records resident on a context's device (sk_batch_*), to be tallied against one or more tables."""
 
@@ -674,6 +686,29 @@ class TallyBatch:
         starts = np.ctypeslib.as_array(rs, shape=(int(info.nrecords),)).copy() if ok else np.zeros(0, dtype=np.uint32)
         self.nbytes, self.nrec = (int(info.stream_bytes), int(info.nrecords)) if ok else (0, 0)
         return info, starts
+
+    def pack_home_begin(self, out, flag):
+        """sk_batch_pack_home alone: the device pack of the bytes this batch holds is enqueued behind their upload; `out` (a pinned
+        uint8 array of at least sk_packed_bytes(nbytes)) and `flag` (a pinned uint32 array) hold the result once pack_home_wait returned"""
+        self._ctx._ck(lib.sk_batch_pack_home(self._h, out.ctypes.data, flag.ctypes.data))
+
+    def pack_home_wait(self):
+        self._ctx._ck(lib.sk_batch_pack_wait(self._h))
+
+    def pack_home(self, guard=0):
+        """the bytes this batch holds, packed on the device into sk_pack_stream's form: (packed bytes as a uint8 array, odd).
+        guard > 0: that many bytes behind the packed form are returned as well, filled with 0xA5 before the call (tests: the
+        copy home must leave them alone)"""
+        n = int(lib.sk_packed_bytes(self.nbytes))
+        buf = self._ctx.pinned_alloc(n + guard + 16)
+        try:
+            buf[:] = 0xA5
+            flag = buf[(n + guard + 7) // 8 * 8:][:4].view(np.uint32)
+            self.pack_home_begin(buf, flag)
+            self.pack_home_wait()
+            return buf[: n + guard].copy(), bool(flag[0])
+        finally:
+            self._ctx.pinned_free(buf)
 
     def close(self):
         if getattr(self, "_h", None):
