@@ -608,6 +608,63 @@ int sk_distinct_count(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample,
  * as the script's global dictionary has it.  Synchronous. */
 int sk_first_seen_count(sk_ctx *ctx, const uint32_t *id, const uint32_t *sample, uint64_t n, uint32_t nids, uint32_t nsamples,
                         uint64_t *out_unique, uint64_t *out_total);
+/* The same two numbers per strain WITHOUT a hit list (new): a coverage accumulator on the device, fed by the results a TALLY launch
+ * leaves in HBM.  What it computes is what scripts/coverage_depth.py:62-129 computes from the lines src/strain_detect.c:443-626
+ * prints, under this rule: in a run of read pairs in which every record, of PE1 and of PE2, has at least k bases, the reference
+ * prints one line per informative hit of either mate, all lines of a pair carry total_kmer = h1 + h2 (the "all hits" tallies of
+ * the two mates; h2 = 0 for single reads), and the script counts a line iff h1 + h2 > min_kmer_hits.  So per member (strain) and
+ * target: total = log entries of pairs that pass ("depth"), unique = distinct rows among them ("coverage").  A "record" below is a
+ * record of the batch (sk_batch_fill's rec_start); runs with a record shorter than k (it carries the previous read's tallies and
+ * rows in the reference) are the caller's to replay on the host and hand in through sk_covacc_add_rows.
+ *   sk_covacc_create: nmembers (1..4096) strains with nrows[m] table rows each; one u32 counter per row and member, zeroed, on ctx's
+ *   device.  Errors of every call are reported through ctx (sk_last_error).  One caller at a time.
+ *   sk_tally_collect_counts / sk_union_tally_collect_counts: collect a launch WITHOUT copying its sparse records or its hit log
+ *   home -- only the counters cross the link (a union's launch sends its first 16384 records and log entries home with its
+ *   counters; sk_union_tally_launch_ex with results_stay != 0 is the launch that does not).  The results stay addressable on the
+ *   device until the next launch on that context / union, and the batch must stay filled as it is until then (its record starts
+ *   are part of them).  sk_tally_fetch_held / sk_union_tally_fetch_held copy them home
+ *   after all, in sk_tally_collect_sparse's / sk_union_tally_collect's form (the host's fallback).  The existing collect calls and
+ *   what they return are unchanged.
+ *   sk_covacc_add: fold the held results of ctx's launch (u NULL; they go to member `member0`) or of u's launch (the union's member
+ *   i goes to member0 + i).  The run: npairs pairs, pair j's PE1 read is record a0 + j * astep of the launch.  mate NULL: single
+ *   reads.  mate->held == 0: pair j's mate is record b0 + j * bstep of the SAME launch (interleaved pairs: a0, b0 = a0 + 1, both
+ *   steps 2).  mate->held != 0: it is record b0 + j * bstep of the launch saved by sk_covacc_hold.  SK_E_STATE if the launch's hit
+ *   log overflowed (launch again with more room first), SK_E_ARG for a run that leaves the batch.  Synchronous.
+ *   sk_covacc_hold: copy the held results of a launch (device to device) into buffers the accumulator owns, so that the launch's
+ *   context, union and batch may go on -- two-file pairs: hold PE1's launch, add PE2's with mate->held.  One launch is held at a time,
+ *   and the add that uses it must name the same ctx / u / member0 kind of launch (same number of members).
+ *   sk_covacc_add_rows: n hits on these rows of `member`, already filtered by the caller (host-replayed runs).
+ *   sk_covacc_finish_target: out_unique[m] = rows of member m with a non-zero counter, out_total[m] = their sum; every counter is
+ *   zero again afterwards (a second call returns zeros).  sk_covacc_rows: member's counters as they stand (tests). */
+typedef struct sk_covacc sk_covacc;
+typedef struct sk_covacc_mate { int held; uint32_t b0, bstep; } sk_covacc_mate;
+int  sk_covacc_create(sk_ctx *ctx, uint32_t nmembers, const uint32_t *nrows, int64_t min_kmer_hits, sk_covacc **out);
+void sk_covacc_destroy(sk_covacc *a);
+int  sk_tally_collect_counts(sk_ctx *ctx, uint64_t *n, uint64_t *out_nhits);
+int  sk_tally_fetch_held(sk_ctx *ctx, sk_tally_rec *out, uint64_t cap, sk_hit *out_hits);
+int  sk_union_tally_launch_ex(sk_union *u, const sk_batch *b, uint64_t hits_cap, int results_stay);
+int  sk_union_tally_collect_counts(sk_union *u, uint64_t *n, uint64_t *out_nhits);
+int  sk_union_tally_fetch_held(sk_union *u, sk_tally_rec *out, uint64_t cap, sk_hit *out_hits);
+int  sk_covacc_hold(sk_covacc *a, sk_ctx *ctx_or_null, sk_union *u_or_null);
+int  sk_covacc_add(sk_covacc *a, sk_ctx *ctx_or_null, sk_union *u_or_null, uint32_t member0,
+                   uint32_t a0, uint32_t astep, uint32_t npairs, const sk_covacc_mate *mate);
+int  sk_covacc_add_rows(sk_covacc *a, uint32_t member, const uint32_t *rows, uint64_t n);
+/* The few results the host still needs of a launch it folds on the device: sk_covacc_pick copies home, in the collect calls' form,
+ * the sparse records and log entries of record 0 (first != 0) and of the last ntail records of the held launch of ctx / u
+ * (from_hold != 0: of the launch sk_covacc_hold copied) -- the tallies and rows a run's last pair leaves to the read after it,
+ * and a record whose mate sits in another batch.  *n / *out_nhits are what matched; more than cap / hits_cap: nothing was copied,
+ * pick again with room.  sk_covacc_fetch_hold brings the whole launch last held home, in the same form and with the same rule
+ * (a held launch whose mate's launch turns out not to be foldable).  An add that finds a log entry naming no row of its member
+ * returns SK_E_STATE after the other entries were counted: the target's counters are then of no use (finish_target clears them). */
+int  sk_covacc_pick(sk_covacc *a, sk_ctx *ctx_or_null, sk_union *u_or_null, int from_hold, int first, uint32_t ntail,
+                    sk_tally_rec *out, uint64_t cap, uint64_t *n, sk_hit *out_hits, uint64_t hits_cap, uint64_t *out_nhits);
+int  sk_covacc_fetch_hold(sk_covacc *a, sk_tally_rec *out, uint64_t cap, uint64_t *n, sk_hit *out_hits, uint64_t hits_cap, uint64_t *out_nhits);
+/* strain_detect --coverage-only, process-wide like skh_target_cache_stats: runs (chunks of a target) folded on the device, runs
+ * replayed on the host (a read shorter than k, a missing mate, pairs across two chunks or unaligned chunks of two files), and
+ * targets counted by the host accumulator (two targets of the run share a basename). */
+void skh_coverage_only_stats(uint64_t *runs_on_device, uint64_t *runs_replayed, uint64_t *targets_host_accumulated, int reset);
+int  sk_covacc_finish_target(sk_covacc *a, uint64_t *out_unique /* nmembers */, uint64_t *out_total /* nmembers */);
+int  sk_covacc_rows(sk_covacc *a, uint32_t member, uint32_t *out /* nrows[member] */);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
  * same stdout bytes and exit status. */
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err);

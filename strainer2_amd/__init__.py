@@ -11,6 +11,7 @@ from .native import (  # noqa: F401
     SKError,
     KmerContext,
     KmerUnion,
+    CoverageAcc,
     Keyset,
     lib,
     library_path,
@@ -19,5 +20,5 @@ from .native import (  # noqa: F401
     run_cli_inprocess,
 )
 
-__all__ = ["SKError", "KmerContext", "KmerUnion", "Keyset", "lib", "library_path", "cli_path", "decode_file",
+__all__ = ["SKError", "KmerContext", "KmerUnion", "CoverageAcc", "Keyset", "lib", "library_path", "cli_path", "decode_file",
            "run_cli_inprocess"]

@@ -1,0 +1,389 @@
+// sk_covacc.hip -- the coverage accumulator: step 4's two numbers per strain and target (reference scripts/coverage_depth.py:62-129)
+// from what a TALLY launch leaves in HBM, without the hit list of step 3 (src/strain_detect.c:443-626) ever being written, for gfx950.
+//
+// The rule (include/strainer_kmer.h has it in full): in a run of read pairs whose records all have k bases or more the reference
+// prints one line per informative hit of either mate, every line of a pair carries h1 + h2 (the mates' "all hits" tallies), and the
+// script counts a line iff h1 + h2 > min_kmer_hits.  A launch leaves the sparse records {record * members + member, all, inf} and
+// the hit log {window end, member << SK_UNION_ROW_BITS | row} on the device; three small kernels fold them:
+//   covacc_scatter   all of every sparse record of the run -> tot[pair * members + member]  (both mates add into one cell)
+//   covacc_hits      every log entry: its record by bisection of the batch's record starts, its pair, and if the pair's total passes
+//                    one atomicAdd on depth[member][row].  Rows are spread over the strain and the add returns nothing: no lane
+//                    waits for it (the one-address returning atomic that cost sk_union_compact 587 us does not occur here).
+//   covacc_scatter   again, storing zeros: tot[] is all zero between folds, so no fold pays a memset of pairs x members.
+// covacc_finish sweeps depth[] once per target: non-zero rows, their sum, and zeros left behind.
+// Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <new>
+#include <vector>
+#include "sk_internal.h"
+
+struct cov_side {                       // one mate's results: a launch's (or the held copy's) records, log and record starts
+    const uint32_t *recs; uint64_t nrecs;
+    const sk_hit *hits; uint64_t nhits;
+    const uint32_t *rec_start; uint32_t nrec;
+    uint32_t r0, step;                  // pair j's read is record r0 + j * step
+};
+
+// record -> pair of the run, or npairs if the record is not one of the run's
+__device__ __forceinline__ uint32_t cov_pair(uint32_t rec, uint32_t r0, uint32_t step, uint32_t npairs)
+{
+    if (rec < r0) return npairs;
+    const uint32_t off = rec - r0, j = off / step;
+    return (off - j * step) == 0u && j < npairs ? j : npairs;
+}
+
+__global__ void covacc_scatter(const uint32_t *__restrict__ recs, uint64_t n, uint32_t ns, uint32_t nrec, uint32_t r0, uint32_t step,
+                               uint32_t npairs, uint32_t *__restrict__ tot, int clear)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t key = recs[3 * i], rec = key / ns, m = key - rec * ns;
+        if (rec >= nrec) continue;
+        const uint32_t j = cov_pair(rec, r0, step, npairs);
+        if (j >= npairs) continue;
+        uint32_t *cell = tot + (size_t)j * ns + m;
+        if (clear) *cell = 0u;
+        else atomicAdd(cell, recs[3 * i + 1]);
+    }
+}
+
+__global__ void covacc_hits(const sk_hit *__restrict__ hits, uint64_t n, const uint32_t *__restrict__ rec_start, uint32_t nrec,
+                            uint32_t ns, int is_union, uint32_t r0, uint32_t step, uint32_t npairs, const uint32_t *__restrict__ tot,
+                            long long min_hits, uint32_t *__restrict__ depth, const uint64_t *__restrict__ row_base,
+                            const uint32_t *__restrict__ nrows, uint32_t *bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const sk_hit e = hits[i];
+        uint32_t lo = 0, hi = nrec;                           // the last record that starts at or before the window's end
+        while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (rec_start[mid] <= e.pos) lo = mid; else hi = mid; }
+        const uint32_t m = is_union ? e.row >> SK_UNION_ROW_BITS : 0u;
+        const uint32_t row = is_union ? e.row & ((1u << SK_UNION_ROW_BITS) - 1u) : e.row;
+        if (rec_start[lo] > e.pos || m >= ns || row >= nrows[m]) { *bad = 1u; continue; }   // (never: an entry no table row stands behind)
+        const uint32_t j = cov_pair(lo, r0, step, npairs);
+        if (j >= npairs) continue;
+        if ((long long)tot[(size_t)j * ns + m] > min_hits) atomicAdd(depth + row_base[m] + row, 1u);
+    }
+}
+
+__global__ void covacc_rows(const uint32_t *__restrict__ rows, uint64_t n, uint32_t nrows, uint32_t *__restrict__ depth)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        if (rows[i] < nrows) atomicAdd(depth + rows[i], 1u);
+}
+
+// the records and log entries of a few records of a launch -- record 0 (first != 0) and the records from tail0 on -- copied out in the
+// launch's own form: what the host needs of a folded run (the tallies and rows its last pair leaves to the read after it, and the
+// record whose mate sits in another batch).  Matches are rare, so the returning atomic that numbers them costs nothing.
+__global__ void covacc_pick(const uint32_t *__restrict__ recs, uint64_t nrecs, const sk_hit *__restrict__ hits, uint64_t nhits,
+                            const uint32_t *__restrict__ rec_start, uint32_t nrec, uint32_t ns, int first, uint32_t tail0,
+                            uint32_t *__restrict__ out_recs, uint32_t cap_r, sk_hit *__restrict__ out_hits, uint32_t cap_h,
+                            uint32_t *__restrict__ cnt)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, n = nrecs + nhits;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (i < nrecs) {
+            const uint32_t rec = recs[3 * i] / ns;
+            if (rec >= nrec || !((first && rec == 0u) || rec >= tail0)) continue;
+            const uint32_t k = atomicAdd(cnt, 1u);
+            if (k < cap_r) { out_recs[3 * k] = recs[3 * i]; out_recs[3 * k + 1] = recs[3 * i + 1]; out_recs[3 * k + 2] = recs[3 * i + 2]; }
+        } else {
+            const sk_hit e = hits[i - nrecs];
+            uint32_t lo = 0, hi = nrec;
+            while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (rec_start[mid] <= e.pos) lo = mid; else hi = mid; }
+            if (rec_start[lo] > e.pos || !((first && lo == 0u) || lo >= tail0)) continue;
+            const uint32_t k = atomicAdd(cnt + 1, 1u);
+            if (k < cap_h) out_hits[k] = e;
+        }
+    }
+}
+
+// blockIdx.y = member: its non-zero rows and their sum, one pair of atomics per workgroup; the rows are zero afterwards
+__global__ void __launch_bounds__(256) covacc_finish(uint32_t *__restrict__ depth, const uint64_t *__restrict__ row_base,
+                                                     const uint32_t *__restrict__ nrows, unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long s_tot[256];
+    __shared__ uint32_t s_unq[256];
+    const uint32_t m = blockIdx.y, n = nrows[m];
+    uint32_t *d = depth + row_base[m];
+    unsigned long long t = 0;
+    uint32_t u = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t v = d[i];
+        if (v) { d[i] = 0u; u++; t += v; }
+    }
+    s_tot[threadIdx.x] = t; s_unq[threadIdx.x] = u;
+    __syncthreads();
+    for (uint32_t w = 128u; w; w >>= 1) {
+        if (threadIdx.x < w) { s_tot[threadIdx.x] += s_tot[threadIdx.x + w]; s_unq[threadIdx.x] += s_unq[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u && s_unq[0]) {
+        atomicAdd(out + 2u * m, (unsigned long long)s_unq[0]);
+        atomicAdd(out + 2u * m + 1u, s_tot[0]);
+    }
+}
+
+struct sk_covacc {
+    sk_ctx *ctx; int device;
+    hipStream_t stream;
+    uint32_t nm; long long min_hits;
+    std::vector<uint32_t> nrows; std::vector<uint64_t> base;
+    uint64_t total_rows; uint32_t max_rows;
+    uint32_t *d_depth; uint64_t *d_base; uint32_t *d_nrows; unsigned long long *d_out;
+    uint32_t *d_tot; size_t tot_cap;                        // all zero between folds
+    uint32_t *d_rows; size_t rows_cap;                      // sk_covacc_add_rows' upload
+    uint32_t *h_bad, *d_bad;                                // page-locked: a log entry that named no row
+    // the held launch (sk_covacc_hold)
+    void *h_recs, *h_hits, *h_rs; size_t h_recs_cap, h_hits_cap, h_rs_cap;
+    bool held; cov_side hs; uint32_t held_members;
+    bool hold_kept;                                         // the buffers still hold the launch last held (sk_covacc_fetch_hold, pick)
+    void *p_recs, *p_hits; uint32_t *p_cnt; size_t p_recs_cap, p_hits_cap, p_cnt_cap;   // sk_covacc_pick's landing area
+};
+
+#define CA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sk_fail_(a->ctx, SK_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+static unsigned cov_grid(uint64_t n) { const uint64_t g = (n + 255u) / 256u; return (unsigned)(g < 1u ? 1u : g > 4096u ? 4096u : g); }
+
+static int cov_room(sk_covacc *a, void **p, size_t *cap, size_t need, bool zeroed)
+{
+    if (need <= *cap) return SK_OK;
+    if (*p) { CA_HIP(hipStreamSynchronize(a->stream)); (void)hipFree(*p); *p = NULL; *cap = 0; }
+    const size_t want = need + need / 4 + 4096;
+    CA_HIP(hipMalloc(p, want));
+    if (zeroed) CA_HIP(hipMemsetAsync(*p, 0, want, a->stream));
+    *cap = want;
+    return SK_OK;
+}
+
+extern "C" void sk_covacc_destroy(sk_covacc *a)
+{
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    if (a->stream) (void)hipStreamSynchronize(a->stream);
+    (void)hipFree(a->d_depth); (void)hipFree(a->d_base); (void)hipFree(a->d_nrows); (void)hipFree(a->d_out);
+    (void)hipFree(a->d_tot); (void)hipFree(a->d_rows); (void)hipFree(a->h_recs); (void)hipFree(a->h_hits); (void)hipFree(a->h_rs);
+    (void)hipFree(a->p_recs); (void)hipFree(a->p_hits); (void)hipFree(a->p_cnt);
+    if (a->h_bad) (void)hipHostFree(a->h_bad);
+    if (a->stream) (void)hipStreamDestroy(a->stream);
+    delete a;
+}
+
+static int cov_create_steps(sk_covacc *a)
+{
+    CA_HIP(hipSetDevice(a->device));
+    CA_HIP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
+    CA_HIP(hipMalloc((void **)&a->d_depth, (size_t)(a->total_rows ? a->total_rows : 1u) * 4u));
+    CA_HIP(hipMalloc((void **)&a->d_base, (size_t)a->nm * 8u));
+    CA_HIP(hipMalloc((void **)&a->d_nrows, (size_t)a->nm * 4u));
+    CA_HIP(hipMalloc((void **)&a->d_out, (size_t)a->nm * 16u));
+    CA_HIP(hipHostMalloc((void **)&a->h_bad, 64, hipHostMallocDefault));
+    *a->h_bad = 0u;
+    CA_HIP(hipHostGetDevicePointer((void **)&a->d_bad, a->h_bad, 0));
+    CA_HIP(hipMemsetAsync(a->d_depth, 0, (size_t)(a->total_rows ? a->total_rows : 1u) * 4u, a->stream));
+    CA_HIP(hipMemcpyAsync(a->d_base, a->base.data(), (size_t)a->nm * 8u, hipMemcpyHostToDevice, a->stream));
+    CA_HIP(hipMemcpyAsync(a->d_nrows, a->nrows.data(), (size_t)a->nm * 4u, hipMemcpyHostToDevice, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_create(sk_ctx *ctx, uint32_t nmembers, const uint32_t *nrows, int64_t min_kmer_hits, sk_covacc **out)
+{
+    if (!ctx || !out || !nrows || nmembers < 1u || nmembers > 4096u) return SK_E_ARG;
+    *out = NULL;
+    sk_covacc *a = new (std::nothrow) sk_covacc();
+    if (!a) return SK_E_NOMEM;
+    a->ctx = ctx; a->device = sk_ctx_device_(ctx); a->nm = nmembers; a->min_hits = (long long)min_kmer_hits;
+    a->nrows.assign(nrows, nrows + nmembers);
+    a->base.resize(nmembers);
+    for (uint32_t m = 0; m < nmembers; m++) {
+        a->base[m] = a->total_rows;
+        a->total_rows += nrows[m];
+        if (nrows[m] > a->max_rows) a->max_rows = nrows[m];
+    }
+    const int rc = cov_create_steps(a);
+    if (rc != SK_OK) { sk_covacc_destroy(a); return rc; }
+    *out = a;
+    return SK_OK;
+}
+
+// the held results of a launch as one side of a fold; `members` of the launch come back through *ns (1 for a single context)
+static int cov_view(sk_covacc *a, sk_ctx *ctx, sk_union *u, cov_side *s, uint32_t *members)
+{
+    sk_tally_view v;
+    if ((!ctx && !u) || (ctx && u)) return sk_fail_(a->ctx, SK_E_ARG, "name a context or a union");
+    const int rc = sk_tally_view_(ctx, u, &v);
+    if (rc != SK_OK) return sk_fail_(a->ctx, rc, "%s", sk_last_error(u ? sk_union_context(u) : ctx));
+    if (v.device != a->device) return sk_fail_(a->ctx, SK_E_ARG, "the launch ran on another device");
+    s->recs = v.d_recs; s->nrecs = v.nrecs; s->hits = v.d_hits; s->nhits = v.nhits; s->rec_start = v.d_rec_start; s->nrec = v.nrec;
+    s->r0 = 0; s->step = 1;
+    *members = v.members;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_hold(sk_covacc *a, sk_ctx *ctx, sk_union *u)
+{
+    if (!a) return SK_E_ARG;
+    cov_side s; uint32_t members = 0;
+    int rc = cov_view(a, ctx, u, &s, &members);
+    if (rc != SK_OK) return rc;
+    CA_HIP(hipSetDevice(a->device));
+    a->held = false; a->hold_kept = false;
+    if ((rc = cov_room(a, &a->h_recs, &a->h_recs_cap, (size_t)s.nrecs * 12u + 16u, false)) != SK_OK) return rc;
+    if ((rc = cov_room(a, &a->h_hits, &a->h_hits_cap, (size_t)s.nhits * sizeof(sk_hit) + 16u, false)) != SK_OK) return rc;
+    if ((rc = cov_room(a, &a->h_rs, &a->h_rs_cap, (size_t)s.nrec * 4u + 16u, false)) != SK_OK) return rc;
+    if (s.nrecs) CA_HIP(hipMemcpyAsync(a->h_recs, s.recs, (size_t)s.nrecs * 12u, hipMemcpyDeviceToDevice, a->stream));
+    if (s.nhits) CA_HIP(hipMemcpyAsync(a->h_hits, s.hits, (size_t)s.nhits * sizeof(sk_hit), hipMemcpyDeviceToDevice, a->stream));
+    CA_HIP(hipMemcpyAsync(a->h_rs, s.rec_start, (size_t)s.nrec * 4u, hipMemcpyDeviceToDevice, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    a->hs = s;
+    a->hs.recs = (const uint32_t *)a->h_recs; a->hs.hits = (const sk_hit *)a->h_hits; a->hs.rec_start = (const uint32_t *)a->h_rs;
+    a->held_members = members; a->held = true; a->hold_kept = true;
+    return SK_OK;
+}
+
+// what sk_covacc_hold copied, brought home in the collect calls' form (a held launch whose mate's launch cannot be folded after all)
+extern "C" int sk_covacc_fetch_hold(sk_covacc *a, sk_tally_rec *out, uint64_t cap, uint64_t *n, sk_hit *out_hits, uint64_t hits_cap,
+                                    uint64_t *out_nhits)
+{
+    if (!a || !n || !out_nhits) return SK_E_ARG;
+    if (!a->hold_kept) return sk_fail_(a->ctx, SK_E_STATE, "no launch held (sk_covacc_hold)");
+    *n = a->hs.nrecs; *out_nhits = a->hs.nhits;
+    if (a->hs.nrecs > cap || a->hs.nhits > hits_cap) return SK_OK;       // (the counts say how much room it takes)
+    if ((a->hs.nrecs && !out) || (a->hs.nhits && !out_hits)) return SK_E_ARG;
+    CA_HIP(hipSetDevice(a->device));
+    if (a->hs.nrecs) CA_HIP(hipMemcpy(out, a->hs.recs, (size_t)a->hs.nrecs * 12u, hipMemcpyDeviceToHost));
+    if (a->hs.nhits) CA_HIP(hipMemcpy(out_hits, a->hs.hits, (size_t)a->hs.nhits * sizeof(sk_hit), hipMemcpyDeviceToHost));
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_pick(sk_covacc *a, sk_ctx *ctx, sk_union *u, int from_hold, int first, uint32_t ntail,
+                              sk_tally_rec *out, uint64_t cap, uint64_t *n, sk_hit *out_hits, uint64_t hits_cap, uint64_t *out_nhits)
+{
+    if (!a || !n || !out_nhits || (cap && !out) || (hits_cap && !out_hits) || cap > 0x7FFFFFFFu || hits_cap > 0x7FFFFFFFu) return SK_E_ARG;
+    cov_side s; uint32_t members = 0;
+    int rc;
+    if (from_hold) {
+        if (!a->hold_kept) return sk_fail_(a->ctx, SK_E_STATE, "no launch held (sk_covacc_hold)");
+        s = a->hs; members = a->held_members;
+    } else if ((rc = cov_view(a, ctx, u, &s, &members)) != SK_OK) return rc;
+    *n = 0; *out_nhits = 0;
+    if (!s.nrec || !(s.nrecs + s.nhits)) return SK_OK;
+    CA_HIP(hipSetDevice(a->device));
+    if ((rc = cov_room(a, &a->p_recs, &a->p_recs_cap, (size_t)cap * 12u + 16u, false)) != SK_OK) return rc;
+    if ((rc = cov_room(a, &a->p_hits, &a->p_hits_cap, (size_t)hits_cap * sizeof(sk_hit) + 16u, false)) != SK_OK) return rc;
+    if ((rc = cov_room(a, (void **)&a->p_cnt, &a->p_cnt_cap, 8u, false)) != SK_OK) return rc;
+    CA_HIP(hipMemsetAsync(a->p_cnt, 0, 8u, a->stream));
+    hipLaunchKernelGGL(covacc_pick, dim3(cov_grid(s.nrecs + s.nhits)), dim3(256), 0, a->stream, s.recs, s.nrecs, s.hits, s.nhits,
+                       s.rec_start, s.nrec, members ? members : 1u, first, ntail < s.nrec ? s.nrec - ntail : 0u,
+                       (uint32_t *)a->p_recs, (uint32_t)cap, (sk_hit *)a->p_hits, (uint32_t)hits_cap, a->p_cnt);
+    CA_HIP(hipGetLastError());
+    uint32_t cnt[2];
+    CA_HIP(hipMemcpyAsync(cnt, a->p_cnt, 8u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    *n = cnt[0]; *out_nhits = cnt[1];
+    if (cnt[0] > cap || cnt[1] > hits_cap) return SK_OK;                  // (the counts say how much room it takes: pick again)
+    if (cnt[0]) CA_HIP(hipMemcpy(out, a->p_recs, (size_t)cnt[0] * 12u, hipMemcpyDeviceToHost));
+    if (cnt[1]) CA_HIP(hipMemcpy(out_hits, a->p_hits, (size_t)cnt[1] * sizeof(sk_hit), hipMemcpyDeviceToHost));
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t member0, uint32_t a0, uint32_t astep, uint32_t npairs,
+                             const sk_covacc_mate *mate)
+{
+    if (!a) return SK_E_ARG;
+    cov_side side[2]; uint32_t members = 0, nsides = 1;
+    int rc = cov_view(a, ctx, u, &side[0], &members);
+    if (rc != SK_OK) return rc;
+    const uint32_t ns = members ? members : 1u;
+    if (member0 >= a->nm || ns > a->nm - member0) return sk_fail_(a->ctx, SK_E_ARG, "members %u..%u: the accumulator has %u", member0, member0 + ns - 1u, a->nm);
+    if (!npairs) return SK_OK;
+    side[0].r0 = a0; side[0].step = astep;
+    if (mate) {
+        if (mate->held) {
+            if (!a->held) return sk_fail_(a->ctx, SK_E_STATE, "no launch held (sk_covacc_hold)");
+            if (a->held_members != members) return sk_fail_(a->ctx, SK_E_ARG, "the held launch had other members");
+            side[1] = a->hs;
+        } else side[1] = side[0];
+        side[1].r0 = mate->b0; side[1].step = mate->bstep;
+        nsides = 2;
+    }
+    for (uint32_t k = 0; k < nsides; k++)
+        if (!side[k].step || !side[k].nrec || side[k].r0 >= side[k].nrec ||
+            (uint64_t)side[k].r0 + (uint64_t)(npairs - 1u) * side[k].step >= side[k].nrec)
+            return sk_fail_(a->ctx, SK_E_ARG, "the run leaves the batch (records %u + %u x %u of %u)", side[k].r0, npairs, side[k].step, side[k].nrec);
+    if ((uint64_t)npairs * ns > 0x3FFFFFF0ull) return sk_fail_(a->ctx, SK_E_ARG, "too many pairs x members");
+    CA_HIP(hipSetDevice(a->device));
+    if ((rc = cov_room(a, (void **)&a->d_tot, &a->tot_cap, (size_t)npairs * ns * 4u, true)) != SK_OK) return rc;
+    for (int clear = 0; clear < 2; clear++) {
+        for (uint32_t k = 0; k < nsides; k++)
+            if (side[k].nrecs)
+                hipLaunchKernelGGL(covacc_scatter, dim3(cov_grid(side[k].nrecs)), dim3(256), 0, a->stream, side[k].recs, side[k].nrecs, ns,
+                                   side[k].nrec, side[k].r0, side[k].step, npairs, a->d_tot, clear);
+        for (uint32_t k = 0; k < nsides && !clear; k++)
+            if (side[k].nhits)
+                hipLaunchKernelGGL(covacc_hits, dim3(cov_grid(side[k].nhits)), dim3(256), 0, a->stream, side[k].hits, side[k].nhits,
+                                   side[k].rec_start, side[k].nrec, ns, members ? 1 : 0, side[k].r0, side[k].step, npairs,
+                                   (const uint32_t *)a->d_tot, a->min_hits, a->d_depth, (const uint64_t *)a->d_base + member0,
+                                   (const uint32_t *)a->d_nrows + member0, a->d_bad);
+    }
+    {   // a fold that fails half way leaves tot[] as it must be between folds: all zero
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
+        if (e != hipSuccess) {
+            (void)hipMemset(a->d_tot, 0, a->tot_cap);
+            return sk_fail_(a->ctx, SK_E_HIP, "the fold failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (mate && mate->held) a->held = false;
+    if (*(volatile uint32_t *)a->h_bad) { *a->h_bad = 0u; return sk_fail_(a->ctx, SK_E_STATE, "a hit log entry names no row of its member"); }
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_add_rows(sk_covacc *a, uint32_t member, const uint32_t *rows, uint64_t n)
+{
+    if (!a || (n && !rows)) return SK_E_ARG;
+    if (member >= a->nm) return sk_fail_(a->ctx, SK_E_ARG, "member %u: the accumulator has %u", member, a->nm);
+    if (!n) return SK_OK;
+    for (uint64_t i = 0; i < n; i++)
+        if (rows[i] >= a->nrows[member]) return sk_fail_(a->ctx, SK_E_ARG, "row %u: member %u has %u", rows[i], member, a->nrows[member]);
+    CA_HIP(hipSetDevice(a->device));
+    const int rc = cov_room(a, (void **)&a->d_rows, &a->rows_cap, (size_t)n * 4u, false);
+    if (rc != SK_OK) return rc;
+    CA_HIP(hipMemcpyAsync(a->d_rows, rows, (size_t)n * 4u, hipMemcpyHostToDevice, a->stream));
+    hipLaunchKernelGGL(covacc_rows, dim3(cov_grid(n)), dim3(256), 0, a->stream, (const uint32_t *)a->d_rows, n, a->nrows[member],
+                       a->d_depth + a->base[member]);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipStreamSynchronize(a->stream));
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_finish_target(sk_covacc *a, uint64_t *out_unique, uint64_t *out_total)
+{
+    if (!a || !out_unique || !out_total) return SK_E_ARG;
+    CA_HIP(hipSetDevice(a->device));
+    std::vector<unsigned long long> h((size_t)a->nm * 2u);
+    CA_HIP(hipMemsetAsync(a->d_out, 0, (size_t)a->nm * 16u, a->stream));
+    unsigned gx = (a->max_rows + 255u) / 256u;
+    gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
+    hipLaunchKernelGGL(covacc_finish, dim3(gx, a->nm), dim3(256), 0, a->stream, a->d_depth, (const uint64_t *)a->d_base,
+                       (const uint32_t *)a->d_nrows, a->d_out);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipMemcpyAsync(h.data(), a->d_out, (size_t)a->nm * 16u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    for (uint32_t m = 0; m < a->nm; m++) { out_unique[m] = h[2u * m]; out_total[m] = h[2u * m + 1u]; }
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_rows(sk_covacc *a, uint32_t member, uint32_t *out)
+{
+    if (!a || !out) return SK_E_ARG;
+    if (member >= a->nm) return sk_fail_(a->ctx, SK_E_ARG, "member %u: the accumulator has %u", member, a->nm);
+    CA_HIP(hipSetDevice(a->device));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    if (a->nrows[member]) CA_HIP(hipMemcpy(out, a->d_depth + a->base[member], (size_t)a->nrows[member] * 4u, hipMemcpyDeviceToHost));
+    return SK_OK;
+}

@@ -143,6 +143,12 @@ struct sk_ctx {
     size_t       h_tally_cap;
     uint32_t     t_inflight_nrec;     // a sk_tally_launch waiting for its sk_tally_collect
     uint64_t     t_inflight_cap;
+    // the launch whose results were left on the device (sk_tally_collect_counts): its batch, its counters, the room its log had
+    const struct sk_batch *t_batch;   // the batch of the launch in flight or held
+    bool         t_held;
+    uint64_t     t_held_n, t_held_nh, t_held_cap;
+    const uint32_t *t_rec_start; uint32_t t_nrec;      // the launch's record starts and count, taken when it started
+    uint32_t     t_eager;             // union launches: how many records / log entries the launch in flight sends home with its counters
     struct sk_batch *own_batch;       // sk_tally_batch's private batch
     void        *comm;                // RCCL communicator from sk_comm_init (NULL: single process)
     int          comm_rank, comm_world;
@@ -1144,6 +1150,7 @@ extern "C" int sk_tally_launch(sk_ctx *c, const sk_batch *b, uint32_t type_col, 
     SK_HIP(c, hipMemcpyAsync(c->h_tally, d_n, 16, hipMemcpyDeviceToHost, c->stream));
     c->t_inflight_nrec = nrec;
     c->t_inflight_cap = hits_cap;
+    c->t_batch = b; c->t_held = false; c->t_rec_start = (const uint32_t *)b->d_rec; c->t_nrec = b->nrec;
     return SK_OK;
 }
 
@@ -1186,6 +1193,38 @@ extern "C" int sk_tally_collect_sparse(sk_ctx *c, sk_tally_rec *out, uint64_t ca
     if (take && !out_hits) return SK_E_ARG;
     if (take) SK_HIP(c, hipMemcpy(out_hits, c->t_hits, (size_t)take * sizeof(uint2), hipMemcpyDeviceToHost));
     *out_nhits = two[0];
+    return SK_OK;
+}
+
+// Wait for the launch and hand out its two counters ONLY: the sparse records and the hit log stay where the launch left them, in
+// the context's device buffers, until the context's next launch (sk_covacc_add folds them there; sk_tally_fetch_held brings them
+// home after all).  The batch must stay as it is for as long: its record starts are part of the results.
+extern "C" int sk_tally_collect_counts(sk_ctx *c, uint64_t *n, uint64_t *out_nhits)
+{
+    if (!c || !n || !out_nhits) return SK_E_ARG;
+    if (!c->t_inflight_nrec) return sk_fail(c, SK_E_STATE, "no tally in flight");
+    SK_HIP(c, hipSetDevice(c->device));
+    SK_HIP(c, hipStreamSynchronize(c->stream));
+    c->t_inflight_nrec = 0;
+    unsigned long long two[2];
+    memcpy(two, c->h_tally, 16);
+    c->t_held = true; c->t_held_n = two[1]; c->t_held_nh = two[0]; c->t_held_cap = c->t_inflight_cap;
+    *n = two[1];
+    *out_nhits = two[0];
+    return SK_OK;
+}
+
+// ... and what sk_tally_collect_sparse would have copied, for a caller that needs the held results on the host after all
+extern "C" int sk_tally_fetch_held(sk_ctx *c, sk_tally_rec *out, uint64_t cap, sk_hit *out_hits)
+{
+    if (!c) return SK_E_ARG;
+    if (!c->t_held) return sk_fail(c, SK_E_STATE, "no tally results held on the device");
+    SK_HIP(c, hipSetDevice(c->device));
+    const uint64_t take_r = c->t_held_n < cap ? c->t_held_n : cap;
+    const uint64_t take = c->t_held_nh < c->t_held_cap ? c->t_held_nh : c->t_held_cap;
+    if ((take_r && !out) || (take && !out_hits)) return SK_E_ARG;
+    if (take_r) SK_HIP(c, hipMemcpy(out, c->t_compact, (size_t)take_r * sizeof(sk_tally_rec), hipMemcpyDeviceToHost));
+    if (take) SK_HIP(c, hipMemcpy(out_hits, c->t_hits, (size_t)take * sizeof(uint2), hipMemcpyDeviceToHost));
     return SK_OK;
 }
 
@@ -1365,6 +1404,12 @@ static int sk_union_zeroed(sk_union *u, void **p, size_t *cap, size_t need)
 // Start the tallies of batch `b` against every member at once; returns at once.  Results: sk_union_tally_collect.
 extern "C" int sk_union_tally_launch(sk_union *u, const sk_batch *b, uint64_t hits_cap)
 {
+    return sk_union_tally_launch_ex(u, b, hits_cap, 0);
+}
+// results_stay != 0: only the three counters travel home with the launch (no record, no log entry rides along): for launches that
+// are collected with sk_union_tally_collect_counts.  sk_union_tally_collect still works on such a launch (it copies everything then).
+extern "C" int sk_union_tally_launch_ex(sk_union *u, const sk_batch *b, uint64_t hits_cap, int results_stay)
+{
     if (!u || !b) return SK_E_ARG;
     sk_ctx *c = u->uc;
     if (b->owner->device != c->device) return sk_fail(c, SK_E_ARG, "batch lives on another device");
@@ -1422,11 +1467,13 @@ extern "C" int sk_union_tally_launch(sk_union *u, const sk_batch *b, uint64_t hi
     // the counters and the first SK_UNION_EAGER results go home in one kernel (and the other set of counters is zeroed for the next launch)
     hipLaunchKernelGGL(sk_union_ship, dim3(32), dim3(256), 0, c->stream, (const unsigned long long *)d_cnt, d_cnt_next,
                        (const uint32_t *)c->t_compact, (unsigned long long)vrec, (const uint2 *)c->t_hits, (unsigned long long)hits_cap,
-                       (uint32_t)SK_UNION_EAGER, d_land);
+                       results_stay ? 0u : (uint32_t)SK_UNION_EAGER, d_land);
     SK_HIP(c, hipGetLastError());
+    c->t_eager = results_stay ? 0u : (uint32_t)SK_UNION_EAGER;
     u->cnt_clean = true;
     c->t_inflight_nrec = (uint32_t)vrec;
     c->t_inflight_cap = hits_cap;
+    c->t_batch = b; c->t_held = false; c->t_rec_start = (const uint32_t *)b->d_rec; c->t_nrec = b->nrec;
     return SK_OK;
 }
 
@@ -1445,7 +1492,7 @@ extern "C" int sk_union_tally_collect(sk_union *u, sk_tally_rec *out, uint64_t c
     memcpy(cnt, c->h_tally, 24);
     const unsigned long long take_r = cnt[1] < cap ? cnt[1] : cap;
     {   // what came back with the counters, then (rarely) the rest
-        const unsigned long long have = take_r < SK_UNION_EAGER ? take_r : SK_UNION_EAGER;
+        const unsigned long long have = take_r < c->t_eager ? take_r : c->t_eager;
         if (have) memcpy(out, c->h_tally + 64, (size_t)have * sizeof(sk_tally_rec));
         if (take_r > have) SK_HIP(c, hipMemcpy(out + have, (const sk_tally_rec *)c->t_compact + have, (size_t)(take_r - have) * sizeof(sk_tally_rec), hipMemcpyDeviceToHost));
     }
@@ -1457,7 +1504,7 @@ extern "C" int sk_union_tally_collect(sk_union *u, sk_tally_rec *out, uint64_t c
     const unsigned long long take = nh < c->t_inflight_cap ? nh : c->t_inflight_cap;
     if (take && !out_hits) return SK_E_ARG;
     {
-        const unsigned long long have = take < SK_UNION_EAGER ? take : SK_UNION_EAGER;
+        const unsigned long long have = take < c->t_eager ? take : c->t_eager;
         if (have) memcpy(out_hits, c->h_tally + 64 + (size_t)SK_UNION_EAGER * sizeof(sk_tally_rec), (size_t)have * sizeof(uint2));
         if (take > have) SK_HIP(c, hipMemcpy(out_hits + have, (const uint2 *)c->t_hits + have, (size_t)(take - have) * sizeof(uint2), hipMemcpyDeviceToHost));
     }
@@ -1474,6 +1521,45 @@ extern "C" int sk_union_sync(sk_union *u)
     { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
     SK_HIP(c, hipStreamSynchronize(c->stream));
     c->t_inflight_nrec = 0;
+    return SK_OK;
+}
+
+// sk_tally_collect_counts / sk_tally_fetch_held for a union's launch: *n pairs, *out_nhits dealt-out log entries (reported as
+// sk_union_tally_collect reports them: more than the launch's hits_cap = launch again with more room).  After
+// sk_union_tally_launch_ex(.., results_stay = 1) the three counters are all that crossed the link.
+extern "C" int sk_union_tally_collect_counts(sk_union *u, uint64_t *n, uint64_t *out_nhits)
+{
+    if (!u || !n || !out_nhits) return SK_E_ARG;
+    sk_ctx *c = u->uc;
+    if (!c->t_inflight_nrec) return sk_fail(c, SK_E_STATE, "no tally in flight");
+    SK_HIP(c, hipSetDevice(c->device));
+    SK_HIP(c, hipStreamSynchronize(c->stream));
+    c->t_inflight_nrec = 0;
+    unsigned long long cnt[3];
+    memcpy(cnt, c->h_tally, 24);
+    unsigned long long nh = cnt[2];
+    if (cnt[0] > c->t_inflight_cap && nh <= c->t_inflight_cap) nh = cnt[0] > nh ? cnt[0] : c->t_inflight_cap + 1;
+    c->t_held = true; c->t_held_n = cnt[1]; c->t_held_nh = nh; c->t_held_cap = c->t_inflight_cap;
+    *n = cnt[1];
+    *out_nhits = nh;
+    return SK_OK;
+}
+extern "C" int sk_union_tally_fetch_held(sk_union *u, sk_tally_rec *out, uint64_t cap, sk_hit *out_hits)
+{
+    return u ? sk_tally_fetch_held(u->uc, out, cap, out_hits) : SK_E_ARG;
+}
+
+// Where the held results of a context's (u NULL) or a union's launch are, for the coverage accumulator (sk_covacc.hip)
+extern "C" int sk_tally_view_(sk_ctx *c, sk_union *u, sk_tally_view *v)
+{
+    if (!v || (!c && !u)) return SK_E_ARG;
+    if (u) c = u->uc;
+    if (!c->t_held || !c->t_batch) return sk_fail(c, SK_E_STATE, "no tally results held on the device (sk_tally_collect_counts first)");
+    if (c->t_held_nh > c->t_held_cap) return sk_fail(c, SK_E_STATE, "the hit log overflowed: launch again with more room");
+    v->owner = c; v->device = c->device; v->members = u ? u->n : 0u;
+    v->d_recs = (const uint32_t *)c->t_compact; v->nrecs = c->t_held_n;
+    v->d_hits = (const sk_hit *)c->t_hits; v->nhits = c->t_held_nh;
+    v->d_rec_start = c->t_rec_start; v->nrec = c->t_nrec;
     return SK_OK;
 }
 

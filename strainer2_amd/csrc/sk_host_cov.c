@@ -104,6 +104,7 @@ typedef struct {
     uint32_t *gid, *gsample; uint64_t gn, gcap;        /* general mode: per passing line, in file order: joined-string number, sample */
     int       general;
     size_t    klen;                                    /* k-mer field length seen so far (0 = none yet) */
+    uint64_t *given_u, *given_t; uint32_t ngiven; int given;   /* counts handed in per sample (skc_add_counts) instead of hits */
 } hitlist;
 
 enum { COV_OK = 0, COV_OPEN, COV_FIELDS, COV_INT, COV_NOMEM };
@@ -335,7 +336,9 @@ static int cov_report(hitlist *h, sk_ctx *ctx, const char *kfile, const char *bf
         }
     if (h->smp.n) {
         if (!(uniq = calloc(h->smp.n, sizeof *uniq)) || !(total = calloc(h->smp.n, sizeof *total))) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
-        if (h->general) {                            /* out-of-domain k-mer text: first sightings of the joined strings */
+        if (h->given) {                              /* counted already (strain_detect --coverage-only: on the device, target by target) */
+            for (s = 0; s < h->ngiven && s < h->smp.n; s++) { uniq[s] = h->given_u[s]; total[s] = h->given_t[s]; }
+        } else if (h->general) {                     /* out-of-domain k-mer text: first sightings of the joined strings */
             rc = sk_first_seen_count(ctx, h->gid, h->gsample, h->gn, h->text.n, h->smp.n, uniq, total);
             if (rc != SK_OK) { fprintf(err, "coverage_depth: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx)); goto done; }
         } else {
@@ -405,6 +408,7 @@ done:
 
 static void hitlist_free(hitlist *h)
 {
+    free(h->given_u); free(h->given_t);
     free(h->key); free(h->sample); free(h->depth_order); free(h->eval_order); free(h->gid); free(h->gsample);
     names_free(&h->smp); names_free(&h->text);
     memset(h, 0, sizeof *h);
@@ -432,6 +436,31 @@ int skc_add_hit(skc_acc *a, const char *metagenome, int64_t hits_pe1, int64_t hi
     sn = base_of(metagenome, metagenome + strlen(metagenome));
     if ((g = cov_sample(&a->h, sn, strlen(sn))) < 0) return -1;
     return cov_push(&a->h, (uint32_t)g, (uint64_t)row) == COV_OK ? 0 : -1;
+}
+
+/* a metagenome's two numbers, counted elsewhere: `total` hit lines that passed the read filter, on `unique` distinct rows.  Called
+ * where the metagenome's first passing line would have come (before its trailers), so that the order of the table's lines is the
+ * script's; an accumulator takes either hits or counts, and a metagenome's counts once (the caller sees to both). */
+int skc_add_counts(skc_acc *a, const char *metagenome, uint64_t unique, uint64_t total)
+{
+    hitlist *h = &a->h;
+    const char *sn = base_of(metagenome, metagenome + strlen(metagenome));
+    const int64_t g = total ? cov_sample(h, sn, strlen(sn)) : name_get(&h->smp, sn, strlen(sn));
+    if (g < 0) return -1;
+    h->given = 1;
+    if ((uint64_t)g >= h->ngiven) {
+        const uint32_t n2 = (uint32_t)g + 16u;
+        uint64_t *u2 = realloc(h->given_u, (size_t)n2 * sizeof *u2), *t2;
+        if (!u2) return -1;
+        h->given_u = u2;
+        if (!(t2 = realloc(h->given_t, (size_t)n2 * sizeof *t2))) return -1;
+        h->given_t = t2;
+        memset(u2 + h->ngiven, 0, (size_t)(n2 - h->ngiven) * sizeof *u2);
+        memset(t2 + h->ngiven, 0, (size_t)(n2 - h->ngiven) * sizeof *t2);
+        h->ngiven = n2;
+    }
+    h->given_u[g] += unique; h->given_t[g] += total;
+    return 0;
 }
 
 int skc_add_trailer(skc_acc *a, const char *metagenome, const char *name, int64_t value)

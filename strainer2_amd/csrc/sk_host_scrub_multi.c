@@ -302,13 +302,27 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
                 free(v);
                 return 1;
             }
-            *want_cov = 1;
+            *want_cov |= 1;
+            continue;
+        }
+        if (c > 0 && !strncmp(argv[c], "--coverage-only", 15) && (argv[c][15] == 0 || argv[c][15] == '=')) {
+            if (argv[c][15] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-only takes no file name (each strain's table goes where its hit list would name it)\n");
+                free(v);
+                return 1;
+            }
+            *want_cov |= 2;                          /* (no hit list is written: none is created up front either) */
             continue;
         }
         if (c > 0 && !strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { c++; continue; }
         v[n++] = argv[c];
     }
     v[n] = NULL;
+    if (*want_cov == 3) {
+        fprintf(err, "kmer_scrub_count: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n");
+        free(v);
+        return 1;
+    }
     opterr = 0;                                      /* (strain_detect itself reports unknown letters later) */
     optind = 1;
     while (!bad && (c = getopt(n, v, "g:r:a:A:b:c:B:S:M:o:t:Hhuspn")) != -1)
@@ -466,7 +480,7 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
         else st[k].fp = fopen(st[k].outfile, "w");
         if (!st[k].zo && !st[k].fp) { fprintf(err, "kmer_scrub_count: cannot write %s\n", st[k].outfile); goto done; }
         st[k].made |= 1u;
-        more[0] = st[k].hits; more[1] = st[k].cov;
+        more[0] = (want_cov & 2) ? NULL : st[k].hits; more[1] = st[k].cov;
         for (m = 0; m < 2; m++) {
             FILE *f;
             if (!more[m]) continue;

@@ -90,6 +90,7 @@ typedef struct {
     sk_hit     *hitbuf; uint64_t hitcap;   /* landing area of the hit log */
     uint32_t   *tallybuf; uint32_t tallycap;
     int         job_rc;                    /* result of this strain's part of a pool job */
+    uint32_t   *co_rows; uint64_t co_n, co_cap;   /* --coverage-only: rows of host-replayed passing hits on their way to the device's counters */
 } sd_prog;
 
 /* ---------------------------------------------------------------------------------------------
@@ -121,7 +122,11 @@ typedef struct sd_chunk {
     uint64_t  t_reads, t_eval;               /* accepted: records of k bases or more, and their windows */
     int       tc_handed;                     /* the target cache's writer has been given this chunk */
     int       cache_err;                     /* the serving thread's marker: its cache file failed a check here (SKPC_*) */
+    /* --coverage-only: SD_CO_FOLDED the chunk's pairs were counted on the device and res_* holds only its first and last records'
+     * results; SD_CO_HELD (a PE1 chunk) the accumulators hold its results until the PE2 chunk shows whether the two fold together */
+    int       co; uint32_t co_a0;            /* (co_a0: PEI, the chunk's first record is the mate of the last chunk's last: 1) */
 } sd_chunk;
+enum { SD_CO_NONE = 0, SD_CO_FOLDED = 1, SD_CO_HELD = 2 };
 enum { SD_TEXT_PENDING = 1, SD_TEXT_ACCEPTED = 2, SD_TEXT_DECLINED = 3 };   /* (DECLINED before it went up: the reader found no piece to send) */
 typedef struct sd_sp { uint32_t n; uint32_t *rec, *all, *inf, *hbeg /* n + 1 */, *rows; } sd_sp;
 
@@ -156,6 +161,7 @@ typedef struct {
     sk_batch   *bat[2][SD_MAX_DEV]; int bcur;
     sd_chunk   *pre;                         /* the queued chunk whose bytes are already in bat[bcur ^ 1] */
     sd_chunk   *ahead;                       /* ... and whose scan has been launched as well (solo streams: see sd_launch_ahead) */
+    uint32_t    co_next;                     /* --coverage-only, PEI: the next chunk's co_a0 */
     int         solo;                        /* the only stream that uses the tables now (SE, PEI): its next chunk may be scanned while this one is replayed */
     /* the target cache (sd_tc): a file that is served has a serving thread in the decode thread's place; one that is filled has a writer */
     int         serving, cache_failed;
@@ -1328,6 +1334,7 @@ typedef struct sd_job {
     const char *f1;
     uint32_t a0, b0, astep, n, first_valid;
     int have_copy;
+    int mute;                                  /* REPLAY: nothing is emitted, only the carried state moves on (a run the device counted) */
     int pending;                               /* lanes that still have it (atomic) */
 } sd_job;
 struct sd_lanes;
@@ -1350,7 +1357,7 @@ static pthread_mutex_t sd_dev_mu = PTHREAD_MUTEX_INITIALIZER;
 static double t_lane_busy, t_lane_backpressure, t_lane_drain;
 
 static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk *ca, uint32_t a0, const sd_chunk *cb, uint32_t b0,
-                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid);
+                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute);
 
 static void lane_job_done(sd_lanes *L, sd_job *j)
 {
@@ -1389,7 +1396,7 @@ static void *lane_main(void *arg)
                 sd_prog *p = &L->p[s];
                 if (j->kind == SD_JOB_TALLY) tally_one(p, j->ca, s);
                 else if (j->kind == SD_JOB_REPLAY && p->job_rc == SK_OK)
-                    sd_replay_run(p, s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid);
+                    sd_replay_run(p, s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute);
             }
             ln->busy += now_s() - t0;
         }
@@ -1436,7 +1443,7 @@ static void lanes_post(sd_job *j)
             for (s = ln->id; s < L->ns; s += L->n) {
                 if (j->kind == SD_JOB_TALLY) tally_one(&L->p[s], j->ca, s);
                 else if (j->kind == SD_JOB_REPLAY && L->p[s].job_rc == SK_OK)
-                    sd_replay_run(&L->p[s], s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid);
+                    sd_replay_run(&L->p[s], s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute);
             }
             lane_job_done(L, j);
             continue;
@@ -1573,6 +1580,237 @@ static void sd_prefetch(sd_stream *st)
     t_fill += now_s() - t0;
 }
 
+/* ---------------------------------------------------------------------------------------------
+ * --coverage-only: step 4's table without the hit list (scripts/coverage_depth.py:62-129 over src/strain_detect.c:443-626).
+ * One coverage accumulator (sk_covacc) per launch unit -- a union table's group of strains, or a strain -- on the unit's device.
+ * A chunk all of whose records have k bases or more is counted where its scan left its results (sk_covacc_add): single reads
+ * whole, interleaved pairs as far as both mates are in the chunk, two files when the PE1 chunk and the PE2 chunk hold the same
+ * records (the PE1 chunk's results wait in the accumulator: sk_covacc_hold).  Of such a chunk only the results of its first and
+ * its last three records come home (sk_covacc_pick): the last pair's tallies and rows are what a short read behind it would
+ * repeat -- a muted replay of that pair carries them on -- and a pair that straddles two chunks is replayed as ever.  Every
+ * other chunk is collected and replayed as without the flag, and emit_rows hands the passing pairs' rows to
+ * sk_covacc_add_rows.  At a target's end sk_covacc_finish_target gives each strain's two numbers to its skc_acc.
+ * ------------------------------------------------------------------------------------------- */
+/* The device's entry points are weak, as the text parser's are: the host-only test builds link this file without them, and there
+ * the flag counts every target on the host accumulator (co_open). */
+#pragma weak sk_covacc_create
+#pragma weak sk_covacc_destroy
+#pragma weak sk_covacc_hold
+#pragma weak sk_covacc_add
+#pragma weak sk_covacc_add_rows
+#pragma weak sk_covacc_finish_target
+#pragma weak sk_covacc_pick
+#pragma weak sk_covacc_fetch_hold
+#pragma weak sk_tally_collect_counts
+#pragma weak sk_union_tally_collect_counts
+#pragma weak sk_union_tally_launch_ex
+static int chunk_res_reserve(sd_chunk *c, uint64_t *rcap, uint64_t *hcap, uint64_t nrec_total, uint64_t nhit_total);
+static struct {
+    int on, host;                               /* the flag; every target through the host accumulator (two targets share a basename) */
+    long long min;                              /* --min-kmer-hits */
+    int mode; sd_stream *pe_a;                  /* the target being read: SD_*, and the PE1 stream of two files */
+    sk_covacc **acc; uint32_t nacc;             /* one per unit; NULL: nothing is counted on the device */
+    sk_tally_rec *recs; uint64_t rcap; sk_hit *hits; uint64_t hcap;    /* landing area of picks and fetched holds */
+    uint64_t flush_rows;                        /* a strain's replayed rows go to the device when this many wait (SK_SD_CO_FLUSH_ROWS: tests) */
+    sd_chunk *post;                             /* a PE1 chunk whose TALLY job waits for the device mutex to be let go */
+} sd_co;
+static uint64_t sd_co_dev, sd_co_replayed, sd_co_hostacc;
+static uint64_t sd_res_bytes;                   /* scan results copied device to host by this run (SK_SD_RESULT_BYTES=1 prints it) */
+
+void skh_coverage_only_stats(uint64_t *runs_on_device, uint64_t *runs_replayed, uint64_t *targets_host_accumulated, int reset)
+{
+    if (runs_on_device) *runs_on_device = sd_co_dev;
+    if (runs_replayed) *runs_replayed = sd_co_replayed;
+    if (targets_host_accumulated) *targets_host_accumulated = sd_co_hostacc;
+    if (reset) sd_co_dev = sd_co_replayed = sd_co_hostacc = 0;
+}
+
+static uint32_t co_units(uint32_t ns) { return sd_un.n ? sd_un.n : ns; }
+static uint32_t co_unit_first(uint32_t unit) { return sd_un.n ? unit * sd_group : unit; }
+static uint32_t co_unit_members(uint32_t unit) { return sd_un.n ? sk_union_members(sd_un.u[unit]) : 1u; }
+
+static void co_close(void)
+{
+    uint32_t k;
+    for (k = 0; k < sd_co.nacc; k++) if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
+    free(sd_co.acc); free(sd_co.recs); free(sd_co.hits);
+    sd_co.acc = NULL; sd_co.nacc = 0; sd_co.recs = NULL; sd_co.hits = NULL; sd_co.rcap = sd_co.hcap = 0; sd_co.post = NULL;
+}
+
+static int co_open(sd_prog *p, uint32_t ns)
+{
+    const uint32_t nu = co_units(ns);
+    uint32_t k, m;
+    if (!sd_co.on || sd_co.host) return SK_OK;
+    if (!sk_covacc_create || !sk_covacc_pick || !sk_tally_collect_counts || !sk_union_tally_launch_ex) {
+        fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
+        sd_co.host = 1;
+        return SK_OK;
+    }
+    sd_co.acc = (sk_covacc **)calloc(nu, sizeof *sd_co.acc);
+    if (!sd_co.acc) return SK_E_NOMEM;
+    for (k = 0; k < nu; k++) {
+        const uint32_t a = co_unit_first(k), n = co_unit_members(k);
+        uint32_t nrows[SK_UNION_MAX];
+        int rc;
+        for (m = 0; m < n; m++) nrows[m] = (uint32_t)p[a + m].ks.nrows;
+        rc = sk_covacc_create(p[a].ctx, n, nrows, (int64_t)sd_co.min, &sd_co.acc[k]);
+        sd_co.nacc = k + 1;
+        if (rc != SK_OK) { sd_co.nacc = k; co_close(); return rc; }
+    }
+    return SK_OK;
+}
+
+/* every record of the chunk has k bases or more and is one record of its batch */
+static int co_chunk_clean(const sd_chunk *c)
+{
+    uint32_t i;
+    if (!c->np || c->np != c->nrec) return 0;
+    if (c->text) return c->t_reads == c->nrec;
+    for (i = 0; i < c->np; i++) if (c->prec[i] != i) return 0;
+    return 1;
+}
+
+/* the rows of a replayed, passing pair wait here for the device (a lane's strain; the main thread at a target's end) */
+static void co_flush(sd_prog *p, uint32_t s)
+{
+    const uint32_t unit = sd_un.n ? s / sd_group : s;
+    int rc;
+    if (!p->co_n) return;
+    pthread_mutex_lock(&sd_dev_mu);
+    rc = sk_covacc_add_rows(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_n);
+    pthread_mutex_unlock(&sd_dev_mu);
+    p->co_n = 0;
+    if (rc != SK_OK) p->job_rc = rc;
+}
+
+enum { CO_PICK, CO_PICK_HOLD, CO_HOLD_ALL };
+/* c->res_*: a few records' results of the unit's launches (CO_PICK), of the launches held (CO_PICK_HOLD), or the held launches'
+ * results in full (CO_HOLD_ALL), dealt to the strains as sd_collect deals a chunk's */
+static int co_deal(uint32_t ns, sd_prog *p, sd_chunk *c, int src, int first, uint32_t ntail)
+{
+    const uint32_t nu = co_units(ns);
+    uint64_t rcap = 0, hcap = 0, nr = 0, nhit = 0, e;
+    uint32_t k, s;
+    int rc;
+    free(c->res_off);
+    c->res_off = (uint64_t *)calloc(2 * ((size_t)ns + 1), sizeof(uint64_t));
+    if (!c->res_off) return SK_E_NOMEM;
+    c->res_hoff = c->res_off + ns + 1;
+    for (k = 0; k < nu; k++) {
+        const uint32_t a = co_unit_first(k), n = co_unit_members(k);
+        uint64_t nsp = 0, nh = 0, cnt[SK_UNION_MAX + 1], hcnt[SK_UNION_MAX + 1];
+        for (;;) {
+            if (!sd_co.recs) { sd_co.rcap = 4096; sd_co.recs = (sk_tally_rec *)malloc((size_t)sd_co.rcap * sizeof *sd_co.recs); }
+            if (!sd_co.hits) { sd_co.hcap = 1u << 16; sd_co.hits = (sk_hit *)malloc((size_t)sd_co.hcap * sizeof *sd_co.hits); }
+            if (!sd_co.recs || !sd_co.hits) return SK_E_NOMEM;
+            if (src == CO_HOLD_ALL) rc = sk_covacc_fetch_hold(sd_co.acc[k], sd_co.recs, sd_co.rcap, &nsp, sd_co.hits, sd_co.hcap, &nh);
+            else rc = sk_covacc_pick(sd_co.acc[k], src == CO_PICK && !sd_un.n ? p[a].ctx : NULL, src == CO_PICK && sd_un.n ? sd_un.u[k] : NULL,
+                                     src == CO_PICK_HOLD, first, ntail, sd_co.recs, sd_co.rcap, &nsp, sd_co.hits, sd_co.hcap, &nh);
+            if (rc != SK_OK) return rc;
+            if (nsp <= sd_co.rcap && nh <= sd_co.hcap) break;
+            if (nsp > sd_co.rcap) { free(sd_co.recs); sd_co.recs = NULL; sd_co.rcap = nsp + nsp / 4; sd_co.recs = (sk_tally_rec *)malloc((size_t)sd_co.rcap * sizeof *sd_co.recs); }
+            if (nh > sd_co.hcap) { free(sd_co.hits); sd_co.hits = NULL; sd_co.hcap = nh + nh / 4; sd_co.hits = (sk_hit *)malloc((size_t)sd_co.hcap * sizeof *sd_co.hits); }
+        }
+        sd_res_bytes += nsp * sizeof(sk_tally_rec) + nh * sizeof(sk_hit) + 8;
+        if ((rc = chunk_res_reserve(c, &rcap, &hcap, nr + nsp, nhit + nh)) != SK_OK) return rc;
+        if (!sd_un.n) {
+            memcpy(c->res_recs + nr, sd_co.recs, (size_t)nsp * sizeof(sk_tally_rec));
+            memcpy(c->res_hits + nhit, sd_co.hits, (size_t)nh * sizeof(sk_hit));
+            c->res_off[a] = nr; c->res_hoff[a] = nhit;
+            nr += nsp; nhit += nh;
+            continue;
+        }
+        memset(cnt, 0, sizeof cnt); memset(hcnt, 0, sizeof hcnt);
+        for (e = 0; e < nsp; e++) cnt[sd_co.recs[e].rec % n]++;
+        for (e = 0; e < nh; e++) hcnt[sd_co.hits[e].row >> SK_UNION_ROW_BITS]++;
+        for (s = 0; s < n; s++) {
+            c->res_off[a + s] = nr; c->res_hoff[a + s] = nhit;
+            nr += cnt[s]; nhit += hcnt[s];
+            cnt[s] = c->res_off[a + s]; hcnt[s] = c->res_hoff[a + s];
+        }
+        for (e = 0; e < nsp; e++) {
+            sk_tally_rec *out = c->res_recs + cnt[sd_co.recs[e].rec % n]++;
+            out->rec = sd_co.recs[e].rec / n; out->all = sd_co.recs[e].all; out->inf = sd_co.recs[e].inf;
+        }
+        for (e = 0; e < nh; e++) {
+            sk_hit *out = c->res_hits + hcnt[sd_co.hits[e].row >> SK_UNION_ROW_BITS]++;
+            out->pos = sd_co.hits[e].pos; out->row = sd_co.hits[e].row & ((1u << SK_UNION_ROW_BITS) - 1u);
+        }
+    }
+    c->res_off[ns] = nr; c->res_hoff[ns] = nhit;
+    return SK_OK;
+}
+
+enum { CO_PLAN_NONE, CO_PLAN_SELF, CO_PLAN_HOLD, CO_PLAN_MATE };
+static int co_plan(const sd_stream *st, const sd_chunk *c)
+{
+    if (!sd_co.acc || !st || !co_chunk_clean(c)) return CO_PLAN_NONE;
+    if (sd_co.mode != SD_PE) return CO_PLAN_SELF;
+    if (st == sd_co.pe_a) return CO_PLAN_HOLD;
+    {
+        const sd_stream *A = sd_co.pe_a;
+        return A && A->c && A->c->co == SD_CO_HELD && A->ci == 0 && A->c->nrec == c->nrec ? CO_PLAN_MATE : CO_PLAN_NONE;
+    }
+}
+
+/* the chunk's launches are in flight and its plan is to count it on the device: only the counters come home, then the picks */
+static int co_collect(sd_prog *p, uint32_t ns, sk_batch **batches, sd_chunk *c, int plan)
+{
+    const uint32_t nu = co_units(ns);
+    uint32_t k;
+    int rc;
+    for (k = 0; k < nu; k++) {
+        const uint32_t a = co_unit_first(k);
+        sk_union *u = sd_un.n ? sd_un.u[k] : NULL;
+        sk_ctx *ctx = u ? NULL : p[a].ctx;
+        uint64_t nsp = 0, nh = 0;
+        for (;;) {
+            uint64_t *cap = u ? &sd_un.hcap[k] : &p[a].hitcap;
+            if ((rc = u ? sk_union_tally_collect_counts(u, &nsp, &nh) : sk_tally_collect_counts(ctx, &nsp, &nh)) != SK_OK) return rc;
+            sd_res_bytes += 24;
+            if (nh <= *cap) break;
+            *cap = nh + nh / 4;                                 /* the log overflowed: once more with room */
+            if (!u) p[a].hitbuf = (sk_hit *)realloc(p[a].hitbuf, (size_t)p[a].hitcap * sizeof(sk_hit));
+            rc = u ? sk_union_tally_launch_ex(u, batches[sd_dev_of_strain(a)], *cap, 1) : sk_tally_launch(ctx, batches[sd_dev_of_strain(a)], SD_TYPE, SD_INFORMATIVE, *cap);
+            if (rc != SK_OK) return rc;
+        }
+        if (plan == CO_PLAN_HOLD) rc = sk_covacc_hold(sd_co.acc[k], ctx, u);
+        else if (plan == CO_PLAN_MATE) {
+            const sk_covacc_mate mate = { 1, 0, 1 };
+            rc = sk_covacc_add(sd_co.acc[k], ctx, u, 0, 0, 1, c->nrec, &mate);
+        } else if (sd_co.mode == SD_PEI) {
+            const sk_covacc_mate mate = { 0, c->co_a0 + 1, 2 };
+            const uint32_t npairs = c->nrec > c->co_a0 ? (c->nrec - c->co_a0) / 2 : 0;
+            rc = npairs ? sk_covacc_add(sd_co.acc[k], ctx, u, 0, c->co_a0, 2, npairs, &mate) : SK_OK;
+        } else rc = sk_covacc_add(sd_co.acc[k], ctx, u, 0, 0, 1, c->nrec, NULL);
+        if (rc != SK_OK) return rc;
+    }
+    if (plan == CO_PLAN_HOLD) { c->co = SD_CO_HELD; return SK_OK; }
+    if ((rc = co_deal(ns, p, c, CO_PICK, c->co_a0 == 1, 3)) != SK_OK) return rc;
+    c->co = SD_CO_FOLDED;
+    if (plan == CO_PLAN_MATE) {
+        sd_chunk *ca = sd_co.pe_a->c;
+        if ((rc = co_deal(ns, p, ca, CO_PICK_HOLD, 0, 3)) != SK_OK) return rc;
+        ca->co = SD_CO_FOLDED;
+        sd_co.post = ca;
+    }
+    return SK_OK;
+}
+
+/* a held PE1 chunk that does not fold with its mates' chunk after all: its results come home in full, and it goes the usual way */
+static int co_materialise(sd_prog *p, uint32_t ns, sd_chunk *c)
+{
+    int rc;
+    pthread_mutex_lock(&sd_dev_mu);
+    rc = co_deal(ns, p, c, CO_HOLD_ALL, 0, 0);
+    pthread_mutex_unlock(&sd_dev_mu);
+    if (rc != SK_OK) return rc;
+    c->co = SD_CO_NONE;
+    lanes_post(job_new(SD_JOB_TALLY, c, NULL));
+    return SK_OK;
+}
+
 /* start the scans of one uploaded chunk: against every union table, or strain by strain (they overlap on the devices) */
 static int sd_launch(sd_prog *p, uint32_t ns, sk_batch **batches)
 {
@@ -1580,7 +1818,8 @@ static int sd_launch(sd_prog *p, uint32_t ns, sk_batch **batches)
     int rc;
     if (sd_un.n) {
         for (g = 0; g < sd_un.n; g++)
-            if ((rc = sk_union_tally_launch(sd_un.u[g], batches[sd_dev_of_strain(g * sd_group)], sd_un.hcap[g])) != SK_OK) return rc;
+            if ((rc = sd_co.acc ? sk_union_tally_launch_ex(sd_un.u[g], batches[sd_dev_of_strain(g * sd_group)], sd_un.hcap[g], 1)
+                                : sk_union_tally_launch(sd_un.u[g], batches[sd_dev_of_strain(g * sd_group)], sd_un.hcap[g])) != SK_OK) return rc;
         return SK_OK;
     }
     for (s = 0; s < ns; s++) {
@@ -1604,14 +1843,16 @@ static int chunk_res_reserve(sd_chunk *c, uint64_t *rcap, uint64_t *hcap, uint64
     return c->res_recs && c->res_hits ? SK_OK : SK_E_NOMEM;
 }
 
+
 /* The results of the chunk whose scans are in flight, collected and laid out strain by strain IN THE CHUNK (res_recs/res_off,
  * res_hits/res_hoff) -- from the union tables (every group's results dealt to its members by a counting sort), or member by
  * member.  After this the device side may be overwritten by the next launch, and the lanes take it from here. */
-static int sd_collect(sd_prog *p, uint32_t ns, sk_batch **batches, sd_chunk *c)
+static int sd_collect(sd_prog *p, uint32_t ns, sk_batch **batches, sd_chunk *c, const sd_stream *st)
 {
     uint32_t g, s;
     int rc;
     uint64_t rcap = 0, hcap = 0, nr = 0, nhit = 0;
+    if ((rc = co_plan(st, c)) != CO_PLAN_NONE) return co_collect(p, ns, batches, c, rc);
     c->res_off = (uint64_t *)calloc(2 * ((size_t)ns + 1), sizeof(uint64_t));
     if (!c->res_off) return SK_E_NOMEM;
     c->res_hoff = c->res_off + ns + 1;
@@ -1629,6 +1870,7 @@ static int sd_collect(sd_prog *p, uint32_t ns, sk_batch **batches, sd_chunk *c)
                 if ((rc = sk_tally_launch(p[s].ctx, batches[sd_dev_of_strain(s)], SD_TYPE, SD_INFORMATIVE, p[s].hitcap)) != SK_OK ||
                     (rc = sk_tally_collect_sparse(p[s].ctx, (sk_tally_rec *)p[s].tallybuf, c->np, &nsp, p[s].hitbuf, &nh)) != SK_OK) return rc;
             }
+            sd_res_bytes += 16 + nsp * sizeof(sk_tally_rec) + nh * sizeof(sk_hit);
             if ((rc = chunk_res_reserve(c, &rcap, &hcap, nr + nsp, nhit + nh)) != SK_OK) return rc;
             memcpy(c->res_recs + nr, p[s].tallybuf, (size_t)nsp * sizeof(sk_tally_rec));
             memcpy(c->res_hits + nhit, p[s].hitbuf, (size_t)nh * sizeof(sk_hit));
@@ -1653,8 +1895,10 @@ static int sd_collect(sd_prog *p, uint32_t ns, sk_batch **batches, sd_chunk *c)
             if ((rc = sk_union_tally_collect(sd_un.u[g], sd_un.recs, sd_un.recs_cap, &nsp, sd_un.hits, &nh)) != SK_OK) return rc;
             if (nh <= sd_un.hcap[g]) break;
             sd_un.hcap[g] = nh + nh / 4;                    /* the log overflowed: once more with room */
-            if ((rc = sk_union_tally_launch(sd_un.u[g], batches[sd_dev_of_strain(a)], sd_un.hcap[g])) != SK_OK) return rc;
+            if ((rc = sd_co.acc ? sk_union_tally_launch_ex(sd_un.u[g], batches[sd_dev_of_strain(a)], sd_un.hcap[g], 1)
+                                : sk_union_tally_launch(sd_un.u[g], batches[sd_dev_of_strain(a)], sd_un.hcap[g])) != SK_OK) return rc;
         }
+        sd_res_bytes += 24 + nsp * sizeof(sk_tally_rec) + nh * sizeof(sk_hit);
         if ((rc = chunk_res_reserve(c, &rcap, &hcap, nr + nsp, nhit + nh)) != SK_OK) return rc;
         memset(cnt, 0, sizeof cnt); memset(hcnt, 0, sizeof hcnt);
         for (e = 0; e < nsp; e++) cnt[sd_un.recs[e].rec % n]++;
@@ -1766,10 +2010,12 @@ static int sd_tally_chunk(sd_prog *p, uint32_t ns, sk_batch **batches, sd_pool *
         if (rc == SK_OK && !launched) rc = sd_launch(p, ns, batches);
         if (rc == SK_OK) {
             sd_prefetch(st);                                     /* the next chunk goes up while this one is scanned */
-            rc = sd_collect(p, ns, batches, c);
+            rc = sd_collect(p, ns, batches, c, st);
         }
         pthread_mutex_unlock(&sd_dev_mu);
+        if (sd_co.post) { lanes_post(job_new(SD_JOB_TALLY, sd_co.post, NULL)); sd_co.post = NULL; }     /* (a PE1 chunk folded with this one) */
         if (rc != SK_OK) return rc;
+        if (c->co == SD_CO_HELD) { t_launch += now_s() - t0; return SK_OK; }      /* (its TALLY job follows when the PE2 chunk has shown what becomes of it) */
         t1 = now_s(); t_launch += t1 - t0; t0 = t1;
     }
     else sd_tc_hand(st, c, NULL);                                /* (nothing went up: the target cache still wants its records' lengths) */
@@ -1842,6 +2088,10 @@ static int stream_fill(sd_stream *st, sd_prog *p, uint32_t ns, sk_batch *batch, 
                 if (rc == 0) { sd_text_decline(st, c); chunk_free(c); t_tally += now_s() - t0; continue; }      /* the host parser's chunks follow */
                 uploaded = 1;                              /* (the batch holds it) */
             }
+            if (sd_co.acc && sd_co.mode == SD_PEI) {       /* (interleaved pairs: is the chunk's first record the last chunk's last record's mate?) */
+                c->co_a0 = c->nrec ? st->co_next : 0;
+                if (c->nrec) st->co_next = (c->nrec - c->co_a0) & 1u;
+            }
             rc = sd_tally_chunk(p, ns, st->bat[st->bcur], pool, c, uploaded, launched, st);
             if (rc == SK_OK) sd_launch_ahead(st, p, ns);
             t_tally += now_s() - t0;
@@ -1879,6 +2129,19 @@ static void emit_rows(sd_prog *p, const uint32_t *rows, uint32_t n, const char *
     const size_t nl = strlen(name);
     uint32_t j;
     char key[32];
+    if (sd_co.on) {                                        /* --coverage-only: no line, only what the script would count of it */
+        if (!sd_co.acc) { for (j = 0; j < n; j++) skc_add_hit(p->cov, name, p->h1, p->h2, rows[j]); return; }
+        if (!n || !((long long)p->h1 + p->h2 > sd_co.min)) return;
+        if (p->co_n + n > p->co_cap) {
+            p->co_cap = (p->co_n + n) * 2 + 1024;
+            p->co_rows = (uint32_t *)realloc(p->co_rows, (size_t)p->co_cap * sizeof *p->co_rows);
+            if (!p->co_rows) { p->co_cap = p->co_n = 0; p->job_rc = SK_E_NOMEM; return; }
+        }
+        memcpy(p->co_rows + p->co_n, rows, (size_t)n * sizeof *rows);
+        p->co_n += n;
+        if (p->co_n >= sd_co.flush_rows) co_flush(p, (uint32_t)(p - sd_ln.p));
+        return;
+    }
     for (j = 0; j < n; j++) {
         if (p->table_on_device && p->ks.packed[rows[j]] == 0) {       /* (a row whose key was not fetched with the informative ones: one at a time) */
             int frc;
@@ -1916,6 +2179,7 @@ static void emit_rows(sd_prog *p, const uint32_t *rows, uint32_t n, const char *
 static void emit_trailer(sd_prog *p, const char *f1, const char *what, long long v)
 {
     char num[64];
+    if (!p->zo) return;                                    /* (--coverage-only: there is no hit list) */
     skzo_append(p->zo, "#", 1);
     skzo_append(p->zo, f1, strlen(f1));
     skzo_append(p->zo, "\t", 1);
@@ -1939,7 +2203,7 @@ static uint32_t sp_lower(const sd_sp *q, uint32_t rec)
  * not all zero (a read shorter than k refreshes nothing, :444, so it re-emits what the read before it left).  A pair without
  * hits met with all-zero tallies leaves them all zero and emits nothing: skipped. */
 static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk *ca, uint32_t a0, const sd_chunk *cb, uint32_t b0,
-                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid)
+                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute)
 {
     const sd_sp *A = &ca->sp[s], *B = cb ? &cb->sp[s] : NULL;
     const uint64_t a_end = (uint64_t)a0 + (uint64_t)n * astep, b_end = (uint64_t)b0 + (uint64_t)n * astep;
@@ -1976,7 +2240,7 @@ static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk
             if (ib < B->n && B->rec[ib] == rb) { p->h2 = (int)B->all[ib]; p->i2 = (int)B->inf[ib]; }
             else { p->h2 = p->i2 = 0; b_valid = 2; }       /* (valid, no rows) */
         }
-        if (p->h1 + p->h2 >= 1 && p->i1 + p->i2 >= 1) {
+        if (!mute && p->h1 + p->h2 >= 1 && p->i1 + p->i2 >= 1) {
             if (have_copy_in || first_valid <= j) emit_rows(p, p->copy_rows, p->copy_n, f1);
             if (b_valid == 1) emit_rows(p, B->rows + B->hbeg[ib], B->hbeg[ib + 1] - B->hbeg[ib], f1);
         }
@@ -2022,6 +2286,9 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
     }
     for (s = 0; s < ns; s++) { p[s].h1 = p[s].i1 = p[s].h2 = p[s].i2 = 0; p[s].copy_n = 0; }
     t_sopen += now_s() - t_mark;
+    sd_co.mode = mode; sd_co.pe_a = mode == SD_PE ? &A : NULL;
+    A.co_next = 0;
+    if (sd_co.on && !sd_co.acc) sd_co_hostacc++;
     A.solo = mode != SD_PE;                              /* (two streams take turns at the tables: no scan ahead of the replay) */
 
     while ((got = stream_fill(&A, p, ns, batch, pool)) == 1) {
@@ -2066,7 +2333,20 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
             goto done;
         }
         t_lens += now_s() - t_mark; t_mark = now_s();
-        have_copy = post_replay(f1, ca, a0, cb, b0, astep, n, have_copy);
+        if (ca->co == SD_CO_HELD && (got = co_materialise(p, ns, ca)) != SK_OK) { chunk_free(held); break; }
+        if (mode == SD_PEI && cb == ca && ca->co == SD_CO_FOLDED && a0 != ca->co_a0) { got = SK_E_STATE; break; }     /* (never: the fold began elsewhere) */
+        if (sd_co.acc && n && ca->co == SD_CO_FOLDED &&
+            (mode == SD_SE ? !cb : mode == SD_PEI ? cb == ca : cb && cb != ca && cb->co == SD_CO_FOLDED)) {
+            /* the run was counted on the device: only the state its last pair leaves behind is replayed, and nothing is emitted */
+            sd_job *jb = job_new(SD_JOB_REPLAY, ca, cb);
+            jb->f1 = f1; jb->a0 = a0 + (n - 1) * astep; jb->b0 = b0 + (n - 1) * astep; jb->astep = astep; jb->n = 1; jb->have_copy = 1; jb->mute = 1;
+            lanes_post(jb);
+            have_copy = 1;
+            sd_co_dev++;
+        } else {
+            have_copy = post_replay(f1, ca, a0, cb, b0, astep, n, have_copy);
+            if (sd_co.on) sd_co_replayed++;
+        }
         t_replay += now_s() - t_mark;
         if (held) { chunk_free(held); if (cb) A.ci++; }  /* PEI across a chunk boundary: the mate was A's next record */
         else {
@@ -2097,6 +2377,20 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
         fprintf(err, "strain_detect: device error on %s: %s (%s)\n", f1, sk_strerror(got), sk_last_error(p[0].ctx));
         goto done;
     }
+    if (sd_co.acc) {                                     /* the target's two numbers per strain, from the device's counters */
+        uint32_t k, m;
+        for (s = 0; s < ns; s++) { co_flush(&p[s], s); if (p[s].job_rc != SK_OK) got = p[s].job_rc; }
+        for (k = 0; k < sd_co.nacc && got >= 0; k++) {
+            uint64_t uq[SK_UNION_MAX], tot[SK_UNION_MAX];
+            const uint32_t a = co_unit_first(k), n = co_unit_members(k);
+            pthread_mutex_lock(&sd_dev_mu);
+            rc = sk_covacc_finish_target(sd_co.acc[k], uq, tot);
+            pthread_mutex_unlock(&sd_dev_mu);
+            if (rc != SK_OK) { got = rc; break; }
+            for (m = 0; m < n; m++) if (skc_add_counts(p[a + m].cov, f1, uq[m], tot[m])) got = SK_E_NOMEM;
+        }
+        if (got < 0) { fprintf(err, "strain_detect: device error on %s: %s (%s)\n", f1, sk_strerror(got), sk_last_error(p[0].ctx)); goto done; }
+    }
     for (s = 0; s < ns; s++) {
         emit_trailer(&p[s], f1, "total_kmer_evaluated", (long long)evaluated);
         emit_trailer(&p[s], f1, "total_reads_evaluated", (long long)reads);
@@ -2112,6 +2406,7 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
     status = 0;
 done:
     lanes_drain();                                       /* (every way out: nothing of this file is in work when its streams go) */
+    sd_co.pe_a = NULL;
     t_mark = now_s();
     stream_close(&A);
     stream_close(&B);
@@ -2343,8 +2638,8 @@ static int sd_strain_flags(sd_prog *p, const char *a, const char *g, const char 
         free(rows);
         if (rc) { fprintf(p->err, "strain_detect: device error: %s (%s)\n", sk_strerror(rc), sk_last_error(p->ctx)); return 1; }
     }
-    p->zo = skzo_open(sd_zpool, o);
-    if (!p->zo) { fprintf(p->err, "could not open *gzout file outfile %s in quantify_hits_all_files()\n", o); return 1; }
+    p->zo = sd_co.on ? NULL : skzo_open(sd_zpool, o);      /* (--coverage-only: -o only names the strain and the table) */
+    if (!p->zo && !sd_co.on) { fprintf(p->err, "could not open *gzout file outfile %s in quantify_hits_all_files()\n", o); return 1; }
     p->o_path = strdup(o);
     return 0;
 }
@@ -2454,12 +2749,26 @@ static void sd_strain_close(sd_prog *p)
     if (getenv("SK_LEAK_AT_EXIT") && strcmp(getenv("SK_LEAK_AT_EXIT"), "0")) { memset(p, 0, sizeof *p); return; }
     if (p->ctx) { skh_pack_cache_set(p->ctx, NULL, NULL); sk_ctx_destroy(p->ctx); }
     skh_keyset_free(&p->ks);
-    free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path);
+    free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows);
     skc_destroy(p->cov);
     memset(p, 0, sizeof *p);
 }
 
 static void close_one(void *arg, uint32_t s) { sd_strain_close(&((sd_prog *)arg)[s]); }
+
+/* one line of a -B list, cut in place: <type> TAB <file> [TAB <second file>] (src/strain_detect.c:300-340) */
+enum { SD_LL_TARGET, SD_LL_EMPTY, SD_LL_UNKNOWN, SD_LL_NO_FIRST, SD_LL_NO_SECOND };
+static int sd_list_line(char *line, int *m, char **tok, char **f1, char **f2)
+{
+    char *nl = strchr(line, '\n');
+    if (nl) *nl = '\0';
+    *f1 = *f2 = NULL;
+    if (!(*tok = strtok(line, "\t"))) return SD_LL_EMPTY;
+    if ((*m = file_type(*tok)) == SD_UNKNOWN) return SD_LL_UNKNOWN;
+    if (!(*f1 = strtok(NULL, "\t"))) return SD_LL_NO_FIRST;
+    if (*m == SD_PE && !(*f2 = strtok(NULL, "\t"))) return SD_LL_NO_SECOND;
+    return SD_LL_TARGET;
+}
 
 /* the metagenome side of main (src/strain_detect.c:263-384), for ns strains at once */
 static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const char *b2, int mode, FILE *out, FILE *err)
@@ -2470,27 +2779,51 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     sd_pin_open(p[0].ctx, sd_chunk_bytes());
     sd_all_p = p; sd_all_ns = ns;
     sd_unions_open(p, ns);
+    sd_co.host = 0;
+    if (sd_co.on && B) {                                 /* the script keys its samples by basename: two targets that share one are one sample */
+        FILE *fp = fopen(B, "r");
+        char *line = NULL, **seen = NULL;
+        size_t cap = 0;
+        uint32_t nseen = 0, k;
+        int nomem = 0;
+        while (fp && !nomem && getline(&line, &cap, fp) != -1) {
+            char *tok, *f1, *f2, **grown, *copy;
+            int m;
+            if (sd_list_line(line, &m, &tok, &f1, &f2) != SD_LL_TARGET) continue;       /* (the lines the loop below quantifies, and no others) */
+            if (strrchr(f1, '/')) f1 = strrchr(f1, '/') + 1;
+            for (k = 0; k < nseen; k++) if (!strcmp(seen[k], f1)) sd_co.host = 1;
+            grown = (char **)realloc(seen, ((size_t)nseen + 1) * sizeof *seen);
+            copy = grown ? strdup(f1) : NULL;
+            if (grown) seen = grown;
+            if (!copy) { nomem = 1; break; }
+            seen[nseen++] = copy;
+        }
+        for (k = 0; k < nseen; k++) free(seen[k]);
+        free(seen); free(line);
+        if (fp) fclose(fp);
+        if (nomem) { fprintf(err, "strain_detect: out of memory\n"); sd_unions_close(); return 1; }
+        if (sd_co.host) fprintf(err, "strain_detect: --coverage-only: two targets of %s share a file name, the script counts them as one sample: "
+                                     "this run is counted on the host\n", B);
+    }
+    {
+        const int crc = co_open(p, ns);
+        if (crc != SK_OK) { fprintf(err, "strain_detect: device error: %s (%s)\n", sk_strerror(crc), sk_last_error(p[0].ctx)); sd_unions_close(); return 1; }
+    }
     pool_start(&pool, ns);
     lanes_start(p, ns);
     if (B) {
         FILE *fp = fopen(B, "r");
-        char *line = NULL, *nl, *tok, *f1, *f2;
+        char *line = NULL, *tok, *f1, *f2;
         size_t cap = 0;
-        if (!fp) { fprintf(err, "could not read file file_of_filenames %s in quantify_hits_all_files()\n", B); lanes_stop(); pool_stop(&pool); sd_unions_close(); return 1; }
+        if (!fp) { fprintf(err, "could not read file file_of_filenames %s in quantify_hits_all_files()\n", B); lanes_stop(); pool_stop(&pool); co_close(); sd_unions_close(); return 1; }
         while (!bad && getline(&line, &cap, fp) != -1) {
             int m;
-            if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
-            tok = strtok(line, "\t");
-            if (!tok) { fprintf(err, "strain_detect: empty line in %s (the original program crashes here)\n", B); bad = 1; break; }
-            m = file_type(tok);
-            if (m == SD_UNKNOWN) { fprintf(out, "unknown file type skipping line (%s)\n", tok); continue; }
-            f1 = strtok(NULL, "\t");
-            if (!f1) { fprintf(out, "ERROR: no first file specified for %s\n", line); continue; }
-            if (m == SD_PE) {
-                f2 = strtok(NULL, "\t");
-                if (!f2) { fprintf(out, "ERROR: no second file specified for PE: %s\n", line); continue; }
-                bad = sd_quantify(p, ns, batch, &pool, f1, f2, m);
-            } else bad = sd_quantify(p, ns, batch, &pool, f1, NULL, m);
+            const int what = sd_list_line(line, &m, &tok, &f1, &f2);
+            if (what == SD_LL_EMPTY) { fprintf(err, "strain_detect: empty line in %s (the original program crashes here)\n", B); bad = 1; break; }
+            if (what == SD_LL_UNKNOWN) { fprintf(out, "unknown file type skipping line (%s)\n", tok); continue; }
+            if (what == SD_LL_NO_FIRST) { fprintf(out, "ERROR: no first file specified for %s\n", line); continue; }
+            if (what == SD_LL_NO_SECOND) { fprintf(out, "ERROR: no second file specified for PE: %s\n", line); continue; }
+            bad = sd_quantify(p, ns, batch, &pool, f1, m == SD_PE ? f2 : NULL, m);
         }
         free(line);
         fclose(fp);
@@ -2499,6 +2832,7 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     pool_stop(&pool);
     sd_unmap_wait();
     sd_batch_cache_close();
+    co_close();
     if (getenv("SK_LEAK_AT_EXIT") && strcmp(getenv("SK_LEAK_AT_EXIT"), "0")) return bad;     /* (the process is about to end: see sd_strain_close) */
     { const double t0 = now_s(); sd_unions_close(); t_uclose = now_s() - t0; }
     return bad;
@@ -2614,7 +2948,7 @@ static int sd_drop(sd_prog *p, uint32_t ns)
 static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_adoption *ad)
 {
     const char *a = NULL, *r = NULL, *b = NULL, *b2 = NULL, *B = NULL, *tt = NULL, *g = NULL, *o = NULL, *S = NULL, *env;
-    int c, j, mode = SD_SE, status = 1, device = 0, n_S = 0, want_cov = 0;
+    int c, j, mode = SD_SE, status = 1, device = 0, n_S = 0, want_cov = 0, cov_only = 0;
     skzo_pool zpool;
     const char *cov_file = NULL, *tc_dir = NULL;
     long long cov_min = 1;
@@ -2641,12 +2975,21 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             cov_file = argv[c][16] ? argv[c] + 17 : NULL;
             continue;
         }
+        /* "--coverage-only[=FILE]": that table and NO hit list -- -o only names the strain and the table's default path; the counts
+         * stay on the device (sk_covacc) wherever the reads allow it */
+        if (!strncmp(argv[c], "--coverage-only", 15) && (argv[c][15] == 0 || argv[c][15] == '=')) {
+            cov_only = 1;
+            cov_file = argv[c][15] ? argv[c] + 16 : NULL;
+            continue;
+        }
         if (!strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { cov_min = atoll(argv[++c]); continue; }
         if (!strcmp(argv[c], "--target-cache") && c + 1 < argc) { tc_dir = argv[++c]; continue; }       /* (extension: the target cache, see sd_tc) */
         if (!strncmp(argv[c], "--target-cache=", 15)) { tc_dir = argv[c] + 15; continue; }
         argv[j++] = argv[c];
     }
     argc = j;
+    sd_co.on = 0;
+    if (cov_only && want_cov) { fputs("strain_detect: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n", err); return sd_drop(p, ns); }
 
     optind = 1;
     while ((c = getopt(argc, argv, "g:r:a:A:b:c:B:S:M:o:t:Hhuspn")) != -1) {
@@ -2673,6 +3016,11 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (r || a || o || S || g) { fputs("strain_detect: the resident strains bring their own -r, -a, -o and -g\n", err); return sd_drop(p, ns); }
         if (cov_file) { fputs("strain_detect: --coverage-depth=FILE names one file; the resident strains each have their own\n", err); return sd_drop(p, ns); }
         o = ad->o[0];
+    }
+    if (cov_only) {
+        if (cov_file && ((S && !a && !o && !r) || (ad && ad->o))) { fputs("strain_detect: --coverage-only=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        if (!o && !S && !(ad && ad->o)) { fputs("strain_detect: --coverage-only needs -o: it names the strain and the table's default path (no hit list is written)\n", err); return sd_drop(p, ns); }
+        want_cov = 1;
     }
     if (ad) { a = ad->a[0]; r = "(resident)"; S = NULL; }
     if (S && !a && !o && !r) {
@@ -2701,6 +3049,9 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     if ((env = getenv("SK_SD_GROUP")) != NULL && atoi(env) >= 1 && atoi(env) <= SK_UNION_MAX) sd_group = (uint32_t)atoi(env);
     memset(sd_dev.ctx, 0, sizeof sd_dev.ctx);
     t_begin = now_s();
+    sd_co.on = cov_only; sd_co.min = cov_min;
+    sd_co.flush_rows = (env = getenv("SK_SD_CO_FLUSH_ROWS")) != NULL && atoll(env) >= 1 ? (uint64_t)atoll(env) : 1u << 20;
+    sd_res_bytes = 0;
     sd_tc_open(tc_dir, err);
     n_text_taken = n_text_declined = 0;                  /* (per run: the library entry points may be called again in one process) */
     {
@@ -2838,8 +3189,13 @@ done:
     if (getenv("SK_SD_TIMING") && t_pw_parse > 0)
         fprintf(err, "strain_detect timing: parser threads, summed: parsing %.2f s, waiting for a segment %.2f s, for their turn to hand chunks on %.2f s, for room in the queue %.2f s\n",
                 t_pw_parse, t_pw_seg, t_pw_turn, t_pw_push);
+    if (getenv("SK_SD_RESULT_BYTES"))
+        fprintf(err, "strain_detect: scan results copied from the device: %llu bytes; --coverage-only: %llu runs counted on the device, %llu replayed, "
+                     "%llu targets on the host accumulator (the process's totals)\n", (unsigned long long)sd_res_bytes,
+                (unsigned long long)sd_co_dev, (unsigned long long)sd_co_replayed, (unsigned long long)sd_co_hostacc);
     sd_tc_close(err);
     sd_pin_close();
+    sd_co.on = 0;
     {   /* closing a strain = finishing its gz output, freeing its device context and tables: strain by strain on threads */
         sd_pool cp;
         const double t0 = now_s();

@@ -20,6 +20,7 @@ typedef struct skc_acc skc_acc;
 skc_acc *skc_create(int64_t min_hits);
 void skc_destroy(skc_acc *a);
 int skc_add_hit(skc_acc *a, const char *metagenome, int64_t hits_pe1, int64_t hits_pe2, uint32_t row);
+int skc_add_counts(skc_acc *a, const char *metagenome, uint64_t unique, uint64_t total);
 int skc_add_trailer(skc_acc *a, const char *metagenome, const char *name, int64_t value);
 int skc_report(skc_acc *a, sk_ctx *ctx, const char *hits_file_name, FILE *out, FILE *err);
 /* strain_detect's key set built on the device (sk_host.c): SK_OK, the ctx holds the table and *ks the keys in row order; SK_E_UNSUPPORTED: a
@@ -57,6 +58,17 @@ typedef struct sk_batch_pack_hook {
     void *d_pack; uint32_t *d_odd;
 } sk_batch_pack_hook;
 int  sk_batch_pack_hook_(sk_batch *b, int want_room, sk_batch_pack_hook *out);
+/* The results a launch left on the device (sk_tally_collect_counts / sk_union_tally_collect_counts), for the coverage accumulator
+ * (sk_covacc.hip): d_recs = nrecs triples {record * max(members, 1) + member, all, informative}, d_hits = nhits log entries,
+ * d_rec_start = the batch's nrec record starts.  members 0: a single context's launch (a log entry's row is the row itself).
+ * SK_E_STATE when nothing is held or the log ran over. */
+typedef struct sk_tally_view {
+    sk_ctx *owner; int device; uint32_t members;
+    const uint32_t *d_recs; uint64_t nrecs;
+    const sk_hit *d_hits; uint64_t nhits;
+    const uint32_t *d_rec_start; uint32_t nrec;
+} sk_tally_view;
+int sk_tally_view_(sk_ctx *ctx, sk_union *u, sk_tally_view *out);
 #ifdef __cplusplus
 }
 #endif

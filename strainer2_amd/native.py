@@ -63,6 +63,9 @@ ABI_SYMBOLS = [
     "skh_kmer_scrub_count_multi_main",
     "sk_pack_device", "sk_scan_pinned_pack_many", "sk_pack_ticket_wait", "sk_pack_release", "skh_pack_cache_set", "skh_pack_cache_stats",
     "sk_batch_pack_home", "sk_batch_pack_wait", "skh_target_cache_stats",
+    "sk_covacc_create", "sk_covacc_destroy", "sk_covacc_hold", "sk_covacc_add", "sk_covacc_add_rows", "sk_covacc_finish_target", "sk_covacc_rows",
+    "sk_covacc_pick", "sk_covacc_fetch_hold", "skh_coverage_only_stats",
+    "sk_tally_collect_counts", "sk_tally_fetch_held", "sk_union_tally_launch_ex", "sk_union_tally_collect_counts", "sk_union_tally_fetch_held",
 ]
 
 
@@ -170,6 +173,7 @@ lib.skh_scan_list_uncut.argtypes = lib.skh_scan_list.argtypes
 lib.skh_scan_list_many.argtypes = [C.c_void_p, C.c_uint32] + lib.skh_scan_list.argtypes[1:]
 lib.skh_print_counts.argtypes = [C.c_void_p, C.POINTER(_KeysetStruct), C.c_void_p, C.c_int]
 lib.skh_kmer_scrub_count_main.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
+lib.skh_strain_detect_main.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
 lib.skh_decode_file.argtypes = [C.c_char_p, C.c_uint64, _SINK, C.c_void_p, C.POINTER(C.c_uint64)]
 lib.skh_decode_file.restype = C.c_int64
 
@@ -207,6 +211,30 @@ lib.sk_union_tally_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
 lib.sk_union_tally_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
 lib.sk_union_last_error.argtypes = [C.c_void_p]
 lib.sk_union_last_error.restype = C.c_char_p
+
+
+class CovaccMate(C.Structure):
+    _fields_ = [("held", C.c_int), ("b0", C.c_uint32), ("bstep", C.c_uint32)]
+
+
+lib.sk_tally_collect_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+lib.sk_tally_fetch_held.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+lib.sk_union_tally_launch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+lib.sk_union_tally_collect_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+lib.sk_union_tally_fetch_held.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+lib.sk_covacc_create.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+lib.sk_covacc_destroy.argtypes = [C.c_void_p]
+lib.sk_covacc_destroy.restype = None
+lib.sk_covacc_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sk_covacc_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CovaccMate)]
+lib.sk_covacc_add_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
+lib.sk_covacc_finish_target.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sk_covacc_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+lib.sk_covacc_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                               C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+lib.sk_covacc_fetch_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+lib.skh_coverage_only_stats.argtypes = [C.POINTER(C.c_uint64)] * 3 + [C.c_int]
+lib.skh_coverage_only_stats.restype = None
 lib.sk_union_count_enable.argtypes = [C.c_void_p, C.c_uint32]
 lib.sk_union_context.argtypes = [C.c_void_p]
 lib.sk_union_context.restype = C.c_void_p
@@ -402,6 +430,22 @@ class KmerContext:
         self._ck(lib.sk_tally_collect_sparse(self._h, recs.ctypes.data, nrec, C.byref(nr), hits.ctypes.data, C.byref(nh)))
         assert nr.value <= nrec
         return recs[: nr.value], hits[: min(nh.value, cap)], nh.value
+
+    def tally_collect_counts(self):
+        """sk_tally_collect_counts of the launch in flight: (hit records, log entries); the results themselves stay on the device
+        for CoverageAcc.add / tally_fetch_held until this context's next launch"""
+        nr, nh = C.c_uint64(0), C.c_uint64(0)
+        self._ck(lib.sk_tally_collect_counts(self._h, C.byref(nr), C.byref(nh)))
+        self._held = (nr.value, nh.value, self._inflight[1])
+        return nr.value, nh.value
+
+    def tally_fetch_held(self):
+        """sk_tally_fetch_held: the held results in tally_collect_sparse's form, (recs[m, 3], hits as stored)"""
+        nr, nh, cap = self._held
+        recs = np.zeros((max(nr, 1), 3), dtype=np.uint32)
+        hits = np.zeros((max(min(nh, cap), 1), 2), dtype=np.uint32)
+        self._ck(lib.sk_tally_fetch_held(self._h, recs.ctypes.data, nr, hits.ctypes.data))
+        return recs[:nr], hits[: min(nh, cap)]
 
     def pinned_alloc(self, nbytes):
         """A pinned host buffer as a writable numpy uint8 array (free with pinned_free(arr))."""
@@ -644,6 +688,14 @@ def target_cache_stats(reset=False):
     return tuple(int(x.value) for x in v)
 
 
+def coverage_only_stats(reset=False):
+    """skh_coverage_only_stats: (runs counted on the device, runs replayed on the host, targets counted by the host accumulator) of
+    the strain_detect --coverage-only runs in this process"""
+    v = [C.c_uint64(0) for _ in range(3)]
+    lib.skh_coverage_only_stats(*[C.byref(x) for x in v], int(reset))
+    return tuple(int(x.value) for x in v)
+
+
 class TallyBatch:
     """A batch of records resident on a context's device (sk_batch_*), to be tallied against one or more tables."""
 
@@ -803,6 +855,28 @@ class KmerUnion:
         order = np.lexsort((out[:, 2], out[:, 1], out[:, 0]))
         return tally.reshape(nrec, n, 2), out[order]
 
+    def tally_launch(self, batch, hits_cap=None, results_stay=False):
+        """sk_union_tally_launch[_ex] on a filled TallyBatch; returns at once.  results_stay: only the counters travel home with
+        the launch (for tally_collect_counts)"""
+        cap = max(batch.nbytes * 2, 16) if hits_cap is None else hits_cap
+        self._uck(lib.sk_union_tally_launch_ex(self._h, batch._h, cap, int(bool(results_stay))))
+        self._inflight = (batch.nrec, cap)
+
+    def tally_collect_counts(self):
+        """sk_union_tally_collect_counts: ((record, member) pairs hit, log entries); the results stay on the device"""
+        nr, nh = C.c_uint64(0), C.c_uint64(0)
+        self._uck(lib.sk_union_tally_collect_counts(self._h, C.byref(nr), C.byref(nh)))
+        self._held = (nr.value, nh.value, self._inflight[1])
+        return nr.value, nh.value
+
+    def tally_fetch_held(self):
+        """sk_union_tally_fetch_held: (recs[m, 3] = (record * members + member, all, informative), hits[n, 2] as stored)"""
+        nr, nh, cap = self._held
+        recs = np.zeros((max(nr, 1), 3), dtype=np.uint32)
+        hits = np.zeros((max(min(nh, cap), 1), 2), dtype=np.uint32)
+        self._uck(lib.sk_union_tally_fetch_held(self._h, recs.ctypes.data, nr, hits.ctypes.data))
+        return recs[:nr], hits[: min(nh, cap)]
+
     # ---- COUNT on the union (sk_union_count_enable / sk_union_context / sk_union_counts_fold)
     def _uck(self, rc):
         if rc:
@@ -840,6 +914,89 @@ class KmerUnion:
             self._batch = None
         if getattr(self, "_h", None):
             lib.sk_union_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class CoverageAcc:
+    """The coverage accumulator (sk_covacc_*): per member (strain) and target, how many hit lines pass --min-kmer-hits and how
+    many distinct rows they name, folded on the device from the results a tally launch leaves there
+    (KmerContext/KmerUnion.tally_collect_counts)."""
+
+    def __init__(self, ctx: KmerContext, nrows, min_kmer_hits=0):
+        self._ctx = ctx
+        self.nrows = np.ascontiguousarray(nrows, dtype=np.uint32).reshape(-1)
+        self._h = C.c_void_p()
+        ctx._ck(lib.sk_covacc_create(ctx._h, len(self.nrows), self.nrows.ctypes.data, int(min_kmer_hits), C.byref(self._h)))
+
+    @staticmethod
+    def _who(src):
+        return (None, src._h) if isinstance(src, KmerUnion) else (src._h, None)
+
+    def hold(self, src):
+        """sk_covacc_hold: keep a copy of the held results of src's launch (a KmerContext or a KmerUnion) for a later add(mate=('held', ..))"""
+        c, u = self._who(src)
+        self._ctx._ck(lib.sk_covacc_hold(self._h, c, u))
+
+    def add(self, src, a0, astep, npairs, mate=None, member0=0):
+        """sk_covacc_add: fold the held results of src's launch.  mate: None (single reads), ('same', b0, bstep) or ('held', b0, bstep)"""
+        c, u = self._who(src)
+        m = None
+        if mate is not None:
+            m = C.byref(CovaccMate({"same": 0, "held": 1}[mate[0]], mate[1], mate[2]))
+        self._ctx._ck(lib.sk_covacc_add(self._h, c, u, member0, a0, astep, npairs, m))
+
+    def pick(self, src=None, first=False, ntail=1, from_hold=False, cap=4096, hits_cap=65536):
+        """sk_covacc_pick: (records[n, 3], hits[m, 2]) of record 0 (first) and the last ntail records of src's held launch, or of
+        the launch held here (from_hold), in the collect calls' form"""
+        c, u = (None, None) if from_hold else self._who(src)
+        recs = np.zeros((cap, 3), dtype=np.uint32)
+        hits = np.zeros((hits_cap, 2), dtype=np.uint32)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        self._ctx._ck(lib.sk_covacc_pick(self._h, c, u, int(from_hold), int(first), ntail, recs.ctypes.data, cap, C.byref(n),
+                                         hits.ctypes.data, hits_cap, C.byref(nh)))
+        if n.value > cap or nh.value > hits_cap:
+            return self.pick(src, first, ntail, from_hold, max(cap, int(n.value)), max(hits_cap, int(nh.value)))
+        return recs[: n.value], hits[: nh.value]
+
+    def fetch_hold(self, cap=1 << 16, hits_cap=1 << 18):
+        """sk_covacc_fetch_hold: the launch held here, in full, in the collect calls' form"""
+        recs = np.zeros((cap, 3), dtype=np.uint32)
+        hits = np.zeros((hits_cap, 2), dtype=np.uint32)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        self._ctx._ck(lib.sk_covacc_fetch_hold(self._h, recs.ctypes.data, cap, C.byref(n), hits.ctypes.data, hits_cap, C.byref(nh)))
+        if n.value > cap or nh.value > hits_cap:
+            return self.fetch_hold(max(cap, int(n.value)), max(hits_cap, int(nh.value)))
+        return recs[: n.value], hits[: nh.value]
+
+    def add_rows(self, member, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        self._ctx._ck(lib.sk_covacc_add_rows(self._h, member, rows.ctypes.data, len(rows)))
+
+    def rows(self, member):
+        """member's per-row counters as they stand"""
+        out = np.zeros(max(int(self.nrows[member]), 1), dtype=np.uint32)
+        self._ctx._ck(lib.sk_covacc_rows(self._h, member, out.ctypes.data))
+        return out[: int(self.nrows[member])]
+
+    def finish_target(self):
+        """(unique[nmembers], total[nmembers]) as uint64 arrays; the counters are zero afterwards"""
+        uq = np.zeros(len(self.nrows), dtype=np.uint64)
+        tot = np.zeros(len(self.nrows), dtype=np.uint64)
+        self._ctx._ck(lib.sk_covacc_finish_target(self._h, uq.ctypes.data, tot.ctypes.data))
+        return uq, tot
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.sk_covacc_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -928,6 +1085,20 @@ def decode_file(path, chunk_bytes=1 << 26):
     if nrec < 0:
         raise SKError(int(nrec), path)
     return chunks, int(nrec), bases.value
+
+
+def run_strain_detect_inprocess(argv, stdout_path, stderr_path):
+    """Call strain_detect's main() in this process (bin/strain_detect is the same function): what coverage_only_stats() and
+    target_cache_stats() count afterwards is that run's."""
+    args = [b"strain_detect"] + [os.fsencode(a) for a in argv]
+    arr = (C.c_char_p * (len(args) + 1))(*args, None)
+    fo = _libc.fopen(os.fsencode(stdout_path), b"w")
+    fe = _libc.fopen(os.fsencode(stderr_path), b"w")
+    try:
+        return lib.skh_strain_detect_main(len(args), arr, fo, fe)
+    finally:
+        _libc.fclose(fo)
+        _libc.fclose(fe)
 
 
 def run_cli_inprocess(argv, stdout_path, stderr_path):

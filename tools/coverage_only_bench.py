@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""strain_detect --coverage-only against --coverage-depth, measured end to end (one MI355X): `strain_detect -S` with 8 and with 32
+strains of strainer2_amd/cfg5.py over a -B list of 150-base FASTQ targets of --gbases in /dev/shm (the targets of
+tools/target_cache_bench.py), once as .gz files and once plain; the two flags alternate, three rounds.  The MD5 of the strains'
+tables is compared inside the run: both flags must write the same bytes, and --coverage-only no hit list.
+
+Every GPU step is one run of the program under `timeout` of its own; the first step that fails, or whose tables differ, ends the
+whole measurement.  Per step: the pass (the program's own "total before close" less "setup", SK_SD_TIMING), wall time of the
+process, CPU-seconds (user + system of the child) and the bytes of scan results copied from the device (SK_SD_RESULT_BYTES).
+--parent-exe names strain_detect of a build of the parent commit, which runs --coverage-depth three times per case: the figures the
+new flag is to be set against.
+
+    python tools/coverage_only_bench.py [--gbases 1.5] [--parent-exe PATH] [--out profiles/coverage_only_bench.txt]
+"""
+import argparse
+import hashlib
+import os
+import re
+import resource
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+import zlib
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from strainer2_amd import cfg5  # noqa: E402
+from text_parse_bench import reads_text  # noqa: E402  (the generator of the other ingest measurements)
+
+EXE = os.path.join(REPO, "strainer2_amd", "bin", "strain_detect")
+PASS = re.compile(rb"strain_detect timing: setup ([0-9.]+) s,.*?total before close ([0-9.]+) s")
+BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
+
+
+class StepFailed(Exception):
+    pass
+
+
+def row(rs, key, spec):
+    return " ".join(format(r[key], spec) for r in rs)
+
+
+def step(exe, argv, env, limit, cwd, ns, hit_lists):
+    """one run of the program under its own time limit -> measurements; raises StepFailed (nothing more is started then)"""
+    for s in range(ns):
+        for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth"):
+            if os.path.exists(os.path.join(cwd, f)):
+                os.remove(os.path.join(cwd, f))
+    r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
+    t0 = time.perf_counter()
+    p = subprocess.run(["timeout", "-k", "10", str(limit), exe] + argv, env=env, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    wall = time.perf_counter() - t0
+    r1 = resource.getrusage(resource.RUSAGE_CHILDREN)
+    if p.returncode != 0:
+        raise StepFailed(f"exit status {p.returncode}: {p.stderr.decode(errors='replace')[-1500:]}")
+    h = hashlib.md5()
+    for s in range(ns):
+        if os.path.exists(os.path.join(cwd, f"out{s}.gz")) != hit_lists:
+            raise StepFailed(f"out{s}.gz {'is missing' if hit_lists else 'was written'}")
+        with open(os.path.join(cwd, f"out{s}.gz.coverage_depth"), "rb") as f:
+            h.update(f.read())
+    m = PASS.search(p.stderr)
+    b = BYTES.search(p.stderr)
+    return dict(wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
+                passed=float(m.group(2)) - float(m.group(1)) if m else float("nan"),
+                d2h=int(b.group(1)) if b else -1, dev=int(b.group(2)) if b else -1, replayed=int(b.group(3)) if b else -1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gbases", type=float, default=1.5, help="bases per list")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--strains", default="8,32")
+    ap.add_argument("--limit", type=int, default=150, help="seconds one run of the program may take")
+    ap.add_argument("--parent-exe", default=None, help="strain_detect of a build of the parent commit")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    args = ap.parse_args()
+    if args.parent_exe:
+        args.parent_exe = os.path.abspath(args.parent_exe)     # (the runs' working directory is the data's)
+    counts = [int(x) for x in args.strains.split(",")]
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SK_") or k in ("SK_THREADS", "SK_DEVICE")}
+    env["SK_SD_TIMING"] = "1"
+    env["SK_SD_RESULT_BYTES"] = "1"
+    ok = True
+    with tempfile.TemporaryDirectory(dir=args.tmp) as tmp:
+        rng = np.random.default_rng(11)
+        genome = []
+        for s in range(max(counts)):
+            cfg5.write_strain(tmp, s)
+            genome.append(cfg5.strain(s))
+        for ns in counts:
+            with open(os.path.join(tmp, f"S{ns}.txt"), "w") as f:
+                f.write("".join(f"s{s}.fa\ts{s}.inf\tout{s}.gz\n" for s in range(ns)))
+        per = 500_000                                            # reads per file (0.075 Gbase); one text, one deflate, many names
+        text = bytearray(reads_text(rng, per, True))
+        seq = np.frombuffer(text, dtype=np.uint8).reshape(per, -1)
+        for i in range(0, per, 50):                              # (2 % of the reads are a strain's, as in cfg5)
+            g = genome[int(rng.integers(0, min(counts)))]
+            a = int(rng.integers(0, g.size - 150))
+            seq[i, 16:166] = g[a:a + 150]
+        text = bytes(text)
+        nfiles = max(int(args.gbases * 1e9 / (per * 150)), 2)
+        co = zlib.compressobj(6, zlib.DEFLATED, 31)
+        gz = co.compress(text) + co.flush()
+        lists = {}
+        for kind, blob, ext in (("plain FASTQ", text, ".fq"), ("FASTQ .gz", gz, ".fq.gz")):
+            for i in range(nfiles):
+                with open(os.path.join(tmp, f"r{i}{ext}"), "wb") as f:
+                    f.write(blob)
+            lst = "B" + ext + ".txt"
+            with open(os.path.join(tmp, lst), "w") as f:
+                f.write("".join(f"SE\tr{i}{ext}\n" for i in range(nfiles)))
+            lists[kind] = lst
+        gbase = nfiles * per * 150 / 1e9
+        say(f"strain_detect -S <cfg5 strains of {cfg5.STRAIN_BP} bp> -B <list>, {nfiles} files of {per} 150-base FASTQ reads per list "
+            f"({gbase:.2f} Gbase), in {tmp}; {os.cpu_count()} CPUs seen, SK_THREADS={env.get('SK_THREADS', 'default')}; "
+            f"the flags alternate, {args.rounds} rounds")
+        try:
+            for ns in counts:
+                for kind, lst in lists.items():
+                    argv = ["-S", f"S{ns}.txt", "-B", lst]
+                    res = {"--coverage-depth": [], "--coverage-only": []}
+                    md5 = None
+                    for rnd in range(args.rounds):
+                        for flag in res:
+                            r = step(EXE, argv + [flag], dict(env), args.limit, tmp, ns, flag == "--coverage-depth")
+                            md5 = md5 or r["md5"]
+                            if r["md5"] != md5:
+                                raise StepFailed(f"{ns} strains, {kind}, round {rnd}, {flag}: the tables differ from the first run's")
+                            res[flag].append(r)
+                    say(f"{ns} strains, {kind}: the {ns} tables are the same bytes in all {2 * args.rounds} runs (MD5 {md5})")
+                    for flag, rs in res.items():
+                        say(f"    {flag:16s} pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; CPU-seconds {row(rs, 'cpu', '.1f')}; "
+                            f"results copied from the device {rs[0]['d2h']} bytes; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
+                    med = {f: {k: statistics.median(r[k] for r in rs) for k in ("passed", "wall", "cpu")} for f, rs in res.items()}
+                    say("    --coverage-only / --coverage-depth at the medians: pass %.2f, wall %.2f, CPU-seconds %.2f, bytes from the device %.4f" %
+                        tuple([med["--coverage-only"][k] / med["--coverage-depth"][k] for k in ("passed", "wall", "cpu")] +
+                              [res["--coverage-only"][0]["d2h"] / max(res["--coverage-depth"][0]["d2h"], 1)]))
+                    if args.parent_exe:
+                        rs = [step(args.parent_exe, argv + ["--coverage-depth"], dict(env), args.limit, tmp, ns, True) for _ in range(3)]
+                        if any(r["md5"] != md5 for r in rs):
+                            raise StepFailed(f"{ns} strains, {kind}: the parent build writes other tables")
+                        say(f"    parent build, --coverage-depth x3: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; "
+                            f"CPU-seconds {row(rs, 'cpu', '.1f')} (same tables)")
+        except StepFailed as x:
+            ok = False
+            say(f"STOPPED: {x}")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
