@@ -26,6 +26,7 @@ import _oracle
 import _synth
 import _tally_ref as tr
 import strainer2_amd as sk
+from _stage2_worlds import Stream as _Stream, other as _other, type_col as _type_col
 from test_quarter_shift_model import ACGT, _verdict
 
 pytestmark = pytest.mark.gpu
@@ -34,39 +35,6 @@ TILE = 32768
 SIZE = 3 * TILE + 11
 SLOTS = 16384                          # first size of the tables on both sides (the row order follows it)
 K = 31
-
-
-class _Stream:
-    """a record stream laid out by offset: reads at chosen places, random records (no strain) between them"""
-
-    def __init__(self, rng):
-        self.rng, self.buf = rng, bytearray()
-
-    def fill_to(self, off):
-        gap = off - len(self.buf)
-        assert gap == 0 or gap >= 2, (off, len(self.buf))
-        while gap:
-            n = min(gap, self.rng.randrange(42, 122))
-            if gap - n == 1:
-                n -= 1
-            self.buf += _synth.rand_dna(self.rng, n - 1) + b"\n"
-            gap -= n
-
-    def at(self, off, read):
-        self.fill_to(off)
-        self.buf += read + b"\n"
-
-    def at_phase(self, phase, read):
-        off = len(self.buf) + (phase - len(self.buf)) % 16
-        self.at(off + 16 if off - len(self.buf) == 1 else off, read)
-
-    def done(self):
-        self.fill_to(SIZE)
-        return bytes(self.buf)
-
-
-def _other(rng, *not_these):
-    return bytes([rng.choice(sorted(set(b"ACGT") - set(not_these)))])
 
 
 def _window_read(rng, strain, a, pre, post, rev):
@@ -184,7 +152,7 @@ def _world(name):
     """(strains, stream, record starts, per strain: (COUNT column, tally reference, oracle strain, informative rows))"""
     rng = random.Random(4710 + sorted(_WORLDS).index(name))
     g, g2, twice = _strains(rng)
-    s = _Stream(rng)
+    s = _Stream(rng, SIZE)
     single = _WORLDS[name](rng, g, twice, s)
     stream = s.done()
     assert len(stream) == SIZE and stream.endswith(b"\n")
@@ -222,12 +190,6 @@ def _world(name):
         assert int(t.counts()[:, 1].sum()) + 8 <= int(refs[0][0].sum())
         t.close()
     return (g, g2), stream, starts, refs
-
-
-def _type_col(informative):
-    t = np.ones(len(informative), dtype=np.uint32)
-    t[informative] = 2
-    return t
 
 
 @pytest.mark.parametrize("name", sorted(_WORLDS))
