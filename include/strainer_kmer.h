@@ -665,6 +665,56 @@ int  sk_covacc_fetch_hold(sk_covacc *a, sk_tally_rec *out, uint64_t cap, uint64_
 void skh_coverage_only_stats(uint64_t *runs_on_device, uint64_t *runs_replayed, uint64_t *targets_host_accumulated, int reset);
 int  sk_covacc_finish_target(sk_covacc *a, uint64_t *out_unique /* nmembers */, uint64_t *out_total /* nmembers */);
 int  sk_covacc_rows(sk_covacc *a, uint32_t member, uint32_t *out /* nrows[member] */);
+/* The same two numbers per REGION of the strain's genome (new: strain_detect --coverage-regions).  The two numbers of a strain and
+ * target cannot tell a strain that is present (hits all over the genome) from a sample that carries one mobile element of it
+ * (every hit on one plasmid, phage or island); the numbers per region can.  The rule:
+ *   text     the strain's text is what both key-set builders use: the records of the strain file with at least k - 1 = 30 bases, in
+ *            file order, end to end.
+ *   record   records are numbered from 1 over EVERY record of the file, the skipped short ones included.
+ *   region   each kept record is cut into windows of W bases: region j of a record holds its bases [jW, min((j + 1)W, len)); W = 0:
+ *            one region per record.  Regions are numbered in text order.
+ *   a row's region is the one that holds the FIRST base of the row's first occurrence along the text, on either strand (its
+ *            first_pos): a 31-mer that starts on the last base of a window belongs to that window, a k-mer that occurs in two
+ *            records to the first.
+ *   unplaced rows without a text position (0xFFFFFFFF: byte-string keys of a strain with U or IUPAC letters, every row of a strain
+ *            too long for the text stage) go to one extra region, the last: index nregions.
+ *   limit    a strain has at most SKH_REGIONS_MAX regions.
+ * skh_regions_from_file: the region table of a strain file (FASTA/FASTQ, plain or .gz; the record grammar of every other reader
+ * here): per region its offset in the text, its record's number and name (the header up to the first white space), its offset in
+ * the record and its length.  SK_E_OPEN: unreadable; SK_E_ARG with out->too_many set: more than SKH_REGIONS_MAX regions.
+ * skh_regions_free releases it (and zeroes it).
+ * sk_table_first_pos: every row's first text position as the table on the device has it, in the caller's row order, 0xFFFFFFFF for
+ * none -- for a table of sk_table_build_from_text (rows in strain order, positions from the rank map) and one of sk_table_load_ex +
+ * sk_table_load_text (any row order, through the locality permutation) alike; a table without a text stage has no positions.
+ *   sk_covacc_set_regions: member's rows are the rows of ctx's table (same device, same row count); each row is mapped to the last
+ *   region whose start is at or before its first position (region_start[]: nregions text offsets, ascending), rows without one to
+ *   region nregions.  One u32 per row is kept.  A member whose regions were never set has nregions = 0: all its rows are unplaced.
+ *   sk_covacc_region_rows: per region of member (nregions + 1 entries) its rows and those of them whose counter in column type_col
+ *   of ctx's table equals informative_value -- the denominator of the ratios.
+ *   sk_covacc_finish_target_regions: sk_covacc_finish_target, and in the same sweep of the counters every non-zero row adds 1 and
+ *   its count to its region's pair: reg_unique / reg_total hold nregions[m] + 1 entries per member, member after member.  The
+ *   members' sums over their regions are out_unique / out_total.  Every counter is zero afterwards. */
+#define SKH_REGIONS_MAX (1u << 20)
+typedef struct skh_regions {
+    uint32_t  n;            /* regions, in text order                                          */
+    uint32_t  nnames;       /* kept records                                                    */
+    uint64_t  text_bases;   /* length of the text                                              */
+    uint64_t *text_off;     /* [n] offset of the region's first base in the text               */
+    uint32_t *record;       /* [n] number of its record in the file, from 1                    */
+    uint64_t *rec_off;      /* [n] offset of its first base in the record                      */
+    uint64_t *len;          /* [n] its bases                                                   */
+    char    **name;         /* [n] its record's name (regions of a record share the string)    */
+    char    **names;        /* [nnames] the strings themselves                                 */
+    int       too_many;     /* set when the call failed for more than SKH_REGIONS_MAX regions  */
+} skh_regions;
+int  skh_regions_from_file(const char *path, uint64_t window, skh_regions *out);
+void skh_regions_free(skh_regions *r);
+int  sk_table_first_pos(sk_ctx *ctx, uint32_t *out /* nrows */);
+int  sk_covacc_set_regions(sk_covacc *a, uint32_t member, sk_ctx *ctx, const uint32_t *region_start, uint32_t nregions);
+int  sk_covacc_region_rows(sk_covacc *a, uint32_t member, sk_ctx *ctx, uint32_t type_col, uint32_t informative_value,
+                           uint64_t *out_rows /* nregions + 1 */, uint64_t *out_informative /* nregions + 1 */);
+int  sk_covacc_finish_target_regions(sk_covacc *a, uint64_t *out_unique /* nmembers */, uint64_t *out_total /* nmembers */,
+                                     uint64_t *reg_unique /* sum of nregions[m] + 1 */, uint64_t *reg_total);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
  * same stdout bytes and exit status. */
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err);

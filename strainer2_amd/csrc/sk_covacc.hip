@@ -10,7 +10,8 @@
 //                    one atomicAdd on depth[member][row].  Rows are spread over the strain and the add returns nothing: no lane
 //                    waits for it (the one-address returning atomic that cost sk_union_compact 587 us does not occur here).
 //   covacc_scatter   again, storing zeros: tot[] is all zero between folds, so no fold pays a memset of pairs x members.
-// covacc_finish sweeps depth[] once per target: non-zero rows, their sum, and zeros left behind.
+// covacc_finish sweeps depth[] once per target: non-zero rows, their sum, and zeros left behind.  covacc_finish_regions is the same
+// sweep with every non-zero row also added to the pair of its region of the strain's genome (strain_detect --coverage-regions).
 // Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -127,6 +128,112 @@ __global__ void __launch_bounds__(256) covacc_finish(uint32_t *__restrict__ dept
     }
 }
 
+// ---- the same sweep, folded by region of the strain's genome as well (include/strainer_kmer.h has the rule) ----
+// region[] holds one u32 per row: the row's region, nreg for a row without a text position.  A workgroup keeps the pairs of up to
+// COV_BINS regions in LDS and adds each non-empty bin to HBM once when it is done: in a table in strain order the rows of a
+// workgroup lie in one or two regions, and one global atomic per non-zero row would put them all on one address (what cost
+// sk_union_compact 587 us).  More regions than COV_BINS -- windows of a few bases -- spread the rows over as many addresses, and each
+// non-zero row (about 1 % of a table at most: the informative ones) adds to HBM itself.
+#define COV_BINS 1024u
+
+__global__ void covacc_map_regions(const uint32_t *__restrict__ first_pos, uint32_t nrows, const uint32_t *__restrict__ starts, uint32_t nreg,
+                                   uint32_t *__restrict__ region)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += stride) {
+        const uint32_t p = first_pos[i];
+        uint32_t r = nreg;
+        if (p != 0xFFFFFFFFu && nreg && starts[0] <= p) {     // the last region that starts at or before the row's first base
+            uint32_t lo = 0, hi = nreg;
+            while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (starts[mid] <= p) lo = mid; else hi = mid; }
+            r = lo;
+        }
+        region[i] = r;
+    }
+}
+
+// one member's rows and informative rows per region.  Every row counts here, so a thread carries the pair of the region its last
+// row lay in and adds it when the region changes: in strain order that is next to never.
+__global__ void __launch_bounds__(256) covacc_region_rows(const uint32_t *__restrict__ region, uint32_t n, const uint32_t *__restrict__ type,
+                                                          uint32_t value, uint32_t nb, unsigned long long *__restrict__ ro)
+{
+    __shared__ unsigned long long b_inf[COV_BINS];
+    __shared__ unsigned long long b_rows[COV_BINS];
+    const bool in_lds = nb <= COV_BINS;
+    if (in_lds) {
+        for (uint32_t b = threadIdx.x; b < nb; b += 256u) { b_inf[b] = 0ull; b_rows[b] = 0ull; }
+        __syncthreads();
+    }
+    uint32_t cur = 0xFFFFFFFFu;
+    unsigned long long rows = 0, inf = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; ; i += (uint64_t)gridDim.x * 256u) {
+        const bool more = i < n;
+        const uint32_t r = more ? region[i] : 0xFFFFFFFFu;
+        if (r != cur || !more) {
+            if (cur < nb && rows) {
+                if (in_lds) { atomicAdd(&b_rows[cur], rows); if (inf) atomicAdd(&b_inf[cur], inf); }
+                else { atomicAdd(ro + 2ull * cur, rows); if (inf) atomicAdd(ro + 2ull * cur + 1ull, inf); }
+            }
+            cur = r; rows = 0; inf = 0;
+        }
+        if (!more) break;
+        rows++;
+        inf += type[i] == value ? 1u : 0u;
+    }
+    if (in_lds) {
+        __syncthreads();
+        for (uint32_t b = threadIdx.x; b < nb; b += 256u)
+            if (b_rows[b]) { atomicAdd(ro + 2ull * b, b_rows[b]); if (b_inf[b]) atomicAdd(ro + 2ull * b + 1ull, b_inf[b]); }
+    }
+}
+
+// covacc_finish, and every non-zero row adds {1, its count} to its region's pair: reg_out + 2 * reg_base[m] holds member m's
+// nreg[m] + 1 pairs
+__global__ void __launch_bounds__(256) covacc_finish_regions(uint32_t *__restrict__ depth, const uint64_t *__restrict__ row_base,
+                                                             const uint32_t *__restrict__ nrows, const uint32_t *__restrict__ region,
+                                                             const uint32_t *__restrict__ nreg, const uint64_t *__restrict__ reg_base,
+                                                             unsigned long long *__restrict__ out, unsigned long long *__restrict__ reg_out)
+{
+    __shared__ unsigned long long s_tot[256];
+    __shared__ uint32_t s_unq[256];
+    __shared__ unsigned long long b_tot[COV_BINS];
+    __shared__ uint32_t b_unq[COV_BINS];
+    const uint32_t m = blockIdx.y, n = nrows[m], nb = nreg[m] + 1u;
+    const bool in_lds = nb <= COV_BINS;
+    uint32_t *d = depth + row_base[m];
+    const uint32_t *rg = region + row_base[m];
+    unsigned long long *ro = reg_out + 2ull * reg_base[m];
+    if (in_lds) {
+        for (uint32_t b = threadIdx.x; b < nb; b += 256u) { b_tot[b] = 0ull; b_unq[b] = 0u; }
+        __syncthreads();
+    }
+    unsigned long long t = 0;
+    uint32_t u = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t v = d[i];
+        if (!v) continue;
+        d[i] = 0u; u++; t += v;
+        const uint32_t r = rg[i];
+        if (r >= nb) continue;                                // (never: a region no start stands behind)
+        if (in_lds) { atomicAdd(&b_unq[r], 1u); atomicAdd(&b_tot[r], (unsigned long long)v); }
+        else { atomicAdd(ro + 2ull * r, 1ull); atomicAdd(ro + 2ull * r + 1ull, (unsigned long long)v); }
+    }
+    s_tot[threadIdx.x] = t; s_unq[threadIdx.x] = u;
+    __syncthreads();
+    for (uint32_t w = 128u; w; w >>= 1) {
+        if (threadIdx.x < w) { s_tot[threadIdx.x] += s_tot[threadIdx.x + w]; s_unq[threadIdx.x] += s_unq[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (!s_unq[0]) return;                                    // (the whole workgroup: nothing to add anywhere)
+    if (threadIdx.x == 0u) {
+        atomicAdd(out + 2u * m, (unsigned long long)s_unq[0]);
+        atomicAdd(out + 2u * m + 1u, s_tot[0]);
+    }
+    if (in_lds)
+        for (uint32_t b = threadIdx.x; b < nb; b += 256u)
+            if (b_unq[b]) { atomicAdd(ro + 2ull * b, (unsigned long long)b_unq[b]); atomicAdd(ro + 2ull * b + 1ull, b_tot[b]); }
+}
+
 struct sk_covacc {
     sk_ctx *ctx; int device;
     hipStream_t stream;
@@ -142,7 +249,37 @@ struct sk_covacc {
     bool held; cov_side hs; uint32_t held_members;
     bool hold_kept;                                         // the buffers still hold the launch last held (sk_covacc_fetch_hold, pick)
     void *p_recs, *p_hits; uint32_t *p_cnt; size_t p_recs_cap, p_hits_cap, p_cnt_cap;   // sk_covacc_pick's landing area
+    // the fold by region: nothing of it exists until sk_covacc_set_regions or sk_covacc_finish_target_regions is called
+    std::vector<uint32_t> nreg; std::vector<uint64_t> reg_base; uint64_t total_bins;
+    uint32_t *d_region;                                     // [total_rows] each row's region
+    uint32_t *d_nreg; uint64_t *d_reg_base;                 // [nm]
+    void *d_reg_out; size_t reg_out_cap;                    // [total_bins] pairs
+    void *d_fp, *d_starts; size_t fp_cap, starts_cap;       // set_regions' scratch: first positions (region_rows: the type column), region starts
+    // device time of the folds and of the targets' sweeps, kept only when somebody asked (sk_covacc_timing_)
+    bool timed; hipEvent_t ev0, ev1; double ms_fold, ms_sweep;
 };
+
+static void cov_t0(sk_covacc *a) { if (a->timed) (void)hipEventRecord(a->ev0, a->stream); }
+static void cov_t1(sk_covacc *a, double *sum)
+{
+    float ms = 0.f;
+    if (!a->timed) return;
+    if (hipEventRecord(a->ev1, a->stream) == hipSuccess && hipEventSynchronize(a->ev1) == hipSuccess &&
+        hipEventElapsedTime(&ms, a->ev0, a->ev1) == hipSuccess) *sum += (double)ms;
+}
+// on != 0 starts the clocks (events around every fold and every sweep from here on); ms_fold / ms_sweep (NULL: not wanted): the sums so far
+extern "C" int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *ms_sweep)
+{
+    if (!a) return SK_E_ARG;
+    if (on && !a->timed) {
+        if (hipSetDevice(a->device) != hipSuccess || hipEventCreate(&a->ev0) != hipSuccess) return SK_E_HIP;
+        if (hipEventCreate(&a->ev1) != hipSuccess) { (void)hipEventDestroy(a->ev0); return SK_E_HIP; }
+        a->timed = true;
+    }
+    if (ms_fold) *ms_fold = a->ms_fold;
+    if (ms_sweep) *ms_sweep = a->ms_sweep;
+    return SK_OK;
+}
 
 #define CA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sk_fail_(a->ctx, SK_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
@@ -167,6 +304,9 @@ extern "C" void sk_covacc_destroy(sk_covacc *a)
     (void)hipFree(a->d_depth); (void)hipFree(a->d_base); (void)hipFree(a->d_nrows); (void)hipFree(a->d_out);
     (void)hipFree(a->d_tot); (void)hipFree(a->d_rows); (void)hipFree(a->h_recs); (void)hipFree(a->h_hits); (void)hipFree(a->h_rs);
     (void)hipFree(a->p_recs); (void)hipFree(a->p_hits); (void)hipFree(a->p_cnt);
+    (void)hipFree(a->d_region); (void)hipFree(a->d_nreg); (void)hipFree(a->d_reg_base); (void)hipFree(a->d_reg_out);
+    (void)hipFree(a->d_fp); (void)hipFree(a->d_starts);
+    if (a->timed) { (void)hipEventDestroy(a->ev0); (void)hipEventDestroy(a->ev1); }
     if (a->h_bad) (void)hipHostFree(a->h_bad);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
@@ -318,6 +458,7 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
     if ((uint64_t)npairs * ns > 0x3FFFFFF0ull) return sk_fail_(a->ctx, SK_E_ARG, "too many pairs x members");
     CA_HIP(hipSetDevice(a->device));
     if ((rc = cov_room(a, (void **)&a->d_tot, &a->tot_cap, (size_t)npairs * ns * 4u, true)) != SK_OK) return rc;
+    cov_t0(a);
     for (int clear = 0; clear < 2; clear++) {
         for (uint32_t k = 0; k < nsides; k++)
             if (side[k].nrecs)
@@ -338,6 +479,7 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
             return sk_fail_(a->ctx, SK_E_HIP, "the fold failed: %s", hipGetErrorString(e));
         }
     }
+    cov_t1(a, &a->ms_fold);
     if (mate && mate->held) a->held = false;
     if (*(volatile uint32_t *)a->h_bad) { *a->h_bad = 0u; return sk_fail_(a->ctx, SK_E_STATE, "a hit log entry names no row of its member"); }
     return SK_OK;
@@ -353,11 +495,13 @@ extern "C" int sk_covacc_add_rows(sk_covacc *a, uint32_t member, const uint32_t 
     CA_HIP(hipSetDevice(a->device));
     const int rc = cov_room(a, (void **)&a->d_rows, &a->rows_cap, (size_t)n * 4u, false);
     if (rc != SK_OK) return rc;
+    cov_t0(a);
     CA_HIP(hipMemcpyAsync(a->d_rows, rows, (size_t)n * 4u, hipMemcpyHostToDevice, a->stream));
     hipLaunchKernelGGL(covacc_rows, dim3(cov_grid(n)), dim3(256), 0, a->stream, (const uint32_t *)a->d_rows, n, a->nrows[member],
                        a->d_depth + a->base[member]);
     CA_HIP(hipGetLastError());
     CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_fold);
     return SK_OK;
 }
 
@@ -366,6 +510,7 @@ extern "C" int sk_covacc_finish_target(sk_covacc *a, uint64_t *out_unique, uint6
     if (!a || !out_unique || !out_total) return SK_E_ARG;
     CA_HIP(hipSetDevice(a->device));
     std::vector<unsigned long long> h((size_t)a->nm * 2u);
+    cov_t0(a);
     CA_HIP(hipMemsetAsync(a->d_out, 0, (size_t)a->nm * 16u, a->stream));
     unsigned gx = (a->max_rows + 255u) / 256u;
     gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
@@ -374,6 +519,7 @@ extern "C" int sk_covacc_finish_target(sk_covacc *a, uint64_t *out_unique, uint6
     CA_HIP(hipGetLastError());
     CA_HIP(hipMemcpyAsync(h.data(), a->d_out, (size_t)a->nm * 16u, hipMemcpyDeviceToHost, a->stream));
     CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_sweep);
     for (uint32_t m = 0; m < a->nm; m++) { out_unique[m] = h[2u * m]; out_total[m] = h[2u * m + 1u]; }
     return SK_OK;
 }
@@ -385,5 +531,115 @@ extern "C" int sk_covacc_rows(sk_covacc *a, uint32_t member, uint32_t *out)
     CA_HIP(hipSetDevice(a->device));
     CA_HIP(hipStreamSynchronize(a->stream));
     if (a->nrows[member]) CA_HIP(hipMemcpy(out, a->d_depth + a->base[member], (size_t)a->nrows[member] * 4u, hipMemcpyDeviceToHost));
+    return SK_OK;
+}
+
+// ---- the fold by region ----
+// the regions' state on the device as the host's vectors have it: every member's region count and where its pairs begin
+static int cov_regions_sync(sk_covacc *a)
+{
+    if (a->nreg.empty()) { a->nreg.assign(a->nm, 0u); a->reg_base.assign(a->nm, 0u); }
+    a->total_bins = 0;
+    for (uint32_t m = 0; m < a->nm; m++) { a->reg_base[m] = a->total_bins; a->total_bins += (uint64_t)a->nreg[m] + 1u; }
+    if (!a->d_region) {                                   // all zero: a member whose regions were never set has one, "unplaced"
+        const size_t bytes = (size_t)(a->total_rows ? a->total_rows : 1u) * 4u;
+        CA_HIP(hipMalloc((void **)&a->d_region, bytes));
+        CA_HIP(hipMemsetAsync(a->d_region, 0, bytes, a->stream));
+        CA_HIP(hipMalloc((void **)&a->d_nreg, (size_t)a->nm * 4u));
+        CA_HIP(hipMalloc((void **)&a->d_reg_base, (size_t)a->nm * 8u));
+    }
+    const int rc = cov_room(a, &a->d_reg_out, &a->reg_out_cap, (size_t)a->total_bins * 16u, false);
+    if (rc != SK_OK) return rc;
+    CA_HIP(hipMemcpyAsync(a->d_nreg, a->nreg.data(), (size_t)a->nm * 4u, hipMemcpyHostToDevice, a->stream));
+    CA_HIP(hipMemcpyAsync(a->d_reg_base, a->reg_base.data(), (size_t)a->nm * 8u, hipMemcpyHostToDevice, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    return SK_OK;
+}
+
+static int cov_member_ctx(sk_covacc *a, uint32_t member, sk_ctx *ctx)
+{
+    if (member >= a->nm) return sk_fail_(a->ctx, SK_E_ARG, "member %u: the accumulator has %u", member, a->nm);
+    if (sk_ctx_device_(ctx) != a->device) return sk_fail_(a->ctx, SK_E_ARG, "the table is on another device");
+    if (sk_table_rows(ctx) != a->nrows[member]) return sk_fail_(a->ctx, SK_E_ARG, "member %u has %u rows, the table %u", member, a->nrows[member], sk_table_rows(ctx));
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_set_regions(sk_covacc *a, uint32_t member, sk_ctx *ctx, const uint32_t *region_start, uint32_t nregions)
+{
+    if (!a || !ctx || (nregions && !region_start)) return SK_E_ARG;
+    int rc = cov_member_ctx(a, member, ctx);
+    if (rc != SK_OK) return rc;
+    if (nregions > SKH_REGIONS_MAX) return sk_fail_(a->ctx, SK_E_ARG, "%u regions: at most %u", nregions, SKH_REGIONS_MAX);
+    for (uint32_t r = 1; r < nregions; r++)
+        if (region_start[r] < region_start[r - 1]) return sk_fail_(a->ctx, SK_E_ARG, "region starts must ascend");
+    CA_HIP(hipSetDevice(a->device));
+    if (a->nreg.empty()) { a->nreg.assign(a->nm, 0u); a->reg_base.assign(a->nm, 0u); }
+    const uint32_t before = a->nreg[member];
+    a->nreg[member] = nregions;
+    if ((rc = cov_regions_sync(a)) != SK_OK) { a->nreg[member] = before; return rc; }
+    const uint32_t n = a->nrows[member];
+    if (!n) return SK_OK;
+    if ((rc = cov_room(a, &a->d_fp, &a->fp_cap, (size_t)n * 4u, false)) != SK_OK) return rc;
+    if ((rc = cov_room(a, &a->d_starts, &a->starts_cap, (size_t)nregions * 4u + 4u, false)) != SK_OK) return rc;
+    rc = sk_table_first_pos_to_device_(ctx, (uint32_t *)a->d_fp);         // (on the table's stream; complete on return)
+    if (rc != SK_OK) return sk_fail_(a->ctx, rc, "%s", sk_last_error(ctx));
+    if (nregions) CA_HIP(hipMemcpyAsync(a->d_starts, region_start, (size_t)nregions * 4u, hipMemcpyHostToDevice, a->stream));
+    hipLaunchKernelGGL(covacc_map_regions, dim3(cov_grid(n)), dim3(256), 0, a->stream, (const uint32_t *)a->d_fp, n,
+                       (const uint32_t *)a->d_starts, nregions, a->d_region + a->base[member]);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipStreamSynchronize(a->stream));
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_region_rows(sk_covacc *a, uint32_t member, sk_ctx *ctx, uint32_t type_col, uint32_t informative_value,
+                                     uint64_t *out_rows, uint64_t *out_informative)
+{
+    if (!a || !ctx || !out_rows || !out_informative) return SK_E_ARG;
+    int rc = cov_member_ctx(a, member, ctx);
+    if (rc != SK_OK) return rc;
+    CA_HIP(hipSetDevice(a->device));
+    if (!a->d_region && (rc = cov_regions_sync(a)) != SK_OK) return rc;
+    const uint32_t n = a->nrows[member], nb = a->nreg[member] + 1u;
+    std::vector<unsigned long long> h((size_t)nb * 2u, 0ull);
+    if (n) {
+        if ((rc = cov_room(a, &a->d_fp, &a->fp_cap, (size_t)n * 4u, false)) != SK_OK) return rc;
+        rc = sk_counts_rows_to_device_(ctx, type_col, (uint32_t *)a->d_fp);   // (the column in the caller's row order; complete on return)
+        if (rc != SK_OK) return sk_fail_(a->ctx, rc, "%s", sk_last_error(ctx));
+        unsigned long long *ro = (unsigned long long *)a->d_reg_out + 2ull * a->reg_base[member];
+        CA_HIP(hipMemsetAsync(ro, 0, (size_t)nb * 16u, a->stream));
+        unsigned gx = (n + 255u) / 256u;
+        gx = gx > 256u ? 256u : gx;
+        hipLaunchKernelGGL(covacc_region_rows, dim3(gx), dim3(256), 0, a->stream, (const uint32_t *)(a->d_region + a->base[member]), n,
+                           (const uint32_t *)a->d_fp, informative_value, nb, ro);
+        CA_HIP(hipGetLastError());
+        CA_HIP(hipMemcpyAsync(h.data(), ro, (size_t)nb * 16u, hipMemcpyDeviceToHost, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+    }
+    for (uint32_t r = 0; r < nb; r++) { out_rows[r] = h[2u * r]; out_informative[r] = h[2u * r + 1u]; }
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_finish_target_regions(sk_covacc *a, uint64_t *out_unique, uint64_t *out_total, uint64_t *reg_unique, uint64_t *reg_total)
+{
+    if (!a || !out_unique || !out_total || !reg_unique || !reg_total) return SK_E_ARG;
+    CA_HIP(hipSetDevice(a->device));
+    int rc;
+    if (!a->d_region && (rc = cov_regions_sync(a)) != SK_OK) return rc;
+    std::vector<unsigned long long> h((size_t)a->nm * 2u), hr((size_t)a->total_bins * 2u);
+    cov_t0(a);
+    CA_HIP(hipMemsetAsync(a->d_out, 0, (size_t)a->nm * 16u, a->stream));
+    CA_HIP(hipMemsetAsync(a->d_reg_out, 0, (size_t)a->total_bins * 16u, a->stream));
+    unsigned gx = (a->max_rows + 255u) / 256u;
+    gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
+    hipLaunchKernelGGL(covacc_finish_regions, dim3(gx, a->nm), dim3(256), 0, a->stream, a->d_depth, (const uint64_t *)a->d_base,
+                       (const uint32_t *)a->d_nrows, (const uint32_t *)a->d_region, (const uint32_t *)a->d_nreg,
+                       (const uint64_t *)a->d_reg_base, a->d_out, (unsigned long long *)a->d_reg_out);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipMemcpyAsync(h.data(), a->d_out, (size_t)a->nm * 16u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipMemcpyAsync(hr.data(), a->d_reg_out, (size_t)a->total_bins * 16u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_sweep);
+    for (uint32_t m = 0; m < a->nm; m++) { out_unique[m] = h[2u * m]; out_total[m] = h[2u * m + 1u]; }
+    for (uint64_t r = 0; r < a->total_bins; r++) { reg_unique[r] = hr[2u * r]; reg_total[r] = hr[2u * r + 1u]; }
     return SK_OK;
 }

@@ -1984,6 +1984,57 @@ extern "C" int sk_counts_rows_to_device_(sk_ctx *c, uint32_t col, uint32_t *d_ou
     SK_HIP(c, hipStreamSynchronize(c->stream));
     return SK_OK;
 }
+// Every row's first text position, from the rank map: a set bit at text position p is the first occurrence of the row whose counter
+// index is rank[p / 64].x + the set bits of the block below p; inv (NULL: rows in strain order) turns that index into the caller's
+// row.  out[] is all 0xFFFFFFFF before: rows the text does not hold keep it.
+__global__ void sk_first_pos_from_rank(const sk_u4 *__restrict__ rank, uint32_t nbases, const uint32_t *__restrict__ inv, uint32_t nrows,
+                                       uint32_t *__restrict__ out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbases; i += stride) {
+        const uint32_t p = (uint32_t)i;
+        const sk_u4 r = rank[p >> 6];
+        const uint32_t w = (p & 32u) ? r.z : r.y;
+        if (!((w >> (p & 31u)) & 1u)) continue;
+        const uint32_t idx = r.x + ((p & 32u) ? (uint32_t)__popc(r.y) : 0u) + (uint32_t)__popc(w & ((1u << (p & 31u)) - 1u));
+        if (idx >= nrows) continue;
+        const uint32_t row = inv ? inv[idx] : idx;
+        if (row < nrows) out[row] = p;
+    }
+}
+// ... into a device buffer of nrows u32 on the context's device; complete on return
+extern "C" int sk_table_first_pos_to_device_(sk_ctx *c, uint32_t *d_out)
+{
+    if (!c || !d_out) return SK_E_ARG;
+    if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    SK_HIP(c, hipSetDevice(c->device));
+    if (!c->nrows) return SK_OK;
+    SK_HIP(c, hipMemsetAsync(d_out, 0xFF, (size_t)c->nrows * 4, c->stream));
+    if (c->d_rank && c->text_bases) {
+        const uint64_t g = ((uint64_t)c->text_bases + 255u) / 256u;
+        hipLaunchKernelGGL(sk_first_pos_from_rank, dim3((unsigned)(g > 4096u ? 4096u : g)), dim3(256), 0, c->stream, (const sk_u4 *)c->d_rank,
+                           c->text_bases, (const uint32_t *)c->d_inv, c->nrows, d_out);
+        SK_HIP(c, hipGetLastError());
+    }
+    SK_HIP(c, hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+extern "C" int sk_table_first_pos(sk_ctx *c, uint32_t *out)
+{
+    if (!c || (!out && c->nrows)) return SK_E_ARG;
+    if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->nrows) return SK_OK;
+    SK_HIP(c, hipSetDevice(c->device));
+    uint32_t *d = NULL;
+    SK_HIP(c, hipMalloc((void **)&d, (size_t)c->nrows * 4));
+    int rc = sk_table_first_pos_to_device_(c, d);
+    if (rc == SK_OK) {
+        const hipError_t e = hipMemcpy(out, d, (size_t)c->nrows * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = sk_fail(c, SK_E_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(d);
+    return rc;
+}
 extern "C" uint32_t sk_table_rows(const sk_ctx *c) { return c ? c->nrows : 0; }
 extern "C" uint32_t sk_table_cols(const sk_ctx *c) { return c ? c->ncols : 0; }
 

@@ -825,6 +825,7 @@ int skh_keyset_load(sk_ctx *ctx, const skh_keyset *ks, uint32_t ncols)
  * which also finds the record that ends the file for the reference (a quality string of the wrong length, src/kseq.h:205-209)
  * where the reference finds it.  The host-only test builds link this file without the device layer: the entry points are weak,
  * and without them the host path is taken. */
+#pragma weak skh_resident_genomes_
 #pragma weak sk_scan_text_pinned_many
 #pragma weak sk_text_enabled
 
@@ -2679,6 +2680,7 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
             sk_ctx *c2 = ctx;
             ctx = NULL;                               /* ctx and ks now belong to strain_detect, which releases them */
             skh_pack_cache_set(c2, NULL, NULL);       /* (step 1's counters end here; strain_detect forgets the context when it lets it go) */
+            if (skh_resident_genomes_) skh_resident_genomes_((const char *const *)&R, 1);      /* (--coverage-regions reads the records' names from it) */
             status = skh_strain_detect_resident(c2, &ks, list_path, detect_argc, detect_argv, out, err);
         }
         if (tmp_path[0]) unlink(tmp_path);

@@ -105,6 +105,7 @@ typedef struct {
     int       general;
     size_t    klen;                                    /* k-mer field length seen so far (0 = none yet) */
     uint64_t *given_u, *given_t; uint32_t ngiven; int given;   /* counts handed in per sample (skc_add_counts) instead of hits */
+    uint64_t **reg_u, **reg_t; uint32_t nreg_s, reg_bins;      /* ... and per sample and region (skc_add_region_counts): reg_bins each, or NULL */
 } hitlist;
 
 enum { COV_OK = 0, COV_OPEN, COV_FIELDS, COV_INT, COV_NOMEM };
@@ -408,6 +409,9 @@ done:
 
 static void hitlist_free(hitlist *h)
 {
+    uint32_t s;
+    for (s = 0; s < h->nreg_s; s++) { free(h->reg_u[s]); free(h->reg_t[s]); }
+    free(h->reg_u); free(h->reg_t);
     free(h->given_u); free(h->given_t);
     free(h->key); free(h->sample); free(h->depth_order); free(h->eval_order); free(h->gid); free(h->gsample);
     names_free(&h->smp); names_free(&h->text);
@@ -472,6 +476,106 @@ int skc_add_trailer(skc_acc *a, const char *metagenome, const char *name, int64_
 int skc_report(skc_acc *a, sk_ctx *ctx, const char *hits_file_name, FILE *out, FILE *err)
 {
     return cov_report(&a->h, ctx, hits_file_name, NULL, out, err);
+}
+
+/* ---- the same numbers per region of the strain's genome (strain_detect --coverage-regions; include/strainer_kmer.h has the rule) ---- */
+static int reg_room(hitlist *h, uint32_t g, uint32_t nbins)
+{
+    if (h->reg_bins && h->reg_bins != nbins) return -1;
+    h->reg_bins = nbins;
+    if (g >= h->nreg_s) {
+        const uint32_t n2 = g + 16u;
+        uint64_t **u2 = realloc(h->reg_u, (size_t)n2 * sizeof *u2), **t2;
+        if (!u2) return -1;
+        h->reg_u = u2;
+        memset(u2 + h->nreg_s, 0, (size_t)(n2 - h->nreg_s) * sizeof *u2);
+        if (!(t2 = realloc(h->reg_t, (size_t)n2 * sizeof *t2))) return -1;       /* (reg_u is longer than nreg_s says: harmless) */
+        h->reg_t = t2;
+        memset(t2 + h->nreg_s, 0, (size_t)(n2 - h->nreg_s) * sizeof *t2);
+        h->nreg_s = n2;
+    }
+    if (!h->reg_u[g] && !(h->reg_u[g] = calloc(nbins ? nbins : 1, sizeof **h->reg_u))) return -1;
+    if (!h->reg_t[g] && !(h->reg_t[g] = calloc(nbins ? nbins : 1, sizeof **h->reg_t))) return -1;
+    return 0;
+}
+
+/* a metagenome's numbers per region, counted elsewhere (nbins = the strain's regions + 1, "unplaced" last): called next to
+ * skc_add_counts, after it, so that the sample exists */
+int skc_add_region_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t nbins)
+{
+    hitlist *h = &a->h;
+    const char *sn = base_of(metagenome, metagenome + strlen(metagenome));
+    const int64_t g = name_get(&h->smp, sn, strlen(sn));
+    uint32_t r;
+    if (g < 0 || reg_room(h, (uint32_t)g, nbins)) return -1;
+    for (r = 0; r < nbins; r++) { h->reg_u[g][r] += unique[r]; h->reg_t[g][r] += total[r]; }
+    return 0;
+}
+
+static int cmp_u64(const void *x, const void *y)
+{
+    const uint64_t a = *(const uint64_t *)x, b = *(const uint64_t *)y;
+    return a < b ? -1 : a > b;
+}
+
+/* The table: one line per metagenome of the main table (in its order: call this after skc_report) and region with an informative
+ * row.  row_region[row] < nbins for the strain's nrows rows, reg_inf[r] = informative rows of region r.  An accumulator that was
+ * fed hits folds its (sample, row) list here; one that was fed counts prints what skc_add_region_counts left. */
+int skc_report_regions(skc_acc *a, const char *hits_file_name, const skh_regions *rg, const uint32_t *row_region, uint32_t nrows,
+                       const uint64_t *reg_inf, FILE *out, FILE *err)
+{
+    hitlist *h = &a->h;
+    const uint32_t nbins = rg->n + 1u;
+    char *strain;
+    size_t sl;
+    uint32_t k, s, r;
+    for (k = 0; k < h->neval; k++)                       /* (what cov_report did already, when it ran) */
+        if (!h->smp.in_depth[s = h->eval_order[k]]) {
+            uint32_t *o = realloc(h->depth_order, ((size_t)h->ndepth + 1) * sizeof *o);
+            if (!o) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+            h->depth_order = o;
+            o[h->ndepth++] = s;
+            h->smp.in_depth[s] = 1;
+        }
+    if (!h->given && h->n) {
+        uint64_t *v = malloc((size_t)h->n * sizeof *v), i, j;
+        if (!v) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+        for (i = 0; i < h->n; i++) v[i] = ((uint64_t)h->sample[i] << 32) | (h->key[i] & 0xFFFFFFFFu);
+        qsort(v, (size_t)h->n, sizeof *v, cmp_u64);
+        for (i = 0; i < h->n; i = j) {
+            const uint32_t g = (uint32_t)(v[i] >> 32), row = (uint32_t)v[i];
+            const uint32_t bin = row < nrows && row_region[row] < nbins ? row_region[row] : nbins - 1u;
+            for (j = i + 1; j < h->n && v[j] == v[i]; j++) ;
+            if (reg_room(h, g, nbins)) { free(v); fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+            h->reg_u[g][bin] += 1; h->reg_t[g][bin] += j - i;
+        }
+        free(v);
+    }
+    if (!(strain = strdup(base_of(hits_file_name, hits_file_name + strlen(hits_file_name))))) return 1;
+    sl = strlen(strain);
+    if (sl >= 13 && !memcmp(strain + sl - 12, "kmer_hits", 9) && !memcmp(strain + sl - 2, "gz", 2)) strain[sl - 13] = 0;
+    fputs("strain_name\tmetagenome\tregion\trecord_name\tregion_informative_kmers\tunique_observed_informative_kmers\t"
+          "total_observed_informative_kmers\tkmer_coverage\tkmer_depth\n", out);
+    for (k = 0; k < h->ndepth; k++) {
+        s = h->depth_order[k];
+        for (r = 0; r < nbins; r++) {
+            const uint64_t u = s < h->nreg_s && h->reg_u[s] ? h->reg_u[s][r] : 0, t = s < h->nreg_s && h->reg_t[s] ? h->reg_t[s][r] : 0;
+            char c1[32], c2[32];
+            if (!reg_inf[r]) continue;
+            skp_float_str((double)u / (double)reg_inf[r], c1);
+            skp_float_str((double)t / (double)reg_inf[r], c2);
+            if (r < rg->n)
+                fprintf(out, "%s\t%s\t%u:%llu-%llu\t%s\t%llu\t%llu\t%llu\t%s\t%s\n", strain, h->smp.name[s], rg->record[r],
+                        (unsigned long long)rg->rec_off[r], (unsigned long long)(rg->rec_off[r] + rg->len[r]), rg->name[r],
+                        (unsigned long long)reg_inf[r], (unsigned long long)u, (unsigned long long)t, c1, c2);
+            else
+                fprintf(out, "%s\t%s\tunplaced\t-\t%llu\t%llu\t%llu\t%s\t%s\n", strain, h->smp.name[s],
+                        (unsigned long long)reg_inf[r], (unsigned long long)u, (unsigned long long)t, c1, c2);
+        }
+    }
+    free(strain);
+    fflush(out);
+    return 0;
 }
 
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)

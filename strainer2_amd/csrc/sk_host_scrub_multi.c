@@ -35,6 +35,8 @@
 #include "../../include/strainer_kmer.h"
 #include "sk_cpus.h"
 #include "sk_gzout.h"
+#include "sk_internal.h"
+#pragma weak skh_resident_genomes_
 
 typedef struct {
     char      *genome, *outfile;   /* outfile: the count table, or with --scrub the informative list                        */
@@ -293,7 +295,7 @@ static char *sm_cov_path(const char *hits)
 static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
 {
     char **v = (char **)malloc(((size_t)argc + 1) * sizeof *v);
-    int c, n = 0, bad = 0, saved = opterr;
+    int c, n = 0, bad = 0, saved = opterr, want_rg = 0;
     if (!v) return 1;
     for (c = 0; c < argc; c++) {
         if (c > 0 && !strncmp(argv[c], "--coverage-depth", 16) && (argv[c][16] == 0 || argv[c][16] == '=')) {
@@ -314,12 +316,28 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
             *want_cov |= 2;                          /* (no hit list is written: none is created up front either) */
             continue;
         }
+        if (c > 0 && !strncmp(argv[c], "--coverage-regions", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            if (argv[c][18] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-regions takes no file name (each strain's table goes next to its coverage table)\n");
+                free(v);
+                return 1;
+            }
+            want_rg = 1;
+            continue;
+        }
+        if (c > 0 && !strcmp(argv[c], "--region-window") && c + 1 < argc) { c++; continue; }
+        if (c > 0 && !strncmp(argv[c], "--region-window=", 16)) continue;
         if (c > 0 && !strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { c++; continue; }
         v[n++] = argv[c];
     }
     v[n] = NULL;
     if (*want_cov == 3) {
         fprintf(err, "kmer_scrub_count: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n");
+        free(v);
+        return 1;
+    }
+    if (want_rg && !*want_cov) {
+        fprintf(err, "kmer_scrub_count: --coverage-regions goes with --coverage-depth or --coverage-only: it folds their table's numbers by region\n");
         free(v);
         return 1;
     }
@@ -597,20 +615,21 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
         sk_ctx **ctxs = (sk_ctx **)calloc(ns, sizeof *ctxs);
         skh_keyset *kss = (skh_keyset *)calloc(ns, sizeof *kss);
         const char **inf = (const char **)calloc(ns, sizeof *inf), **hits = (const char **)calloc(ns, sizeof *hits);
-        const char **gl = (const char **)calloc(ns, sizeof *gl);
+        const char **gl = (const char **)calloc(ns, sizeof *gl), **gen = (const char **)calloc(ns, sizeof *gen);
         int rc;
-        if (!ctxs || !kss || !inf || !hits || !gl) {
+        if (!ctxs || !kss || !inf || !hits || !gl || !gen) {
             fprintf(err, "kmer_scrub_count: out of memory\n");
-            free(ctxs); free(kss); free(inf); free(hits); free(gl);
+            free(ctxs); free(kss); free(inf); free(hits); free(gl); free(gen);
             goto done;
         }
         for (k = 0; k < ns; k++) {
             ctxs[k] = st[k].ctx; kss[k] = st[k].ks;
             st[k].ctx = NULL; memset(&st[k].ks, 0, sizeof st[k].ks);
-            inf[k] = st[k].outfile; hits[k] = st[k].hits; gl[k] = st[k].glist;
+            inf[k] = st[k].outfile; hits[k] = st[k].hits; gl[k] = st[k].glist; gen[k] = st[k].genome;
         }
+        if (skh_resident_genomes_) skh_resident_genomes_(gen, ns);     /* (--coverage-regions reads the records' names from them) */
         rc = skh_strain_detect_resident_many(ns, ctxs, kss, inf, hits, gl, detect_argc, detect_argv, out, err);
-        free(ctxs); free(kss); free(inf); free(hits); free(gl);
+        free(ctxs); free(kss); free(inf); free(hits); free(gl); free(gen);
         if (rc != 0) goto done;
     }
     t4 = sm_now();

@@ -91,6 +91,8 @@ typedef struct {
     uint32_t   *tallybuf; uint32_t tallycap;
     int         job_rc;                    /* result of this strain's part of a pool job */
     uint32_t   *co_rows; uint64_t co_n, co_cap;   /* --coverage-only: rows of host-replayed passing hits on their way to the device's counters */
+    /* --coverage-regions: the strain's region table, every row's region (rg.n = unplaced), informative rows per region, the table's path */
+    skh_regions rg; uint32_t *row_region; uint64_t *reg_inf; char *rg_path;
 } sd_prog;
 
 /* ---------------------------------------------------------------------------------------------
@@ -1604,6 +1606,25 @@ static void sd_prefetch(sd_stream *st)
 #pragma weak sk_tally_collect_counts
 #pragma weak sk_union_tally_collect_counts
 #pragma weak sk_union_tally_launch_ex
+/* --coverage-regions (include/strainer_kmer.h has the rule): the strain's region table comes from its file (sk_host_regions.c), a
+ * row's region from its first text position -- the key set's on the host, the table's own (sk_table_first_pos) for a key set built
+ * on the device.  With --coverage-only the accumulators fold by region in the sweep that ends a target
+ * (sk_covacc_finish_target_regions; replayed runs reach the same counters through sk_covacc_add_rows); with --coverage-depth, and
+ * where --coverage-only counts on the host, skc_report_regions folds the host accumulator's (sample, row) list. */
+#pragma weak skh_regions_from_file
+#pragma weak skh_regions_free
+#pragma weak sk_table_first_pos
+#pragma weak sk_covacc_set_regions
+#pragma weak sk_covacc_region_rows
+#pragma weak sk_covacc_finish_target_regions
+#pragma weak sk_covacc_timing_
+static double sd_co_ms_fold, sd_co_ms_sweep;          /* SK_SD_TIMING: the accumulators' device time, folds and target sweeps */
+static struct {
+    int on; uint64_t window;
+    const char *const *genomes; uint32_t ngenomes;         /* the strain files of adopted strains (skh_resident_genomes_) */
+} sd_rg;
+void skh_resident_genomes_(const char *const *paths, uint32_t n) { sd_rg.genomes = paths; sd_rg.ngenomes = n; }
+
 static int chunk_res_reserve(sd_chunk *c, uint64_t *rcap, uint64_t *hcap, uint64_t nrec_total, uint64_t nhit_total);
 static struct {
     int on, host;                               /* the flag; every target through the host accumulator (two targets share a basename) */
@@ -1632,7 +1653,11 @@ static uint32_t co_unit_members(uint32_t unit) { return sd_un.n ? sk_union_membe
 static void co_close(void)
 {
     uint32_t k;
-    for (k = 0; k < sd_co.nacc; k++) if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
+    for (k = 0; k < sd_co.nacc; k++) {
+        double f = 0, w = 0;
+        if (sk_covacc_timing_ && sd_co.acc[k] && sk_covacc_timing_(sd_co.acc[k], 0, &f, &w) == SK_OK) { sd_co_ms_fold += f; sd_co_ms_sweep += w; }
+        if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
+    }
     free(sd_co.acc); free(sd_co.recs); free(sd_co.hits);
     sd_co.acc = NULL; sd_co.nacc = 0; sd_co.recs = NULL; sd_co.hits = NULL; sd_co.rcap = sd_co.hcap = 0; sd_co.post = NULL;
 }
@@ -1642,7 +1667,8 @@ static int co_open(sd_prog *p, uint32_t ns)
     const uint32_t nu = co_units(ns);
     uint32_t k, m;
     if (!sd_co.on || sd_co.host) return SK_OK;
-    if (!sk_covacc_create || !sk_covacc_pick || !sk_tally_collect_counts || !sk_union_tally_launch_ex) {
+    if (!sk_covacc_create || !sk_covacc_pick || !sk_tally_collect_counts || !sk_union_tally_launch_ex ||
+        (sd_rg.on && (!sk_covacc_set_regions || !sk_covacc_region_rows || !sk_covacc_finish_target_regions))) {
         fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
         sd_co.host = 1;
         return SK_OK;
@@ -1657,6 +1683,18 @@ static int co_open(sd_prog *p, uint32_t ns)
         rc = sk_covacc_create(p[a].ctx, n, nrows, (int64_t)sd_co.min, &sd_co.acc[k]);
         sd_co.nacc = k + 1;
         if (rc != SK_OK) { sd_co.nacc = k; co_close(); return rc; }
+        if (getenv("SK_SD_TIMING") && sk_covacc_timing_) (void)sk_covacc_timing_(sd_co.acc[k], 1, NULL, NULL);
+        for (m = 0; m < n && sd_rg.on; m++) {             /* every member's rows to their regions, and the regions' denominators */
+            sd_prog *q = &p[a + m];
+            uint32_t *starts = (uint32_t *)malloc(((size_t)q->rg.n + 1) * sizeof *starts), r;
+            uint64_t *rows = (uint64_t *)malloc(((size_t)q->rg.n + 1) * sizeof *rows);
+            if (!starts || !rows) { free(starts); free(rows); co_close(); return SK_E_NOMEM; }
+            for (r = 0; r < q->rg.n; r++) starts[r] = q->rg.text_off[r] < 0xFFFFFFFEull ? (uint32_t)q->rg.text_off[r] : 0xFFFFFFFEu;   /* (no row starts that far out) */
+            rc = sk_covacc_set_regions(sd_co.acc[k], m, q->ctx, starts, q->rg.n);
+            if (rc == SK_OK) rc = sk_covacc_region_rows(sd_co.acc[k], m, q->ctx, SD_TYPE, SD_INFORMATIVE, rows, q->reg_inf);
+            free(starts); free(rows);
+            if (rc != SK_OK) { co_close(); return rc; }
+        }
     }
     return SK_OK;
 }
@@ -2383,11 +2421,25 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
         for (k = 0; k < sd_co.nacc && got >= 0; k++) {
             uint64_t uq[SK_UNION_MAX], tot[SK_UNION_MAX];
             const uint32_t a = co_unit_first(k), n = co_unit_members(k);
+            uint64_t *ru = NULL, *rt = NULL, bins = 0, at = 0;
+            if (sd_rg.on) {                                  /* the same sweep, folded by region as well */
+                for (m = 0; m < n; m++) bins += (uint64_t)p[a + m].rg.n + 1u;
+                ru = (uint64_t *)malloc((size_t)bins * 2 * sizeof *ru);
+                if (!ru) { got = SK_E_NOMEM; break; }
+                rt = ru + bins;
+            }
             pthread_mutex_lock(&sd_dev_mu);
-            rc = sk_covacc_finish_target(sd_co.acc[k], uq, tot);
+            rc = sd_rg.on ? sk_covacc_finish_target_regions(sd_co.acc[k], uq, tot, ru, rt) : sk_covacc_finish_target(sd_co.acc[k], uq, tot);
             pthread_mutex_unlock(&sd_dev_mu);
-            if (rc != SK_OK) { got = rc; break; }
-            for (m = 0; m < n; m++) if (skc_add_counts(p[a + m].cov, f1, uq[m], tot[m])) got = SK_E_NOMEM;
+            if (rc != SK_OK) { free(ru); got = rc; break; }
+            for (m = 0; m < n; m++) {
+                if (skc_add_counts(p[a + m].cov, f1, uq[m], tot[m])) got = SK_E_NOMEM;
+                if (sd_rg.on) {
+                    if (skc_add_region_counts(p[a + m].cov, f1, ru + at, rt + at, p[a + m].rg.n + 1u)) got = SK_E_NOMEM;
+                    at += (uint64_t)p[a + m].rg.n + 1u;
+                }
+            }
+            free(ru);
         }
         if (got < 0) { fprintf(err, "strain_detect: device error on %s: %s (%s)\n", f1, sk_strerror(got), sk_last_error(p[0].ctx)); goto done; }
     }
@@ -2725,7 +2777,77 @@ static int sd_coverage_write(sd_prog *p)
     if (!(f = fopen(p->cov_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->cov_path); return 1; }
     rc = skc_report(p->cov, p->ctx, p->o_path, f, p->err);
     fclose(f);
+    if (rc || !sd_rg.on) return rc;
+    if (!(f = fopen(p->rg_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->rg_path); return 1; }
+    rc = skc_report_regions(p->cov, p->o_path, &p->rg, p->row_region, (uint32_t)p->ks.nrows, p->reg_inf, f, p->err);
+    fclose(f);
     return rc;
+}
+
+/* --coverage-regions: the region table of a strain file, before anything of the run is opened; more than SKH_REGIONS_MAX regions
+ * are refused here */
+static int sd_regions_load(skh_regions *rg, const char *genome, FILE *err)
+{
+    const int rc = skh_regions_from_file(genome, sd_rg.window, rg);
+    if (rc == SK_OK) return 0;
+    if (rg->too_many) fprintf(err, "strain_detect: --coverage-regions: %s has more than %u regions of %llu bases: choose a larger --region-window\n",
+                              genome, SKH_REGIONS_MAX, (unsigned long long)sd_rg.window);
+    else if (rc == SK_E_OPEN) fprintf(err, "strain_detect: --coverage-regions: could not read %s\n", genome);
+    else fprintf(err, "strain_detect: --coverage-regions: %s: %s\n", genome, sk_strerror(rc));
+    return 1;
+}
+
+/* ... and of an open strain: where the table goes (takes over *rg) */
+static int sd_regions_open(sd_prog *p, skh_regions *rg, const char *explicit_path)
+{
+    p->rg = *rg;
+    memset(rg, 0, sizeof *rg);
+    if (explicit_path && *explicit_path) p->rg_path = strdup(explicit_path);
+    else {
+        const size_t n = strlen(p->o_path);
+        p->rg_path = (char *)malloc(n + 32);
+        if (p->rg_path) {
+            strcpy(p->rg_path, p->o_path);
+            if (n >= 13 && !strcmp(p->rg_path + n - 13, ".kmer_hits.gz")) p->rg_path[n - 13] = 0;
+            strcat(p->rg_path, ".coverage_regions");
+        }
+    }
+    p->reg_inf = (uint64_t *)calloc((size_t)p->rg.n + 1, sizeof *p->reg_inf);
+    if (!p->rg_path || !p->reg_inf) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
+    return 0;
+}
+
+/* Every row's region and the informative rows per region ON THE HOST: what skc_report_regions needs to fold the host accumulator's
+ * (sample, row) list -- --coverage-depth, and --coverage-only where it counts on the host.  Where the accumulators on the device
+ * fold, they know both (sk_covacc_set_regions, sk_covacc_region_rows) and this walk over all rows is left out. */
+static int sd_regions_rows(sd_prog *p)
+{
+    const uint32_t nrows = (uint32_t)p->ks.nrows;
+    uint32_t *own = NULL, i;
+    const uint32_t *fp = p->ks.first_pos;
+    if (p->row_region) return 0;
+    p->row_region = (uint32_t *)malloc(((size_t)nrows + 1) * sizeof *p->row_region);
+    if (!p->row_region) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
+    memset(p->reg_inf, 0, ((size_t)p->rg.n + 1) * sizeof *p->reg_inf);
+    if (!fp && nrows) {                                  /* a key set built on the device: the table knows the positions */
+        int rc = SK_E_STATE;
+        own = (uint32_t *)malloc((size_t)nrows * sizeof *own);
+        if (own && sk_table_first_pos) rc = sk_table_first_pos(p->ctx, own);
+        if (!own || rc != SK_OK) { fprintf(p->err, "strain_detect: --coverage-regions: %s (%s)\n", sk_strerror(own ? rc : SK_E_NOMEM), sk_last_error(p->ctx)); free(own); return 1; }
+        fp = own;
+    }
+    for (i = 0; i < nrows; i++) {
+        uint32_t r = p->rg.n;
+        if (fp[i] != 0xFFFFFFFFu && p->rg.n && p->rg.text_off[0] <= fp[i]) {
+            uint32_t lo = 0, hi = p->rg.n;
+            while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (p->rg.text_off[mid] <= fp[i]) lo = mid; else hi = mid; }
+            r = lo;
+        }
+        p->row_region[i] = r;
+        if (p->type[i] == SD_INFORMATIVE) p->reg_inf[r]++;
+    }
+    free(own);
+    return 0;
 }
 
 static int sd_strain_open(sd_prog *p, const char *r, const char *a, const char *g, const char *o, int device, FILE *out, FILE *err)
@@ -2751,6 +2873,8 @@ static void sd_strain_close(sd_prog *p)
     skh_keyset_free(&p->ks);
     free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows);
     skc_destroy(p->cov);
+    if (skh_regions_free) skh_regions_free(&p->rg);
+    free(p->row_region); free(p->reg_inf); free(p->rg_path);
     memset(p, 0, sizeof *p);
 }
 
@@ -2808,6 +2932,10 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     {
         const int crc = co_open(p, ns);
         if (crc != SK_OK) { fprintf(err, "strain_detect: device error: %s (%s)\n", sk_strerror(crc), sk_last_error(p[0].ctx)); sd_unions_close(); return 1; }
+    }
+    if (sd_rg.on && !sd_co.acc) {                        /* (no accumulator on the device folds by region: the host will) */
+        uint32_t s;
+        for (s = 0; s < ns; s++) if (sd_regions_rows(&p[s])) { co_close(); sd_unions_close(); return 1; }
     }
     pool_start(&pool, ns);
     lanes_start(p, ns);
@@ -2950,12 +3078,16 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     const char *a = NULL, *r = NULL, *b = NULL, *b2 = NULL, *B = NULL, *tt = NULL, *g = NULL, *o = NULL, *S = NULL, *env;
     int c, j, mode = SD_SE, status = 1, device = 0, n_S = 0, want_cov = 0, cov_only = 0;
     skzo_pool zpool;
-    const char *cov_file = NULL, *tc_dir = NULL;
+    const char *cov_file = NULL, *tc_dir = NULL, *rg_file = NULL, *rg_window = NULL;
+    const char *const *rg_genomes = sd_rg.genomes;       /* (adopted strains: theirs for this call only) */
+    const uint32_t rg_ngenomes = sd_rg.ngenomes;
+    skh_regions *rgs = NULL;
+    int want_rg = 0;
     long long cov_min = 1;
     double t_begin = 0;
     sd_prog *p = NULL;
     char **paths = NULL;
-    uint32_t ns = 0, s;
+    uint32_t ns = 0, s, nrgs = 0;
 
     if (ad) {                                            /* the resident strains are ours from here, whatever happens */
         p = (sd_prog *)calloc(ad->n, sizeof *p);
@@ -2982,12 +3114,22 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             cov_file = argv[c][15] ? argv[c] + 16 : NULL;
             continue;
         }
+        /* "--coverage-regions[=FILE] [--region-window W]": next to either table, the same numbers per window of W bases of the
+         * strain's records (default 100000; 0: per record), default FILE = outfile with ".kmer_hits.gz" replaced by ".coverage_regions" */
+        if (!strncmp(argv[c], "--coverage-regions", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            want_rg = 1;
+            rg_file = argv[c][18] ? argv[c] + 19 : NULL;
+            continue;
+        }
+        if (!strcmp(argv[c], "--region-window") && c + 1 < argc) { rg_window = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--region-window=", 16)) { rg_window = argv[c] + 16; continue; }
         if (!strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { cov_min = atoll(argv[++c]); continue; }
         if (!strcmp(argv[c], "--target-cache") && c + 1 < argc) { tc_dir = argv[++c]; continue; }       /* (extension: the target cache, see sd_tc) */
         if (!strncmp(argv[c], "--target-cache=", 15)) { tc_dir = argv[c] + 15; continue; }
         argv[j++] = argv[c];
     }
     argc = j;
+    sd_rg.on = 0; sd_rg.genomes = NULL; sd_rg.ngenomes = 0;
     sd_co.on = 0;
     if (cov_only && want_cov) { fputs("strain_detect: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n", err); return sd_drop(p, ns); }
 
@@ -3022,6 +3164,21 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (!o && !S && !(ad && ad->o)) { fputs("strain_detect: --coverage-only needs -o: it names the strain and the table's default path (no hit list is written)\n", err); return sd_drop(p, ns); }
         want_cov = 1;
     }
+    if (want_rg || rg_window) {
+        long long w = 100000;
+        char *end = NULL;
+        if (!want_rg) { fputs("strain_detect: --region-window goes with --coverage-regions\n", err); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-regions goes with --coverage-depth or --coverage-only: it folds their table's numbers by region\n", err); return sd_drop(p, ns); }
+        if (rg_file && ((S && !a && !o && !r) || (ad && ad->o))) { fputs("strain_detect: --coverage-regions=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        if (rg_window) {
+            errno = 0;
+            w = strtoll(rg_window, &end, 10);
+            if (end == rg_window || *end || errno || w < 0) { fprintf(err, "strain_detect: --region-window %s: a number of bases, 0 or more (0: one region per record)\n", rg_window); return sd_drop(p, ns); }
+        }
+        if (!skh_regions_from_file || !skh_regions_free) { fputs("strain_detect: --coverage-regions: this build has no region table\n", err); return sd_drop(p, ns); }
+        if (ad && (!rg_genomes || rg_ngenomes != ad->n)) { fputs("strain_detect: --coverage-regions: the resident strains' genome files are not known\n", err); return sd_drop(p, ns); }
+        sd_rg.window = (uint64_t)w;
+    }
     if (ad) { a = ad->a[0]; r = "(resident)"; S = NULL; }
     if (S && !a && !o && !r) {
         if (!b && !B) { usage(err); return sd_drop(p, ns); }
@@ -3050,6 +3207,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     memset(sd_dev.ctx, 0, sizeof sd_dev.ctx);
     t_begin = now_s();
     sd_co.on = cov_only; sd_co.min = cov_min;
+    sd_co_ms_fold = sd_co_ms_sweep = 0;
+    sd_rg.on = want_rg;
     sd_co.flush_rows = (env = getenv("SK_SD_CO_FLUSH_ROWS")) != NULL && atoll(env) >= 1 ? (uint64_t)atoll(env) : 1u << 20;
     sd_res_bytes = 0;
     sd_tc_open(tc_dir, err);
@@ -3107,6 +3266,10 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             const uint32_t ng = (ns + sd_group - 1) / sd_group;
             if ((uint32_t)sd_dev.n > ng) sd_dev.n = ng ? (int)ng : 1;
         }
+        if (want_rg && ns) {                             /* (before any strain or target is opened: a refusal leaves nothing behind) */
+            if (!(rgs = (skh_regions *)calloc(ns, sizeof *rgs))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
+            for (nrgs = 0; nrgs < ns; nrgs++) if (sd_regions_load(&rgs[nrgs], paths[4 * nrgs], err)) goto done;
+        }
         if (sd_open_strains(p, ns, paths, 0, out, err)) goto done;
         if (ns == 0) { status = 0; goto done; }          /* nothing dealt to this rank */
     } else if (ad) {                                     /* (sd_dev: one device, the one the strains are on) */
@@ -3116,8 +3279,17 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             paths[4 * s + 2] = strdup(ad->o ? ad->o[s] : o);
             paths[4 * s + 3] = ad->o ? (ad->g && ad->g[s] ? strdup(ad->g[s]) : NULL) : (g ? strdup(g) : NULL);
         }
+        if (want_rg) {
+            if (!(rgs = (skh_regions *)calloc(ns, sizeof *rgs))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
+            for (nrgs = 0; nrgs < ns; nrgs++) if (sd_regions_load(&rgs[nrgs], rg_genomes[nrgs], err)) goto done;
+        }
         if (sd_open_strains(p, ns, paths, 1, out, err)) goto done;
     } else {
+        if (want_rg) {
+            if (!(rgs = (skh_regions *)calloc(1, sizeof *rgs))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
+            if (sd_regions_load(&rgs[0], r, err)) goto done;
+            nrgs = 1;
+        }
         p = (sd_prog *)malloc(sizeof *p);
         ns = 1;
         if (sd_strain_open(&p[0], r, a, g, o, device, out, err)) goto done;
@@ -3127,6 +3299,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     if (getenv("SK_SD_TIMING") && sd_dev.n > 1) fprintf(err, "strain_detect timing: %u strains on %d devices, one decode pipeline\n", ns, sd_dev.n);
     for (s = 0; want_cov && s < ns; s++)
         if (sd_coverage_open(&p[s], S ? NULL : cov_file, cov_min)) goto done;
+    for (s = 0; want_rg && s < ns; s++)
+        if (sd_regions_open(&p[s], &rgs[s], S || (ad && ad->o) ? NULL : rg_file)) goto done;
     if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
     for (s = 0; s < ns; s++)
         if (sd_coverage_write(&p[s])) goto done;
@@ -3189,6 +3363,9 @@ done:
     if (getenv("SK_SD_TIMING") && t_pw_parse > 0)
         fprintf(err, "strain_detect timing: parser threads, summed: parsing %.2f s, waiting for a segment %.2f s, for their turn to hand chunks on %.2f s, for room in the queue %.2f s\n",
                 t_pw_parse, t_pw_seg, t_pw_turn, t_pw_push);
+    if (getenv("SK_SD_TIMING") && cov_only)
+        fprintf(err, "strain_detect timing: coverage accumulators on the device: folds %.3f ms, target sweeps %.3f ms%s\n", sd_co_ms_fold, sd_co_ms_sweep,
+                want_rg ? " (folded by region)" : "");
     if (getenv("SK_SD_RESULT_BYTES"))
         fprintf(err, "strain_detect: scan results copied from the device: %llu bytes; --coverage-only: %llu runs counted on the device, %llu replayed, "
                      "%llu targets on the host accumulator (the process's totals)\n", (unsigned long long)sd_res_bytes,
@@ -3196,6 +3373,9 @@ done:
     sd_tc_close(err);
     sd_pin_close();
     sd_co.on = 0;
+    sd_rg.on = 0;
+    for (s = 0; rgs && s < nrgs; s++) skh_regions_free(&rgs[s]);
+    free(rgs);
     {   /* closing a strain = finishing its gz output, freeing its device context and tables: strain by strain on threads */
         sd_pool cp;
         const double t0 = now_s();

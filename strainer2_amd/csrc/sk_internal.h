@@ -15,6 +15,8 @@ int sk_ctx_device_(const sk_ctx *ctx);
 /* column `col` of the resident counters, in the caller's row order, into a device buffer of nrows u32;
  * complete on return */
 int sk_counts_rows_to_device_(sk_ctx *ctx, uint32_t col, uint32_t *d_out);
+/* sk_table_first_pos into a device buffer of nrows u32 on the context's device; complete on return */
+int sk_table_first_pos_to_device_(sk_ctx *ctx, uint32_t *d_out);
 /* coverage/depth accumulator of sk_host_cov.c, fed by strain_detect when steps 3 and 4 are fused */
 typedef struct skc_acc skc_acc;
 skc_acc *skc_create(int64_t min_hits);
@@ -23,6 +25,14 @@ int skc_add_hit(skc_acc *a, const char *metagenome, int64_t hits_pe1, int64_t hi
 int skc_add_counts(skc_acc *a, const char *metagenome, uint64_t unique, uint64_t total);
 int skc_add_trailer(skc_acc *a, const char *metagenome, const char *name, int64_t value);
 int skc_report(skc_acc *a, sk_ctx *ctx, const char *hits_file_name, FILE *out, FILE *err);
+/* ... and per region of the strain's genome (strain_detect --coverage-regions): counts handed in per metagenome and region (next to
+ * skc_add_counts), or folded from the hits by skc_report_regions, which prints the table; call it after skc_report */
+int skc_add_region_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t nbins);
+int skc_report_regions(skc_acc *a, const char *hits_file_name, const skh_regions *rg, const uint32_t *row_region, uint32_t nrows,
+                       const uint64_t *reg_inf, FILE *out, FILE *err);
+/* kmer_scrub_count --detect: the genome files of the strains the next skh_strain_detect_resident[_many] call adopts (it has no -r;
+ * --coverage-regions reads the records' names and lengths from them).  The call takes the list and forgets it. */
+void skh_resident_genomes_(const char *const *paths, uint32_t n);
 /* strain_detect's key set built on the device (sk_host.c): SK_OK, the ctx holds the table and *ks the keys in row order; SK_E_UNSUPPORTED: a
  * strain with letters other than A/C/G/T/N (byte-string keys) or without a key -- the caller builds it on the host */
 int skh_keyset_build_on_device(skh_keyset *ks, sk_ctx *ctx, const char *path, uint32_t ncols, uint32_t col0_value);
@@ -69,6 +79,9 @@ typedef struct sk_tally_view {
     const uint32_t *d_rec_start; uint32_t nrec;
 } sk_tally_view;
 int sk_tally_view_(sk_ctx *ctx, sk_union *u, sk_tally_view *out);
+/* the accumulator's device time (events around every fold and every target sweep): on != 0 starts the clocks, ms_fold / ms_sweep
+ * (NULL: not wanted) are the sums so far.  Off unless asked for: strain_detect asks under SK_SD_TIMING. */
+int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *ms_sweep);
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,11 @@
  *   END_STALE  (-1 before the reset: the file ended while seeking the next header after a FASTQ record;
  *               the reference's seq.l still holds the previous record's length)
  *   END_TRUNC  (-2: quality string length mismatch; seq.l is that record's sequence length)
+ *
+ * A translation unit that defines SKP_NAME_SINK before including this file gets an optional name sink as well: on_name, when set
+ * (parser_set_name_sink), is called with the record's name -- the header's text up to the first white space (src/kseq.h:180) --
+ * right before on_record.  Without the macro nothing of it is compiled; with it and no sink set the parser takes the steps it
+ * takes without it.
  */
 #ifndef SK_PARSER_H
 #define SK_PARSER_H
@@ -33,6 +38,10 @@ typedef struct {
     int     end_kind;       /* SKP_END_* once the input is exhausted or the parser stopped */
     size_t  end_len;        /* the reference's seq.l at that point */
     size_t  last_len;       /* length of the last record handed out */
+#ifdef SKP_NAME_SINK
+    int   (*on_name)(void *user, const char *name, size_t len);
+    char   *name; size_t name_len, name_cap;
+#endif
 } parser;
 
 static void grow(char **p, size_t *cap, size_t need)
@@ -53,7 +62,12 @@ static void parser_init(parser *ps, rec_fn fn, void *user)
     ps->user = user;
 }
 
+#ifdef SKP_NAME_SINK
+static void parser_set_name_sink(parser *ps, int (*fn)(void *user, const char *name, size_t len)) { ps->on_name = fn; }
+static void parser_free(parser *ps) { free(ps->seq); free(ps->qual); free(ps->name); }
+#else
 static void parser_free(parser *ps) { free(ps->seq); free(ps->qual); }
+#endif
 
 static void emit(parser *ps)
 {
@@ -61,6 +75,15 @@ static void emit(parser *ps)
     ps->seq[ps->seq_len] = '\0';
     ps->nrecords++;
     ps->last_len = ps->seq_len;
+#ifdef SKP_NAME_SINK
+    if (ps->on_name) {
+        int rc;
+        grow(&ps->name, &ps->name_cap, ps->name_len);
+        ps->name[ps->name_len] = '\0';
+        rc = ps->on_name(ps->user, ps->name, ps->name_len);
+        if (rc) { ps->sink_rc = rc; ps->state = P_STOP; return; }
+    }
+#endif
     if (ps->on_record) {
         int rc = ps->on_record(ps->user, ps->seq, ps->seq_len);
         if (rc) { ps->sink_rc = rc; ps->state = P_STOP; }
@@ -73,6 +96,9 @@ static void begin_header(parser *ps)
     ps->name_any = 0;
     ps->seq_len = 0;
     ps->qual_len = 0;
+#ifdef SKP_NAME_SINK
+    ps->name_len = 0;
+#endif
 }
 
 /* a trailing CR is dropped once the accumulated text is longer than one byte (src/kseq.h:136) */
@@ -99,6 +125,9 @@ static int parser_whole_record(parser *ps, const unsigned char *b, size_t n, siz
 {
     const unsigned char *const end = b + n, *s, *q, *e1, *e2, *e3, *e4;
     size_t len, qlen;
+#ifdef SKP_NAME_SINK
+    if (ps->on_name) return 0;                           /* (the general way keeps the name) */
+#endif
     if (!(e1 = (const unsigned char *)memchr(b + *at + 1, '\n', (size_t)(end - (b + *at + 1))))) return 0;
     s = e1 + 1;
     if (s >= end || *s == '\n' || *s == '>' || *s == '@' || *s == '+') return 0;
@@ -143,7 +172,19 @@ static void parser_feed(parser *ps, const unsigned char *b, size_t n)
             /* the name ends at the first white space and the rest of the header line is skipped (P_COMMENT), so all
              * that matters is where the line ends; a header cut off by the end of the input gives an empty record
              * from either state (parser_eof) */
-            const unsigned char *nl = (const unsigned char *)memchr(b + i, '\n', n - i);
+            const unsigned char *nl;
+#ifdef SKP_NAME_SINK
+            if (ps->on_name) {                           /* the name's bytes are kept; the rest of the line is P_COMMENT's */
+                while (i < n && !isspace(b[i])) {
+                    grow(&ps->name, &ps->name_cap, ps->name_len + 1);
+                    ps->name[ps->name_len++] = (char)b[i++];
+                    ps->name_any = 1;
+                }
+                if (i < n) { ps->name_any = 1; ps->state = P_COMMENT; }
+                break;
+            }
+#endif
+            nl = (const unsigned char *)memchr(b + i, '\n', n - i);
             if (i < n) ps->name_any = 1;
             if (nl) { i = (size_t)(nl - b) + 1; ps->state = P_LINE_START; } else i = n;
             break; }

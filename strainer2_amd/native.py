@@ -66,6 +66,8 @@ ABI_SYMBOLS = [
     "sk_covacc_create", "sk_covacc_destroy", "sk_covacc_hold", "sk_covacc_add", "sk_covacc_add_rows", "sk_covacc_finish_target", "sk_covacc_rows",
     "sk_covacc_pick", "sk_covacc_fetch_hold", "skh_coverage_only_stats",
     "sk_tally_collect_counts", "sk_tally_fetch_held", "sk_union_tally_launch_ex", "sk_union_tally_collect_counts", "sk_union_tally_fetch_held",
+    "skh_regions_from_file", "skh_regions_free", "sk_table_first_pos", "sk_covacc_set_regions", "sk_covacc_region_rows",
+    "sk_covacc_finish_target_regions",
 ]
 
 
@@ -293,6 +295,10 @@ class Keyset:
     def first_count(self):
         return np.ctypeslib.as_array(self._s.first_count, shape=(max(self.nrows, 1),))[: self.nrows].copy()
 
+    def first_pos(self):
+        """text position of each row's first all-ACGT occurrence along the strain, 0xFFFFFFFF for none"""
+        return np.ctypeslib.as_array(self._s.first_pos, shape=(max(self.nrows, 1),))[: self.nrows].copy()
+
     def key(self, row):
         buf = C.create_string_buffer(32)
         lib.skh_keyset_key(C.byref(self._s), row, buf)
@@ -381,6 +387,47 @@ class KmerContext:
 
     def load_keyset(self, ks: Keyset, ncols=4):
         self._ck(lib.skh_keyset_load(self._h, C.byref(ks._s), ncols))
+
+    def build_from_text(self, records, ncols=4, col0_value=1):
+        """sk_table_build_from_text from records of A/C/G/T/N bytes (those of 30 bases or more make the text, end to end): the whole
+        table is made on the device, rows in strain order; returns the row count"""
+        text, ok = [], []
+        for r in records:
+            if len(r) + 1 < SK_K:
+                continue
+            a = np.frombuffer(bytes(r).upper(), dtype=np.uint8)
+            good = np.isin(a, np.frombuffer(b"ACGT", dtype=np.uint8))
+            run = np.zeros(len(a) + 1, dtype=np.int64)
+            for i in range(len(a)):
+                run[i + 1] = run[i] + 1 if good[i] else 0
+            st = np.zeros(len(a), dtype=bool)
+            st[: max(len(a) - SK_K + 1, 0)] = run[SK_K:] >= SK_K
+            text.append(np.where(good, (a >> 1) & 3, 0).astype(np.uint32))      # (A 0, C 1, T 2, G 3 by bits 1..2 of the letter ...)
+            ok.append(st)
+        code = np.concatenate(text)
+        lut = np.zeros(4, dtype=np.uint32)
+        lut[[0, 1, 2, 3]] = [0, 1, 3, 2]                                           # (... to A 0, C 1, G 2, T 3)
+        code = lut[code]
+        ok = np.concatenate(ok)
+        n = len(code)
+        pad = np.zeros((-n) % 16, dtype=np.uint32)
+        words = np.concatenate([code, pad]).reshape(-1, 16)
+        text2 = np.zeros(len(words) + 4, dtype=np.uint32)
+        for j in range(16):
+            text2[: len(words)] |= words[:, j] << np.uint32(2 * (15 - j))
+        okw = np.zeros((n + 31) // 32 + 2, dtype=np.uint32)
+        idx = np.nonzero(ok)[0]
+        np.bitwise_or.at(okw, idx >> 5, (np.uint32(1) << (idx & 31).astype(np.uint32)))
+        nrows = C.c_uint32(0)
+        self._ck(lib.sk_table_build_from_text(self._h, text2.ctypes.data, okw.ctypes.data, n, len(idx), ncols, col0_value, C.byref(nrows)))
+        return int(nrows.value)
+
+    def first_pos(self):
+        """sk_table_first_pos: every row's first text position as the table on the device has it (0xFFFFFFFF: none)"""
+        n = int(lib.sk_table_rows(self._h))
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._ck(lib.sk_table_first_pos(self._h, out.ctypes.data))
+        return out[:n]
 
     def load_table(self, keys: np.ndarray, ncols=4):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
@@ -696,6 +743,40 @@ def coverage_only_stats(reset=False):
     return tuple(int(x.value) for x in v)
 
 
+SKH_REGIONS_MAX = 1 << 20
+
+
+class _RegionsStruct(C.Structure):
+    """skh_regions"""
+    _fields_ = [("n", C.c_uint32), ("nnames", C.c_uint32), ("text_bases", C.c_uint64), ("text_off", C.POINTER(C.c_uint64)),
+                ("record", C.POINTER(C.c_uint32)), ("rec_off", C.POINTER(C.c_uint64)), ("len", C.POINTER(C.c_uint64)),
+                ("name", C.POINTER(C.c_char_p)), ("names", C.POINTER(C.c_char_p)), ("too_many", C.c_int)]
+
+
+lib.skh_regions_from_file.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(_RegionsStruct)]
+lib.skh_regions_free.argtypes = [C.POINTER(_RegionsStruct)]
+lib.skh_regions_free.restype = None
+lib.sk_table_first_pos.argtypes = [C.c_void_p, C.c_void_p]
+lib.sk_table_build_from_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+lib.sk_covacc_set_regions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+lib.sk_covacc_region_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.sk_covacc_finish_target_regions.argtypes = [C.c_void_p] * 5
+
+
+def regions_from_file(path, window=100000):
+    """skh_regions_from_file: (regions, text_bases); regions = [(text offset, record number from 1, offset in the record, length,
+    record name as bytes)] in text order -- the strain's records of 30 bases or more cut into windows of `window` bases (0: one
+    region per record).  More than SKH_REGIONS_MAX regions: SKError."""
+    s = _RegionsStruct()
+    rc = lib.skh_regions_from_file(os.fsencode(path), int(window), C.byref(s))
+    if rc:
+        raise SKError(rc, f"{path}: more than {SKH_REGIONS_MAX} regions" if s.too_many else str(path))
+    try:
+        return [(int(s.text_off[i]), int(s.record[i]), int(s.rec_off[i]), int(s.len[i]), s.name[i]) for i in range(s.n)], int(s.text_bases)
+    finally:
+        lib.skh_regions_free(C.byref(s))
+
+
 class TallyBatch:
     """A batch of records resident on a context's device (sk_batch_*), to be tallied against one or more tables."""
 
@@ -993,6 +1074,36 @@ class CoverageAcc:
         tot = np.zeros(len(self.nrows), dtype=np.uint64)
         self._ctx._ck(lib.sk_covacc_finish_target(self._h, uq.ctypes.data, tot.ctypes.data))
         return uq, tot
+
+    def set_regions(self, member, ctx, region_start):
+        """sk_covacc_set_regions: member's rows are the rows of ctx's table; each goes to the last region that starts at or before
+        its first text position, rows without one to region len(region_start)"""
+        rs = np.ascontiguousarray(region_start, dtype=np.uint32).reshape(-1)
+        self._ctx._ck(lib.sk_covacc_set_regions(self._h, member, ctx._h, rs.ctypes.data, len(rs)))
+        self._nreg = getattr(self, "_nreg", None) or [0] * len(self.nrows)
+        self._nreg[member] = len(rs)
+
+    def region_rows(self, member, ctx, type_col=0, informative_value=2):
+        """sk_covacc_region_rows: (rows, informative rows) per region of member, the unplaced ones last"""
+        nb = (getattr(self, "_nreg", None) or [0] * len(self.nrows))[member] + 1
+        rows, inf = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+        self._ctx._ck(lib.sk_covacc_region_rows(self._h, member, ctx._h, type_col, informative_value, rows.ctypes.data, inf.ctypes.data))
+        return rows, inf
+
+    def finish_target_regions(self):
+        """sk_covacc_finish_target_regions: (unique[nmembers], total[nmembers], [per member: (unique, total) per region, the unplaced
+        rows' last]); the counters are zero afterwards"""
+        nreg = getattr(self, "_nreg", None) or [0] * len(self.nrows)
+        uq = np.zeros(len(self.nrows), dtype=np.uint64)
+        tot = np.zeros(len(self.nrows), dtype=np.uint64)
+        bins = sum(n + 1 for n in nreg)
+        ru, rt = np.zeros(bins, dtype=np.uint64), np.zeros(bins, dtype=np.uint64)
+        self._ctx._ck(lib.sk_covacc_finish_target_regions(self._h, uq.ctypes.data, tot.ctypes.data, ru.ctypes.data, rt.ctypes.data))
+        per, at = [], 0
+        for n in nreg:
+            per.append((ru[at: at + n + 1].copy(), rt[at: at + n + 1].copy()))
+            at += n + 1
+        return uq, tot, per
 
     def close(self):
         if getattr(self, "_h", None):

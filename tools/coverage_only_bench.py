@@ -10,7 +10,13 @@ process, CPU-seconds (user + system of the child) and the bytes of scan results 
 --parent-exe names strain_detect of a build of the parent commit, which runs --coverage-depth three times per case: the figures the
 new flag is to be set against.
 
+--regions W measures --coverage-regions instead: --coverage-only without and with `--coverage-regions --region-window W` alternate
+(the coverage tables must be the same bytes, and every run with the flag must write the same region tables), --parent-exe runs plain
+--coverage-only, and each line also carries the accumulators' device time -- their folds and their target sweeps, summed over the
+run (SK_SD_TIMING; the parent build does not report it).
+
     python tools/coverage_only_bench.py [--gbases 1.5] [--parent-exe PATH] [--out profiles/coverage_only_bench.txt]
+    python tools/coverage_only_bench.py --regions 100000 --rounds 5 [--parent-exe PATH] [--out profiles/coverage_regions_bench.txt]
 """
 import argparse
 import hashlib
@@ -34,6 +40,7 @@ from text_parse_bench import reads_text  # noqa: E402  (the generator of the oth
 
 EXE = os.path.join(REPO, "strainer2_amd", "bin", "strain_detect")
 PASS = re.compile(rb"strain_detect timing: setup ([0-9.]+) s,.*?total before close ([0-9.]+) s")
+ACC = re.compile(rb"coverage accumulators on the device: folds ([0-9.]+) ms, target sweeps ([0-9.]+) ms")
 BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
 
 
@@ -48,7 +55,7 @@ def row(rs, key, spec):
 def step(exe, argv, env, limit, cwd, ns, hit_lists):
     """one run of the program under its own time limit -> measurements; raises StepFailed (nothing more is started then)"""
     for s in range(ns):
-        for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth"):
+        for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -64,11 +71,49 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             raise StepFailed(f"out{s}.gz {'is missing' if hit_lists else 'was written'}")
         with open(os.path.join(cwd, f"out{s}.gz.coverage_depth"), "rb") as f:
             h.update(f.read())
+    hr = hashlib.md5()
+    for s in range(ns):
+        if os.path.exists(os.path.join(cwd, f"out{s}.gz.coverage_regions")):
+            with open(os.path.join(cwd, f"out{s}.gz.coverage_regions"), "rb") as f:
+                hr.update(f.read())
     m = PASS.search(p.stderr)
     b = BYTES.search(p.stderr)
-    return dict(wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
+    a = ACC.search(p.stderr)
+    return dict(fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
                 passed=float(m.group(2)) - float(m.group(1)) if m else float("nan"),
                 d2h=int(b.group(1)) if b else -1, dev=int(b.group(2)) if b else -1, replayed=int(b.group(3)) if b else -1)
+
+
+def regions_case(say, args, env, tmp, ns, kind, argv):
+    """--coverage-only without and with --coverage-regions, alternating; the parent build's plain --coverage-only behind them"""
+    with_rg = ["--coverage-only", "--coverage-regions", "--region-window", str(args.regions)]
+    res = {"plain": [], "regions": []}
+    md5 = md5r = None
+    for rnd in range(args.rounds):
+        for tag, flags in (("plain", ["--coverage-only"]), ("regions", with_rg)):
+            r = step(EXE, argv + flags, dict(env), args.limit, tmp, ns, False)
+            md5 = md5 or r["md5"]
+            if r["md5"] != md5:
+                raise StepFailed(f"{ns} strains, {kind}, round {rnd}, {tag}: the coverage tables differ from the first run's")
+            if tag == "regions":
+                md5r = md5r or r["md5r"]
+                if r["md5r"] != md5r:
+                    raise StepFailed(f"{ns} strains, {kind}, round {rnd}: the region tables differ from the first run's")
+            res[tag].append(r)
+    say(f"{ns} strains, {kind}: the {ns} coverage tables are the same bytes in all {2 * args.rounds} runs (MD5 {md5}), "
+        f"the region tables in all {args.rounds} (MD5 {md5r})")
+    names = {"plain": "--coverage-only", "regions": f"... --coverage-regions --region-window {args.regions}"}
+    for tag, rs in res.items():
+        say(f"    {names[tag]}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; accumulators on the device: folds "
+            f"{row(rs, 'fold', '.2f')} ms, target sweeps {row(rs, 'sweep', '.3f')} ms; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
+    med = {t: {k: statistics.median(r[k] for r in rs) for k in ("passed", "wall", "fold", "sweep")} for t, rs in res.items()}
+    say("    with regions / without at the medians: pass %.2f, wall %.2f, folds %.2f, target sweeps %.2f" %
+        tuple(med["regions"][k] / med["plain"][k] if med["plain"][k] else float("nan") for k in ("passed", "wall", "fold", "sweep")))
+    if args.parent_exe:
+        rs = [step(args.parent_exe, argv + ["--coverage-only"], dict(env), args.limit, tmp, ns, False) for _ in range(args.rounds)]
+        if any(r["md5"] != md5 for r in rs):
+            raise StepFailed(f"{ns} strains, {kind}: the parent build writes other tables")
+        say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
 def main():
@@ -78,6 +123,7 @@ def main():
     ap.add_argument("--strains", default="8,32")
     ap.add_argument("--limit", type=int, default=150, help="seconds one run of the program may take")
     ap.add_argument("--parent-exe", default=None, help="strain_detect of a build of the parent commit")
+    ap.add_argument("--regions", type=int, default=None, help="measure --coverage-regions with this --region-window")
     ap.add_argument("--out", default=None)
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
     args = ap.parse_args()
@@ -130,6 +176,9 @@ def main():
             for ns in counts:
                 for kind, lst in lists.items():
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
+                    if args.regions is not None:
+                        regions_case(say, args, env, tmp, ns, kind, argv)
+                        continue
                     res = {"--coverage-depth": [], "--coverage-only": []}
                     md5 = None
                     for rnd in range(args.rounds):
