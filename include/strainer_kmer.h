@@ -715,8 +715,42 @@ int  sk_covacc_region_rows(sk_covacc *a, uint32_t member, sk_ctx *ctx, uint32_t 
                            uint64_t *out_rows /* nregions + 1 */, uint64_t *out_informative /* nregions + 1 */);
 int  sk_covacc_finish_target_regions(sk_covacc *a, uint64_t *out_unique /* nmembers */, uint64_t *out_total /* nmembers */,
                                      uint64_t *reg_unique /* sum of nregions[m] + 1 */, uint64_t *reg_total);
+/* The DEPTH SPECTRUM (new: strain_detect --coverage-spectrum, coverage_depth --spectrum): per strain and target, how many
+ * informative k-mers were seen 0, 1, 2, ... times.  kmer_coverage and kmer_depth do not say how the depth is distributed: a strain
+ * present at mean depth L has its informative k-mers around L and about e^-L of them unseen; a related strain, a shared mobile
+ * element or a few conserved high-copy k-mers leave most at depth 0 and a few very deep, with the same kmer_depth.  The rule, for a
+ * strain, a sample and a maximum depth D (--spectrum-max, 1 <= D <= SK_COVACC_SPECTRUM_MAX = 1023, default 255):
+ *   sample    a target's basename, as in the script.
+ *   depth of a row = the number of hit lines on that row that pass the script's read filter (total_kmer > min_kmer_hits): what
+ *             sk_covacc's counter holds before the sweep, and the number of times the host accumulator's list holds (sample, row).
+ *   n[d]      for 1 <= d <= D: rows with depth exactly d.       n[>D]: rows with depth above D.
+ *   hits[d]   = d * n[d].                                        hits[>D]: the sum of the depths above D (u64).
+ *   n[0]      = I - sum over d >= 1 of n[d], hits[0] = 0; I = the strain's informative rows, the value of the
+ *             total_genome_informative_kmers trailer.  Only informative rows are ever logged, so the host subtracts and no device
+ *             pass over the type column is needed.
+ *   invariants  the n[d] with d >= 1 sum to unique_observed_informative_kmers and the hits to total_observed_informative_kmers of
+ *             the main table's line for that sample.
+ *   table     a header line, then one line per sample and non-empty bin, samples in the main table's order; the 0 line is
+ *             printed whenever I is known, even when its count is 0.  All columns are integers:
+ *               strain_name<TAB>metagenome<TAB>depth<TAB>informative_kmers<TAB>observed_hits
+ *             depth is 0, 1, ..., D, then >D.
+ * sk_covacc_set_spectrum: 0 turns the spectrum off (the state after create), 1..SK_COVACC_SPECTRUM_MAX turn it on with that D;
+ * anything else is SK_E_ARG.  sk_covacc_finish_target and sk_covacc_finish_target_regions return what they return without it.
+ * sk_covacc_finish_target_spectrum: sk_covacc_finish_target, and the same one sweep of the counters (they are zero afterwards)
+ * yields every member's spectrum -- spec[m * (D + 1) + d - 1] = n[d] for d <= D, spec[m * (D + 1) + D] = n[>D], deep_total[m] =
+ * hits[>D] -- and, when reg_unique is not NULL, the region pairs of sk_covacc_finish_target_regions.  SK_E_STATE with the spectrum off.
+ * sk_distinct_spectrum: sk_distinct_count with the spectrum of the keys' multiplicities per sample, same layout. */
+#define SK_COVACC_SPECTRUM_MAX 1023u
+int  sk_covacc_set_spectrum(sk_covacc *a, uint32_t max_depth);
+int  sk_covacc_finish_target_spectrum(sk_covacc *a, uint64_t *out_unique /* nmembers */, uint64_t *out_total /* nmembers */,
+                                      uint64_t *spec /* nmembers x (max_depth + 1): n[1..D], n[>D] */, uint64_t *deep_total /* nmembers: hits[>D] */,
+                                      uint64_t *reg_unique /* NULL: no regions */, uint64_t *reg_total);
+int  sk_distinct_spectrum(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, uint64_t n, uint32_t nsamples, uint32_t max_depth,
+                          uint64_t *out_unique, uint64_t *out_total, uint64_t *spec /* nsamples x (max_depth + 1) */, uint64_t *deep_total);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
- * same stdout bytes and exit status. */
+ * same stdout bytes and exit status.  New: --spectrum[=FILE] [--spectrum-max D] also writes the depth spectrum (above) to FILE,
+ * default the hits file's path with a trailing ".kmer_hits.gz" removed plus ".coverage_spectrum"; stdout is unchanged.  A hit list
+ * in the general (non-ACGT text) mode is refused. */
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err);
 
 #ifdef __cplusplus

@@ -12,6 +12,7 @@
 //   covacc_scatter   again, storing zeros: tot[] is all zero between folds, so no fold pays a memset of pairs x members.
 // covacc_finish sweeps depth[] once per target: non-zero rows, their sum, and zeros left behind.  covacc_finish_regions is the same
 // sweep with every non-zero row also added to the pair of its region of the strain's genome (strain_detect --coverage-regions).
+// covacc_finish_spectrum is either of them with every non-zero row also counted in the bin of its depth (--coverage-spectrum).
 // Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -234,6 +235,76 @@ __global__ void __launch_bounds__(256) covacc_finish_regions(uint32_t *__restric
             if (b_unq[b]) { atomicAdd(ro + 2ull * b, (unsigned long long)b_unq[b]); atomicAdd(ro + 2ull * b + 1ull, b_tot[b]); }
 }
 
+// ---- the same sweep with the depth spectrum (include/strainer_kmer.h has the rule; strain_detect --coverage-spectrum) ----
+// covacc_finish (REGIONS: covacc_finish_regions), and every non-zero row of count v also adds 1 to bin min(v, D + 1) - 1 of its
+// member's spectrum and, above D, v to the member's deep sum.  The D + 1 <= COV_SPEC_BINS bins are always in LDS; a workgroup adds
+// its non-empty ones to HBM once.  The bins take plain LDS atomics, not a sub-histogram per wave: only informative rows are ever
+// non-zero, about 1 % of a table, so a wave's 64 rows hold 0.6 of them on average and two lanes of one DS instruction on one bin are
+// the exception; where every row is non-zero at one depth (the test of 70 001 rows at depth 1) the adds of a wave serialise on one
+// bank and the sweep is as correct and still one pass.  Sub-histograms would cost 4 x 4 KB of LDS and a merge in every workgroup to
+// win that case only.  (An argument from the shape of the data; profiles/coverage_spectrum_bench.txt has what was measured.)
+#define COV_SPEC_BINS (SK_COVACC_SPECTRUM_MAX + 1u)
+
+template <bool REGIONS>
+__global__ void __launch_bounds__(256) covacc_finish_spectrum(uint32_t *__restrict__ depth, const uint64_t *__restrict__ row_base,
+                                                              const uint32_t *__restrict__ nrows, const uint32_t *__restrict__ region,
+                                                              const uint32_t *__restrict__ nreg, const uint64_t *__restrict__ reg_base,
+                                                              unsigned long long *__restrict__ out, unsigned long long *__restrict__ reg_out,
+                                                              uint32_t max_depth, unsigned long long *__restrict__ spec,
+                                                              unsigned long long *__restrict__ deep)
+{
+    __shared__ unsigned long long s_tot[256];
+    __shared__ uint32_t s_unq[256];
+    __shared__ uint32_t h_n[COV_SPEC_BINS];
+    __shared__ unsigned long long h_deep;
+    __shared__ unsigned long long b_tot[REGIONS ? COV_BINS : 1u];
+    __shared__ uint32_t b_unq[REGIONS ? COV_BINS : 1u];
+    const uint32_t m = blockIdx.y, n = nrows[m];
+    const uint32_t D = max_depth < SK_COVACC_SPECTRUM_MAX ? max_depth : SK_COVACC_SPECTRUM_MAX, ns = D + 1u;   // (ns <= COV_SPEC_BINS)
+    const uint32_t nb = REGIONS ? nreg[m] + 1u : 0u;
+    const bool in_lds = REGIONS && nb <= COV_BINS;
+    uint32_t *d = depth + row_base[m];
+    const uint32_t *rg = REGIONS ? region + row_base[m] : NULL;
+    unsigned long long *ro = REGIONS ? reg_out + 2ull * reg_base[m] : NULL;
+    for (uint32_t b = threadIdx.x; b < ns; b += 256u) h_n[b] = 0u;
+    if (threadIdx.x == 0u) h_deep = 0ull;
+    if (in_lds)
+        for (uint32_t b = threadIdx.x; b < nb; b += 256u) { b_tot[b] = 0ull; b_unq[b] = 0u; }
+    __syncthreads();
+    unsigned long long t = 0;
+    uint32_t u = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t v = d[i];
+        if (!v) continue;
+        d[i] = 0u; u++; t += v;
+        atomicAdd(&h_n[(v < ns ? v : ns) - 1u], 1u);
+        if (v > D) atomicAdd(&h_deep, (unsigned long long)v);
+        if (REGIONS) {
+            const uint32_t r = rg[i];
+            if (r >= nb) continue;                            // (never: a region no start stands behind)
+            if (in_lds) { atomicAdd(&b_unq[r], 1u); atomicAdd(&b_tot[r], (unsigned long long)v); }
+            else { atomicAdd(ro + 2ull * r, 1ull); atomicAdd(ro + 2ull * r + 1ull, (unsigned long long)v); }
+        }
+    }
+    s_tot[threadIdx.x] = t; s_unq[threadIdx.x] = u;
+    __syncthreads();
+    for (uint32_t w = 128u; w; w >>= 1) {
+        if (threadIdx.x < w) { s_tot[threadIdx.x] += s_tot[threadIdx.x + w]; s_unq[threadIdx.x] += s_unq[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (!s_unq[0]) return;                                    // (the whole workgroup: nothing to add anywhere)
+    if (threadIdx.x == 0u) {
+        atomicAdd(out + 2u * m, (unsigned long long)s_unq[0]);
+        atomicAdd(out + 2u * m + 1u, s_tot[0]);
+        if (h_deep) atomicAdd(deep + m, h_deep);
+    }
+    for (uint32_t b = threadIdx.x; b < ns; b += 256u)
+        if (h_n[b]) atomicAdd(spec + (size_t)m * ns + b, (unsigned long long)h_n[b]);
+    if (in_lds)
+        for (uint32_t b = threadIdx.x; b < nb; b += 256u)
+            if (b_unq[b]) { atomicAdd(ro + 2ull * b, (unsigned long long)b_unq[b]); atomicAdd(ro + 2ull * b + 1ull, b_tot[b]); }
+}
+
 struct sk_covacc {
     sk_ctx *ctx; int device;
     hipStream_t stream;
@@ -255,6 +326,8 @@ struct sk_covacc {
     uint32_t *d_nreg; uint64_t *d_reg_base;                 // [nm]
     void *d_reg_out; size_t reg_out_cap;                    // [total_bins] pairs
     void *d_fp, *d_starts; size_t fp_cap, starts_cap;       // set_regions' scratch: first positions (region_rows: the type column), region starts
+    // the depth spectrum: off (spec_d = 0) until sk_covacc_set_spectrum
+    uint32_t spec_d; void *d_spec; size_t spec_cap;         // [nm x (spec_d + 1)] bins, then [nm] deep sums
     // device time of the folds and of the targets' sweeps, kept only when somebody asked (sk_covacc_timing_)
     bool timed; hipEvent_t ev0, ev1; double ms_fold, ms_sweep;
 };
@@ -305,7 +378,7 @@ extern "C" void sk_covacc_destroy(sk_covacc *a)
     (void)hipFree(a->d_tot); (void)hipFree(a->d_rows); (void)hipFree(a->h_recs); (void)hipFree(a->h_hits); (void)hipFree(a->h_rs);
     (void)hipFree(a->p_recs); (void)hipFree(a->p_hits); (void)hipFree(a->p_cnt);
     (void)hipFree(a->d_region); (void)hipFree(a->d_nreg); (void)hipFree(a->d_reg_base); (void)hipFree(a->d_reg_out);
-    (void)hipFree(a->d_fp); (void)hipFree(a->d_starts);
+    (void)hipFree(a->d_fp); (void)hipFree(a->d_starts); (void)hipFree(a->d_spec);
     if (a->timed) { (void)hipEventDestroy(a->ev0); (void)hipEventDestroy(a->ev1); }
     if (a->h_bad) (void)hipHostFree(a->h_bad);
     if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -641,5 +714,56 @@ extern "C" int sk_covacc_finish_target_regions(sk_covacc *a, uint64_t *out_uniqu
     cov_t1(a, &a->ms_sweep);
     for (uint32_t m = 0; m < a->nm; m++) { out_unique[m] = h[2u * m]; out_total[m] = h[2u * m + 1u]; }
     for (uint64_t r = 0; r < a->total_bins; r++) { reg_unique[r] = hr[2u * r]; reg_total[r] = hr[2u * r + 1u]; }
+    return SK_OK;
+}
+
+// ---- the depth spectrum ----
+extern "C" int sk_covacc_set_spectrum(sk_covacc *a, uint32_t max_depth)
+{
+    if (!a || max_depth > SK_COVACC_SPECTRUM_MAX) return SK_E_ARG;
+    if (max_depth) {
+        CA_HIP(hipSetDevice(a->device));
+        const int rc = cov_room(a, &a->d_spec, &a->spec_cap, ((size_t)a->nm * (max_depth + 1u) + a->nm) * 8u, false);
+        if (rc != SK_OK) return rc;
+    }
+    a->spec_d = max_depth;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_finish_target_spectrum(sk_covacc *a, uint64_t *out_unique, uint64_t *out_total, uint64_t *spec, uint64_t *deep_total,
+                                                uint64_t *reg_unique, uint64_t *reg_total)
+{
+    if (!a || !out_unique || !out_total || !spec || !deep_total || (!reg_unique) != (!reg_total)) return SK_E_ARG;
+    if (!a->spec_d) return sk_fail_(a->ctx, SK_E_STATE, "the spectrum is off (sk_covacc_set_spectrum)");
+    CA_HIP(hipSetDevice(a->device));
+    const bool regions = reg_unique != NULL;
+    int rc;
+    if (regions && !a->d_region && (rc = cov_regions_sync(a)) != SK_OK) return rc;
+    const size_t nspec = (size_t)a->nm * (a->spec_d + 1u), nall = nspec + a->nm;
+    std::vector<unsigned long long> h((size_t)a->nm * 2u), hs(nall), hr(regions ? (size_t)a->total_bins * 2u : 0u);
+    unsigned long long *d_spec = (unsigned long long *)a->d_spec;
+    cov_t0(a);
+    CA_HIP(hipMemsetAsync(a->d_out, 0, (size_t)a->nm * 16u, a->stream));
+    CA_HIP(hipMemsetAsync(a->d_spec, 0, nall * 8u, a->stream));
+    if (regions) CA_HIP(hipMemsetAsync(a->d_reg_out, 0, (size_t)a->total_bins * 16u, a->stream));
+    unsigned gx = (a->max_rows + 255u) / 256u;
+    gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
+    if (regions)
+        hipLaunchKernelGGL(covacc_finish_spectrum<true>, dim3(gx, a->nm), dim3(256), 0, a->stream, a->d_depth, (const uint64_t *)a->d_base,
+                           (const uint32_t *)a->d_nrows, (const uint32_t *)a->d_region, (const uint32_t *)a->d_nreg,
+                           (const uint64_t *)a->d_reg_base, a->d_out, (unsigned long long *)a->d_reg_out, a->spec_d, d_spec, d_spec + nspec);
+    else
+        hipLaunchKernelGGL(covacc_finish_spectrum<false>, dim3(gx, a->nm), dim3(256), 0, a->stream, a->d_depth, (const uint64_t *)a->d_base,
+                           (const uint32_t *)a->d_nrows, (const uint32_t *)NULL, (const uint32_t *)NULL, (const uint64_t *)NULL, a->d_out,
+                           (unsigned long long *)NULL, a->spec_d, d_spec, d_spec + nspec);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipMemcpyAsync(h.data(), a->d_out, (size_t)a->nm * 16u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipMemcpyAsync(hs.data(), a->d_spec, nall * 8u, hipMemcpyDeviceToHost, a->stream));
+    if (regions && a->total_bins) CA_HIP(hipMemcpyAsync(hr.data(), a->d_reg_out, (size_t)a->total_bins * 16u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_sweep);
+    for (uint32_t m = 0; m < a->nm; m++) { out_unique[m] = h[2u * m]; out_total[m] = h[2u * m + 1u]; deep_total[m] = hs[nspec + m]; }
+    for (size_t i = 0; i < nspec; i++) spec[i] = hs[i];
+    for (uint64_t r = 0; regions && r < a->total_bins; r++) { reg_unique[r] = hr[2u * r]; reg_total[r] = hr[2u * r + 1u]; }
     return SK_OK;
 }

@@ -155,3 +155,127 @@ out:
     (void)hipFree(d_keys); (void)hipFree(d_sample); (void)hipFree(d_seg); (void)hipFree(d_table); (void)hipFree(d_out);
     return rc;
 }
+
+// ---- the depth spectrum of a hit list (include/strainer_kmer.h has the rule; coverage_depth --spectrum) ----
+// cov_count with a u32 count beside every slot of the set: the lane that finds or claims its key's slot adds 1 to that slot's count.
+// The two numbers and the spectrum then come from one sweep of the counts.
+__global__ void cov_count_depth(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ sample, uint64_t n, uint32_t nsamples,
+                                const uint64_t *__restrict__ seg_base, const uint64_t *__restrict__ seg_mask,
+                                unsigned long long *__restrict__ table, uint32_t *__restrict__ cnt)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = sample[i];
+    if (s >= nsamples) return;                                // (never: the host has checked)
+    const uint64_t k = keys[i], base = seg_base[s], mask = seg_mask[s];
+    uint64_t slot = cov_mix(k) & mask;
+    for (;;) {
+        const unsigned long long old = atomicCAS(&table[base + slot], COV_EMPTY, (unsigned long long)k);
+        if (old == COV_EMPTY || old == k) break;
+        slot = (slot + 1) & mask;
+    }
+    atomicAdd(&cnt[base + slot], 1u);
+}
+
+// blockIdx.y = sample (and on by gridDim.y): the sample's segment of counts into LDS bins min(v, D + 1) - 1 -- plain LDS atomics, as
+// in sk_covacc.hip's sweep and for its reason: at most half of a segment's slots are taken -- each workgroup adds its non-empty bins
+// and its sums to HBM once.  out: [nsamples] pairs {unique, total}; spec: [nsamples x (D + 1)]; deep: [nsamples].
+__global__ void __launch_bounds__(256) cov_spectrum(const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ seg_base,
+                                                    const uint64_t *__restrict__ seg_mask, uint32_t nsamples, uint32_t max_depth,
+                                                    unsigned long long *__restrict__ out, unsigned long long *__restrict__ spec,
+                                                    unsigned long long *__restrict__ deep)
+{
+    __shared__ uint32_t h_n[SK_COVACC_SPECTRUM_MAX + 1u];
+    __shared__ unsigned long long h_sum[3];                   // unique, total, deep
+    const uint32_t D = max_depth < SK_COVACC_SPECTRUM_MAX ? max_depth : SK_COVACC_SPECTRUM_MAX, ns = D + 1u;
+    for (uint32_t s = blockIdx.y; s < nsamples; s += gridDim.y) {
+        const uint64_t nslot = seg_mask[s] + 1u;
+        if ((uint64_t)blockIdx.x * 256u >= nslot) continue;   // (the whole workgroup)
+        const uint32_t *c = cnt + seg_base[s];
+        for (uint32_t b = threadIdx.x; b < ns; b += 256u) h_n[b] = 0u;
+        if (threadIdx.x < 3u) h_sum[threadIdx.x] = 0ull;
+        __syncthreads();
+        unsigned long long t = 0, dp = 0;
+        uint32_t u = 0;
+        for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nslot; i += (uint64_t)gridDim.x * 256u) {
+            const uint32_t v = c[i];
+            if (!v) continue;
+            u++; t += v;
+            atomicAdd(&h_n[(v < ns ? v : ns) - 1u], 1u);
+            if (v > D) dp += v;
+        }
+        if (u) { atomicAdd(&h_sum[0], (unsigned long long)u); atomicAdd(&h_sum[1], t); if (dp) atomicAdd(&h_sum[2], dp); }
+        __syncthreads();
+        if (threadIdx.x == 0u && h_sum[0]) {
+            atomicAdd(out + 2ull * s, h_sum[0]);
+            atomicAdd(out + 2ull * s + 1ull, h_sum[1]);
+            if (h_sum[2]) atomicAdd(deep + s, h_sum[2]);
+        }
+        for (uint32_t b = threadIdx.x; b < ns; b += 256u)
+            if (h_n[b]) atomicAdd(spec + (size_t)s * ns + b, (unsigned long long)h_n[b]);
+        __syncthreads();
+    }
+}
+
+// sk_distinct_count, and per sample how many of its keys came 1, 2, ..., max_depth and more than max_depth times.  Synchronous.
+extern "C" int sk_distinct_spectrum(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, uint64_t n, uint32_t nsamples, uint32_t max_depth,
+                                    uint64_t *out_unique, uint64_t *out_total, uint64_t *spec, uint64_t *deep_total)
+{
+    if (!ctx || !out_unique || !out_total || !spec || !deep_total || (n && (!keys || !sample))) return SK_E_ARG;
+    if (max_depth < 1u || max_depth > SK_COVACC_SPECTRUM_MAX) return SK_E_ARG;
+    if (nsamples == 0) return n ? SK_E_ARG : SK_OK;
+    const size_t nspec = (size_t)nsamples * (max_depth + 1u);
+    memset(out_unique, 0, (size_t)nsamples * 8);
+    memset(out_total, 0, (size_t)nsamples * 8);
+    memset(deep_total, 0, (size_t)nsamples * 8);
+    memset(spec, 0, nspec * 8);
+    if (!n) return SK_OK;
+    std::vector<uint64_t> cnt(nsamples, 0), base(nsamples), mask(nsamples);
+    for (uint64_t i = 0; i < n; i++) {
+        if (sample[i] >= nsamples) return sk_fail_(ctx, SK_E_ARG, "sample %u out of range", sample[i]);
+        if (keys[i] == COV_EMPTY) return sk_fail_(ctx, SK_E_ARG, "reserved key value");
+        cnt[sample[i]]++;
+    }
+    uint64_t slots = 0, max_seg = 0;
+    for (uint32_t s = 0; s < nsamples; s++) {
+        uint64_t c = 2;
+        while (c < 2 * cnt[s]) c <<= 1;
+        base[s] = slots; mask[s] = c - 1; slots += c;
+        if (c > max_seg) max_seg = c;
+    }
+    int rc = SK_OK;
+    void *d_keys = NULL, *d_sample = NULL, *d_seg = NULL, *d_table = NULL, *d_cnt = NULL, *d_out = NULL;
+    std::vector<unsigned long long> h((size_t)nsamples * 3u + nspec);
+#define COV_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = sk_fail_(ctx, SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); goto out; } } while (0)
+    COV_HIP(hipSetDevice(sk_ctx_device_(ctx)));
+    COV_HIP(hipMalloc(&d_keys, n * 8));
+    COV_HIP(hipMalloc(&d_sample, n * 4));
+    COV_HIP(hipMalloc(&d_seg, (size_t)nsamples * 16));
+    COV_HIP(hipMalloc(&d_table, slots * 8));
+    COV_HIP(hipMalloc(&d_cnt, slots * 4));
+    COV_HIP(hipMalloc(&d_out, h.size() * 8));                 // [nsamples] pairs, [nsamples] deep sums, the bins
+    COV_HIP(hipMemcpy(d_keys, keys, n * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_sample, sample, n * 4, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_seg, base.data(), (size_t)nsamples * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy((uint64_t *)d_seg + nsamples, mask.data(), (size_t)nsamples * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemset(d_table, 0xFF, slots * 8));
+    COV_HIP(hipMemset(d_cnt, 0, slots * 4));
+    COV_HIP(hipMemset(d_out, 0, h.size() * 8));
+    hipLaunchKernelGGL(cov_count_depth, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const uint64_t *)d_keys, (const uint32_t *)d_sample, n,
+                       nsamples, (const uint64_t *)d_seg, (const uint64_t *)d_seg + nsamples, (unsigned long long *)d_table, (uint32_t *)d_cnt);
+    COV_HIP(hipGetLastError());
+    {
+        const uint64_t g = (max_seg + 255u) / 256u;
+        hipLaunchKernelGGL(cov_spectrum, dim3((unsigned)(g > 256u ? 256u : g), nsamples > 4096u ? 4096u : nsamples), dim3(256), 0, 0,
+                           (const uint32_t *)d_cnt, (const uint64_t *)d_seg, (const uint64_t *)d_seg + nsamples, nsamples, max_depth,
+                           (unsigned long long *)d_out, (unsigned long long *)d_out + 3ull * nsamples, (unsigned long long *)d_out + 2ull * nsamples);
+    }
+    COV_HIP(hipGetLastError());
+    COV_HIP(hipMemcpy(h.data(), d_out, h.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < nsamples; s++) { out_unique[s] = h[2u * s]; out_total[s] = h[2u * s + 1u]; deep_total[s] = h[2ull * nsamples + s]; }
+    for (size_t i = 0; i < nspec; i++) spec[i] = h[3ull * nsamples + i];
+#undef COV_HIP
+out:
+    (void)hipFree(d_keys); (void)hipFree(d_sample); (void)hipFree(d_seg); (void)hipFree(d_table); (void)hipFree(d_cnt); (void)hipFree(d_out);
+    return rc;
+}

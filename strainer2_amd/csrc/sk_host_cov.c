@@ -106,6 +106,7 @@ typedef struct {
     size_t    klen;                                    /* k-mer field length seen so far (0 = none yet) */
     uint64_t *given_u, *given_t; uint32_t ngiven; int given;   /* counts handed in per sample (skc_add_counts) instead of hits */
     uint64_t **reg_u, **reg_t; uint32_t nreg_s, reg_bins;      /* ... and per sample and region (skc_add_region_counts): reg_bins each, or NULL */
+    uint64_t **sp_n, *sp_deep; uint32_t nsp_s, sp_bins;        /* the depth spectrum per sample: n[1..D], n[>D] (sp_bins = D + 1 each, or NULL) and hits[>D] */
 } hitlist;
 
 enum { COV_OK = 0, COV_OPEN, COV_FIELDS, COV_INT, COV_NOMEM };
@@ -315,6 +316,21 @@ static int cov_opt(int argc, char **argv, int *i, const char *shortn, const char
     return 0;
 }
 
+/* metagenomes that only have trailer lines come after those with passing hits (:121-124); -1: out of memory */
+static int cov_order_trailers(hitlist *h)
+{
+    uint32_t k, s;
+    for (k = 0; k < h->neval; k++)
+        if (!h->smp.in_depth[s = h->eval_order[k]]) {
+            uint32_t *o = realloc(h->depth_order, ((size_t)h->ndepth + 1) * sizeof *o);
+            if (!o) return -1;
+            h->depth_order = o;
+            o[h->ndepth++] = s;
+            h->smp.in_depth[s] = 1;
+        }
+    return 0;
+}
+
 /* everything after the hit list is read: trailer-only samples, the counts (device), the table (:121-124,200-271).
  * `kfile` only names the strain.  Returns the exit status. */
 static int cov_report(hitlist *h, sk_ctx *ctx, const char *kfile, const char *bfile, FILE *out, FILE *err)
@@ -326,15 +342,7 @@ static int cov_report(hitlist *h, sk_ctx *ctx, const char *kfile, const char *bf
     uint32_t s, k;
     int rc, status = 1;
     memset(&bg, 0, sizeof bg);
-    /* metagenomes that only have trailer lines come after those with passing hits (:121-124) */
-    for (k = 0; k < h->neval; k++)
-        if (!h->smp.in_depth[s = h->eval_order[k]]) {
-            uint32_t *o = realloc(h->depth_order, ((size_t)h->ndepth + 1) * sizeof *o);
-            if (!o) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
-            h->depth_order = o;
-            o[h->ndepth++] = s;
-            h->smp.in_depth[s] = 1;
-        }
+    if (cov_order_trailers(h)) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
     if (h->smp.n) {
         if (!(uniq = calloc(h->smp.n, sizeof *uniq)) || !(total = calloc(h->smp.n, sizeof *total))) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
         if (h->given) {                              /* counted already (strain_detect --coverage-only: on the device, target by target) */
@@ -412,6 +420,8 @@ static void hitlist_free(hitlist *h)
     uint32_t s;
     for (s = 0; s < h->nreg_s; s++) { free(h->reg_u[s]); free(h->reg_t[s]); }
     free(h->reg_u); free(h->reg_t);
+    for (s = 0; s < h->nsp_s; s++) free(h->sp_n[s]);
+    free(h->sp_n); free(h->sp_deep);
     free(h->given_u); free(h->given_t);
     free(h->key); free(h->sample); free(h->depth_order); free(h->eval_order); free(h->gid); free(h->gsample);
     names_free(&h->smp); names_free(&h->text);
@@ -529,14 +539,7 @@ int skc_report_regions(skc_acc *a, const char *hits_file_name, const skh_regions
     char *strain;
     size_t sl;
     uint32_t k, s, r;
-    for (k = 0; k < h->neval; k++)                       /* (what cov_report did already, when it ran) */
-        if (!h->smp.in_depth[s = h->eval_order[k]]) {
-            uint32_t *o = realloc(h->depth_order, ((size_t)h->ndepth + 1) * sizeof *o);
-            if (!o) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
-            h->depth_order = o;
-            o[h->ndepth++] = s;
-            h->smp.in_depth[s] = 1;
-        }
+    if (cov_order_trailers(h)) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }      /* (what cov_report did already, when it ran) */
     if (!h->given && h->n) {
         uint64_t *v = malloc((size_t)h->n * sizeof *v), i, j;
         if (!v) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
@@ -578,19 +581,142 @@ int skc_report_regions(skc_acc *a, const char *hits_file_name, const skh_regions
     return 0;
 }
 
+/* ---- the depth spectrum (strain_detect --coverage-spectrum, coverage_depth --spectrum; include/strainer_kmer.h has the rule) ---- */
+static int sp_room(hitlist *h, uint32_t g, uint32_t nbins)
+{
+    if (h->sp_bins && h->sp_bins != nbins) return -1;
+    h->sp_bins = nbins;
+    if (g >= h->nsp_s) {
+        const uint32_t n2 = g + 16u;
+        uint64_t **n = realloc(h->sp_n, (size_t)n2 * sizeof *n), *d;
+        if (!n) return -1;
+        h->sp_n = n;
+        if (!(d = realloc(h->sp_deep, (size_t)n2 * sizeof *d))) return -1;
+        h->sp_deep = d;
+        memset(n + h->nsp_s, 0, (size_t)(n2 - h->nsp_s) * sizeof *n);
+        memset(d + h->nsp_s, 0, (size_t)(n2 - h->nsp_s) * sizeof *d);
+        h->nsp_s = n2;
+    }
+    if (!h->sp_n[g] && !(h->sp_n[g] = calloc(nbins, sizeof **h->sp_n))) return -1;
+    return 0;
+}
+
+/* a metagenome's bins, counted elsewhere (nbins = D + 1: n[1..D], n[>D]; deep_total = hits[>D]): called next to skc_add_counts,
+ * after it, so that the sample exists */
+int skc_add_spectrum_counts(skc_acc *a, const char *metagenome, const uint64_t *spec, uint64_t deep_total, uint32_t nbins)
+{
+    hitlist *h = &a->h;
+    const char *sn = base_of(metagenome, metagenome + strlen(metagenome));
+    const int64_t g = name_get(&h->smp, sn, strlen(sn));
+    uint32_t d;
+    if (g < 0 || !nbins || sp_room(h, (uint32_t)g, nbins)) return -1;
+    for (d = 0; d < nbins; d++) h->sp_n[g][d] += spec[d];
+    h->sp_deep[g] += deep_total;
+    return 0;
+}
+
+/* the table of what sp_n / sp_deep hold, samples in the main table's order; I comes from the sample's trailer */
+static void spectrum_print(const hitlist *h, const char *hits_file_name, uint32_t max_depth, FILE *out)
+{
+    char *strain = strdup(base_of(hits_file_name, hits_file_name + strlen(hits_file_name)));
+    const size_t sl = strain ? strlen(strain) : 0;
+    uint32_t k, d;
+    if (sl >= 13 && !memcmp(strain + sl - 12, "kmer_hits", 9) && !memcmp(strain + sl - 2, "gz", 2)) strain[sl - 13] = 0;
+    fputs("strain_name\tmetagenome\tdepth\tinformative_kmers\tobserved_hits\n", out);
+    for (k = 0; k < h->ndepth; k++) {
+        const uint32_t s = h->depth_order[k];
+        const uint64_t *n = s < h->nsp_s ? h->sp_n[s] : NULL;
+        uint64_t seen = 0;
+        for (d = 0; n && d <= max_depth; d++) seen += n[d];
+        if (h->smp.have_inf[s])
+            fprintf(out, "%s\t%s\t0\t%lld\t0\n", strain ? strain : "", h->smp.name[s], (long long)(h->smp.g_inf[s] - (int64_t)seen));
+        for (d = 1; n && d <= max_depth; d++)
+            if (n[d - 1])
+                fprintf(out, "%s\t%s\t%u\t%llu\t%llu\n", strain ? strain : "", h->smp.name[s], d, (unsigned long long)n[d - 1],
+                        (unsigned long long)(n[d - 1] * d));
+        if (n && n[max_depth])
+            fprintf(out, "%s\t%s\t>%u\t%llu\t%llu\n", strain ? strain : "", h->smp.name[s], max_depth, (unsigned long long)n[max_depth],
+                    (unsigned long long)h->sp_deep[s]);
+    }
+    free(strain);
+    fflush(out);
+}
+
+/* The table: call it after skc_report.  An accumulator that was fed hits folds its (sample, row) list here by sort and run lengths;
+ * one that was fed counts prints what skc_add_spectrum_counts left. */
+int skc_report_spectrum(skc_acc *a, const char *hits_file_name, uint32_t max_depth, FILE *out, FILE *err)
+{
+    hitlist *h = &a->h;
+    if (max_depth < 1u || max_depth > SK_COVACC_SPECTRUM_MAX || (h->sp_bins && h->sp_bins != max_depth + 1u)) return 1;
+    if (cov_order_trailers(h)) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+    if (!h->given && h->n) {
+        uint64_t *v = malloc((size_t)h->n * sizeof *v), i, j;
+        if (!v) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+        for (i = 0; i < h->n; i++) v[i] = ((uint64_t)h->sample[i] << 32) | (h->key[i] & 0xFFFFFFFFu);
+        qsort(v, (size_t)h->n, sizeof *v, cmp_u64);
+        for (i = 0; i < h->n; i = j) {
+            const uint32_t g = (uint32_t)(v[i] >> 32);
+            for (j = i + 1; j < h->n && v[j] == v[i]; j++) ;
+            if (sp_room(h, g, max_depth + 1u)) { free(v); fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+            if (j - i <= max_depth) h->sp_n[g][j - i - 1]++;
+            else { h->sp_n[g][max_depth]++; h->sp_deep[g] += j - i; }
+        }
+        free(v);
+    }
+    spectrum_print(h, hits_file_name, max_depth, out);
+    return 0;
+}
+
+/* (the host-only test builds link this file without sk_cover.hip's newer entry point: without it --spectrum is refused) */
+#pragma weak sk_distinct_spectrum
+/* coverage_depth --spectrum: the multiplicities of the (sample, packed k-mer) pairs, counted on the device, to the table at `path` */
+static int cov_spectrum_file(hitlist *h, sk_ctx *ctx, const char *kfile, uint32_t max_depth, const char *path, FILE *err)
+{
+    const uint32_t ns = h->smp.n, nb = max_depth + 1u;
+    uint64_t *buf = NULL;
+    FILE *f;
+    uint32_t s, d;
+    int rc, status = 1;
+    if (ns) {
+        if (!(buf = calloc((size_t)ns * (nb + 3u), sizeof *buf))) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+        rc = sk_distinct_spectrum(ctx, h->key, h->sample, h->n, ns, max_depth, buf, buf + ns, buf + 3u * (size_t)ns, buf + 2u * (size_t)ns);
+        if (rc != SK_OK) { fprintf(err, "coverage_depth: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx)); goto done; }
+        for (s = 0; s < ns; s++) {
+            const uint64_t *n = buf + 3u * (size_t)ns + (size_t)s * nb;
+            if (!buf[s]) continue;                   /* (a sample without a passing line keeps no bins) */
+            if (sp_room(h, s, nb)) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+            for (d = 0; d < nb; d++) h->sp_n[s][d] = n[d];
+            h->sp_deep[s] = buf[2u * (size_t)ns + s];
+        }
+    }
+    if (!(f = fopen(path, "w"))) { fprintf(err, "coverage_depth: could not write %s\n", path); goto done; }
+    spectrum_print(h, kfile, max_depth, f);
+    status = ferror(f) ? 1 : 0;
+    if (fclose(f)) status = 1;
+done:
+    free(buf);
+    return status;
+}
+
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
 {
-    const char *kfile = NULL, *mtext = NULL, *bfile = NULL, *env;
-    int64_t min_hits = 1;
-    int i, bad = 0, rc, status = 1, device = 0;
+    const char *kfile = NULL, *mtext = NULL, *bfile = NULL, *env, *sp_file = NULL, *sp_max = NULL;
+    int64_t min_hits = 1, sp_d = 255;
+    int i, bad = 0, rc, status = 1, device = 0, want_sp = 0;
+    char *sp_path = NULL;
     hitlist h;
     sk_ctx *ctx = NULL;
 
     for (i = 1; i < argc; i++) {                     /* :27-41 */
         if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
-            fprintf(out, "usage: coverage_depth [-h] --kmer_hits_file FILE [--min_kmer_hits N] [--background_metagenomes_file FILE]\n");
+            fprintf(out, "usage: coverage_depth [-h] --kmer_hits_file FILE [--min_kmer_hits N] [--background_metagenomes_file FILE]\n"
+                         "                      [--spectrum[=FILE] [--spectrum-max D]]\n");
             return 0;
         }
+        /* "--spectrum[=FILE] [--spectrum-max D]" (extension): the depth spectrum beside the table, see include/strainer_kmer.h */
+        if (!strncmp(argv[i], "--spectrum", 10) && (argv[i][10] == 0 || argv[i][10] == '=')) { want_sp = 1; sp_file = argv[i][10] ? argv[i] + 11 : NULL; continue; }
+        if (!strcmp(argv[i], "--spectrum-max") && i + 1 < argc) { sp_max = argv[++i]; continue; }
+        if (!strncmp(argv[i], "--spectrum-max=", 15)) { sp_max = argv[i] + 15; continue; }
         if (cov_opt(argc, argv, &i, "-k", "--kmer_hits_file", &kfile, err, &bad)) { if (bad) return 2; continue; }
         if (cov_opt(argc, argv, &i, "-m", "--min_kmer_hits", &mtext, err, &bad)) { if (bad) return 2; continue; }
         if (cov_opt(argc, argv, &i, "-b", "--background_metagenomes_file", &bfile, err, &bad)) { if (bad) return 2; continue; }
@@ -602,18 +728,40 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         fprintf(err, "coverage_depth: error: argument --min_kmer_hits/-m: invalid int value: '%s'\n", mtext);
         return 2;
     }
+    if (sp_max && !want_sp) { fprintf(err, "coverage_depth: error: --spectrum-max goes with --spectrum\n"); return 2; }
+    if (sp_max && (!skp_int(sp_max, sp_max + strlen(sp_max), &sp_d) || sp_d < 1 || sp_d > (int64_t)SK_COVACC_SPECTRUM_MAX)) {
+        fprintf(err, "coverage_depth: error: --spectrum-max %s: a depth from 1 to %u\n", sp_max, SK_COVACC_SPECTRUM_MAX);
+        return 2;
+    }
+    if (want_sp && !sk_distinct_spectrum) { fprintf(err, "coverage_depth: error: --spectrum: this build has no device spectrum\n"); return 2; }
     memset(&h, 0, sizeof h);
     rc = read_hits(&h, kfile, min_hits);
     if (rc == COV_OPEN) { fprintf(err, "coverage_depth: could not read %s\n", kfile); goto done; }
     if (rc == COV_FIELDS) { fprintf(err, "coverage_depth: %s: a line has too few tab-separated fields\n", kfile); goto done; }
     if (rc == COV_INT) { fprintf(err, "coverage_depth: %s: a count field is not an integer\n", kfile); goto done; }
     if (rc == COV_NOMEM) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+    if (want_sp && h.general) {                      /* (before anything is printed) */
+        fprintf(err, "coverage_depth: --spectrum: %s has k-mer fields that are not A/C/G/T words of one length: the depth of a k-mer is not defined there\n", kfile);
+        goto done;
+    }
+    if (want_sp) {
+        if (sp_file && *sp_file) sp_path = strdup(sp_file);
+        else if ((sp_path = malloc(strlen(kfile) + 32)) != NULL) {
+            const size_t n = strlen(kfile);
+            strcpy(sp_path, kfile);
+            if (n >= 13 && !strcmp(sp_path + n - 13, ".kmer_hits.gz")) sp_path[n - 13] = 0;
+            strcat(sp_path, ".coverage_spectrum");
+        }
+        if (!sp_path) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+    }
     if ((env = getenv("SK_DEVICE")) != NULL) device = atoi(env);
     rc = sk_ctx_create(&ctx, device);
     if (rc != SK_OK) { fprintf(err, "coverage_depth: cannot use HIP device %d: %s\n", device, sk_strerror(rc)); goto done; }
     status = cov_report(&h, ctx, kfile, bfile, out, err);
+    if (status == 0 && want_sp) status = cov_spectrum_file(&h, ctx, kfile, (uint32_t)sp_d, sp_path, err);
 done:
     fflush(out);
+    free(sp_path);
     sk_ctx_destroy(ctx);
     hitlist_free(&h);
     return status;

@@ -295,7 +295,7 @@ static char *sm_cov_path(const char *hits)
 static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
 {
     char **v = (char **)malloc(((size_t)argc + 1) * sizeof *v);
-    int c, n = 0, bad = 0, saved = opterr, want_rg = 0;
+    int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0;
     if (!v) return 1;
     for (c = 0; c < argc; c++) {
         if (c > 0 && !strncmp(argv[c], "--coverage-depth", 16) && (argv[c][16] == 0 || argv[c][16] == '=')) {
@@ -327,6 +327,17 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
         }
         if (c > 0 && !strcmp(argv[c], "--region-window") && c + 1 < argc) { c++; continue; }
         if (c > 0 && !strncmp(argv[c], "--region-window=", 16)) continue;
+        if (c > 0 && !strncmp(argv[c], "--coverage-spectrum", 19) && (argv[c][19] == 0 || argv[c][19] == '=')) {
+            if (argv[c][19] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-spectrum takes no file name (each strain's table goes next to its coverage table)\n");
+                free(v);
+                return 1;
+            }
+            want_sp = 1;
+            continue;
+        }
+        if (c > 0 && !strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { c++; continue; }
+        if (c > 0 && !strncmp(argv[c], "--spectrum-max=", 15)) continue;
         if (c > 0 && !strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { c++; continue; }
         v[n++] = argv[c];
     }
@@ -338,6 +349,11 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
     }
     if (want_rg && !*want_cov) {
         fprintf(err, "kmer_scrub_count: --coverage-regions goes with --coverage-depth or --coverage-only: it folds their table's numbers by region\n");
+        free(v);
+        return 1;
+    }
+    if (want_sp && !*want_cov) {
+        fprintf(err, "kmer_scrub_count: --coverage-spectrum goes with --coverage-depth or --coverage-only: it bins their table's hits by depth\n");
         free(v);
         return 1;
     }

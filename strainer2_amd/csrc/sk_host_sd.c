@@ -93,6 +93,7 @@ typedef struct {
     uint32_t   *co_rows; uint64_t co_n, co_cap;   /* --coverage-only: rows of host-replayed passing hits on their way to the device's counters */
     /* --coverage-regions: the strain's region table, every row's region (rg.n = unplaced), informative rows per region, the table's path */
     skh_regions rg; uint32_t *row_region; uint64_t *reg_inf; char *rg_path;
+    char *sp_path;                             /* --coverage-spectrum: the table's path */
 } sd_prog;
 
 /* ---------------------------------------------------------------------------------------------
@@ -1618,6 +1619,12 @@ static void sd_prefetch(sd_stream *st)
 #pragma weak sk_covacc_region_rows
 #pragma weak sk_covacc_finish_target_regions
 #pragma weak sk_covacc_timing_
+/* --coverage-spectrum (include/strainer_kmer.h has the rule): with --coverage-only the sweep that ends a target also bins the
+ * counters by depth (sk_covacc_finish_target_spectrum, with the region pairs when --coverage-regions is on too); with
+ * --coverage-depth, and where --coverage-only counts on the host, skc_report_spectrum folds the host accumulator's list. */
+#pragma weak sk_covacc_set_spectrum
+#pragma weak sk_covacc_finish_target_spectrum
+static struct { int on; uint32_t max; } sd_spec;
 static double sd_co_ms_fold, sd_co_ms_sweep;          /* SK_SD_TIMING: the accumulators' device time, folds and target sweeps */
 static struct {
     int on; uint64_t window;
@@ -1668,7 +1675,8 @@ static int co_open(sd_prog *p, uint32_t ns)
     uint32_t k, m;
     if (!sd_co.on || sd_co.host) return SK_OK;
     if (!sk_covacc_create || !sk_covacc_pick || !sk_tally_collect_counts || !sk_union_tally_launch_ex ||
-        (sd_rg.on && (!sk_covacc_set_regions || !sk_covacc_region_rows || !sk_covacc_finish_target_regions))) {
+        (sd_rg.on && (!sk_covacc_set_regions || !sk_covacc_region_rows || !sk_covacc_finish_target_regions)) ||
+        (sd_spec.on && (!sk_covacc_set_spectrum || !sk_covacc_finish_target_spectrum))) {
         fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
         sd_co.host = 1;
         return SK_OK;
@@ -1684,6 +1692,7 @@ static int co_open(sd_prog *p, uint32_t ns)
         sd_co.nacc = k + 1;
         if (rc != SK_OK) { sd_co.nacc = k; co_close(); return rc; }
         if (getenv("SK_SD_TIMING") && sk_covacc_timing_) (void)sk_covacc_timing_(sd_co.acc[k], 1, NULL, NULL);
+        if (sd_spec.on && (rc = sk_covacc_set_spectrum(sd_co.acc[k], sd_spec.max)) != SK_OK) { co_close(); return rc; }
         for (m = 0; m < n && sd_rg.on; m++) {             /* every member's rows to their regions, and the regions' denominators */
             sd_prog *q = &p[a + m];
             uint32_t *starts = (uint32_t *)malloc(((size_t)q->rg.n + 1) * sizeof *starts), r;
@@ -2421,25 +2430,33 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
         for (k = 0; k < sd_co.nacc && got >= 0; k++) {
             uint64_t uq[SK_UNION_MAX], tot[SK_UNION_MAX];
             const uint32_t a = co_unit_first(k), n = co_unit_members(k);
-            uint64_t *ru = NULL, *rt = NULL, bins = 0, at = 0;
+            uint64_t *ru = NULL, *rt = NULL, bins = 0, at = 0, *sp = NULL, *deep = NULL;
+            const uint32_t nsp = sd_spec.max + 1u;
             if (sd_rg.on) {                                  /* the same sweep, folded by region as well */
                 for (m = 0; m < n; m++) bins += (uint64_t)p[a + m].rg.n + 1u;
                 ru = (uint64_t *)malloc((size_t)bins * 2 * sizeof *ru);
                 if (!ru) { got = SK_E_NOMEM; break; }
                 rt = ru + bins;
             }
+            if (sd_spec.on) {                                  /* ... and binned by depth */
+                sp = (uint64_t *)malloc(((size_t)n * nsp + n) * sizeof *sp);
+                if (!sp) { free(ru); got = SK_E_NOMEM; break; }
+                deep = sp + (size_t)n * nsp;
+            }
             pthread_mutex_lock(&sd_dev_mu);
-            rc = sd_rg.on ? sk_covacc_finish_target_regions(sd_co.acc[k], uq, tot, ru, rt) : sk_covacc_finish_target(sd_co.acc[k], uq, tot);
+            rc = sd_spec.on ? sk_covacc_finish_target_spectrum(sd_co.acc[k], uq, tot, sp, deep, ru, rt) :
+                 sd_rg.on ? sk_covacc_finish_target_regions(sd_co.acc[k], uq, tot, ru, rt) : sk_covacc_finish_target(sd_co.acc[k], uq, tot);
             pthread_mutex_unlock(&sd_dev_mu);
-            if (rc != SK_OK) { free(ru); got = rc; break; }
+            if (rc != SK_OK) { free(ru); free(sp); got = rc; break; }
             for (m = 0; m < n; m++) {
                 if (skc_add_counts(p[a + m].cov, f1, uq[m], tot[m])) got = SK_E_NOMEM;
                 if (sd_rg.on) {
                     if (skc_add_region_counts(p[a + m].cov, f1, ru + at, rt + at, p[a + m].rg.n + 1u)) got = SK_E_NOMEM;
                     at += (uint64_t)p[a + m].rg.n + 1u;
                 }
+                if (sd_spec.on && skc_add_spectrum_counts(p[a + m].cov, f1, sp + (size_t)m * nsp, deep[m], nsp)) got = SK_E_NOMEM;
             }
-            free(ru);
+            free(ru); free(sp);
         }
         if (got < 0) { fprintf(err, "strain_detect: device error on %s: %s (%s)\n", f1, sk_strerror(got), sk_last_error(p[0].ctx)); goto done; }
     }
@@ -2777,11 +2794,34 @@ static int sd_coverage_write(sd_prog *p)
     if (!(f = fopen(p->cov_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->cov_path); return 1; }
     rc = skc_report(p->cov, p->ctx, p->o_path, f, p->err);
     fclose(f);
-    if (rc || !sd_rg.on) return rc;
-    if (!(f = fopen(p->rg_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->rg_path); return 1; }
-    rc = skc_report_regions(p->cov, p->o_path, &p->rg, p->row_region, (uint32_t)p->ks.nrows, p->reg_inf, f, p->err);
-    fclose(f);
+    if (!rc && sd_rg.on) {
+        if (!(f = fopen(p->rg_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->rg_path); return 1; }
+        rc = skc_report_regions(p->cov, p->o_path, &p->rg, p->row_region, (uint32_t)p->ks.nrows, p->reg_inf, f, p->err);
+        fclose(f);
+    }
+    if (!rc && sd_spec.on) {
+        if (!(f = fopen(p->sp_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->sp_path); return 1; }
+        rc = skc_report_spectrum(p->cov, p->o_path, sd_spec.max, f, p->err);
+        fclose(f);
+    }
     return rc;
+}
+
+/* --coverage-spectrum: where the table of strain p goes */
+static int sd_spectrum_open(sd_prog *p, const char *explicit_path)
+{
+    if (explicit_path && *explicit_path) p->sp_path = strdup(explicit_path);
+    else {
+        const size_t n = strlen(p->o_path);
+        p->sp_path = (char *)malloc(n + 32);
+        if (p->sp_path) {
+            strcpy(p->sp_path, p->o_path);
+            if (n >= 13 && !strcmp(p->sp_path + n - 13, ".kmer_hits.gz")) p->sp_path[n - 13] = 0;
+            strcat(p->sp_path, ".coverage_spectrum");
+        }
+    }
+    if (!p->sp_path) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
+    return 0;
 }
 
 /* --coverage-regions: the region table of a strain file, before anything of the run is opened; more than SKH_REGIONS_MAX regions
@@ -2874,7 +2914,7 @@ static void sd_strain_close(sd_prog *p)
     free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows);
     skc_destroy(p->cov);
     if (skh_regions_free) skh_regions_free(&p->rg);
-    free(p->row_region); free(p->reg_inf); free(p->rg_path);
+    free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path);
     memset(p, 0, sizeof *p);
 }
 
@@ -3082,7 +3122,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     const char *const *rg_genomes = sd_rg.genomes;       /* (adopted strains: theirs for this call only) */
     const uint32_t rg_ngenomes = sd_rg.ngenomes;
     skh_regions *rgs = NULL;
-    int want_rg = 0;
+    int want_rg = 0, want_sp = 0;
+    const char *sp_file = NULL, *sp_max = NULL;
     long long cov_min = 1;
     double t_begin = 0;
     sd_prog *p = NULL;
@@ -3123,6 +3164,15 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         }
         if (!strcmp(argv[c], "--region-window") && c + 1 < argc) { rg_window = argv[++c]; continue; }
         if (!strncmp(argv[c], "--region-window=", 16)) { rg_window = argv[c] + 16; continue; }
+        /* "--coverage-spectrum[=FILE] [--spectrum-max D]": next to either table, how many informative k-mers were seen 0, 1, ..., D and
+         * more than D times (default D 255, at most 1023), default FILE = outfile with ".kmer_hits.gz" replaced by ".coverage_spectrum" */
+        if (!strncmp(argv[c], "--coverage-spectrum", 19) && (argv[c][19] == 0 || argv[c][19] == '=')) {
+            want_sp = 1;
+            sp_file = argv[c][19] ? argv[c] + 20 : NULL;
+            continue;
+        }
+        if (!strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { sp_max = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--spectrum-max=", 15)) { sp_max = argv[c] + 15; continue; }
         if (!strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { cov_min = atoll(argv[++c]); continue; }
         if (!strcmp(argv[c], "--target-cache") && c + 1 < argc) { tc_dir = argv[++c]; continue; }       /* (extension: the target cache, see sd_tc) */
         if (!strncmp(argv[c], "--target-cache=", 15)) { tc_dir = argv[c] + 15; continue; }
@@ -3130,6 +3180,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     }
     argc = j;
     sd_rg.on = 0; sd_rg.genomes = NULL; sd_rg.ngenomes = 0;
+    sd_spec.on = 0;
     sd_co.on = 0;
     if (cov_only && want_cov) { fputs("strain_detect: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n", err); return sd_drop(p, ns); }
 
@@ -3179,6 +3230,19 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (ad && (!rg_genomes || rg_ngenomes != ad->n)) { fputs("strain_detect: --coverage-regions: the resident strains' genome files are not known\n", err); return sd_drop(p, ns); }
         sd_rg.window = (uint64_t)w;
     }
+    if (want_sp || sp_max) {
+        long long d = 255;
+        char *end = NULL;
+        if (!want_sp) { fputs("strain_detect: --spectrum-max goes with --coverage-spectrum\n", err); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-spectrum goes with --coverage-depth or --coverage-only: it bins their table's hits by depth\n", err); return sd_drop(p, ns); }
+        if (sp_file && ((S && !a && !o && !r) || (ad && ad->o))) { fputs("strain_detect: --coverage-spectrum=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        if (sp_max) {
+            errno = 0;
+            d = strtoll(sp_max, &end, 10);
+            if (end == sp_max || *end || errno || d < 1 || d > (long long)SK_COVACC_SPECTRUM_MAX) { fprintf(err, "strain_detect: --spectrum-max %s: a depth from 1 to %u\n", sp_max, SK_COVACC_SPECTRUM_MAX); return sd_drop(p, ns); }
+        }
+        sd_spec.max = (uint32_t)d;
+    }
     if (ad) { a = ad->a[0]; r = "(resident)"; S = NULL; }
     if (S && !a && !o && !r) {
         if (!b && !B) { usage(err); return sd_drop(p, ns); }
@@ -3209,6 +3273,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_co.on = cov_only; sd_co.min = cov_min;
     sd_co_ms_fold = sd_co_ms_sweep = 0;
     sd_rg.on = want_rg;
+    sd_spec.on = want_sp;
     sd_co.flush_rows = (env = getenv("SK_SD_CO_FLUSH_ROWS")) != NULL && atoll(env) >= 1 ? (uint64_t)atoll(env) : 1u << 20;
     sd_res_bytes = 0;
     sd_tc_open(tc_dir, err);
@@ -3301,6 +3366,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (sd_coverage_open(&p[s], S ? NULL : cov_file, cov_min)) goto done;
     for (s = 0; want_rg && s < ns; s++)
         if (sd_regions_open(&p[s], &rgs[s], S || (ad && ad->o) ? NULL : rg_file)) goto done;
+    for (s = 0; want_sp && s < ns; s++)
+        if (sd_spectrum_open(&p[s], S || (ad && ad->o) ? NULL : sp_file)) goto done;
     if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
     for (s = 0; s < ns; s++)
         if (sd_coverage_write(&p[s])) goto done;
@@ -3365,7 +3432,7 @@ done:
                 t_pw_parse, t_pw_seg, t_pw_turn, t_pw_push);
     if (getenv("SK_SD_TIMING") && cov_only)
         fprintf(err, "strain_detect timing: coverage accumulators on the device: folds %.3f ms, target sweeps %.3f ms%s\n", sd_co_ms_fold, sd_co_ms_sweep,
-                want_rg ? " (folded by region)" : "");
+                want_rg && want_sp ? " (folded by region, binned by depth)" : want_rg ? " (folded by region)" : want_sp ? " (binned by depth)" : "");
     if (getenv("SK_SD_RESULT_BYTES"))
         fprintf(err, "strain_detect: scan results copied from the device: %llu bytes; --coverage-only: %llu runs counted on the device, %llu replayed, "
                      "%llu targets on the host accumulator (the process's totals)\n", (unsigned long long)sd_res_bytes,
@@ -3374,6 +3441,7 @@ done:
     sd_pin_close();
     sd_co.on = 0;
     sd_rg.on = 0;
+    sd_spec.on = 0;
     for (s = 0; rgs && s < nrgs; s++) skh_regions_free(&rgs[s]);
     free(rgs);
     {   /* closing a strain = finishing its gz output, freeing its device context and tables: strain by strain on threads */

@@ -30,6 +30,11 @@ int skc_report(skc_acc *a, sk_ctx *ctx, const char *hits_file_name, FILE *out, F
 int skc_add_region_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t nbins);
 int skc_report_regions(skc_acc *a, const char *hits_file_name, const skh_regions *rg, const uint32_t *row_region, uint32_t nrows,
                        const uint64_t *reg_inf, FILE *out, FILE *err);
+/* ... and the depth spectrum (strain_detect --coverage-spectrum): a metagenome's bins handed in (nbins = max_depth + 1: n[1..D],
+ * n[>D]; deep_total = hits[>D]; next to skc_add_counts), or folded from the hits by skc_report_spectrum, which prints the table;
+ * call it after skc_report */
+int skc_add_spectrum_counts(skc_acc *a, const char *metagenome, const uint64_t *spec, uint64_t deep_total, uint32_t nbins);
+int skc_report_spectrum(skc_acc *a, const char *hits_file_name, uint32_t max_depth, FILE *out, FILE *err);
 /* kmer_scrub_count --detect: the genome files of the strains the next skh_strain_detect_resident[_many] call adopts (it has no -r;
  * --coverage-regions reads the records' names and lengths from them).  The call takes the list and forgets it. */
 void skh_resident_genomes_(const char *const *paths, uint32_t n);

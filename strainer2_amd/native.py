@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "sk_tally_collect_counts", "sk_tally_fetch_held", "sk_union_tally_launch_ex", "sk_union_tally_collect_counts", "sk_union_tally_fetch_held",
     "skh_regions_from_file", "skh_regions_free", "sk_table_first_pos", "sk_covacc_set_regions", "sk_covacc_region_rows",
     "sk_covacc_finish_target_regions",
+    "sk_covacc_set_spectrum", "sk_covacc_finish_target_spectrum", "sk_distinct_spectrum",
 ]
 
 
@@ -700,6 +701,20 @@ class KmerContext:
                                        uniq.ctypes.data, total.ctypes.data))
         return uniq, total
 
+    def distinct_spectrum(self, keys, sample, nsamples, max_depth):
+        """sk_distinct_spectrum: (unique[nsamples], total[nsamples], spec[nsamples, max_depth + 1], deep[nsamples]) -- distinct_count,
+        and per sample how many of its keys came 1, 2, ..., max_depth and (last column) more than max_depth times; deep = the sum of
+        the multiplicities above max_depth"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32)
+        assert len(keys) == len(sample)
+        nb = max(int(max_depth), 0) + 1
+        uniq, total, deep = (np.zeros(nsamples, dtype=np.uint64) for _ in range(3))
+        spec = np.zeros((nsamples, nb), dtype=np.uint64)
+        self._ck(lib.sk_distinct_spectrum(self._h, keys.ctypes.data, sample.ctypes.data, len(keys), nsamples, int(max_depth),
+                                          uniq.ctypes.data, total.ctypes.data, spec.ctypes.data, deep.ctypes.data))
+        return uniq, total, spec, deep
+
     def print_counts(self, ks: Keyset, path, with_drug_column=False):
         fp = _libc.fopen(os.fsencode(path), b"w")
         try:
@@ -761,6 +776,10 @@ lib.sk_table_build_from_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c
 lib.sk_covacc_set_regions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
 lib.sk_covacc_region_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.sk_covacc_finish_target_regions.argtypes = [C.c_void_p] * 5
+SK_COVACC_SPECTRUM_MAX = 1023
+lib.sk_covacc_set_spectrum.argtypes = [C.c_void_p, C.c_uint32]
+lib.sk_covacc_finish_target_spectrum.argtypes = [C.c_void_p] * 7
+lib.sk_distinct_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
 
 
 def regions_from_file(path, window=100000):
@@ -775,6 +794,11 @@ def regions_from_file(path, window=100000):
         return [(int(s.text_off[i]), int(s.record[i]), int(s.rec_off[i]), int(s.len[i]), s.name[i]) for i in range(s.n)], int(s.text_bases)
     finally:
         lib.skh_regions_free(C.byref(s))
+
+
+def distinct_spectrum(ctx, keys, sample, nsamples, max_depth=255):
+    """KmerContext.distinct_spectrum on ctx"""
+    return ctx.distinct_spectrum(keys, sample, nsamples, max_depth)
 
 
 class TallyBatch:
@@ -1104,6 +1128,31 @@ class CoverageAcc:
             per.append((ru[at: at + n + 1].copy(), rt[at: at + n + 1].copy()))
             at += n + 1
         return uq, tot, per
+
+    def set_spectrum(self, max_depth):
+        """sk_covacc_set_spectrum: 0 turns the depth spectrum off, 1..SK_COVACC_SPECTRUM_MAX on with that maximum depth"""
+        self._ctx._ck(lib.sk_covacc_set_spectrum(self._h, int(max_depth)))
+        self._spec_d = int(max_depth)
+
+    def finish_target_spectrum(self, regions=False):
+        """sk_covacc_finish_target_spectrum: (unique[nmembers], total[nmembers], spec[nmembers, D + 1], deep[nmembers][, per region as
+        finish_target_regions has it]) from one sweep: spec[m, d - 1] rows of member m with count d <= D, spec[m, D] those above D,
+        deep[m] the sum of the counts above D; the counters are zero afterwards"""
+        nm, nb = len(self.nrows), getattr(self, "_spec_d", 0) + 1
+        uq, tot, deep = (np.zeros(nm, dtype=np.uint64) for _ in range(3))
+        spec = np.zeros((nm, nb), dtype=np.uint64)
+        nreg = getattr(self, "_nreg", None) or [0] * nm
+        bins = sum(n + 1 for n in nreg)
+        ru, rt = np.zeros(bins, dtype=np.uint64), np.zeros(bins, dtype=np.uint64)
+        self._ctx._ck(lib.sk_covacc_finish_target_spectrum(self._h, uq.ctypes.data, tot.ctypes.data, spec.ctypes.data, deep.ctypes.data,
+                                                           ru.ctypes.data if regions else None, rt.ctypes.data if regions else None))
+        if not regions:
+            return uq, tot, spec, deep
+        per, at = [], 0
+        for n in nreg:
+            per.append((ru[at: at + n + 1].copy(), rt[at: at + n + 1].copy()))
+            at += n + 1
+        return uq, tot, spec, deep, per
 
     def close(self):
         if getattr(self, "_h", None):

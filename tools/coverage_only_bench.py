@@ -15,8 +15,13 @@ new flag is to be set against.
 --coverage-only, and each line also carries the accumulators' device time -- their folds and their target sweeps, summed over the
 run (SK_SD_TIMING; the parent build does not report it).
 
+--spectrum D measures --coverage-spectrum in the same way: --coverage-only without and with `--coverage-spectrum --spectrum-max D`
+alternate, the parent build's plain --coverage-only runs behind them, and the summary sets the new build's plain runs and the runs
+with the flag against the parent's medians and the parent's own run-to-run spread (max - min over its rounds).
+
     python tools/coverage_only_bench.py [--gbases 1.5] [--parent-exe PATH] [--out profiles/coverage_only_bench.txt]
     python tools/coverage_only_bench.py --regions 100000 --rounds 5 [--parent-exe PATH] [--out profiles/coverage_regions_bench.txt]
+    python tools/coverage_only_bench.py --spectrum 255 --rounds 5 --parent-exe PATH [--out profiles/coverage_spectrum_bench.txt]
 """
 import argparse
 import hashlib
@@ -55,7 +60,7 @@ def row(rs, key, spec):
 def step(exe, argv, env, limit, cwd, ns, hit_lists):
     """one run of the program under its own time limit -> measurements; raises StepFailed (nothing more is started then)"""
     for s in range(ns):
-        for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions"):
+        for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -73,9 +78,10 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             h.update(f.read())
     hr = hashlib.md5()
     for s in range(ns):
-        if os.path.exists(os.path.join(cwd, f"out{s}.gz.coverage_regions")):
-            with open(os.path.join(cwd, f"out{s}.gz.coverage_regions"), "rb") as f:
-                hr.update(f.read())
+        for ext in ("coverage_regions", "coverage_spectrum"):    # (the table beside the coverage table, whichever the run wrote)
+            if os.path.exists(os.path.join(cwd, f"out{s}.gz.{ext}")):
+                with open(os.path.join(cwd, f"out{s}.gz.{ext}"), "rb") as f:
+                    hr.update(f.read())
     m = PASS.search(p.stderr)
     b = BYTES.search(p.stderr)
     a = ACC.search(p.stderr)
@@ -116,6 +122,48 @@ def regions_case(say, args, env, tmp, ns, kind, argv):
         say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
+def spectrum_case(say, args, env, tmp, ns, kind, argv):
+    """--coverage-only without and with --coverage-spectrum, alternating; the parent build's plain --coverage-only behind them and
+    the new build's medians set against the parent's"""
+    with_sp = ["--coverage-only", "--coverage-spectrum", "--spectrum-max", str(args.spectrum)]
+    res = {"plain": [], "spectrum": [], "parent": []}
+    md5 = md5s = None
+    for rnd in range(args.rounds):
+        for tag, flags in (("plain", ["--coverage-only"]), ("spectrum", with_sp)):
+            r = step(EXE, argv + flags, dict(env), args.limit, tmp, ns, False)
+            md5 = md5 or r["md5"]
+            if r["md5"] != md5:
+                raise StepFailed(f"{ns} strains, {kind}, round {rnd}, {tag}: the coverage tables differ from the first run's")
+            if tag == "spectrum":
+                md5s = md5s or r["md5r"]
+                if r["md5r"] != md5s:
+                    raise StepFailed(f"{ns} strains, {kind}, round {rnd}: the spectrum tables differ from the first run's")
+            res[tag].append(r)
+    if args.parent_exe:
+        res["parent"] = [step(args.parent_exe, argv + ["--coverage-only"], dict(env), args.limit, tmp, ns, False) for _ in range(args.rounds)]
+        if any(r["md5"] != md5 for r in res["parent"]):
+            raise StepFailed(f"{ns} strains, {kind}: the parent build writes other tables")
+    say(f"{ns} strains, {kind}: the {ns} coverage tables are the same bytes in all runs (MD5 {md5}), the spectrum tables in all "
+        f"{args.rounds} (MD5 {md5s})")
+    names = {"plain": "--coverage-only", "spectrum": f"... --coverage-spectrum --spectrum-max {args.spectrum}", "parent": "parent build, --coverage-only"}
+    for tag, rs in res.items():
+        if rs:
+            say(f"    {names[tag]}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; accumulators on the device: folds "
+                f"{row(rs, 'fold', '.2f')} ms, target sweeps {row(rs, 'sweep', '.3f')} ms; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
+    keys = ("passed", "wall", "fold", "sweep")
+    med = {t: {k: statistics.median(r[k] for r in rs) for k in keys} for t, rs in res.items() if rs}
+    say("    with the spectrum / without at the medians: pass %.2f, wall %.2f, folds %.2f, target sweeps %.2f" %
+        tuple(med["spectrum"][k] / med["plain"][k] if med["plain"][k] else float("nan") for k in keys))
+    if res["parent"]:                                        # the yardstick: the parent's medians; the margin: its own spread
+        for k, unit in (("passed", "s"), ("sweep", "ms")):
+            spread = max(r[k] for r in res["parent"]) - min(r[k] for r in res["parent"])
+            for tag in ("plain", "spectrum"):
+                diff = med[tag][k] - med["parent"][k]
+                say(f"    {k}: {names[tag]} median {med[tag][k]:.3f} {unit} against the parent's {med['parent'][k]:.3f} {unit} "
+                    f"({diff:+.3f}; the parent's spread over {args.rounds} rounds is {spread:.3f}): {'within' if diff <= spread else 'BEYOND'} it, "
+                    f"ratio {med[tag][k] / med['parent'][k] if med['parent'][k] else float('nan'):.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbases", type=float, default=1.5, help="bases per list")
@@ -124,6 +172,7 @@ def main():
     ap.add_argument("--limit", type=int, default=150, help="seconds one run of the program may take")
     ap.add_argument("--parent-exe", default=None, help="strain_detect of a build of the parent commit")
     ap.add_argument("--regions", type=int, default=None, help="measure --coverage-regions with this --region-window")
+    ap.add_argument("--spectrum", type=int, default=None, help="measure --coverage-spectrum with this --spectrum-max")
     ap.add_argument("--out", default=None)
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
     args = ap.parse_args()
@@ -176,6 +225,9 @@ def main():
             for ns in counts:
                 for kind, lst in lists.items():
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
+                    if args.spectrum is not None:
+                        spectrum_case(say, args, env, tmp, ns, kind, argv)
+                        continue
                     if args.regions is not None:
                         regions_case(say, args, env, tmp, ns, kind, argv)
                         continue
