@@ -32,6 +32,7 @@
 #include "sk_common.h"
 
 #include "sk_parser.h"
+#include "sk_input.h"
 #include "sk_pack.h"
 #include "sk_pcache.h"
 #include "sk_ctxjob.h"
@@ -86,13 +87,13 @@ int sk_pack_stream(const uint8_t *stream, uint64_t nbytes, void *packed, int *od
 
 /* pipe: inflate on a helper thread while this one parses (worth it when there are fewer files than cores);
  * pipe > 1: the helper inflates each gzip member with that many threads (sk_gzpar.h) */
-/* how a plain file's bytes are got at: 0 = its pages populated into a mapping block by block (default), 1 = read() (SK_LIST_INPUT=read,
- * or set by the first thread that finds the kernel without MADV_POPULATE_READ) */
-static int list_input_mode = 0;
+/* how a plain file's bytes are got at (sk_input.h): SKI_POPULATE (default), or SKI_PREAD -- SK_LIST_INPUT=read, or latched by the first
+ * thread that finds the kernel without the populate advice */
+static int list_input_mode = SKI_POPULATE;
 static int list_input_read(void)
 {
     const char *e = getenv("SK_LIST_INPUT");
-    return __atomic_load_n(&list_input_mode, __ATOMIC_RELAXED) || (e && !strcmp(e, "read"));
+    return __atomic_load_n(&list_input_mode, __ATOMIC_RELAXED) == SKI_PREAD || (e && !strcmp(e, "read"));
 }
 
 /* this thread is parsing PLAIN text (set by parse_file / parse_range, read by the list scan's sink): only then are its chunks packed
@@ -123,67 +124,29 @@ static int parse_file(const char *path, rec_fn fn, void *user, int64_t *nrecords
     } else zrc = skz_decode_file(path, parse_feed_sink, &ps);
     if (zrc == SKZ_OPEN) { parser_free(&ps); return SK_E_OPEN; }
     if (zrc == SKZ_NOT_GZIP && !getenv("SK_ZLIB")) {
-        /* plain text: read() in 4 MiB blocks (round 4).  zlib's pass-through does the same copy behind more layers and cuts
-         * the text every MiB (the parser's whole-record shortcuts want their records inside ONE block).  Parsing out of a
-         * mapping of the file was measured and LOSES with 16 decode threads (BASELINE configs[2], 1,670 files in /dev/shm,
-         * gpurun_out/r04/cfg3_where.txt -> profiles/r04_cfg3_where.txt: the threads spend 31 s on a core and 37 s asleep in
-         * page faults behind the address space's lock, which every mmap/munmap of the other threads takes for writing --
-         * scans 4.6 s; read(): 42 s on a core, next to none asleep -- scans 3.4 s).  What is not a regular file goes
-         * through gzread below, which hands the same bytes on */
+        /* plain text in 4 MiB blocks, populated into a mapping of the file or copied (sk_input.h has the measurements).  zlib's
+         * pass-through copies behind more layers and cuts the text every MiB (the parser's whole-record shortcuts want their records
+         * inside ONE block).  What is not a regular file goes through gzread below, which hands the same bytes on */
         const int fd = open(path, O_RDONLY);
         struct stat sb;
-        size_t resume_at = 0;
         tl_plain_text = 1;
-        /* Later in round 4: the mapping WITHOUT its two costs.  A block's pages are put into the address space by one call
-         * (MADV_POPULATE_READ: no trap per 64 KiB), parsed where they lie, and taken out again by one call (MADV_DONTNEED) -- the
-         * lock is only ever taken for reading, and munmap finds nothing to tear down (that teardown under the lock for WRITING is
-         * what the other threads' page faults waited for).  No copy: once the chunks went up packed and the scan was bound by
-         * its CPUs, a sampling of the program counter had 56 % of the decode threads' time inside read()
-         * (tools/probes/sigprof_preload.c, profiles/r04_sigprof.txt).  SK_LIST_INPUT=read is the copying way, also taken where the
-         * kernel has no MADV_POPULATE_READ (before 5.14) or the pages cannot be had (a file that shrank) */
-#ifdef MADV_POPULATE_READ
-        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0 && !list_input_read()) {
-            const size_t n = (size_t)sb.st_size, PBLK = (size_t)4 << 20;
-            unsigned char *t = (unsigned char *)mmap(NULL, n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (t != MAP_FAILED) {
-                size_t at = 0;
-                while (at < n && ps.state != P_STOP) {
-                    const size_t take = n - at < PBLK ? n - at : PBLK;
-                    const size_t span = (take + 4095u) & ~(size_t)4095u;          /* (PBLK is a multiple of the page size: `at` stays page-aligned) */
-                    if (madvise(t + at, span, MADV_POPULATE_READ) != 0) {
-                        if (errno == EINVAL) __atomic_store_n(&list_input_mode, 1, __ATOMIC_RELAXED);
-                        break;
-                    }
-                    parser_feed(&ps, t + at, take);
-                    (void)madvise(t + at, span, MADV_DONTNEED);
-                    at += take;
-                }
-                munmap(t, n);
-                if (at >= n || ps.state == P_STOP) zrc = SKZ_OK;
-                else resume_at = at;
+        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
+            const size_t n = (size_t)sb.st_size, PBLK = (size_t)4 << 20, RBLK = ski_read_block(PBLK);
+            const unsigned char *t = n > 0 && !list_input_read() ? (const unsigned char *)mmap(NULL, n, PROT_READ, MAP_PRIVATE, fd, 0) : NULL;
+            ski_rbuf rb = { NULL, 0 };
+            size_t at = 0;
+            int fr = SKI_FED;
+            if (t == MAP_FAILED) t = NULL;
+            if (!t) (void)posix_fadvise(fd, 0, 0, POSIX_FADV_SEQUENTIAL);
+            /* (mapped: up to the size it was mapped with; copied: up to wherever the reads end, as with gzread) */
+            while (fr == SKI_FED && ps.state != P_STOP && (!t || at < n)) {
+                const size_t take = !t ? RBLK : n - at < PBLK ? n - at : PBLK;
+                fr = ski_feed_span(&ps, t, fd, at, take, &list_input_mode, &rb, RBLK, NULL);
+                at += take;
             }
-        }
-#endif
-        if (zrc == SKZ_NOT_GZIP && fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && lseek(fd, (off_t)resume_at, SEEK_SET) == (off_t)resume_at) {
-            const char *e = getenv("SK_READ_BLOCK");                /* (64 bytes -- tests -- .. 32 MiB; default 4 MiB) */
-            const long long ev = e ? atoll(e) : 0;
-            const size_t RBLK = ev >= 64 && ev <= (32 << 20) ? (size_t)ev : (size_t)4 << 20;
-            unsigned char *rb = (unsigned char *)malloc(RBLK);
-            if (rb) {
-                (void)posix_fadvise(fd, 0, 0, POSIX_FADV_SEQUENTIAL);
-                while (ps.state != P_STOP) {
-                    size_t have = 0;
-                    ssize_t r = 1;
-                    while (have < RBLK && (r = read(fd, rb + have, RBLK - have)) != 0) {
-                        if (r < 0) { if (errno == EINTR) continue; break; }
-                        have += (size_t)r;
-                    }
-                    if (have) parser_feed(&ps, rb, have);
-                    if (r <= 0) break;                  /* (end of file, or an error: what was read counts, as with gzread) */
-                }
-                free(rb);
-                zrc = SKZ_OK;
-            }
+            if (t) munmap((void *)t, n);
+            free(rb.buf);
+            if (fr != SKI_NOMEM) zrc = SKZ_OK;
         }
         if (fd >= 0) close(fd);
     }
@@ -857,17 +820,15 @@ static int parse_from(const char *path, uint64_t off, rec_fn fn, void *user, int
     enum { BLK = 4 << 20 };
     const int fd = open(path, O_RDONLY);
     unsigned char *rb;
+    size_t n;
     parser ps;
     if (fd < 0) return SK_E_OPEN;
     if (!(rb = (unsigned char *)malloc(BLK))) { close(fd); return SK_E_NOMEM; }
     parser_init(&ps, fn, user);
     tl_plain_text = 0;                                   /* (an item that began on the device never packs) */
-    while (ps.state != P_STOP) {
-        const ssize_t r = pread(fd, rb, BLK, (off_t)off);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) break;
-        parser_feed(&ps, rb, (size_t)r);
-        off += (uint64_t)r;
+    while (ps.state != P_STOP && (n = ski_pread_exact(fd, rb, BLK, off)) > 0) {
+        parser_feed(&ps, rb, n);
+        off += n;
     }
     free(rb);
     close(fd);
@@ -904,11 +865,9 @@ static int text_scan(sk_ctx *const *ctxs, uint32_t nctx, pthread_mutex_t *mu, co
     }
     for (;;) {
         sk_text_info info;
-        while (!eof && have < cap) {
-            const ssize_t r = pread(fd, buf + have, (size_t)(cap - have), (off_t)(off + have));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) { eof = 1; break; }
-            have += (uint64_t)r;
+        if (!eof && have < cap) {
+            have += ski_pread_exact(fd, buf + have, (size_t)(cap - have), off + have);
+            if (have < cap) eof = 1;
         }
         if (off + have >= (uint64_t)st.st_size) eof = 1;
         if (!have) break;
@@ -1393,40 +1352,22 @@ static int parse_range(const scan_item *it, rec_fn fn, void *user, int64_t *nrec
     if (fstat(fd, &st) != 0 || (uint64_t)st.st_size != it->size) { close(fd); return SK_E_SPLIT; }     /* (changed since the plan) */
     t = (const unsigned char *)mmap(NULL, (size_t)it->size, PROT_READ, MAP_PRIVATE, fd, 0);
     if (t == MAP_FAILED) { close(fd); return SK_E_OPEN; }
-    /* the mapping serves the two guesses and the look at the byte behind the piece (a few pages); the piece's text is read()
-     * into a block of this thread's -- sixteen threads faulting mapped pages in wait for each other (parse_file above) */
+    /* the mapping serves the two guesses and the look at the byte behind the piece (a few pages); the piece's text goes to the
+     * parser block by block, populated or copied (sk_input.h) */
     sa = parser_guess_start(t, it->size, it->a, 1);
     sb = it->b >= it->size ? it->size : parser_guess_start(t, it->size, it->b, 1);
     parser_init(&ps, fn, user);
     tl_plain_text = 1;
     {
-        unsigned char *rb = (unsigned char *)malloc(BLK);
+        int copy = SKI_PREAD;
+        int *const mode = list_input_read() ? &copy : &list_input_mode;
+        ski_rbuf rb = { NULL, 0 };
         for (i = sa; i < sb && ps.state != P_STOP; ) {
             const size_t want = (size_t)(sb - i < BLK ? sb - i : BLK);
-            size_t have = 0;
-#ifdef MADV_POPULATE_READ
-            if (!list_input_read()) {                        /* the block's pages populated, parsed in place, dropped (parse_file above) */
-                const uintptr_t pa = (uintptr_t)(t + i) & ~(uintptr_t)4095u, pe = ((uintptr_t)(t + i) + want + 4095u) & ~(uintptr_t)4095u;
-                if (madvise((void *)pa, (size_t)(pe - pa), MADV_POPULATE_READ) == 0) {
-                    const uintptr_t da = ((uintptr_t)(t + i) + 4095u) & ~(uintptr_t)4095u, de = ((uintptr_t)(t + i) + want) & ~(uintptr_t)4095u;
-                    parser_feed(&ps, t + i, want);
-                    if (de > da) (void)madvise((void *)da, (size_t)(de - da), MADV_DONTNEED);
-                    i += want;
-                    continue;
-                }
-                if (errno == EINVAL) __atomic_store_n(&list_input_mode, 1, __ATOMIC_RELAXED);
-            }
-#endif
-            while (rb && have < want) {
-                const ssize_t r = pread(fd, rb + have, want - have, (off_t)(i + have));
-                if (r < 0 && errno == EINTR) continue;
-                if (r <= 0) break;
-                have += (size_t)r;
-            }
-            if (rb && have == want) parser_feed(&ps, rb, want); else parser_feed(&ps, t + i, want);       /* (a failed read: out of the mapping) */
+            (void)ski_feed_span(&ps, t, fd, i, want, mode, &rb, BLK, NULL);      /* (never short: there is a mapping) */
             i += want;
         }
-        free(rb);
+        free(rb.buf);
     }
     close(fd);
     if (ps.state != P_STOP && sb < it->size && sb > sa)
@@ -1459,7 +1400,7 @@ static int parse_range(const scan_item *it, rec_fn fn, void *user, int64_t *nrec
  * 7.4 Gbase/s with the one parser, 5.1 with four helpers; FASTQ.gz 5.0 against 2.6-4.8.  Gathering the text into segments is
  * one more copy of every byte on the cutting thread, which is about what parsing it costs, and FASTQ is bound by the inflate
  * (9.5 GB/s of text = 4.6 Gbase/s) either way.  So it runs only when SK_PARSE_THREADS asks for it (tests do). */
-typedef struct gz_seg { unsigned char *buf; size_t n, cap; int is_last; struct gz_seg *next; } gz_seg;
+typedef struct gz_seg { unsigned char *buf; size_t n; int is_last; struct gz_seg *next; } gz_seg;
 typedef struct {
     scan_pool *pool;
     pthread_mutex_t mu; pthread_cond_t cv;
@@ -1519,11 +1460,13 @@ static void *gz_split_worker(void *arg)
     return NULL;
 }
 
-static void gz_split_push(gz_split *g, gz_seg *sg, int limit)
+/* a segment of the cutter's (sk_input.h) into the helpers' queue; they free it */
+static void gz_split_push(gz_split *g, unsigned char *buf, size_t n, int is_last, int limit)
 {
+    gz_seg *sg = (gz_seg *)calloc(1, sizeof *sg);
+    sg->buf = buf; sg->n = n; sg->is_last = is_last;
     pthread_mutex_lock(&g->mu);
     while (g->nq >= limit && !g->stop) pthread_cond_wait(&g->cv, &g->mu);
-    sg->next = NULL;
     if (g->tail) g->tail->next = sg; else g->head = sg;
     g->tail = sg;
     g->nq++;
@@ -1534,16 +1477,13 @@ static void gz_split_push(gz_split *g, gz_seg *sg, int limit)
 /* records (or a negative SK_E_*); -100: not a gzip file / no helper could be started -- the caller parses it the ordinary way */
 static int64_t parse_gz_split(scan_worker *w, const scan_item *it, uint64_t *bases)
 {
-    enum { BLK = 1 << 20 };
     skzp zp;
     gz_split g;
     pthread_t th[8];
     const char *e = getenv("SK_PARSE_THREADS");
     int npar = e ? atoi(e) : 0, nth = 0, i;          /* off unless asked for: measured, it loses -- see the comment above */
-    const size_t want = POOL_CHUNK / 2 < (1u << 20) ? POOL_CHUNK : POOL_CHUNK / 2;
-    const size_t TAIL = want / 2 < (64u << 10) ? (want / 2 < 256 ? 256 : want / 2) : (64u << 10);
-    size_t scan_from = want;
-    gz_seg *sg;
+    ski_cutter cut;
+    unsigned char *seg; size_t seg_n;
     if (npar < 2) return -100;
     if (npar > 8) npar = 8;
     if (skzp_open_threads(&zp, it->path, w->pool->pipe) != SKZ_OK) return -100;
@@ -1554,9 +1494,7 @@ static int64_t parse_gz_split(scan_worker *w, const scan_item *it, uint64_t *bas
     pthread_cond_init(&g.cv, NULL);
     for (i = 0; i < npar; i++) if (pthread_create(&th[nth], NULL, gz_split_worker, &g) == 0) nth++;
     if (nth == 0) { skzp_close(&zp); pthread_mutex_destroy(&g.mu); pthread_cond_destroy(&g.cv); return -100; }
-    sg = (gz_seg *)calloc(1, sizeof *sg);
-    sg->cap = want + (want >> 2) + BLK;
-    sg->buf = (unsigned char *)malloc(sg->cap);
+    ski_cutter_init(&cut, POOL_CHUNK / 2 < (1u << 20) ? POOL_CHUNK : POOL_CHUNK / 2);
     for (;;) {
         const unsigned char *data = NULL;
         size_t n;
@@ -1567,28 +1505,11 @@ static int64_t parse_gz_split(scan_worker *w, const scan_item *it, uint64_t *bas
         if (stop) break;
         n = skzp_next(&zp, &data);
         if (n == 0) break;
-        if (sg->n + n > sg->cap) { sg->cap = (sg->n + n) * 2; sg->buf = (unsigned char *)realloc(sg->buf, sg->cap); }
-        memcpy(sg->buf + sg->n, data, n);
-        sg->n += n;
-        while (sg->n >= want + TAIL) {                      /* (a delivery may hold several segments' worth) */
-            const uint64_t cut = parser_guess_start(sg->buf, sg->n, scan_from, 0);
-            if (cut >= sg->n) { scan_from = sg->n - TAIL; break; }     /* no likely record start yet (very long records): keep gathering */
-            else {
-                gz_seg *nx = (gz_seg *)calloc(1, sizeof *nx);
-                nx->cap = want + (want >> 2) + BLK;
-                if (nx->cap < sg->n - cut) nx->cap = (sg->n - cut) * 2;
-                nx->buf = (unsigned char *)malloc(nx->cap);
-                nx->n = sg->n - (size_t)cut;
-                memcpy(nx->buf, sg->buf + cut, nx->n);
-                sg->n = (size_t)cut;
-                gz_split_push(&g, sg, nth + 2);
-                sg = nx;
-                scan_from = want;
-            }
-        }
+        ski_cutter_add(&cut, data, n);
+        while (ski_cutter_take(&cut, &seg, &seg_n)) gz_split_push(&g, seg, seg_n, 0, nth + 2);      /* (a delivery may hold several segments' worth) */
     }
-    sg->is_last = 1;
-    gz_split_push(&g, sg, nth + 2);
+    ski_cutter_rest(&cut, &seg, &seg_n);
+    gz_split_push(&g, seg, seg_n, 1, nth + 2);
     pthread_mutex_lock(&g.mu);
     g.done = 1;
     pthread_cond_broadcast(&g.cv);

@@ -32,6 +32,7 @@
 #include "sk_alloc.h"
 #include "sk_common.h"
 #include "sk_parser.h"
+#include "sk_input.h"
 #include "sk_internal.h"
 #include "sk_ctxjob.h"
 #include "sk_gzpipe.h"
@@ -151,7 +152,7 @@ typedef struct {
     size_t      carry_last_len;              /* length of the last record handed out so far (for an END_STALE ending) */
     int         split_failed;                /* a segment did not end between two records */
     int         cancel_segments;             /* the file is over for the reader (truncated record): later segments are dropped */
-    int         in_mode;                     /* SD_IN_*: how the parser threads get at the bytes of a mapped plain file's segments */
+    int         in_mode;                     /* SKI_*: how the parser threads get at the bytes of a mapped plain file's segments */
     /* plain text parsed on the device (sd_text_read): the reader sends pieces of text until the main thread's verdict */
     int         text_mode;                   /* the option is on and the entry points are there */
     int         text_verdict;                /* 0 none yet, SD_VERDICT_DONE the last piece was accepted, SD_VERDICT_HOST the piece at text_off declined */
@@ -252,8 +253,7 @@ static void stream_push(sd_stream *st, sd_chunk *c)
 }
 
 /* chunk builder of one parser: where finished chunks go depends on who parses */
-enum { SD_IN_POPULATE = 0, SD_IN_PREAD = 1, SD_IN_MAPPED = 2 };
-typedef struct sd_seg { unsigned char *buf; size_t n, cap; uint64_t seq; int is_last, borrowed; int fd; uint64_t off; } sd_seg;   /* borrowed: buf points into the mapped file */
+typedef struct sd_seg { unsigned char *buf; size_t n; uint64_t seq; int is_last, borrowed; int fd; uint64_t off; } sd_seg;   /* borrowed: buf points into the mapped file */
 typedef struct {
     sd_stream *st;
     sd_chunk  *cur;                          /* chunk under construction */
@@ -340,19 +340,11 @@ static int sd_on_record(void *user, char *seq, size_t len)
  * (src/kseq.h:171-211 reads from the top; nothing here changes what a record is).  A failed check fails the run with
  * a message (SK_NO_SPLIT=1 turns the cutting off) -- it is never papered over.  Chunks reach the queue in segment
  * order: the replay of the reference's read-after-read bookkeeping (src/strain_detect.c:443-626) sees the file's order. */
-/* bytes per pread of a parser thread: SK_READ_BLOCK (64 bytes -- tests -- .. 32 MiB), default 2 MiB */
-static size_t sd_read_block(void)
-{
-    const char *e = getenv("SK_READ_BLOCK");
-    const long long v = e ? atoll(e) : 0;
-    return v >= 64 && v <= (32 << 20) ? (size_t)v : (size_t)2 << 20;
-}
-
 static void *sd_parse_worker(void *arg)
 {
     sd_stream *st = (sd_stream *)arg;
-    unsigned char *rbuf = NULL;
-    size_t rcap = 0;
+    ski_rbuf rb = { NULL, 0 };                             /* this thread's block, should it copy */
+    const size_t rblk = ski_read_block((size_t)2 << 20);
     pthread_setname_np(pthread_self(), "sk-parse");
     for (;;) {
         sd_seg *sg;
@@ -365,7 +357,7 @@ static void *sd_parse_worker(void *arg)
         if (st->segn == 0) {
             pthread_mutex_unlock(&st->pmu);
             pthread_mutex_lock(&t_pw_mu); cpu_parsers += thread_cpu_s(); pthread_mutex_unlock(&t_pw_mu);
-            free(rbuf);
+            free(rb.buf);
             return NULL;
         }
         sg = st->segq[0];
@@ -378,50 +370,10 @@ static void *sd_parse_worker(void *arg)
         memset(&b, 0, sizeof b);
         b.st = st;
         parser_init(&ps, sd_on_record, &b);
-        if (sg->borrowed && !st->cancel) {
-            /* A segment of a plain file: it points into the mapping of the whole file.  Three ways to get at its bytes (round 4):
-             *   SD_IN_POPULATE (default)  the segment's pages are put into the address space by ONE call, parsed where they lie, and
-             *       taken out again by one call: no copy, no trap per 64 KiB of text, and the address space's lock is only ever
-             *       taken for READING -- BASELINE configs[4]'s share pass 3.5-3.6 s, 40 CPU-seconds;
-             *   SD_IN_PREAD               read into a buffer of this thread's, in blocks that stay in the core's cache between the
-             *       copy and the parse: 3.9-4.1 s on the same box, 48 CPU-seconds -- a sampling of the program counter says 59 % of
-             *       a parser thread's time is the kernel's copy (tools/probes/sigprof_preload.c); also where the kernel has no
-             *       MADV_POPULATE_READ (before 5.14);
-             *   SD_IN_MAPPED              parsed out of the mapping, every page faulted in where it is first touched: 5.1-6.7 s.  Not
-             *       the faults themselves: the file's munmap at its end tears 2.7 M page-table entries down under the lock for
-             *       WRITING, and the next file's faults wait a third of a second for it, file after file.
-             * (profiles/r04_cfg5_pread.json, r04_cfg5_read_blocks.json, r04_cfg5_populate.json; SK_SD_INPUT=populate|pread|mapped) */
-            int mode = st->in_mode;
-            const uintptr_t pa = (uintptr_t)sg->buf & ~(uintptr_t)4095u, pe = ((uintptr_t)sg->buf + sg->n + 4095u) & ~(uintptr_t)4095u;
-            if (mode == SD_IN_POPULATE) {
-#ifdef MADV_POPULATE_READ
-                if (madvise((void *)pa, (size_t)(pe - pa), MADV_POPULATE_READ) != 0 && errno == EINVAL) st->in_mode = mode = SD_IN_PREAD;   /* (an older kernel: from now on the copy) */
-#else
-                st->in_mode = mode = SD_IN_PREAD;
-#endif
-            }
-            if (mode == SD_IN_PREAD && sg->fd >= 0) {
-                size_t done = 0;
-                if (!rbuf) { rcap = sd_read_block(); rbuf = (unsigned char *)malloc(rcap); }
-                while (done < sg->n && ps.state != P_STOP && !st->cancel) {
-                    const size_t want = sg->n - done < rcap ? sg->n - done : rcap;
-                    size_t have = 0;
-                    while (rbuf && have < want) {
-                        const ssize_t r = pread(sg->fd, rbuf + have, want - have, (off_t)(sg->off + done + have));
-                        if (r < 0 && errno == EINTR) continue;
-                        if (r <= 0) break;
-                        have += (size_t)r;
-                    }
-                    if (rbuf && have == want) parser_feed(&ps, rbuf, want); else parser_feed(&ps, sg->buf + done, want);    /* (a failed read: out of the mapping) */
-                    done += want;
-                }
-            } else parser_feed(&ps, sg->buf, sg->n);
-            if (mode == SD_IN_POPULATE) {               /* (whole pages inside the segment only: a neighbour may still be reading the ones at its ends) */
-                const uintptr_t da = ((uintptr_t)sg->buf + 4095u) & ~(uintptr_t)4095u, de = ((uintptr_t)sg->buf + sg->n) & ~(uintptr_t)4095u;
-                if (de > da) (void)madvise((void *)da, (size_t)(de - da), MADV_DONTNEED);
-            }
-        } else
-        if (!st->cancel) parser_feed(&ps, sg->buf, sg->n);
+        /* a segment of a plain file points into the mapping of the whole file: its pages populated, copied or faulted in (sk_input.h;
+         * SK_SD_INPUT=populate|pread|mapped) */
+        if (sg->borrowed) (void)ski_feed_span(&ps, sg->buf - sg->off, sg->fd, sg->off, sg->n, &st->in_mode, &rb, rblk, &st->cancel);
+        else if (!st->cancel) parser_feed(&ps, sg->buf, sg->n);
         if (!sg->is_last && ps.state != P_STOP && !parser_between_records(&ps)) ok = 0;
         if (ps.state != P_STOP || ps.end_kind != SKP_END_NONE) { /* (stopped by cancel or by a truncated record: the ending stands) */ }
         parser_eof(&ps);
@@ -465,6 +417,13 @@ static void *sd_parse_worker(void *arg)
         if (!sg->borrowed) free(sg->buf);
         free(sg);
     }
+}
+
+static sd_seg *sd_seg_new(unsigned char *buf, size_t n, uint64_t seq, int is_last)
+{
+    sd_seg *sg = (sd_seg *)calloc(1, sizeof *sg);
+    sg->buf = buf; sg->n = n; sg->seq = seq; sg->is_last = is_last;
+    return sg;
 }
 
 /* hand a segment to the parser threads (blocks while all of them are busy and a few wait) */
@@ -541,7 +500,7 @@ static int sd_text_read(sd_stream *st, const unsigned char *map, size_t mlen, in
         c->toff = at;
         if (cut == at || (cut == mlen && map[mlen - 1] != '\n')) c->text = SD_TEXT_DECLINED;      /* no cut within one buffer; a last line without its '\n' */
         else {
-            size_t have = 0;
+            size_t have;
             c->text = SD_TEXT_PENDING;
             c->tlen = cut - at;
             c->tla = cut < mlen;
@@ -549,12 +508,7 @@ static int sd_text_read(sd_stream *st, const unsigned char *map, size_t mlen, in
             if ((c->buf = (uint8_t *)sd_pin_get()) != NULL) c->pinned = 1;
             else { c->buf = (uint8_t *)malloc(cap); __atomic_add_fetch(&n_unpinned_chunks, 1, __ATOMIC_RELAXED); }
             if (!c->buf) { c->text = SD_TEXT_DECLINED; c->tlen = 0; }
-            while (c->buf && fd >= 0 && have < c->tlen + (size_t)c->tla) {
-                const ssize_t r = pread(fd, c->buf + have, c->tlen + (size_t)c->tla - have, (off_t)(at + have));
-                if (r < 0 && errno == EINTR) continue;
-                if (r <= 0) break;
-                have += (size_t)r;
-            }
+            have = c->buf && fd >= 0 ? ski_pread_exact(fd, c->buf, c->tlen + (size_t)c->tla, at) : 0;
             if (c->buf && have < c->tlen + (size_t)c->tla) memcpy(c->buf + have, map + at + have, c->tlen + (size_t)c->tla - have);   /* (a failed read: out of the mapping) */
         }
         {
@@ -577,7 +531,6 @@ static void *sd_decode_thread(void *arg)
 {
     enum { BLK = 1 << 20 };
     sd_stream *st = (sd_stream *)arg;
-    const size_t TAIL = st->chunk_bytes / 2 < (64u << 10) ? (st->chunk_bytes / 2 < 256 ? 256 : st->chunk_bytes / 2) : (64u << 10);   /* text wanted behind a cut */
     unsigned char *blk = (unsigned char *)malloc(BLK);
     int got;
     skzp zp;
@@ -610,9 +563,7 @@ static void *sd_decode_thread(void *arg)
         pthread_t wk[SD_PARSERS_MAX];
         int nw = 0, i;
         uint64_t seq = 0;
-        size_t scan_from;
         const size_t want = st->chunk_bytes;              /* about a chunk's worth of text per segment */
-        sd_seg *sg = NULL;
         {   /* a mapped file costs nothing to read: with a whole thread budget behind one file, eight parsers (an inflating
              * file keeps its four: the inflate threads need the CPUs) */
             const int npar = map && !getenv("SK_PARSE_THREADS") && st->gz_threads >= 16 ? SD_PARSERS_MAPPED : st->par;
@@ -623,65 +574,37 @@ static void *sd_decode_thread(void *arg)
             while (at < mlen && nw) {
                 size_t cut = mlen;
                 int over;
+                sd_seg *sg;
                 pthread_mutex_lock(&st->pmu);
                 over = st->cancel_segments;
                 pthread_mutex_unlock(&st->pmu);
                 if (st->cancel || over) break;
-                if (mlen - at > want + TAIL) cut = at + (size_t)parser_guess_start(map + at, mlen - at, want, 1);
-                sg = (sd_seg *)calloc(1, sizeof *sg);
-                sg->buf = (unsigned char *)map + at;
-                sg->n = cut - at;
-                sg->borrowed = 1;
-                sg->fd = map_fd;
-                sg->off = at;
-                sg->seq = seq++;
-                sg->is_last = cut == mlen;
+                if (mlen - at > want + ski_cut_tail(want)) cut = at + (size_t)parser_guess_start(map + at, mlen - at, want, 1);
+                sg = sd_seg_new((unsigned char *)map + at, cut - at, seq++, cut == mlen);
+                sg->borrowed = 1; sg->fd = map_fd; sg->off = at;
                 sd_seg_dispatch(st, sg);
                 at = cut;
             }
-            sg = NULL;
         } else {
-        sg = (sd_seg *)calloc(1, sizeof *sg);
-        sg->cap = want + (want >> 2) + BLK;
-        sg->buf = (unsigned char *)malloc(sg->cap);
-        scan_from = want;
-        for (;;) {
-            const unsigned char *data = NULL;
-            size_t n = 0;
-            int over;
-            pthread_mutex_lock(&st->pmu);
-            over = st->cancel_segments;
-            pthread_mutex_unlock(&st->pmu);
-            if (st->cancel || over || nw == 0) break;
-            if (own) n = skzp_next(&zp, &data);
-            else { got = gzread(st->g, blk, BLK); n = got > 0 ? (size_t)got : 0; data = blk; }
-            if (n == 0) break;
-            if (sg->n + n > sg->cap) { sg->cap = (sg->n + n) * 2; sg->buf = (unsigned char *)realloc(sg->buf, sg->cap); }
-            memcpy(sg->buf + sg->n, data, n);
-            sg->n += n;
-            if (sg->n >= want + TAIL) {
-                /* the first likely record start behind a chunk's worth of text (looked for in what has not been looked at
-                 * yet; the guess wants two more lines of text behind it); none so far (very long records): keep gathering */
-                const uint64_t cut = parser_guess_start(sg->buf, sg->n, scan_from, 0);
-                if (cut >= sg->n) scan_from = sg->n - TAIL;
-                else {
-                    scan_from = want;
-                    sd_seg *nx = (sd_seg *)calloc(1, sizeof *nx);
-                    nx->cap = want + (want >> 2) + BLK;
-                    if (nx->cap < sg->n - cut) nx->cap = (sg->n - cut) * 2;
-                    nx->buf = (unsigned char *)malloc(nx->cap);
-                    nx->n = sg->n - (size_t)cut;
-                    memcpy(nx->buf, sg->buf + cut, nx->n);
-                    sg->n = (size_t)cut;
-                    sg->seq = seq++;
-                    sd_seg_dispatch(st, sg);
-                    sg = nx;
-                }
+            ski_cutter ct;                                 /* the inflated text gathered and cut (sk_input.h) */
+            unsigned char *buf; size_t len;
+            ski_cutter_init(&ct, want);
+            for (;;) {
+                const unsigned char *data = NULL;
+                size_t n = 0;
+                int over;
+                pthread_mutex_lock(&st->pmu);
+                over = st->cancel_segments;
+                pthread_mutex_unlock(&st->pmu);
+                if (st->cancel || over || nw == 0) break;
+                if (own) n = skzp_next(&zp, &data);
+                else { got = gzread(st->g, blk, BLK); n = got > 0 ? (size_t)got : 0; data = blk; }
+                if (n == 0) break;
+                ski_cutter_add(&ct, data, n);
+                if (ski_cutter_take(&ct, &buf, &len)) sd_seg_dispatch(st, sd_seg_new(buf, len, seq++, 0));     /* (one cut per delivery) */
             }
-        }
-        sg->seq = seq++;
-        sg->is_last = 1;
-        if (nw) sd_seg_dispatch(st, sg); else { free(sg->buf); free(sg); }
+            ski_cutter_rest(&ct, &buf, &len);
+            if (nw) sd_seg_dispatch(st, sd_seg_new(buf, len, seq++, 1)); else free(buf);
         }
         pthread_mutex_lock(&st->pmu);
         st->seg_done = 1;
@@ -1040,7 +963,7 @@ static int stream_open(sd_stream *st, const char *path, int gz_threads)
     st->chunk_bytes = sd_chunk_bytes();
     {   /* SK_SD_INPUT=populate|pread|mapped (SK_SD_MAPPED=1: the round-3 way, kept for the A/B) */
         const char *e = getenv("SK_SD_INPUT");
-        st->in_mode = e && !strcmp(e, "pread") ? SD_IN_PREAD : (e && !strcmp(e, "mapped")) || getenv("SK_SD_MAPPED") ? SD_IN_MAPPED : SD_IN_POPULATE;
+        st->in_mode = e && !strcmp(e, "pread") ? SKI_PREAD : (e && !strcmp(e, "mapped")) || getenv("SK_SD_MAPPED") ? SKI_MAPPED : SKI_POPULATE;
     }
     {   /* parser threads for this file: when the budget leaves several threads per file (the case of one or two big
          * metagenomes), a quarter of them parse; SK_PARSE_THREADS sets the number, SK_NO_SPLIT=1 means one */
