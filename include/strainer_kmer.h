@@ -330,6 +330,22 @@ uint32_t sk_union_rows(const sk_union *u);                   /* the members' row
 int  sk_union_count_enable(sk_union *u, uint32_t ncols);
 sk_ctx *sk_union_context(sk_union *u);
 int  sk_union_counts_fold(sk_union *u, uint32_t ucol, uint32_t member_col, uint32_t member_mask, int subtract);
+/* The k-mers the strains of a panel SHARE (new: strain_detect -S --panel-share=FILE): every pair of members at once, at the
+ * workflow's k, from the masks every row of a union carries.  The reference has no counterpart: its genome_compare
+ * (src/genome_compare.c) compares one pair of genomes per process at k = 20 and knows no informative sets.
+ * out[3][SK_UNION_MAX][SK_UNION_MAX], u64, row = member of a, column = member of b (b == NULL: b is a):
+ *   out[0][i][j] distinct keys that member i of a and member j of b both hold
+ *   out[1][i][j] keys informative in member i of a that member j of b holds
+ *   out[2][i][j] keys informative in both
+ * cells of members that do not exist are 0.  "Informative" is what the union's snapshot holds (sk_union_create's type_col and
+ * informative_value).  Synchronous.  SK_E_ARG: a and b on different devices.
+ * The table of --panel-share: one file for the whole panel, integers, this header line and then one line per ORDERED pair of
+ * strains, a == b included, in the order of the -S file (a outer, b inner):
+ *   strain_a<TAB>strain_b<TAB>kmers_a<TAB>informative_a<TAB>shared_kmers<TAB>informative_a_in_b<TAB>informative_both
+ * strain names are formed as the coverage tables' strain_name (the -o file's basename without a trailing ".kmer_hits.gz");
+ * kmers_a = out[0] and informative_a = out[1] on the diagonal (a against itself), the other three columns are the pair's cells of
+ * out[0], out[1], out[2].  Strains of different unions are compared by sk_union_share(u[g], u[h], ..) for g != h. */
+int  sk_union_share(sk_union *a, sk_union *b_or_null, uint64_t *out /* 3 * SK_UNION_MAX * SK_UNION_MAX */);
 
 /* Wait for all queued work of the context. */
 int sk_sync(sk_ctx *ctx);

@@ -266,3 +266,57 @@ __global__ void sk_union_fold_member(uint32_t *__restrict__ dst, const uint32_t 
     const uint32_t v = ucol[canon[base + i]];
     dst[i] = subtract ? dst[i] - v : dst[i] + v;
 }
+
+// ---- the panel's shared keys (sk_union_share; strain_detect -S --panel-share).  New: the reference compares one pair of genomes
+// per process (src/genome_compare.c); here every pair of members of union a and union b is counted in one sweep of a's slots.
+// A non-empty slot is one distinct key; its row's pair of masks says which members of a hold it (xa) and in which it is
+// informative (ya).  With b == a the key's masks in b are the same pair; with another union the key is probed in b's slots (the
+// probe of sk_union_mask_a) and a key b lacks adds nothing.  out[0][i][j] += 1 for i in xa, j in xb; out[1] for i in ya, j in xb;
+// out[2] for i in ya, j in yb.  As the coverage sweeps (sk_covacc.hip): counted in LDS first -- three 32 x 32 u32 matrices, 12 KiB
+// a workgroup, which sees fewer than 2^32 keys -- then the non-zero cells go out with 64-bit atomics.
+#define SK_SHARE_BLOCKS 512u                                        // at most this many workgroups of 256: two per CU
+#define SK_SHARE_CELLS (3u * SK_UNION_MAX * SK_UNION_MAX)
+__device__ __forceinline__ void sk_share_add(uint32_t *m, uint32_t rows, const uint32_t cols)
+{
+    while (rows) {
+        const uint32_t i = (uint32_t)__builtin_ctz(rows);
+        rows &= rows - 1u;
+        for (uint32_t c = cols; c; c &= c - 1u) atomicAdd(&m[i * SK_UNION_MAX + (uint32_t)__builtin_ctz(c)], 1u);
+    }
+}
+__global__ void __launch_bounds__(256) sk_union_share_sweep(const sk_u4 *__restrict__ aslots, uint64_t naslots, const uint2 *__restrict__ amask,
+                                                            const sk_u4 *__restrict__ bslots, uint32_t bmask, const uint2 *__restrict__ bumask,
+                                                            unsigned long long *__restrict__ out)
+{
+    __shared__ uint32_t acc[SK_SHARE_CELLS];
+    for (uint32_t c = threadIdx.x; c < SK_SHARE_CELLS; c += blockDim.x) acc[c] = 0u;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < naslots; i += stride) {
+        const sk_u4 e = aslots[i];
+        const uint64_t k = sk_slot_key(e);
+        if (k == SK_EMPTY64) continue;
+        const uint2 ma = amask[e.z];
+        uint2 mb = ma;
+        if (bslots) {                                              // (uniform: a kernel argument)
+            mb = make_uint2(0u, 0u);
+            uint32_t slot = sk_slot0(sk_khash(k), bmask);
+            for (uint32_t step = 0; ; step++) {
+                const sk_u4 u = bslots[slot];
+                const uint64_t uk = sk_slot_key(u);
+                if (uk == k) { mb = bumask[u.z]; break; }
+                if (uk == SK_EMPTY64 || step == bmask) break;      // b does not hold the key (step: a table without an empty slot)
+                slot = (slot + 1u) & bmask;
+            }
+            if (!mb.x) continue;
+        }
+        sk_share_add(acc, ma.x, mb.x);
+        sk_share_add(acc + SK_UNION_MAX * SK_UNION_MAX, ma.y, mb.x);
+        sk_share_add(acc + 2u * SK_UNION_MAX * SK_UNION_MAX, ma.y, mb.y);
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < SK_SHARE_CELLS; c += blockDim.x) {
+        const uint32_t v = acc[c];
+        if (v) atomicAdd(out + c, (unsigned long long)v);
+    }
+}

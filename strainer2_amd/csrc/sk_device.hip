@@ -1637,6 +1637,37 @@ extern "C" const char *sk_union_last_error(const sk_union *u) { return u ? u->uc
 extern "C" uint32_t sk_union_members(const sk_union *u) { return u ? u->n : 0u; }
 extern "C" uint32_t sk_union_rows(const sk_union *u) { return u ? u->uc->nrows : 0u; }
 
+// The panel's shared keys: one sweep of a's slots (sk_union_share_sweep), a's own masks or a probe in b's table per key.  The three
+// matrices are allocated for the call and freed again: a union that is never asked holds nothing for it.
+extern "C" int sk_union_share(sk_union *a, sk_union *b, uint64_t *out)
+{
+    if (!a || !out) return SK_E_ARG;
+    sk_ctx *c = a->uc;
+    if (b == a) b = NULL;
+    if (b && b->uc->device != c->device) return sk_fail(c, SK_E_ARG, "the two unions live on different devices");
+    SK_HIP(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)SK_SHARE_CELLS * sizeof(unsigned long long);
+    unsigned long long *d_out = NULL;
+    SK_UNION_MALLOC(c, hipMalloc((void **)&d_out, bytes));
+    const uint64_t naslots = (uint64_t)1 << c->slots_log2;
+    uint64_t gx = (naslots + 255u) / 256u;
+    if (gx > SK_SHARE_BLOCKS) gx = SK_SHARE_BLOCKS;
+    hipError_t e = hipSuccess;
+    if (b) e = hipStreamSynchronize(b->uc->stream);               // (b's table and masks are complete since its create; nothing of b's is in flight that writes them)
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, bytes, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(sk_union_share_sweep, dim3((unsigned)gx), dim3(256), 0, c->stream, (const sk_u4 *)c->d_keys, naslots, (const uint2 *)a->d_umask,
+                           b ? (const sk_u4 *)b->uc->d_keys : (const sk_u4 *)NULL, b ? (uint32_t)(((uint64_t)1 << b->uc->slots_log2) - 1u) : 0u,
+                           b ? (const uint2 *)b->d_umask : (const uint2 *)NULL, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) { (void)hipGetLastError(); return sk_fail(c, SK_E_HIP, "sk_union_share failed: %s", hipGetErrorString(e)); }
+    return SK_OK;
+}
+
 extern "C" int sk_scan_device(sk_ctx *c, const void *dev_stream, uint64_t nbytes, uint32_t col)
 {
     if (!c || (!dev_stream && nbytes)) return SK_E_ARG;

@@ -338,6 +338,14 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
         }
         if (c > 0 && !strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { c++; continue; }
         if (c > 0 && !strncmp(argv[c], "--spectrum-max=", 15)) continue;
+        if (c > 0 && !strncmp(argv[c], "--panel-share", 13) && (argv[c][13] == 0 || argv[c][13] == '=')) {
+            if (argv[c][13] == 0 || argv[c][14] == 0) {      /* (the one table of the whole panel: here a file name is needed) */
+                fprintf(err, "kmer_scrub_count: --panel-share=FILE needs a file name: the table is one file for the whole panel\n");
+                free(v);
+                return 1;
+            }
+            continue;
+        }
         if (c > 0 && !strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { c++; continue; }
         v[n++] = argv[c];
     }

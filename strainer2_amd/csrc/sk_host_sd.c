@@ -1482,6 +1482,85 @@ static void sd_unions_open(sd_prog *p, uint32_t ns)
     if (getenv("SK_SD_TIMING")) fprintf(p[0].err, "strain_detect timing: %u union table(s) for %u strains in %.2f s\n", ng, ns, now_s() - t0);
 }
 
+/* ---------------------------------------------------------------------------------------------
+ * --panel-share=FILE (-S only; include/strainer_kmer.h has the table): how many k-mers the strains of the panel share, every ordered
+ * pair of them, from the masks the union tables carry -- sk_union_share(u[g], NULL) for every group, (u[g], u[h]) for every ordered
+ * pair of groups -- before the first target is read.  The table depends on the strains alone.  The device's entry is weak, as the
+ * accumulators' are: the host-only test builds link this file without it, and there the flag fails the run.
+ * ------------------------------------------------------------------------------------------- */
+#pragma weak sk_union_share
+static struct { const char *path; double ms; unsigned calls; } sd_ps;
+
+/* the coverage tables' strain_name: the -o file's basename without a trailing "<any>kmer_hits<any>gz" */
+static char *sd_strain_name(const char *o_path)
+{
+    const char *b = strrchr(o_path, '/');
+    char *n = strdup(b ? b + 1 : o_path);
+    const size_t l = n ? strlen(n) : 0;
+    if (l >= 13 && !memcmp(n + l - 12, "kmer_hits", 9) && !memcmp(n + l - 2, "gz", 2)) n[l - 13] = 0;
+    return n;
+}
+
+static int sd_panel_share(sd_prog *p, uint32_t ns)
+{
+    const uint32_t M = SK_UNION_MAX, ng = (ns + sd_group - 1) / sd_group;
+    const size_t cells = (size_t)3 * M * M;
+    const double t0 = now_s();
+    FILE *err = p[0].err, *f = NULL;
+    sk_union *one = NULL, **u = sd_un.u;
+    uint64_t *blk = NULL, *mat = NULL;
+    char **name = NULL;
+    uint32_t g, h, s, t;
+    int rc = SK_OK, bad = 1;
+    sd_ps.ms = 0; sd_ps.calls = 0;
+    if (!sk_union_share) { fprintf(err, "strain_detect: --panel-share: this build has no sk_union_share\n"); return 1; }
+    if (!sd_un.n && ns == 1 && !getenv("SK_SD_NO_UNION")) {          /* (a panel of one: a union for this table only) */
+        if (sk_union_create(&p[0].ctx, 1, SD_TYPE, SD_INFORMATIVE, &one) == SK_OK) u = &one;
+    }
+    if (!u || (!one && sd_un.n != ng)) {
+        fprintf(err, "strain_detect: --panel-share: the strains cannot all be held in union tables (a strain with byte-string keys or "
+                     "without a text stage, a union that could not be built, or SK_SD_NO_UNION): no table of the panel\n");
+        return 1;
+    }
+    blk = (uint64_t *)malloc(cells * sizeof *blk);
+    mat = (uint64_t *)calloc((size_t)3 * ns * ns, sizeof *mat);
+    name = (char **)calloc(ns, sizeof *name);
+    for (s = 0; name && s < ns; s++) if (!(name[s] = sd_strain_name(p[s].o_path))) break;
+    if (!blk || !mat || !name || s < ns) { fprintf(err, "strain_detect: out of memory\n"); goto out; }
+    for (g = 0; g < ng; g++)
+        for (h = 0; h < ng; h++) {
+            const uint32_t a0 = g * sd_group, b0 = h * sd_group;
+            const uint32_t na = ns - a0 < sd_group ? ns - a0 : sd_group, nb = ns - b0 < sd_group ? ns - b0 : sd_group;
+            uint32_t k;
+            if ((rc = sk_union_share(u[g], g == h ? NULL : u[h], blk)) != SK_OK) {
+                fprintf(err, "strain_detect: --panel-share: device error: %s (%s)\n", sk_strerror(rc), sk_union_last_error(u[g]));
+                goto out;
+            }
+            sd_ps.calls++;
+            for (k = 0; k < 3; k++)
+                for (s = 0; s < na; s++)
+                    for (t = 0; t < nb; t++)
+                        mat[((size_t)k * ns + a0 + s) * ns + b0 + t] = blk[((size_t)k * M + s) * M + t];
+        }
+    sd_ps.ms = (now_s() - t0) * 1e3;
+    if (!(f = fopen(sd_ps.path, "w"))) { fprintf(err, "strain_detect: could not write %s\n", sd_ps.path); goto out; }
+    fputs("strain_a\tstrain_b\tkmers_a\tinformative_a\tshared_kmers\tinformative_a_in_b\tinformative_both\n", f);
+    for (s = 0; s < ns; s++)
+        for (t = 0; t < ns; t++)
+            fprintf(f, "%s\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\n", name[s], name[t],
+                    (unsigned long long)mat[(size_t)s * ns + s], (unsigned long long)mat[((size_t)ns + s) * ns + s],
+                    (unsigned long long)mat[(size_t)s * ns + t], (unsigned long long)mat[((size_t)ns + s) * ns + t],
+                    (unsigned long long)mat[((size_t)2 * ns + s) * ns + t]);
+    bad = ferror(f) != 0;
+    if (fclose(f)) bad = 1;
+    if (bad) fprintf(err, "strain_detect: error writing %s\n", sd_ps.path);
+out:
+    sk_union_destroy(one);
+    for (s = 0; name && s < ns; s++) free(name[s]);
+    free(name); free(blk); free(mat);
+    return bad;
+}
+
 /* while the device scans the current chunk: the next chunk of the stream's queue (if the reader is ahead) goes up into the
  * stream's other batch -- the upload of a 32 MiB chunk takes about twice as long as its scan against a union table */
 static void sd_prefetch(sd_stream *st)
@@ -2866,6 +2945,7 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     sd_pin_open(p[0].ctx, sd_chunk_bytes());
     sd_all_p = p; sd_all_ns = ns;
     sd_unions_open(p, ns);
+    if (sd_ps.path && sd_panel_share(p, ns)) { sd_unions_close(); return 1; }      /* (before any target is read) */
     sd_co.host = 0;
     if (sd_co.on && B) {                                 /* the script keys its samples by basename: two targets that share one are one sample */
         FILE *fp = fopen(B, "r");
@@ -3045,8 +3125,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     const char *const *rg_genomes = sd_rg.genomes;       /* (adopted strains: theirs for this call only) */
     const uint32_t rg_ngenomes = sd_rg.ngenomes;
     skh_regions *rgs = NULL;
-    int want_rg = 0, want_sp = 0;
-    const char *sp_file = NULL, *sp_max = NULL;
+    int want_rg = 0, want_sp = 0, want_ps = 0;
+    const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL;
     long long cov_min = 1;
     double t_begin = 0;
     sd_prog *p = NULL;
@@ -3096,6 +3176,13 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         }
         if (!strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { sp_max = argv[++c]; continue; }
         if (!strncmp(argv[c], "--spectrum-max=", 15)) { sp_max = argv[c] + 15; continue; }
+        /* "--panel-share=FILE" (-S only): before the first target, the k-mers every ordered pair of the panel's strains share, one
+         * table for the whole panel (sd_panel_share) */
+        if (!strncmp(argv[c], "--panel-share", 13) && (argv[c][13] == 0 || argv[c][13] == '=')) {
+            want_ps = 1;
+            ps_file = argv[c][13] ? argv[c] + 14 : NULL;
+            continue;
+        }
         if (!strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { cov_min = atoll(argv[++c]); continue; }
         if (!strcmp(argv[c], "--target-cache") && c + 1 < argc) { tc_dir = argv[++c]; continue; }       /* (extension: the target cache, see sd_tc) */
         if (!strncmp(argv[c], "--target-cache=", 15)) { tc_dir = argv[c] + 15; continue; }
@@ -3105,6 +3192,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_rg.on = 0; sd_rg.genomes = NULL; sd_rg.ngenomes = 0;
     sd_spec.on = 0;
     sd_co.on = 0;
+    sd_ps.path = NULL;
     if (cov_only && want_cov) { fputs("strain_detect: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n", err); return sd_drop(p, ns); }
 
     optind = 1;
@@ -3166,6 +3254,23 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         }
         sd_spec.max = (uint32_t)d;
     }
+    if (want_ps) {
+        const char *ws = getenv("SK_WORLD_SIZE") ? getenv("SK_WORLD_SIZE") : getenv("WORLD_SIZE");
+        if (!ps_file || !*ps_file) { fputs("strain_detect: --panel-share=FILE needs a file name: the table is one file for the whole panel\n", err); return sd_drop(p, ns); }
+        if (!((S && !a && !o && !r) || (ad && ad->o))) { fputs("strain_detect: --panel-share goes with -S: it compares the strains of a panel\n", err); return sd_drop(p, ns); }
+        if (!sk_union_share) { fputs("strain_detect: --panel-share: this build has no sk_union_share\n", err); return sd_drop(p, ns); }
+        if (ws && atoi(ws) > 1) { fprintf(err, "strain_detect: --panel-share is for ONE process: with WORLD_SIZE %d each rank holds only its own strains\n", atoi(ws)); return sd_drop(p, ns); }
+        if (!ad && (env = getenv("SK_DEVICES")) != NULL && *env) {     /* (several logical devices on ONE card are fine: SK_DEVICES=0,0) */
+            int several = !strchr(env, ',') && atoi(env) > 1;
+            const char *q = strchr(env, ',');
+            for (; q && !several; q = strchr(q + 1, ',')) several = atoi(q + 1) != atoi(env);
+            if (several) {
+                fprintf(err, "strain_detect: --panel-share compares strains on ONE device and SK_DEVICES=%s names several: the table depends on the strains "
+                             "only, take it in a one-device run\n", env);
+                return sd_drop(p, ns);
+            }
+        }
+    }
     if (ad) { a = ad->a[0]; r = "(resident)"; S = NULL; }
     if (S && !a && !o && !r) {
         if (!b && !B) { usage(err); return sd_drop(p, ns); }
@@ -3197,6 +3302,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_co_ms_fold = sd_co_ms_sweep = 0;
     sd_rg.on = want_rg;
     sd_spec.on = want_sp;
+    sd_ps.path = want_ps ? ps_file : NULL;
+    sd_ps.ms = 0; sd_ps.calls = 0;
     sd_co.flush_rows = (env = getenv("SK_SD_CO_FLUSH_ROWS")) != NULL && atoll(env) >= 1 ? (uint64_t)atoll(env) : 1u << 20;
     sd_res_bytes = 0;
     sd_tc_open(tc_dir, err);
@@ -3356,6 +3463,8 @@ done:
     if (getenv("SK_SD_TIMING") && cov_only)
         fprintf(err, "strain_detect timing: coverage accumulators on the device: folds %.3f ms, target sweeps %.3f ms%s\n", sd_co_ms_fold, sd_co_ms_sweep,
                 want_rg && want_sp ? " (folded by region, binned by depth)" : want_rg ? " (folded by region)" : want_sp ? " (binned by depth)" : "");
+    if (getenv("SK_SD_TIMING") && want_ps)
+        fprintf(err, "strain_detect timing: panel share %.3f ms, %u call(s) of sk_union_share\n", sd_ps.ms, sd_ps.calls);
     if (getenv("SK_SD_RESULT_BYTES"))
         fprintf(err, "strain_detect: scan results copied from the device: %llu bytes; --coverage-only: %llu runs counted on the device, %llu replayed, "
                      "%llu targets on the host accumulator (the process's totals)\n", (unsigned long long)sd_res_bytes,
@@ -3365,6 +3474,7 @@ done:
     sd_co.on = 0;
     sd_rg.on = 0;
     sd_spec.on = 0;
+    sd_ps.path = NULL;
     for (s = 0; rgs && s < nrgs; s++) skh_regions_free(&rgs[s]);
     free(rgs);
     {   /* closing a strain = finishing its gz output, freeing its device context and tables: strain by strain on threads */

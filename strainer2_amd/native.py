@@ -31,6 +31,7 @@ def _load():
 lib = _load()
 
 SK_K = 31
+SK_UNION_MAX = 32
 SK_REF_TABLE_SLOTS = 8000000
 SK_KEY_NONE = 0xFFFFFFFFFFFFFFFF
 SK_OK = 0
@@ -69,6 +70,7 @@ ABI_SYMBOLS = [
     "skh_regions_from_file", "skh_regions_free", "sk_table_first_pos", "sk_covacc_set_regions", "sk_covacc_region_rows",
     "sk_covacc_finish_target_regions",
     "sk_covacc_set_spectrum", "sk_covacc_finish_target_spectrum", "sk_distinct_spectrum",
+    "sk_union_share",
 ]
 
 
@@ -246,6 +248,7 @@ lib.sk_union_members.argtypes = [C.c_void_p]
 lib.sk_union_members.restype = C.c_uint32
 lib.sk_union_rows.argtypes = [C.c_void_p]
 lib.sk_union_rows.restype = C.c_uint32
+lib.sk_union_share.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 
 _libc = C.CDLL(None)
 _libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
@@ -1005,6 +1008,16 @@ class KmerUnion:
         if member_mask is None:
             member_mask = (1 << len(self._members)) - 1
         self._uck(lib.sk_union_counts_fold(self._h, ucol, member_col, member_mask & 0xFFFFFFFF, int(bool(subtract))))
+
+    def share(self, other=None):
+        """sk_union_share: (shared, informative_in_other, informative_both), three uint64 arrays [members of self, members of
+        other or self] -- distinct keys member i and member j both hold, keys informative in i that j holds, keys informative
+        in both.  The cells beyond the members (all zero) are kept in .share_raw for the tests."""
+        raw = np.zeros((3, SK_UNION_MAX, SK_UNION_MAX), dtype=np.uint64)
+        self._uck(lib.sk_union_share(self._h, other._h if other is not None else None, raw.ctypes.data))
+        self.share_raw = raw
+        n, m = len(self._members), len((self if other is None else other)._members)
+        return tuple(raw[k, :n, :m].copy() for k in range(3))
 
     def scan_timing(self, reset=False):
         """(milliseconds, launches) of the union's scan kernels since the last reset, from HIP events"""
