@@ -763,10 +763,64 @@ int  sk_covacc_finish_target_spectrum(sk_covacc *a, uint64_t *out_unique /* nmem
                                       uint64_t *reg_unique /* NULL: no regions */, uint64_t *reg_total);
 int  sk_distinct_spectrum(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, uint64_t n, uint32_t nsamples, uint32_t max_depth,
                           uint64_t *out_unique, uint64_t *out_total, uint64_t *spec /* nsamples x (max_depth + 1) */, uint64_t *deep_total);
+/* RECURRENCE (new: strain_detect --coverage-recurrence [--recurrence-pairs], coverage_depth --recurrence [--recurrence-pairs]): which informative k-mers of a strain were seen in sample
+ * after sample of one run.  Every other number here is per (strain, sample); two cases with the same numbers per sample differ
+ * across samples: a strain present at low depth shows another random subset of its informative k-mers in every sample (the union
+ * grows, few are seen everywhere, few never), a relative, a shared plasmid or a handful of conserved k-mers shows the same subset
+ * in every sample (a block seen in all T samples, the rest in none).  The rule, for a strain and the T samples of a run:
+ *   sample    a target's basename, as in the script; T = the samples of the main coverage table, in its order.  Samples without a
+ *             hit count in T.
+ *   seen      a row is seen in a sample when its depth there is >= 1 after the script's read filter (total_kmer > min_kmer_hits):
+ *             exactly the row set that unique_observed_informative_kmers counts.
+ *   limits    1 <= T <= SK_RECUR_SAMPLES_MAX = 4096; the pair table takes T <= SK_RECUR_PAIRS_MAX = 256.
+ *   n[m]      for 1 <= m <= T: the rows seen in exactly m samples.  n[0] = I - sum over m >= 1 of n[m]; I = the strain's informative
+ *             rows (the total_genome_informative_kmers trailer), as the spectrum does it.
+ *   shared[i][j]  for samples i <= j: the rows seen in both; shared[i][i] is sample i's unique column.
+ *             either[i][j] = shared[i][i] + shared[j][j] - shared[i][j].
+ *   invariants  sum of m * n[m] = sum of shared[i][i] = the sum of the main table's unique column; sum of n[m] over m >= 0 = I;
+ *             shared is symmetric and shared[i][j] <= min(shared[i][i], shared[j][j]).
+ *   tables    a header line each, all columns integers:
+ *               strain_name<TAB>samples<TAB>seen_in<TAB>informative_kmers
+ *             seen_in ascends, one line per non-empty m, the 0 line whenever I is known;
+ *               strain_name<TAB>metagenome_a<TAB>metagenome_b<TAB>shared_informative_kmers<TAB>either_informative_kmers
+ *             every i <= j, zeros included, i ascending, then j.
+ * The engine works on generic bit planes: nmembers (1..SK_RECUR_MEMBERS_MAX) members of nbits[m] bits, nsamples planes, all zero
+ * after create, on ctx's device; errors go through ctx (sk_last_error); one caller at a time; every call is synchronous.
+ *   sk_recur_create: SK_E_ARG for nsamples of 0 or above SK_RECUR_SAMPLES_MAX.
+ *   sk_recur_mark_bits: OR these bits of `member` into plane `sample`; duplicates are fine.  SK_E_ARG for a bit, member or sample
+ *   out of range, and then nothing of the call is marked.
+ *   sk_recur_finish: hist[m * (nsamples + 1) + k] = bits of member m set in exactly k planes (entry 0: in none); pairs (NULL: not
+ *   wanted; SK_E_ARG with nsamples > SK_RECUR_PAIRS_MAX): pairs[(m * nsamples + i) * nsamples + j] = bits of member m set in planes i
+ *   and j, symmetric, diagonal filled.  It reads only: it may be called again, and after more marks.
+ *   sk_covacc_set_recurrence: build member's rank map from ctx's table (same device, same row count, the row order of
+ *   sk_covacc_region_rows): a row whose counter in type_col equals informative_value gets its rank among the member's such rows,
+ *   every other row 0xFFFFFFFF.  *out_informative = the number of such rows: the member's nbits.  One u32 per row of the
+ *   accumulator is kept from the first call on; a member never set has no informative row.
+ *   sk_covacc_mark_target: every row with a non-zero counter sets bit rank[row] of its member in plane `sample` of r; the counters
+ *   are not changed (call it before the sweep that ends the target).  A non-zero row without a rank marks nothing and is counted in
+ *   *out_stray.  SK_E_ARG when r's members or a member's nbits differ from what set_recurrence returned, when the devices differ or
+ *   the sample is out of range.
+ *   sk_distinct_recurrence: the two tables of a hit list of (sample, key) pairs, one member: hist[nsamples + 1] with entry 0 left 0
+ *   (the list does not say how many keys there are), pairs NULL or [nsamples x nsamples].  Keys must not be 0xFFFFFFFFFFFFFFFF; the
+ *   engine's limits and refusals. */
+#define SK_RECUR_SAMPLES_MAX 4096u
+#define SK_RECUR_PAIRS_MAX    256u
+#define SK_RECUR_MEMBERS_MAX 65535u
+typedef struct sk_recur sk_recur;
+int  sk_recur_create(sk_ctx *ctx, uint32_t nmembers, const uint32_t *nbits, uint32_t nsamples, sk_recur **out);
+void sk_recur_destroy(sk_recur *r);
+int  sk_recur_mark_bits(sk_recur *r, uint32_t member, uint32_t sample, const uint32_t *bits, uint64_t n);
+int  sk_recur_finish(sk_recur *r, uint64_t *hist /* nmembers x (nsamples + 1) */, uint64_t *pairs /* NULL, or nmembers x nsamples x nsamples */);
+int  sk_covacc_set_recurrence(sk_covacc *a, uint32_t member, sk_ctx *ctx, uint32_t type_col, uint32_t informative_value,
+                              uint32_t *out_informative);
+int  sk_covacc_mark_target(sk_covacc *a, sk_recur *r, uint32_t sample, uint64_t *out_stray);
+int  sk_distinct_recurrence(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, uint64_t n, uint32_t nsamples,
+                            uint64_t *hist /* nsamples + 1; entry 0 is left 0 */, uint64_t *pairs /* NULL or nsamples^2 */);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
  * same stdout bytes and exit status.  New: --spectrum[=FILE] [--spectrum-max D] also writes the depth spectrum (above) to FILE,
  * default the hits file's path with a trailing ".kmer_hits.gz" removed plus ".coverage_spectrum"; stdout is unchanged.  A hit list
- * in the general (non-ACGT text) mode is refused. */
+ * in the general (non-ACGT text) mode is refused.  New: --recurrence[=FILE] [--recurrence-pairs[=FILE]] also writes the recurrence
+ * tables (above), default paths with ".coverage_recurrence" and ".coverage_recurrence_pairs", under the same conditions. */
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err);
 
 #ifdef __cplusplus

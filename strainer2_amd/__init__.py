@@ -12,6 +12,9 @@ from .native import (  # noqa: F401
     KmerContext,
     KmerUnion,
     CoverageAcc,
+    Recurrence,
+    SK_RECUR_SAMPLES_MAX,
+    SK_RECUR_PAIRS_MAX,
     Keyset,
     lib,
     library_path,
@@ -20,5 +23,5 @@ from .native import (  # noqa: F401
     run_cli_inprocess,
 )
 
-__all__ = ["SKError", "KmerContext", "KmerUnion", "CoverageAcc", "Keyset", "lib", "library_path", "cli_path", "decode_file",
+__all__ = ["SKError", "KmerContext", "KmerUnion", "CoverageAcc", "Recurrence", "SK_RECUR_SAMPLES_MAX", "SK_RECUR_PAIRS_MAX", "Keyset", "lib", "library_path", "cli_path", "decode_file",
            "run_cli_inprocess"]

@@ -13,6 +13,8 @@
 // covacc_finish sweeps depth[] once per target: non-zero rows, their sum, and zeros left behind.  covacc_finish_regions is the same
 // sweep with every non-zero row also added to the pair of its region of the strain's genome (strain_detect --coverage-regions).
 // covacc_finish_spectrum is either of them with every non-zero row also counted in the bin of its depth (--coverage-spectrum).
+// covacc_mark is a pass of its own in front of any of the three (recurrence: sk_recur.hip has the planes): it reads the counters and
+// changes none, so a run that never marks launches exactly the sweeps it launched before.
 // Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -305,6 +307,87 @@ __global__ void __launch_bounds__(256) covacc_finish_spectrum(uint32_t *__restri
             if (b_unq[b]) { atomicAdd(ro + 2ull * b, (unsigned long long)b_unq[b]); atomicAdd(ro + 2ull * b + 1ull, b_tot[b]); }
 }
 
+// ---- recurrence: each informative row's bit, and the pass that sets the bits of a target's non-zero rows ----
+// irank[row] = the row's rank among its member's informative rows, 0xFFFFFFFF for every other row: an exclusive prefix count over the
+// member's rows as a block scan in three small kernels -- the informative rows of each block of 256, an exclusive scan of the blocks'
+// counts by one workgroup, and each row's rank within its block on top of its block's.
+__device__ __forceinline__ uint32_t cov_block_rank(bool f, uint32_t *s_w, uint32_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(f);
+    if (lane == 0u) s_w[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (uint32_t w = 0; w < 4u; w++) { if (w < wave) before += s_w[w]; all += s_w[w]; }
+    *total = all;
+    return before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+}
+
+__global__ void __launch_bounds__(256) covacc_rank_count(const uint32_t *__restrict__ type, uint32_t n, uint32_t value, uint32_t *__restrict__ blk)
+{
+    __shared__ uint32_t s_w[4];
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint32_t total;
+    (void)cov_block_rank(i < n && type[i] == value, s_w, &total);
+    if (threadIdx.x == 0u) blk[blockIdx.x] = total;
+}
+
+// one workgroup: blk[] becomes its exclusive prefix sums, blk[nblk] the total
+__global__ void __launch_bounds__(256) covacc_rank_scan(uint32_t *__restrict__ blk, uint32_t nblk)
+{
+    __shared__ uint32_t s[256];
+    __shared__ uint32_t carry;
+    if (threadIdx.x == 0u) carry = 0u;
+    __syncthreads();
+    for (uint32_t b0 = 0; b0 < nblk; b0 += 256u) {
+        const uint32_t i = b0 + threadIdx.x, v = i < nblk ? blk[i] : 0u;
+        s[threadIdx.x] = v;
+        __syncthreads();
+        for (uint32_t d = 1u; d < 256u; d <<= 1) {
+            const uint32_t t = threadIdx.x >= d ? s[threadIdx.x - d] : 0u;
+            __syncthreads();
+            s[threadIdx.x] += t;
+            __syncthreads();
+        }
+        if (i < nblk) blk[i] = carry + s[threadIdx.x] - v;
+        __syncthreads();
+        if (threadIdx.x == 0u) carry += s[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u) blk[nblk] = carry;
+}
+
+__global__ void __launch_bounds__(256) covacc_rank_write(const uint32_t *__restrict__ type, uint32_t n, uint32_t value,
+                                                         const uint32_t *__restrict__ blk, uint32_t *__restrict__ irank)
+{
+    __shared__ uint32_t s_w[4];
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const bool f = i < n && type[i] == value;
+    uint32_t total;
+    const uint32_t r = cov_block_rank(f, s_w, &total);
+    if (i < n) irank[i] = f ? blk[blockIdx.x] + r : 0xFFFFFFFFu;
+}
+
+// blockIdx.y = member: every row with a non-zero counter sets its bit of plane[word_base[m] ..]; a non-zero row whose rank is not
+// below the member's nbits (0xFFFFFFFF: not informative) sets nothing and is counted.  The counters are only read.
+__global__ void __launch_bounds__(256) covacc_mark(const uint32_t *__restrict__ depth, const uint64_t *__restrict__ row_base,
+                                                   const uint32_t *__restrict__ nrows, const uint32_t *__restrict__ irank,
+                                                   const uint32_t *__restrict__ nbits, const uint64_t *__restrict__ word_base,
+                                                   unsigned long long *__restrict__ plane, unsigned long long *__restrict__ stray)
+{
+    const uint32_t m = blockIdx.y, n = nrows[m], nb = nbits[m];
+    const uint32_t *d = depth + row_base[m], *rk = irank + row_base[m];
+    unsigned long long *p = plane + word_base[m];
+    uint32_t bad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        if (!d[i]) continue;
+        const uint32_t b = rk[i];
+        if (b < nb) atomicOr(p + (b >> 6), 1ull << (b & 63u));
+        else bad++;
+    }
+    if (bad) atomicAdd(stray, (unsigned long long)bad);      // (never in the programs: only informative rows are logged)
+}
+
 struct sk_covacc {
     sk_ctx *ctx; int device;
     hipStream_t stream;
@@ -329,7 +412,12 @@ struct sk_covacc {
     // the depth spectrum: off (spec_d = 0) until sk_covacc_set_spectrum
     uint32_t spec_d; void *d_spec; size_t spec_cap;         // [nm x (spec_d + 1)] bins, then [nm] deep sums
     // device time of the folds and of the targets' sweeps, kept only when somebody asked (sk_covacc_timing_)
-    bool timed; hipEvent_t ev0, ev1; double ms_fold, ms_sweep;
+    bool timed; hipEvent_t ev0, ev1; double ms_fold, ms_sweep, ms_mark;
+    // recurrence: nothing of it exists until sk_covacc_set_recurrence is called
+    uint32_t *d_irank;                                      // [total_rows] each row's bit of its member's planes, 0xFFFFFFFF: none
+    std::vector<uint32_t> rec_nbits; uint32_t *d_rec_nbits; // [nm] informative rows per member (0: never set)
+    void *d_blk; size_t blk_cap;                            // set_recurrence's scratch: the blocks' counts
+    unsigned long long *d_stray;
 };
 
 static void cov_t0(sk_covacc *a) { if (a->timed) (void)hipEventRecord(a->ev0, a->stream); }
@@ -351,6 +439,12 @@ extern "C" int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *
     }
     if (ms_fold) *ms_fold = a->ms_fold;
     if (ms_sweep) *ms_sweep = a->ms_sweep;
+    return SK_OK;
+}
+extern "C" int sk_covacc_mark_timing_(sk_covacc *a, double *ms_mark)
+{
+    if (!a || !ms_mark) return SK_E_ARG;
+    *ms_mark = a->ms_mark;
     return SK_OK;
 }
 
@@ -379,6 +473,7 @@ extern "C" void sk_covacc_destroy(sk_covacc *a)
     (void)hipFree(a->p_recs); (void)hipFree(a->p_hits); (void)hipFree(a->p_cnt);
     (void)hipFree(a->d_region); (void)hipFree(a->d_nreg); (void)hipFree(a->d_reg_base); (void)hipFree(a->d_reg_out);
     (void)hipFree(a->d_fp); (void)hipFree(a->d_starts); (void)hipFree(a->d_spec);
+    (void)hipFree(a->d_irank); (void)hipFree(a->d_rec_nbits); (void)hipFree(a->d_blk); (void)hipFree(a->d_stray);
     if (a->timed) { (void)hipEventDestroy(a->ev0); (void)hipEventDestroy(a->ev1); }
     if (a->h_bad) (void)hipHostFree(a->h_bad);
     if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -765,5 +860,78 @@ extern "C" int sk_covacc_finish_target_spectrum(sk_covacc *a, uint64_t *out_uniq
     for (uint32_t m = 0; m < a->nm; m++) { out_unique[m] = h[2u * m]; out_total[m] = h[2u * m + 1u]; deep_total[m] = hs[nspec + m]; }
     for (size_t i = 0; i < nspec; i++) spec[i] = hs[i];
     for (uint64_t r = 0; regions && r < a->total_bins; r++) { reg_unique[r] = hr[2u * r]; reg_total[r] = hr[2u * r + 1u]; }
+    return SK_OK;
+}
+
+// ---- recurrence ----
+extern "C" int sk_covacc_set_recurrence(sk_covacc *a, uint32_t member, sk_ctx *ctx, uint32_t type_col, uint32_t informative_value,
+                                        uint32_t *out_informative)
+{
+    if (!a || !ctx || !out_informative) return SK_E_ARG;
+    int rc = cov_member_ctx(a, member, ctx);
+    if (rc != SK_OK) return rc;
+    CA_HIP(hipSetDevice(a->device));
+    if (!a->d_irank) {                                    // all ones: a member never set has no informative row
+        const size_t bytes = (size_t)(a->total_rows ? a->total_rows : 1u) * 4u;
+        uint32_t *p = NULL, *q = NULL; unsigned long long *st = NULL;
+        CA_HIP(hipMalloc((void **)&p, bytes));
+        if (hipMalloc((void **)&q, (size_t)a->nm * 4u) != hipSuccess || hipMalloc((void **)&st, 8u) != hipSuccess) {
+            (void)hipFree(p); (void)hipFree(q);
+            return sk_fail_(a->ctx, SK_E_HIP, "no room for the rank map");
+        }
+        a->d_irank = p; a->d_rec_nbits = q; a->d_stray = st;
+        a->rec_nbits.assign(a->nm, 0u);
+        CA_HIP(hipMemsetAsync(a->d_irank, 0xFF, bytes, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_rec_nbits, 0, (size_t)a->nm * 4u, a->stream));
+    }
+    const uint32_t n = a->nrows[member];
+    uint32_t inf = 0;
+    if (n) {
+        const uint32_t nblk = (uint32_t)(((uint64_t)n + 255u) / 256u);
+        if ((rc = cov_room(a, &a->d_fp, &a->fp_cap, (size_t)n * 4u, false)) != SK_OK) return rc;
+        if ((rc = cov_room(a, &a->d_blk, &a->blk_cap, ((size_t)nblk + 1u) * 4u, false)) != SK_OK) return rc;
+        rc = sk_counts_rows_to_device_(ctx, type_col, (uint32_t *)a->d_fp);   // (the column in the caller's row order; complete on return)
+        if (rc != SK_OK) return sk_fail_(a->ctx, rc, "%s", sk_last_error(ctx));
+        hipLaunchKernelGGL(covacc_rank_count, dim3(nblk), dim3(256), 0, a->stream, (const uint32_t *)a->d_fp, n, informative_value,
+                           (uint32_t *)a->d_blk);
+        hipLaunchKernelGGL(covacc_rank_scan, dim3(1), dim3(256), 0, a->stream, (uint32_t *)a->d_blk, nblk);
+        hipLaunchKernelGGL(covacc_rank_write, dim3(nblk), dim3(256), 0, a->stream, (const uint32_t *)a->d_fp, n, informative_value,
+                           (const uint32_t *)a->d_blk, a->d_irank + a->base[member]);
+        CA_HIP(hipGetLastError());
+        CA_HIP(hipMemcpyAsync(&inf, (uint32_t *)a->d_blk + nblk, 4u, hipMemcpyDeviceToHost, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+    }
+    a->rec_nbits[member] = inf;
+    CA_HIP(hipMemcpy(a->d_rec_nbits + member, &inf, 4u, hipMemcpyHostToDevice));
+    *out_informative = inf;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_mark_target(sk_covacc *a, sk_recur *r, uint32_t sample, uint64_t *out_stray)
+{
+    if (!a || !r || !out_stray) return SK_E_ARG;
+    sk_recur_view v;
+    if (sk_recur_view_(r, &v) != SK_OK) return SK_E_ARG;
+    if (!a->d_irank) return sk_fail_(a->ctx, SK_E_STATE, "no rank map (sk_covacc_set_recurrence)");
+    if (v.device != a->device) return sk_fail_(a->ctx, SK_E_ARG, "the planes are on another device");
+    if (v.nmembers != a->nm) return sk_fail_(a->ctx, SK_E_ARG, "the planes have %u members, the accumulator %u", v.nmembers, a->nm);
+    for (uint32_t m = 0; m < a->nm; m++)
+        if (v.nbits[m] != a->rec_nbits[m])
+            return sk_fail_(a->ctx, SK_E_ARG, "member %u: %u bits in the planes, %u informative rows", m, v.nbits[m], a->rec_nbits[m]);
+    if (sample >= v.nsamples) return sk_fail_(a->ctx, SK_E_ARG, "sample %u: the planes have %u", sample, v.nsamples);
+    CA_HIP(hipSetDevice(a->device));
+    unsigned long long stray = 0;
+    cov_t0(a);
+    CA_HIP(hipMemsetAsync(a->d_stray, 0, 8u, a->stream));
+    unsigned gx = (a->max_rows + 255u) / 256u;
+    gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
+    hipLaunchKernelGGL(covacc_mark, dim3(gx, a->nm), dim3(256), 0, a->stream, (const uint32_t *)a->d_depth, (const uint64_t *)a->d_base,
+                       (const uint32_t *)a->d_nrows, (const uint32_t *)a->d_irank, (const uint32_t *)a->d_rec_nbits, v.d_word_base,
+                       v.d_planes + (size_t)sample * v.words, a->d_stray);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipMemcpyAsync(&stray, a->d_stray, 8u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_mark);
+    *out_stray = stray;
     return SK_OK;
 }

@@ -279,3 +279,72 @@ out:
     (void)hipFree(d_keys); (void)hipFree(d_sample); (void)hipFree(d_seg); (void)hipFree(d_table); (void)hipFree(d_cnt); (void)hipFree(d_out);
     return rc;
 }
+
+// ---- recurrence of a hit list (include/strainer_kmer.h has the rule; coverage_depth --recurrence) ----
+// All samples share ONE open-addressed set here (cov_count gives every sample a segment of its own): a key's slot number is its bit,
+// the same in every sample's plane.  cov_count's insert, then one atomicOr into the lane's sample's plane of the engine
+// (sk_recur.hip), whose two sweeps then run over one member of nslots bits.
+__global__ void cov_recur_insert(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ sample, uint64_t n, uint32_t nsamples,
+                                 uint64_t mask, unsigned long long *__restrict__ table, unsigned long long *__restrict__ planes, uint64_t words)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t s = sample[i];
+        if (s >= nsamples) continue;                          // (never: the host has checked)
+        const uint64_t k = keys[i];
+        uint64_t slot = cov_mix(k) & mask;
+        for (;;) {
+            const unsigned long long old = atomicCAS(&table[slot], COV_EMPTY, (unsigned long long)k);
+            if (old == COV_EMPTY || old == k) break;
+            slot = (slot + 1) & mask;
+        }
+        atomicOr(planes + (uint64_t)s * words + (slot >> 6), 1ull << (slot & 63u));   // (slot <= mask < nbits = 64 * words)
+    }
+}
+
+extern "C" int sk_distinct_recurrence(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, uint64_t n, uint32_t nsamples,
+                                      uint64_t *hist, uint64_t *pairs)
+{
+    if (!ctx || !hist || (n && (!keys || !sample))) return SK_E_ARG;
+    if (nsamples < 1u || nsamples > SK_RECUR_SAMPLES_MAX) return sk_fail_(ctx, SK_E_ARG, "%u samples: from 1 to %u", nsamples, SK_RECUR_SAMPLES_MAX);
+    if (pairs && nsamples > SK_RECUR_PAIRS_MAX) return sk_fail_(ctx, SK_E_ARG, "%u samples: the pair table takes at most %u", nsamples, SK_RECUR_PAIRS_MAX);
+    if (n > (1ull << 30)) return sk_fail_(ctx, SK_E_ARG, "too many hits for one key set");
+    for (uint64_t i = 0; i < n; i++) {
+        if (sample[i] >= nsamples) return sk_fail_(ctx, SK_E_ARG, "sample %u out of range", sample[i]);
+        if (keys[i] == COV_EMPTY) return sk_fail_(ctx, SK_E_ARG, "reserved key value");
+    }
+    memset(hist, 0, ((size_t)nsamples + 1u) * 8);
+    if (pairs) memset(pairs, 0, (size_t)nsamples * nsamples * 8);
+    if (!n) return SK_OK;
+    uint64_t slots = 64;                                      // next power of two >= 2 n, whole words
+    while (slots < 2 * n) slots <<= 1;
+    const uint32_t nbits = (uint32_t)slots;
+    sk_recur *r = NULL;
+    sk_recur_view v;
+    int rc = sk_recur_create(ctx, 1u, &nbits, nsamples, &r);
+    if (rc != SK_OK) return rc;
+    void *d_keys = NULL, *d_sample = NULL, *d_table = NULL;
+#define COV_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = sk_fail_(ctx, SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); goto out; } } while (0)
+    if ((rc = sk_recur_view_(r, &v)) != SK_OK) goto out;
+    COV_HIP(hipSetDevice(sk_ctx_device_(ctx)));
+    COV_HIP(hipMalloc(&d_keys, n * 8));
+    COV_HIP(hipMalloc(&d_sample, n * 4));
+    COV_HIP(hipMalloc(&d_table, slots * 8));
+    COV_HIP(hipMemcpy(d_keys, keys, n * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_sample, sample, n * 4, hipMemcpyHostToDevice));
+    COV_HIP(hipMemset(d_table, 0xFF, slots * 8));
+    {
+        const uint64_t g = (n + 255) / 256;
+        hipLaunchKernelGGL(cov_recur_insert, dim3((unsigned)(g > 65536u ? 65536u : g)), dim3(256), 0, 0, (const uint64_t *)d_keys,
+                           (const uint32_t *)d_sample, n, nsamples, slots - 1, (unsigned long long *)d_table, v.d_planes, v.words);
+    }
+    COV_HIP(hipGetLastError());
+    COV_HIP(hipStreamSynchronize(0));
+    rc = sk_recur_finish(r, hist, pairs);
+    hist[0] = 0;                                              // (the engine's "never set" counts empty slots here)
+#undef COV_HIP
+out:
+    (void)hipFree(d_keys); (void)hipFree(d_sample); (void)hipFree(d_table);
+    sk_recur_destroy(r);
+    return rc;
+}

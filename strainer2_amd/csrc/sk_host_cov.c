@@ -107,6 +107,8 @@ typedef struct {
     uint64_t *given_u, *given_t; uint32_t ngiven; int given;   /* counts handed in per sample (skc_add_counts) instead of hits */
     uint64_t **reg_u, **reg_t; uint32_t nreg_s, reg_bins;      /* ... and per sample and region (skc_add_region_counts): reg_bins each, or NULL */
     uint64_t **sp_n, *sp_deep; uint32_t nsp_s, sp_bins;        /* the depth spectrum per sample: n[1..D], n[>D] (sp_bins = D + 1 each, or NULL) and hits[>D] */
+    uint64_t *rc_hist, *rc_pairs; uint32_t *rc_smp, rc_T;      /* recurrence handed in (skc_add_recurrence_counts): n[0..T] (entry 0 unused), shared[T x T] or NULL,
+                                                                  both by the caller's sample ordinals; rc_smp[ordinal] = the sample */
 } hitlist;
 
 enum { COV_OK = 0, COV_OPEN, COV_FIELDS, COV_INT, COV_NOMEM };
@@ -423,6 +425,7 @@ static void hitlist_free(hitlist *h)
     for (s = 0; s < h->nsp_s; s++) free(h->sp_n[s]);
     free(h->sp_n); free(h->sp_deep);
     free(h->given_u); free(h->given_t);
+    free(h->rc_hist); free(h->rc_pairs); free(h->rc_smp);
     free(h->key); free(h->sample); free(h->depth_order); free(h->eval_order); free(h->gid); free(h->gsample);
     names_free(&h->smp); names_free(&h->text);
     memset(h, 0, sizeof *h);
@@ -667,7 +670,184 @@ int skc_report_spectrum(skc_acc *a, const char *hits_file_name, uint32_t max_dep
     return 0;
 }
 
-/* (the host-only test builds link this file without sk_cover.hip's newer entry point: without it --spectrum is refused) */
+/* ---- recurrence (strain_detect --coverage-recurrence, coverage_depth --recurrence; include/strainer_kmer.h has the rule) ---- */
+/* a run's tables, counted elsewhere: T samples by the caller's ordinals (metagenome[i] names ordinal i; every one of them has been
+ * handed to skc_add_counts or skc_add_trailer, so the sample exists), hist[T + 1] (entry 0 is not used) and pairs[T x T] or NULL.
+ * Once per accumulator. */
+int skc_add_recurrence_counts(skc_acc *a, const char *const *metagenome, uint32_t T, const uint64_t *hist, const uint64_t *pairs)
+{
+    hitlist *h = &a->h;
+    uint32_t i;
+    if (h->rc_hist || !T) return -1;
+    if (!(h->rc_hist = malloc(((size_t)T + 1u) * sizeof *h->rc_hist)) || !(h->rc_smp = malloc((size_t)T * sizeof *h->rc_smp))) return -1;
+    if (pairs && !(h->rc_pairs = malloc((size_t)T * T * sizeof *h->rc_pairs))) return -1;
+    memcpy(h->rc_hist, hist, ((size_t)T + 1u) * sizeof *hist);
+    if (pairs) memcpy(h->rc_pairs, pairs, (size_t)T * T * sizeof *pairs);
+    for (i = 0; i < T; i++) {
+        const char *sn = base_of(metagenome[i], metagenome[i] + strlen(metagenome[i]));
+        const int64_t g = name_get(&h->smp, sn, strlen(sn));
+        if (g < 0) return -1;
+        h->rc_smp[i] = (uint32_t)g;
+    }
+    h->rc_T = T;
+    return 0;
+}
+
+/* both tables of hist[T + 1] (entry 0 is computed here) and shared[T x T] by position in the main table's order (NULL: no pair table) */
+static void recurrence_print(const hitlist *h, const char *hits_file_name, uint32_t T, const uint64_t *hist, const uint64_t *shared,
+                             FILE *out, FILE *out_pairs)
+{
+    char *strain = strdup(base_of(hits_file_name, hits_file_name + strlen(hits_file_name)));
+    const size_t sl = strain ? strlen(strain) : 0;
+    const char *nm;
+    uint64_t seen = 0;
+    uint32_t k, m, i, j;
+    if (sl >= 13 && !memcmp(strain + sl - 12, "kmer_hits", 9) && !memcmp(strain + sl - 2, "gz", 2)) strain[sl - 13] = 0;
+    nm = strain ? strain : "";
+    fputs("strain_name\tsamples\tseen_in\tinformative_kmers\n", out);
+    for (m = 1; m <= T; m++) seen += hist[m];
+    for (k = 0; k < h->ndepth; k++)                  /* I: the trailer of the first sample of the table that has one */
+        if (h->smp.have_inf[h->depth_order[k]]) {
+            fprintf(out, "%s\t%u\t0\t%lld\n", nm, T, (long long)(h->smp.g_inf[h->depth_order[k]] - (int64_t)seen));
+            break;
+        }
+    for (m = 1; m <= T; m++)
+        if (hist[m]) fprintf(out, "%s\t%u\t%u\t%llu\n", nm, T, m, (unsigned long long)hist[m]);
+    fflush(out);
+    if (out_pairs && (shared || !T)) {
+        fputs("strain_name\tmetagenome_a\tmetagenome_b\tshared_informative_kmers\teither_informative_kmers\n", out_pairs);
+        for (i = 0; i < T; i++)
+            for (j = i; j < T; j++) {
+                const uint64_t sh = shared[(size_t)i * T + j];
+                fprintf(out_pairs, "%s\t%s\t%s\t%llu\t%llu\n", nm, h->smp.name[h->depth_order[i]], h->smp.name[h->depth_order[j]],
+                        (unsigned long long)sh, (unsigned long long)(shared[(size_t)i * T + i] + shared[(size_t)j * T + j] - sh));
+            }
+        fflush(out_pairs);
+    }
+    free(strain);
+}
+
+typedef struct { uint64_t key; uint32_t pos; } rc_item;
+static int cmp_rc_item(const void *x, const void *y)
+{
+    const rc_item *a = x, *b = y;
+    return a->key < b->key ? -1 : a->key > b->key ? 1 : a->pos < b->pos ? -1 : a->pos > b->pos;
+}
+
+/* the fold of a (sample, key) list: pos_of[sample] = its position among T, hist[T + 1] and shared[T x T] (NULL: not wanted) zeroed
+ * by the caller.  Sort by key, then position; a key's distinct positions give its m and its pairs. */
+static int recurrence_fold(const uint64_t *key, const uint32_t *sample, uint64_t n, const uint32_t *pos_of, uint32_t T, uint64_t *hist,
+                           uint64_t *shared)
+{
+    rc_item *v;
+    uint32_t *at;
+    uint64_t i, j;
+    if (!n) return 0;
+    if (!(v = malloc((size_t)n * sizeof *v))) return -1;
+    if (!(at = malloc(((size_t)T + 1u) * sizeof *at))) { free(v); return -1; }
+    for (i = 0; i < n; i++) { v[i].key = key[i]; v[i].pos = pos_of[sample[i]]; }
+    qsort(v, (size_t)n, sizeof *v, cmp_rc_item);
+    for (i = 0; i < n; i = j) {
+        uint32_t m = 0, x, y;
+        for (j = i; j < n && v[j].key == v[i].key; j++)
+            if (v[j].pos < T && (!m || at[m - 1] != v[j].pos)) at[m++] = v[j].pos;
+        hist[m]++;
+        for (x = 0; shared && x < m; x++)
+            for (y = x; y < m; y++) {
+                shared[(size_t)at[x] * T + at[y]]++;
+                if (x != y) shared[(size_t)at[y] * T + at[x]]++;
+            }
+    }
+    hist[0] = 0;
+    free(at); free(v);
+    return 0;
+}
+
+/* The tables: call it after skc_report.  T = the samples of the main table, in its order.  An accumulator that was fed hits folds
+ * its (sample, row) list here; one that was fed counts prints what skc_add_recurrence_counts left.  out_pairs NULL: no pair table. */
+int skc_report_recurrence(skc_acc *a, const char *hits_file_name, FILE *out, FILE *out_pairs, FILE *err)
+{
+    hitlist *h = &a->h;
+    uint64_t *hist = NULL, *shared = NULL;
+    uint32_t *pos_of = NULL, T, k, i, j;
+    int status = 1;
+    if (cov_order_trailers(h)) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+    T = h->ndepth;
+    if (T > SK_RECUR_SAMPLES_MAX || (out_pairs && T > SK_RECUR_PAIRS_MAX)) {
+        fprintf(err, "coverage_depth: %u samples: recurrence takes at most %u, its pair table %u\n", T, SK_RECUR_SAMPLES_MAX, SK_RECUR_PAIRS_MAX);
+        return 1;
+    }
+    if (!(hist = calloc((size_t)T + 1u, sizeof *hist)) || !(pos_of = malloc(((size_t)h->smp.n + 1u) * sizeof *pos_of)) ||
+        (out_pairs && !(shared = calloc((size_t)T * T + 1u, sizeof *shared)))) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+    for (k = 0; k < h->smp.n; k++) pos_of[k] = T;    /* (a sample outside the table: never) */
+    for (k = 0; k < T; k++) pos_of[h->depth_order[k]] = k;
+    if (h->rc_hist) {
+        if (h->rc_T != T || (out_pairs && !h->rc_pairs)) { fprintf(err, "coverage_depth: the recurrence counts are of %u samples, the table has %u\n", h->rc_T, T); goto done; }
+        memcpy(hist, h->rc_hist, ((size_t)T + 1u) * sizeof *hist);
+        for (i = 0; out_pairs && i < T; i++)
+            for (j = 0; j < T; j++) {
+                const uint32_t pi = pos_of[h->rc_smp[i]], pj = pos_of[h->rc_smp[j]];
+                if (pi < T && pj < T) shared[(size_t)pi * T + pj] = h->rc_pairs[(size_t)i * T + j];
+            }
+    } else if (!h->given && recurrence_fold(h->key, h->sample, h->n, pos_of, T, hist, shared)) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+    recurrence_print(h, hits_file_name, T, hist, shared, out, out_pairs);
+    status = 0;
+done:
+    free(hist); free(shared); free(pos_of);
+    return status;
+}
+
+/* (the host-only test builds link this file without sk_cover.hip's newer entry points: without them --spectrum / --recurrence are refused) */
+#pragma weak sk_distinct_recurrence
+/* coverage_depth --recurrence [--recurrence-pairs]: the (sample, packed k-mer) pairs through the device's bit planes, to the tables
+ * at `path` and `pairs_path` (NULL: no pair table) */
+static int cov_recurrence_files(hitlist *h, sk_ctx *ctx, const char *kfile, const char *path, const char *pairs_path, FILE *err)
+{
+    const uint32_t T = h->ndepth;
+    uint64_t *hist = NULL, *shared = NULL, i;
+    uint32_t *pos_of = NULL, *smp = NULL, k;
+    FILE *f = NULL, *fp = NULL;
+    int rc, status = 1;
+    if (T > SK_RECUR_SAMPLES_MAX || (pairs_path && T > SK_RECUR_PAIRS_MAX)) {
+        fprintf(err, "coverage_depth: %u samples: --recurrence takes at most %u, --recurrence-pairs %u\n", T, SK_RECUR_SAMPLES_MAX, SK_RECUR_PAIRS_MAX);
+        return 1;
+    }
+    if (!(hist = calloc((size_t)T + 1u, sizeof *hist)) || !(pos_of = malloc(((size_t)h->smp.n + 1u) * sizeof *pos_of)) ||
+        !(smp = malloc(((size_t)h->n + 1u) * sizeof *smp)) || (pairs_path && !(shared = calloc((size_t)T * T + 1u, sizeof *shared)))) {
+        fprintf(err, "coverage_depth: out of memory\n");
+        goto done;
+    }
+    for (k = 0; k < h->smp.n; k++) pos_of[k] = 0;
+    for (k = 0; k < T; k++) pos_of[h->depth_order[k]] = k;   /* (every sample of a passing line is in the table) */
+    for (i = 0; i < h->n; i++) smp[i] = pos_of[h->sample[i]];
+    if (T) {
+        rc = sk_distinct_recurrence(ctx, h->key, smp, h->n, T, hist, shared);
+        if (rc != SK_OK) { fprintf(err, "coverage_depth: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx)); goto done; }
+    }
+    if (!(f = fopen(path, "w"))) { fprintf(err, "coverage_depth: could not write %s\n", path); goto done; }
+    if (pairs_path && !(fp = fopen(pairs_path, "w"))) { fprintf(err, "coverage_depth: could not write %s\n", pairs_path); goto done; }
+    recurrence_print(h, kfile, T, hist, shared, f, fp);
+    status = ferror(f) || (fp && ferror(fp)) ? 1 : 0;
+done:
+    if (f && fclose(f)) status = 1;
+    if (fp && fclose(fp)) status = 1;
+    free(hist); free(shared); free(pos_of); free(smp);
+    return status;
+}
+
+/* where a table goes: the explicit name, or the hits file's path with a trailing ".kmer_hits.gz" replaced by `suffix` */
+static char *cov_table_path(const char *explicit_path, const char *kfile, const char *suffix)
+{
+    char *p;
+    size_t n = strlen(kfile);
+    if (explicit_path && *explicit_path) return strdup(explicit_path);
+    if (!(p = malloc(n + strlen(suffix) + 1))) return NULL;
+    strcpy(p, kfile);
+    if (n >= 13 && !strcmp(p + n - 13, ".kmer_hits.gz")) p[n - 13] = 0;
+    strcat(p, suffix);
+    return p;
+}
+
 #pragma weak sk_distinct_spectrum
 /* coverage_depth --spectrum: the multiplicities of the (sample, packed k-mer) pairs, counted on the device, to the table at `path` */
 static int cov_spectrum_file(hitlist *h, sk_ctx *ctx, const char *kfile, uint32_t max_depth, const char *path, FILE *err)
@@ -700,21 +880,24 @@ done:
 
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
 {
-    const char *kfile = NULL, *mtext = NULL, *bfile = NULL, *env, *sp_file = NULL, *sp_max = NULL;
+    const char *kfile = NULL, *mtext = NULL, *bfile = NULL, *env, *sp_file = NULL, *sp_max = NULL, *rc_file = NULL, *rp_file = NULL;
     int64_t min_hits = 1, sp_d = 255;
-    int i, bad = 0, rc, status = 1, device = 0, want_sp = 0;
-    char *sp_path = NULL;
+    int i, bad = 0, rc, status = 1, device = 0, want_sp = 0, want_rc = 0, want_rp = 0;
+    char *sp_path = NULL, *rc_path = NULL, *rp_path = NULL;
     hitlist h;
     sk_ctx *ctx = NULL;
 
     for (i = 1; i < argc; i++) {                     /* :27-41 */
         if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
             fprintf(out, "usage: coverage_depth [-h] --kmer_hits_file FILE [--min_kmer_hits N] [--background_metagenomes_file FILE]\n"
-                         "                      [--spectrum[=FILE] [--spectrum-max D]]\n");
+                         "                      [--spectrum[=FILE] [--spectrum-max D]] [--recurrence[=FILE] [--recurrence-pairs[=FILE]]]\n");
             return 0;
         }
         /* "--spectrum[=FILE] [--spectrum-max D]" (extension): the depth spectrum beside the table, see include/strainer_kmer.h */
         if (!strncmp(argv[i], "--spectrum", 10) && (argv[i][10] == 0 || argv[i][10] == '=')) { want_sp = 1; sp_file = argv[i][10] ? argv[i] + 11 : NULL; continue; }
+        /* "--recurrence[=FILE] [--recurrence-pairs[=FILE]]" (extension): in how many samples each k-mer was seen, and what two samples share */
+        if (!strncmp(argv[i], "--recurrence-pairs", 18) && (argv[i][18] == 0 || argv[i][18] == '=')) { want_rp = 1; rp_file = argv[i][18] ? argv[i] + 19 : NULL; continue; }
+        if (!strncmp(argv[i], "--recurrence", 12) && (argv[i][12] == 0 || argv[i][12] == '=')) { want_rc = 1; rc_file = argv[i][12] ? argv[i] + 13 : NULL; continue; }
         if (!strcmp(argv[i], "--spectrum-max") && i + 1 < argc) { sp_max = argv[++i]; continue; }
         if (!strncmp(argv[i], "--spectrum-max=", 15)) { sp_max = argv[i] + 15; continue; }
         if (cov_opt(argc, argv, &i, "-k", "--kmer_hits_file", &kfile, err, &bad)) { if (bad) return 2; continue; }
@@ -734,6 +917,8 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         return 2;
     }
     if (want_sp && !sk_distinct_spectrum) { fprintf(err, "coverage_depth: error: --spectrum: this build has no device spectrum\n"); return 2; }
+    if (want_rp && !want_rc) { fprintf(err, "coverage_depth: error: --recurrence-pairs goes with --recurrence\n"); return 2; }
+    if (want_rc && !sk_distinct_recurrence) { fprintf(err, "coverage_depth: error: --recurrence: this build has no device recurrence\n"); return 2; }
     memset(&h, 0, sizeof h);
     rc = read_hits(&h, kfile, min_hits);
     if (rc == COV_OPEN) { fprintf(err, "coverage_depth: could not read %s\n", kfile); goto done; }
@@ -744,6 +929,12 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         fprintf(err, "coverage_depth: --spectrum: %s has k-mer fields that are not A/C/G/T words of one length: the depth of a k-mer is not defined there\n", kfile);
         goto done;
     }
+    if (want_rc && h.general) {
+        fprintf(err, "coverage_depth: --recurrence: %s has k-mer fields that are not A/C/G/T words of one length: a k-mer seen in two samples is not defined there\n", kfile);
+        goto done;
+    }
+    if (want_rc && (!(rc_path = cov_table_path(rc_file, kfile, ".coverage_recurrence")) ||
+                    (want_rp && !(rp_path = cov_table_path(rp_file, kfile, ".coverage_recurrence_pairs"))))) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
     if (want_sp) {
         if (sp_file && *sp_file) sp_path = strdup(sp_file);
         else if ((sp_path = malloc(strlen(kfile) + 32)) != NULL) {
@@ -759,9 +950,10 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
     if (rc != SK_OK) { fprintf(err, "coverage_depth: cannot use HIP device %d: %s\n", device, sk_strerror(rc)); goto done; }
     status = cov_report(&h, ctx, kfile, bfile, out, err);
     if (status == 0 && want_sp) status = cov_spectrum_file(&h, ctx, kfile, (uint32_t)sp_d, sp_path, err);
+    if (status == 0 && want_rc) status = cov_recurrence_files(&h, ctx, kfile, rc_path, rp_path, err);
 done:
     fflush(out);
-    free(sp_path);
+    free(sp_path); free(rc_path); free(rp_path);
     sk_ctx_destroy(ctx);
     hitlist_free(&h);
     return status;

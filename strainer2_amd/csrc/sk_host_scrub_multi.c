@@ -295,7 +295,7 @@ static char *sm_cov_path(const char *hits)
 static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
 {
     char **v = (char **)malloc(((size_t)argc + 1) * sizeof *v);
-    int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0;
+    int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0, want_rc = 0, want_rp = 0;
     if (!v) return 1;
     for (c = 0; c < argc; c++) {
         if (c > 0 && !strncmp(argv[c], "--coverage-depth", 16) && (argv[c][16] == 0 || argv[c][16] == '=')) {
@@ -336,6 +336,24 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
             want_sp = 1;
             continue;
         }
+        if (c > 0 && !strncmp(argv[c], "--coverage-recurrence", 21) && (argv[c][21] == 0 || argv[c][21] == '=')) {
+            if (argv[c][21] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-recurrence takes no file name (each strain's table goes next to its coverage table)\n");
+                free(v);
+                return 1;
+            }
+            want_rc = 1;
+            continue;
+        }
+        if (c > 0 && !strncmp(argv[c], "--recurrence-pairs", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            if (argv[c][18] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --recurrence-pairs takes no file name (each strain's table goes next to its coverage table)\n");
+                free(v);
+                return 1;
+            }
+            want_rp = 1;
+            continue;
+        }
         if (c > 0 && !strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { c++; continue; }
         if (c > 0 && !strncmp(argv[c], "--spectrum-max=", 15)) continue;
         if (c > 0 && !strncmp(argv[c], "--panel-share", 13) && (argv[c][13] == 0 || argv[c][13] == '=')) {
@@ -362,6 +380,16 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
     }
     if (want_sp && !*want_cov) {
         fprintf(err, "kmer_scrub_count: --coverage-spectrum goes with --coverage-depth or --coverage-only: it bins their table's hits by depth\n");
+        free(v);
+        return 1;
+    }
+    if (want_rp && !want_rc) {
+        fprintf(err, "kmer_scrub_count: --recurrence-pairs goes with --coverage-recurrence\n");
+        free(v);
+        return 1;
+    }
+    if (want_rc && !*want_cov) {
+        fprintf(err, "kmer_scrub_count: --coverage-recurrence goes with --coverage-depth or --coverage-only: it follows their table's k-mers over the samples\n");
         free(v);
         return 1;
     }

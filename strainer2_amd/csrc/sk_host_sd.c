@@ -95,6 +95,7 @@ typedef struct {
     /* --coverage-regions: the strain's region table, every row's region (rg.n = unplaced), informative rows per region, the table's path */
     skh_regions rg; uint32_t *row_region; uint64_t *reg_inf; char *rg_path;
     char *sp_path;                             /* --coverage-spectrum: the table's path */
+    char *rc_path, *rp_path;                   /* --coverage-recurrence, --recurrence-pairs: the tables' paths */
 } sd_prog;
 
 /* ---------------------------------------------------------------------------------------------
@@ -1627,6 +1628,25 @@ static void sd_prefetch(sd_stream *st)
 #pragma weak sk_covacc_set_spectrum
 #pragma weak sk_covacc_finish_target_spectrum
 static struct { int on; uint32_t max; } sd_spec;
+/* --coverage-recurrence [--recurrence-pairs] (include/strainer_kmer.h has the rule): with the accumulators on the device every unit
+ * has one set of bit planes (sk_recur) over the run's target lines; the end of a target sets the bits of its non-zero rows
+ * (sk_covacc_mark_target, right before the sweep) and the end of the run takes both tables once (sk_recur_finish) and hands them to
+ * the strains' skc_acc; with --coverage-depth, and where --coverage-only counts on the host, skc_report_recurrence folds the host
+ * accumulator's list. */
+#pragma weak sk_recur_create
+#pragma weak sk_recur_destroy
+#pragma weak sk_recur_finish
+#pragma weak sk_recur_timing_
+#pragma weak sk_covacc_set_recurrence
+#pragma weak sk_covacc_mark_target
+#pragma weak sk_covacc_mark_timing_
+static struct {
+    int on, pairs;
+    uint32_t T;                                 /* the run's target lines */
+    uint32_t next; char **name;                 /* the targets counted so far, and ordinal -> the target's path */
+    sk_recur **r; uint32_t nr;                  /* one per unit, beside sd_co.acc */
+    double ms_mark, ms_hist, ms_gram;           /* SK_SD_TIMING */
+} sd_rec;
 static double sd_co_ms_fold, sd_co_ms_sweep;          /* SK_SD_TIMING: the accumulators' device time, folds and target sweeps */
 static struct {
     int on; uint64_t window;
@@ -1665,8 +1685,17 @@ static void co_close(void)
     for (k = 0; k < sd_co.nacc; k++) {
         double f = 0, w = 0;
         if (sk_covacc_timing_ && sd_co.acc[k] && sk_covacc_timing_(sd_co.acc[k], 0, &f, &w) == SK_OK) { sd_co_ms_fold += f; sd_co_ms_sweep += w; }
+        if (sd_rec.on && sk_covacc_mark_timing_ && sd_co.acc[k] && sk_covacc_mark_timing_(sd_co.acc[k], &f) == SK_OK) sd_rec.ms_mark += f;
         if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
     }
+    for (k = 0; k < sd_rec.nr; k++) {
+        double f = 0, w = 0;
+        if (sk_recur_timing_ && sd_rec.r[k] && sk_recur_timing_(sd_rec.r[k], 0, &f, &w) == SK_OK) { sd_rec.ms_hist += f; sd_rec.ms_gram += w; }
+        if (sk_recur_destroy) sk_recur_destroy(sd_rec.r[k]);
+    }
+    for (k = 0; sd_rec.name && k < sd_rec.T; k++) free(sd_rec.name[k]);
+    free(sd_rec.r); free(sd_rec.name);
+    sd_rec.r = NULL; sd_rec.nr = 0; sd_rec.name = NULL; sd_rec.next = 0;
     free(sd_co.acc); free(sd_co.recs); free(sd_co.hits);
     sd_co.acc = NULL; sd_co.nacc = 0; sd_co.recs = NULL; sd_co.hits = NULL; sd_co.rcap = sd_co.hcap = 0; sd_co.post = NULL;
 }
@@ -1678,13 +1707,19 @@ static int co_open(sd_prog *p, uint32_t ns)
     if (!sd_co.on || sd_co.host) return SK_OK;
     if (!sk_covacc_create || !sk_covacc_pick || !sk_tally_collect_counts || !sk_union_tally_launch_ex ||
         (sd_rg.on && (!sk_covacc_set_regions || !sk_covacc_region_rows || !sk_covacc_finish_target_regions)) ||
-        (sd_spec.on && (!sk_covacc_set_spectrum || !sk_covacc_finish_target_spectrum))) {
+        (sd_spec.on && (!sk_covacc_set_spectrum || !sk_covacc_finish_target_spectrum)) ||
+        (sd_rec.on && (!sk_recur_create || !sk_recur_finish || !sk_covacc_set_recurrence || !sk_covacc_mark_target))) {
         fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
         sd_co.host = 1;
         return SK_OK;
     }
     sd_co.acc = (sk_covacc **)calloc(nu, sizeof *sd_co.acc);
     if (!sd_co.acc) return SK_E_NOMEM;
+    if (sd_rec.on) {
+        sd_rec.r = (sk_recur **)calloc(nu, sizeof *sd_rec.r);
+        sd_rec.name = (char **)calloc(sd_rec.T ? sd_rec.T : 1u, sizeof *sd_rec.name);
+        if (!sd_rec.r || !sd_rec.name) { co_close(); return SK_E_NOMEM; }
+    }
     for (k = 0; k < nu; k++) {
         const uint32_t a = co_unit_first(k), n = co_unit_members(k);
         uint32_t nrows[SK_UNION_MAX];
@@ -1695,6 +1730,22 @@ static int co_open(sd_prog *p, uint32_t ns)
         if (rc != SK_OK) { sd_co.nacc = k; co_close(); return rc; }
         if (getenv("SK_SD_TIMING") && sk_covacc_timing_) (void)sk_covacc_timing_(sd_co.acc[k], 1, NULL, NULL);
         if (sd_spec.on && (rc = sk_covacc_set_spectrum(sd_co.acc[k], sd_spec.max)) != SK_OK) { co_close(); return rc; }
+        if (sd_rec.on) {                                  /* every member's informative rows ranked: its bits of the unit's planes */
+            uint32_t nbits[SK_UNION_MAX];
+            for (m = 0; m < n; m++) {
+                if ((rc = sk_covacc_set_recurrence(sd_co.acc[k], m, p[a + m].ctx, SD_TYPE, SD_INFORMATIVE, &nbits[m])) != SK_OK) { co_close(); return rc; }
+                if ((uint64_t)nbits[m] != (uint64_t)p[a + m].genome_inf) {
+                    fprintf(p[0].err, "strain_detect: --coverage-recurrence: the table of strain %u has %u informative rows, its trailer says %llu\n",
+                            a + m, nbits[m], (unsigned long long)p[a + m].genome_inf);
+                    co_close();
+                    return SK_E_STATE;
+                }
+            }
+            rc = sk_recur_create(p[a].ctx, n, nbits, sd_rec.T, &sd_rec.r[k]);
+            sd_rec.nr = k + 1;
+            if (rc != SK_OK) { sd_rec.nr = k; co_close(); return rc; }
+            if (getenv("SK_SD_TIMING") && sk_recur_timing_) (void)sk_recur_timing_(sd_rec.r[k], 1, NULL, NULL);
+        }
         for (m = 0; m < n && sd_rg.on; m++) {             /* every member's rows to their regions, and the regions' denominators */
             sd_prog *q = &p[a + m];
             uint32_t *starts = (uint32_t *)malloc(((size_t)q->rg.n + 1) * sizeof *starts), r;
@@ -2446,6 +2497,12 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
                 deep = sp + (size_t)n * nsp;
             }
             pthread_mutex_lock(&sd_dev_mu);
+            if (sd_rec.r) {                                  /* the target's non-zero rows into its plane, before the sweep clears them */
+                uint64_t stray = 0;
+                rc = sd_rec.next < sd_rec.T ? sk_covacc_mark_target(sd_co.acc[k], sd_rec.r[k], sd_rec.next, &stray) : SK_E_STATE;
+                if (rc == SK_OK && stray) rc = SK_E_STATE;       /* (only informative rows are ever logged) */
+                if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
+            }
             rc = sd_spec.on ? sk_covacc_finish_target_spectrum(sd_co.acc[k], uq, tot, sp, deep, ru, rt) :
                  sd_rg.on ? sk_covacc_finish_target_regions(sd_co.acc[k], uq, tot, ru, rt) : sk_covacc_finish_target(sd_co.acc[k], uq, tot);
             pthread_mutex_unlock(&sd_dev_mu);
@@ -2461,6 +2518,10 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
             free(ru); free(sp);
         }
         if (got < 0) { fprintf(err, "strain_detect: device error on %s: %s (%s)\n", f1, sk_strerror(got), sk_last_error(p[0].ctx)); goto done; }
+        if (sd_rec.r) {                                      /* the host remembers ordinal -> sample name */
+            if (!(sd_rec.name[sd_rec.next] = strdup(f1))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
+            sd_rec.next++;
+        }
     }
     for (s = 0; s < ns; s++) {
         emit_trailer(&p[s], f1, "total_kmer_evaluated", (long long)evaluated);
@@ -2806,7 +2867,36 @@ static int sd_coverage_write(sd_prog *p)
         rc = skc_report_spectrum(p->cov, p->o_path, sd_spec.max, f, p->err);
         fclose(f);
     }
+    if (!rc && sd_rec.on) {
+        FILE *fp = NULL;
+        if (!(f = fopen(p->rc_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->rc_path); return 1; }
+        if (sd_rec.pairs && !(fp = fopen(p->rp_path, "w"))) { fclose(f); fprintf(p->err, "strain_detect: could not write %s\n", p->rp_path); return 1; }
+        rc = skc_report_recurrence(p->cov, p->o_path, f, fp, p->err);
+        fclose(f);
+        if (fp) fclose(fp);
+    }
     return rc;
+}
+
+/* --coverage-recurrence, --recurrence-pairs: where the tables of strain p go */
+static char *sd_table_path(const char *o_path, const char *explicit_path, const char *suffix)
+{
+    const size_t n = strlen(o_path);
+    char *t;
+    if (explicit_path && *explicit_path) return strdup(explicit_path);
+    if (!(t = (char *)malloc(n + strlen(suffix) + 1))) return NULL;
+    strcpy(t, o_path);
+    if (n >= 13 && !strcmp(t + n - 13, ".kmer_hits.gz")) t[n - 13] = 0;
+    strcat(t, suffix);
+    return t;
+}
+
+static int sd_recurrence_open(sd_prog *p, const char *explicit_path, const char *explicit_pairs)
+{
+    p->rc_path = sd_table_path(p->o_path, explicit_path, ".coverage_recurrence");
+    if (sd_rec.pairs) p->rp_path = sd_table_path(p->o_path, explicit_pairs, ".coverage_recurrence_pairs");
+    if (!p->rc_path || (sd_rec.pairs && !p->rp_path)) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
+    return 0;
 }
 
 /* --coverage-spectrum: where the table of strain p goes */
@@ -2916,7 +3006,7 @@ static void sd_strain_close(sd_prog *p)
     free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows);
     skc_destroy(p->cov);
     if (skh_regions_free) skh_regions_free(&p->rg);
-    free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path);
+    free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->rc_path); free(p->rp_path);
     memset(p, 0, sizeof *p);
 }
 
@@ -2934,6 +3024,31 @@ static int sd_list_line(char *line, int *m, char **tok, char **f1, char **f2)
     if (!(*f1 = strtok(NULL, "\t"))) return SD_LL_NO_FIRST;
     if (*m == SD_PE && !(*f2 = strtok(NULL, "\t"))) return SD_LL_NO_SECOND;
     return SD_LL_TARGET;
+}
+
+/* the run's recurrence tables, once per unit, from the planes to each strain's accumulator */
+static int sd_recurrence_finish(sd_prog *p, FILE *err)
+{
+    const uint32_t T = sd_rec.T;
+    uint32_t k, m;
+    if (sd_rec.next != T) { fprintf(err, "strain_detect: --coverage-recurrence: %u of %u targets were counted\n", sd_rec.next, T); return 1; }
+    for (k = 0; k < sd_rec.nr; k++) {
+        const uint32_t a = co_unit_first(k), n = co_unit_members(k);
+        uint64_t *hist = (uint64_t *)malloc((size_t)n * (T + 1u) * sizeof *hist);
+        uint64_t *pairs = sd_rec.pairs ? (uint64_t *)malloc((size_t)n * T * T * sizeof *pairs) : NULL;
+        int rc = !hist || (sd_rec.pairs && !pairs) ? SK_E_NOMEM : SK_OK;
+        if (rc == SK_OK) {
+            pthread_mutex_lock(&sd_dev_mu);
+            rc = sk_recur_finish(sd_rec.r[k], hist, pairs);
+            pthread_mutex_unlock(&sd_dev_mu);
+        }
+        for (m = 0; m < n && rc == SK_OK; m++)
+            if (skc_add_recurrence_counts(p[a + m].cov, (const char *const *)sd_rec.name, T, hist + (size_t)m * (T + 1u),
+                                          pairs ? pairs + (size_t)m * T * T : NULL)) rc = SK_E_NOMEM;
+        free(hist); free(pairs);
+        if (rc != SK_OK) { fprintf(err, "strain_detect: --coverage-recurrence: %s (%s)\n", sk_strerror(rc), sk_last_error(p[a].ctx)); return 1; }
+    }
+    return 0;
 }
 
 /* the metagenome side of main (src/strain_detect.c:263-384), for ns strains at once */
@@ -3003,6 +3118,7 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     pool_stop(&pool);
     sd_unmap_wait();
     sd_batch_cache_close();
+    if (!bad && sd_rec.r) bad = sd_recurrence_finish(p, err);
     co_close();
     if (getenv("SK_LEAK_AT_EXIT") && strcmp(getenv("SK_LEAK_AT_EXIT"), "0")) return bad;     /* (the process is about to end: see sd_strain_close) */
     { const double t0 = now_s(); sd_unions_close(); t_uclose = now_s() - t0; }
@@ -3125,7 +3241,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     const char *const *rg_genomes = sd_rg.genomes;       /* (adopted strains: theirs for this call only) */
     const uint32_t rg_ngenomes = sd_rg.ngenomes;
     skh_regions *rgs = NULL;
-    int want_rg = 0, want_sp = 0, want_ps = 0;
+    int want_rg = 0, want_sp = 0, want_ps = 0, want_rc = 0, want_rp = 0;
+    const char *rc_file = NULL, *rp_file = NULL;
     const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL;
     long long cov_min = 1;
     double t_begin = 0;
@@ -3176,6 +3293,19 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         }
         if (!strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { sp_max = argv[++c]; continue; }
         if (!strncmp(argv[c], "--spectrum-max=", 15)) { sp_max = argv[c] + 15; continue; }
+        /* "--coverage-recurrence[=FILE] [--recurrence-pairs[=FILE]]": next to either table, in how many of the run's samples each
+         * informative k-mer was seen, and what every two samples share; default FILEs = outfile with ".kmer_hits.gz" replaced by
+         * ".coverage_recurrence" and ".coverage_recurrence_pairs" */
+        if (!strncmp(argv[c], "--coverage-recurrence", 21) && (argv[c][21] == 0 || argv[c][21] == '=')) {
+            want_rc = 1;
+            rc_file = argv[c][21] ? argv[c] + 22 : NULL;
+            continue;
+        }
+        if (!strncmp(argv[c], "--recurrence-pairs", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            want_rp = 1;
+            rp_file = argv[c][18] ? argv[c] + 19 : NULL;
+            continue;
+        }
         /* "--panel-share=FILE" (-S only): before the first target, the k-mers every ordered pair of the panel's strains share, one
          * table for the whole panel (sd_panel_share) */
         if (!strncmp(argv[c], "--panel-share", 13) && (argv[c][13] == 0 || argv[c][13] == '=')) {
@@ -3191,6 +3321,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     argc = j;
     sd_rg.on = 0; sd_rg.genomes = NULL; sd_rg.ngenomes = 0;
     sd_spec.on = 0;
+    sd_rec.on = 0;
     sd_co.on = 0;
     sd_ps.path = NULL;
     if (cov_only && want_cov) { fputs("strain_detect: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n", err); return sd_drop(p, ns); }
@@ -3254,6 +3385,27 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         }
         sd_spec.max = (uint32_t)d;
     }
+    if (want_rc || want_rp) {
+        uint32_t T = 1;
+        if (!want_rc) { fputs("strain_detect: --recurrence-pairs goes with --coverage-recurrence\n", err); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-recurrence goes with --coverage-depth or --coverage-only: it follows their table's k-mers over the samples\n", err); return sd_drop(p, ns); }
+        if ((rc_file || rp_file) && ((S && !a && !o && !r) || (ad && ad->o))) { fputs("strain_detect: --coverage-recurrence=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        if (!sk_recur_create || !sk_recur_destroy || !sk_recur_finish || !sk_covacc_set_recurrence || !sk_covacc_mark_target) { fputs("strain_detect: --coverage-recurrence: this build has no recurrence engine\n", err); return sd_drop(p, ns); }
+        if (B) {                                             /* the target lines of the run: its samples */
+            FILE *fp = fopen(B, "r");
+            char *line = NULL, *tok, *f1, *f2;
+            size_t cap = 0;
+            int m;
+            for (T = 0; fp && getline(&line, &cap, fp) != -1; )
+                if (sd_list_line(line, &m, &tok, &f1, &f2) == SD_LL_TARGET) T++;
+            free(line);
+            if (fp) fclose(fp);
+            else T = 1;                                      /* (unreadable: the run says so) */
+        }
+        if (T > SK_RECUR_SAMPLES_MAX) { fprintf(err, "strain_detect: --coverage-recurrence: %s names %u targets, at most %u\n", B, T, SK_RECUR_SAMPLES_MAX); return sd_drop(p, ns); }
+        if (want_rp && T > SK_RECUR_PAIRS_MAX) { fprintf(err, "strain_detect: --recurrence-pairs: %s names %u targets, at most %u\n", B, T, SK_RECUR_PAIRS_MAX); return sd_drop(p, ns); }
+        sd_rec.T = T ? T : 1u;
+    }
     if (want_ps) {
         const char *ws = getenv("SK_WORLD_SIZE") ? getenv("SK_WORLD_SIZE") : getenv("WORLD_SIZE");
         if (!ps_file || !*ps_file) { fputs("strain_detect: --panel-share=FILE needs a file name: the table is one file for the whole panel\n", err); return sd_drop(p, ns); }
@@ -3302,6 +3454,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_co_ms_fold = sd_co_ms_sweep = 0;
     sd_rg.on = want_rg;
     sd_spec.on = want_sp;
+    sd_rec.on = want_rc; sd_rec.pairs = want_rp; sd_rec.next = 0;
+    sd_rec.ms_mark = sd_rec.ms_hist = sd_rec.ms_gram = 0;
     sd_ps.path = want_ps ? ps_file : NULL;
     sd_ps.ms = 0; sd_ps.calls = 0;
     sd_co.flush_rows = (env = getenv("SK_SD_CO_FLUSH_ROWS")) != NULL && atoll(env) >= 1 ? (uint64_t)atoll(env) : 1u << 20;
@@ -3398,6 +3552,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (sd_regions_open(&p[s], &rgs[s], S || (ad && ad->o) ? NULL : rg_file)) goto done;
     for (s = 0; want_sp && s < ns; s++)
         if (sd_spectrum_open(&p[s], S || (ad && ad->o) ? NULL : sp_file)) goto done;
+    for (s = 0; want_rc && s < ns; s++)
+        if (sd_recurrence_open(&p[s], S || (ad && ad->o) ? NULL : rc_file, S || (ad && ad->o) ? NULL : rp_file)) goto done;
     if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
     for (s = 0; s < ns; s++)
         if (sd_coverage_write(&p[s])) goto done;
@@ -3463,6 +3619,9 @@ done:
     if (getenv("SK_SD_TIMING") && cov_only)
         fprintf(err, "strain_detect timing: coverage accumulators on the device: folds %.3f ms, target sweeps %.3f ms%s\n", sd_co_ms_fold, sd_co_ms_sweep,
                 want_rg && want_sp ? " (folded by region, binned by depth)" : want_rg ? " (folded by region)" : want_sp ? " (binned by depth)" : "");
+    if (getenv("SK_SD_TIMING") && cov_only && want_rc)
+        fprintf(err, "strain_detect timing: recurrence on the device: marks %.3f ms (%u targets), finish: histogram %.3f ms, pairs %.3f ms\n",
+                sd_rec.ms_mark, sd_rec.T, sd_rec.ms_hist, sd_rec.ms_gram);
     if (getenv("SK_SD_TIMING") && want_ps)
         fprintf(err, "strain_detect timing: panel share %.3f ms, %u call(s) of sk_union_share\n", sd_ps.ms, sd_ps.calls);
     if (getenv("SK_SD_RESULT_BYTES"))
@@ -3474,6 +3633,7 @@ done:
     sd_co.on = 0;
     sd_rg.on = 0;
     sd_spec.on = 0;
+    sd_rec.on = 0;
     sd_ps.path = NULL;
     for (s = 0; rgs && s < nrgs; s++) skh_regions_free(&rgs[s]);
     free(rgs);

@@ -35,6 +35,12 @@ int skc_report_regions(skc_acc *a, const char *hits_file_name, const skh_regions
  * call it after skc_report */
 int skc_add_spectrum_counts(skc_acc *a, const char *metagenome, const uint64_t *spec, uint64_t deep_total, uint32_t nbins);
 int skc_report_spectrum(skc_acc *a, const char *hits_file_name, uint32_t max_depth, FILE *out, FILE *err);
+/* ... and recurrence over the run's samples (strain_detect --coverage-recurrence [--recurrence-pairs]): the run's tables handed in
+ * once, by the caller's sample ordinals (hist[T + 1], entry 0 unused; pairs[T x T] or NULL; metagenome[i] names ordinal i, known to
+ * the accumulator already), or folded from the hits by skc_report_recurrence, which prints both tables (out_pairs NULL: the first
+ * alone); call it after skc_report */
+int skc_add_recurrence_counts(skc_acc *a, const char *const *metagenome, uint32_t T, const uint64_t *hist, const uint64_t *pairs);
+int skc_report_recurrence(skc_acc *a, const char *hits_file_name, FILE *out, FILE *out_pairs, FILE *err);
 /* kmer_scrub_count --detect: the genome files of the strains the next skh_strain_detect_resident[_many] call adopts (it has no -r;
  * --coverage-regions reads the records' names and lengths from them).  The call takes the list and forgets it. */
 void skh_resident_genomes_(const char *const *paths, uint32_t n);
@@ -87,6 +93,21 @@ int sk_tally_view_(sk_ctx *ctx, sk_union *u, sk_tally_view *out);
 /* the accumulator's device time (events around every fold and every target sweep): on != 0 starts the clocks, ms_fold / ms_sweep
  * (NULL: not wanted) are the sums so far.  Off unless asked for: strain_detect asks under SK_SD_TIMING. */
 int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *ms_sweep);
+/* the device time of the accumulator's marks (sk_covacc_mark_target), kept by the same clocks */
+int sk_covacc_mark_timing_(sk_covacc *a, double *ms_mark);
+/* The recurrence engine's planes (sk_recur.hip), for the feeders that set bits with kernels of their own (sk_covacc.hip,
+ * sk_cover.hip): plane `sample` of member m begins at d_planes + sample * words + word_base[m] and holds (nbits[m] + 63) / 64
+ * words; a feeder sets no bit at or above nbits[m] and synchronises before the engine's next call. */
+typedef struct sk_recur_view {
+    int device; uint32_t nmembers, nsamples;
+    const uint32_t *nbits;                 /* [nmembers], host */
+    const uint64_t *word_base;             /* [nmembers + 1], host */
+    const uint64_t *d_word_base;           /* the same on the device */
+    unsigned long long *d_planes; uint64_t words;
+} sk_recur_view;
+int sk_recur_view_(sk_recur *r, sk_recur_view *out);
+/* the device time of the engine's two sweeps (events around them in sk_recur_finish): on != 0 starts the clocks */
+int sk_recur_timing_(sk_recur *r, int on, double *ms_hist, double *ms_gram);
 #ifdef __cplusplus
 }
 #endif

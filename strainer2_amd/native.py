@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "sk_covacc_finish_target_regions",
     "sk_covacc_set_spectrum", "sk_covacc_finish_target_spectrum", "sk_distinct_spectrum",
     "sk_union_share",
+    "sk_recur_create", "sk_recur_destroy", "sk_recur_mark_bits", "sk_recur_finish", "sk_covacc_set_recurrence", "sk_covacc_mark_target",
+    "sk_distinct_recurrence",
 ]
 
 
@@ -718,6 +720,18 @@ class KmerContext:
                                           uniq.ctypes.data, total.ctypes.data, spec.ctypes.data, deep.ctypes.data))
         return uniq, total, spec, deep
 
+    def distinct_recurrence(self, keys, sample, nsamples, pairs=False):
+        """sk_distinct_recurrence: hist[nsamples + 1] -- hist[m] = distinct keys seen in exactly m samples, hist[0] left 0 -- and, with
+        pairs, shared[nsamples, nsamples]: the distinct keys two samples have in common (the diagonal: a sample's own)"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32)
+        assert len(keys) == len(sample)
+        hist = np.zeros(max(int(nsamples), 0) + 1, dtype=np.uint64)
+        pr = np.zeros((max(int(nsamples), 0),) * 2, dtype=np.uint64) if pairs else None
+        self._ck(lib.sk_distinct_recurrence(self._h, keys.ctypes.data, sample.ctypes.data, len(keys), int(nsamples), hist.ctypes.data,
+                                            pr.ctypes.data if pairs else None))
+        return (hist, pr) if pairs else hist
+
     def print_counts(self, ks: Keyset, path, with_drug_column=False):
         fp = _libc.fopen(os.fsencode(path), b"w")
         try:
@@ -783,6 +797,19 @@ SK_COVACC_SPECTRUM_MAX = 1023
 lib.sk_covacc_set_spectrum.argtypes = [C.c_void_p, C.c_uint32]
 lib.sk_covacc_finish_target_spectrum.argtypes = [C.c_void_p] * 7
 lib.sk_distinct_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+
+
+SK_RECUR_SAMPLES_MAX = 4096
+SK_RECUR_PAIRS_MAX = 256
+SK_RECUR_MEMBERS_MAX = 65535
+lib.sk_recur_create.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+lib.sk_recur_destroy.argtypes = [C.c_void_p]
+lib.sk_recur_destroy.restype = None
+lib.sk_recur_mark_bits.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]
+lib.sk_recur_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sk_covacc_set_recurrence.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+lib.sk_covacc_mark_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+lib.sk_distinct_recurrence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
 
 
 def regions_from_file(path, window=100000):
@@ -1167,9 +1194,63 @@ class CoverageAcc:
             at += n + 1
         return uq, tot, spec, deep, per
 
+    def set_recurrence(self, member, ctx, type_col=0, informative_value=2):
+        """sk_covacc_set_recurrence: rank member's informative rows (those whose counter in type_col of ctx's table equals
+        informative_value); returns their number, the member's bits in a Recurrence"""
+        n = C.c_uint32(0)
+        self._ctx._ck(lib.sk_covacc_set_recurrence(self._h, member, ctx._h, type_col, informative_value, C.byref(n)))
+        return int(n.value)
+
+    def mark_target(self, recur, sample):
+        """sk_covacc_mark_target: every row with a non-zero counter sets its bit of plane sample of recur; the counters stay.  Returns
+        the non-zero rows that have no rank (they mark nothing)"""
+        stray = C.c_uint64(0)
+        self._ctx._ck(lib.sk_covacc_mark_target(self._h, recur._h, int(sample), C.byref(stray)))
+        return int(stray.value)
+
     def close(self):
         if getattr(self, "_h", None):
             lib.sk_covacc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Recurrence:
+    """The recurrence engine (sk_recur_*): bit planes of len(nbits) members over nsamples samples on ctx's device, and the two tables
+    over them -- per member how many bits are set in exactly m planes, and how many bits two planes share."""
+
+    def __init__(self, ctx: KmerContext, nbits, nsamples):
+        self._ctx = ctx
+        self.nbits = np.ascontiguousarray(nbits, dtype=np.uint32).reshape(-1)
+        self.nsamples = int(nsamples)
+        self._h = C.c_void_p()
+        ctx._ck(lib.sk_recur_create(ctx._h, len(self.nbits), self.nbits.ctypes.data, self.nsamples, C.byref(self._h)))
+
+    def mark_bits(self, member, sample, bits):
+        """sk_recur_mark_bits: OR these bits of member into plane sample"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+        self._ctx._ck(lib.sk_recur_mark_bits(self._h, int(member), int(sample), bits.ctypes.data, len(bits)))
+
+    def finish(self, pairs=False):
+        """sk_recur_finish: hist[nmembers, nsamples + 1] (column 0: the member's bits set in no plane) and, with pairs,
+        shared[nmembers, nsamples, nsamples]; the planes are only read"""
+        nm, T = len(self.nbits), self.nsamples
+        hist = np.zeros((nm, T + 1), dtype=np.uint64)
+        pr = np.zeros((nm, T, T), dtype=np.uint64) if pairs else None
+        self._ctx._ck(lib.sk_recur_finish(self._h, hist.ctypes.data, pr.ctypes.data if pairs else None))
+        return (hist, pr) if pairs else hist
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.sk_recur_destroy(self._h)
             self._h = None
 
     def __del__(self):

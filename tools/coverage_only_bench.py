@@ -19,9 +19,14 @@ run (SK_SD_TIMING; the parent build does not report it).
 alternate, the parent build's plain --coverage-only runs behind them, and the summary sets the new build's plain runs and the runs
 with the flag against the parent's medians and the parent's own run-to-run spread (max - min over its rounds).
 
+--recurrence measures --coverage-recurrence --recurrence-pairs in the same way (the samples are the list's files), and each line
+with the flag also carries the device time of the marks (summed over the targets) and of the one finish, histogram and pair table
+apart.
+
     python tools/coverage_only_bench.py [--gbases 1.5] [--parent-exe PATH] [--out profiles/coverage_only_bench.txt]
     python tools/coverage_only_bench.py --regions 100000 --rounds 5 [--parent-exe PATH] [--out profiles/coverage_regions_bench.txt]
     python tools/coverage_only_bench.py --spectrum 255 --rounds 5 --parent-exe PATH [--out profiles/coverage_spectrum_bench.txt]
+    python tools/coverage_only_bench.py --recurrence --rounds 5 --parent-exe PATH [--out profiles/coverage_recurrence_bench.txt]
 """
 import argparse
 import hashlib
@@ -46,7 +51,11 @@ from text_parse_bench import reads_text  # noqa: E402  (the generator of the oth
 EXE = os.path.join(REPO, "strainer2_amd", "bin", "strain_detect")
 PASS = re.compile(rb"strain_detect timing: setup ([0-9.]+) s,.*?total before close ([0-9.]+) s")
 ACC = re.compile(rb"coverage accumulators on the device: folds ([0-9.]+) ms, target sweeps ([0-9.]+) ms")
+REC = re.compile(rb"recurrence on the device: marks ([0-9.]+) ms \((\d+) targets\), finish: histogram ([0-9.]+) ms, pairs ([0-9.]+) ms")
 BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
+
+
+STDERR_DIR = None
 
 
 class StepFailed(Exception):
@@ -60,7 +69,8 @@ def row(rs, key, spec):
 def step(exe, argv, env, limit, cwd, ns, hit_lists):
     """one run of the program under its own time limit -> measurements; raises StepFailed (nothing more is started then)"""
     for s in range(ns):
-        for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum"):
+        for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum",
+                  f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -68,6 +78,9 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     p = subprocess.run(["timeout", "-k", "10", str(limit), exe] + argv, env=env, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     wall = time.perf_counter() - t0
     r1 = resource.getrusage(resource.RUSAGE_CHILDREN)
+    if STDERR_DIR:                                           # (--stderr-dir: every run's timing lines, for a closer look)
+        with open(os.path.join(STDERR_DIR, f"run{len(os.listdir(STDERR_DIR)):03d}.err"), "wb") as f:
+            f.write((" ".join([exe] + argv) + "\n").encode() + p.stderr)
     if p.returncode != 0:
         raise StepFailed(f"exit status {p.returncode}: {p.stderr.decode(errors='replace')[-1500:]}")
     h = hashlib.md5()
@@ -78,14 +91,16 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             h.update(f.read())
     hr = hashlib.md5()
     for s in range(ns):
-        for ext in ("coverage_regions", "coverage_spectrum"):    # (the table beside the coverage table, whichever the run wrote)
+        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs"):    # (the table beside the coverage table, whichever the run wrote)
             if os.path.exists(os.path.join(cwd, f"out{s}.gz.{ext}")):
                 with open(os.path.join(cwd, f"out{s}.gz.{ext}"), "rb") as f:
                     hr.update(f.read())
     m = PASS.search(p.stderr)
     b = BYTES.search(p.stderr)
     a = ACC.search(p.stderr)
-    return dict(fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
+    rc = REC.search(p.stderr)
+    return dict(mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
+                fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
                 passed=float(m.group(2)) - float(m.group(1)) if m else float("nan"),
                 d2h=int(b.group(1)) if b else -1, dev=int(b.group(2)) if b else -1, replayed=int(b.group(3)) if b else -1)
 
@@ -122,10 +137,14 @@ def regions_case(say, args, env, tmp, ns, kind, argv):
         say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
-def spectrum_case(say, args, env, tmp, ns, kind, argv):
-    """--coverage-only without and with --coverage-spectrum, alternating; the parent build's plain --coverage-only behind them and
-    the new build's medians set against the parent's"""
+def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False):
+    """--coverage-only without and with --coverage-spectrum (recurrence: --coverage-recurrence --recurrence-pairs), alternating; the
+    parent build's plain --coverage-only behind them and the new build's medians set against the parent's"""
     with_sp = ["--coverage-only", "--coverage-spectrum", "--spectrum-max", str(args.spectrum)]
+    word, label = "spectrum", f"... --coverage-spectrum --spectrum-max {args.spectrum}"
+    if recurrence:
+        with_sp = ["--coverage-only", "--coverage-recurrence", "--recurrence-pairs"]
+        word, label = "recurrence", "... --coverage-recurrence --recurrence-pairs"
     res = {"plain": [], "spectrum": [], "parent": []}
     md5 = md5s = None
     for rnd in range(args.rounds):
@@ -137,22 +156,25 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv):
             if tag == "spectrum":
                 md5s = md5s or r["md5r"]
                 if r["md5r"] != md5s:
-                    raise StepFailed(f"{ns} strains, {kind}, round {rnd}: the spectrum tables differ from the first run's")
+                    raise StepFailed(f"{ns} strains, {kind}, round {rnd}: the {word} tables differ from the first run's")
             res[tag].append(r)
     if args.parent_exe:
         res["parent"] = [step(args.parent_exe, argv + ["--coverage-only"], dict(env), args.limit, tmp, ns, False) for _ in range(args.rounds)]
         if any(r["md5"] != md5 for r in res["parent"]):
             raise StepFailed(f"{ns} strains, {kind}: the parent build writes other tables")
-    say(f"{ns} strains, {kind}: the {ns} coverage tables are the same bytes in all runs (MD5 {md5}), the spectrum tables in all "
+    say(f"{ns} strains, {kind}: the {ns} coverage tables are the same bytes in all runs (MD5 {md5}), the {word} tables in all "
         f"{args.rounds} (MD5 {md5s})")
-    names = {"plain": "--coverage-only", "spectrum": f"... --coverage-spectrum --spectrum-max {args.spectrum}", "parent": "parent build, --coverage-only"}
+    names = {"plain": "--coverage-only", "spectrum": label, "parent": "parent build, --coverage-only"}
     for tag, rs in res.items():
         if rs:
             say(f"    {names[tag]}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; accumulators on the device: folds "
                 f"{row(rs, 'fold', '.2f')} ms, target sweeps {row(rs, 'sweep', '.3f')} ms; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
+            if recurrence and tag == "spectrum":
+                say(f"        recurrence on the device: marks of all targets {row(rs, 'mark', '.3f')} ms; the one finish: histogram "
+                    f"{row(rs, 'hist', '.3f')} ms, pair table {row(rs, 'gram', '.3f')} ms")
     keys = ("passed", "wall", "fold", "sweep")
     med = {t: {k: statistics.median(r[k] for r in rs) for k in keys} for t, rs in res.items() if rs}
-    say("    with the spectrum / without at the medians: pass %.2f, wall %.2f, folds %.2f, target sweeps %.2f" %
+    say(f"    with the {word} / without at the medians: pass %.2f, wall %.2f, folds %.2f, target sweeps %.2f" %
         tuple(med["spectrum"][k] / med["plain"][k] if med["plain"][k] else float("nan") for k in keys))
     if res["parent"]:                                        # the yardstick: the parent's medians; the margin: its own spread
         for k, unit in (("passed", "s"), ("sweep", "ms")):
@@ -173,9 +195,15 @@ def main():
     ap.add_argument("--parent-exe", default=None, help="strain_detect of a build of the parent commit")
     ap.add_argument("--regions", type=int, default=None, help="measure --coverage-regions with this --region-window")
     ap.add_argument("--spectrum", type=int, default=None, help="measure --coverage-spectrum with this --spectrum-max")
+    ap.add_argument("--recurrence", action="store_true", help="measure --coverage-recurrence --recurrence-pairs")
+    ap.add_argument("--stderr-dir", default=None, help="keep every run's stderr (the SK_SD_TIMING lines) in this directory")
     ap.add_argument("--out", default=None)
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
     args = ap.parse_args()
+    if args.stderr_dir:
+        global STDERR_DIR
+        STDERR_DIR = os.path.abspath(args.stderr_dir)
+        os.makedirs(STDERR_DIR, exist_ok=True)
     if args.parent_exe:
         args.parent_exe = os.path.abspath(args.parent_exe)     # (the runs' working directory is the data's)
     counts = [int(x) for x in args.strains.split(",")]
@@ -225,8 +253,8 @@ def main():
             for ns in counts:
                 for kind, lst in lists.items():
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
-                    if args.spectrum is not None:
-                        spectrum_case(say, args, env, tmp, ns, kind, argv)
+                    if args.spectrum is not None or args.recurrence:
+                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence)
                         continue
                     if args.regions is not None:
                         regions_case(say, args, env, tmp, ns, kind, argv)
