@@ -816,8 +816,50 @@ int  sk_covacc_set_recurrence(sk_covacc *a, uint32_t member, sk_ctx *ctx, uint32
 int  sk_covacc_mark_target(sk_covacc *a, sk_recur *r, uint32_t sample, uint64_t *out_stray);
 int  sk_distinct_recurrence(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, uint64_t n, uint32_t nsamples,
                             uint64_t *hist /* nsamples + 1; entry 0 is left 0 */, uint64_t *pairs /* NULL or nsamples^2 */);
+/* THRESHOLDS (new: strain_detect --coverage-thresholds, coverage_depth --thresholds): step 4's two numbers at several
+ * min_kmer_hits from one pass.  In the reference the read filter of step 4 is chosen after the pass -- scripts/coverage_depth.py -m N
+ * counts a hit line iff total_kmer_pe1 + total_kmer_pe2 > N (:89) and is run at several N over one hit list; --coverage-only
+ * writes no hit list, so the choice would cost a pass per N.  The rule, for a strain, a sample and a list t[0] < t[1] < ...:
+ *   list      1 to SK_COVACC_THRESHOLDS_MAX = 16 integers, 0 <= t <= 2^31 - 2, strictly ascending (--threshold-list t1,t2,...;
+ *             default 0,1,2,3,5,10,20,50).  An empty field, a duplicate, a descending value, more than 16 entries or a value out of
+ *             range is refused.
+ *   sample    a target's basename, as in the script; the table's samples and their order are the main coverage table's.
+ *   total[t]  the number of hit lines of step 3 whose pair has h1 + h2 > t.
+ *   unique[t] the number of distinct k-mers (rows) those lines name.
+ *             Exactly the main table's total_observed_informative_kmers and unique_observed_informative_kmers of a run with
+ *             --min-kmer-hits t.  The run's own --min-kmer-hits still governs the main table and the regions, spectrum and
+ *             recurrence tables, and need not be in the list.
+ *   table     a header line, then for every sample one line per threshold, ascending, zeros included, all columns integers:
+ *               strain_name<TAB>metagenome<TAB>min_kmer_hits<TAB>unique_observed_informative_kmers<TAB>total_observed_informative_kmers
+ *   invariants  neither number increases with t; unique[t] <= total[t]; where the run's --min-kmer-hits is in the list, that line
+ *             carries the main table's two numbers for the sample.
+ * The class of a hit line is the number of thresholds its pair's total exceeds; total[t[q]] is the number of lines of class > q and
+ * unique[t[q]] the number of rows with a line of class > q, so the accumulator keeps the lines per class and every row's highest
+ * class: one u32 per accumulator row from the first sk_covacc_set_thresholds on, whatever the list's length.
+ *   sk_covacc_set_thresholds: n = 0 turns thresholds off (the state after create); otherwise the list is checked by the rule above
+ *   (SK_E_ARG).  It may be called between targets; whatever was classified since the last finish is discarded.
+ *   sk_covacc_add with thresholds on classifies every log entry of the run by its pair's total: the entry counts for the main
+ *   counters iff the total exceeds min_kmer_hits, as ever, and for threshold q iff it exceeds t[q] -- whichever of the two is lower.
+ *   sk_covacc_add_rows_hits: n host-replayed hits on these rows of `member`, NOT filtered, each with its pair's total h1 + h2, under
+ *   the same rule for the main counters and the thresholds (thresholds off: the main counters only).  With thresholds on the
+ *   filtered sk_covacc_add_rows returns SK_E_STATE: its rows carry no totals.
+ *   sk_covacc_finish_target_thresholds: thr_unique[m * n + q], thr_total[m * n + q] for the list's n thresholds.  A pass of its own
+ *   in front of whichever sweep ends the target, as sk_covacc_mark_target is: it changes no depth counter, so the three sweeps
+ *   return what they return without it; the threshold state is zero afterwards (a second call returns zeros).  SK_E_STATE with
+ *   thresholds off.
+ *   sk_distinct_thresholds: the same two numbers per sample and threshold ([nsamples x nt]) for a hit list of (sample, key, total)
+ *   triples; keys as for sk_distinct_count. */
+#define SK_COVACC_THRESHOLDS_MAX 16u
+int  sk_covacc_set_thresholds(sk_covacc *a, const int64_t *t, uint32_t n);
+int  sk_covacc_add_rows_hits(sk_covacc *a, uint32_t member, const uint32_t *rows, const uint32_t *total_hits, uint64_t n);
+int  sk_covacc_finish_target_thresholds(sk_covacc *a, uint64_t *thr_unique /* nmembers x n */, uint64_t *thr_total /* nmembers x n */);
+int  sk_distinct_thresholds(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, const uint32_t *total_hits, uint64_t n,
+                            uint32_t nsamples, const int64_t *t, uint32_t nt, uint64_t *out_unique /* nsamples x nt */,
+                            uint64_t *out_total /* nsamples x nt */);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
- * same stdout bytes and exit status.  New: --spectrum[=FILE] [--spectrum-max D] also writes the depth spectrum (above) to FILE,
+ * same stdout bytes and exit status.  New: --thresholds[=FILE] [--threshold-list t1,t2,...] also writes the thresholds table (above)
+ * to FILE, default the hits file's path with a trailing ".kmer_hits.gz" replaced by ".coverage_thresholds"; stdout is unchanged and a
+ * hit list in the general mode is refused.  New: --spectrum[=FILE] [--spectrum-max D] also writes the depth spectrum (above) to FILE,
  * default the hits file's path with a trailing ".kmer_hits.gz" removed plus ".coverage_spectrum"; stdout is unchanged.  A hit list
  * in the general (non-ACGT text) mode is refused.  New: --recurrence[=FILE] [--recurrence-pairs[=FILE]] also writes the recurrence
  * tables (above), default paths with ".coverage_recurrence" and ".coverage_recurrence_pairs", under the same conditions. */

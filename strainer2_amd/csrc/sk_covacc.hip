@@ -15,6 +15,9 @@
 // covacc_finish_spectrum is either of them with every non-zero row also counted in the bin of its depth (--coverage-spectrum).
 // covacc_mark is a pass of its own in front of any of the three (recurrence: sk_recur.hip has the planes): it reads the counters and
 // changes none, so a run that never marks launches exactly the sweeps it launched before.
+// covacc_hits_thr is covacc_hits with every entry also classified by how many of a list of thresholds its pair's total exceeds
+// (--coverage-thresholds), covacc_thr_finish the pass of its own that turns the rows' highest classes into numbers; like the mark it
+// changes no counter, and a run without thresholds launches neither.
 // Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -388,6 +391,134 @@ __global__ void __launch_bounds__(256) covacc_mark(const uint32_t *__restrict__ 
     if (bad) atomicAdd(stray, (unsigned long long)bad);      // (never in the programs: only informative rows are logged)
 }
 
+// ---- thresholds: step 4's two numbers at several min_kmer_hits from one pass (include/strainer_kmer.h has the rule) ----
+// The class of a log entry is c = the number of thresholds its pair's total exceeds (the list ascends, so c says which).  total[q] is
+// the number of entries of class > q and unique[q] the number of rows with some entry of class > q, so the folds keep
+//   cls_cnt[member][c]   entries per class: LDS bins per workgroup, one 64-bit atomic per non-empty bin and workgroup at its end;
+//   thr_max[row]         the row's highest class: one atomicMax per entry with c >= 1, spread over the rows as the depth adds are,
+// and covacc_thr_finish bins thr_max[] by class (and leaves it zero); the host takes the suffix sums.  One u32 per accumulator row
+// whatever the list's length.  Most entries of a wave share one (member, class) -- a present strain's pairs pass every threshold --
+// so the lanes of a wave first agree on who holds which bin and the first lane of each bin adds the count for all of them
+// (cov_bin_add): one LDS atomic per distinct bin and wave, not 64 on one address.
+#define COV_THR_CLASSES (SK_COVACC_THRESHOLDS_MAX + 1u)
+#define COV_THR_LDS_MEMBERS SK_UNION_MAX
+struct cov_thr { long long t[SK_COVACC_THRESHOLDS_MAX]; uint32_t n; };
+
+__device__ __forceinline__ uint32_t cov_class(const cov_thr &th, uint32_t total)
+{
+    uint32_t c = 0;
+    const uint32_t n = th.n < SK_COVACC_THRESHOLDS_MAX ? th.n : SK_COVACC_THRESHOLDS_MAX;
+    for (uint32_t q = 0; q < n; q++) c += (long long)total > th.t[q] ? 1u : 0u;
+    return c;
+}
+
+// every lane of the wave calls it (converged); bin = 0xFFFFFFFF: this lane has nothing.  bins[] has nbins entries.
+__device__ __forceinline__ void cov_bin_add(unsigned long long *bins, uint32_t nbins, uint32_t bin)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    if (bin >= nbins) bin = 0xFFFFFFFFu;
+    unsigned long long todo = __ballot(bin != 0xFFFFFFFFu);
+    while (todo) {
+        const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
+        const uint32_t b0 = (uint32_t)__shfl((int)bin, (int)lead);
+        const unsigned long long same = __ballot(bin == b0);
+        if (lane == lead) atomicAdd(&bins[b0], (unsigned long long)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+// covacc_hits, and every entry also classified: cls_cnt + member0's offset is the caller's, thr_max indexed like depth
+__global__ void __launch_bounds__(256) covacc_hits_thr(const sk_hit *__restrict__ hits, uint64_t n, const uint32_t *__restrict__ rec_start,
+                                                       uint32_t nrec, uint32_t ns, int is_union, uint32_t r0, uint32_t step, uint32_t npairs,
+                                                       const uint32_t *__restrict__ tot, long long min_hits, uint32_t *__restrict__ depth,
+                                                       const uint64_t *__restrict__ row_base, const uint32_t *__restrict__ nrows, uint32_t *bad,
+                                                       cov_thr th, uint32_t *__restrict__ thr_max, unsigned long long *__restrict__ cls_cnt)
+{
+    __shared__ unsigned long long s_bin[COV_THR_LDS_MEMBERS * COV_THR_CLASSES];
+    const bool in_lds = ns <= COV_THR_LDS_MEMBERS;
+    const uint32_t nbins = in_lds ? ns * COV_THR_CLASSES : 0u;
+    for (uint32_t b = threadIdx.x; b < nbins; b += 256u) s_bin[b] = 0ull;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < n; i0 += stride) {      // (i0 is the workgroup's: every wave stays whole)
+        const uint64_t i = i0 + threadIdx.x;
+        uint32_t bin = 0xFFFFFFFFu;
+        if (i < n) {
+            const sk_hit e = hits[i];
+            uint32_t lo = 0, hi = nrec;
+            while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (rec_start[mid] <= e.pos) lo = mid; else hi = mid; }
+            const uint32_t m = is_union ? e.row >> SK_UNION_ROW_BITS : 0u;
+            const uint32_t row = is_union ? e.row & ((1u << SK_UNION_ROW_BITS) - 1u) : e.row;
+            if (rec_start[lo] > e.pos || m >= ns || row >= nrows[m]) *bad = 1u;   // (never: an entry no table row stands behind)
+            else {
+                const uint32_t j = cov_pair(lo, r0, step, npairs);
+                if (j < npairs) {
+                    const uint32_t total = tot[(size_t)j * ns + m];
+                    if ((long long)total > min_hits) atomicAdd(depth + row_base[m] + row, 1u);
+                    const uint32_t c = cov_class(th, total);
+                    if (c) {
+                        atomicMax(thr_max + row_base[m] + row, c);
+                        if (in_lds) bin = m * COV_THR_CLASSES + c;
+                        else atomicAdd(cls_cnt + (size_t)m * COV_THR_CLASSES + c, 1ull);
+                    }
+                }
+            }
+        }
+        if (in_lds) cov_bin_add(s_bin, nbins, bin);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < nbins; b += 256u)
+        if (s_bin[b]) atomicAdd(cls_cnt + b, s_bin[b]);
+}
+
+// host-replayed entries of one member, unfiltered, each with its pair's total: depth/thr_max are the member's, cls_cnt its
+// COV_THR_CLASSES bins; th.n = 0: only the main counters
+__global__ void __launch_bounds__(256) covacc_rows_hits(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ totals, uint64_t n,
+                                                        uint32_t nrows, long long min_hits, uint32_t *__restrict__ depth, cov_thr th,
+                                                        uint32_t *__restrict__ thr_max, unsigned long long *__restrict__ cls_cnt)
+{
+    __shared__ unsigned long long s_bin[COV_THR_CLASSES];
+    if (threadIdx.x < COV_THR_CLASSES) s_bin[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < n; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        uint32_t bin = 0xFFFFFFFFu;
+        if (i < n && rows[i] < nrows) {
+            const uint32_t total = totals[i];
+            if ((long long)total > min_hits) atomicAdd(depth + rows[i], 1u);
+            const uint32_t c = cov_class(th, total);
+            if (c) { atomicMax(thr_max + rows[i], c); bin = c; }
+        }
+        if (th.n) cov_bin_add(s_bin, COV_THR_CLASSES, bin);
+    }
+    __syncthreads();
+    if (th.n && threadIdx.x < COV_THR_CLASSES && s_bin[threadIdx.x]) atomicAdd(cls_cnt + threadIdx.x, s_bin[threadIdx.x]);
+}
+
+// blockIdx.y = member: its rows' highest classes binned into row_cnt[m][class]; thr_max is zero afterwards.  The depth counters are
+// not touched.
+__global__ void __launch_bounds__(256) covacc_thr_finish(uint32_t *__restrict__ thr_max, const uint64_t *__restrict__ row_base,
+                                                         const uint32_t *__restrict__ nrows, unsigned long long *__restrict__ row_cnt)
+{
+    __shared__ unsigned long long s_bin[COV_THR_CLASSES];
+    const uint32_t m = blockIdx.y, n = nrows[m];
+    uint32_t *mx = thr_max + row_base[m];
+    if (threadIdx.x < COV_THR_CLASSES) s_bin[threadIdx.x] = 0ull;
+    __syncthreads();
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < n; i0 += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = i0 + threadIdx.x;
+        uint32_t bin = 0xFFFFFFFFu;
+        if (i < n) {
+            const uint32_t v = mx[i];
+            if (v) { mx[i] = 0u; bin = v; }                   // (v < COV_THR_CLASSES, or cov_bin_add drops it)
+        }
+        cov_bin_add(s_bin, COV_THR_CLASSES, bin);
+    }
+    __syncthreads();
+    if (threadIdx.x < COV_THR_CLASSES && s_bin[threadIdx.x]) atomicAdd(row_cnt + (size_t)m * COV_THR_CLASSES + threadIdx.x, s_bin[threadIdx.x]);
+}
+
 struct sk_covacc {
     sk_ctx *ctx; int device;
     hipStream_t stream;
@@ -418,6 +549,12 @@ struct sk_covacc {
     std::vector<uint32_t> rec_nbits; uint32_t *d_rec_nbits; // [nm] informative rows per member (0: never set)
     void *d_blk; size_t blk_cap;                            // set_recurrence's scratch: the blocks' counts
     unsigned long long *d_stray;
+    // thresholds: nothing of it exists until sk_covacc_set_thresholds is called with a list
+    cov_thr thr;                                            // thr.n = 0: off
+    uint32_t *d_thr_max;                                    // [total_rows] each row's highest class since the last finish
+    unsigned long long *d_thr_cnt;                          // [nm x COV_THR_CLASSES] entries per class, then as many: rows per class
+    uint32_t *d_tots; size_t tots_cap;                      // sk_covacc_add_rows_hits' upload of the totals
+    bool thr_dirty; double ms_thr;                          // something was classified since the last finish; the finishing passes' device time
 };
 
 static void cov_t0(sk_covacc *a) { if (a->timed) (void)hipEventRecord(a->ev0, a->stream); }
@@ -447,6 +584,12 @@ extern "C" int sk_covacc_mark_timing_(sk_covacc *a, double *ms_mark)
     *ms_mark = a->ms_mark;
     return SK_OK;
 }
+extern "C" int sk_covacc_thresholds_timing_(sk_covacc *a, double *ms_thr)
+{
+    if (!a || !ms_thr) return SK_E_ARG;
+    *ms_thr = a->ms_thr;
+    return SK_OK;
+}
 
 #define CA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sk_fail_(a->ctx, SK_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
@@ -474,6 +617,7 @@ extern "C" void sk_covacc_destroy(sk_covacc *a)
     (void)hipFree(a->d_region); (void)hipFree(a->d_nreg); (void)hipFree(a->d_reg_base); (void)hipFree(a->d_reg_out);
     (void)hipFree(a->d_fp); (void)hipFree(a->d_starts); (void)hipFree(a->d_spec);
     (void)hipFree(a->d_irank); (void)hipFree(a->d_rec_nbits); (void)hipFree(a->d_blk); (void)hipFree(a->d_stray);
+    (void)hipFree(a->d_thr_max); (void)hipFree(a->d_thr_cnt); (void)hipFree(a->d_tots);
     if (a->timed) { (void)hipEventDestroy(a->ev0); (void)hipEventDestroy(a->ev1); }
     if (a->h_bad) (void)hipHostFree(a->h_bad);
     if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -633,7 +777,14 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
                 hipLaunchKernelGGL(covacc_scatter, dim3(cov_grid(side[k].nrecs)), dim3(256), 0, a->stream, side[k].recs, side[k].nrecs, ns,
                                    side[k].nrec, side[k].r0, side[k].step, npairs, a->d_tot, clear);
         for (uint32_t k = 0; k < nsides && !clear; k++)
-            if (side[k].nhits)
+            if (side[k].nhits && a->thr.n) {                  // (thresholds: the same fold, every entry classified as well)
+                hipLaunchKernelGGL(covacc_hits_thr, dim3(cov_grid(side[k].nhits)), dim3(256), 0, a->stream, side[k].hits, side[k].nhits,
+                                   side[k].rec_start, side[k].nrec, ns, members ? 1 : 0, side[k].r0, side[k].step, npairs,
+                                   (const uint32_t *)a->d_tot, a->min_hits, a->d_depth, (const uint64_t *)a->d_base + member0,
+                                   (const uint32_t *)a->d_nrows + member0, a->d_bad, a->thr, a->d_thr_max,
+                                   a->d_thr_cnt + (size_t)member0 * COV_THR_CLASSES);
+                a->thr_dirty = true;
+            } else if (side[k].nhits)
                 hipLaunchKernelGGL(covacc_hits, dim3(cov_grid(side[k].nhits)), dim3(256), 0, a->stream, side[k].hits, side[k].nhits,
                                    side[k].rec_start, side[k].nrec, ns, members ? 1 : 0, side[k].r0, side[k].step, npairs,
                                    (const uint32_t *)a->d_tot, a->min_hits, a->d_depth, (const uint64_t *)a->d_base + member0,
@@ -657,6 +808,7 @@ extern "C" int sk_covacc_add_rows(sk_covacc *a, uint32_t member, const uint32_t 
 {
     if (!a || (n && !rows)) return SK_E_ARG;
     if (member >= a->nm) return sk_fail_(a->ctx, SK_E_ARG, "member %u: the accumulator has %u", member, a->nm);
+    if (a->thr.n) return sk_fail_(a->ctx, SK_E_STATE, "thresholds are on: filtered rows carry no totals (sk_covacc_add_rows_hits)");
     if (!n) return SK_OK;
     for (uint64_t i = 0; i < n; i++)
         if (rows[i] >= a->nrows[member]) return sk_fail_(a->ctx, SK_E_ARG, "row %u: member %u has %u", rows[i], member, a->nrows[member]);
@@ -670,6 +822,31 @@ extern "C" int sk_covacc_add_rows(sk_covacc *a, uint32_t member, const uint32_t 
     CA_HIP(hipGetLastError());
     CA_HIP(hipStreamSynchronize(a->stream));
     cov_t1(a, &a->ms_fold);
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_add_rows_hits(sk_covacc *a, uint32_t member, const uint32_t *rows, const uint32_t *total_hits, uint64_t n)
+{
+    if (!a || (n && (!rows || !total_hits))) return SK_E_ARG;
+    if (member >= a->nm) return sk_fail_(a->ctx, SK_E_ARG, "member %u: the accumulator has %u", member, a->nm);
+    if (!n) return SK_OK;
+    for (uint64_t i = 0; i < n; i++)
+        if (rows[i] >= a->nrows[member]) return sk_fail_(a->ctx, SK_E_ARG, "row %u: member %u has %u", rows[i], member, a->nrows[member]);
+    CA_HIP(hipSetDevice(a->device));
+    int rc = cov_room(a, (void **)&a->d_rows, &a->rows_cap, (size_t)n * 4u, false);
+    if (rc == SK_OK) rc = cov_room(a, (void **)&a->d_tots, &a->tots_cap, (size_t)n * 4u, false);
+    if (rc != SK_OK) return rc;
+    cov_t0(a);
+    CA_HIP(hipMemcpyAsync(a->d_rows, rows, (size_t)n * 4u, hipMemcpyHostToDevice, a->stream));
+    CA_HIP(hipMemcpyAsync(a->d_tots, total_hits, (size_t)n * 4u, hipMemcpyHostToDevice, a->stream));
+    hipLaunchKernelGGL(covacc_rows_hits, dim3(cov_grid(n)), dim3(256), 0, a->stream, (const uint32_t *)a->d_rows, (const uint32_t *)a->d_tots, n,
+                       a->nrows[member], a->min_hits, a->d_depth + a->base[member], a->thr,
+                       a->thr.n ? a->d_thr_max + a->base[member] : (uint32_t *)NULL,
+                       a->thr.n ? a->d_thr_cnt + (size_t)member * COV_THR_CLASSES : (unsigned long long *)NULL);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_fold);
+    if (a->thr.n) a->thr_dirty = true;
     return SK_OK;
 }
 
@@ -933,5 +1110,73 @@ extern "C" int sk_covacc_mark_target(sk_covacc *a, sk_recur *r, uint32_t sample,
     CA_HIP(hipStreamSynchronize(a->stream));
     cov_t1(a, &a->ms_mark);
     *out_stray = stray;
+    return SK_OK;
+}
+
+// ---- thresholds ----
+static int cov_thr_clear(sk_covacc *a)
+{
+    if (a->d_thr_max && a->thr_dirty) {
+        CA_HIP(hipMemsetAsync(a->d_thr_max, 0, (size_t)(a->total_rows ? a->total_rows : 1u) * 4u, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_thr_cnt, 0, (size_t)a->nm * COV_THR_CLASSES * 16u, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+    }
+    a->thr_dirty = false;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_set_thresholds(sk_covacc *a, const int64_t *t, uint32_t n)
+{
+    if (!a || n > SK_COVACC_THRESHOLDS_MAX || (n && !t)) return SK_E_ARG;
+    for (uint32_t q = 0; q < n; q++)
+        if (t[q] < 0 || t[q] > 0x7FFFFFFEll || (q && t[q] <= t[q - 1])) return SK_E_ARG;
+    CA_HIP(hipSetDevice(a->device));
+    if (n && !a->d_thr_max) {                             // all zero: no row has an entry of any class
+        const size_t bytes = (size_t)(a->total_rows ? a->total_rows : 1u) * 4u, cb = (size_t)a->nm * COV_THR_CLASSES * 16u;
+        uint32_t *p = NULL; unsigned long long *c = NULL;
+        CA_HIP(hipMalloc((void **)&p, bytes));
+        if (hipMalloc((void **)&c, cb) != hipSuccess) { (void)hipFree(p); return sk_fail_(a->ctx, SK_E_HIP, "no room for the class counts"); }
+        a->d_thr_max = p; a->d_thr_cnt = c;
+        CA_HIP(hipMemsetAsync(a->d_thr_max, 0, bytes, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_thr_cnt, 0, cb, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+        a->thr_dirty = false;
+    }
+    const int rc = cov_thr_clear(a);                      // (whatever was classified under the old list is gone)
+    if (rc != SK_OK) return rc;
+    memset(&a->thr, 0, sizeof a->thr);
+    for (uint32_t q = 0; q < n; q++) a->thr.t[q] = (long long)t[q];
+    a->thr.n = n;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_finish_target_thresholds(sk_covacc *a, uint64_t *thr_unique, uint64_t *thr_total)
+{
+    if (!a || !thr_unique || !thr_total) return SK_E_ARG;
+    if (!a->thr.n) return sk_fail_(a->ctx, SK_E_STATE, "thresholds are off (sk_covacc_set_thresholds)");
+    CA_HIP(hipSetDevice(a->device));
+    const size_t ncell = (size_t)a->nm * COV_THR_CLASSES;
+    std::vector<unsigned long long> h(ncell * 2u, 0ull);
+    if (a->thr_dirty) {                                   // (nothing classified since the last finish: every number is zero)
+        cov_t0(a);
+        unsigned gx = (a->max_rows + 255u) / 256u;
+        gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
+        hipLaunchKernelGGL(covacc_thr_finish, dim3(gx, a->nm), dim3(256), 0, a->stream, a->d_thr_max, (const uint64_t *)a->d_base,
+                           (const uint32_t *)a->d_nrows, a->d_thr_cnt + ncell);
+        CA_HIP(hipGetLastError());
+        CA_HIP(hipMemcpyAsync(h.data(), a->d_thr_cnt, ncell * 16u, hipMemcpyDeviceToHost, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_thr_cnt, 0, ncell * 16u, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+        cov_t1(a, &a->ms_thr);
+        a->thr_dirty = false;
+    }
+    for (uint32_t m = 0; m < a->nm; m++) {                // class c counts for the thresholds 0 .. c - 1: suffix sums
+        unsigned long long u = 0, t = 0;
+        for (uint32_t q = a->thr.n; q-- > 0u; ) {
+            t += h[(size_t)m * COV_THR_CLASSES + q + 1u];
+            u += h[ncell + (size_t)m * COV_THR_CLASSES + q + 1u];
+            thr_unique[(size_t)m * a->thr.n + q] = u; thr_total[(size_t)m * a->thr.n + q] = t;
+        }
+    }
     return SK_OK;
 }

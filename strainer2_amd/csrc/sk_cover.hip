@@ -348,3 +348,132 @@ out:
     sk_recur_destroy(r);
     return rc;
 }
+
+// ---- a hit list at several thresholds (include/strainer_kmer.h has the rule; coverage_depth --thresholds) ----
+// cov_count_depth's insert with the highest class of a key's lines beside its slot instead of their number: a line's class is the
+// number of thresholds its pair's total exceeds, a line of class 0 counts nowhere and is not inserted.  cov_thr_sweep then bins each
+// sample's slots by class as cov_spectrum bins them by depth; the host takes the suffix sums.  The lines per sample and class are
+// counted by the host in the pass that sizes the samples' segments, which has to classify every line anyway.
+struct cov_thr_list { long long t[SK_COVACC_THRESHOLDS_MAX]; uint32_t n; };
+
+__global__ void cov_thr_insert(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ sample, const uint32_t *__restrict__ total_hits,
+                               uint64_t n, uint32_t nsamples, const uint64_t *__restrict__ seg_base, const uint64_t *__restrict__ seg_mask,
+                               cov_thr_list th, unsigned long long *__restrict__ table, uint32_t *__restrict__ cls)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t nt = th.n < SK_COVACC_THRESHOLDS_MAX ? th.n : SK_COVACC_THRESHOLDS_MAX;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t s = sample[i];
+        if (s >= nsamples) continue;                          // (never: the host has checked)
+        uint32_t c = 0;
+        for (uint32_t q = 0; q < nt; q++) c += (long long)total_hits[i] > th.t[q] ? 1u : 0u;
+        if (!c) continue;
+        const uint64_t k = keys[i], base = seg_base[s], mask = seg_mask[s];
+        uint64_t slot = cov_mix(k) & mask;
+        for (;;) {                                            // (ends: the segment has twice the slots of the sample's lines of class >= 1)
+            const unsigned long long old = atomicCAS(&table[base + slot], COV_EMPTY, (unsigned long long)k);
+            if (old == COV_EMPTY || old == k) break;
+            slot = (slot + 1) & mask;
+        }
+        atomicMax(&cls[base + slot], c);
+    }
+}
+
+// blockIdx.y = sample (and on by gridDim.y): out[s * (MAX + 1) + c] = the sample's keys whose highest class is c
+__global__ void __launch_bounds__(256) cov_thr_sweep(const uint32_t *__restrict__ cls, const uint64_t *__restrict__ seg_base,
+                                                     const uint64_t *__restrict__ seg_mask, uint32_t nsamples, unsigned long long *__restrict__ out)
+{
+    __shared__ uint32_t h_n[SK_COVACC_THRESHOLDS_MAX + 1u];
+    for (uint32_t s = blockIdx.y; s < nsamples; s += gridDim.y) {
+        const uint64_t nslot = seg_mask[s] + 1u;
+        if ((uint64_t)blockIdx.x * 256u >= nslot) continue;   // (the whole workgroup)
+        const uint32_t *c = cls + seg_base[s];
+        if (threadIdx.x <= SK_COVACC_THRESHOLDS_MAX) h_n[threadIdx.x] = 0u;
+        __syncthreads();
+        for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nslot; i += (uint64_t)gridDim.x * 256u) {
+            const uint32_t v = c[i];
+            if (v && v <= SK_COVACC_THRESHOLDS_MAX) atomicAdd(&h_n[v], 1u);      // (at most half of the slots are taken)
+        }
+        __syncthreads();
+        if (threadIdx.x <= SK_COVACC_THRESHOLDS_MAX && h_n[threadIdx.x])
+            atomicAdd(out + (size_t)s * (SK_COVACC_THRESHOLDS_MAX + 1u) + threadIdx.x, (unsigned long long)h_n[threadIdx.x]);
+        __syncthreads();
+    }
+}
+
+extern "C" int sk_distinct_thresholds(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, const uint32_t *total_hits, uint64_t n,
+                                      uint32_t nsamples, const int64_t *t, uint32_t nt, uint64_t *out_unique, uint64_t *out_total)
+{
+    const uint32_t NC = SK_COVACC_THRESHOLDS_MAX + 1u;
+    if (!ctx || !out_unique || !out_total || !t || nt < 1u || nt > SK_COVACC_THRESHOLDS_MAX || (n && (!keys || !sample || !total_hits))) return SK_E_ARG;
+    for (uint32_t q = 0; q < nt; q++)
+        if (t[q] < 0 || t[q] > 0x7FFFFFFEll || (q && t[q] <= t[q - 1])) return SK_E_ARG;
+    if (nsamples == 0) return n ? SK_E_ARG : SK_OK;
+    memset(out_unique, 0, (size_t)nsamples * nt * 8);
+    memset(out_total, 0, (size_t)nsamples * nt * 8);
+    if (!n) return SK_OK;
+    cov_thr_list th;
+    memset(&th, 0, sizeof th);
+    for (uint32_t q = 0; q < nt; q++) th.t[q] = (long long)t[q];
+    th.n = nt;
+    std::vector<uint64_t> lines((size_t)nsamples * NC, 0), cnt(nsamples, 0), base(nsamples), mask(nsamples);
+    for (uint64_t i = 0; i < n; i++) {
+        if (sample[i] >= nsamples) return sk_fail_(ctx, SK_E_ARG, "sample %u out of range", sample[i]);
+        if (keys[i] == COV_EMPTY) return sk_fail_(ctx, SK_E_ARG, "reserved key value");
+        uint32_t c = 0;
+        for (uint32_t q = 0; q < nt; q++) c += (long long)total_hits[i] > th.t[q] ? 1u : 0u;
+        lines[(size_t)sample[i] * NC + c]++;
+        if (c) cnt[sample[i]]++;
+    }
+    uint64_t slots = 0, max_seg = 0;
+    for (uint32_t s = 0; s < nsamples; s++) {
+        uint64_t c = 2;
+        while (c < 2 * cnt[s]) c <<= 1;
+        base[s] = slots; mask[s] = c - 1; slots += c;
+        if (c > max_seg) max_seg = c;
+    }
+    int rc = SK_OK;
+    void *d_keys = NULL, *d_sample = NULL, *d_tot = NULL, *d_seg = NULL, *d_table = NULL, *d_cls = NULL, *d_out = NULL;
+    std::vector<unsigned long long> h((size_t)nsamples * NC);
+#define COV_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = sk_fail_(ctx, SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); goto out; } } while (0)
+    COV_HIP(hipSetDevice(sk_ctx_device_(ctx)));
+    COV_HIP(hipMalloc(&d_keys, n * 8));
+    COV_HIP(hipMalloc(&d_sample, n * 4));
+    COV_HIP(hipMalloc(&d_tot, n * 4));
+    COV_HIP(hipMalloc(&d_seg, (size_t)nsamples * 16));
+    COV_HIP(hipMalloc(&d_table, slots * 8));
+    COV_HIP(hipMalloc(&d_cls, slots * 4));
+    COV_HIP(hipMalloc(&d_out, h.size() * 8));
+    COV_HIP(hipMemcpy(d_keys, keys, n * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_sample, sample, n * 4, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_tot, total_hits, n * 4, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_seg, base.data(), (size_t)nsamples * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy((uint64_t *)d_seg + nsamples, mask.data(), (size_t)nsamples * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemset(d_table, 0xFF, slots * 8));
+    COV_HIP(hipMemset(d_cls, 0, slots * 4));
+    COV_HIP(hipMemset(d_out, 0, h.size() * 8));
+    {
+        const uint64_t g = (n + 255) / 256, gs = (max_seg + 255u) / 256u;
+        hipLaunchKernelGGL(cov_thr_insert, dim3((unsigned)(g > 65536u ? 65536u : g)), dim3(256), 0, 0, (const uint64_t *)d_keys,
+                           (const uint32_t *)d_sample, (const uint32_t *)d_tot, n, nsamples, (const uint64_t *)d_seg,
+                           (const uint64_t *)d_seg + nsamples, th, (unsigned long long *)d_table, (uint32_t *)d_cls);
+        COV_HIP(hipGetLastError());
+        hipLaunchKernelGGL(cov_thr_sweep, dim3((unsigned)(gs > 256u ? 256u : gs), nsamples > 4096u ? 4096u : nsamples), dim3(256), 0, 0,
+                           (const uint32_t *)d_cls, (const uint64_t *)d_seg, (const uint64_t *)d_seg + nsamples, nsamples,
+                           (unsigned long long *)d_out);
+    }
+    COV_HIP(hipGetLastError());
+    COV_HIP(hipMemcpy(h.data(), d_out, h.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < nsamples; s++) {                 // class c counts for the thresholds 0 .. c - 1: suffix sums
+        uint64_t u = 0, l = 0;
+        for (uint32_t q = nt; q-- > 0u; ) {
+            u += h[(size_t)s * NC + q + 1u]; l += lines[(size_t)s * NC + q + 1u];
+            out_unique[(size_t)s * nt + q] = u; out_total[(size_t)s * nt + q] = l;
+        }
+    }
+#undef COV_HIP
+out:
+    (void)hipFree(d_keys); (void)hipFree(d_sample); (void)hipFree(d_tot); (void)hipFree(d_seg); (void)hipFree(d_table); (void)hipFree(d_cls);
+    (void)hipFree(d_out);
+    return rc;
+}

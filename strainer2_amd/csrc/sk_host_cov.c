@@ -109,6 +109,11 @@ typedef struct {
     uint64_t **sp_n, *sp_deep; uint32_t nsp_s, sp_bins;        /* the depth spectrum per sample: n[1..D], n[>D] (sp_bins = D + 1 each, or NULL) and hits[>D] */
     uint64_t *rc_hist, *rc_pairs; uint32_t *rc_smp, rc_T;      /* recurrence handed in (skc_add_recurrence_counts): n[0..T] (entry 0 unused), shared[T x T] or NULL,
                                                                   both by the caller's sample ordinals; rc_smp[ordinal] = the sample */
+    /* thresholds (th_nt = 0: off): the list; every hit line above t[0], whatever the main filter does with it, with its pair's total;
+     * th_bad: a k-mer field among them that is no A/C/G/T word of the one length; per sample the numbers handed in (th_nt each, or NULL) */
+    int64_t   th_t[SK_COVACC_THRESHOLDS_MAX]; uint32_t th_nt;
+    uint64_t *th_key; uint32_t *th_sample, *th_tot; uint64_t th_n, th_cap; size_t th_klen; int th_bad;
+    uint64_t **th_u, **th_tt; uint32_t nth_s;
 } hitlist;
 
 enum { COV_OK = 0, COV_OPEN, COV_FIELDS, COV_INT, COV_NOMEM };
@@ -191,10 +196,56 @@ static int cov_push(hitlist *h, uint32_t g, uint64_t key)
     return COV_OK;
 }
 
+/* thresholds: how many of the list a pair's total exceeds (0: the line counts at no threshold) */
+static uint32_t th_class(const hitlist *h, int64_t total)
+{
+    uint32_t q, c = 0;
+    for (q = 0; q < h->th_nt; q++) c += total > h->th_t[q];
+    return c;
+}
+
+/* ... and one line of class >= 1: its sample, key and total (totals beyond 32 bits exceed every threshold alike) */
+static int th_push(hitlist *h, uint32_t g, uint64_t key, int64_t total)
+{
+    if (h->th_n == h->th_cap) {
+        const uint64_t cap = h->th_cap ? h->th_cap * 2 : 1u << 16;
+        uint64_t *k2 = realloc(h->th_key, cap * sizeof *k2);
+        uint32_t *s2, *t2;
+        if (!k2) return COV_NOMEM;
+        h->th_key = k2;
+        if (!(s2 = realloc(h->th_sample, cap * sizeof *s2))) return COV_NOMEM;
+        h->th_sample = s2;
+        if (!(t2 = realloc(h->th_tot, cap * sizeof *t2))) return COV_NOMEM;
+        h->th_tot = t2;
+        h->th_cap = cap;
+    }
+    h->th_key[h->th_n] = key;
+    h->th_sample[h->th_n] = g;
+    h->th_tot[h->th_n++] = total > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)total;
+    return COV_OK;
+}
+
+/* ... of a hit list's text: the k-mer field packed, if it is an A/C/G/T word of the length of all the others; th_bad otherwise */
+static int th_push_text(hitlist *h, uint32_t g, const char *ktext, size_t klen, int64_t total)
+{
+    uint64_t key = 0;
+    size_t j;
+    int plain = klen >= 1 && klen <= 31 && (h->th_klen == 0 || h->th_klen == klen);
+    for (j = 0; plain && j < klen; j++) {
+        const unsigned cde = sk_code((uint8_t)ktext[j]);
+        if (ktext[j] != "ACGT"[cde]) plain = 0;
+        key = (key << 2) | (cde & 3u);
+    }
+    if (!plain) { h->th_bad = 1; return COV_OK; }
+    h->th_klen = klen;
+    return th_push(h, g, key, total);
+}
+
 static int hit_line(hitlist *h, char *s, size_t len, int64_t min_hits)
 {
     char *f[7], *end = s + len, *p;
     int nf = 1;
+    uint32_t cls;
     int64_t a, b, c, d, g;
     const char *sn, *kend;
     size_t klen, j;
@@ -205,11 +256,20 @@ static int hit_line(hitlist *h, char *s, size_t len, int64_t min_hits)
     if (nf < 6) return COV_FIELDS;
     if (!skp_int(f[1], f[2] - 1, &a) || !skp_int(f[2], f[3] - 1, &b) || !skp_int(f[3], f[4] - 1, &c) || !skp_int(f[4], f[5] - 1, &d))
         return COV_INT;
-    if (!(a + c > min_hits)) return COV_OK;           /* hits of the read pair, informative or not (:83-86) */
+    cls = th_class(h, a + c);
+    if (!(a + c > min_hits)) {                        /* hits of the read pair, informative or not (:83-86) */
+        if (!cls) return COV_OK;
+        sn = base_of(f[0], f[1] - 1);                 /* (thresholds: a line below the main filter and above t[0]; it names its sample
+                                                         and changes nothing else of what the main table is made from) */
+        if ((g = name_get(&h->smp, sn, (size_t)(f[1] - 1 - sn))) < 0) return COV_NOMEM;
+        kend = nf > 6 ? f[6] - 1 : end;
+        return th_push_text(h, (uint32_t)g, f[5], (size_t)(kend - f[5]), a + c);
+    }
     sn = base_of(f[0], f[1] - 1);
     if ((g = cov_sample(h, sn, (size_t)(f[1] - 1 - sn))) < 0) return COV_NOMEM;
     kend = nf > 6 ? f[6] - 1 : end;
     klen = (size_t)(kend - f[5]);
+    if (cls) { const int rc = th_push_text(h, (uint32_t)g, f[5], klen, a + c); if (rc) return rc; }
     if (!h->general) {
         int plain = klen >= 1 && klen <= 31 && (h->klen == 0 || h->klen == klen);
         for (j = 0; plain && j < klen; j++) {
@@ -426,6 +486,8 @@ static void hitlist_free(hitlist *h)
     free(h->sp_n); free(h->sp_deep);
     free(h->given_u); free(h->given_t);
     free(h->rc_hist); free(h->rc_pairs); free(h->rc_smp);
+    for (s = 0; s < h->nth_s; s++) { free(h->th_u[s]); free(h->th_tt[s]); }
+    free(h->th_u); free(h->th_tt); free(h->th_key); free(h->th_sample); free(h->th_tot);
     free(h->key); free(h->sample); free(h->depth_order); free(h->eval_order); free(h->gid); free(h->gsample);
     names_free(&h->smp); names_free(&h->text);
     memset(h, 0, sizeof *h);
@@ -449,6 +511,10 @@ int skc_add_hit(skc_acc *a, const char *metagenome, int64_t hits_pe1, int64_t hi
 {
     const char *sn;
     int64_t g;
+    if (a->h.th_nt && th_class(&a->h, hits_pe1 + hits_pe2)) {         /* thresholds: the line above t[0], kept with its total */
+        sn = base_of(metagenome, metagenome + strlen(metagenome));
+        if ((g = name_get(&a->h.smp, sn, strlen(sn))) < 0 || th_push(&a->h, (uint32_t)g, (uint64_t)row, hits_pe1 + hits_pe2) != COV_OK) return -1;
+    }
     if (!(hits_pe1 + hits_pe2 > a->min_hits)) return 0;
     sn = base_of(metagenome, metagenome + strlen(metagenome));
     if ((g = cov_sample(&a->h, sn, strlen(sn))) < 0) return -1;
@@ -670,6 +736,130 @@ int skc_report_spectrum(skc_acc *a, const char *hits_file_name, uint32_t max_dep
     return 0;
 }
 
+/* ---- thresholds (strain_detect --coverage-thresholds, coverage_depth --thresholds; include/strainer_kmer.h has the rule) ---- */
+/* "t1,t2,...": 0 on success; otherwise `why` says what is wrong with the list */
+int skc_parse_threshold_list(const char *text, int64_t *t, uint32_t *n, char *why, size_t why_cap)
+{
+    const char *p = text;
+    *n = 0;
+    for (;;) {
+        const char *e = p;
+        int64_t v;
+        while (*e && *e != ',') e++;
+        if (e == p) { snprintf(why, why_cap, "an empty field"); return 1; }
+        if (*n == SK_COVACC_THRESHOLDS_MAX) { snprintf(why, why_cap, "more than %u thresholds", SK_COVACC_THRESHOLDS_MAX); return 1; }
+        if (e - p > 18 || !skp_int(p, e, &v)) { snprintf(why, why_cap, "'%.*s' is no integer from 0 to 2147483646", (int)(e - p > 40 ? 40 : e - p), p); return 1; }
+        if (v < 0 || v > 0x7FFFFFFEll) { snprintf(why, why_cap, "%lld is out of range (0 to 2147483646)", (long long)v); return 1; }
+        if (*n && v <= t[*n - 1]) { snprintf(why, why_cap, "%lld after %lld: the list must ascend strictly", (long long)v, (long long)t[*n - 1]); return 1; }
+        t[(*n)++] = v;
+        if (!*e) return 0;
+        p = e + 1;
+    }
+}
+
+int skc_set_thresholds(skc_acc *a, const int64_t *t, uint32_t n)
+{
+    uint32_t q;
+    if (!a || n > SK_COVACC_THRESHOLDS_MAX || (n && !t) || a->h.th_n) return -1;
+    for (q = 0; q < n; q++) {
+        if (t[q] < 0 || t[q] > 0x7FFFFFFEll || (q && t[q] <= t[q - 1])) return -1;
+        a->h.th_t[q] = t[q];
+    }
+    a->h.th_nt = n;
+    return 0;
+}
+
+static int th_room(hitlist *h, uint32_t g)
+{
+    if (g >= h->nth_s) {
+        const uint32_t n2 = g + 16u;
+        uint64_t **u = realloc(h->th_u, (size_t)n2 * sizeof *u), **t;
+        if (!u) return -1;
+        h->th_u = u;
+        memset(u + h->nth_s, 0, (size_t)(n2 - h->nth_s) * sizeof *u);
+        if (!(t = realloc(h->th_tt, (size_t)n2 * sizeof *t))) return -1;       /* (nth_s stays: the new th_u entries are NULL and unread) */
+        h->th_tt = t;
+        memset(t + h->nth_s, 0, (size_t)(n2 - h->nth_s) * sizeof *t);
+        h->nth_s = n2;
+    }
+    if (!h->th_u[g] && !(h->th_u[g] = calloc(SK_COVACC_THRESHOLDS_MAX, sizeof **h->th_u))) return -1;
+    if (!h->th_tt[g] && !(h->th_tt[g] = calloc(SK_COVACC_THRESHOLDS_MAX, sizeof **h->th_tt))) return -1;
+    return 0;
+}
+
+/* a metagenome's numbers per threshold, counted elsewhere (n = the list's length): called next to skc_add_counts */
+int skc_add_threshold_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t n)
+{
+    hitlist *h = &a->h;
+    const char *sn = base_of(metagenome, metagenome + strlen(metagenome));
+    const int64_t g = name_get(&h->smp, sn, strlen(sn));
+    uint32_t q;
+    if (g < 0 || n != h->th_nt || th_room(h, (uint32_t)g)) return -1;
+    for (q = 0; q < n; q++) { h->th_u[g][q] += unique[q]; h->th_tt[g][q] += total[q]; }
+    return 0;
+}
+
+/* the table of what th_u / th_tt hold, samples in the main table's order: one line per sample and threshold, zeros included */
+static void thresholds_print(const hitlist *h, const char *hits_file_name, FILE *out)
+{
+    char *strain = strdup(base_of(hits_file_name, hits_file_name + strlen(hits_file_name)));
+    const size_t sl = strain ? strlen(strain) : 0;
+    uint32_t k, q;
+    if (sl >= 13 && !memcmp(strain + sl - 12, "kmer_hits", 9) && !memcmp(strain + sl - 2, "gz", 2)) strain[sl - 13] = 0;
+    fputs("strain_name\tmetagenome\tmin_kmer_hits\tunique_observed_informative_kmers\ttotal_observed_informative_kmers\n", out);
+    for (k = 0; k < h->ndepth; k++) {
+        const uint32_t s = h->depth_order[k];
+        const uint64_t *u = s < h->nth_s ? h->th_u[s] : NULL, *t = s < h->nth_s ? h->th_tt[s] : NULL;
+        for (q = 0; q < h->th_nt; q++)
+            fprintf(out, "%s\t%s\t%lld\t%llu\t%llu\n", strain ? strain : "", h->smp.name[s], (long long)h->th_t[q],
+                    (unsigned long long)(u ? u[q] : 0u), (unsigned long long)(t ? t[q] : 0u));
+    }
+    free(strain);
+    fflush(out);
+}
+
+typedef struct { uint64_t v; uint32_t cls; } th_item;
+static int cmp_th_item(const void *x, const void *y)
+{
+    const th_item *a = x, *b = y;
+    return a->v < b->v ? -1 : a->v > b->v ? 1 : 0;
+}
+
+/* The table: call it after skc_report.  An accumulator that was fed hits folds its kept lines here -- a line of class c counts for
+ * the thresholds below c, a (sample, row) pair for those below its highest class -- one that was fed counts prints what
+ * skc_add_threshold_counts left. */
+int skc_report_thresholds(skc_acc *a, const char *hits_file_name, FILE *out, FILE *err)
+{
+    hitlist *h = &a->h;
+    if (!h->th_nt) return 1;
+    if (cov_order_trailers(h)) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+    if (!h->given && h->th_n) {
+        th_item *v = malloc((size_t)h->th_n * sizeof *v);
+        uint64_t i, j;
+        uint32_t q;
+        if (!v) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+        for (i = 0; i < h->th_n; i++) {
+            v[i].v = ((uint64_t)h->th_sample[i] << 32) | (h->th_key[i] & 0xFFFFFFFFu);
+            v[i].cls = th_class(h, (int64_t)h->th_tot[i]);
+        }
+        qsort(v, (size_t)h->th_n, sizeof *v, cmp_th_item);
+        for (i = 0; i < h->th_n; i = j) {
+            const uint32_t g = (uint32_t)(v[i].v >> 32);
+            uint32_t top = 0;
+            if (th_room(h, g)) { free(v); fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+            for (j = i; j < h->th_n && v[j].v == v[i].v; j++) {
+                for (q = 0; q < v[j].cls; q++) h->th_tt[g][q]++;
+                if (v[j].cls > top) top = v[j].cls;
+            }
+            for (q = 0; q < top; q++) h->th_u[g][q]++;
+        }
+        free(v);
+        h->th_n = 0;                                 /* (folded: a second report prints the same table) */
+    }
+    thresholds_print(h, hits_file_name, out);
+    return 0;
+}
+
 /* ---- recurrence (strain_detect --coverage-recurrence, coverage_depth --recurrence; include/strainer_kmer.h has the rule) ---- */
 /* a run's tables, counted elsewhere: T samples by the caller's ordinals (metagenome[i] names ordinal i; every one of them has been
  * handed to skc_add_counts or skc_add_trailer, so the sample exists), hist[T + 1] (entry 0 is not used) and pairs[T x T] or NULL.
@@ -878,8 +1068,41 @@ done:
     return status;
 }
 
+#pragma weak sk_distinct_thresholds
+/* coverage_depth --thresholds: the kept lines' (sample, packed k-mer, total) triples, counted on the device, to the table at `path` */
+static int cov_thresholds_file(hitlist *h, sk_ctx *ctx, const char *kfile, const char *path, FILE *err)
+{
+    const uint32_t ns = h->smp.n, nt = h->th_nt;
+    uint64_t *buf = NULL;
+    FILE *f;
+    uint32_t s, q;
+    int rc, status = 1;
+    if (ns) {
+        if (!(buf = calloc((size_t)ns * nt * 2u, sizeof *buf))) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+        rc = sk_distinct_thresholds(ctx, h->th_key, h->th_sample, h->th_tot, h->th_n, ns, h->th_t, nt, buf, buf + (size_t)ns * nt);
+        if (rc != SK_OK) { fprintf(err, "coverage_depth: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx)); goto done; }
+        for (s = 0; s < ns; s++) {
+            if (!buf[(size_t)ns * nt + (size_t)s * nt]) continue;      /* (no line above t[0]: zeros are printed without) */
+            if (th_room(h, s)) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+            for (q = 0; q < nt; q++) { h->th_u[s][q] = buf[(size_t)s * nt + q]; h->th_tt[s][q] = buf[(size_t)ns * nt + (size_t)s * nt + q]; }
+        }
+    }
+    if (!(f = fopen(path, "w"))) { fprintf(err, "coverage_depth: could not write %s\n", path); goto done; }
+    thresholds_print(h, kfile, f);
+    status = ferror(f) ? 1 : 0;
+    if (fclose(f)) status = 1;
+done:
+    free(buf);
+    return status;
+}
+
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
 {
+    const char *th_file = NULL, *th_list = NULL;
+    int want_th = 0;
+    char *th_path = NULL;
+    int64_t th_t[SK_COVACC_THRESHOLDS_MAX] = { 0, 1, 2, 3, 5, 10, 20, 50 };
+    uint32_t th_nt = 8;
     const char *kfile = NULL, *mtext = NULL, *bfile = NULL, *env, *sp_file = NULL, *sp_max = NULL, *rc_file = NULL, *rp_file = NULL;
     int64_t min_hits = 1, sp_d = 255;
     int i, bad = 0, rc, status = 1, device = 0, want_sp = 0, want_rc = 0, want_rp = 0;
@@ -890,7 +1113,8 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
     for (i = 1; i < argc; i++) {                     /* :27-41 */
         if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
             fprintf(out, "usage: coverage_depth [-h] --kmer_hits_file FILE [--min_kmer_hits N] [--background_metagenomes_file FILE]\n"
-                         "                      [--spectrum[=FILE] [--spectrum-max D]] [--recurrence[=FILE] [--recurrence-pairs[=FILE]]]\n");
+                         "                      [--spectrum[=FILE] [--spectrum-max D]] [--recurrence[=FILE] [--recurrence-pairs[=FILE]]]\n"
+                         "                      [--thresholds[=FILE] [--threshold-list t1,t2,...]]\n");
             return 0;
         }
         /* "--spectrum[=FILE] [--spectrum-max D]" (extension): the depth spectrum beside the table, see include/strainer_kmer.h */
@@ -900,6 +1124,10 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         if (!strncmp(argv[i], "--recurrence", 12) && (argv[i][12] == 0 || argv[i][12] == '=')) { want_rc = 1; rc_file = argv[i][12] ? argv[i] + 13 : NULL; continue; }
         if (!strcmp(argv[i], "--spectrum-max") && i + 1 < argc) { sp_max = argv[++i]; continue; }
         if (!strncmp(argv[i], "--spectrum-max=", 15)) { sp_max = argv[i] + 15; continue; }
+        /* "--thresholds[=FILE] [--threshold-list t1,t2,...]" (extension): the table's two numbers at several --min_kmer_hits */
+        if (!strncmp(argv[i], "--thresholds", 12) && (argv[i][12] == 0 || argv[i][12] == '=')) { want_th = 1; th_file = argv[i][12] ? argv[i] + 13 : NULL; continue; }
+        if (!strcmp(argv[i], "--threshold-list") && i + 1 < argc) { th_list = argv[++i]; continue; }
+        if (!strncmp(argv[i], "--threshold-list=", 17)) { th_list = argv[i] + 17; continue; }
         if (cov_opt(argc, argv, &i, "-k", "--kmer_hits_file", &kfile, err, &bad)) { if (bad) return 2; continue; }
         if (cov_opt(argc, argv, &i, "-m", "--min_kmer_hits", &mtext, err, &bad)) { if (bad) return 2; continue; }
         if (cov_opt(argc, argv, &i, "-b", "--background_metagenomes_file", &bfile, err, &bad)) { if (bad) return 2; continue; }
@@ -918,8 +1146,15 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
     }
     if (want_sp && !sk_distinct_spectrum) { fprintf(err, "coverage_depth: error: --spectrum: this build has no device spectrum\n"); return 2; }
     if (want_rp && !want_rc) { fprintf(err, "coverage_depth: error: --recurrence-pairs goes with --recurrence\n"); return 2; }
+    if (th_list && !want_th) { fprintf(err, "coverage_depth: error: --threshold-list goes with --thresholds\n"); return 2; }
+    if (th_list) {
+        char why[160];
+        if (skc_parse_threshold_list(th_list, th_t, &th_nt, why, sizeof why)) { fprintf(err, "coverage_depth: error: --threshold-list %s: %s\n", th_list, why); return 2; }
+    }
+    if (want_th && !sk_distinct_thresholds) { fprintf(err, "coverage_depth: error: --thresholds: this build has no device thresholds\n"); return 2; }
     if (want_rc && !sk_distinct_recurrence) { fprintf(err, "coverage_depth: error: --recurrence: this build has no device recurrence\n"); return 2; }
     memset(&h, 0, sizeof h);
+    if (want_th) { memcpy(h.th_t, th_t, sizeof h.th_t); h.th_nt = th_nt; }
     rc = read_hits(&h, kfile, min_hits);
     if (rc == COV_OPEN) { fprintf(err, "coverage_depth: could not read %s\n", kfile); goto done; }
     if (rc == COV_FIELDS) { fprintf(err, "coverage_depth: %s: a line has too few tab-separated fields\n", kfile); goto done; }
@@ -929,6 +1164,11 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         fprintf(err, "coverage_depth: --spectrum: %s has k-mer fields that are not A/C/G/T words of one length: the depth of a k-mer is not defined there\n", kfile);
         goto done;
     }
+    if (want_th && (h.general || h.th_bad)) {
+        fprintf(err, "coverage_depth: --thresholds: %s has k-mer fields that are not A/C/G/T words of one length: a distinct k-mer is not defined there\n", kfile);
+        goto done;
+    }
+    if (want_th && !(th_path = cov_table_path(th_file, kfile, ".coverage_thresholds"))) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
     if (want_rc && h.general) {
         fprintf(err, "coverage_depth: --recurrence: %s has k-mer fields that are not A/C/G/T words of one length: a k-mer seen in two samples is not defined there\n", kfile);
         goto done;
@@ -951,9 +1191,10 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
     status = cov_report(&h, ctx, kfile, bfile, out, err);
     if (status == 0 && want_sp) status = cov_spectrum_file(&h, ctx, kfile, (uint32_t)sp_d, sp_path, err);
     if (status == 0 && want_rc) status = cov_recurrence_files(&h, ctx, kfile, rc_path, rp_path, err);
+    if (status == 0 && want_th) status = cov_thresholds_file(&h, ctx, kfile, th_path, err);
 done:
     fflush(out);
-    free(sp_path); free(rc_path); free(rp_path);
+    free(sp_path); free(rc_path); free(rp_path); free(th_path);
     sk_ctx_destroy(ctx);
     hitlist_free(&h);
     return status;

@@ -295,7 +295,8 @@ static char *sm_cov_path(const char *hits)
 static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
 {
     char **v = (char **)malloc(((size_t)argc + 1) * sizeof *v);
-    int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0, want_rc = 0, want_rp = 0;
+    int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0, want_rc = 0, want_rp = 0, want_th = 0;
+    const char *th_list = NULL;
     if (!v) return 1;
     for (c = 0; c < argc; c++) {
         if (c > 0 && !strncmp(argv[c], "--coverage-depth", 16) && (argv[c][16] == 0 || argv[c][16] == '=')) {
@@ -354,6 +355,17 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
             want_rp = 1;
             continue;
         }
+        if (c > 0 && !strncmp(argv[c], "--coverage-thresholds", 21) && (argv[c][21] == 0 || argv[c][21] == '=')) {
+            if (argv[c][21] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-thresholds takes no file name (each strain's table goes next to its coverage table)\n");
+                free(v);
+                return 1;
+            }
+            want_th = 1;
+            continue;
+        }
+        if (c > 0 && !strcmp(argv[c], "--threshold-list") && c + 1 < argc) { th_list = argv[++c]; continue; }
+        if (c > 0 && !strncmp(argv[c], "--threshold-list=", 17)) { th_list = argv[c] + 17; continue; }
         if (c > 0 && !strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { c++; continue; }
         if (c > 0 && !strncmp(argv[c], "--spectrum-max=", 15)) continue;
         if (c > 0 && !strncmp(argv[c], "--panel-share", 13) && (argv[c][13] == 0 || argv[c][13] == '=')) {
@@ -382,6 +394,26 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
         fprintf(err, "kmer_scrub_count: --coverage-spectrum goes with --coverage-depth or --coverage-only: it bins their table's hits by depth\n");
         free(v);
         return 1;
+    }
+    if (th_list && !want_th) {
+        fprintf(err, "kmer_scrub_count: --threshold-list goes with --coverage-thresholds\n");
+        free(v);
+        return 1;
+    }
+    if (want_th && !*want_cov) {
+        fprintf(err, "kmer_scrub_count: --coverage-thresholds goes with --coverage-depth or --coverage-only: it gives their table's two numbers at several --min-kmer-hits\n");
+        free(v);
+        return 1;
+    }
+    if (th_list) {                                   /* (the list is read before the lists are: strain_detect runs after the scrub) */
+        int64_t t[SK_COVACC_THRESHOLDS_MAX];
+        uint32_t nt = 0;
+        char why[160];
+        if (skc_parse_threshold_list(th_list, t, &nt, why, sizeof why)) {
+            fprintf(err, "kmer_scrub_count: --threshold-list %s: %s\n", th_list, why);
+            free(v);
+            return 1;
+        }
     }
     if (want_rp && !want_rc) {
         fprintf(err, "kmer_scrub_count: --recurrence-pairs goes with --coverage-recurrence\n");

@@ -92,6 +92,8 @@ typedef struct {
     uint32_t   *tallybuf; uint32_t tallycap;
     int         job_rc;                    /* result of this strain's part of a pool job */
     uint32_t   *co_rows; uint64_t co_n, co_cap;   /* --coverage-only: rows of host-replayed passing hits on their way to the device's counters */
+    uint32_t   *co_tot;                        /* --coverage-thresholds: beside every such row its pair's h1 + h2 (the rows then pass min(--min-kmer-hits, t[0])) */
+    char *th_path;                             /* --coverage-thresholds: the table's path */
     /* --coverage-regions: the strain's region table, every row's region (rg.n = unplaced), informative rows per region, the table's path */
     skh_regions rg; uint32_t *row_region; uint64_t *reg_inf; char *rg_path;
     char *sp_path;                             /* --coverage-spectrum: the table's path */
@@ -1628,6 +1630,16 @@ static void sd_prefetch(sd_stream *st)
 #pragma weak sk_covacc_set_spectrum
 #pragma weak sk_covacc_finish_target_spectrum
 static struct { int on; uint32_t max; } sd_spec;
+/* --coverage-thresholds [--threshold-list t1,t2,...] (include/strainer_kmer.h has the rule): with the accumulators on the device every
+ * fold also classifies its entries by the list (sk_covacc_set_thresholds), replayed rows travel unfiltered with their pairs' totals
+ * (sk_covacc_add_rows_hits) and a pass of its own in front of the target's sweep yields the numbers
+ * (sk_covacc_finish_target_thresholds); with --coverage-depth, and where --coverage-only counts on the host, the host accumulator
+ * keeps the lines above t[0] and skc_report_thresholds folds them. */
+#pragma weak sk_covacc_set_thresholds
+#pragma weak sk_covacc_add_rows_hits
+#pragma weak sk_covacc_finish_target_thresholds
+#pragma weak sk_covacc_thresholds_timing_
+static struct { int on; uint32_t n; int64_t t[SK_COVACC_THRESHOLDS_MAX]; double ms_finish; } sd_thr;
 /* --coverage-recurrence [--recurrence-pairs] (include/strainer_kmer.h has the rule): with the accumulators on the device every unit
  * has one set of bit planes (sk_recur) over the run's target lines; the end of a target sets the bits of its non-zero rows
  * (sk_covacc_mark_target, right before the sweep) and the end of the run takes both tables once (sk_recur_finish) and hands them to
@@ -1686,6 +1698,7 @@ static void co_close(void)
         double f = 0, w = 0;
         if (sk_covacc_timing_ && sd_co.acc[k] && sk_covacc_timing_(sd_co.acc[k], 0, &f, &w) == SK_OK) { sd_co_ms_fold += f; sd_co_ms_sweep += w; }
         if (sd_rec.on && sk_covacc_mark_timing_ && sd_co.acc[k] && sk_covacc_mark_timing_(sd_co.acc[k], &f) == SK_OK) sd_rec.ms_mark += f;
+        if (sd_thr.on && sk_covacc_thresholds_timing_ && sd_co.acc[k] && sk_covacc_thresholds_timing_(sd_co.acc[k], &f) == SK_OK) sd_thr.ms_finish += f;
         if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
     }
     for (k = 0; k < sd_rec.nr; k++) {
@@ -1708,6 +1721,7 @@ static int co_open(sd_prog *p, uint32_t ns)
     if (!sk_covacc_create || !sk_covacc_pick || !sk_tally_collect_counts || !sk_union_tally_launch_ex ||
         (sd_rg.on && (!sk_covacc_set_regions || !sk_covacc_region_rows || !sk_covacc_finish_target_regions)) ||
         (sd_spec.on && (!sk_covacc_set_spectrum || !sk_covacc_finish_target_spectrum)) ||
+        (sd_thr.on && (!sk_covacc_set_thresholds || !sk_covacc_add_rows_hits || !sk_covacc_finish_target_thresholds)) ||
         (sd_rec.on && (!sk_recur_create || !sk_recur_finish || !sk_covacc_set_recurrence || !sk_covacc_mark_target))) {
         fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
         sd_co.host = 1;
@@ -1730,6 +1744,7 @@ static int co_open(sd_prog *p, uint32_t ns)
         if (rc != SK_OK) { sd_co.nacc = k; co_close(); return rc; }
         if (getenv("SK_SD_TIMING") && sk_covacc_timing_) (void)sk_covacc_timing_(sd_co.acc[k], 1, NULL, NULL);
         if (sd_spec.on && (rc = sk_covacc_set_spectrum(sd_co.acc[k], sd_spec.max)) != SK_OK) { co_close(); return rc; }
+        if (sd_thr.on && (rc = sk_covacc_set_thresholds(sd_co.acc[k], sd_thr.t, sd_thr.n)) != SK_OK) { co_close(); return rc; }
         if (sd_rec.on) {                                  /* every member's informative rows ranked: its bits of the unit's planes */
             uint32_t nbits[SK_UNION_MAX];
             for (m = 0; m < n; m++) {
@@ -1778,7 +1793,8 @@ static void co_flush(sd_prog *p, uint32_t s)
     int rc;
     if (!p->co_n) return;
     pthread_mutex_lock(&sd_dev_mu);
-    rc = sk_covacc_add_rows(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_n);
+    rc = sd_thr.on ? sk_covacc_add_rows_hits(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_tot, p->co_n)
+                   : sk_covacc_add_rows(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_n);
     pthread_mutex_unlock(&sd_dev_mu);
     p->co_n = 0;
     if (rc != SK_OK) p->job_rc = rc;
@@ -2231,11 +2247,20 @@ static void emit_rows(sd_prog *p, const uint32_t *rows, uint32_t n, const char *
     char key[32];
     if (sd_co.on) {                                        /* --coverage-only: no line, only what the script would count of it */
         if (!sd_co.acc) { for (j = 0; j < n; j++) skc_add_hit(p->cov, name, p->h1, p->h2, rows[j]); return; }
-        if (!n || !((long long)p->h1 + p->h2 > sd_co.min)) return;
+        if (!n || !((long long)p->h1 + p->h2 > (sd_thr.on && sd_thr.t[0] < sd_co.min ? (long long)sd_thr.t[0] : sd_co.min))) return;
         if (p->co_n + n > p->co_cap) {
             p->co_cap = (p->co_n + n) * 2 + 1024;
             p->co_rows = (uint32_t *)realloc(p->co_rows, (size_t)p->co_cap * sizeof *p->co_rows);
+            if (p->co_rows && sd_thr.on) {
+                uint32_t *t2 = (uint32_t *)realloc(p->co_tot, (size_t)p->co_cap * sizeof *p->co_tot);
+                if (t2) p->co_tot = t2;
+                else { free(p->co_rows); p->co_rows = NULL; }
+            }
             if (!p->co_rows) { p->co_cap = p->co_n = 0; p->job_rc = SK_E_NOMEM; return; }
+        }
+        if (sd_thr.on) {                                   /* (unfiltered: the device applies --min-kmer-hits and the list to the total) */
+            const long long tot = (long long)p->h1 + p->h2;
+            for (j = 0; j < n; j++) p->co_tot[p->co_n + j] = tot > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)tot;
         }
         memcpy(p->co_rows + p->co_n, rows, (size_t)n * sizeof *rows);
         p->co_n += n;
@@ -2501,6 +2526,13 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
                 uint64_t stray = 0;
                 rc = sd_rec.next < sd_rec.T ? sk_covacc_mark_target(sd_co.acc[k], sd_rec.r[k], sd_rec.next, &stray) : SK_E_STATE;
                 if (rc == SK_OK && stray) rc = SK_E_STATE;       /* (only informative rows are ever logged) */
+                if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
+            }
+            if (sd_thr.on) {                                 /* the numbers per threshold: a pass of its own that changes no counter */
+                uint64_t tu[SK_UNION_MAX * SK_COVACC_THRESHOLDS_MAX], tt[SK_UNION_MAX * SK_COVACC_THRESHOLDS_MAX];
+                rc = sk_covacc_finish_target_thresholds(sd_co.acc[k], tu, tt);
+                for (m = 0; m < n && rc == SK_OK; m++)
+                    if (skc_add_threshold_counts(p[a + m].cov, f1, tu + (size_t)m * sd_thr.n, tt + (size_t)m * sd_thr.n, sd_thr.n)) rc = SK_E_NOMEM;
                 if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
             }
             rc = sd_spec.on ? sk_covacc_finish_target_spectrum(sd_co.acc[k], uq, tot, sp, deep, ru, rt) :
@@ -2867,6 +2899,11 @@ static int sd_coverage_write(sd_prog *p)
         rc = skc_report_spectrum(p->cov, p->o_path, sd_spec.max, f, p->err);
         fclose(f);
     }
+    if (!rc && sd_thr.on) {
+        if (!(f = fopen(p->th_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->th_path); return 1; }
+        rc = skc_report_thresholds(p->cov, p->o_path, f, p->err);
+        fclose(f);
+    }
     if (!rc && sd_rec.on) {
         FILE *fp = NULL;
         if (!(f = fopen(p->rc_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->rc_path); return 1; }
@@ -2896,6 +2933,23 @@ static int sd_recurrence_open(sd_prog *p, const char *explicit_path, const char 
     p->rc_path = sd_table_path(p->o_path, explicit_path, ".coverage_recurrence");
     if (sd_rec.pairs) p->rp_path = sd_table_path(p->o_path, explicit_pairs, ".coverage_recurrence_pairs");
     if (!p->rc_path || (sd_rec.pairs && !p->rp_path)) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
+    return 0;
+}
+
+/* --coverage-thresholds: where the table of strain p goes, and the list to the strain's host accumulator */
+static int sd_thresholds_open(sd_prog *p, const char *explicit_path)
+{
+    if (explicit_path && *explicit_path) p->th_path = strdup(explicit_path);
+    else {
+        const size_t n = strlen(p->o_path);
+        p->th_path = (char *)malloc(n + 32);
+        if (p->th_path) {
+            strcpy(p->th_path, p->o_path);
+            if (n >= 13 && !strcmp(p->th_path + n - 13, ".kmer_hits.gz")) p->th_path[n - 13] = 0;
+            strcat(p->th_path, ".coverage_thresholds");
+        }
+    }
+    if (!p->th_path || skc_set_thresholds(p->cov, sd_thr.t, sd_thr.n)) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
     return 0;
 }
 
@@ -3003,10 +3057,10 @@ static void sd_strain_close(sd_prog *p)
     if (getenv("SK_LEAK_AT_EXIT") && strcmp(getenv("SK_LEAK_AT_EXIT"), "0")) { memset(p, 0, sizeof *p); return; }
     if (p->ctx) { skh_pack_cache_set(p->ctx, NULL, NULL); sk_ctx_destroy(p->ctx); }
     skh_keyset_free(&p->ks);
-    free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows);
+    free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows); free(p->co_tot);
     skc_destroy(p->cov);
     if (skh_regions_free) skh_regions_free(&p->rg);
-    free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->rc_path); free(p->rp_path);
+    free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->th_path); free(p->rc_path); free(p->rp_path);
     memset(p, 0, sizeof *p);
 }
 
@@ -3243,7 +3297,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     skh_regions *rgs = NULL;
     int want_rg = 0, want_sp = 0, want_ps = 0, want_rc = 0, want_rp = 0;
     const char *rc_file = NULL, *rp_file = NULL;
-    const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL;
+    const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL, *th_file = NULL, *th_list = NULL;
+    int want_th = 0;
     long long cov_min = 1;
     double t_begin = 0;
     sd_prog *p = NULL;
@@ -3293,6 +3348,16 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         }
         if (!strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { sp_max = argv[++c]; continue; }
         if (!strncmp(argv[c], "--spectrum-max=", 15)) { sp_max = argv[c] + 15; continue; }
+        /* "--coverage-thresholds[=FILE] [--threshold-list t1,t2,...]": next to either table, its two numbers at each of up to 16
+         * --min-kmer-hits from the one pass (default list 0,1,2,3,5,10,20,50), default FILE = outfile with ".kmer_hits.gz" replaced
+         * by ".coverage_thresholds" */
+        if (!strncmp(argv[c], "--coverage-thresholds", 21) && (argv[c][21] == 0 || argv[c][21] == '=')) {
+            want_th = 1;
+            th_file = argv[c][21] ? argv[c] + 22 : NULL;
+            continue;
+        }
+        if (!strcmp(argv[c], "--threshold-list") && c + 1 < argc) { th_list = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--threshold-list=", 17)) { th_list = argv[c] + 17; continue; }
         /* "--coverage-recurrence[=FILE] [--recurrence-pairs[=FILE]]": next to either table, in how many of the run's samples each
          * informative k-mer was seen, and what every two samples share; default FILEs = outfile with ".kmer_hits.gz" replaced by
          * ".coverage_recurrence" and ".coverage_recurrence_pairs" */
@@ -3321,6 +3386,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     argc = j;
     sd_rg.on = 0; sd_rg.genomes = NULL; sd_rg.ngenomes = 0;
     sd_spec.on = 0;
+    sd_thr.on = 0;
     sd_rec.on = 0;
     sd_co.on = 0;
     sd_ps.path = NULL;
@@ -3384,6 +3450,17 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             if (end == sp_max || *end || errno || d < 1 || d > (long long)SK_COVACC_SPECTRUM_MAX) { fprintf(err, "strain_detect: --spectrum-max %s: a depth from 1 to %u\n", sp_max, SK_COVACC_SPECTRUM_MAX); return sd_drop(p, ns); }
         }
         sd_spec.max = (uint32_t)d;
+    }
+    if (want_th || th_list) {
+        static const int64_t dflt[8] = { 0, 1, 2, 3, 5, 10, 20, 50 };
+        char why[160];
+        if (!want_th) { fputs("strain_detect: --threshold-list goes with --coverage-thresholds\n", err); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-thresholds goes with --coverage-depth or --coverage-only: it gives their table's two numbers at several --min-kmer-hits\n", err); return sd_drop(p, ns); }
+        if (th_file && ((S && !a && !o && !r) || (ad && ad->o))) { fputs("strain_detect: --coverage-thresholds=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        memset(sd_thr.t, 0, sizeof sd_thr.t);
+        memcpy(sd_thr.t, dflt, sizeof dflt);
+        sd_thr.n = 8;
+        if (th_list && skc_parse_threshold_list(th_list, sd_thr.t, &sd_thr.n, why, sizeof why)) { fprintf(err, "strain_detect: --threshold-list %s: %s\n", th_list, why); return sd_drop(p, ns); }
     }
     if (want_rc || want_rp) {
         uint32_t T = 1;
@@ -3454,6 +3531,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_co_ms_fold = sd_co_ms_sweep = 0;
     sd_rg.on = want_rg;
     sd_spec.on = want_sp;
+    sd_thr.on = want_th; sd_thr.ms_finish = 0;
     sd_rec.on = want_rc; sd_rec.pairs = want_rp; sd_rec.next = 0;
     sd_rec.ms_mark = sd_rec.ms_hist = sd_rec.ms_gram = 0;
     sd_ps.path = want_ps ? ps_file : NULL;
@@ -3552,6 +3630,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (sd_regions_open(&p[s], &rgs[s], S || (ad && ad->o) ? NULL : rg_file)) goto done;
     for (s = 0; want_sp && s < ns; s++)
         if (sd_spectrum_open(&p[s], S || (ad && ad->o) ? NULL : sp_file)) goto done;
+    for (s = 0; want_th && s < ns; s++)
+        if (sd_thresholds_open(&p[s], S || (ad && ad->o) ? NULL : th_file)) goto done;
     for (s = 0; want_rc && s < ns; s++)
         if (sd_recurrence_open(&p[s], S || (ad && ad->o) ? NULL : rc_file, S || (ad && ad->o) ? NULL : rp_file)) goto done;
     if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
@@ -3619,6 +3699,9 @@ done:
     if (getenv("SK_SD_TIMING") && cov_only)
         fprintf(err, "strain_detect timing: coverage accumulators on the device: folds %.3f ms, target sweeps %.3f ms%s\n", sd_co_ms_fold, sd_co_ms_sweep,
                 want_rg && want_sp ? " (folded by region, binned by depth)" : want_rg ? " (folded by region)" : want_sp ? " (binned by depth)" : "");
+    if (getenv("SK_SD_TIMING") && cov_only && want_th)
+        fprintf(err, "strain_detect timing: thresholds on the device: %u thresholds, finishing passes %.3f ms (the folds above classify as well)\n",
+                sd_thr.n, sd_thr.ms_finish);
     if (getenv("SK_SD_TIMING") && cov_only && want_rc)
         fprintf(err, "strain_detect timing: recurrence on the device: marks %.3f ms (%u targets), finish: histogram %.3f ms, pairs %.3f ms\n",
                 sd_rec.ms_mark, sd_rec.T, sd_rec.ms_hist, sd_rec.ms_gram);
@@ -3633,6 +3716,7 @@ done:
     sd_co.on = 0;
     sd_rg.on = 0;
     sd_spec.on = 0;
+    sd_thr.on = 0;
     sd_rec.on = 0;
     sd_ps.path = NULL;
     for (s = 0; rgs && s < nrgs; s++) skh_regions_free(&rgs[s]);

@@ -41,6 +41,15 @@ int skc_report_spectrum(skc_acc *a, const char *hits_file_name, uint32_t max_dep
  * alone); call it after skc_report */
 int skc_add_recurrence_counts(skc_acc *a, const char *const *metagenome, uint32_t T, const uint64_t *hist, const uint64_t *pairs);
 int skc_report_recurrence(skc_acc *a, const char *hits_file_name, FILE *out, FILE *out_pairs, FILE *err);
+/* ... and the two numbers at several thresholds (strain_detect --coverage-thresholds): skc_set_thresholds right after skc_create
+ * (-1: a bad list, or hits were added already) makes skc_add_hit also keep, in a list of its own and with its pair's total, every
+ * hit above t[0], whatever the main filter does with it; a metagenome's numbers handed in per threshold (next to skc_add_counts),
+ * or folded from the kept hits by skc_report_thresholds, which prints the table; call it after skc_report.
+ * skc_parse_threshold_list reads "t1,t2,..." by the rule of include/strainer_kmer.h: 0, or 1 and in `why` what is wrong */
+int skc_parse_threshold_list(const char *text, int64_t *t /* SK_COVACC_THRESHOLDS_MAX */, uint32_t *n, char *why, size_t why_cap);
+int skc_set_thresholds(skc_acc *a, const int64_t *t, uint32_t n);
+int skc_add_threshold_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t n);
+int skc_report_thresholds(skc_acc *a, const char *hits_file_name, FILE *out, FILE *err);
 /* kmer_scrub_count --detect: the genome files of the strains the next skh_strain_detect_resident[_many] call adopts (it has no -r;
  * --coverage-regions reads the records' names and lengths from them).  The call takes the list and forgets it. */
 void skh_resident_genomes_(const char *const *paths, uint32_t n);
@@ -95,6 +104,8 @@ int sk_tally_view_(sk_ctx *ctx, sk_union *u, sk_tally_view *out);
 int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *ms_sweep);
 /* the device time of the accumulator's marks (sk_covacc_mark_target), kept by the same clocks */
 int sk_covacc_mark_timing_(sk_covacc *a, double *ms_mark);
+/* ... and of its threshold finishing passes (sk_covacc_finish_target_thresholds) */
+int sk_covacc_thresholds_timing_(sk_covacc *a, double *ms_thr);
 /* The recurrence engine's planes (sk_recur.hip), for the feeders that set bits with kernels of their own (sk_covacc.hip,
  * sk_cover.hip): plane `sample` of member m begins at d_planes + sample * words + word_base[m] and holds (nbits[m] + 63) / 64
  * words; a feeder sets no bit at or above nbits[m] and synchronises before the engine's next call. */

@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "sk_union_share",
     "sk_recur_create", "sk_recur_destroy", "sk_recur_mark_bits", "sk_recur_finish", "sk_covacc_set_recurrence", "sk_covacc_mark_target",
     "sk_distinct_recurrence",
+    "sk_covacc_set_thresholds", "sk_covacc_add_rows_hits", "sk_covacc_finish_target_thresholds", "sk_distinct_thresholds",
 ]
 
 
@@ -732,6 +733,20 @@ class KmerContext:
                                             pr.ctypes.data if pairs else None))
         return (hist, pr) if pairs else hist
 
+    def distinct_thresholds(self, keys, sample, total_hits, nsamples, thresholds):
+        """sk_distinct_thresholds: (unique[nsamples, nt], total[nsamples, nt]) -- for every sample and threshold t the hits whose
+        total_hits exceeds t, and the distinct keys they name"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32)
+        total_hits = np.ascontiguousarray(total_hits, dtype=np.uint32)
+        t = np.ascontiguousarray(thresholds, dtype=np.int64).reshape(-1)
+        assert len(keys) == len(sample) == len(total_hits)
+        uniq = np.zeros((max(int(nsamples), 0), len(t)), dtype=np.uint64)
+        total = np.zeros_like(uniq)
+        self._ck(lib.sk_distinct_thresholds(self._h, keys.ctypes.data, sample.ctypes.data, total_hits.ctypes.data, len(keys), int(nsamples),
+                                            t.ctypes.data, len(t), uniq.ctypes.data, total.ctypes.data))
+        return uniq, total
+
     def print_counts(self, ks: Keyset, path, with_drug_column=False):
         fp = _libc.fopen(os.fsencode(path), b"w")
         try:
@@ -810,6 +825,13 @@ lib.sk_recur_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 lib.sk_covacc_set_recurrence.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
 lib.sk_covacc_mark_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_distinct_recurrence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+SK_COVACC_THRESHOLDS_MAX = 16
+DEFAULT_THRESHOLDS = (0, 1, 2, 3, 5, 10, 20, 50)
+lib.sk_covacc_set_thresholds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+lib.sk_covacc_add_rows_hits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]
+lib.sk_covacc_finish_target_thresholds.argtypes = [C.c_void_p] * 3
+lib.sk_distinct_thresholds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_void_p]
 
 
 def regions_from_file(path, window=100000):
@@ -824,6 +846,11 @@ def regions_from_file(path, window=100000):
         return [(int(s.text_off[i]), int(s.record[i]), int(s.rec_off[i]), int(s.len[i]), s.name[i]) for i in range(s.n)], int(s.text_bases)
     finally:
         lib.skh_regions_free(C.byref(s))
+
+
+def distinct_thresholds(ctx, keys, sample, total_hits, nsamples, thresholds=DEFAULT_THRESHOLDS):
+    """KmerContext.distinct_thresholds on ctx"""
+    return ctx.distinct_thresholds(keys, sample, total_hits, nsamples, thresholds)
 
 
 def distinct_spectrum(ctx, keys, sample, nsamples, max_depth=255):
@@ -1125,6 +1152,29 @@ class CoverageAcc:
     def add_rows(self, member, rows):
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
         self._ctx._ck(lib.sk_covacc_add_rows(self._h, member, rows.ctypes.data, len(rows)))
+
+    def add_rows_hits(self, member, rows, total_hits):
+        """sk_covacc_add_rows_hits: unfiltered hits on these rows of member, each with its pair's total h1 + h2"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        total_hits = np.ascontiguousarray(total_hits, dtype=np.uint32)
+        assert len(rows) == len(total_hits)
+        self._ctx._ck(lib.sk_covacc_add_rows_hits(self._h, member, rows.ctypes.data, total_hits.ctypes.data, len(rows)))
+
+    def set_thresholds(self, thresholds):
+        """sk_covacc_set_thresholds: an empty list turns thresholds off; otherwise 1..SK_COVACC_THRESHOLDS_MAX strictly ascending
+        integers from 0 to 2^31 - 2.  Whatever was classified since the last finish is discarded."""
+        t = np.ascontiguousarray(thresholds, dtype=np.int64).reshape(-1)
+        self._ctx._ck(lib.sk_covacc_set_thresholds(self._h, t.ctypes.data if len(t) else None, len(t)))
+        self._thr_n = len(t)
+
+    def finish_target_thresholds(self):
+        """sk_covacc_finish_target_thresholds: (unique[nmembers, nt], total[nmembers, nt]); the depth counters are not touched, the
+        threshold state is zero afterwards.  Call it before the sweep that ends the target."""
+        nt = getattr(self, "_thr_n", 0)
+        uq = np.zeros((len(self.nrows), max(nt, 1)), dtype=np.uint64)
+        tot = np.zeros_like(uq)
+        self._ctx._ck(lib.sk_covacc_finish_target_thresholds(self._h, uq.ctypes.data, tot.ctypes.data))
+        return uq[:, :nt], tot[:, :nt]
 
     def rows(self, member):
         """member's per-row counters as they stand"""

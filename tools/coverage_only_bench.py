@@ -27,6 +27,7 @@ apart.
     python tools/coverage_only_bench.py --regions 100000 --rounds 5 [--parent-exe PATH] [--out profiles/coverage_regions_bench.txt]
     python tools/coverage_only_bench.py --spectrum 255 --rounds 5 --parent-exe PATH [--out profiles/coverage_spectrum_bench.txt]
     python tools/coverage_only_bench.py --recurrence --rounds 5 --parent-exe PATH [--out profiles/coverage_recurrence_bench.txt]
+    python tools/coverage_only_bench.py --thresholds [--threshold-list 0,1,2] --rounds 3 --parent-exe PATH [--out profiles/coverage_thresholds_bench.txt]
 """
 import argparse
 import hashlib
@@ -52,6 +53,7 @@ EXE = os.path.join(REPO, "strainer2_amd", "bin", "strain_detect")
 PASS = re.compile(rb"strain_detect timing: setup ([0-9.]+) s,.*?total before close ([0-9.]+) s")
 ACC = re.compile(rb"coverage accumulators on the device: folds ([0-9.]+) ms, target sweeps ([0-9.]+) ms")
 REC = re.compile(rb"recurrence on the device: marks ([0-9.]+) ms \((\d+) targets\), finish: histogram ([0-9.]+) ms, pairs ([0-9.]+) ms")
+THR = re.compile(rb"thresholds on the device: (\d+) thresholds, finishing passes ([0-9.]+) ms")
 BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
 
 
@@ -70,7 +72,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     """one run of the program under its own time limit -> measurements; raises StepFailed (nothing more is started then)"""
     for s in range(ns):
         for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum",
-                  f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs"):
+                  f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs", f"out{s}.gz.coverage_thresholds"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -91,7 +93,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             h.update(f.read())
     hr = hashlib.md5()
     for s in range(ns):
-        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs"):    # (the table beside the coverage table, whichever the run wrote)
+        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds"):    # (the table beside the coverage table, whichever the run wrote)
             if os.path.exists(os.path.join(cwd, f"out{s}.gz.{ext}")):
                 with open(os.path.join(cwd, f"out{s}.gz.{ext}"), "rb") as f:
                     hr.update(f.read())
@@ -99,7 +101,8 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     b = BYTES.search(p.stderr)
     a = ACC.search(p.stderr)
     rc = REC.search(p.stderr)
-    return dict(mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
+    th = THR.search(p.stderr)
+    return dict(thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
                 fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
                 passed=float(m.group(2)) - float(m.group(1)) if m else float("nan"),
                 d2h=int(b.group(1)) if b else -1, dev=int(b.group(2)) if b else -1, replayed=int(b.group(3)) if b else -1)
@@ -137,19 +140,26 @@ def regions_case(say, args, env, tmp, ns, kind, argv):
         say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
-def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False):
-    """--coverage-only without and with --coverage-spectrum (recurrence: --coverage-recurrence --recurrence-pairs), alternating; the
-    parent build's plain --coverage-only behind them and the new build's medians set against the parent's"""
+def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False):
+    """--coverage-only without and with --coverage-spectrum (recurrence: --coverage-recurrence --recurrence-pairs; thresholds:
+    --coverage-thresholds [--threshold-list ..]), alternating; the parent build's plain --coverage-only behind them -- with
+    thresholds: in turn with them, round by round -- and the new build's medians set against the parent's"""
     with_sp = ["--coverage-only", "--coverage-spectrum", "--spectrum-max", str(args.spectrum)]
     word, label = "spectrum", f"... --coverage-spectrum --spectrum-max {args.spectrum}"
     if recurrence:
         with_sp = ["--coverage-only", "--coverage-recurrence", "--recurrence-pairs"]
         word, label = "recurrence", "... --coverage-recurrence --recurrence-pairs"
+    if thresholds:
+        with_sp = ["--coverage-only", "--coverage-thresholds"] + (["--threshold-list", args.threshold_list] if args.threshold_list else [])
+        word, label = "thresholds", "... " + " ".join(with_sp[1:])
     res = {"plain": [], "spectrum": [], "parent": []}
     md5 = md5s = None
     for rnd in range(args.rounds):
-        for tag, flags in (("plain", ["--coverage-only"]), ("spectrum", with_sp)):
-            r = step(EXE, argv + flags, dict(env), args.limit, tmp, ns, False)
+        turns = [("plain", ["--coverage-only"]), ("spectrum", with_sp)]
+        if thresholds and args.parent_exe:
+            turns.append(("parent", ["--coverage-only"]))
+        for tag, flags in turns:
+            r = step(args.parent_exe if tag == "parent" else EXE, argv + flags, dict(env), args.limit, tmp, ns, False)
             md5 = md5 or r["md5"]
             if r["md5"] != md5:
                 raise StepFailed(f"{ns} strains, {kind}, round {rnd}, {tag}: the coverage tables differ from the first run's")
@@ -158,7 +168,7 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False):
                 if r["md5r"] != md5s:
                     raise StepFailed(f"{ns} strains, {kind}, round {rnd}: the {word} tables differ from the first run's")
             res[tag].append(r)
-    if args.parent_exe:
+    if args.parent_exe and not thresholds:
         res["parent"] = [step(args.parent_exe, argv + ["--coverage-only"], dict(env), args.limit, tmp, ns, False) for _ in range(args.rounds)]
         if any(r["md5"] != md5 for r in res["parent"]):
             raise StepFailed(f"{ns} strains, {kind}: the parent build writes other tables")
@@ -169,6 +179,8 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False):
         if rs:
             say(f"    {names[tag]}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; accumulators on the device: folds "
                 f"{row(rs, 'fold', '.2f')} ms, target sweeps {row(rs, 'sweep', '.3f')} ms; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
+            if thresholds and tag == "spectrum":
+                say(f"        thresholds on the device: finishing passes of all targets {row(rs, 'thr', '.3f')} ms (the folds above classify as well)")
             if recurrence and tag == "spectrum":
                 say(f"        recurrence on the device: marks of all targets {row(rs, 'mark', '.3f')} ms; the one finish: histogram "
                     f"{row(rs, 'hist', '.3f')} ms, pair table {row(rs, 'gram', '.3f')} ms")
@@ -177,7 +189,7 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False):
     say(f"    with the {word} / without at the medians: pass %.2f, wall %.2f, folds %.2f, target sweeps %.2f" %
         tuple(med["spectrum"][k] / med["plain"][k] if med["plain"][k] else float("nan") for k in keys))
     if res["parent"]:                                        # the yardstick: the parent's medians; the margin: its own spread
-        for k, unit in (("passed", "s"), ("sweep", "ms")):
+        for k, unit in (("passed", "s"), ("fold", "ms"), ("sweep", "ms")) if thresholds else (("passed", "s"), ("sweep", "ms")):
             spread = max(r[k] for r in res["parent"]) - min(r[k] for r in res["parent"])
             for tag in ("plain", "spectrum"):
                 diff = med[tag][k] - med["parent"][k]
@@ -196,6 +208,8 @@ def main():
     ap.add_argument("--regions", type=int, default=None, help="measure --coverage-regions with this --region-window")
     ap.add_argument("--spectrum", type=int, default=None, help="measure --coverage-spectrum with this --spectrum-max")
     ap.add_argument("--recurrence", action="store_true", help="measure --coverage-recurrence --recurrence-pairs")
+    ap.add_argument("--thresholds", action="store_true", help="measure --coverage-thresholds, the parent build's runs in turn with this build's")
+    ap.add_argument("--threshold-list", default=None, help="... with this --threshold-list (default: the program's)")
     ap.add_argument("--stderr-dir", default=None, help="keep every run's stderr (the SK_SD_TIMING lines) in this directory")
     ap.add_argument("--out", default=None)
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -253,8 +267,8 @@ def main():
             for ns in counts:
                 for kind, lst in lists.items():
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
-                    if args.spectrum is not None or args.recurrence:
-                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence)
+                    if args.spectrum is not None or args.recurrence or args.thresholds:
+                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds)
                         continue
                     if args.regions is not None:
                         regions_case(say, args, env, tmp, ns, kind, argv)
