@@ -601,14 +601,45 @@ int  sk_filter_hist(sk_filter *f, int which, int64_t lo, uint32_t nbins, uint64_
 int  sk_filter_joint(sk_filter *f, int64_t pan_sum, int64_t meta_sum, uint64_t n_scrub, uint8_t *out /* n */);
 /* independent_scrub (:72-84): remove rows whose pan count exceeds pan_thr or meta count meta_thr. */
 int  sk_filter_above(sk_filter *f, int64_t pan_thr, int64_t meta_thr, uint8_t *out /* n */);
+/* SCRUB SWEEP, step 2 (new: kmer_scrub_filter --min_fraction_list, kmer_scrub_count --scrub f0,f1,...): the informative sets of one
+ * strain at several min_fraction from one run.  The rule, for a list f[0] > f[1] > ... > f[F-1]:
+ *   list      1 to SK_SCRUB_SWEEP_MAX = 16 numbers in [0, 1], strictly descending; an empty field, a duplicate, an ascending pair,
+ *             more than 16 entries, a value outside [0, 1] or a field that is no number is refused.  A fraction is printed
+ *             everywhere as the text the user gave.
+ *   set q     the informative list a run at f[q] alone prints.  The sets are nested, set 0 the largest: in the joint mode rows
+ *             leave in one fixed order (descending score, ties in row order) while 1 - (n + 1) / all > min_fraction, so a smaller
+ *             fraction removes a longer prefix of the same order (:87-137); in the independent mode the walked thresholds do not
+ *             decrease with the fraction (:30-58, :72-84); the drug scrub does not depend on it (:62-68).
+ *   class     of a row: the number of q whose set holds it, 0 .. F.  By nestedness a row is in set q iff class >= q + 1.
+ * The class bytes are built on the device and only they come back: out_class[r] for all n rows (rows gone before have class 0),
+ * kept[q] = the size of set q.
+ *   sk_filter_classes_joint: n_scrub[q] is joint_scrub's row count at f[q] and must not decrease along the list (SK_E_ARG);
+ *   ties at a cut go in row order until the quota is used, as in sk_filter_joint.  On an error (a cut beyond the rows that take part
+ *   among them) kept[] is all zero and out_class is not written.
+ *   sk_filter_classes_above: the pair of thresholds per fraction; neither may increase along the list (SK_E_ARG). */
+#define SK_SCRUB_SWEEP_MAX 16u
+int  sk_filter_classes_joint(sk_filter *f, int64_t pan_sum, int64_t meta_sum, const uint64_t *n_scrub /* F */, uint32_t F,
+                             uint8_t *out_class /* n bytes */, uint64_t *kept /* F */);
+int  sk_filter_classes_above(sk_filter *f, const int64_t *pan_thr /* F */, const int64_t *meta_thr /* F */, uint32_t F,
+                             uint8_t *out_class /* n bytes */, uint64_t *kept /* F */);
 
 /* The script's command line (-s/--scrub_count_file, -l/--scrub_count_list, -m/--min_fraction,
- * -i/--independent): same stdout bytes, same exit status, the same "kept ..." lines on stderr. */
+ * -i/--independent): same stdout bytes, same exit status, the same "kept ..." lines on stderr.
+ * New: --min_fraction_list f0,f1,... --classes_out FILE (both or neither, not with -m; refused with status 2 otherwise, and for a
+ * bad list): the run is the run at --min_fraction f0, stdout and stderr byte for byte, and FILE (gzip if its name ends in .gz)
+ * gets the class file:
+ *   #min_fractions<TAB>f0,f1,...
+ *   #post_scrub_kmers<TAB>n0,n1,...
+ *   kmer<TAB>class          one line per row of class >= 1, in the order of the informative list
+ * A run that fails (where the run at f0 fails) writes no class file. */
 int skh_scrub_filter_main(int argc, char **argv, FILE *out, FILE *err);
 /* Fused step 1 -> step 2: what the script would print for the table skh_print_counts would print,
  * computed from the resident counters (columns 1, 2 and, with_drug_column, 3). */
 int skh_scrub_filter_resident(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, double min_fraction,
                               int independent, FILE *out, FILE *err);
+/* ... at a list of fractions "f0,f1,..." (the scrub sweep above): the run at f0, and the class file to classes_path; 1 for a bad list */
+int skh_scrub_filter_resident_sweep(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, const char *fraction_list,
+                                    int independent, const char *classes_path, FILE *out, FILE *err);
 
 /* ------------------------------------------------------------------------------------------------
  * Coverage / depth: the consumer of strain_detect's hit list (reference scripts/coverage_depth.py,
@@ -856,8 +887,34 @@ int  sk_covacc_finish_target_thresholds(sk_covacc *a, uint64_t *thr_unique /* nm
 int  sk_distinct_thresholds(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, const uint32_t *total_hits, uint64_t n,
                             uint32_t nsamples, const int64_t *t, uint32_t nt, uint64_t *out_unique /* nsamples x nt */,
                             uint64_t *out_total /* nsamples x nt */);
+/* SCRUB SWEEP, step 4 (new: strain_detect --coverage-scrub-sweep, coverage_depth --scrub-sweep): step 4's numbers at every fraction
+ * of a class file (above) from the one pass made with set 0.  Step 4's read filter uses the reads' hits on ALL k-mers of the strain
+ * (scripts/coverage_depth.py:84-89), which the informative set does not change, so a row's depth counter in the run at f[0] is what
+ * it would be in a run at f[q] for every q whose set holds the row: the numbers at q are sums over the rows of class >= q + 1,
+ * exactly those of a separate run.  A -g list breaks this (its cut is sized by the number of informative rows) and is refused.
+ *   table     a header line, then per sample of the main coverage table, in its order, one line per fraction, descending, zeros
+ *             included, all numbers integers; genome_num_informative_kmers is the size of set q:
+ *               strain_name<TAB>metagenome<TAB>min_fraction<TAB>genome_num_informative_kmers<TAB>unique_observed_informative_kmers<TAB>total_observed_informative_kmers
+ *   sk_covacc_set_classes: member's class bytes from a sparse list: rows[i] gets cls[i] (1 .. ncls), rows not named class 0.  A row
+ *   or a class out of range is SK_E_ARG before anything is launched; a row named twice keeps one of its classes, which one is not
+ *   defined (the programs refuse such a class file).  ncls = 0 turns the member's classes off (n must be 0).
+ *   sk_covacc_finish_target_classes: out_unique[m * F + q], out_total[m * F + q], F = the largest ncls set (members with fewer, or
+ *   none, have zeros beyond theirs).  A pass of its own in front of whichever sweep ends the target: it reads the depth counters and
+ *   the class bytes and changes no counter; two calls return the same numbers and the sweeps return what they return without it.
+ *   *out_stray = non-zero rows of class 0 or of a class above their member's ncls, members without classes not counted (the
+ *   programs treat a non-zero count as an internal error).  SK_E_STATE when no member has classes.
+ *   sk_distinct_classes: the same two numbers per sample and fraction ([nsamples x ncls]) for a hit list of (sample, key, class)
+ *   triples with class 1 .. ncls (SK_E_ARG otherwise); the lines of a (sample, key) pair carry one class; keys as for
+ *   sk_distinct_count. */
+int  sk_covacc_set_classes(sk_covacc *a, uint32_t member, const uint32_t *rows, const uint8_t *cls, uint64_t n, uint32_t ncls);
+int  sk_covacc_finish_target_classes(sk_covacc *a, uint64_t *out_unique /* nmembers x F */, uint64_t *out_total /* nmembers x F */,
+                                     uint64_t *out_stray);
+int  sk_distinct_classes(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, const uint8_t *cls, uint64_t n, uint32_t nsamples,
+                         uint32_t ncls, uint64_t *out_unique /* nsamples x ncls */, uint64_t *out_total /* nsamples x ncls */);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
- * same stdout bytes and exit status.  New: --thresholds[=FILE] [--threshold-list t1,t2,...] also writes the thresholds table (above)
+ * same stdout bytes and exit status.  New: --scrub-classes FILE --scrub-sweep[=FILE] also writes the scrub sweep table (above) to
+ * FILE, default the hits file's path with a trailing ".kmer_hits.gz" replaced by ".coverage_scrub_sweep"; stdout is unchanged; a hit
+ * list in the general mode, or one with a k-mer the class file does not name, is refused.  New: --thresholds[=FILE] [--threshold-list t1,t2,...] also writes the thresholds table (above)
  * to FILE, default the hits file's path with a trailing ".kmer_hits.gz" replaced by ".coverage_thresholds"; stdout is unchanged and a
  * hit list in the general mode is refused.  New: --spectrum[=FILE] [--spectrum-max D] also writes the depth spectrum (above) to FILE,
  * default the hits file's path with a trailing ".kmer_hits.gz" removed plus ".coverage_spectrum"; stdout is unchanged.  A hit list

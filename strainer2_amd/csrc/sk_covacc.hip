@@ -18,6 +18,8 @@
 // covacc_hits_thr is covacc_hits with every entry also classified by how many of a list of thresholds its pair's total exceeds
 // (--coverage-thresholds), covacc_thr_finish the pass of its own that turns the rows' highest classes into numbers; like the mark it
 // changes no counter, and a run without thresholds launches neither.
+// covacc_class_scatter / covacc_class_finish are the scrub sweep (--coverage-scrub-sweep): one class byte per row, and a pass of its own
+// in front of the sweep that bins the non-zero rows by class; it changes nothing at all, and a run without classes launches neither.
 // Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -519,6 +521,82 @@ __global__ void __launch_bounds__(256) covacc_thr_finish(uint32_t *__restrict__ 
     if (threadIdx.x < COV_THR_CLASSES && s_bin[threadIdx.x]) atomicAdd(row_cnt + (size_t)m * COV_THR_CLASSES + threadIdx.x, s_bin[threadIdx.x]);
 }
 
+// ---- the scrub sweep: step 4's numbers at several min_fraction from one pass (include/strainer_kmer.h has the rule) ----
+// A row's class is the number of listed fractions whose informative set holds it; the sets are nested, so the numbers at fraction q
+// are sums over the non-zero rows of class >= q + 1.  covacc_class_finish bins a member's non-zero rows by exact class into
+// {rows, sum of depth} pairs and the host takes the suffix sums.  All rows of a workgroup fall into at most 16 bins, so the lanes of
+// a wave first reduce count and sum per class present among them and one lane adds each (wave, class) to the LDS bins; every
+// workgroup ends with one pair of 64-bit adds per non-empty bin.
+#define COV_CLS_NONE 0xFFu
+
+// rows[i] of the member gets cls[i]; out is the member's (zeroed before).  The host has checked both ranges already.
+__global__ void covacc_class_scatter(const uint32_t *__restrict__ rows, const uint8_t *__restrict__ cls, uint64_t n, uint32_t nrows,
+                                     uint32_t ncls, uint8_t *__restrict__ out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t r = rows[i], c = cls[i];
+        if (r < nrows && c >= 1u && c <= ncls) out[r] = (uint8_t)c;
+    }
+}
+
+__device__ __forceinline__ unsigned long long cov_wave_sum(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned lo = (unsigned)__shfl_down((int)(unsigned)v, off), hi = (unsigned)__shfl_down((int)(unsigned)(v >> 32), off);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// blockIdx.y = member: out[(m * MAX + c - 1) * 2 + {0, 1}] += the member's non-zero rows of class c and the sum of their depths;
+// *stray += its non-zero rows of class 0 or above ncls[m].  A member with ncls[m] = 0 is skipped.  Nothing is written but out and stray.
+__global__ void __launch_bounds__(256) covacc_class_finish(const uint32_t *__restrict__ depth, const uint64_t *__restrict__ row_base,
+                                                           const uint32_t *__restrict__ nrows, const uint8_t *__restrict__ cls,
+                                                           const uint32_t *__restrict__ ncls, unsigned long long *__restrict__ out,
+                                                           unsigned long long *__restrict__ stray)
+{
+    __shared__ unsigned long long s_cnt[SK_SCRUB_SWEEP_MAX], s_sum[SK_SCRUB_SWEEP_MAX];
+    __shared__ uint32_t s_bad;
+    const uint32_t m = blockIdx.y, n = nrows[m], lane = threadIdx.x & 63u;
+    const uint32_t nc = ncls[m] < SK_SCRUB_SWEEP_MAX ? ncls[m] : SK_SCRUB_SWEEP_MAX;
+    if (!nc) return;                                          // (the whole workgroup)
+    const uint32_t *d = depth + row_base[m];
+    const uint8_t *cl = cls + row_base[m];
+    if (threadIdx.x < SK_SCRUB_SWEEP_MAX) { s_cnt[threadIdx.x] = 0ull; s_sum[threadIdx.x] = 0ull; }
+    if (threadIdx.x == 0) s_bad = 0u;
+    __syncthreads();
+    uint32_t bad = 0;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < n; i0 += (uint64_t)gridDim.x * 256u) {   // (i0 is the workgroup's: every wave stays whole)
+        const uint64_t i = i0 + threadIdx.x;
+        uint32_t v = 0, c = COV_CLS_NONE;
+        if (i < n && (v = d[i]) != 0u) {
+            c = cl[i];
+            if (c < 1u || c > nc) { bad++; c = COV_CLS_NONE; }
+        }
+        unsigned long long todo = __ballot(c != COV_CLS_NONE);
+        while (todo) {                                        // one round per class present in the wave
+            const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
+            const uint32_t c0 = (uint32_t)__shfl((int)c, (int)lead);
+            const unsigned long long same = __ballot(c == c0);
+            const unsigned long long sum = cov_wave_sum(c == c0 ? (unsigned long long)v : 0ull);
+            if (lane == 0u && c0 >= 1u && c0 <= SK_SCRUB_SWEEP_MAX) {
+                atomicAdd(&s_cnt[c0 - 1u], (unsigned long long)__popcll(same));
+                atomicAdd(&s_sum[c0 - 1u], sum);
+            }
+            todo &= ~same;
+        }
+    }
+    if (bad) atomicAdd(&s_bad, bad);
+    __syncthreads();
+    if (threadIdx.x < nc && s_cnt[threadIdx.x]) {
+        unsigned long long *o = out + ((size_t)m * SK_SCRUB_SWEEP_MAX + threadIdx.x) * 2u;
+        atomicAdd(o, s_cnt[threadIdx.x]);
+        atomicAdd(o + 1, s_sum[threadIdx.x]);
+    }
+    if (threadIdx.x == 0 && s_bad) atomicAdd(stray, (unsigned long long)s_bad);
+}
+
 struct sk_covacc {
     sk_ctx *ctx; int device;
     hipStream_t stream;
@@ -555,6 +633,12 @@ struct sk_covacc {
     unsigned long long *d_thr_cnt;                          // [nm x COV_THR_CLASSES] entries per class, then as many: rows per class
     uint32_t *d_tots; size_t tots_cap;                      // sk_covacc_add_rows_hits' upload of the totals
     bool thr_dirty; double ms_thr;                          // something was classified since the last finish; the finishing passes' device time
+    // the scrub sweep: nothing of it exists until sk_covacc_set_classes is called with classes
+    uint8_t *d_cls;                                         // [total_rows] each row's class, 0: in no set
+    std::vector<uint32_t> ncls; uint32_t *d_ncls;           // [nm] the member's number of fractions (0: off)
+    uint8_t *d_cls_up; size_t cls_up_cap;                   // set_classes' upload of the sparse list's classes
+    unsigned long long *d_cls_out;                          // [nm x SK_SCRUB_SWEEP_MAX] pairs, then the stray count
+    double ms_cls;                                          // the class passes' device time
 };
 
 static void cov_t0(sk_covacc *a) { if (a->timed) (void)hipEventRecord(a->ev0, a->stream); }
@@ -591,6 +675,13 @@ extern "C" int sk_covacc_thresholds_timing_(sk_covacc *a, double *ms_thr)
     return SK_OK;
 }
 
+extern "C" int sk_covacc_classes_timing_(sk_covacc *a, double *ms_cls)
+{
+    if (!a || !ms_cls) return SK_E_ARG;
+    *ms_cls = a->ms_cls;
+    return SK_OK;
+}
+
 #define CA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sk_fail_(a->ctx, SK_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 static unsigned cov_grid(uint64_t n) { const uint64_t g = (n + 255u) / 256u; return (unsigned)(g < 1u ? 1u : g > 4096u ? 4096u : g); }
@@ -618,6 +709,7 @@ extern "C" void sk_covacc_destroy(sk_covacc *a)
     (void)hipFree(a->d_fp); (void)hipFree(a->d_starts); (void)hipFree(a->d_spec);
     (void)hipFree(a->d_irank); (void)hipFree(a->d_rec_nbits); (void)hipFree(a->d_blk); (void)hipFree(a->d_stray);
     (void)hipFree(a->d_thr_max); (void)hipFree(a->d_thr_cnt); (void)hipFree(a->d_tots);
+    (void)hipFree(a->d_cls); (void)hipFree(a->d_ncls); (void)hipFree(a->d_cls_up); (void)hipFree(a->d_cls_out);
     if (a->timed) { (void)hipEventDestroy(a->ev0); (void)hipEventDestroy(a->ev1); }
     if (a->h_bad) (void)hipHostFree(a->h_bad);
     if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -1178,5 +1270,79 @@ extern "C" int sk_covacc_finish_target_thresholds(sk_covacc *a, uint64_t *thr_un
             thr_unique[(size_t)m * a->thr.n + q] = u; thr_total[(size_t)m * a->thr.n + q] = t;
         }
     }
+    return SK_OK;
+}
+
+// ---- the scrub sweep ----
+extern "C" int sk_covacc_set_classes(sk_covacc *a, uint32_t member, const uint32_t *rows, const uint8_t *cls, uint64_t n, uint32_t ncls)
+{
+    if (!a || (n && (!rows || !cls))) return SK_E_ARG;
+    if (member >= a->nm) return sk_fail_(a->ctx, SK_E_ARG, "member %u: the accumulator has %u", member, a->nm);
+    if (ncls > SK_SCRUB_SWEEP_MAX) return sk_fail_(a->ctx, SK_E_ARG, "%u classes: at most %u", ncls, SK_SCRUB_SWEEP_MAX);
+    if (!ncls && n) return sk_fail_(a->ctx, SK_E_ARG, "rows with classes, and no class");
+    for (uint64_t i = 0; i < n; i++) {
+        if (rows[i] >= a->nrows[member]) return sk_fail_(a->ctx, SK_E_ARG, "row %u: member %u has %u", rows[i], member, a->nrows[member]);
+        if (cls[i] < 1u || cls[i] > ncls) return sk_fail_(a->ctx, SK_E_ARG, "class %u of row %u: 1 to %u", cls[i], rows[i], ncls);
+    }
+    if (!ncls && !a->d_cls) return SK_OK;                 // (off, and never on)
+    CA_HIP(hipSetDevice(a->device));
+    if (!a->d_cls) {                                      // all zero: no row is in any set, no member has classes
+        const size_t bytes = (size_t)(a->total_rows ? a->total_rows : 1u), ob = ((size_t)a->nm * SK_SCRUB_SWEEP_MAX * 2u + 1u) * 8u;
+        uint8_t *p = NULL; uint32_t *q = NULL; unsigned long long *o = NULL;
+        CA_HIP(hipMalloc((void **)&p, bytes));
+        if (hipMalloc((void **)&q, (size_t)a->nm * 4u) != hipSuccess || hipMalloc((void **)&o, ob) != hipSuccess) {
+            (void)hipFree(p); (void)hipFree(q);
+            return sk_fail_(a->ctx, SK_E_HIP, "no room for the class bytes");
+        }
+        a->d_cls = p; a->d_ncls = q; a->d_cls_out = o;
+        a->ncls.assign(a->nm, 0u);
+        CA_HIP(hipMemsetAsync(a->d_cls, 0, bytes, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_ncls, 0, (size_t)a->nm * 4u, a->stream));
+    }
+    if (a->nrows[member]) CA_HIP(hipMemsetAsync(a->d_cls + a->base[member], 0, a->nrows[member], a->stream));
+    if (n) {
+        int rc = cov_room(a, (void **)&a->d_rows, &a->rows_cap, (size_t)n * 4u, false);
+        if (rc == SK_OK) rc = cov_room(a, (void **)&a->d_cls_up, &a->cls_up_cap, (size_t)n, false);
+        if (rc != SK_OK) return rc;
+        CA_HIP(hipMemcpyAsync(a->d_rows, rows, (size_t)n * 4u, hipMemcpyHostToDevice, a->stream));
+        CA_HIP(hipMemcpyAsync(a->d_cls_up, cls, (size_t)n, hipMemcpyHostToDevice, a->stream));
+        hipLaunchKernelGGL(covacc_class_scatter, dim3(cov_grid(n)), dim3(256), 0, a->stream, (const uint32_t *)a->d_rows,
+                           (const uint8_t *)a->d_cls_up, n, a->nrows[member], ncls, a->d_cls + a->base[member]);
+        CA_HIP(hipGetLastError());
+    }
+    CA_HIP(hipMemcpyAsync(a->d_ncls + member, &ncls, 4u, hipMemcpyHostToDevice, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    a->ncls[member] = ncls;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_finish_target_classes(sk_covacc *a, uint64_t *out_unique, uint64_t *out_total, uint64_t *out_stray)
+{
+    if (!a || !out_unique || !out_total || !out_stray) return SK_E_ARG;
+    uint32_t F = 0;
+    for (uint32_t m = 0; m < a->nm && !a->ncls.empty(); m++) if (a->ncls[m] > F) F = a->ncls[m];
+    if (!F) return sk_fail_(a->ctx, SK_E_STATE, "no member has classes (sk_covacc_set_classes)");
+    CA_HIP(hipSetDevice(a->device));
+    const size_t ncell = (size_t)a->nm * SK_SCRUB_SWEEP_MAX * 2u;
+    std::vector<unsigned long long> h(ncell + 1u, 0ull);
+    cov_t0(a);
+    CA_HIP(hipMemsetAsync(a->d_cls_out, 0, (ncell + 1u) * 8u, a->stream));
+    unsigned gx = (a->max_rows + 255u) / 256u;
+    gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
+    hipLaunchKernelGGL(covacc_class_finish, dim3(gx, a->nm), dim3(256), 0, a->stream, (const uint32_t *)a->d_depth,
+                       (const uint64_t *)a->d_base, (const uint32_t *)a->d_nrows, (const uint8_t *)a->d_cls, (const uint32_t *)a->d_ncls,
+                       a->d_cls_out, a->d_cls_out + ncell);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipMemcpyAsync(h.data(), a->d_cls_out, (ncell + 1u) * 8u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_cls);
+    for (uint32_t m = 0; m < a->nm; m++) {                // class c counts for the fractions 0 .. c - 1: suffix sums
+        unsigned long long u = 0, t = 0;
+        for (uint32_t q = F; q-- > 0u; ) {
+            if (q < a->ncls[m]) { u += h[((size_t)m * SK_SCRUB_SWEEP_MAX + q) * 2u]; t += h[((size_t)m * SK_SCRUB_SWEEP_MAX + q) * 2u + 1u]; }
+            out_unique[(size_t)m * F + q] = u; out_total[(size_t)m * F + q] = t;
+        }
+    }
+    *out_stray = h[ncell];
     return SK_OK;
 }

@@ -477,3 +477,98 @@ out:
     (void)hipFree(d_out);
     return rc;
 }
+
+// ---- a hit list by scrub class (include/strainer_kmer.h has the rule; coverage_depth --scrub-sweep) ----
+// cov_thr_insert with every line's class handed in instead of worked out from its pair's total: the lines of a (sample, key) pair carry
+// one class, which lands beside the pair's slot, and cov_thr_sweep bins each sample's slots by class; the host counts the lines per
+// sample and class in the pass that sizes the segments and takes the suffix sums.
+static_assert(SK_SCRUB_SWEEP_MAX == SK_COVACC_THRESHOLDS_MAX, "cov_thr_sweep's bins serve both lists");
+
+__global__ void cov_cls_insert(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ sample, const uint8_t *__restrict__ kcls,
+                               uint64_t n, uint32_t nsamples, uint32_t ncls, const uint64_t *__restrict__ seg_base,
+                               const uint64_t *__restrict__ seg_mask, unsigned long long *__restrict__ table, uint32_t *__restrict__ cls)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t s = sample[i], c = kcls[i];
+        if (s >= nsamples || c < 1u || c > ncls) continue;    // (never: the host has checked)
+        const uint64_t k = keys[i], base = seg_base[s], mask = seg_mask[s];
+        uint64_t slot = cov_mix(k) & mask;
+        for (;;) {                                            // (ends: the segment has twice the slots of the sample's lines)
+            const unsigned long long old = atomicCAS(&table[base + slot], COV_EMPTY, (unsigned long long)k);
+            if (old == COV_EMPTY || old == k) break;
+            slot = (slot + 1) & mask;
+        }
+        atomicMax(&cls[base + slot], c);
+    }
+}
+
+extern "C" int sk_distinct_classes(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, const uint8_t *cls, uint64_t n, uint32_t nsamples,
+                                   uint32_t ncls, uint64_t *out_unique, uint64_t *out_total)
+{
+    const uint32_t NC = SK_SCRUB_SWEEP_MAX + 1u;
+    if (!ctx || !out_unique || !out_total || ncls < 1u || ncls > SK_SCRUB_SWEEP_MAX || (n && (!keys || !sample || !cls))) return SK_E_ARG;
+    if (nsamples == 0) return n ? SK_E_ARG : SK_OK;
+    memset(out_unique, 0, (size_t)nsamples * ncls * 8);
+    memset(out_total, 0, (size_t)nsamples * ncls * 8);
+    if (!n) return SK_OK;
+    std::vector<uint64_t> lines((size_t)nsamples * NC, 0), cnt(nsamples, 0), base(nsamples), mask(nsamples);
+    for (uint64_t i = 0; i < n; i++) {
+        if (sample[i] >= nsamples) return sk_fail_(ctx, SK_E_ARG, "sample %u out of range", sample[i]);
+        if (keys[i] == COV_EMPTY) return sk_fail_(ctx, SK_E_ARG, "reserved key value");
+        if (cls[i] < 1u || cls[i] > ncls) return sk_fail_(ctx, SK_E_ARG, "class %u: 1 to %u", cls[i], ncls);
+        lines[(size_t)sample[i] * NC + cls[i]]++;
+        cnt[sample[i]]++;
+    }
+    uint64_t slots = 0, max_seg = 0;
+    for (uint32_t s = 0; s < nsamples; s++) {
+        uint64_t c = 2;
+        while (c < 2 * cnt[s]) c <<= 1;
+        base[s] = slots; mask[s] = c - 1; slots += c;
+        if (c > max_seg) max_seg = c;
+    }
+    int rc = SK_OK;
+    void *d_keys = NULL, *d_sample = NULL, *d_kcls = NULL, *d_seg = NULL, *d_table = NULL, *d_cls = NULL, *d_out = NULL;
+    std::vector<unsigned long long> h((size_t)nsamples * NC);
+#define COV_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = sk_fail_(ctx, SK_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); goto out; } } while (0)
+    COV_HIP(hipSetDevice(sk_ctx_device_(ctx)));
+    COV_HIP(hipMalloc(&d_keys, n * 8));
+    COV_HIP(hipMalloc(&d_sample, n * 4));
+    COV_HIP(hipMalloc(&d_kcls, n));
+    COV_HIP(hipMalloc(&d_seg, (size_t)nsamples * 16));
+    COV_HIP(hipMalloc(&d_table, slots * 8));
+    COV_HIP(hipMalloc(&d_cls, slots * 4));
+    COV_HIP(hipMalloc(&d_out, h.size() * 8));
+    COV_HIP(hipMemcpy(d_keys, keys, n * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_sample, sample, n * 4, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_kcls, cls, n, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy(d_seg, base.data(), (size_t)nsamples * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemcpy((uint64_t *)d_seg + nsamples, mask.data(), (size_t)nsamples * 8, hipMemcpyHostToDevice));
+    COV_HIP(hipMemset(d_table, 0xFF, slots * 8));
+    COV_HIP(hipMemset(d_cls, 0, slots * 4));
+    COV_HIP(hipMemset(d_out, 0, h.size() * 8));
+    {
+        const uint64_t g = (n + 255) / 256, gs = (max_seg + 255u) / 256u;
+        hipLaunchKernelGGL(cov_cls_insert, dim3((unsigned)(g > 65536u ? 65536u : g)), dim3(256), 0, 0, (const uint64_t *)d_keys,
+                           (const uint32_t *)d_sample, (const uint8_t *)d_kcls, n, nsamples, ncls, (const uint64_t *)d_seg,
+                           (const uint64_t *)d_seg + nsamples, (unsigned long long *)d_table, (uint32_t *)d_cls);
+        COV_HIP(hipGetLastError());
+        hipLaunchKernelGGL(cov_thr_sweep, dim3((unsigned)(gs > 256u ? 256u : gs), nsamples > 4096u ? 4096u : nsamples), dim3(256), 0, 0,
+                           (const uint32_t *)d_cls, (const uint64_t *)d_seg, (const uint64_t *)d_seg + nsamples, nsamples,
+                           (unsigned long long *)d_out);
+    }
+    COV_HIP(hipGetLastError());
+    COV_HIP(hipMemcpy(h.data(), d_out, h.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < nsamples; s++) {                 // class c counts for the fractions 0 .. c - 1: suffix sums
+        uint64_t u = 0, l = 0;
+        for (uint32_t q = ncls; q-- > 0u; ) {
+            u += h[(size_t)s * NC + q + 1u]; l += lines[(size_t)s * NC + q + 1u];
+            out_unique[(size_t)s * ncls + q] = u; out_total[(size_t)s * ncls + q] = l;
+        }
+    }
+#undef COV_HIP
+out:
+    (void)hipFree(d_keys); (void)hipFree(d_sample); (void)hipFree(d_kcls); (void)hipFree(d_seg); (void)hipFree(d_table); (void)hipFree(d_cls);
+    (void)hipFree(d_out);
+    return rc;
+}

@@ -14,6 +14,8 @@
 //   flt_eq_count/flt_eq_scan/flt_mark   rows with key > T go; rows with key == T go in row order until
 //                 the quota is used (what a stable descending sort does with ties)
 //   flt_hist      value histogram of one column (LDS-privatised) for the independent mode's threshold walk
+//   flt_class_add/flt_class_above   the scrub sweep (sk_filter_classes_*): a row's class is the number of listed fractions whose
+//                 informative set holds it; one byte per row is built here and only that byte comes back
 //
 // All of it is HBM-streaming integer/double work over N rows (N ~ 5-7 M: a few tens of MB per pass);
 // at that size every kernel is launch-latency bound, the point of running it here is that the fused
@@ -49,6 +51,9 @@ struct sk_filter {
     size_t       hist_cap;
     flt_state   *d_state;
     unsigned long long *d_sums;              // pan sum, meta sum, #pan > 0, #meta > 0, #gone
+    unsigned long long h_need[SK_SCRUB_SWEEP_MAX];   // the selects' row counts on their way up: a slot per run still on the stream
+    uint8_t     *d_cls; uint64_t cls_cap;    // the scrub sweep's class bytes: nothing of it exists until sk_filter_classes_* is called
+    unsigned long long *d_kept;              // [SK_SCRUB_SWEEP_MAX] rows kept per fraction, then as many: each select's cut key
 };
 
 #define FLT_HIP(f, call)                                                                           \
@@ -233,6 +238,46 @@ __global__ void flt_above(const int64_t *__restrict__ pan, const int64_t *__rest
     out[i] = (gone[i] || (p > 0 && p > pan_thr) || (m > 0 && m > meta_thr)) ? 1 : 0;
 }
 
+// the scrub sweep: cls[i] += 1 for every row the marks of this fraction keep, `times` fractions at once (fractions with one
+// n_scrub share their marks); kept += the rows kept, one atomic per wave
+__global__ void flt_class_add(const uint8_t *__restrict__ marks, uint64_t n, uint8_t times, uint8_t *__restrict__ cls,
+                              unsigned long long *__restrict__ kept)
+{
+    unsigned long long c = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        if (!marks[i]) { cls[i] = (uint8_t)(cls[i] + times); c++; }
+    c = flt_wave_sum(c);
+    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(kept, c);
+}
+
+struct flt_thr_list { long long pan[SK_SCRUB_SWEEP_MAX], meta[SK_SCRUB_SWEEP_MAX]; uint32_t n; };
+
+// ... and the independent mode: flt_above's test at every fraction's pair of thresholds, kept[q] += the rows fraction q keeps
+__global__ void flt_class_above(const int64_t *__restrict__ pan, const int64_t *__restrict__ meta, const uint8_t *__restrict__ gone, uint64_t n,
+                                flt_thr_list th, uint8_t *__restrict__ cls, unsigned long long *__restrict__ kept)
+{
+    const uint32_t nf = th.n < SK_SCRUB_SWEEP_MAX ? th.n : SK_SCRUB_SWEEP_MAX;
+    uint32_t k[SK_SCRUB_SWEEP_MAX];                  // (every loop over it is unrolled: registers)
+#pragma unroll
+    for (uint32_t q = 0; q < SK_SCRUB_SWEEP_MAX; q++) k[q] = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const int64_t p = pan[i], m = meta[i];
+        const bool alive = !gone[i];
+        uint8_t c = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < SK_SCRUB_SWEEP_MAX; q++) {
+            const bool in = alive && q < nf && !((p > 0 && p > th.pan[q]) || (m > 0 && m > th.meta[q]));
+            c += in ? 1 : 0; k[q] += in ? 1u : 0u;
+        }
+        cls[i] = c;
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < SK_SCRUB_SWEEP_MAX; q++) {
+        const unsigned long long s = flt_wave_sum(k[q]);
+        if ((threadIdx.x & 63u) == 0 && s && q < nf) atomicAdd(&kept[q], s);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 static void flt_release(sk_filter *f)
 {
@@ -282,7 +327,7 @@ extern "C" void sk_filter_destroy(sk_filter *f)
     hipSetDevice(f->device);
     hipStreamSynchronize(f->stream);
     flt_release(f);
-    hipFree(f->d_hist); hipFree(f->d_state); hipFree(f->d_sums);
+    hipFree(f->d_hist); hipFree(f->d_state); hipFree(f->d_sums); hipFree(f->d_cls); hipFree(f->d_kept);
     hipStreamDestroy(f->stream);
     delete f;
 }
@@ -358,6 +403,28 @@ extern "C" int sk_filter_hist(sk_filter *f, int which, int64_t lo, uint32_t nbin
     return SK_OK;
 }
 
+// the marks of a joint scrub of n_scrub rows into d_out (n_scrub >= 1, f->n >= 1); with_keys = 0: d_keys already holds the scores.
+// slot: which of h_need carries the count up (it must stay as it is until the stream has been waited for)
+static int flt_joint_marks(sk_filter *f, int64_t pan_sum, int64_t meta_sum, uint64_t n_scrub, int with_keys, uint32_t slot)
+{
+    const uint64_t n = f->n;
+    const unsigned nb = (unsigned)((n + 255) / 256), nchunk = (unsigned)((n + FLT_CHUNK - 1) / FLT_CHUNK);
+    f->h_need[slot] = n_scrub;
+    FLT_HIP(f, hipMemsetAsync(f->d_state, 0, sizeof(flt_state), f->stream));
+    FLT_HIP(f, hipMemcpyAsync(&f->d_state->need, &f->h_need[slot], 8, hipMemcpyHostToDevice, f->stream));
+    if (with_keys)
+        hipLaunchKernelGGL(flt_score, dim3(nb), dim3(256), 0, f->stream, f->d_pan, f->d_meta, f->d_gone, n, (double)pan_sum, (double)meta_sum, f->d_keys);
+    for (int pass = 0; pass < 8; pass++) {
+        hipLaunchKernelGGL(flt_digit, dim3(1024), dim3(256), 0, f->stream, f->d_keys, n, f->d_state, pass);
+        hipLaunchKernelGGL(flt_pick, dim3(1), dim3(64), 0, f->stream, f->d_state, pass);
+    }
+    hipLaunchKernelGGL(flt_eq_count, dim3(nchunk), dim3(FLT_THREADS), 0, f->stream, f->d_keys, n, f->d_state, f->d_blk);
+    hipLaunchKernelGGL(flt_eq_scan, dim3(1), dim3(FLT_THREADS), 0, f->stream, f->d_blk, nchunk);
+    hipLaunchKernelGGL(flt_mark, dim3(nchunk), dim3(FLT_THREADS), 0, f->stream, f->d_keys, n, f->d_state, f->d_blk, f->d_out);
+    FLT_HIP(f, hipGetLastError());
+    return SK_OK;
+}
+
 extern "C" int sk_filter_joint(sk_filter *f, int64_t pan_sum, int64_t meta_sum, uint64_t n_scrub, uint8_t *out_scrub)
 {
     if (!f || (f->n && !out_scrub)) return SK_E_ARG;
@@ -369,19 +436,8 @@ extern "C" int sk_filter_joint(sk_filter *f, int64_t pan_sum, int64_t meta_sum, 
         FLT_HIP(f, hipStreamSynchronize(f->stream));
         return SK_OK;
     }
-    const unsigned nb = (unsigned)((n + 255) / 256), nchunk = (unsigned)((n + FLT_CHUNK - 1) / FLT_CHUNK);
-    flt_state init;
-    memset(&init, 0, sizeof init);
-    init.need = n_scrub;
-    FLT_HIP(f, hipMemcpyAsync(f->d_state, &init, sizeof init, hipMemcpyHostToDevice, f->stream));
-    hipLaunchKernelGGL(flt_score, dim3(nb), dim3(256), 0, f->stream, f->d_pan, f->d_meta, f->d_gone, n, (double)pan_sum, (double)meta_sum, f->d_keys);
-    for (int pass = 0; pass < 8; pass++) {
-        hipLaunchKernelGGL(flt_digit, dim3(1024), dim3(256), 0, f->stream, f->d_keys, n, f->d_state, pass);
-        hipLaunchKernelGGL(flt_pick, dim3(1), dim3(64), 0, f->stream, f->d_state, pass);
-    }
-    hipLaunchKernelGGL(flt_eq_count, dim3(nchunk), dim3(FLT_THREADS), 0, f->stream, f->d_keys, n, f->d_state, f->d_blk);
-    hipLaunchKernelGGL(flt_eq_scan, dim3(1), dim3(FLT_THREADS), 0, f->stream, f->d_blk, nchunk);
-    hipLaunchKernelGGL(flt_mark, dim3(nchunk), dim3(FLT_THREADS), 0, f->stream, f->d_keys, n, f->d_state, f->d_blk, f->d_out);
+    const int rc = flt_joint_marks(f, pan_sum, meta_sum, n_scrub, 1, 0);
+    if (rc != SK_OK) return rc;
     flt_state fin;
     FLT_HIP(f, hipMemcpyAsync(out_scrub, f->d_out, n, hipMemcpyDeviceToHost, f->stream));
     FLT_HIP(f, hipMemcpyAsync(&fin, f->d_state, 3 * 8, hipMemcpyDeviceToHost, f->stream));
@@ -400,5 +456,95 @@ extern "C" int sk_filter_above(sk_filter *f, int64_t pan_thr, int64_t meta_thr, 
     hipLaunchKernelGGL(flt_above, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, f->stream, f->d_pan, f->d_meta, f->d_gone, n, pan_thr, meta_thr, f->d_out);
     FLT_HIP(f, hipMemcpyAsync(out_scrub, f->d_out, n, hipMemcpyDeviceToHost, f->stream));
     FLT_HIP(f, hipStreamSynchronize(f->stream));
+    return SK_OK;
+}
+
+// ---- the scrub sweep: every row's class for a descending list of fractions (include/strainer_kmer.h has the rule) ----
+static int flt_class_room(sk_filter *f)
+{
+    if (!f->d_kept) FLT_HIP(f, hipMalloc((void **)&f->d_kept, 2 * SK_SCRUB_SWEEP_MAX * 8));
+    if (f->n > f->cls_cap) {
+        if (f->d_cls) { hipFree(f->d_cls); f->d_cls = NULL; f->cls_cap = 0; }
+        FLT_HIP(f, hipMalloc((void **)&f->d_cls, f->cap ? f->cap : 1));
+        f->cls_cap = f->cap;
+    }
+    FLT_HIP(f, hipMemsetAsync(f->d_kept, 0, 2 * SK_SCRUB_SWEEP_MAX * 8, f->stream));
+    return SK_OK;
+}
+
+// The select runs once per distinct n_scrub (the scores are computed once); flt_class_add folds each run's marks into the class
+// bytes.  The runs follow each other on the stream without a wait: each leaves its cut key in a slot behind kept[], and all of them
+// are looked at once at the end (a cut key of 0: that run was asked for more rows than take part).  n_scrub must not decrease along
+// the list: a smaller fraction scrubs at least as many rows.
+extern "C" int sk_filter_classes_joint(sk_filter *f, int64_t pan_sum, int64_t meta_sum, const uint64_t *n_scrub, uint32_t nf,
+                                       uint8_t *out_class, uint64_t *kept)
+{
+    if (!f || !n_scrub || !kept || nf < 1u || nf > SK_SCRUB_SWEEP_MAX || (f->n && !out_class)) return SK_E_ARG;
+    for (uint32_t q = 1; q < nf; q++)
+        if (n_scrub[q] < n_scrub[q - 1]) return sk_fail_(f->ctx, SK_E_ARG, "filter: the rows to scrub must not decrease along the list");
+    FLT_HIP(f, hipSetDevice(f->device));
+    const uint64_t n = f->n;
+    for (uint32_t q = 0; q < nf; q++) kept[q] = 0;
+    if (!n) return SK_OK;
+    int rc = flt_class_room(f);
+    if (rc != SK_OK) return rc;
+    FLT_HIP(f, hipMemsetAsync(f->d_cls, 0, n, f->stream));
+    unsigned long long h[2 * SK_SCRUB_SWEEP_MAX];
+    int scored = 0;
+    for (uint32_t q = 0; q < nf; ) {
+        uint32_t e = q + 1;
+        while (e < nf && n_scrub[e] == n_scrub[q]) e++;
+        if (n_scrub[q] == 0) {
+            hipLaunchKernelGGL(flt_class_add, dim3(1024), dim3(256), 0, f->stream, (const uint8_t *)f->d_gone, n, (uint8_t)(e - q), f->d_cls, f->d_kept + q);
+        } else {
+            if ((rc = flt_joint_marks(f, pan_sum, meta_sum, n_scrub[q], !scored, q)) != SK_OK) return rc;
+            scored = 1;
+            hipLaunchKernelGGL(flt_class_add, dim3(1024), dim3(256), 0, f->stream, (const uint8_t *)f->d_out, n, (uint8_t)(e - q), f->d_cls, f->d_kept + q);
+            FLT_HIP(f, hipMemcpyAsync(f->d_kept + SK_SCRUB_SWEEP_MAX + q, &f->d_state->prefix, 8, hipMemcpyDeviceToDevice, f->stream));
+        }
+        FLT_HIP(f, hipGetLastError());
+        q = e;                                                // (in order on the stream: the next select reuses d_state and d_out)
+    }
+    FLT_HIP(f, hipMemcpyAsync(h, f->d_kept, sizeof h, hipMemcpyDeviceToHost, f->stream));
+    FLT_HIP(f, hipStreamSynchronize(f->stream));
+    for (uint32_t q = 0; q < nf; q++)
+        if (n_scrub[q] && (q == 0 || n_scrub[q] != n_scrub[q - 1]) && h[SK_SCRUB_SWEEP_MAX + q] == 0)
+            return sk_fail_(f->ctx, SK_E_ARG, "filter: asked to scrub %llu rows, fewer take part", (unsigned long long)n_scrub[q]);
+    FLT_HIP(f, hipMemcpyAsync(out_class, f->d_cls, n, hipMemcpyDeviceToHost, f->stream));
+    FLT_HIP(f, hipStreamSynchronize(f->stream));
+    for (uint32_t q = 0; q < nf; ) {                          // (fractions with one n_scrub share one count)
+        uint32_t e = q + 1;
+        while (e < nf && n_scrub[e] == n_scrub[q]) e++;
+        for (uint32_t j = q; j < e; j++) kept[j] = h[q];
+        q = e;
+    }
+    return SK_OK;
+}
+
+// thresholds must not increase along the list: a smaller fraction walks to a threshold at most as high
+extern "C" int sk_filter_classes_above(sk_filter *f, const int64_t *pan_thr, const int64_t *meta_thr, uint32_t nf, uint8_t *out_class,
+                                       uint64_t *kept)
+{
+    if (!f || !pan_thr || !meta_thr || !kept || nf < 1u || nf > SK_SCRUB_SWEEP_MAX || (f->n && !out_class)) return SK_E_ARG;
+    for (uint32_t q = 1; q < nf; q++)
+        if (pan_thr[q] > pan_thr[q - 1] || meta_thr[q] > meta_thr[q - 1])
+            return sk_fail_(f->ctx, SK_E_ARG, "filter: the thresholds must not increase along the list");
+    FLT_HIP(f, hipSetDevice(f->device));
+    const uint64_t n = f->n;
+    for (uint32_t q = 0; q < nf; q++) kept[q] = 0;
+    if (!n) return SK_OK;
+    const int rc = flt_class_room(f);
+    if (rc != SK_OK) return rc;
+    flt_thr_list th;
+    memset(&th, 0, sizeof th);
+    for (uint32_t q = 0; q < nf; q++) { th.pan[q] = (long long)pan_thr[q]; th.meta[q] = (long long)meta_thr[q]; }
+    th.n = nf;
+    unsigned long long h[SK_SCRUB_SWEEP_MAX];
+    hipLaunchKernelGGL(flt_class_above, dim3(1024), dim3(256), 0, f->stream, f->d_pan, f->d_meta, f->d_gone, n, th, f->d_cls, f->d_kept);
+    FLT_HIP(f, hipGetLastError());
+    FLT_HIP(f, hipMemcpyAsync(out_class, f->d_cls, n, hipMemcpyDeviceToHost, f->stream));
+    FLT_HIP(f, hipMemcpyAsync(h, f->d_kept, sizeof h, hipMemcpyDeviceToHost, f->stream));
+    FLT_HIP(f, hipStreamSynchronize(f->stream));
+    for (uint32_t q = 0; q < nf; q++) kept[q] = h[q];
     return SK_OK;
 }

@@ -40,6 +40,8 @@
 #include "sk_cpus.h"
 #include "sk_rendezvous.h"
 #include "sk_internal.h"
+#include "sk_sweep.h"
+#pragma weak skh_scrub_filter_resident_sweep
 
 int sk_rendezvous_exchange(int rank, int world, const char *base_path, int my_status, unsigned char *payload128, double timeout_s)
 {
@@ -2431,6 +2433,8 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
     int crc;
     double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
     double scrub_fraction = -1.0;                    /* >= 0: print the scrub filter's result instead of the table */
+    const char *scrub_list = NULL;                   /* --scrub f0,f1,...: the scrub sweep (scrub_fraction is f0) */
+    skw_list scrub_sw;
     int scrub_independent = 0, j;
     const char *scrub_out = NULL;                    /* --scrub-out FILE: the filter's result goes there instead of stdout */
     int detect_argc = 0;                             /* --detect ...: strain_detect's arguments, run on the resident table */
@@ -2465,6 +2469,13 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
         if (!strncmp(argv[c], "--scrub", 7) && (argv[c][7] == 0 || argv[c][7] == '=')) {
             const char *v = argv[c][7] ? argv[c] + 8 : (c + 1 < argc ? argv[++c] : "");
             char *e;
+            if (strchr(v, ',')) {                    /* a list: the scrub sweep (include/strainer_kmer.h has the rule) */
+                char why[160];
+                if (skw_parse_list(v, &scrub_sw, why, sizeof why)) { fprintf(err, "kmer_scrub_count: --scrub %s: %s\n", v, why); return 1; }
+                scrub_list = v;
+                scrub_fraction = scrub_sw.f[0];
+                continue;
+            }
             scrub_fraction = strtod(v, &e);
             if (e == v || *e || scrub_fraction < 0.0 || scrub_fraction > 1.0) {
                 fprintf(err, "kmer_scrub_count: --scrub needs a fraction between 0.0 and 1.0\n");
@@ -2475,6 +2486,24 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
         argv[j++] = argv[c];
     }
     argc = j;
+    {   /* a list of fractions and --coverage-scrub-sweep behind --detect go together: step 3 reads the class file step 2 writes */
+        int want_sw = 0;
+        for (c = 1; c < detect_argc; c++)
+            if (!strncmp(detect_argv[c], "--coverage-scrub-sweep", 22) && (detect_argv[c][22] == 0 || detect_argv[c][22] == '=')) want_sw = 1;
+            else if (!strncmp(detect_argv[c], "--scrub-classes", 15) && (detect_argv[c][15] == 0 || detect_argv[c][15] == '=')) {
+                fprintf(err, "kmer_scrub_count: behind --detect the class file is the one --scrub f0,f1,... writes (no --scrub-classes)\n");
+                return 1;
+            }
+        if (scrub_list && !want_sw) {
+            fprintf(err, "kmer_scrub_count: --scrub %s: a list of fractions goes with --detect ... --coverage-scrub-sweep\n", scrub_list);
+            return 1;
+        }
+        if (want_sw && !scrub_list) {
+            fprintf(err, "kmer_scrub_count: --coverage-scrub-sweep behind --detect goes with a list of fractions, --scrub f0,f1,...\n");
+            return 1;
+        }
+        if (scrub_list && !skh_scrub_filter_resident_sweep) { fprintf(err, "kmer_scrub_count: this build has no scrub sweep\n"); return 1; }
+    }
 
     optind = 1;
     while ((c = getopt(argc, argv, "A:B:C:r:p:Hhud")) != -1) {
@@ -2575,7 +2604,7 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
     t4 = now_s();
     if (rank == 0 && scrub_fraction >= 0.0) {
         FILE *so = out;
-        char tmp_path[64] = "";
+        char tmp_path[64] = "", cls_path[4200] = "";
         const char *list_path = scrub_out;
         if (detect_argv && !scrub_out) {              /* step 3 reads the list from a file: a temporary one, copied to stdout */
             int fd;
@@ -2586,7 +2615,12 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
             list_path = tmp_path;
         }
         if (list_path && !(so = fopen(list_path, "w"))) { fprintf(err, "kmer_scrub_count: cannot write %s\n", list_path); goto done; }
-        status = skh_scrub_filter_resident(ctx, &ks, C != NULL, scrub_fraction, scrub_independent, so, err);
+        if (scrub_list) {                             /* (a list goes with --detect: list_path is a file) */
+            if (strlen(list_path) + 9 > sizeof cls_path) { fprintf(err, "kmer_scrub_count: %s: the path is too long\n", list_path); fclose(so); goto done; }
+            snprintf(cls_path, sizeof cls_path, "%s.classes", list_path);
+            status = skh_scrub_filter_resident_sweep(ctx, &ks, C != NULL, scrub_list, scrub_independent, cls_path, so, err);
+        } else
+            status = skh_scrub_filter_resident(ctx, &ks, C != NULL, scrub_fraction, scrub_independent, so, err);
         if (so != out) fclose(so);
         if (tmp_path[0] && status == 0) {             /* no --scrub-out: the list still goes to stdout, as --scrub alone does */
             FILE *f = fopen(tmp_path, "r");
@@ -2605,6 +2639,7 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
             status = skh_strain_detect_resident(c2, &ks, list_path, detect_argc, detect_argv, out, err);
         }
         if (tmp_path[0]) unlink(tmp_path);
+        if (tmp_path[0] && cls_path[0]) unlink(cls_path);
         goto done;
     }
     if (rank == 0) {

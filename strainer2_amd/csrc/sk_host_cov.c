@@ -18,6 +18,7 @@
 #include "../../include/strainer_kmer.h"
 #include "sk_common.h"
 #include "sk_pyfmt.h"
+#include "sk_sweep.h"
 #include "sk_internal.h"
 
 /* ------------------------------------------------------------------ a small insertion-ordered name table */
@@ -114,6 +115,9 @@ typedef struct {
     int64_t   th_t[SK_COVACC_THRESHOLDS_MAX]; uint32_t th_nt;
     uint64_t *th_key; uint32_t *th_sample, *th_tot; uint64_t th_n, th_cap; size_t th_klen; int th_bad;
     uint64_t **th_u, **th_tt; uint32_t nth_s;
+    /* the scrub sweep (cl_F = 0: off): the fractions' texts and the sets' sizes; per sample the numbers per fraction (cl_F each, or NULL) */
+    uint32_t  cl_F; char cl_frac[SK_SCRUB_SWEEP_MAX][SKW_TEXT_MAX]; uint64_t cl_size[SK_SCRUB_SWEEP_MAX];
+    uint64_t **cl_u, **cl_t; uint32_t ncl_s;
 } hitlist;
 
 enum { COV_OK = 0, COV_OPEN, COV_FIELDS, COV_INT, COV_NOMEM };
@@ -488,6 +492,8 @@ static void hitlist_free(hitlist *h)
     free(h->rc_hist); free(h->rc_pairs); free(h->rc_smp);
     for (s = 0; s < h->nth_s; s++) { free(h->th_u[s]); free(h->th_tt[s]); }
     free(h->th_u); free(h->th_tt); free(h->th_key); free(h->th_sample); free(h->th_tot);
+    for (s = 0; s < h->ncl_s; s++) { free(h->cl_u[s]); free(h->cl_t[s]); }
+    free(h->cl_u); free(h->cl_t);
     free(h->key); free(h->sample); free(h->depth_order); free(h->eval_order); free(h->gid); free(h->gsample);
     names_free(&h->smp); names_free(&h->text);
     memset(h, 0, sizeof *h);
@@ -860,6 +866,205 @@ int skc_report_thresholds(skc_acc *a, const char *hits_file_name, FILE *out, FIL
     return 0;
 }
 
+/* ---- the scrub sweep (strain_detect --coverage-scrub-sweep, coverage_depth --scrub-sweep; include/strainer_kmer.h has the rule) ---- */
+void skc_classes_free(skc_classes *c)
+{
+    if (!c) return;
+    free(c->arena); free(c->off); free(c->cls);
+    memset(c, 0, sizeof *c);
+}
+
+/* a class file's k-mer line: text (len bytes) and class */
+static int classes_push(skc_classes *c, uint64_t *cap, uint64_t *acap, const char *text, size_t len, uint8_t cls)
+{
+    if (c->n == *cap) {
+        const uint64_t cap2 = *cap ? *cap * 2 : 1u << 12;
+        uint64_t *o = realloc(c->off, cap2 * sizeof *o);
+        uint8_t *k;
+        if (!o) return 1;
+        c->off = o;
+        if (!(k = realloc(c->cls, cap2))) return 1;
+        c->cls = k;
+        *cap = cap2;
+    }
+    if (c->arena_len + len + 1 > *acap) {
+        uint64_t cap2 = *acap ? *acap * 2 : 1u << 16;
+        char *a;
+        while (cap2 < c->arena_len + len + 1) cap2 *= 2;
+        if (!(a = realloc(c->arena, cap2))) return 1;
+        c->arena = a;
+        *acap = cap2;
+    }
+    memcpy(c->arena + c->arena_len, text, len);
+    c->arena[c->arena_len + len] = 0;
+    c->off[c->n] = c->arena_len;
+    c->cls[c->n++] = cls;
+    c->arena_len += len + 1;
+    return 0;
+}
+
+int skc_classes_read(const char *path, skc_classes *c, char *why, size_t why_cap)
+{
+    gzFile g;
+    char line[1024];
+    uint64_t cap = 0, acap = 0, lineno = 0, per[SK_SCRUB_SWEEP_MAX + 1u], run;
+    uint32_t q;
+    int seen = 0;
+    FILE *probe = fopen(path, "rb");
+    memset(c, 0, sizeof *c);
+    memset(per, 0, sizeof per);
+    if (!probe) { snprintf(why, why_cap, "could not read it"); return 1; }
+    fclose(probe);
+    if (!(g = gzopen(path, "rb"))) { snprintf(why, why_cap, "could not read it"); return 1; }
+    while (gzgets(g, line, (int)sizeof line)) {
+        size_t len = strlen(line);
+        lineno++;
+        if (!len || line[len - 1] != '\n') {
+            if (len + 1 == sizeof line) { snprintf(why, why_cap, "line %llu is too long", (unsigned long long)lineno); goto bad; }
+        } else line[--len] = 0;
+        if (lineno == 1) {
+            skw_list l;
+            char w[120];
+            if (strncmp(line, "#min_fractions\t", 15)) { snprintf(why, why_cap, "its first line is not #min_fractions<TAB>f0,f1,..."); goto bad; }
+            if (skw_parse_list(line + 15, &l, w, sizeof w)) { snprintf(why, why_cap, "its fraction list: %s", w); goto bad; }
+            c->F = l.n;
+            memcpy(c->frac, l.text, sizeof c->frac);
+            continue;
+        }
+        if (lineno == 2) {
+            const char *p = line + 18;
+            if (strncmp(line, "#post_scrub_kmers\t", 18)) { snprintf(why, why_cap, "its second line is not #post_scrub_kmers<TAB>n0,n1,..."); goto bad; }
+            for (q = 0; q < c->F; q++) {
+                const char *e = p;
+                int64_t v;
+                while (*e && *e != ',') e++;
+                if (e == p || e - p > 18 || !skp_int(p, e, &v) || v < 0 || (q + 1 < c->F) != (*e == ',') || (q && (uint64_t)v > c->size[q - 1])) {
+                    snprintf(why, why_cap, "its second line does not give %u set sizes that do not grow", c->F);
+                    goto bad;
+                }
+                c->size[q] = (uint64_t)v;
+                p = e + 1;
+            }
+            seen = 1;
+            continue;
+        }
+        {
+            const char *tab = strchr(line, '\t');
+            int64_t v;
+            if (!tab || tab == line || strchr(tab + 1, '\t') || !skp_int(tab + 1, line + len, &v) || v < 1 || v > (int64_t)c->F) {
+                snprintf(why, why_cap, "line %llu is not kmer<TAB>class with a class from 1 to %u", (unsigned long long)lineno, c->F);
+                goto bad;
+            }
+            if (classes_push(c, &cap, &acap, line, (size_t)(tab - line), (uint8_t)v)) { snprintf(why, why_cap, "out of memory"); goto bad; }
+            per[v]++;
+        }
+    }
+    if (!seen) { snprintf(why, why_cap, "its two header lines are missing"); goto bad; }
+    for (run = 0, q = c->F; q-- > 0u; ) {              /* set q holds the rows of class >= q + 1 */
+        run += per[q + 1u];
+        if (run != c->size[q]) {
+            snprintf(why, why_cap, "%llu lines have class %u or more, its header says %llu", (unsigned long long)run, q + 1u, (unsigned long long)c->size[q]);
+            goto bad;
+        }
+    }
+    gzclose(g);
+    return 0;
+bad:
+    gzclose(g);
+    skc_classes_free(c);
+    return 1;
+}
+
+int skc_set_classes(skc_acc *a, const skc_classes *c)
+{
+    if (!a || !c || c->F < 1u || c->F > SK_SCRUB_SWEEP_MAX) return -1;
+    a->h.cl_F = c->F;
+    memcpy(a->h.cl_frac, c->frac, sizeof a->h.cl_frac);
+    memcpy(a->h.cl_size, c->size, sizeof a->h.cl_size);
+    return 0;
+}
+
+static int cl_room(hitlist *h, uint32_t g)
+{
+    if (g >= h->ncl_s) {
+        const uint32_t n2 = g + 16u;
+        uint64_t **u = realloc(h->cl_u, (size_t)n2 * sizeof *u), **t;
+        if (!u) return -1;
+        h->cl_u = u;
+        memset(u + h->ncl_s, 0, (size_t)(n2 - h->ncl_s) * sizeof *u);
+        if (!(t = realloc(h->cl_t, (size_t)n2 * sizeof *t))) return -1;        /* (ncl_s stays: the new cl_u entries are NULL and unread) */
+        h->cl_t = t;
+        memset(t + h->ncl_s, 0, (size_t)(n2 - h->ncl_s) * sizeof *t);
+        h->ncl_s = n2;
+    }
+    if (!h->cl_u[g] && !(h->cl_u[g] = calloc(SK_SCRUB_SWEEP_MAX, sizeof **h->cl_u))) return -1;
+    if (!h->cl_t[g] && !(h->cl_t[g] = calloc(SK_SCRUB_SWEEP_MAX, sizeof **h->cl_t))) return -1;
+    return 0;
+}
+
+/* a metagenome's numbers per fraction, counted elsewhere (F = the list's length): called next to skc_add_counts */
+int skc_add_class_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t F)
+{
+    hitlist *h = &a->h;
+    const char *sn = base_of(metagenome, metagenome + strlen(metagenome));
+    const int64_t g = name_get(&h->smp, sn, strlen(sn));
+    uint32_t q;
+    if (g < 0 || F != h->cl_F || cl_room(h, (uint32_t)g)) return -1;
+    for (q = 0; q < F; q++) { h->cl_u[g][q] += unique[q]; h->cl_t[g][q] += total[q]; }
+    return 0;
+}
+
+/* the table of what cl_u / cl_t hold, samples in the main table's order: one line per sample and fraction, zeros included */
+static void classes_print(const hitlist *h, const char *hits_file_name, FILE *out)
+{
+    char *strain = strdup(base_of(hits_file_name, hits_file_name + strlen(hits_file_name)));
+    const size_t sl = strain ? strlen(strain) : 0;
+    uint32_t k, q;
+    if (sl >= 13 && !memcmp(strain + sl - 12, "kmer_hits", 9) && !memcmp(strain + sl - 2, "gz", 2)) strain[sl - 13] = 0;
+    fputs("strain_name\tmetagenome\tmin_fraction\tgenome_num_informative_kmers\tunique_observed_informative_kmers\t"
+          "total_observed_informative_kmers\n", out);
+    for (k = 0; k < h->ndepth; k++) {
+        const uint32_t s = h->depth_order[k];
+        const uint64_t *u = s < h->ncl_s ? h->cl_u[s] : NULL, *t = s < h->ncl_s ? h->cl_t[s] : NULL;
+        for (q = 0; q < h->cl_F; q++)
+            fprintf(out, "%s\t%s\t%s\t%llu\t%llu\t%llu\n", strain ? strain : "", h->smp.name[s], h->cl_frac[q],
+                    (unsigned long long)h->cl_size[q], (unsigned long long)(u ? u[q] : 0u), (unsigned long long)(t ? t[q] : 0u));
+    }
+    free(strain);
+    fflush(out);
+}
+
+/* The table: call it after skc_report.  An accumulator that was fed hits folds its (sample, row) list here -- a row of class c counts
+ * for the fractions below c -- one that was fed counts prints what skc_add_class_counts left. */
+int skc_report_classes(skc_acc *a, const char *hits_file_name, const uint8_t *row_class, uint32_t nrows, FILE *out, FILE *err)
+{
+    hitlist *h = &a->h;
+    if (!h->cl_F) return 1;
+    if (cov_order_trailers(h)) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+    if (!h->given && h->n && !h->ncl_s) {            /* (folded already: a second report prints the same table) */
+        uint64_t *v = malloc((size_t)h->n * sizeof *v), i, j;
+        uint32_t q;
+        if (!v || !row_class) { free(v); fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+        for (i = 0; i < h->n; i++) v[i] = ((uint64_t)h->sample[i] << 32) | (h->key[i] & 0xFFFFFFFFu);
+        qsort(v, (size_t)h->n, sizeof *v, cmp_u64);
+        for (i = 0; i < h->n; i = j) {
+            const uint32_t g = (uint32_t)(v[i] >> 32), row = (uint32_t)v[i];
+            const uint32_t c = row < nrows ? row_class[row] : 0u;
+            for (j = i + 1; j < h->n && v[j] == v[i]; j++) ;
+            if (c < 1u || c > h->cl_F) {
+                free(v);
+                fprintf(err, "coverage_depth: internal error: a hit on row %u, which is in none of the scrub sweep's sets\n", row);
+                return 1;
+            }
+            if (cl_room(h, g)) { free(v); fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+            for (q = 0; q < c; q++) { h->cl_u[g][q] += 1; h->cl_t[g][q] += j - i; }
+        }
+        free(v);
+    }
+    classes_print(h, hits_file_name, out);
+    return 0;
+}
+
 /* ---- recurrence (strain_detect --coverage-recurrence, coverage_depth --recurrence; include/strainer_kmer.h has the rule) ---- */
 /* a run's tables, counted elsewhere: T samples by the caller's ordinals (metagenome[i] names ordinal i; every one of them has been
  * handed to skc_add_counts or skc_add_trailer, so the sample exists), hist[T + 1] (entry 0 is not used) and pairs[T x T] or NULL.
@@ -1096,8 +1301,91 @@ done:
     return status;
 }
 
+#pragma weak sk_distinct_classes
+typedef struct { uint64_t key; uint8_t cls; } cl_key;
+static int cmp_cl_key(const void *x, const void *y)
+{
+    const cl_key *a = x, *b = y;
+    return a->key < b->key ? -1 : a->key > b->key;
+}
+
+/* coverage_depth --scrub-sweep, before anything is printed: every passing line's class by its packed k-mer; *out_cls has h->n bytes.
+ * 1 with one line on err: a k-mer of the class file that is no A/C/G/T word of the hit list's length, one named twice, or a hit
+ * line whose k-mer the class file does not name. */
+static int cov_sweep_classes(const hitlist *h, const skc_classes *c, const char *kfile, const char *cfile, uint8_t **out_cls, FILE *err)
+{
+    cl_key *v = malloc((size_t)(c->n ? c->n : 1) * sizeof *v);
+    uint8_t *cls = malloc((size_t)(h->n ? h->n : 1));
+    uint64_t i;
+    if (!v || !cls) { fprintf(err, "coverage_depth: out of memory\n"); goto bad; }
+    for (i = 0; i < c->n; i++) {
+        const char *t = c->arena + c->off[i];
+        const size_t len = strlen(t);
+        uint64_t key = 0;
+        size_t j;
+        int plain = len >= 1 && len <= 31 && (h->klen == 0 || h->klen == len);
+        for (j = 0; plain && j < len; j++) {
+            const unsigned cde = sk_code((uint8_t)t[j]);
+            if (t[j] != "ACGT"[cde]) plain = 0;
+            key = (key << 2) | (cde & 3u);
+        }
+        if (!plain) { fprintf(err, "coverage_depth: --scrub-classes %s: k-mer %s is no A/C/G/T word of the hit list's k-mer length\n", cfile, t); goto bad; }
+        v[i].key = key; v[i].cls = c->cls[i];
+    }
+    qsort(v, (size_t)c->n, sizeof *v, cmp_cl_key);
+    for (i = 1; i < c->n; i++)
+        if (v[i].key == v[i - 1].key) { fprintf(err, "coverage_depth: --scrub-classes %s names a k-mer twice\n", cfile); goto bad; }
+    for (i = 0; i < h->n; i++) {
+        uint64_t lo = 0, hi = c->n;
+        while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (v[mid].key < h->key[i]) lo = mid + 1; else hi = mid; }
+        if (lo >= c->n || v[lo].key != h->key[i]) {
+            fprintf(err, "coverage_depth: --scrub-sweep: %s has a hit on a k-mer that the class file %s does not name\n", kfile, cfile);
+            goto bad;
+        }
+        cls[i] = v[lo].cls;
+    }
+    free(v);
+    *out_cls = cls;
+    return 0;
+bad:
+    free(v); free(cls);
+    return 1;
+}
+
+/* ... and the passing lines' (sample, packed k-mer, class) triples, counted on the device, to the table at `path` */
+static int cov_sweep_file(hitlist *h, sk_ctx *ctx, const char *kfile, const uint8_t *cls, const char *path, FILE *err)
+{
+    const uint32_t ns = h->smp.n, F = h->cl_F;
+    uint64_t *buf = NULL;
+    FILE *f;
+    uint32_t s, q;
+    int rc, status = 1;
+    if (ns) {
+        if (!(buf = calloc((size_t)ns * F * 2u, sizeof *buf))) { fprintf(err, "coverage_depth: out of memory\n"); return 1; }
+        rc = sk_distinct_classes(ctx, h->key, h->sample, cls, h->n, ns, F, buf, buf + (size_t)ns * F);
+        if (rc != SK_OK) { fprintf(err, "coverage_depth: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx)); goto done; }
+        for (s = 0; s < ns; s++) {
+            if (!buf[(size_t)ns * F + (size_t)s * F]) continue;        /* (no passing line: zeros are printed without) */
+            if (cl_room(h, s)) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+            for (q = 0; q < F; q++) { h->cl_u[s][q] = buf[(size_t)s * F + q]; h->cl_t[s][q] = buf[(size_t)ns * F + (size_t)s * F + q]; }
+        }
+    }
+    if (!(f = fopen(path, "w"))) { fprintf(err, "coverage_depth: could not write %s\n", path); goto done; }
+    classes_print(h, kfile, f);
+    status = ferror(f) ? 1 : 0;
+    if (fclose(f)) status = 1;
+done:
+    free(buf);
+    return status;
+}
+
 int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
 {
+    const char *sw_file = NULL, *sw_classes = NULL;
+    int want_sw = 0;
+    char *sw_path = NULL;
+    uint8_t *sw_cls = NULL;
+    skc_classes sw_c;
     const char *th_file = NULL, *th_list = NULL;
     int want_th = 0;
     char *th_path = NULL;
@@ -1114,7 +1402,8 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
             fprintf(out, "usage: coverage_depth [-h] --kmer_hits_file FILE [--min_kmer_hits N] [--background_metagenomes_file FILE]\n"
                          "                      [--spectrum[=FILE] [--spectrum-max D]] [--recurrence[=FILE] [--recurrence-pairs[=FILE]]]\n"
-                         "                      [--thresholds[=FILE] [--threshold-list t1,t2,...]]\n");
+                         "                      [--thresholds[=FILE] [--threshold-list t1,t2,...]]\n"
+                         "                      [--scrub-classes FILE --scrub-sweep[=FILE]]\n");
             return 0;
         }
         /* "--spectrum[=FILE] [--spectrum-max D]" (extension): the depth spectrum beside the table, see include/strainer_kmer.h */
@@ -1128,6 +1417,10 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         if (!strncmp(argv[i], "--thresholds", 12) && (argv[i][12] == 0 || argv[i][12] == '=')) { want_th = 1; th_file = argv[i][12] ? argv[i] + 13 : NULL; continue; }
         if (!strcmp(argv[i], "--threshold-list") && i + 1 < argc) { th_list = argv[++i]; continue; }
         if (!strncmp(argv[i], "--threshold-list=", 17)) { th_list = argv[i] + 17; continue; }
+        /* "--scrub-classes FILE --scrub-sweep[=FILE]" (extension): the table's numbers at every fraction of a class file */
+        if (!strncmp(argv[i], "--scrub-sweep", 13) && (argv[i][13] == 0 || argv[i][13] == '=')) { want_sw = 1; sw_file = argv[i][13] ? argv[i] + 14 : NULL; continue; }
+        if (!strcmp(argv[i], "--scrub-classes") && i + 1 < argc) { sw_classes = argv[++i]; continue; }
+        if (!strncmp(argv[i], "--scrub-classes=", 16)) { sw_classes = argv[i] + 16; continue; }
         if (cov_opt(argc, argv, &i, "-k", "--kmer_hits_file", &kfile, err, &bad)) { if (bad) return 2; continue; }
         if (cov_opt(argc, argv, &i, "-m", "--min_kmer_hits", &mtext, err, &bad)) { if (bad) return 2; continue; }
         if (cov_opt(argc, argv, &i, "-b", "--background_metagenomes_file", &bfile, err, &bad)) { if (bad) return 2; continue; }
@@ -1153,6 +1446,13 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
     }
     if (want_th && !sk_distinct_thresholds) { fprintf(err, "coverage_depth: error: --thresholds: this build has no device thresholds\n"); return 2; }
     if (want_rc && !sk_distinct_recurrence) { fprintf(err, "coverage_depth: error: --recurrence: this build has no device recurrence\n"); return 2; }
+    memset(&sw_c, 0, sizeof sw_c);
+    if (want_sw != (sw_classes != NULL)) { fprintf(err, "coverage_depth: error: --scrub-sweep and --scrub-classes go together\n"); return 2; }
+    if (want_sw && !sk_distinct_classes) { fprintf(err, "coverage_depth: error: --scrub-sweep: this build has no device classes\n"); return 2; }
+    if (want_sw) {
+        char why[200];
+        if (skc_classes_read(sw_classes, &sw_c, why, sizeof why)) { fprintf(err, "coverage_depth: error: --scrub-classes %s: %s\n", sw_classes, why); return 2; }
+    }
     memset(&h, 0, sizeof h);
     if (want_th) { memcpy(h.th_t, th_t, sizeof h.th_t); h.th_nt = th_nt; }
     rc = read_hits(&h, kfile, min_hits);
@@ -1169,6 +1469,17 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
         goto done;
     }
     if (want_th && !(th_path = cov_table_path(th_file, kfile, ".coverage_thresholds"))) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+    if (want_sw && h.general) {
+        fprintf(err, "coverage_depth: --scrub-sweep: %s has k-mer fields that are not A/C/G/T words of one length: a k-mer's class is not defined there\n", kfile);
+        goto done;
+    }
+    if (want_sw) {
+        h.cl_F = sw_c.F;
+        memcpy(h.cl_frac, sw_c.frac, sizeof h.cl_frac);
+        memcpy(h.cl_size, sw_c.size, sizeof h.cl_size);
+        if (cov_sweep_classes(&h, &sw_c, kfile, sw_classes, &sw_cls, err)) goto done;
+        if (!(sw_path = cov_table_path(sw_file, kfile, ".coverage_scrub_sweep"))) { fprintf(err, "coverage_depth: out of memory\n"); goto done; }
+    }
     if (want_rc && h.general) {
         fprintf(err, "coverage_depth: --recurrence: %s has k-mer fields that are not A/C/G/T words of one length: a k-mer seen in two samples is not defined there\n", kfile);
         goto done;
@@ -1192,9 +1503,11 @@ int skh_coverage_depth_main(int argc, char **argv, FILE *out, FILE *err)
     if (status == 0 && want_sp) status = cov_spectrum_file(&h, ctx, kfile, (uint32_t)sp_d, sp_path, err);
     if (status == 0 && want_rc) status = cov_recurrence_files(&h, ctx, kfile, rc_path, rp_path, err);
     if (status == 0 && want_th) status = cov_thresholds_file(&h, ctx, kfile, th_path, err);
+    if (status == 0 && want_sw) status = cov_sweep_file(&h, ctx, kfile, sw_cls, sw_path, err);
 done:
     fflush(out);
-    free(sp_path); free(rc_path); free(rp_path); free(th_path);
+    free(sp_path); free(rc_path); free(rp_path); free(th_path); free(sw_path); free(sw_cls);
+    skc_classes_free(&sw_c);
     sk_ctx_destroy(ctx);
     hitlist_free(&h);
     return status;

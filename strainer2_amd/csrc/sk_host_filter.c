@@ -19,6 +19,11 @@
 #include "../../include/strainer_kmer.h"
 #include "sk_pyfmt.h"
 #include "sk_gzfast.h"
+#include "sk_sweep.h"
+
+/* (the scrub sweep's device entries: weak, so that a build over a double of the device calls that lacks them still links) */
+#pragma weak sk_filter_classes_joint
+#pragma weak sk_filter_classes_above
 
 /* ------------------------------------------------------------------ distinct keys */
 typedef struct {
@@ -282,7 +287,7 @@ static int same_strain_dict(const tables *t, int file_idx)
 typedef const char *(*key_fn)(void *user, uint64_t row, char tmp[32]);
 
 /* scrub_max_kmers (:30-58): the smallest threshold t with 1 - #{v > t}/total >= min_frac, every step
- * reported on stderr exactly as the script words it */
+ * reported on stderr exactly as the script words it (err = NULL: the walk alone, for the scrub sweep's further fractions) */
 static int walk_threshold(sk_filter *f, int which, double min_frac, double total, FILE *err, int64_t *thr_out)
 {
     enum { W = 65536 };
@@ -296,7 +301,7 @@ static int walk_threshold(sk_filter *f, int which, double min_frac, double total
     for (;;) {
         const double kept = 1 - ((double)hits / total);
         skp_float_str(kept, r);
-        fprintf(err, "kept %s with threshold %lld\n", r, (long long)thr);
+        if (err) fprintf(err, "kept %s with threshold %lld\n", r, (long long)thr);
         if (!(kept < min_frac)) break;
         thr++;
         if (thr >= lo + W) {
@@ -306,18 +311,53 @@ static int walk_threshold(sk_filter *f, int which, double min_frac, double total
         hits -= hist[thr - lo];
     }
     skp_float_str(total, r);
-    fprintf(err, "threshold was %lld left with %llu out of %s that will be scrubbed\n", (long long)thr, (unsigned long long)hits, r);
+    if (err) fprintf(err, "threshold was %lld left with %llu out of %s that will be scrubbed\n", (long long)thr, (unsigned long long)hits, r);
     free(hist);
     *thr_out = thr;
     return SK_OK;
 }
 
+/* the scrub sweep's class file (include/strainer_kmer.h has its lines): the rows of class >= 1 in the informative list's order */
+static int write_classes(const char *path, const skw_list *sw, const uint64_t *kept, uint64_t n_strain, const uint8_t *cls,
+                         key_fn key_of, void *user, FILE *err)
+{
+    const size_t pl = strlen(path);
+    const int gz = pl >= 3 && !strcmp(path + pl - 3, ".gz");
+    gzFile g = gz ? gzopen(path, "wb") : NULL;
+    FILE *fp = gz ? NULL : fopen(path, "w");
+    char tmp[32], line[SKW_TEXT_MAX + 64];
+    uint64_t r;
+    uint32_t q;
+    int bad = 0;
+    if (!g && !fp) { fprintf(err, "kmer_scrub_filter: could not write %s\n", path); return 1; }
+#define PUT(text) do { const char *t_ = (text); if (*t_ && (gz ? gzputs(g, t_) < 0 : fputs(t_, fp) < 0)) bad = 1; } while (0)
+    PUT("#min_fractions\t");
+    for (q = 0; q < sw->n; q++) { PUT(q ? "," : ""); PUT(sw->text[q]); }
+    PUT("\n#post_scrub_kmers\t");
+    for (q = 0; q < sw->n; q++) { snprintf(line, sizeof line, "%s%llu", q ? "," : "", (unsigned long long)kept[q]); PUT(line); }
+    PUT("\n");
+    for (r = 0; r < n_strain && !bad; r++)
+        if (cls[r]) {
+            PUT(key_of(user, r, tmp));
+            snprintf(line, sizeof line, "\t%u\n", (unsigned)cls[r]);
+            PUT(line);
+        }
+#undef PUT
+    if (gz ? gzclose(g) != Z_OK : fclose(fp) != 0) bad = 1;
+    if (bad) fprintf(err, "kmer_scrub_filter: could not write %s\n", path);
+    return bad;
+}
+
 /* Everything after the tables are read (:204-231).  `n` rows are on the device, the first `n_strain` of
- * them are the strain dictionary in order; `n_drug_keys` = len(drug_genome_hash). */
+ * them are the strain dictionary in order; `n_drug_keys` = len(drug_genome_hash).  sw != NULL: the scrub sweep -- the run is the run
+ * at sw->f[0] (min_fraction is that), every row's class comes back from the device instead of the marks, and the class file is
+ * written last. */
 static int decide_and_print(sk_ctx *ctx, sk_filter *f, uint64_t n, uint64_t n_strain, int64_t all_kmers, int drug_filter,
                             uint64_t n_drug_keys, uint64_t n_strain_gone, double min_fraction, int independent,
-                            key_fn key_of, void *user, FILE *out, FILE *err)
+                            key_fn key_of, void *user, FILE *out, FILE *err, const skw_list *sw, const char *classes_path)
 {
+    uint64_t kept[SK_SCRUB_SWEEP_MAX];
+    uint32_t q;
     int64_t pan_sum, meta_sum, drug_scrubbed = 0;
     uint64_t n_pan, n_meta, n_alive = n_strain, left = 0, r;
     uint8_t *gone_or_scrubbed = NULL;
@@ -341,18 +381,47 @@ static int decide_and_print(sk_ctx *ctx, sk_filter *f, uint64_t n, uint64_t n_st
             return 1;
         }
     }
-    if (n && !(gone_or_scrubbed = malloc(n))) { fprintf(err, "kmer_scrub_filter: out of memory\n"); return 1; }
+    if (sw && (!sk_filter_classes_joint || !sk_filter_classes_above)) { fprintf(err, "kmer_scrub_filter: this build has no device classes\n"); return 1; }
+    if (!(gone_or_scrubbed = malloc(n ? n : 1))) { fprintf(err, "kmer_scrub_filter: out of memory\n"); return 1; }
     if (independent) {                                /* :72-84 */
         int64_t tp, tm;
         if (all_kmers == 0) { fflush(out); fprintf(err, "ZeroDivisionError: float division by zero\n"); free(gone_or_scrubbed); return 1; }
         if ((rc = walk_threshold(f, 0, min_fraction, (double)all_kmers, err, &tp)) != SK_OK) goto dev_fail;
         if ((rc = walk_threshold(f, 1, min_fraction, (double)all_kmers, err, &tm)) != SK_OK) goto dev_fail;
-        if ((rc = sk_filter_above(f, tp, tm, gone_or_scrubbed)) != SK_OK) goto dev_fail;
+        if (sw) {                                     /* the further fractions' walks say nothing; their thresholds do not increase */
+            int64_t ap[SK_SCRUB_SWEEP_MAX], am[SK_SCRUB_SWEEP_MAX];
+            ap[0] = tp; am[0] = tm;
+            for (q = 1; q < sw->n; q++) {
+                if ((rc = walk_threshold(f, 0, sw->f[q], (double)all_kmers, NULL, &ap[q])) != SK_OK) goto dev_fail;
+                if ((rc = walk_threshold(f, 1, sw->f[q], (double)all_kmers, NULL, &am[q])) != SK_OK) goto dev_fail;
+            }
+            if ((rc = sk_filter_classes_above(f, ap, am, sw->n, gone_or_scrubbed, kept)) != SK_OK) goto dev_fail;
+        } else if ((rc = sk_filter_above(f, tp, tm, gone_or_scrubbed)) != SK_OK) goto dev_fail;
     } else {                                          /* :87-137: rows go, most frequent first, while more than min_fraction would remain */
         double num_scrubbed = (double)drug_scrubbed;
         uint64_t n_scrub = 0;
         while (n_scrub < n_alive && (1 - ((num_scrubbed + 1) / (double)all_kmers)) > min_fraction) { num_scrubbed += 1.0; n_scrub++; }
-        if ((rc = sk_filter_joint(f, pan_sum, meta_sum, n_scrub, gone_or_scrubbed)) != SK_OK) goto dev_fail;
+        if (sw) {                                     /* the same loop per fraction: a smaller one goes on for at least as long */
+            uint64_t ns[SK_SCRUB_SWEEP_MAX];
+            ns[0] = n_scrub;
+            for (q = 1; q < sw->n; q++) {
+                double num = (double)drug_scrubbed;
+                uint64_t k = 0;
+                while (k < n_alive && (1 - ((num + 1) / (double)all_kmers)) > sw->f[q]) { num += 1.0; k++; }
+                ns[q] = k;
+            }
+            if ((rc = sk_filter_classes_joint(f, pan_sum, meta_sum, ns, sw->n, gone_or_scrubbed, kept)) != SK_OK) goto dev_fail;
+        } else if ((rc = sk_filter_joint(f, pan_sum, meta_sum, n_scrub, gone_or_scrubbed)) != SK_OK) goto dev_fail;
+    }
+    if (sw) {                                         /* (what came back are classes: a row is scrubbed at f[0] iff its class is 0) */
+        if (!n) memset(kept, 0, sizeof kept);
+        for (r = 0; r < n_strain; r++) left += gone_or_scrubbed[r] != 0;
+        fprintf(out, "#post scrub kmers %llu out of %lld\n", (unsigned long long)left, (long long)all_kmers);
+        for (r = 0; r < n_strain; r++)
+            if (gone_or_scrubbed[r]) { fputs(key_of(user, r, tmp), out); fputc('\n', out); }
+        rc = write_classes(classes_path, sw, kept, n_strain, gone_or_scrubbed, key_of, user, err);
+        free(gone_or_scrubbed);
+        return rc;
     }
     for (r = 0; r < n_strain; r++) left += !gone_or_scrubbed[r];
     fprintf(out, "#post scrub kmers %llu out of %lld\n", (unsigned long long)left, (long long)all_kmers);
@@ -391,7 +460,8 @@ static int opt_value(int argc, char **argv, int *i, const char *shortn, const ch
 
 int skh_scrub_filter_main(int argc, char **argv, FILE *out, FILE *err)
 {
-    const char *sfile = NULL, *lfile = NULL, *mtext = NULL, *env;
+    const char *sfile = NULL, *lfile = NULL, *mtext = NULL, *env, *ltext = NULL, *cfile = NULL;
+    skw_list sw;
     double min_fraction = 0.04;
     int independent = 0, i, bad = 0, status = 1, rc, device = 0;
     char **files = NULL;
@@ -406,14 +476,28 @@ int skh_scrub_filter_main(int argc, char **argv, FILE *out, FILE *err)
     for (i = 1; i < argc; i++) {                     /* argparse surface of the script (:14-28) */
         if (!strcmp(argv[i], "-i") || !strcmp(argv[i], "--independent")) { independent = 1; continue; }
         if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
-            fprintf(out, "usage: kmer_scrub_filter [-h] [--scrub_count_file FILE | --scrub_count_list LIST] [--min_fraction M] [--independent]\n");
+            fprintf(out, "usage: kmer_scrub_filter [-h] [--scrub_count_file FILE | --scrub_count_list LIST] [--min_fraction M] [--independent]\n"
+                         "                         [--min_fraction_list f0,f1,... --classes_out FILE]\n");
             return 0;
         }
         if (opt_value(argc, argv, &i, "-s", "--scrub_count_file", &sfile, err, &bad)) { if (bad) return 2; continue; }
         if (opt_value(argc, argv, &i, "-l", "--scrub_count_list", &lfile, err, &bad)) { if (bad) return 2; continue; }
+        /* "--min_fraction_list f0,f1,... --classes_out FILE" (extension): the scrub sweep, see include/strainer_kmer.h */
+        if (!strcmp(argv[i], "--min_fraction_list") && i + 1 < argc) { ltext = argv[++i]; continue; }
+        if (!strncmp(argv[i], "--min_fraction_list=", 20)) { ltext = argv[i] + 20; continue; }
+        if (!strcmp(argv[i], "--classes_out") && i + 1 < argc) { cfile = argv[++i]; continue; }
+        if (!strncmp(argv[i], "--classes_out=", 14)) { cfile = argv[i] + 14; continue; }
         if (opt_value(argc, argv, &i, "-m", "--min_fraction", &mtext, err, &bad)) { if (bad) return 2; continue; }
         fprintf(err, "kmer_scrub_filter: error: unrecognized arguments: %s\n", argv[i]);
         return 2;
+    }
+    if ((ltext != NULL) != (cfile != NULL)) { fprintf(err, "kmer_scrub_filter: error: --min_fraction_list and --classes_out go together\n"); return 2; }
+    if (ltext && mtext) { fprintf(err, "kmer_scrub_filter: error: --min_fraction_list replaces --min_fraction/-m: give one of them\n"); return 2; }
+    if (ltext) {
+        char why[160];
+        if (skw_parse_list(ltext, &sw, why, sizeof why)) { fprintf(err, "kmer_scrub_filter: error: --min_fraction_list %s: %s\n", ltext, why); return 2; }
+        if (!*cfile) { fprintf(err, "kmer_scrub_filter: error: --classes_out needs a file name\n"); return 2; }
+        min_fraction = sw.f[0];
     }
     if (mtext) {
         char *e;
@@ -496,7 +580,7 @@ int skh_scrub_filter_main(int argc, char **argv, FILE *out, FILE *err)
         }
         fk.d = d; fk.rows = rows;
         status = decide_and_print(ctx, flt, n, t.norder, t.all_kmers, t.drug_filter, n_drug, n_strain_gone, min_fraction, independent,
-                                  file_key_of, &fk, out, err);
+                                  file_key_of, &fk, out, err, ltext ? &sw : NULL, cfile);
     }
 done:
     fflush(out);
@@ -516,8 +600,8 @@ static const char *keyset_key_of(void *user, uint64_t row, char tmp[32])
     return tmp;
 }
 
-int skh_scrub_filter_resident(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, double min_fraction,
-                              int independent, FILE *out, FILE *err)
+static int resident_impl(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, double min_fraction, int independent, FILE *out, FILE *err,
+                         const skw_list *sw, const char *classes_path)
 {
     sk_filter *flt = NULL;
     uint64_t n_gone = 0;
@@ -532,8 +616,25 @@ int skh_scrub_filter_resident(sk_ctx *ctx, const skh_keyset *ks, int with_drug_c
     /* a printed table has one line per row and no repeated key: all_kmers = len(strain_hash) = rows;
      * len(drug_genome_hash) = rows with a positive drug count */
     status = decide_and_print(ctx, flt, ks->nrows, ks->nrows, (int64_t)ks->nrows, with_drug_column, n_gone, n_gone, min_fraction,
-                              independent, keyset_key_of, (void *)ks, out, err);
+                              independent, keyset_key_of, (void *)ks, out, err, sw, classes_path);
     fflush(out);
     sk_filter_destroy(flt);
     return status;
+}
+
+int skh_scrub_filter_resident(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, double min_fraction,
+                              int independent, FILE *out, FILE *err)
+{
+    return resident_impl(ctx, ks, with_drug_column, min_fraction, independent, out, err, NULL, NULL);
+}
+
+/* ... at a list of fractions (the scrub sweep): the run at the list's first, and the class file to classes_path */
+int skh_scrub_filter_resident_sweep(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, const char *fraction_list,
+                                    int independent, const char *classes_path, FILE *out, FILE *err)
+{
+    skw_list sw;
+    char why[160];
+    if (!fraction_list || !classes_path || !*classes_path) { fprintf(err, "kmer_scrub_filter: the scrub sweep needs a list of fractions and a class file's path\n"); return 1; }
+    if (skw_parse_list(fraction_list, &sw, why, sizeof why)) { fprintf(err, "kmer_scrub_filter: fraction list %s: %s\n", fraction_list, why); return 1; }
+    return resident_impl(ctx, ks, with_drug_column, sw.f[0], independent, out, err, &sw, classes_path);
 }

@@ -36,7 +36,9 @@
 #include "sk_cpus.h"
 #include "sk_gzout.h"
 #include "sk_internal.h"
+#include "sk_sweep.h"
 #pragma weak skh_resident_genomes_
+#pragma weak skh_scrub_filter_resident_sweep
 
 typedef struct {
     char      *genome, *outfile;   /* outfile: the count table, or with --scrub the informative list                        */
@@ -57,6 +59,7 @@ typedef struct {
     uint32_t   n;
     int        device, with_drug, ncols;
     double     scrub_fraction;     /* >= 0: step 2 instead of the table */
+    const char *scrub_list;        /* --scrub f0,f1,...: the scrub sweep -- each strain's class file goes to <informative outfile>.classes */
     int        independent;
     uint32_t   next;               /* pool: the next strain to take */
     pthread_mutex_t mu;
@@ -139,8 +142,12 @@ static void *sm_print_worker(void *arg)
         setvbuf(f, NULL, _IOFBF, 1 << 20);
         if (j->scrub_fraction >= 0.0) {              /* step 2: the informative list, as `-r <genome> ... --scrub f` prints it */
             FILE *me = open_memstream(&s->err_buf, &s->err_len);
-            s->print_rc = skh_scrub_filter_resident(s->ctx, &s->ks, j->with_drug, j->scrub_fraction, j->independent, f, me ? me : stderr)
+            char *cp = j->scrub_list ? (char *)malloc(strlen(s->outfile) + 9) : NULL;
+            if (cp) { strcpy(cp, s->outfile); strcat(cp, ".classes"); }
+            s->print_rc = (j->scrub_list ? (!cp || skh_scrub_filter_resident_sweep(s->ctx, &s->ks, j->with_drug, j->scrub_list, j->independent, cp, f, me ? me : stderr))
+                                         : skh_scrub_filter_resident(s->ctx, &s->ks, j->with_drug, j->scrub_fraction, j->independent, f, me ? me : stderr))
                               ? SM_FILTER_FAILED : SK_OK;
+            free(cp);
             if (me) fclose(me);
         } else s->print_rc = skh_print_counts(s->ctx, &s->ks, f, j->with_drug);
         if (s->zo) { if (fclose(f) != 0 && s->print_rc == SK_OK) s->print_rc = SK_E_OPEN; }
@@ -292,7 +299,7 @@ static char *sm_cov_path(const char *hits)
 
 /* the arguments behind --detect, checked before anything is opened: strain_detect's own letters, less the ones every strain's
  * line gives (-r -a -o -g) and -S; --coverage-depth without a file name (one name cannot serve many strains) */
-static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
+static int sm_check_detect(int argc, char **argv, int *want_cov, int *want_sw, FILE *err)
 {
     char **v = (char **)malloc(((size_t)argc + 1) * sizeof *v);
     int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0, want_rc = 0, want_rp = 0, want_th = 0;
@@ -364,6 +371,20 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
             want_th = 1;
             continue;
         }
+        if (c > 0 && !strncmp(argv[c], "--coverage-scrub-sweep", 22) && (argv[c][22] == 0 || argv[c][22] == '=')) {
+            if (argv[c][22] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-scrub-sweep takes no file name (each strain's table goes next to its coverage table)\n");
+                free(v);
+                return 1;
+            }
+            *want_sw = 1;
+            continue;
+        }
+        if (c > 0 && !strncmp(argv[c], "--scrub-classes", 15) && (argv[c][15] == 0 || argv[c][15] == '=')) {
+            fprintf(err, "kmer_scrub_count: with -S, each strain's class file is the one --scrub f0,f1,... writes beside its informative list (no --scrub-classes)\n");
+            free(v);
+            return 1;
+        }
         if (c > 0 && !strcmp(argv[c], "--threshold-list") && c + 1 < argc) { th_list = argv[++c]; continue; }
         if (c > 0 && !strncmp(argv[c], "--threshold-list=", 17)) { th_list = argv[c] + 17; continue; }
         if (c > 0 && !strcmp(argv[c], "--spectrum-max") && c + 1 < argc) { c++; continue; }
@@ -415,6 +436,11 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, FILE *err)
             return 1;
         }
     }
+    if (*want_sw && !*want_cov) {
+        fprintf(err, "kmer_scrub_count: --coverage-scrub-sweep goes with --coverage-depth or --coverage-only: it gives their table's numbers at several min_fraction\n");
+        free(v);
+        return 1;
+    }
     if (want_rp && !want_rc) {
         fprintf(err, "kmer_scrub_count: --recurrence-pairs goes with --coverage-recurrence\n");
         free(v);
@@ -463,7 +489,8 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
     int zpool_on = 0, status = 1, c, j, any_gz = 0, want_cov = 0;
     double t0 = sm_now(), t1 = 0, t2 = 0, t3 = 0, t4 = 0, fold_ms = 0;
     double scrub_fraction = -1.0;                    /* >= 0: step 2 on the resident counts instead of the table */
-    int independent = 0, detect_argc = 0;
+    int independent = 0, detect_argc = 0, want_sw = 0;
+    const char *scrub_list = NULL;                   /* --scrub f0,f1,...: the scrub sweep (scrub_fraction is f0) */
     char **detect_argv = NULL;                       /* --detect ...: strain_detect's arguments (step 3 for all the strains) */
 
     /* the words of the single-strain program's extensions (skh_kmer_scrub_count_main): everything behind --detect is
@@ -493,6 +520,14 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
         if (!strncmp(argv[c], "--scrub", 7) && (argv[c][7] == 0 || argv[c][7] == '=')) {
             const char *v = argv[c][7] ? argv[c] + 8 : (c + 1 < argc ? argv[++c] : "");
             char *e;
+            if (strchr(v, ',')) {                    /* a list: the scrub sweep (include/strainer_kmer.h has the rule) */
+                skw_list l;
+                char why[160];
+                if (skw_parse_list(v, &l, why, sizeof why)) { fprintf(err, "kmer_scrub_count: --scrub %s: %s\n", v, why); return 1; }
+                scrub_list = v;
+                scrub_fraction = l.f[0];
+                continue;
+            }
             scrub_fraction = strtod(v, &e);
             if (e == v || *e || scrub_fraction < 0.0 || scrub_fraction > 1.0) {
                 fprintf(err, "kmer_scrub_count: --scrub needs a fraction between 0.0 and 1.0\n");
@@ -525,7 +560,16 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
         fprintf(err, "kmer_scrub_count: --detect needs --scrub <min_fraction> and a single process\n");
         return 1;
     }
-    if (detect_argv && sm_check_detect(detect_argc, detect_argv, &want_cov, err)) return 1;
+    if (detect_argv && sm_check_detect(detect_argc, detect_argv, &want_cov, &want_sw, err)) return 1;
+    if (scrub_list && !want_sw) {
+        fprintf(err, "kmer_scrub_count: --scrub %s: a list of fractions goes with --detect ... --coverage-scrub-sweep\n", scrub_list);
+        return 1;
+    }
+    if (want_sw && !scrub_list) {
+        fprintf(err, "kmer_scrub_count: --coverage-scrub-sweep behind --detect goes with a list of fractions, --scrub f0,f1,...\n");
+        return 1;
+    }
+    if (scrub_list && !skh_scrub_filter_resident_sweep) { fprintf(err, "kmer_scrub_count: this build has no scrub sweep\n"); return 1; }
     if (world < 1 || rank < 0 || rank >= world) { fprintf(err, "kmer_scrub_count: bad rank %d of %d\n", rank, world); return 1; }
     if (detect_argv && (env = getenv("SK_DEVICES")) != NULL && *env) {
         fprintf(err, "kmer_scrub_count: -S --detect keeps every strain on the device that counted it (SK_DEVICES is not for this run)\n");
@@ -682,7 +726,7 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
          * lists (sk_filter on each strain's device table); what the filters said is replayed here in list order */
         sm_job j;
         memset(&j, 0, sizeof j);
-        j.st = st; j.n = ns; j.with_drug = C != NULL; j.scrub_fraction = scrub_fraction; j.independent = independent;
+        j.st = st; j.n = ns; j.with_drug = C != NULL; j.scrub_fraction = scrub_fraction; j.scrub_list = scrub_list; j.independent = independent;
         sm_pool_run(&j, sm_threads(), sm_print_worker);
         for (k = 0; k < ns; k++) {
             int wrc = st[k].print_rc;

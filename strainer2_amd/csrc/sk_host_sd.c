@@ -94,6 +94,9 @@ typedef struct {
     uint32_t   *co_rows; uint64_t co_n, co_cap;   /* --coverage-only: rows of host-replayed passing hits on their way to the device's counters */
     uint32_t   *co_tot;                        /* --coverage-thresholds: beside every such row its pair's h1 + h2 (the rows then pass min(--min-kmer-hits, t[0])) */
     char *th_path;                             /* --coverage-thresholds: the table's path */
+    /* --coverage-scrub-sweep: the table's path, the strain's class file, its k-mers' rows and classes (the device's sparse list), and
+     * every row's class (the host fold's) */
+    char *sw_path; skc_classes sw_c; uint32_t *sw_rows; uint8_t *row_class;
     /* --coverage-regions: the strain's region table, every row's region (rg.n = unplaced), informative rows per region, the table's path */
     skh_regions rg; uint32_t *row_region; uint64_t *reg_inf; char *rg_path;
     char *sp_path;                             /* --coverage-spectrum: the table's path */
@@ -1640,6 +1643,15 @@ static struct { int on; uint32_t max; } sd_spec;
 #pragma weak sk_covacc_finish_target_thresholds
 #pragma weak sk_covacc_thresholds_timing_
 static struct { int on; uint32_t n; int64_t t[SK_COVACC_THRESHOLDS_MAX]; double ms_finish; } sd_thr;
+/* --coverage-scrub-sweep [--scrub-classes FILE] (include/strainer_kmer.h has the rule): the run is made with the informative list of
+ * the largest fraction; every strain's class file says in how many of the listed fractions' sets each informative k-mer is.  With the
+ * accumulators on the device the classes go up once as one byte per row (sk_covacc_set_classes) and a pass of its own in front of the
+ * target's sweep bins the non-zero rows by class (sk_covacc_finish_target_classes); with --coverage-depth, and where --coverage-only
+ * counts on the host, skc_report_classes folds the host accumulator's list. */
+#pragma weak sk_covacc_set_classes
+#pragma weak sk_covacc_finish_target_classes
+#pragma weak sk_covacc_classes_timing_
+static struct { int on; double ms_cls; } sd_sw;
 /* --coverage-recurrence [--recurrence-pairs] (include/strainer_kmer.h has the rule): with the accumulators on the device every unit
  * has one set of bit planes (sk_recur) over the run's target lines; the end of a target sets the bits of its non-zero rows
  * (sk_covacc_mark_target, right before the sweep) and the end of the run takes both tables once (sk_recur_finish) and hands them to
@@ -1699,6 +1711,7 @@ static void co_close(void)
         if (sk_covacc_timing_ && sd_co.acc[k] && sk_covacc_timing_(sd_co.acc[k], 0, &f, &w) == SK_OK) { sd_co_ms_fold += f; sd_co_ms_sweep += w; }
         if (sd_rec.on && sk_covacc_mark_timing_ && sd_co.acc[k] && sk_covacc_mark_timing_(sd_co.acc[k], &f) == SK_OK) sd_rec.ms_mark += f;
         if (sd_thr.on && sk_covacc_thresholds_timing_ && sd_co.acc[k] && sk_covacc_thresholds_timing_(sd_co.acc[k], &f) == SK_OK) sd_thr.ms_finish += f;
+        if (sd_sw.on && sk_covacc_classes_timing_ && sd_co.acc[k] && sk_covacc_classes_timing_(sd_co.acc[k], &f) == SK_OK) sd_sw.ms_cls += f;
         if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
     }
     for (k = 0; k < sd_rec.nr; k++) {
@@ -1722,6 +1735,7 @@ static int co_open(sd_prog *p, uint32_t ns)
         (sd_rg.on && (!sk_covacc_set_regions || !sk_covacc_region_rows || !sk_covacc_finish_target_regions)) ||
         (sd_spec.on && (!sk_covacc_set_spectrum || !sk_covacc_finish_target_spectrum)) ||
         (sd_thr.on && (!sk_covacc_set_thresholds || !sk_covacc_add_rows_hits || !sk_covacc_finish_target_thresholds)) ||
+        (sd_sw.on && (!sk_covacc_set_classes || !sk_covacc_finish_target_classes)) ||
         (sd_rec.on && (!sk_recur_create || !sk_recur_finish || !sk_covacc_set_recurrence || !sk_covacc_mark_target))) {
         fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
         sd_co.host = 1;
@@ -1745,6 +1759,12 @@ static int co_open(sd_prog *p, uint32_t ns)
         if (getenv("SK_SD_TIMING") && sk_covacc_timing_) (void)sk_covacc_timing_(sd_co.acc[k], 1, NULL, NULL);
         if (sd_spec.on && (rc = sk_covacc_set_spectrum(sd_co.acc[k], sd_spec.max)) != SK_OK) { co_close(); return rc; }
         if (sd_thr.on && (rc = sk_covacc_set_thresholds(sd_co.acc[k], sd_thr.t, sd_thr.n)) != SK_OK) { co_close(); return rc; }
+        for (m = 0; m < n && sd_sw.on; m++) {             /* every member's class bytes, from its class file's k-mers */
+            const sd_prog *q = &p[a + m];
+            uint8_t one = 0;
+            rc = sk_covacc_set_classes(sd_co.acc[k], m, q->sw_rows, q->sw_c.n ? q->sw_c.cls : &one, q->sw_c.n, q->sw_c.F);
+            if (rc != SK_OK) { co_close(); return rc; }
+        }
         if (sd_rec.on) {                                  /* every member's informative rows ranked: its bits of the unit's planes */
             uint32_t nbits[SK_UNION_MAX];
             for (m = 0; m < n; m++) {
@@ -2535,6 +2555,16 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
                     if (skc_add_threshold_counts(p[a + m].cov, f1, tu + (size_t)m * sd_thr.n, tt + (size_t)m * sd_thr.n, sd_thr.n)) rc = SK_E_NOMEM;
                 if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
             }
+            if (sd_sw.on) {                                  /* the numbers per fraction: a pass of its own that changes nothing */
+                uint64_t cu[SK_UNION_MAX * SK_SCRUB_SWEEP_MAX], ct[SK_UNION_MAX * SK_SCRUB_SWEEP_MAX], stray = 0;
+                uint32_t F = 0;
+                for (m = 0; m < n; m++) if (p[a + m].sw_c.F > F) F = p[a + m].sw_c.F;
+                rc = sk_covacc_finish_target_classes(sd_co.acc[k], cu, ct, &stray);
+                if (rc == SK_OK && stray) rc = SK_E_STATE;       /* (only informative rows are ever logged, and each of them has a class) */
+                for (m = 0; m < n && rc == SK_OK; m++)
+                    if (skc_add_class_counts(p[a + m].cov, f1, cu + (size_t)m * F, ct + (size_t)m * F, p[a + m].sw_c.F)) rc = SK_E_NOMEM;
+                if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
+            }
             rc = sd_spec.on ? sk_covacc_finish_target_spectrum(sd_co.acc[k], uq, tot, sp, deep, ru, rt) :
                  sd_rg.on ? sk_covacc_finish_target_regions(sd_co.acc[k], uq, tot, ru, rt) : sk_covacc_finish_target(sd_co.acc[k], uq, tot);
             pthread_mutex_unlock(&sd_dev_mu);
@@ -2904,6 +2934,11 @@ static int sd_coverage_write(sd_prog *p)
         rc = skc_report_thresholds(p->cov, p->o_path, f, p->err);
         fclose(f);
     }
+    if (!rc && sd_sw.on) {
+        if (!(f = fopen(p->sw_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->sw_path); return 1; }
+        rc = skc_report_classes(p->cov, p->o_path, p->row_class, (uint32_t)p->ks.nrows, f, p->err);
+        fclose(f);
+    }
     if (!rc && sd_rec.on) {
         FILE *fp = NULL;
         if (!(f = fopen(p->rc_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->rc_path); return 1; }
@@ -2951,6 +2986,106 @@ static int sd_thresholds_open(sd_prog *p, const char *explicit_path)
     }
     if (!p->th_path || skc_set_thresholds(p->cov, sd_thr.t, sd_thr.n)) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
     return 0;
+}
+
+/* --coverage-scrub-sweep, before a strain is opened or a file written: the class files of all strains read and held against their
+ * informative lists -- a class file names exactly the list's k-mers, in its order, each with a class.  paths: four per strain as
+ * sd_open_strains takes them (entry 1 the list, entry 3 a -g list, which is refused); explicit_classes: the one strain's class file. */
+static int sd_sweep_load(skc_classes **out, uint32_t ns, char **paths, const char *explicit_classes, FILE *err)
+{
+    skc_classes *c = (skc_classes *)calloc(ns ? ns : 1u, sizeof *c);
+    uint32_t s;
+    if (!c) { fprintf(err, "strain_detect: out of memory\n"); return 1; }
+    *out = c;
+    for (s = 0; s < ns; s++)
+        if (paths[4 * s + 3]) {
+            fprintf(err, "strain_detect: --coverage-scrub-sweep does not go with a -g list (%s): its cut is sized by the number of informative k-mers, "
+                         "so the fractions' sets would no longer be nested\n", paths[4 * s + 3]);
+            return 1;
+        }
+    for (s = 0; s < ns; s++) {
+        const char *a = paths[4 * s + 1];
+        char *cp = explicit_classes ? strdup(explicit_classes) : (char *)malloc(strlen(a) + 16), why[240], line[100];
+        gzFile g;
+        uint64_t i = 0;
+        int bad = 0;
+        if (!cp) { fprintf(err, "strain_detect: out of memory\n"); return 1; }
+        if (!explicit_classes) { strcpy(cp, a); strcat(cp, ".classes"); }
+        if (skc_classes_read(cp, &c[s], why, sizeof why)) { fprintf(err, "strain_detect: --coverage-scrub-sweep: class file %s: %s\n", cp, why); free(cp); return 1; }
+        if (!(g = gzopen(a, "r"))) { free(cp); continue; }           /* (an unreadable list: the strain's opening says so) */
+        while (!bad && gzgets(g, line, 100)) {                       /* the list as sd_flag_informative reads it */
+            char *nl;
+            if (line[0] == '#') continue;
+            if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
+            if (i >= c[s].n || strcmp(line, c[s].arena + c[s].off[i])) bad = 1;
+            i++;
+        }
+        gzclose(g);
+        if (bad || i != c[s].n) {
+            fprintf(err, "strain_detect: --coverage-scrub-sweep: class file %s does not name the k-mers of the informative list %s, each once and in its order "
+                         "(they differ at k-mer %llu)\n", cp, a, (unsigned long long)(bad ? i : (i < c[s].n ? i : c[s].n) + 1u));
+            free(cp);
+            return 1;
+        }
+        free(cp);
+    }
+    return 0;
+}
+
+static void sd_sweep_drop(skc_classes *c, uint32_t ns)
+{
+    uint32_t s;
+    for (s = 0; c && s < ns; s++) skc_classes_free(&c[s]);
+    free(c);
+}
+
+/* ... and once the strain is open: where its table goes, its class file's k-mers to rows by one tally batch (as the -a list's are),
+ * the header to the strain's host accumulator.  *c is taken over. */
+static int sd_sweep_open(sd_prog *p, skc_classes *c, const char *explicit_path)
+{
+    const uint32_t nq = (uint32_t)c->n;
+    uint8_t *stream = NULL; uint32_t *start = NULL, *tally = NULL; sk_hit *hits = NULL;
+    uint64_t nh = 0, i, named = 0;
+    int rc = SK_OK, bad = 0;
+    p->sw_c = *c;
+    memset(c, 0, sizeof *c);
+    p->sw_path = sd_table_path(p->o_path, explicit_path, ".coverage_scrub_sweep");
+    p->row_class = (uint8_t *)calloc(p->ks.nrows ? p->ks.nrows : 1, 1);
+    p->sw_rows = (uint32_t *)malloc(((size_t)nq + 1) * sizeof *p->sw_rows);
+    if (!p->sw_path || !p->row_class || !p->sw_rows || skc_set_classes(p->cov, &p->sw_c)) { fprintf(p->err, "strain_detect: out of memory\n"); return 1; }
+    for (i = 0; i < nq; i++) p->sw_rows[i] = 0xFFFFFFFFu;
+    if (nq) {
+        stream = (uint8_t *)malloc((size_t)nq * 32);
+        start = (uint32_t *)malloc((size_t)nq * 4);
+        tally = (uint32_t *)calloc((size_t)nq * 2, 4);
+        hits = (sk_hit *)malloc((size_t)nq * sizeof *hits);
+        if (!stream || !start || !tally || !hits) { fprintf(p->err, "strain_detect: out of memory\n"); bad = 1; goto out; }
+        for (i = 0; i < nq; i++) {
+            const char *t = p->sw_c.arena + p->sw_c.off[i];
+            if (strlen(t) != SK_K) { bad = 2; break; }                /* (held against the list already: a piece the list's reader also rejects) */
+            start[i] = (uint32_t)i * 32;
+            memcpy(stream + (size_t)i * 32, t, SK_K);
+            stream[(size_t)i * 32 + SK_K] = '\n';
+        }
+        if (!bad) {
+            rc = sk_tally_batch(p->ctx, stream, (uint64_t)nq * 32, start, nq, SD_TYPE, SD_INFORMATIVE, tally, hits, nq, &nh);
+            if (rc) { fprintf(p->err, "strain_detect: device error: %s (%s)\n", sk_strerror(rc), sk_last_error(p->ctx)); bad = 1; goto out; }
+        }
+        for (i = 0; !bad && i < nh && i < nq; i++) {                  /* one informative hit per k-mer, on a row of its own */
+            const uint32_t q = hits[i].pos / 32u, row = hits[i].row;
+            if (q >= nq || row >= p->ks.nrows || p->row_class[row] || p->sw_rows[q] != 0xFFFFFFFFu) { bad = 2; break; }
+            p->row_class[row] = p->sw_c.cls[q];
+            p->sw_rows[q] = row;
+            named++;
+        }
+    }
+    if (!bad && (named != nq || (uint64_t)p->genome_inf != nq)) bad = 2;
+    if (bad == 2)
+        fprintf(p->err, "strain_detect: --coverage-scrub-sweep: the class file of %s does not name the strain's %u informative k-mers, each once\n",
+                p->o_path, p->genome_inf);
+out:
+    free(stream); free(start); free(tally); free(hits);
+    return bad ? 1 : 0;
 }
 
 /* --coverage-spectrum: where the table of strain p goes */
@@ -3061,6 +3196,8 @@ static void sd_strain_close(sd_prog *p)
     skc_destroy(p->cov);
     if (skh_regions_free) skh_regions_free(&p->rg);
     free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->th_path); free(p->rc_path); free(p->rp_path);
+    free(p->sw_path); free(p->sw_rows); free(p->row_class);
+    skc_classes_free(&p->sw_c);
     memset(p, 0, sizeof *p);
 }
 
@@ -3298,7 +3435,10 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     int want_rg = 0, want_sp = 0, want_ps = 0, want_rc = 0, want_rp = 0;
     const char *rc_file = NULL, *rp_file = NULL;
     const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL, *th_file = NULL, *th_list = NULL;
-    int want_th = 0;
+    int want_th = 0, want_sw = 0;
+    const char *sw_file = NULL, *sw_classes = NULL;
+    skc_classes *swc = NULL;
+    uint32_t nswc = 0;
     long long cov_min = 1;
     double t_begin = 0;
     sd_prog *p = NULL;
@@ -3358,6 +3498,16 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         }
         if (!strcmp(argv[c], "--threshold-list") && c + 1 < argc) { th_list = argv[++c]; continue; }
         if (!strncmp(argv[c], "--threshold-list=", 17)) { th_list = argv[c] + 17; continue; }
+        /* "--coverage-scrub-sweep[=FILE] [--scrub-classes FILE]": next to either table, its numbers at every min_fraction of the strain's
+         * class file (kmer_scrub_filter --min_fraction_list; default the -a path plus ".classes") from the one pass, default FILE =
+         * outfile with ".kmer_hits.gz" replaced by ".coverage_scrub_sweep" */
+        if (!strncmp(argv[c], "--coverage-scrub-sweep", 22) && (argv[c][22] == 0 || argv[c][22] == '=')) {
+            want_sw = 1;
+            sw_file = argv[c][22] ? argv[c] + 23 : NULL;
+            continue;
+        }
+        if (!strcmp(argv[c], "--scrub-classes") && c + 1 < argc) { sw_classes = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--scrub-classes=", 16)) { sw_classes = argv[c] + 16; continue; }
         /* "--coverage-recurrence[=FILE] [--recurrence-pairs[=FILE]]": next to either table, in how many of the run's samples each
          * informative k-mer was seen, and what every two samples share; default FILEs = outfile with ".kmer_hits.gz" replaced by
          * ".coverage_recurrence" and ".coverage_recurrence_pairs" */
@@ -3387,6 +3537,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_rg.on = 0; sd_rg.genomes = NULL; sd_rg.ngenomes = 0;
     sd_spec.on = 0;
     sd_thr.on = 0;
+    sd_sw.on = 0;
     sd_rec.on = 0;
     sd_co.on = 0;
     sd_ps.path = NULL;
@@ -3462,6 +3613,14 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         sd_thr.n = 8;
         if (th_list && skc_parse_threshold_list(th_list, sd_thr.t, &sd_thr.n, why, sizeof why)) { fprintf(err, "strain_detect: --threshold-list %s: %s\n", th_list, why); return sd_drop(p, ns); }
     }
+    if (want_sw || sw_classes) {
+        const int several = (S && !a && !o && !r) || (ad && ad->o);
+        if (!want_sw) { fputs("strain_detect: --scrub-classes goes with --coverage-scrub-sweep\n", err); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-scrub-sweep goes with --coverage-depth or --coverage-only: it gives their table's numbers at several min_fraction\n", err); return sd_drop(p, ns); }
+        if ((sw_file || sw_classes) && several) { fputs("strain_detect: --coverage-scrub-sweep=FILE and --scrub-classes name one file; with several strains each table and class file is at its default path\n", err); return sd_drop(p, ns); }
+        if (sw_classes && !*sw_classes) { fputs("strain_detect: --scrub-classes needs a file name\n", err); return sd_drop(p, ns); }
+        if (g) { fprintf(err, "strain_detect: --coverage-scrub-sweep does not go with a -g list (%s): its cut is sized by the number of informative k-mers, so the fractions' sets would no longer be nested\n", g); return sd_drop(p, ns); }
+    }
     if (want_rc || want_rp) {
         uint32_t T = 1;
         if (!want_rc) { fputs("strain_detect: --recurrence-pairs goes with --coverage-recurrence\n", err); return sd_drop(p, ns); }
@@ -3532,6 +3691,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_rg.on = want_rg;
     sd_spec.on = want_sp;
     sd_thr.on = want_th; sd_thr.ms_finish = 0;
+    sd_sw.on = want_sw; sd_sw.ms_cls = 0;
     sd_rec.on = want_rc; sd_rec.pairs = want_rp; sd_rec.next = 0;
     sd_rec.ms_mark = sd_rec.ms_hist = sd_rec.ms_gram = 0;
     sd_ps.path = want_ps ? ps_file : NULL;
@@ -3597,6 +3757,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             if (!(rgs = (skh_regions *)calloc(ns, sizeof *rgs))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
             for (nrgs = 0; nrgs < ns; nrgs++) if (sd_regions_load(&rgs[nrgs], paths[4 * nrgs], err)) goto done;
         }
+        if (want_sw && ns) { nswc = ns; if (sd_sweep_load(&swc, ns, paths, NULL, err)) goto done; }
         if (sd_open_strains(p, ns, paths, 0, out, err)) goto done;
         if (ns == 0) { status = 0; goto done; }          /* nothing dealt to this rank */
     } else if (ad) {                                     /* (sd_dev: one device, the one the strains are on) */
@@ -3610,12 +3771,18 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             if (!(rgs = (skh_regions *)calloc(ns, sizeof *rgs))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
             for (nrgs = 0; nrgs < ns; nrgs++) if (sd_regions_load(&rgs[nrgs], rg_genomes[nrgs], err)) goto done;
         }
+        if (want_sw) { nswc = ns; if (sd_sweep_load(&swc, ns, paths, ad->o ? NULL : sw_classes, err)) goto done; }
         if (sd_open_strains(p, ns, paths, 1, out, err)) goto done;
     } else {
         if (want_rg) {
             if (!(rgs = (skh_regions *)calloc(1, sizeof *rgs))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
             if (sd_regions_load(&rgs[0], r, err)) goto done;
             nrgs = 1;
+        }
+        if (want_sw) {                                   /* (before the strain is opened: a refusal leaves nothing behind) */
+            char *one[4] = { NULL, (char *)a, NULL, NULL };
+            nswc = 1;
+            if (sd_sweep_load(&swc, 1, one, sw_classes, err)) goto done;
         }
         p = (sd_prog *)malloc(sizeof *p);
         ns = 1;
@@ -3632,6 +3799,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (sd_spectrum_open(&p[s], S || (ad && ad->o) ? NULL : sp_file)) goto done;
     for (s = 0; want_th && s < ns; s++)
         if (sd_thresholds_open(&p[s], S || (ad && ad->o) ? NULL : th_file)) goto done;
+    for (s = 0; want_sw && s < ns; s++)
+        if (sd_sweep_open(&p[s], &swc[s], S || (ad && ad->o) ? NULL : sw_file)) goto done;
     for (s = 0; want_rc && s < ns; s++)
         if (sd_recurrence_open(&p[s], S || (ad && ad->o) ? NULL : rc_file, S || (ad && ad->o) ? NULL : rp_file)) goto done;
     if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
@@ -3702,6 +3871,8 @@ done:
     if (getenv("SK_SD_TIMING") && cov_only && want_th)
         fprintf(err, "strain_detect timing: thresholds on the device: %u thresholds, finishing passes %.3f ms (the folds above classify as well)\n",
                 sd_thr.n, sd_thr.ms_finish);
+    if (getenv("SK_SD_TIMING") && cov_only && want_sw)
+        fprintf(err, "strain_detect timing: scrub sweep on the device: class passes %.3f ms\n", sd_sw.ms_cls);
     if (getenv("SK_SD_TIMING") && cov_only && want_rc)
         fprintf(err, "strain_detect timing: recurrence on the device: marks %.3f ms (%u targets), finish: histogram %.3f ms, pairs %.3f ms\n",
                 sd_rec.ms_mark, sd_rec.T, sd_rec.ms_hist, sd_rec.ms_gram);
@@ -3717,8 +3888,10 @@ done:
     sd_rg.on = 0;
     sd_spec.on = 0;
     sd_thr.on = 0;
+    sd_sw.on = 0;
     sd_rec.on = 0;
     sd_ps.path = NULL;
+    sd_sweep_drop(swc, nswc);
     for (s = 0; rgs && s < nrgs; s++) skh_regions_free(&rgs[s]);
     free(rgs);
     {   /* closing a strain = finishing its gz output, freeing its device context and tables: strain by strain on threads */

@@ -50,6 +50,23 @@ int skc_parse_threshold_list(const char *text, int64_t *t /* SK_COVACC_THRESHOLD
 int skc_set_thresholds(skc_acc *a, const int64_t *t, uint32_t n);
 int skc_add_threshold_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t n);
 int skc_report_thresholds(skc_acc *a, const char *hits_file_name, FILE *out, FILE *err);
+/* ... and the scrub sweep (strain_detect --coverage-scrub-sweep, coverage_depth --scrub-sweep; include/strainer_kmer.h has the rule and
+ * the class file's lines).  skc_classes_read reads a class file (gzip or plain): 0, or 1 and in `why` what is wrong -- a missing or
+ * unreadable file, a header line missing or out of place, a bad fraction list, a line that is not kmer<TAB>class with class 1..F, or
+ * set sizes that the lines do not add up to.  skc_set_classes right after skc_create hands the accumulator the fractions' texts and
+ * the sets' sizes; a metagenome's numbers per fraction are handed in (next to skc_add_counts), or folded from the hits by
+ * skc_report_classes (row_class[row] for the strain's nrows rows; a hit on a row of class 0 or above F is an error), which prints the
+ * table; call it after skc_report. */
+#define SKW_TEXT_MAX 48                          /* a fraction's text, terminator included (sk_sweep.h parses the lists) */
+typedef struct {
+    uint32_t F; char frac[SK_SCRUB_SWEEP_MAX][SKW_TEXT_MAX]; uint64_t size[SK_SCRUB_SWEEP_MAX];   /* the header lines */
+    char *arena; uint64_t *off; uint8_t *cls; uint64_t n, arena_len;                    /* the k-mer lines: text at arena + off[i], class */
+} skc_classes;
+int skc_classes_read(const char *path, skc_classes *c, char *why, size_t why_cap);
+void skc_classes_free(skc_classes *c);
+int skc_set_classes(skc_acc *a, const skc_classes *c);
+int skc_add_class_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t F);
+int skc_report_classes(skc_acc *a, const char *hits_file_name, const uint8_t *row_class, uint32_t nrows, FILE *out, FILE *err);
 /* kmer_scrub_count --detect: the genome files of the strains the next skh_strain_detect_resident[_many] call adopts (it has no -r;
  * --coverage-regions reads the records' names and lengths from them).  The call takes the list and forgets it. */
 void skh_resident_genomes_(const char *const *paths, uint32_t n);
@@ -106,6 +123,8 @@ int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *ms_sweep);
 int sk_covacc_mark_timing_(sk_covacc *a, double *ms_mark);
 /* ... and of its threshold finishing passes (sk_covacc_finish_target_thresholds) */
 int sk_covacc_thresholds_timing_(sk_covacc *a, double *ms_thr);
+/* ... and of its class passes (sk_covacc_finish_target_classes) */
+int sk_covacc_classes_timing_(sk_covacc *a, double *ms_cls);
 /* The recurrence engine's planes (sk_recur.hip), for the feeders that set bits with kernels of their own (sk_covacc.hip,
  * sk_cover.hip): plane `sample` of member m begins at d_planes + sample * words + word_base[m] and holds (nbits[m] + 63) / 64
  * words; a feeder sets no bit at or above nbits[m] and synchronises before the engine's next call. */

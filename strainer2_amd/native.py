@@ -74,6 +74,8 @@ ABI_SYMBOLS = [
     "sk_recur_create", "sk_recur_destroy", "sk_recur_mark_bits", "sk_recur_finish", "sk_covacc_set_recurrence", "sk_covacc_mark_target",
     "sk_distinct_recurrence",
     "sk_covacc_set_thresholds", "sk_covacc_add_rows_hits", "sk_covacc_finish_target_thresholds", "sk_distinct_thresholds",
+    "sk_filter_classes_joint", "sk_filter_classes_above", "skh_scrub_filter_resident_sweep",
+    "sk_covacc_set_classes", "sk_covacc_finish_target_classes", "sk_distinct_classes",
 ]
 
 
@@ -195,6 +197,10 @@ lib.sk_filter_sums.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_i
 lib.sk_filter_hist.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_void_p]
 lib.sk_filter_joint.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p]
 lib.sk_filter_above.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+SK_SCRUB_SWEEP_MAX = 16
+lib.sk_filter_classes_joint.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.sk_filter_classes_above.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.skh_scrub_filter_resident_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p, C.c_void_p]
 lib.skh_scrub_filter_main.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
 lib.skh_scrub_filter_resident.argtypes = [C.c_void_p, C.POINTER(_KeysetStruct), C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
 
@@ -747,6 +753,19 @@ class KmerContext:
                                             t.ctypes.data, len(t), uniq.ctypes.data, total.ctypes.data))
         return uniq, total
 
+    def distinct_classes(self, keys, sample, cls, nsamples, ncls):
+        """sk_distinct_classes: (unique[nsamples, ncls], total[nsamples, ncls]) -- for every sample and fraction q the hits of class
+        >= q + 1, and the distinct keys they name; classes run from 1 to ncls"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32)
+        cls = np.ascontiguousarray(cls, dtype=np.uint8)
+        assert len(keys) == len(sample) == len(cls)
+        uniq = np.zeros((max(int(nsamples), 0), max(int(ncls), 1)), dtype=np.uint64)
+        total = np.zeros_like(uniq)
+        self._ck(lib.sk_distinct_classes(self._h, keys.ctypes.data, sample.ctypes.data, cls.ctypes.data, len(keys), int(nsamples), int(ncls),
+                                         uniq.ctypes.data, total.ctypes.data))
+        return uniq, total
+
     def print_counts(self, ks: Keyset, path, with_drug_column=False):
         fp = _libc.fopen(os.fsencode(path), b"w")
         try:
@@ -832,6 +851,9 @@ lib.sk_covacc_add_rows_hits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_
 lib.sk_covacc_finish_target_thresholds.argtypes = [C.c_void_p] * 3
 lib.sk_distinct_thresholds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
                                        C.c_void_p, C.c_void_p]
+lib.sk_covacc_set_classes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+lib.sk_covacc_finish_target_classes.argtypes = [C.c_void_p] * 4
+lib.sk_distinct_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
 
 
 def regions_from_file(path, window=100000):
@@ -1176,6 +1198,27 @@ class CoverageAcc:
         self._ctx._ck(lib.sk_covacc_finish_target_thresholds(self._h, uq.ctypes.data, tot.ctypes.data))
         return uq[:, :nt], tot[:, :nt]
 
+    def set_classes(self, member, rows, cls, ncls):
+        """sk_covacc_set_classes: member's rows[i] gets the scrub class cls[i] (1..ncls), every other row class 0; ncls = 0 (and no
+        rows) turns the member's classes off"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        cls = np.ascontiguousarray(cls, dtype=np.uint8)
+        assert len(rows) == len(cls)
+        self._ctx._ck(lib.sk_covacc_set_classes(self._h, member, rows.ctypes.data if len(rows) else None,
+                                                cls.ctypes.data if len(cls) else None, len(rows), int(ncls)))
+        self._ncls = getattr(self, "_ncls", None) or [0] * len(self.nrows)
+        self._ncls[member] = int(ncls)
+
+    def finish_target_classes(self):
+        """sk_covacc_finish_target_classes: (unique[nmembers, F], total[nmembers, F], stray), F = the largest ncls set; it changes no
+        counter.  Call it before the sweep that ends the target."""
+        F = max(getattr(self, "_ncls", None) or [0])
+        uq = np.zeros((len(self.nrows), max(F, 1)), dtype=np.uint64)
+        tot = np.zeros_like(uq)
+        stray = C.c_uint64()
+        self._ctx._ck(lib.sk_covacc_finish_target_classes(self._h, uq.ctypes.data, tot.ctypes.data, C.byref(stray)))
+        return uq[:, :F], tot[:, :F], int(stray.value)
+
     def rows(self, member):
         """member's per-row counters as they stand"""
         out = np.zeros(max(int(self.nrows[member]), 1), dtype=np.uint32)
@@ -1366,6 +1409,24 @@ class ScrubFilter:
         out = np.zeros(self.n, dtype=np.uint8)
         self._ctx._ck(lib.sk_filter_above(self._h, pan_thr, meta_thr, out.ctypes.data))
         return out
+
+    def classes_joint(self, pan_sum, meta_sum, n_scrub):
+        """sk_filter_classes_joint: (class[n] bytes, kept[F]) for the non-decreasing list n_scrub of joint scrubs"""
+        ns = np.ascontiguousarray(n_scrub, dtype=np.uint64).reshape(-1)
+        out = np.zeros(max(self.n, 1), dtype=np.uint8)
+        kept = np.zeros(max(len(ns), 1), dtype=np.uint64)
+        self._ctx._ck(lib.sk_filter_classes_joint(self._h, pan_sum, meta_sum, ns.ctypes.data, len(ns), out.ctypes.data, kept.ctypes.data))
+        return out[: self.n], kept[: len(ns)]
+
+    def classes_above(self, pan_thr, meta_thr):
+        """sk_filter_classes_above: (class[n] bytes, kept[F]) for the non-increasing lists of thresholds"""
+        tp = np.ascontiguousarray(pan_thr, dtype=np.int64).reshape(-1)
+        tm = np.ascontiguousarray(meta_thr, dtype=np.int64).reshape(-1)
+        assert len(tp) == len(tm)
+        out = np.zeros(max(self.n, 1), dtype=np.uint8)
+        kept = np.zeros(max(len(tp), 1), dtype=np.uint64)
+        self._ctx._ck(lib.sk_filter_classes_above(self._h, tp.ctypes.data, tm.ctypes.data, len(tp), out.ctypes.data, kept.ctypes.data))
+        return out[: self.n], kept[: len(tp)]
 
     def close(self):
         if self._h:

@@ -28,6 +28,12 @@ apart.
     python tools/coverage_only_bench.py --spectrum 255 --rounds 5 --parent-exe PATH [--out profiles/coverage_spectrum_bench.txt]
     python tools/coverage_only_bench.py --recurrence --rounds 5 --parent-exe PATH [--out profiles/coverage_recurrence_bench.txt]
     python tools/coverage_only_bench.py --thresholds [--threshold-list 0,1,2] --rounds 3 --parent-exe PATH [--out profiles/coverage_thresholds_bench.txt]
+    python tools/coverage_only_bench.py --scrub-sweep --rounds 3 --parent-exe PATH [--out profiles/coverage_scrub_sweep_bench.txt]
+
+--scrub-sweep measures --coverage-scrub-sweep like --thresholds (class files of 8 fractions are made up for the strains' lists: the
+class pass does not care where the classes come from), then step 2 alone at 8 fractions against 1 (kmer_scrub_filter over one
+strain's count table) and one fused kmer_scrub_count -S --scrub <8 fractions> --detect run against 8 fused runs of one fraction
+each, whose coverage tables must carry the sweep table's numbers.
 """
 import argparse
 import hashlib
@@ -54,6 +60,8 @@ PASS = re.compile(rb"strain_detect timing: setup ([0-9.]+) s,.*?total before clo
 ACC = re.compile(rb"coverage accumulators on the device: folds ([0-9.]+) ms, target sweeps ([0-9.]+) ms")
 REC = re.compile(rb"recurrence on the device: marks ([0-9.]+) ms \((\d+) targets\), finish: histogram ([0-9.]+) ms, pairs ([0-9.]+) ms")
 THR = re.compile(rb"thresholds on the device: (\d+) thresholds, finishing passes ([0-9.]+) ms")
+SWP = re.compile(rb"scrub sweep on the device: class passes ([0-9.]+) ms")
+SWEEP_LIST = "0.5,0.4,0.3,0.2,0.1,0.05,0.02,0.01"
 BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
 
 
@@ -72,7 +80,8 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     """one run of the program under its own time limit -> measurements; raises StepFailed (nothing more is started then)"""
     for s in range(ns):
         for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum",
-                  f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs", f"out{s}.gz.coverage_thresholds"):
+                  f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs", f"out{s}.gz.coverage_thresholds",
+                  f"out{s}.gz.coverage_scrub_sweep"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -93,7 +102,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             h.update(f.read())
     hr = hashlib.md5()
     for s in range(ns):
-        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds"):    # (the table beside the coverage table, whichever the run wrote)
+        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds", "coverage_scrub_sweep"):    # (the table beside the coverage table, whichever the run wrote)
             if os.path.exists(os.path.join(cwd, f"out{s}.gz.{ext}")):
                 with open(os.path.join(cwd, f"out{s}.gz.{ext}"), "rb") as f:
                     hr.update(f.read())
@@ -102,7 +111,8 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     a = ACC.search(p.stderr)
     rc = REC.search(p.stderr)
     th = THR.search(p.stderr)
-    return dict(thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
+    sw = SWP.search(p.stderr)
+    return dict(cls=float(sw.group(1)) if sw else float("nan"), thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
                 fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
                 passed=float(m.group(2)) - float(m.group(1)) if m else float("nan"),
                 d2h=int(b.group(1)) if b else -1, dev=int(b.group(2)) if b else -1, replayed=int(b.group(3)) if b else -1)
@@ -140,7 +150,7 @@ def regions_case(say, args, env, tmp, ns, kind, argv):
         say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
-def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False):
+def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False, sweep=False):
     """--coverage-only without and with --coverage-spectrum (recurrence: --coverage-recurrence --recurrence-pairs; thresholds:
     --coverage-thresholds [--threshold-list ..]), alternating; the parent build's plain --coverage-only behind them -- with
     thresholds: in turn with them, round by round -- and the new build's medians set against the parent's"""
@@ -152,6 +162,10 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
     if thresholds:
         with_sp = ["--coverage-only", "--coverage-thresholds"] + (["--threshold-list", args.threshold_list] if args.threshold_list else [])
         word, label = "thresholds", "... " + " ".join(with_sp[1:])
+    if sweep:                                                # (measured like the thresholds: the parent's runs in turn, folds compared too)
+        with_sp = ["--coverage-only", "--coverage-scrub-sweep"]
+        word, label = "scrub sweep", "... --coverage-scrub-sweep"
+        thresholds = True
     res = {"plain": [], "spectrum": [], "parent": []}
     md5 = md5s = None
     for rnd in range(args.rounds):
@@ -179,7 +193,9 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
         if rs:
             say(f"    {names[tag]}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; accumulators on the device: folds "
                 f"{row(rs, 'fold', '.2f')} ms, target sweeps {row(rs, 'sweep', '.3f')} ms; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
-            if thresholds and tag == "spectrum":
+            if sweep and tag == "spectrum":
+                say(f"        scrub sweep on the device: class passes of all targets {row(rs, 'cls', '.3f')} ms")
+            elif thresholds and tag == "spectrum":
                 say(f"        thresholds on the device: finishing passes of all targets {row(rs, 'thr', '.3f')} ms (the folds above classify as well)")
             if recurrence and tag == "spectrum":
                 say(f"        recurrence on the device: marks of all targets {row(rs, 'mark', '.3f')} ms; the one finish: histogram "
@@ -198,6 +214,62 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
                     f"ratio {med[tag][k] / med['parent'][k] if med['parent'][k] else float('nan'):.3f}")
 
 
+def timed(argv, env, limit, cwd, stdout=None):
+    """one run of a program under its own time limit -> wall seconds; raises StepFailed"""
+    t0 = time.perf_counter()
+    p = subprocess.run(["timeout", "-k", "10", str(limit)] + argv, env=env, cwd=cwd, stdout=stdout or subprocess.DEVNULL, stderr=subprocess.PIPE)
+    if p.returncode != 0:
+        raise StepFailed(f"{' '.join(argv[:3])} ...: exit status {p.returncode}: {p.stderr.decode(errors='replace')[-800:]}")
+    return time.perf_counter() - t0
+
+
+def sweep_steps(say, args, env, tmp, target_list, nfiles):
+    """step 2 alone at 8 fractions against 1, and one fused run at 8 fractions against 8 fused runs of one"""
+    count = os.path.join(REPO, "strainer2_amd", "bin", "kmer_scrub_count")
+    filt = os.path.join(REPO, "strainer2_amd", "bin", "kmer_scrub_filter")
+    fr = SWEEP_LIST.split(",")
+    if not os.path.exists(os.path.join(tmp, "s15.fa")):
+        raise StepFailed("the fused measurement scrubs strains 0..7 against strains 8..15: --strains needs a count of 16 or more")
+    with open(os.path.join(tmp, "A.txt"), "w") as f:
+        f.write("".join(f"s{s}.fa\n" for s in range(8, 16)))
+    with open(os.path.join(tmp, "Bs.txt"), "w") as f:
+        f.write("".join(f"r{i}.fq\n" for i in range(min(nfiles, 4))))
+    with open(os.path.join(tmp, "table.txt"), "wb") as f:
+        timed([count, "-r", "s0.fa", "-A", "A.txt", "-B", "Bs.txt"], env, args.limit, tmp, stdout=f)
+    one = [timed([filt, "-s", "table.txt", "-m", fr[0]], env, args.limit, tmp) for _ in range(args.rounds)]
+    many = [timed([filt, "-s", "table.txt", "--min_fraction_list", SWEEP_LIST, "--classes_out", "table.classes"], env, args.limit, tmp) for _ in range(args.rounds)]
+    say(f"step 2 alone, kmer_scrub_filter over one strain's count table ({os.path.getsize(os.path.join(tmp, 'table.txt')) >> 20} MiB of text): wall "
+        f"{' '.join(format(x, '.2f') for x in one)} s at F = 1 (-m {fr[0]}), {' '.join(format(x, '.2f') for x in many)} s at F = 8 "
+        f"({SWEEP_LIST}); medians {statistics.median(one):.2f} and {statistics.median(many):.2f} s")
+    with open(os.path.join(tmp, "Sf.txt"), "w") as f:
+        f.write("".join(f"s{s}.fa\tf{s}.inf\tfo{s}.gz\n" for s in range(8)))
+    front = [count, "-S", "Sf.txt", "-A", "A.txt", "-B", "Bs.txt"]
+    back = ["--detect", "-B", target_list, "--coverage-only"]
+    w8 = timed(front + ["--scrub", SWEEP_LIST] + back + ["--coverage-scrub-sweep"], env, args.limit, tmp)
+    sweep = {}
+    for s in range(8):
+        with open(os.path.join(tmp, f"fo{s}.gz.coverage_scrub_sweep"), "rb") as f:
+            for ln in f.read().split(b"\n")[1:]:
+                if ln:
+                    c = ln.split(b"\t")
+                    sweep[(s, c[1], c[2].decode())] = (int(c[3]), int(c[4]), int(c[5]))
+    w1, wrong, rows = [], 0, 0
+    for q in fr:
+        w1.append(timed(front + ["--scrub", q] + back, env, args.limit, tmp))
+        for s in range(8):
+            with open(os.path.join(tmp, f"fo{s}.gz.coverage_depth"), "rb") as f:
+                for ln in f.read().split(b"\n")[1:]:
+                    if ln:
+                        c = ln.split(b"\t")
+                        rows += 1
+                        wrong += sweep.get((s, c[5], q)) != (int(c[4]), max(int(c[8]), 0), int(c[9]))
+    if wrong or rows != len(sweep):
+        raise StepFailed(f"fused: {wrong} of {rows} coverage-table rows of the 8 single-fraction runs differ from the sweep table ({len(sweep)} rows)")
+    say(f"fused, 8 strains, kmer_scrub_count -S --scrub .. --detect -B {target_list} --coverage-only: one run at 8 fractions with "
+        f"--coverage-scrub-sweep, wall {w8:.2f} s; 8 runs at one fraction each, wall {' '.join(format(x, '.2f') for x in w1)} s, together "
+        f"{sum(w1):.2f} s: {sum(w1) / w8:.2f} x; all {rows} coverage-table rows of the 8 runs carry the sweep table's numbers")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbases", type=float, default=1.5, help="bases per list")
@@ -210,6 +282,7 @@ def main():
     ap.add_argument("--recurrence", action="store_true", help="measure --coverage-recurrence --recurrence-pairs")
     ap.add_argument("--thresholds", action="store_true", help="measure --coverage-thresholds, the parent build's runs in turn with this build's")
     ap.add_argument("--threshold-list", default=None, help="... with this --threshold-list (default: the program's)")
+    ap.add_argument("--scrub-sweep", action="store_true", help="measure --coverage-scrub-sweep, step 2 at 8 fractions and the fused form")
     ap.add_argument("--stderr-dir", default=None, help="keep every run's stderr (the SK_SD_TIMING lines) in this directory")
     ap.add_argument("--out", default=None)
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -236,6 +309,13 @@ def main():
         for s in range(max(counts)):
             cfg5.write_strain(tmp, s)
             genome.append(cfg5.strain(s))
+            if args.scrub_sweep:                                 # a class file of 8 fractions for the strain's list: line i has class i % 8 + 1
+                with open(os.path.join(tmp, f"s{s}.inf"), "rb") as f:
+                    kms = [ln for ln in f.read().split(b"\n") if ln and not ln.startswith(b"#")]
+                with open(os.path.join(tmp, f"s{s}.inf.classes"), "wb") as f:
+                    f.write(b"#min_fractions\t" + SWEEP_LIST.encode() + b"\n#post_scrub_kmers\t" +
+                            ",".join(str(sum(1 for i in range(len(kms)) if i % 8 + 1 >= q + 1)) for q in range(8)).encode() + b"\n" +
+                            b"".join(b"%s\t%d\n" % (k, i % 8 + 1) for i, k in enumerate(kms)))
         for ns in counts:
             with open(os.path.join(tmp, f"S{ns}.txt"), "w") as f:
                 f.write("".join(f"s{s}.fa\ts{s}.inf\tout{s}.gz\n" for s in range(ns)))
@@ -267,8 +347,8 @@ def main():
             for ns in counts:
                 for kind, lst in lists.items():
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
-                    if args.spectrum is not None or args.recurrence or args.thresholds:
-                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds)
+                    if args.spectrum is not None or args.recurrence or args.thresholds or args.scrub_sweep:
+                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds, args.scrub_sweep)
                         continue
                     if args.regions is not None:
                         regions_case(say, args, env, tmp, ns, kind, argv)
@@ -296,6 +376,8 @@ def main():
                             raise StepFailed(f"{ns} strains, {kind}: the parent build writes other tables")
                         say(f"    parent build, --coverage-depth x3: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; "
                             f"CPU-seconds {row(rs, 'cpu', '.1f')} (same tables)")
+            if args.scrub_sweep:
+                sweep_steps(say, args, env, tmp, lists["plain FASTQ"], nfiles)
         except StepFailed as x:
             ok = False
             say(f"STOPPED: {x}")
