@@ -454,10 +454,83 @@ def diff_strain(nrows):
 
 
 # ---- a world in every form ----------------------------------------------------------------------------------------------------------------
-def run_every_form(w, main=0, tally=True, union=True):
+def device_buildable(w):
+    """every strain of the world holds only what build_from_text takes: A/C/G/T/N in either case (no U, no IUPAC letter)"""
+    return all(set(r) <= set(b"ACGTNacgtn") for recs in w.strains for r in recs)
+
+
+def run_built_on_the_device(w, main=0, tally=True, union=True):
+    """the form "built on the device": every table comes from build_from_text(records) -- the builder's own text, rank map, orientation
+    bits and filters, rows in strain order and no row permutation on the device (d_inv == NULL in the union's resolve step and in
+    sk_first_pos_from_rank).  Counts and logged rows are taken to the oracle's rows by key.  COUNT, the host-packed form, resident
+    twice (both lanes), one TALLY launch; union: the TALLY launch of a union whose members were ALL built on the device."""
+    import _build_model as bm
+    import strainer2_amd as sk
+    assert device_buildable(w)
+    stream, starts = w.stream, w.starts
+    packed, odd = sk.pack_stream(stream)
+    assert not odd
+    members = range(len(w.strains)) if union else [main]
+    ctxs, orow = {}, {}
+    try:
+        for m in members:
+            c = sk.KmerContext(0)
+            ctxs[m] = c
+            n = c.build_from_text(w.strains[m], 6, 1)
+            okeys = w.count_refs[m][0]
+            dev = bm.key_bytes(bm.exported_keys(c))
+            row_of = {k: i for i, k in enumerate(okeys)}
+            assert n == len(okeys) == len(row_of) and sorted(dev) == sorted(okeys), (w.name, m, "the device's key set is not the oracle's")
+            orow[m] = np.array([row_of[k] for k in dev], dtype=np.int64)      # the oracle's row of every row of the device
+            assert (np.diff(c.first_pos().astype(np.int64)) > 0).all()
+            if tally:
+                c.set_counts(0, type_col(w.tally_refs[m][2])[orow[m]])
+        c, want = ctxs[main], w.count_refs[main][1].astype(np.int64)[orow[main]]
+
+        def same(got, what, times=1):
+            assert np.array_equal(got, times * want), (w.name, "built on the device", what, np.nonzero(got != times * want)[0][:10])
+
+        c.scan_stream(stream, 1)
+        same(c.counts(1), "COUNT")
+        buf = c.dev_alloc(len(packed))
+        c.dev_upload(buf, packed)
+        c.scan_device_packed(buf, len(stream), 2)
+        c.sync()
+        c.dev_free(buf)
+        same(c.counts(2), "PACKED")
+        buf = c.dev_alloc(len(stream))
+        c.dev_upload(buf, np.frombuffer(stream, dtype=np.uint8))
+        c.scan_device(buf, len(stream), 3)
+        c.scan_device(buf, len(stream), 3)
+        c.sync()
+        c.dev_free(buf)
+        same(c.counts(3), "RESIDENT twice", 2)
+        if tally:
+            ref, o, _ = w.tally_refs[main]
+            t, h = c.tally_batch(stream, starts, 0, 2)
+            h = np.stack([h[:, 0].astype(np.int64), orow[main][h[:, 1]]], axis=1) if len(h) else h
+            tr.check_single(o, stream, starts, ref, t, h, (w.name, "built on the device", "TALLY"))
+        if union:
+            with sk.KmerUnion([ctxs[m] for m in members], 0, 2) as u:
+                t, h = u.tally_batch(stream, starts)
+                for m in members:
+                    ref, o, _ = w.tally_refs[m]
+                    hm = h[h[:, 0] == m][:, 1:].astype(np.int64)
+                    hm[:, 1] = orow[m][hm[:, 1]]
+                    tr.check_single(o, stream, starts, ref, t[:, m, :], hm, (w.name, "built on the device", "UNION", m))
+    finally:
+        for c in ctxs.values():
+            c.close()
+
+
+def run_every_form(w, main=0, tally=True, union=True, built="host"):
     """world w's stream against its strain `main`: COUNT with text_stage 1 and 0, pipeline 2, resident on the device (scanned twice:
     both lanes see it), the host-packed form on the device; tally: one TALLY launch; union: the TALLY launch of a union of all
-    the world's strains, each member credited exactly.  text_stage 0 uses none of stage 2's text and rank map: the control."""
+    the world's strains, each member credited exactly.  text_stage 0 uses none of stage 2's text and rank map: the control.
+    built="device": the form run_built_on_the_device, whose tables the device builds itself, instead of these."""
+    if built == "device":
+        return run_built_on_the_device(w, main, tally, union)
+    assert built == "host"
     import strainer2_amd as sk
     stream, starts = w.stream, w.starts
     packed, odd = sk.pack_stream(stream)

@@ -25,6 +25,7 @@ from strainer2_amd.native import TallyBatch, lib
 pytestmark = pytest.mark.gpu
 
 SK_E_ARG = -3
+STRAIN_ORDER = 0xFFFFFFFF                                              # Keyset.from_stream(initial_slots=...): rows by first occurrence
 _CODE = np.full(256, 255, dtype=np.uint8)
 for _i, _b in enumerate(b"ACGT"):
     _CODE[_b] = _i
@@ -132,8 +133,8 @@ def test_table_from_the_hosts_key_set(name):
 
 @pytest.mark.parametrize("name", ["wrap50", "full90"])
 def test_table_built_on_the_device(name, tmp_path):
-    """skh_keyset_build_on_device (sk_build_insert, sk_build_first, sk_build_index): the host's key set exactly, column 0 all
-    col0_value, and the oracle's count for every key"""
+    """skh_keyset_build_on_device (sk_build_insert, sk_build_first, sk_build_index): the host's key set exactly, row by row that of
+    the host builder in strain order, column 0 all col0_value, and the oracle's count for every key"""
     x = _want(name)
     w = x["w"]
     fa = tmp_path / "s.fa"
@@ -149,6 +150,11 @@ def test_table_built_on_the_device(name, tmp_path):
             lib.sk_table_export_keys.argtypes = [C.c_void_p, C.c_void_p]
             assert lib.sk_table_export_keys(cd._h, whole.ctypes.data) == 0
             assert np.array_equal(np.sort(whole), np.sort(x["packed"]))
+            ordered = sk.Keyset.from_stream(w.sstream, initial_slots=STRAIN_ORDER, default_val=1, incr=0)
+            try:                                                           # and in the ORDER of the host's key set in strain order
+                assert ordered.nrows == n and np.array_equal(whole, ordered.packed()), np.nonzero(whole != ordered.packed())[0][:10]
+            finally:
+                ordered.close()
             assert cd.counts(0).tolist() == [7] * n
             cd.scan_stream(w.stream, 1)
             cd.scan_stream(w.stream_clean, 2)

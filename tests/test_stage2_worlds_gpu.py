@@ -12,7 +12,8 @@ premises: tests/test_stage2_worlds_host.py), in every form of the kernel, agains
   diff    the difference array and its three flush kernels at nrows + 1 around multiples of 4096
 
 Forms: COUNT with text_stage 1 and 0 (0: the control, none of stage 2's text), pipeline 2, resident on the device twice (both lanes),
-the host-packed form on the device, one TALLY launch, the TALLY launch of a union."""
+the host-packed form on the device, one TALLY launch, the TALLY launch of a union.  And one form more, for shift, ends and seams: every
+table built on the device from the strain's records (COUNT, packed, resident twice, TALLY, a union of members all built there)."""
 import numpy as np
 import pytest
 
@@ -45,6 +46,43 @@ def test_seams_in_every_form(main):
 
 def test_runs_in_every_count_form():
     w2.run_every_form(w2.runs_world(), tally=False, union=False)
+
+
+# ---- the same worlds on tables the device built itself (sk_table_build_from_text) ----------------------------------------------------------
+def _device_form(w):
+    """the id of a case of the form "built on the device": a world whose strains hold a letter build_from_text cannot take (U, an
+    IUPAC letter) says so and runs nothing"""
+    return "device" if w2.device_buildable(w) else "device-not-run-strain-has-U-or-IUPAC"
+
+
+def _built_on_the_device(w, **kw):
+    if w2.device_buildable(w):
+        w2.run_every_form(w, built="device", **kw)
+
+
+_ENDS = [pytest.param(L, id="%d-%s" % (L, _device_form(w2.ends_world(L)))) for L in w2.ENDS_LENGTHS]
+_UNIONS = [pytest.param(p, id="%d+%d-%s" % (p + (_device_form(w2.ends_union_world(p)),))) for p in w2.ENDS_UNIONS]
+_SEAMS = [pytest.param(m, id="%s-%s" % (n, _device_form(w2.seams_world()))) for m, n in enumerate(["records", "N-A", "N-C", "N-G", "N-T"])]
+
+
+def test_shift_built_on_the_device():
+    assert _device_form(w2.shift_world()) == "device"
+    _built_on_the_device(w2.shift_world())
+
+
+@pytest.mark.parametrize("L", _ENDS)
+def test_ends_built_on_the_device(L):
+    _built_on_the_device(w2.ends_world(L), union=False)
+
+
+@pytest.mark.parametrize("pair", _UNIONS)
+def test_ends_of_union_members_built_on_the_device(pair):
+    _built_on_the_device(w2.ends_union_world(pair))
+
+
+@pytest.mark.parametrize("main", _SEAMS)
+def test_seams_built_on_the_device(main):
+    _built_on_the_device(w2.seams_world(), main=main, union=main == 0)
 
 
 @pytest.mark.parametrize("resident", [False, True], ids=["scan_stream", "scan_device"])

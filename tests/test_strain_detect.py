@@ -99,8 +99,9 @@ def test_sd_program_with_the_key_set_built_on_the_host(golden, name, tmp_path, m
 @pytest.mark.gpu
 def test_table_built_on_the_device_equals_the_hosts(tmp_path):
     """sk_table_build_from_text against the host's key set on a strain with repeats, both strands of a segment, N runs, lower
-    case, a record of 30 bases (no window) and one of 31: the same SET of keys (the numbering is by first occurrence along the
-    text in both, so the same order too), column 0 all 1, and a scan counts every row alike through either table."""
+    case, a record of 30 bases (no window) and one of 31: the same SET of keys as the host's in its default order, the same keys row
+    by row as the host's in strain order (both number by first occurrence along the text), column 0 all 1, and a scan counts every
+    row alike through either table."""
     import ctypes as C
     from strainer2_amd.native import lib
     rng = random.Random(314)
@@ -133,6 +134,9 @@ def test_table_built_on_the_device_equals_the_hosts(tmp_path):
         assert list(dks.packed[:n]) == list(whole)
         dev_keys = [lib_key(dks, r) for r in range(n)]
         assert sorted(dev_keys) == sorted(host.keys()) and n == host.nrows
+        ordered = sk.Keyset.from_stream(b"\n".join(recs) + b"\n", initial_slots=0xFFFFFFFF, default_val=1, incr=0)   # (the host's rows in strain order)
+        assert dev_keys == ordered.keys() and ordered.first_pos().tolist() == cd.first_pos().tolist()
+        ordered.close()
         cd.scan_stream(reads, 2)
         hc, dc = ch.counts(2), cd.counts(2)
         by_key_h = dict(zip(host.keys(), hc.tolist()))
