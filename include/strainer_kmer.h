@@ -911,6 +911,54 @@ int  sk_covacc_finish_target_classes(sk_covacc *a, uint64_t *out_unique /* nmemb
                                      uint64_t *out_stray);
 int  sk_distinct_classes(sk_ctx *ctx, const uint64_t *keys, const uint32_t *sample, const uint8_t *cls, uint64_t n, uint32_t nsamples,
                          uint32_t ncls, uint64_t *out_unique /* nsamples x ncls */, uint64_t *out_total /* nsamples x ncls */);
+/* SUPPORT (new): the READ PAIRS behind step 4's numbers, per strain and across the strains of a panel.  Every other table here counts
+ * k-mers; 500 counted lines can be 500 pairs of one hit or 10 pairs of 50, and a strain whose lines come from pairs that also support
+ * a sibling of its panel is a relative of both or a chimera, not either strain (after a -C scrub the informative sets of two panel
+ * strains are disjoint).  The reference never built this view (the commented-out --read_hits_file of scripts/coverage_depth.py).
+ * The rule, for one strain m and a target whose pairs are numbered j = 0, 1, ... in file order (single reads: a pair is a read):
+ *   the reference's read loop (src/strain_detect.c:443-626) refreshes the tallies h (all hits) and i (informative hits) of every
+ *   read with at least k bases; a shorter read keeps the tallies and rows of the read before it.  If h1 + h2 >= 1 and i1 + i2 >= 1 it
+ *   prints the PE1 read's informative rows, then, if the PE2 read is valid, that read's; every line carries h1 + h2 and the script
+ *   counts a line iff h1 + h2 > min_kmer_hits.
+ *   emission    one pass of pair j through that point that prints L >= 1 lines, all of them counted.  A short read re-emits the rows
+ *               of the read before it: that counts as an emission, so that `lines` stays equal to step 4's total.
+ *   supporting_pairs[m]  the number of emissions of m.
+ *   lines[m]             the sum of L over them: total_observed_informative_kmers of the main table's line.
+ *   both_mates[m]        emissions in which the PE1 part and the PE2 part each printed at least one line; 0 for single reads.
+ *   group       the strains that share one launch (a union's members; a single context is a group of one).  For a, b of one group:
+ *   shared_pairs[a][b]   pairs j at which both a and b have an emission (symmetric);
+ *   lines_a[a][b]        the sum of a's L over those pairs (not symmetric);
+ *   exclusive_pairs[a], exclusive_lines[a]   emissions of a at pairs where no other strain of the group has one, and their L: the
+ *               diagonal [a][a] of the two matrices.  Strains of different groups are not compared: their cells are zero.
+ *   invariants  supporting_pairs[a] >= exclusive_pairs[a]; shared_pairs[a][b] <= min(supporting_pairs[a], supporting_pairs[b]);
+ *               lines_a[a][b] <= lines[a]; both_mates[a] <= supporting_pairs[a] <= lines[a].
+ *   tables      strain_detect --coverage-support[=FILE] (with --coverage-depth or --coverage-only; default FILE the -o path with
+ *               ".kmer_hits.gz" replaced by ".coverage_support") writes per strain a header line and one line per sample, in the
+ *               order of the strain's main table (a sample is a target's basename; two targets with one basename are one sample; a
+ *               sample without an emission has a line of zeros), all numbers integers:
+ *                 metagenome<TAB>supporting_pairs<TAB>both_mates<TAB>lines
+ *               --support-pairs=FILE (with --coverage-support and -S; one process, union tables) writes ONE file for the panel: a
+ *               line "#group<TAB>g<TAB>strain names..." per group (the consecutive -S lines that share a union table: 32, or
+ *               SK_SD_GROUP), a header line, then per sample (first appearance), strain a (-S order) and strain b of a's group:
+ *                 metagenome<TAB>strain_a<TAB>strain_b<TAB>pairs<TAB>lines_a
+ *               a != b: shared_pairs and lines_a, only where pairs > 0, both orders; a == b: exclusive_pairs and exclusive_lines,
+ *               for every strain and sample, zeros included.  Strain names as in the coverage tables.  Strains of different groups
+ *               are not compared and have no line.
+ * In a run the device folds every read has k bases or more, so an emission of (j, m) is tot[j, m] > min_kmer_hits with
+ * inf_1 + inf_2 >= 1 and L = inf_1 + inf_2 (the sparse records' third word): the fold needs nothing beyond the records.
+ *   sk_covacc_set_support: on != 0 switches support on, 0 off (the state after create).  While it is off nothing of it is allocated
+ *   and no fold or sweep launches a kernel it did not launch before; every other result of the accumulator is the same either way.
+ *   At most SK_COVACC_SUPPORT_MEMBERS_MAX members (the matrices are nmembers x nmembers), and with support on sk_covacc_add takes
+ *   launches of at most SK_UNION_MAX members (SK_E_ARG otherwise).  Rows handed in by sk_covacc_add_rows / sk_covacc_add_rows_hits
+ *   carry no read identity and add nothing here: the emissions of replayed runs are the caller's to count.
+ *   sk_covacc_finish_target_support: the numbers of the folds since the last call, all u64 -- out_pairs, out_lines, out_both per
+ *   member; out_shared and out_lines_a as [nmembers x nmembers], row a, column b, zero outside a launch's members -- and the
+ *   accumulators are zero afterwards (a second call returns zeros).  Independent of the sweeps.  SK_E_STATE while support is off. */
+#define SK_COVACC_SUPPORT_MEMBERS_MAX 1024u
+int  sk_covacc_set_support(sk_covacc *a, int on);
+int  sk_covacc_finish_target_support(sk_covacc *a, uint64_t *out_pairs /* nmembers */, uint64_t *out_lines /* nmembers */,
+                                     uint64_t *out_both /* nmembers */, uint64_t *out_shared /* nmembers x nmembers */,
+                                     uint64_t *out_lines_a /* nmembers x nmembers */);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
  * same stdout bytes and exit status.  New: --scrub-classes FILE --scrub-sweep[=FILE] also writes the scrub sweep table (above) to
  * FILE, default the hits file's path with a trailing ".kmer_hits.gz" replaced by ".coverage_scrub_sweep"; stdout is unchanged; a hit

@@ -20,6 +20,10 @@
 // changes no counter, and a run without thresholds launches neither.
 // covacc_class_scatter / covacc_class_finish are the scrub sweep (--coverage-scrub-sweep): one class byte per row, and a pass of its own
 // in front of the sweep that bins the non-zero rows by class; it changes nothing at all, and a run without classes launches neither.
+// covacc_scatter_sup / covacc_take are the read pairs behind those numbers (support: include/strainer_kmer.h has the rule): the scatter
+// that also sums each (pair, member)'s informative tallies and marks the pair's word, and the pass between the scatter and the clearing
+// scatter in which one lane per marked pair adds the pair's supporters to per-workgroup LDS tables.  A run with support off launches
+// neither and allocates nothing of them.
 // Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -597,6 +601,103 @@ __global__ void __launch_bounds__(256) covacc_class_finish(const uint32_t *__res
     if (threadIdx.x == 0 && s_bad) atomicAdd(stray, (unsigned long long)s_bad);
 }
 
+// ---- support: the read pairs behind step 4's numbers, per member and across the members of a launch (include/strainer_kmer.h) ----
+// An emission of (pair j, member m) in a folded run is tot[j, m] > min_hits with inf[j, m] >= 1, its lines L = inf[j, m] (both mates'
+// informative tallies).  Three steps inside the fold:
+//   mark   covacc_scatter_sup is covacc_scatter, and a record with inf > 0 also adds inf to sinf[pair * members + member] and sets bit
+//          member (side 0: PE1) or 32 + member (side 1: PE2) of word[pair] with a 64-bit atomicOr that returns nothing.  Both arrays
+//          are all zero between folds, as tot[] is.
+//   take   covacc_take, behind a kernel boundary: every record with inf > 0 exchanges its pair's word for 0; the one lane that gets a
+//          non-zero word owns the pair.  At most 2 x members records meet on one word and the pairs are spread over the run, so the
+//          returning atomic is not the one-address queue that cost sk_union_compact 587 us.  The owner masks the word by "member
+//          passes tot > min_hits" -- S = (PE1 | PE2) & pass, both = PE1 & PE2 & pass -- and adds to the workgroup's LDS tables: per
+//          member {pairs, lines, both}, per ordered (a, b) of S x S {pairs, lines of a}; the diagonal takes only pairs with |S| = 1
+//          (the exclusive ones).  Two 32 x 32 tables of 64-bit cells plus 32 x 3: sk_union_share's layout.  A pair that supports all
+//          32 members costs its owner 32 x 31 x 2 LDS adds in a divergent loop; real pairs support one member or two.  Each workgroup
+//          adds its non-zero cells to the target's accumulators once, with 64-bit global atomics.
+//   clear  the clearing scatter also zeroes the sinf cells; the words are zero after the take.
+#define COV_SUP_M SK_UNION_MAX
+
+__global__ void covacc_scatter_sup(const uint32_t *__restrict__ recs, uint64_t n, uint32_t ns, uint32_t nrec, uint32_t r0, uint32_t step,
+                                   uint32_t npairs, uint32_t *__restrict__ tot, uint32_t *__restrict__ sinf,
+                                   unsigned long long *__restrict__ word, uint32_t side, int clear)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t key = recs[3 * i], rec = key / ns, m = key - rec * ns;
+        if (rec >= nrec) continue;
+        const uint32_t j = cov_pair(rec, r0, step, npairs);
+        if (j >= npairs) continue;
+        const size_t cell = (size_t)j * ns + m;
+        if (clear) { tot[cell] = 0u; sinf[cell] = 0u; continue; }
+        atomicAdd(tot + cell, recs[3 * i + 1]);                // (exactly covacc_scatter up to here)
+        const uint32_t inf = recs[3 * i + 2];
+        if (inf && m < COV_SUP_M) {                           // (m >= COV_SUP_M never: the host refuses launches of more members; no bit stands for it)
+            atomicAdd(sinf + cell, inf);
+            atomicOr(word + j, (unsigned long long)(1u << m) << (side ? 32u : 0u));
+        }
+    }
+}
+
+// acc: [nm x 3] {pairs, lines, both} per member, then [nm x nm] shared pairs, then [nm x nm] lines of the row's member; the launch's
+// members are members member0 .. member0 + ns - 1 of the accumulator's nm (the host has checked that they fit, and ns <= COV_SUP_M)
+__global__ void __launch_bounds__(256) covacc_take(const uint32_t *__restrict__ recs, uint64_t n, uint32_t ns, uint32_t nrec, uint32_t r0,
+                                                   uint32_t step, uint32_t npairs, const uint32_t *__restrict__ tot,
+                                                   const uint32_t *__restrict__ sinf, unsigned long long *__restrict__ word,
+                                                   long long min_hits, uint32_t member0, uint32_t nm, unsigned long long *__restrict__ acc)
+{
+    __shared__ unsigned long long s_pairs[COV_SUP_M * COV_SUP_M], s_lines[COV_SUP_M * COV_SUP_M], s_mem[COV_SUP_M * 3u];
+    for (uint32_t c = threadIdx.x; c < COV_SUP_M * COV_SUP_M; c += 256u) { s_pairs[c] = 0ull; s_lines[c] = 0ull; }
+    if (threadIdx.x < COV_SUP_M * 3u) s_mem[threadIdx.x] = 0ull;
+    __syncthreads();
+    if (ns > COV_SUP_M || member0 >= nm || ns > nm - member0) return;     // (never; the whole workgroup)
+    const uint32_t all = ns >= 32u ? 0xFFFFFFFFu : (1u << ns) - 1u;
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += stride) {
+        if (!recs[3 * i + 2]) continue;
+        const uint32_t key = recs[3 * i], rec = key / ns;
+        if (rec >= nrec) continue;
+        const uint32_t j = cov_pair(rec, r0, step, npairs);
+        if (j >= npairs) continue;
+        const unsigned long long w = atomicExch(word + j, 0ull);
+        if (!w) continue;                                     // another lane owns the pair (or owned it)
+        const uint32_t lo = (uint32_t)w & all, hi = (uint32_t)(w >> 32) & all;
+        const uint32_t *t = tot + (size_t)j * ns, *li = sinf + (size_t)j * ns;
+        uint32_t pass = 0;
+        for (uint32_t b = lo | hi; b; b &= b - 1u) {
+            const uint32_t m = (uint32_t)__builtin_ctz(b);
+            if ((long long)t[m] > min_hits) pass |= 1u << m;
+        }
+        const uint32_t S = (lo | hi) & pass, both = lo & hi & pass;
+        if (!S) continue;
+        const bool alone = (S & (S - 1u)) == 0u;
+        for (uint32_t x = S; x; x &= x - 1u) {
+            const uint32_t a = (uint32_t)__builtin_ctz(x);
+            const unsigned long long L = li[a];
+            atomicAdd(&s_mem[a * 3u], 1ull);
+            atomicAdd(&s_mem[a * 3u + 1u], L);
+            if (both & (1u << a)) atomicAdd(&s_mem[a * 3u + 2u], 1ull);
+            if (alone) { atomicAdd(&s_pairs[a * COV_SUP_M + a], 1ull); atomicAdd(&s_lines[a * COV_SUP_M + a], L); continue; }
+            for (uint32_t y = S & ~(1u << a); y; y &= y - 1u) {
+                const uint32_t b = (uint32_t)__builtin_ctz(y);
+                atomicAdd(&s_pairs[a * COV_SUP_M + b], 1ull);
+                atomicAdd(&s_lines[a * COV_SUP_M + b], L);
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long *g_pairs = acc + (size_t)nm * 3u, *g_lines = g_pairs + (size_t)nm * nm;
+    for (uint32_t c = threadIdx.x; c < COV_SUP_M * COV_SUP_M; c += 256u) {
+        const uint32_t a = c / COV_SUP_M, b = c - a * COV_SUP_M;
+        if (a >= ns || b >= ns || !s_pairs[c]) continue;
+        const size_t g = (size_t)(member0 + a) * nm + member0 + b;
+        atomicAdd(g_pairs + g, s_pairs[c]);
+        if (s_lines[c]) atomicAdd(g_lines + g, s_lines[c]);
+    }
+    if (threadIdx.x < COV_SUP_M * 3u && threadIdx.x / 3u < ns && s_mem[threadIdx.x])
+        atomicAdd(acc + (size_t)member0 * 3u + threadIdx.x, s_mem[threadIdx.x]);
+}
+
 struct sk_covacc {
     sk_ctx *ctx; int device;
     hipStream_t stream;
@@ -639,6 +740,12 @@ struct sk_covacc {
     uint8_t *d_cls_up; size_t cls_up_cap;                   // set_classes' upload of the sparse list's classes
     unsigned long long *d_cls_out;                          // [nm x SK_SCRUB_SWEEP_MAX] pairs, then the stray count
     double ms_cls;                                          // the class passes' device time
+    // support: nothing of it exists until sk_covacc_set_support switches it on
+    bool sup_on;
+    uint32_t *d_sinf; size_t sinf_cap;                      // [pairs x members] summed informative tallies; all zero between folds
+    unsigned long long *d_sword; size_t sword_cap;          // [pairs] PE1 members | PE2 members << 32; all zero between folds
+    unsigned long long *d_sup; size_t sup_cells;            // the target's accumulators (covacc_take has the layout); zero after a finish
+    hipEvent_t ev2, ev3; bool sup_timed; double ms_take, ms_supfin;   // the takes' and the finishes' device time
 };
 
 static void cov_t0(sk_covacc *a) { if (a->timed) (void)hipEventRecord(a->ev0, a->stream); }
@@ -682,6 +789,15 @@ extern "C" int sk_covacc_classes_timing_(sk_covacc *a, double *ms_cls)
     return SK_OK;
 }
 
+// ms_take: the takes' device time inside the folds (the mark rides in the fold's scatter and is part of ms_fold only); ms_finish: the
+// copies home.  Both are kept only while sk_covacc_timing_ is on.
+extern "C" int sk_covacc_support_timing_(sk_covacc *a, double *ms_take, double *ms_finish)
+{
+    if (!a || !ms_take || !ms_finish) return SK_E_ARG;
+    *ms_take = a->ms_take; *ms_finish = a->ms_supfin;
+    return SK_OK;
+}
+
 #define CA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sk_fail_(a->ctx, SK_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 static unsigned cov_grid(uint64_t n) { const uint64_t g = (n + 255u) / 256u; return (unsigned)(g < 1u ? 1u : g > 4096u ? 4096u : g); }
@@ -710,6 +826,8 @@ extern "C" void sk_covacc_destroy(sk_covacc *a)
     (void)hipFree(a->d_irank); (void)hipFree(a->d_rec_nbits); (void)hipFree(a->d_blk); (void)hipFree(a->d_stray);
     (void)hipFree(a->d_thr_max); (void)hipFree(a->d_thr_cnt); (void)hipFree(a->d_tots);
     (void)hipFree(a->d_cls); (void)hipFree(a->d_ncls); (void)hipFree(a->d_cls_up); (void)hipFree(a->d_cls_out);
+    (void)hipFree(a->d_sinf); (void)hipFree(a->d_sword); (void)hipFree(a->d_sup);
+    if (a->sup_timed) { (void)hipEventDestroy(a->ev2); (void)hipEventDestroy(a->ev3); }
     if (a->timed) { (void)hipEventDestroy(a->ev0); (void)hipEventDestroy(a->ev1); }
     if (a->h_bad) (void)hipHostFree(a->h_bad);
     if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -862,12 +980,37 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
     if ((uint64_t)npairs * ns > 0x3FFFFFF0ull) return sk_fail_(a->ctx, SK_E_ARG, "too many pairs x members");
     CA_HIP(hipSetDevice(a->device));
     if ((rc = cov_room(a, (void **)&a->d_tot, &a->tot_cap, (size_t)npairs * ns * 4u, true)) != SK_OK) return rc;
+    const bool sup = a->sup_on;
+    if (sup) {
+        if (ns > COV_SUP_M) return sk_fail_(a->ctx, SK_E_ARG, "support is on: a launch of %u members, at most %u", ns, COV_SUP_M);
+        if ((rc = cov_room(a, (void **)&a->d_sinf, &a->sinf_cap, (size_t)npairs * ns * 4u, true)) != SK_OK) return rc;
+        if ((rc = cov_room(a, (void **)&a->d_sword, &a->sword_cap, (size_t)npairs * 8u, true)) != SK_OK) return rc;
+        if (a->timed && !a->sup_timed) {
+            CA_HIP(hipEventCreate(&a->ev2));
+            if (hipEventCreate(&a->ev3) != hipSuccess) { (void)hipEventDestroy(a->ev2); return sk_fail_(a->ctx, SK_E_HIP, "no event for the take"); }
+            a->sup_timed = true;
+        }
+    }
     cov_t0(a);
     for (int clear = 0; clear < 2; clear++) {
         for (uint32_t k = 0; k < nsides; k++)
-            if (side[k].nrecs)
+            if (side[k].nrecs && sup)
+                hipLaunchKernelGGL(covacc_scatter_sup, dim3(cov_grid(side[k].nrecs)), dim3(256), 0, a->stream, side[k].recs, side[k].nrecs, ns,
+                                   side[k].nrec, side[k].r0, side[k].step, npairs, a->d_tot, a->d_sinf, a->d_sword, k, clear);
+            else if (side[k].nrecs)
                 hipLaunchKernelGGL(covacc_scatter, dim3(cov_grid(side[k].nrecs)), dim3(256), 0, a->stream, side[k].recs, side[k].nrecs, ns,
                                    side[k].nrec, side[k].r0, side[k].step, npairs, a->d_tot, clear);
+        if (sup && !clear) {                                  // the take: behind every side's marks, in front of the clearing scatter
+            if (a->sup_timed) (void)hipEventRecord(a->ev2, a->stream);
+            for (uint32_t k = 0; k < nsides; k++)
+                if (side[k].nrecs) {
+                    const unsigned g = cov_grid(side[k].nrecs);
+                    hipLaunchKernelGGL(covacc_take, dim3(g > 256u ? 256u : g), dim3(256), 0, a->stream, side[k].recs, side[k].nrecs, ns,
+                                       side[k].nrec, side[k].r0, side[k].step, npairs, (const uint32_t *)a->d_tot,
+                                       (const uint32_t *)a->d_sinf, a->d_sword, a->min_hits, member0, a->nm, a->d_sup);
+                }
+            if (a->sup_timed) (void)hipEventRecord(a->ev3, a->stream);
+        }
         for (uint32_t k = 0; k < nsides && !clear; k++)
             if (side[k].nhits && a->thr.n) {                  // (thresholds: the same fold, every entry classified as well)
                 hipLaunchKernelGGL(covacc_hits_thr, dim3(cov_grid(side[k].nhits)), dim3(256), 0, a->stream, side[k].hits, side[k].nhits,
@@ -882,17 +1025,58 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
                                    (const uint32_t *)a->d_tot, a->min_hits, a->d_depth, (const uint64_t *)a->d_base + member0,
                                    (const uint32_t *)a->d_nrows + member0, a->d_bad);
     }
-    {   // a fold that fails half way leaves tot[] as it must be between folds: all zero
+    {   // a fold that fails half way leaves tot[] (and support's cells and words) as they must be between folds: all zero
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
         if (e != hipSuccess) {
             (void)hipMemset(a->d_tot, 0, a->tot_cap);
+            if (a->d_sinf) (void)hipMemset(a->d_sinf, 0, a->sinf_cap);
+            if (a->d_sword) (void)hipMemset(a->d_sword, 0, a->sword_cap);
             return sk_fail_(a->ctx, SK_E_HIP, "the fold failed: %s", hipGetErrorString(e));
         }
     }
     cov_t1(a, &a->ms_fold);
+    if (sup && a->sup_timed) { float ms = 0.f; if (hipEventElapsedTime(&ms, a->ev2, a->ev3) == hipSuccess) a->ms_take += (double)ms; }
     if (mate && mate->held) a->held = false;
     if (*(volatile uint32_t *)a->h_bad) { *a->h_bad = 0u; return sk_fail_(a->ctx, SK_E_STATE, "a hit log entry names no row of its member"); }
+    return SK_OK;
+}
+
+// ---- support ----
+extern "C" int sk_covacc_set_support(sk_covacc *a, int on)
+{
+    if (!a) return SK_E_ARG;
+    if (on && !a->d_sup) {
+        if (a->nm > SK_COVACC_SUPPORT_MEMBERS_MAX) return sk_fail_(a->ctx, SK_E_ARG, "support: %u members, at most %u", a->nm, SK_COVACC_SUPPORT_MEMBERS_MAX);
+        CA_HIP(hipSetDevice(a->device));
+        const size_t cells = (size_t)a->nm * 3u + (size_t)a->nm * a->nm * 2u;
+        unsigned long long *p = NULL;
+        CA_HIP(hipMalloc((void **)&p, cells * 8u));
+        if (hipMemsetAsync(p, 0, cells * 8u, a->stream) != hipSuccess || hipStreamSynchronize(a->stream) != hipSuccess) {
+            (void)hipFree(p);
+            return sk_fail_(a->ctx, SK_E_HIP, "no room for the support accumulators");
+        }
+        a->d_sup = p; a->sup_cells = cells;
+    }
+    a->sup_on = on != 0;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_finish_target_support(sk_covacc *a, uint64_t *out_pairs, uint64_t *out_lines, uint64_t *out_both,
+                                               uint64_t *out_shared, uint64_t *out_lines_a)
+{
+    if (!a || !out_pairs || !out_lines || !out_both || !out_shared || !out_lines_a) return SK_E_ARG;
+    if (!a->sup_on) return sk_fail_(a->ctx, SK_E_STATE, "support is off (sk_covacc_set_support)");
+    CA_HIP(hipSetDevice(a->device));
+    std::vector<unsigned long long> h(a->sup_cells);
+    cov_t0(a);
+    CA_HIP(hipMemcpyAsync(h.data(), a->d_sup, a->sup_cells * 8u, hipMemcpyDeviceToHost, a->stream));
+    CA_HIP(hipMemsetAsync(a->d_sup, 0, a->sup_cells * 8u, a->stream));
+    CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_supfin);
+    const size_t nn = (size_t)a->nm * a->nm;
+    for (uint32_t m = 0; m < a->nm; m++) { out_pairs[m] = h[3u * m]; out_lines[m] = h[3u * m + 1u]; out_both[m] = h[3u * m + 2u]; }
+    for (size_t c = 0; c < nn; c++) { out_shared[c] = h[(size_t)a->nm * 3u + c]; out_lines_a[c] = h[(size_t)a->nm * 3u + nn + c]; }
     return SK_OK;
 }
 

@@ -302,7 +302,7 @@ static char *sm_cov_path(const char *hits)
 static int sm_check_detect(int argc, char **argv, int *want_cov, int *want_sw, FILE *err)
 {
     char **v = (char **)malloc(((size_t)argc + 1) * sizeof *v);
-    int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0, want_rc = 0, want_rp = 0, want_th = 0;
+    int c, n = 0, bad = 0, saved = opterr, want_rg = 0, want_sp = 0, want_rc = 0, want_rp = 0, want_th = 0, want_su = 0, want_sq = 0;
     const char *th_list = NULL;
     if (!v) return 1;
     for (c = 0; c < argc; c++) {
@@ -397,6 +397,24 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, int *want_sw, F
             }
             continue;
         }
+        if (c > 0 && !strncmp(argv[c], "--coverage-support", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            if (argv[c][18] == '=') {
+                fprintf(err, "kmer_scrub_count: with -S, --coverage-support takes no file name (each strain's table goes next to its coverage table)\n");
+                free(v);
+                return 1;
+            }
+            want_su = 1;
+            continue;
+        }
+        if (c > 0 && !strncmp(argv[c], "--support-pairs", 15) && (argv[c][15] == 0 || argv[c][15] == '=')) {
+            if (argv[c][15] == 0 || argv[c][16] == 0) {      /* (the one file of the whole panel: here a file name is needed) */
+                fprintf(err, "kmer_scrub_count: --support-pairs=FILE needs a file name: the table is one file for the whole panel\n");
+                free(v);
+                return 1;
+            }
+            want_sq = 1;
+            continue;
+        }
         if (c > 0 && !strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { c++; continue; }
         v[n++] = argv[c];
     }
@@ -438,6 +456,16 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, int *want_sw, F
     }
     if (*want_sw && !*want_cov) {
         fprintf(err, "kmer_scrub_count: --coverage-scrub-sweep goes with --coverage-depth or --coverage-only: it gives their table's numbers at several min_fraction\n");
+        free(v);
+        return 1;
+    }
+    if (want_sq && !want_su) {
+        fprintf(err, "kmer_scrub_count: --support-pairs goes with --coverage-support\n");
+        free(v);
+        return 1;
+    }
+    if (want_su && !*want_cov) {
+        fprintf(err, "kmer_scrub_count: --coverage-support goes with --coverage-depth or --coverage-only: it counts the read pairs behind their table's numbers\n");
         free(v);
         return 1;
     }

@@ -14,6 +14,7 @@
  * FASTQ record in a PE2 file the file is treated as ended.
  */
 #define _GNU_SOURCE
+#include <assert.h>
 #include <dirent.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -94,6 +95,7 @@ typedef struct {
     uint32_t   *co_rows; uint64_t co_n, co_cap;   /* --coverage-only: rows of host-replayed passing hits on their way to the device's counters */
     uint32_t   *co_tot;                        /* --coverage-thresholds: beside every such row its pair's h1 + h2 (the rows then pass min(--min-kmer-hits, t[0])) */
     char *th_path;                             /* --coverage-thresholds: the table's path */
+    char *su_path;                             /* --coverage-support: the table's path */
     /* --coverage-scrub-sweep: the table's path, the strain's class file, its k-mers' rows and classes (the device's sparse list), and
      * every row's class (the host fold's) */
     char *sw_path; skc_classes sw_c; uint32_t *sw_rows; uint8_t *row_class;
@@ -1268,6 +1270,7 @@ typedef struct sd_job {
     int have_copy;
     int mute;                                  /* REPLAY: nothing is emitted, only the carried state moves on (a run the device counted) */
     int pending;                               /* lanes that still have it (atomic) */
+    sks_list *sup; int sup_sample;             /* REPLAY with --coverage-support: the run's emissions, a list per strain, and the target's sample */
 } sd_job;
 struct sd_lanes;
 typedef struct sd_lane {
@@ -1289,7 +1292,30 @@ static pthread_mutex_t sd_dev_mu = PTHREAD_MUTEX_INITIALIZER;
 static double t_lane_busy, t_lane_backpressure, t_lane_drain;
 
 static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk *ca, uint32_t a0, const sd_chunk *cb, uint32_t b0,
-                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute);
+                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute, sks_list *sup);
+
+/* --coverage-support[=FILE] [--support-pairs=FILE] (include/strainer_kmer.h has the rule): the read pairs behind the table's numbers.
+ * A run the device folds is counted there (sk_covacc_set_support; the numbers come home at the target's end beside the sweep's);
+ * a run replayed here records its emissions at sd_replay_run's emission site into the lists its job owns, and the last lane through
+ * the job merges them across each group's strains (sks_merge, sk_host_support.c).  A pair is counted by one of the two and never by
+ * both: a run is folded or replayed for ALL strains alike (sd_quantify decides per run, not per strain), the job of a folded run is
+ * mute and owns no lists.  sk_host_support.c's entries are weak, as the device's are: host-only test builds link without that file,
+ * and there the flag is refused. */
+#pragma weak sks_create
+#pragma weak sks_destroy
+#pragma weak sks_sample
+#pragma weak sks_list_push
+#pragma weak sks_list_free
+#pragma weak sks_merge
+#pragma weak sks_add_device
+#pragma weak sks_write_support
+#pragma weak sks_write_pairs
+static struct {
+    int on; const char *pairs_path;
+    sks_acc *acc; int sample;                  /* the run's numbers; the sample of the target being read */
+    int failed;                                /* a merge ran out of memory (any lane) */
+    double ms_take, ms_finish;                 /* SK_SD_TIMING */
+} sd_sup;
 
 static void lane_job_done(sd_lanes *L, sd_job *j)
 {
@@ -1299,6 +1325,13 @@ static void lane_job_done(sd_lanes *L, sd_job *j)
         L->syncs_done++;
         pthread_cond_broadcast(&L->scv);
         pthread_mutex_unlock(&L->smu);
+    }
+    if (j->sup) {                                          /* every lane is through: the emissions of all strains are in */
+        uint32_t s;
+        assert(!j->mute);                                  /* (a run the device counted records nothing here) */
+        if (sks_merge(sd_sup.acc, (uint32_t)j->sup_sample, j->sup)) __atomic_store_n(&sd_sup.failed, 1, __ATOMIC_RELAXED);
+        for (s = 0; s < L->ns; s++) sks_list_free(&j->sup[s]);
+        free(j->sup);
     }
     chunk_free(j->ca);
     chunk_free(j->cb);
@@ -1328,7 +1361,7 @@ static void *lane_main(void *arg)
                 sd_prog *p = &L->p[s];
                 if (j->kind == SD_JOB_TALLY) tally_one(p, j->ca, s);
                 else if (j->kind == SD_JOB_REPLAY && p->job_rc == SK_OK)
-                    sd_replay_run(p, s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute);
+                    sd_replay_run(p, s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute, j->sup ? &j->sup[s] : NULL);
             }
             ln->busy += now_s() - t0;
         }
@@ -1375,7 +1408,7 @@ static void lanes_post(sd_job *j)
             for (s = ln->id; s < L->ns; s += L->n) {
                 if (j->kind == SD_JOB_TALLY) tally_one(&L->p[s], j->ca, s);
                 else if (j->kind == SD_JOB_REPLAY && L->p[s].job_rc == SK_OK)
-                    sd_replay_run(&L->p[s], s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute);
+                    sd_replay_run(&L->p[s], s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute, j->sup ? &j->sup[s] : NULL);
             }
             lane_job_done(L, j);
             continue;
@@ -1651,6 +1684,9 @@ static struct { int on; uint32_t n; int64_t t[SK_COVACC_THRESHOLDS_MAX]; double 
 #pragma weak sk_covacc_set_classes
 #pragma weak sk_covacc_finish_target_classes
 #pragma weak sk_covacc_classes_timing_
+#pragma weak sk_covacc_set_support
+#pragma weak sk_covacc_finish_target_support
+#pragma weak sk_covacc_support_timing_
 static struct { int on; double ms_cls; } sd_sw;
 /* --coverage-recurrence [--recurrence-pairs] (include/strainer_kmer.h has the rule): with the accumulators on the device every unit
  * has one set of bit planes (sk_recur) over the run's target lines; the end of a target sets the bits of its non-zero rows
@@ -1712,6 +1748,7 @@ static void co_close(void)
         if (sd_rec.on && sk_covacc_mark_timing_ && sd_co.acc[k] && sk_covacc_mark_timing_(sd_co.acc[k], &f) == SK_OK) sd_rec.ms_mark += f;
         if (sd_thr.on && sk_covacc_thresholds_timing_ && sd_co.acc[k] && sk_covacc_thresholds_timing_(sd_co.acc[k], &f) == SK_OK) sd_thr.ms_finish += f;
         if (sd_sw.on && sk_covacc_classes_timing_ && sd_co.acc[k] && sk_covacc_classes_timing_(sd_co.acc[k], &f) == SK_OK) sd_sw.ms_cls += f;
+        if (sd_sup.on && sk_covacc_support_timing_ && sd_co.acc[k] && sk_covacc_support_timing_(sd_co.acc[k], &f, &w) == SK_OK) { sd_sup.ms_take += f; sd_sup.ms_finish += w; }
         if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
     }
     for (k = 0; k < sd_rec.nr; k++) {
@@ -1736,6 +1773,7 @@ static int co_open(sd_prog *p, uint32_t ns)
         (sd_spec.on && (!sk_covacc_set_spectrum || !sk_covacc_finish_target_spectrum)) ||
         (sd_thr.on && (!sk_covacc_set_thresholds || !sk_covacc_add_rows_hits || !sk_covacc_finish_target_thresholds)) ||
         (sd_sw.on && (!sk_covacc_set_classes || !sk_covacc_finish_target_classes)) ||
+        (sd_sup.on && (!sk_covacc_set_support || !sk_covacc_finish_target_support)) ||
         (sd_rec.on && (!sk_recur_create || !sk_recur_finish || !sk_covacc_set_recurrence || !sk_covacc_mark_target))) {
         fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
         sd_co.host = 1;
@@ -1759,6 +1797,7 @@ static int co_open(sd_prog *p, uint32_t ns)
         if (getenv("SK_SD_TIMING") && sk_covacc_timing_) (void)sk_covacc_timing_(sd_co.acc[k], 1, NULL, NULL);
         if (sd_spec.on && (rc = sk_covacc_set_spectrum(sd_co.acc[k], sd_spec.max)) != SK_OK) { co_close(); return rc; }
         if (sd_thr.on && (rc = sk_covacc_set_thresholds(sd_co.acc[k], sd_thr.t, sd_thr.n)) != SK_OK) { co_close(); return rc; }
+        if (sd_sup.on && (rc = sk_covacc_set_support(sd_co.acc[k], 1)) != SK_OK) { co_close(); return rc; }
         for (m = 0; m < n && sd_sw.on; m++) {             /* every member's class bytes, from its class file's k-mers */
             const sd_prog *q = &p[a + m];
             uint8_t one = 0;
@@ -2348,7 +2387,7 @@ static uint32_t sp_lower(const sd_sp *q, uint32_t rec)
  * not all zero (a read shorter than k refreshes nothing, :444, so it re-emits what the read before it left).  A pair without
  * hits met with all-zero tallies leaves them all zero and emits nothing: skipped. */
 static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk *ca, uint32_t a0, const sd_chunk *cb, uint32_t b0,
-                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute)
+                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute, sks_list *sup)
 {
     const sd_sp *A = &ca->sp[s], *B = cb ? &cb->sp[s] : NULL;
     const uint64_t a_end = (uint64_t)a0 + (uint64_t)n * astep, b_end = (uint64_t)b0 + (uint64_t)n * astep;
@@ -2386,8 +2425,12 @@ static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk
             else { p->h2 = p->i2 = 0; b_valid = 2; }       /* (valid, no rows) */
         }
         if (!mute && p->h1 + p->h2 >= 1 && p->i1 + p->i2 >= 1) {
-            if (have_copy_in || first_valid <= j) emit_rows(p, p->copy_rows, p->copy_n, f1);
-            if (b_valid == 1) emit_rows(p, B->rows + B->hbeg[ib], B->hbeg[ib + 1] - B->hbeg[ib], f1);
+            uint32_t la = 0, lb = 0;
+            if (have_copy_in || first_valid <= j) { emit_rows(p, p->copy_rows, p->copy_n, f1); la = p->copy_n; }
+            if (b_valid == 1) { lb = B->hbeg[ib + 1] - B->hbeg[ib]; emit_rows(p, B->rows + B->hbeg[ib], lb, f1); }
+            /* support: the emission, by the run's own --min-kmer-hits whatever emit_rows lets through for a threshold list */
+            if (sup && la + lb && (long long)p->h1 + p->h2 > sd_co.min && sks_list_push(sup, j, la + lb, (la ? 1u : 0u) | (lb ? 2u : 0u)))
+                p->job_rc = SK_E_NOMEM;
         }
         j++;
     }
@@ -2402,6 +2445,11 @@ static int post_replay(const char *f1, sd_chunk *ca, uint32_t a0, sd_chunk *cb, 
     j->f1 = f1; j->a0 = a0; j->b0 = b0; j->astep = astep; j->n = n; j->have_copy = have_copy;
     for (k = 0; k < n && ca->len[a0 + k * astep] < SK_K; k++) { }
     j->first_valid = k;
+    if (sd_sup.acc) {                                        /* (no lists: nothing is recorded, and the target's end reports the failure) */
+        j->sup = (sks_list *)calloc(sd_ln.ns, sizeof *j->sup);
+        j->sup_sample = sd_sup.sample;
+        if (!j->sup) __atomic_store_n(&sd_sup.failed, 1, __ATOMIC_RELAXED);
+    }
     lanes_post(j);
     return have_copy || k < n;
 }
@@ -2430,6 +2478,7 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
         if (rc) { fprintf(err, "strain_detect: cannot start the reader of %s\n", f2); stream_close(&A); return 1; }
     }
     for (s = 0; s < ns; s++) { p[s].h1 = p[s].i1 = p[s].h2 = p[s].i2 = 0; p[s].copy_n = 0; }
+    if (sd_sup.acc && (sd_sup.sample = sks_sample(sd_sup.acc, f1)) < 0) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
     t_sopen += now_s() - t_mark;
     sd_co.mode = mode; sd_co.pe_a = mode == SD_PE ? &A : NULL;
     A.co_next = 0;
@@ -2565,6 +2614,13 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
                     if (skc_add_class_counts(p[a + m].cov, f1, cu + (size_t)m * F, ct + (size_t)m * F, p[a + m].sw_c.F)) rc = SK_E_NOMEM;
                 if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
             }
+            if (sd_sup.acc) {                                /* the pairs behind the numbers, of the runs folded on the device */
+                uint64_t *sm = (uint64_t *)malloc(((size_t)3 * n + (size_t)2 * n * n) * sizeof *sm);
+                rc = sm ? sk_covacc_finish_target_support(sd_co.acc[k], sm, sm + n, sm + 2 * n, sm + 3 * n, sm + 3 * n + (size_t)n * n) : SK_E_NOMEM;
+                if (rc == SK_OK && sks_add_device(sd_sup.acc, (uint32_t)sd_sup.sample, a, n, sm, sm + n, sm + 2 * n, sm + 3 * n, sm + 3 * n + (size_t)n * n)) rc = SK_E_NOMEM;
+                free(sm);
+                if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
+            }
             rc = sd_spec.on ? sk_covacc_finish_target_spectrum(sd_co.acc[k], uq, tot, sp, deep, ru, rt) :
                  sd_rg.on ? sk_covacc_finish_target_regions(sd_co.acc[k], uq, tot, ru, rt) : sk_covacc_finish_target(sd_co.acc[k], uq, tot);
             pthread_mutex_unlock(&sd_dev_mu);
@@ -2585,6 +2641,7 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
             sd_rec.next++;
         }
     }
+    if (__atomic_load_n(&sd_sup.failed, __ATOMIC_RELAXED)) { fprintf(err, "strain_detect: --coverage-support: out of memory\n"); goto done; }
     for (s = 0; s < ns; s++) {
         emit_trailer(&p[s], f1, "total_kmer_evaluated", (long long)evaluated);
         emit_trailer(&p[s], f1, "total_reads_evaluated", (long long)reads);
@@ -2963,6 +3020,34 @@ static char *sd_table_path(const char *o_path, const char *explicit_path, const 
     return t;
 }
 
+/* --coverage-support: every strain's table, and with --support-pairs the panel's one file */
+static int sd_support_write(sd_prog *p, uint32_t ns)
+{
+    FILE *err = p[0].err, *f;
+    char **name = NULL;
+    uint32_t s;
+    int bad = 0;
+    for (s = 0; s < ns && !bad; s++) {
+        if (!(f = fopen(p[s].su_path, "w"))) { fprintf(err, "strain_detect: could not write %s\n", p[s].su_path); return 1; }
+        bad = sks_write_support(sd_sup.acc, s, f) != 0;
+        if (fclose(f)) bad = 1;
+        if (bad) fprintf(err, "strain_detect: error writing %s\n", p[s].su_path);
+    }
+    if (bad || !sd_sup.pairs_path) return bad;
+    name = (char **)calloc(ns, sizeof *name);
+    for (s = 0; name && s < ns; s++) if (!(name[s] = sd_strain_name(p[s].o_path))) break;
+    if (!name || s < ns) { fprintf(err, "strain_detect: out of memory\n"); bad = 1; }
+    else if (!(f = fopen(sd_sup.pairs_path, "w"))) { fprintf(err, "strain_detect: could not write %s\n", sd_sup.pairs_path); bad = 1; }
+    else {
+        bad = sks_write_pairs(sd_sup.acc, (const char *const *)name, f) != 0;
+        if (fclose(f)) bad = 1;
+        if (bad) fprintf(err, "strain_detect: error writing %s\n", sd_sup.pairs_path);
+    }
+    for (s = 0; name && s < ns; s++) free(name[s]);
+    free(name);
+    return bad;
+}
+
 static int sd_recurrence_open(sd_prog *p, const char *explicit_path, const char *explicit_pairs)
 {
     p->rc_path = sd_table_path(p->o_path, explicit_path, ".coverage_recurrence");
@@ -3195,7 +3280,7 @@ static void sd_strain_close(sd_prog *p)
     free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows); free(p->co_tot);
     skc_destroy(p->cov);
     if (skh_regions_free) skh_regions_free(&p->rg);
-    free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->th_path); free(p->rc_path); free(p->rp_path);
+    free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->th_path); free(p->su_path); free(p->rc_path); free(p->rp_path);
     free(p->sw_path); free(p->sw_rows); free(p->row_class);
     skc_classes_free(&p->sw_c);
     memset(p, 0, sizeof *p);
@@ -3252,6 +3337,16 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     sd_all_p = p; sd_all_ns = ns;
     sd_unions_open(p, ns);
     if (sd_ps.path && sd_panel_share(p, ns)) { sd_unions_close(); return 1; }      /* (before any target is read) */
+    if (sd_sup.on) {                                     /* a group = the strains of one union table; without unions every strain is alone */
+        if (sd_sup.pairs_path && ns > 1 && sd_un.n != (ns + sd_group - 1) / sd_group) {
+            fprintf(err, "strain_detect: --support-pairs: the strains cannot all be held in union tables (a strain with byte-string keys or "
+                         "without a text stage, or a union that could not be built): no pairs of the panel\n");
+            sd_unions_close();
+            return 1;
+        }
+        sd_sup.failed = 0;
+        if (!(sd_sup.acc = sks_create(ns, sd_un.n ? sd_group : 1u))) { fprintf(err, "strain_detect: out of memory\n"); sd_unions_close(); return 1; }
+    }
     sd_co.host = 0;
     if (sd_co.on && B) {                                 /* the script keys its samples by basename: two targets that share one are one sample */
         FILE *fp = fopen(B, "r");
@@ -3435,7 +3530,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     int want_rg = 0, want_sp = 0, want_ps = 0, want_rc = 0, want_rp = 0;
     const char *rc_file = NULL, *rp_file = NULL;
     const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL, *th_file = NULL, *th_list = NULL;
-    int want_th = 0, want_sw = 0;
+    int want_th = 0, want_sw = 0, want_su = 0, want_sq = 0;
+    const char *su_file = NULL, *sq_file = NULL;
     const char *sw_file = NULL, *sw_classes = NULL;
     skc_classes *swc = NULL;
     uint32_t nswc = 0;
@@ -3528,6 +3624,19 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             ps_file = argv[c][13] ? argv[c] + 14 : NULL;
             continue;
         }
+        /* "--coverage-support[=FILE] [--support-pairs=FILE]": next to either table, the read pairs behind its numbers -- supporting pairs,
+         * those with both mates, their lines -- default FILE = outfile with ".kmer_hits.gz" replaced by ".coverage_support"; with -S,
+         * --support-pairs=FILE is one file for the panel: the pairs every two strains of a group share */
+        if (!strncmp(argv[c], "--coverage-support", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            want_su = 1;
+            su_file = argv[c][18] ? argv[c] + 19 : NULL;
+            continue;
+        }
+        if (!strncmp(argv[c], "--support-pairs", 15) && (argv[c][15] == 0 || argv[c][15] == '=')) {
+            want_sq = 1;
+            sq_file = argv[c][15] ? argv[c] + 16 : NULL;
+            continue;
+        }
         if (!strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { cov_min = atoll(argv[++c]); continue; }
         if (!strcmp(argv[c], "--target-cache") && c + 1 < argc) { tc_dir = argv[++c]; continue; }       /* (extension: the target cache, see sd_tc) */
         if (!strncmp(argv[c], "--target-cache=", 15)) { tc_dir = argv[c] + 15; continue; }
@@ -3541,6 +3650,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_rec.on = 0;
     sd_co.on = 0;
     sd_ps.path = NULL;
+    sd_sup.on = 0; sd_sup.pairs_path = NULL;
     if (cov_only && want_cov) { fputs("strain_detect: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n", err); return sd_drop(p, ns); }
 
     optind = 1;
@@ -3642,6 +3752,20 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (want_rp && T > SK_RECUR_PAIRS_MAX) { fprintf(err, "strain_detect: --recurrence-pairs: %s names %u targets, at most %u\n", B, T, SK_RECUR_PAIRS_MAX); return sd_drop(p, ns); }
         sd_rec.T = T ? T : 1u;
     }
+    if (want_su || want_sq) {
+        const int several = (S && !a && !o && !r) || (ad && ad->o);
+        const char *ws = getenv("SK_WORLD_SIZE") ? getenv("SK_WORLD_SIZE") : getenv("WORLD_SIZE");
+        if (!want_su) { fputs("strain_detect: --support-pairs goes with --coverage-support\n", err); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-support goes with --coverage-depth or --coverage-only: it counts the read pairs behind their table's numbers\n", err); return sd_drop(p, ns); }
+        if (su_file && several) { fputs("strain_detect: --coverage-support=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        if (!sks_create || !sks_merge || !sks_write_support || !sks_write_pairs) { fputs("strain_detect: --coverage-support: this build has no support accumulator\n", err); return sd_drop(p, ns); }
+        if (want_sq) {
+            if (!sq_file || !*sq_file) { fputs("strain_detect: --support-pairs=FILE needs a file name: the table is one file for the whole panel\n", err); return sd_drop(p, ns); }
+            if (!several) { fputs("strain_detect: --support-pairs goes with -S: it compares the strains of a panel\n", err); return sd_drop(p, ns); }
+            if (ws && atoi(ws) > 1) { fprintf(err, "strain_detect: --support-pairs is for ONE process: with WORLD_SIZE %d each rank holds only its own strains\n", atoi(ws)); return sd_drop(p, ns); }
+            if (getenv("SK_SD_NO_UNION")) { fputs("strain_detect: --support-pairs compares the strains of a union table and SK_SD_NO_UNION is set: no pairs of the panel\n", err); return sd_drop(p, ns); }
+        }
+    }
     if (want_ps) {
         const char *ws = getenv("SK_WORLD_SIZE") ? getenv("SK_WORLD_SIZE") : getenv("WORLD_SIZE");
         if (!ps_file || !*ps_file) { fputs("strain_detect: --panel-share=FILE needs a file name: the table is one file for the whole panel\n", err); return sd_drop(p, ns); }
@@ -3696,6 +3820,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_rec.ms_mark = sd_rec.ms_hist = sd_rec.ms_gram = 0;
     sd_ps.path = want_ps ? ps_file : NULL;
     sd_ps.ms = 0; sd_ps.calls = 0;
+    sd_sup.on = want_su; sd_sup.pairs_path = want_sq ? sq_file : NULL; sd_sup.acc = NULL; sd_sup.ms_take = sd_sup.ms_finish = 0;
     sd_co.flush_rows = (env = getenv("SK_SD_CO_FLUSH_ROWS")) != NULL && atoll(env) >= 1 ? (uint64_t)atoll(env) : 1u << 20;
     sd_res_bytes = 0;
     sd_tc_open(tc_dir, err);
@@ -3801,11 +3926,14 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (sd_thresholds_open(&p[s], S || (ad && ad->o) ? NULL : th_file)) goto done;
     for (s = 0; want_sw && s < ns; s++)
         if (sd_sweep_open(&p[s], &swc[s], S || (ad && ad->o) ? NULL : sw_file)) goto done;
+    for (s = 0; want_su && s < ns; s++)
+        if (!(p[s].su_path = sd_table_path(p[s].o_path, S || (ad && ad->o) ? NULL : su_file, ".coverage_support"))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
     for (s = 0; want_rc && s < ns; s++)
         if (sd_recurrence_open(&p[s], S || (ad && ad->o) ? NULL : rc_file, S || (ad && ad->o) ? NULL : rp_file)) goto done;
     if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
     for (s = 0; s < ns; s++)
         if (sd_coverage_write(&p[s])) goto done;
+    if (sd_sup.acc && sd_support_write(p, ns)) goto done;
     status = 0;
 done:
     if (getenv("SK_SD_TIMING") && ns > 1)
@@ -3876,6 +4004,8 @@ done:
     if (getenv("SK_SD_TIMING") && cov_only && want_rc)
         fprintf(err, "strain_detect timing: recurrence on the device: marks %.3f ms (%u targets), finish: histogram %.3f ms, pairs %.3f ms\n",
                 sd_rec.ms_mark, sd_rec.T, sd_rec.ms_hist, sd_rec.ms_gram);
+    if (getenv("SK_SD_TIMING") && cov_only && want_su)
+        fprintf(err, "strain_detect timing: support on the device: takes %.3f ms (inside the folds above), finishes %.3f ms\n", sd_sup.ms_take, sd_sup.ms_finish);
     if (getenv("SK_SD_TIMING") && want_ps)
         fprintf(err, "strain_detect timing: panel share %.3f ms, %u call(s) of sk_union_share\n", sd_ps.ms, sd_ps.calls);
     if (getenv("SK_SD_RESULT_BYTES"))
@@ -3891,6 +4021,8 @@ done:
     sd_sw.on = 0;
     sd_rec.on = 0;
     sd_ps.path = NULL;
+    if (sd_sup.acc) sks_destroy(sd_sup.acc);
+    sd_sup.acc = NULL; sd_sup.on = 0; sd_sup.pairs_path = NULL;
     sd_sweep_drop(swc, nswc);
     for (s = 0; rgs && s < nrgs; s++) skh_regions_free(&rgs[s]);
     free(rgs);

@@ -50,6 +50,26 @@ int skc_parse_threshold_list(const char *text, int64_t *t /* SK_COVACC_THRESHOLD
 int skc_set_thresholds(skc_acc *a, const int64_t *t, uint32_t n);
 int skc_add_threshold_counts(skc_acc *a, const char *metagenome, const uint64_t *unique, const uint64_t *total, uint32_t n);
 int skc_report_thresholds(skc_acc *a, const char *hits_file_name, FILE *out, FILE *err);
+/* support on the host (sk_host_support.c; include/strainer_kmer.h has the rule): a run's numbers per sample and strain.
+ * sks_create: `group` consecutive strains form a group (1: no strain is compared with another).  sks_sample: the sample of a target's
+ * path, made at first sight; call it once per target, before anything is added for it (-1: out of memory).  It takes no lock (it
+ * counts the targets and may move the samples): no sks_merge or sks_add_device may be under way on another thread while it runs --
+ * strain_detect drains its lanes at the end of every target, before the next target's sks_sample.  The other calls lock.  A replayed run's
+ * emissions go into one sks_list per strain ({the run's pair number, lines, parts: 1 PE1 | 2 PE2}, pairs ascending) and
+ * sks_merge adds all of them; sks_add_device adds what sk_covacc_finish_target_support returned for n strains from `first` on. */
+typedef struct sks_em { uint32_t pair, lines, parts; } sks_em;
+typedef struct sks_list { sks_em *e; uint32_t n, cap; } sks_list;
+typedef struct sks_acc sks_acc;
+sks_acc *sks_create(uint32_t nstrains, uint32_t group);
+void sks_destroy(sks_acc *a);
+int sks_sample(sks_acc *a, const char *metagenome);
+int sks_list_push(sks_list *l, uint32_t pair, uint32_t lines, uint32_t parts);
+void sks_list_free(sks_list *l);
+int sks_merge(sks_acc *a, uint32_t sample, const sks_list *lists /* nstrains */);
+int sks_add_device(sks_acc *a, uint32_t sample, uint32_t first, uint32_t n, const uint64_t *pairs, const uint64_t *lines, const uint64_t *both,
+                   const uint64_t *shared /* n x n */, const uint64_t *lines_a /* n x n */);
+int sks_write_support(const sks_acc *a, uint32_t strain, FILE *f);
+int sks_write_pairs(const sks_acc *a, const char *const *names /* nstrains */, FILE *f);
 /* ... and the scrub sweep (strain_detect --coverage-scrub-sweep, coverage_depth --scrub-sweep; include/strainer_kmer.h has the rule and
  * the class file's lines).  skc_classes_read reads a class file (gzip or plain): 0, or 1 and in `why` what is wrong -- a missing or
  * unreadable file, a header line missing or out of place, a bad fraction list, a line that is not kmer<TAB>class with class 1..F, or
@@ -125,6 +145,8 @@ int sk_covacc_mark_timing_(sk_covacc *a, double *ms_mark);
 int sk_covacc_thresholds_timing_(sk_covacc *a, double *ms_thr);
 /* ... and of its class passes (sk_covacc_finish_target_classes) */
 int sk_covacc_classes_timing_(sk_covacc *a, double *ms_cls);
+/* ... and of support: the takes inside the folds (a part of ms_fold) and the copies home (sk_covacc_finish_target_support) */
+int sk_covacc_support_timing_(sk_covacc *a, double *ms_take, double *ms_finish);
 /* The recurrence engine's planes (sk_recur.hip), for the feeders that set bits with kernels of their own (sk_covacc.hip,
  * sk_cover.hip): plane `sample` of member m begins at d_planes + sample * words + word_base[m] and holds (nbits[m] + 63) / 64
  * words; a feeder sets no bit at or above nbits[m] and synchronises before the engine's next call. */

@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     "sk_covacc_set_thresholds", "sk_covacc_add_rows_hits", "sk_covacc_finish_target_thresholds", "sk_distinct_thresholds",
     "sk_filter_classes_joint", "sk_filter_classes_above", "skh_scrub_filter_resident_sweep",
     "sk_covacc_set_classes", "sk_covacc_finish_target_classes", "sk_distinct_classes",
+    "sk_covacc_set_support", "sk_covacc_finish_target_support",
 ]
 
 
@@ -854,6 +855,11 @@ lib.sk_distinct_thresholds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_v
 lib.sk_covacc_set_classes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
 lib.sk_covacc_finish_target_classes.argtypes = [C.c_void_p] * 4
 lib.sk_distinct_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+SK_COVACC_SUPPORT_MEMBERS_MAX = 1024
+lib.sk_covacc_set_support.argtypes = [C.c_void_p, C.c_int]
+lib.sk_covacc_finish_target_support.argtypes = [C.c_void_p] * 6
+lib.sk_covacc_timing_.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+lib.sk_covacc_support_timing_.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
 
 
 def regions_from_file(path, window=100000):
@@ -1286,6 +1292,34 @@ class CoverageAcc:
             per.append((ru[at: at + n + 1].copy(), rt[at: at + n + 1].copy()))
             at += n + 1
         return uq, tot, spec, deep, per
+
+    def set_support(self, on=True):
+        """sk_covacc_set_support: from here on every add() also counts the read pairs behind the numbers (off after create)"""
+        self._ctx._ck(lib.sk_covacc_set_support(self._h, int(bool(on))))
+
+    def finish_target_support(self):
+        """sk_covacc_finish_target_support: (supporting_pairs[nmembers], lines[nmembers], both_mates[nmembers],
+        shared_pairs[nmembers, nmembers], lines_a[nmembers, nmembers]) of the folds since the last call, as uint64 arrays; the diagonal
+        of the two matrices holds the exclusive pairs and their lines; everything is zero afterwards.  SKError (SK_E_STATE) while
+        support is off."""
+        nm = len(self.nrows)
+        pairs, lines, both = (np.zeros(nm, dtype=np.uint64) for _ in range(3))
+        shared, lines_a = np.zeros((nm, nm), dtype=np.uint64), np.zeros((nm, nm), dtype=np.uint64)
+        self._ctx._ck(lib.sk_covacc_finish_target_support(self._h, pairs.ctypes.data, lines.ctypes.data, both.ctypes.data,
+                                                          shared.ctypes.data, lines_a.ctypes.data))
+        return pairs, lines, both, shared, lines_a
+
+    def timing(self, on=True):
+        """sk_covacc_timing_: start the device clocks (on) and return (ms in folds, ms in sweeps) so far"""
+        f, w = C.c_double(0), C.c_double(0)
+        self._ctx._ck(lib.sk_covacc_timing_(self._h, int(bool(on)), C.byref(f), C.byref(w)))
+        return f.value, w.value
+
+    def support_timing(self):
+        """sk_covacc_support_timing_: (ms in the takes inside the folds, ms in finish_target_support), kept while timing() is on"""
+        t, f = C.c_double(0), C.c_double(0)
+        self._ctx._ck(lib.sk_covacc_support_timing_(self._h, C.byref(t), C.byref(f)))
+        return t.value, f.value
 
     def set_recurrence(self, member, ctx, type_col=0, informative_value=2):
         """sk_covacc_set_recurrence: rank member's informative rows (those whose counter in type_col of ctx's table equals

@@ -29,6 +29,11 @@ apart.
     python tools/coverage_only_bench.py --recurrence --rounds 5 --parent-exe PATH [--out profiles/coverage_recurrence_bench.txt]
     python tools/coverage_only_bench.py --thresholds [--threshold-list 0,1,2] --rounds 3 --parent-exe PATH [--out profiles/coverage_thresholds_bench.txt]
     python tools/coverage_only_bench.py --scrub-sweep --rounds 3 --parent-exe PATH [--out profiles/coverage_scrub_sweep_bench.txt]
+    python tools/coverage_only_bench.py --support [--pairs] --rounds 3 --parent-exe PATH [--out profiles/coverage_support_bench.txt]
+
+--support measures --coverage-support (--pairs: with --support-pairs=FILE) like --thresholds: the parent's plain --coverage-only runs in
+turn with this build's plain runs and its runs with the flag; each line with the flag also carries the device time of the takes (a
+part of the folds) and of the finishes.
 
 --scrub-sweep measures --coverage-scrub-sweep like --thresholds (class files of 8 fractions are made up for the strains' lists: the
 class pass does not care where the classes come from), then step 2 alone at 8 fractions against 1 (kmer_scrub_filter over one
@@ -60,6 +65,7 @@ PASS = re.compile(rb"strain_detect timing: setup ([0-9.]+) s,.*?total before clo
 ACC = re.compile(rb"coverage accumulators on the device: folds ([0-9.]+) ms, target sweeps ([0-9.]+) ms")
 REC = re.compile(rb"recurrence on the device: marks ([0-9.]+) ms \((\d+) targets\), finish: histogram ([0-9.]+) ms, pairs ([0-9.]+) ms")
 THR = re.compile(rb"thresholds on the device: (\d+) thresholds, finishing passes ([0-9.]+) ms")
+SUPT = re.compile(rb"support on the device: takes ([0-9.]+) ms \(inside the folds above\), finishes ([0-9.]+) ms")
 SWP = re.compile(rb"scrub sweep on the device: class passes ([0-9.]+) ms")
 SWEEP_LIST = "0.5,0.4,0.3,0.2,0.1,0.05,0.02,0.01"
 BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
@@ -81,7 +87,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     for s in range(ns):
         for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum",
                   f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs", f"out{s}.gz.coverage_thresholds",
-                  f"out{s}.gz.coverage_scrub_sweep"):
+                  f"out{s}.gz.coverage_scrub_sweep", f"out{s}.gz.coverage_support"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -102,7 +108,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             h.update(f.read())
     hr = hashlib.md5()
     for s in range(ns):
-        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds", "coverage_scrub_sweep"):    # (the table beside the coverage table, whichever the run wrote)
+        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds", "coverage_scrub_sweep", "coverage_support"):    # (the table beside the coverage table, whichever the run wrote)
             if os.path.exists(os.path.join(cwd, f"out{s}.gz.{ext}")):
                 with open(os.path.join(cwd, f"out{s}.gz.{ext}"), "rb") as f:
                     hr.update(f.read())
@@ -112,7 +118,8 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     rc = REC.search(p.stderr)
     th = THR.search(p.stderr)
     sw = SWP.search(p.stderr)
-    return dict(cls=float(sw.group(1)) if sw else float("nan"), thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
+    su = SUPT.search(p.stderr)
+    return dict(take=float(su.group(1)) if su else float("nan"), supfin=float(su.group(2)) if su else float("nan"), cls=float(sw.group(1)) if sw else float("nan"), thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
                 fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
                 passed=float(m.group(2)) - float(m.group(1)) if m else float("nan"),
                 d2h=int(b.group(1)) if b else -1, dev=int(b.group(2)) if b else -1, replayed=int(b.group(3)) if b else -1)
@@ -150,7 +157,7 @@ def regions_case(say, args, env, tmp, ns, kind, argv):
         say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
-def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False, sweep=False):
+def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False, sweep=False, support=False):
     """--coverage-only without and with --coverage-spectrum (recurrence: --coverage-recurrence --recurrence-pairs; thresholds:
     --coverage-thresholds [--threshold-list ..]), alternating; the parent build's plain --coverage-only behind them -- with
     thresholds: in turn with them, round by round -- and the new build's medians set against the parent's"""
@@ -165,6 +172,10 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
     if sweep:                                                # (measured like the thresholds: the parent's runs in turn, folds compared too)
         with_sp = ["--coverage-only", "--coverage-scrub-sweep"]
         word, label = "scrub sweep", "... --coverage-scrub-sweep"
+        thresholds = True
+    if support:                                              # (measured like the thresholds: the parent's runs in turn, folds compared too)
+        with_sp = ["--coverage-only", "--coverage-support"] + (["--support-pairs=" + os.path.join(tmp, "support_pairs.tsv")] if args.pairs else [])
+        word, label = "support", "... --coverage-support" + (" --support-pairs=FILE" if args.pairs else "")
         thresholds = True
     res = {"plain": [], "spectrum": [], "parent": []}
     md5 = md5s = None
@@ -193,7 +204,10 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
         if rs:
             say(f"    {names[tag]}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; accumulators on the device: folds "
                 f"{row(rs, 'fold', '.2f')} ms, target sweeps {row(rs, 'sweep', '.3f')} ms; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
-            if sweep and tag == "spectrum":
+            if support and tag == "spectrum":
+                say(f"        support on the device: takes of all folds {row(rs, 'take', '.3f')} ms (a part of the folds above), finishes of all targets "
+                    f"{row(rs, 'supfin', '.3f')} ms")
+            elif sweep and tag == "spectrum":
                 say(f"        scrub sweep on the device: class passes of all targets {row(rs, 'cls', '.3f')} ms")
             elif thresholds and tag == "spectrum":
                 say(f"        thresholds on the device: finishing passes of all targets {row(rs, 'thr', '.3f')} ms (the folds above classify as well)")
@@ -283,6 +297,8 @@ def main():
     ap.add_argument("--thresholds", action="store_true", help="measure --coverage-thresholds, the parent build's runs in turn with this build's")
     ap.add_argument("--threshold-list", default=None, help="... with this --threshold-list (default: the program's)")
     ap.add_argument("--scrub-sweep", action="store_true", help="measure --coverage-scrub-sweep, step 2 at 8 fractions and the fused form")
+    ap.add_argument("--support", action="store_true", help="measure --coverage-support, the parent build's runs in turn with this build's")
+    ap.add_argument("--pairs", action="store_true", help="... with --support-pairs=FILE as well")
     ap.add_argument("--stderr-dir", default=None, help="keep every run's stderr (the SK_SD_TIMING lines) in this directory")
     ap.add_argument("--out", default=None)
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -347,8 +363,8 @@ def main():
             for ns in counts:
                 for kind, lst in lists.items():
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
-                    if args.spectrum is not None or args.recurrence or args.thresholds or args.scrub_sweep:
-                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds, args.scrub_sweep)
+                    if args.spectrum is not None or args.recurrence or args.thresholds or args.scrub_sweep or args.support:
+                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds, args.scrub_sweep, args.support)
                         continue
                     if args.regions is not None:
                         regions_case(say, args, env, tmp, ns, kind, argv)
