@@ -347,6 +347,40 @@ int  sk_union_counts_fold(sk_union *u, uint32_t ucol, uint32_t member_col, uint3
  * out[0], out[1], out[2].  Strains of different unions are compared by sk_union_share(u[g], u[h], ..) for g != h. */
 int  sk_union_share(sk_union *a, sk_union *b_or_null, uint64_t *out /* 3 * SK_UNION_MAX * SK_UNION_MAX */);
 
+/* The BACKGROUND of step 4's numbers (new: strain_detect --coverage-background; no counterpart in the reference, whose advice is to
+ * decide presence "based on the frequency of the rare kmers in the metagenome" -- the frequency to expect depends on how deep the
+ * organism is, which only ALL of the strain's k-mers show).  The rule, for strain s and target t:
+ *   c[row] = the count step 1's scan (kmer_scrub_count) would give the row with t's files as its list: one per window of any record
+ *   of any file of the target whose canonical 31-mer is the row's key.  The window rules are the COUNT scan's, unchanged (case
+ *   folding, N, other bytes through the byte-string kernel); pairing, mates and --min-kmer-hits play no part; a record shorter than
+ *   k has no window.
+ *   A row is INFORMATIVE when its type column holds the informative value after -a/-g (exactly the set the TALLY scan uses),
+ *   otherwise it is BACKGROUND.
+ *   Per strain, target and class: kmers = rows of the class, covered_kmers = those with c > 0, total_hits = the sum of c (u64);
+ *   with a spectrum, per depth d = 0..D the rows with c == d, and the rows and hits above D.
+ * sk_scan_batch: a COUNT scan of batch b as it lies on the device (bytes, the packed form, or filled from text) into column `col` of
+ *   ctx -- a strain's context, or sk_union_context(u) with count columns.  Ordered behind the batch's upload, on ctx's stream (never on
+ *   the second scan lane sk_scan_device[_packed] may take), with the kernels those two launch; counts equal sk_scan_stream of the same byte stream, bit for bit.  It returns at
+ *   once: the batch may be refilled only after the scan is done (sk_sync(ctx), or anything else that waits for ctx's stream).
+ *   Refused as sk_tally_launch refuses: a batch on another device (SK_E_ARG), an empty or declined batch (SK_E_STATE).
+ * sk_background_finish: one sweep over column `col` of ctx, each row classed by column type_col; then the column is zero again (a
+ *   second call returns kmers and zeros).  out[SK_BACKGROUND_WORDS(max_depth)], u64: for class 0 (informative) and then class 1
+ *   (background) the block {kmers, covered_kmers, total_hits, rows above D, hits above D, rows at depth 0, 1, .., D}.
+ *   max_depth D <= SK_BACKGROUND_MAX_DEPTH (SK_E_ARG above); col == type_col is SK_E_ARG.  Synchronous.
+ * sk_union_background_finish: the same for every member of a union from ONE count column of its context (the column every batch
+ *   of the target went into with one sk_scan_batch each): every key's count is gathered on its slot row, then one sweep over the
+ *   union's slots -- each distinct key once -- gives the count to every member that holds the key, in the class that member's bit
+ *   of the informative mask names.  out[members][SK_BACKGROUND_WORDS(max_depth)].  The column is zero afterwards.  Nothing is
+ *   folded into the members' own columns.  "Informative" is what the union's snapshot holds (sk_union_create).  Synchronous. */
+#define SK_BACKGROUND_MAX_DEPTH 255u
+#define SK_BACKGROUND_HEAD 5u                                 /* kmers, covered_kmers, total_hits, deep rows, deep hits */
+#define SK_BACKGROUND_CLASS_WORDS(D) (SK_BACKGROUND_HEAD + (D) + 1u)
+#define SK_BACKGROUND_WORDS(D) (2u * SK_BACKGROUND_CLASS_WORDS(D))
+int  sk_scan_batch(sk_ctx *ctx, const sk_batch *b, uint32_t col);
+int  sk_background_finish(sk_ctx *ctx, uint32_t col, uint32_t type_col, uint32_t informative_value, uint32_t max_depth,
+                          uint64_t *out /* SK_BACKGROUND_WORDS(max_depth) */);
+int  sk_union_background_finish(sk_union *u, uint32_t ucol, uint32_t max_depth, uint64_t *out /* members x SK_BACKGROUND_WORDS(max_depth) */);
+
 /* Wait for all queued work of the context. */
 int sk_sync(sk_ctx *ctx);
 

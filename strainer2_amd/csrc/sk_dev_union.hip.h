@@ -320,3 +320,77 @@ __global__ void __launch_bounds__(256) sk_union_share_sweep(const sk_u4 *__restr
         if (v) atomicAdd(out + c, (unsigned long long)v);
     }
 }
+
+// ---- the background of step 4's numbers on a union (sk_union_background_finish; include/strainer_kmer.h has the rule).  After
+// sk_union_fold_canon a key's count stands on its slot row; one sweep over the union's SLOTS then sees each distinct key once, with
+// its masks in hand (the shape of sk_union_share_sweep), and gives the count to every member of the hold mask, in the class its bit
+// of the informative mask names (class 0 informative, 1 background).  Counted in LDS first, per (member, class): D + 2 u32 cells --
+// depths 0..D and the rows above D -- then two u64, the hits above D and all hits; the non-zero cells go out once per workgroup with
+// 64-bit atomics.  32 members at D = 255 are 32 x 2 x 257 u32 + 32 x 2 x 2 u64 = 66 KB, two workgroups per CU on 160 KiB: the host
+// sizes the dynamic LDS to the union's members and the call's D.
+// COUNT_KEYS (the first call on a union): the rows of every (member, class), whatever their count -- one uniform round per member
+// with two ballots, so that the 64 keys of a wave, which related strains nearly all share, cost two LDS adds a member and not 64.
+// Later calls take a key with count 0 for granted (rows at depth 0 = the class's rows - its covered rows, on the host): in a
+// metagenome that does not hold the strains the sweep then makes no LDS add at all.
+// out: per member SK_BACKGROUND_WORDS(D) u64 in sk_background_finish's layout; this kernel adds to total_hits, the two deep
+// cells and the depth cells 1..D, and with COUNT_KEYS to nothing else but keys[member * 2 + class].
+#define SK_UBG_BLOCKS 512u                                          // at most this many workgroups of 256: two per CU
+template <bool COUNT_KEYS>
+__global__ void __launch_bounds__(256) sk_union_background_sweep(const sk_u4 *__restrict__ slots, uint64_t nslots, const uint2 *__restrict__ umask,
+                                                                 const uint32_t *__restrict__ ucol, uint32_t nrows, uint32_t ns, uint32_t D,
+                                                                 unsigned long long *__restrict__ out, unsigned long long *__restrict__ keys)
+{
+    extern __shared__ unsigned long long ubg_lds[];                 // [ns * 2 * 2] u64, then [ns * 2 * (D + 2)] u32
+    const uint32_t cells = ns * 2u, cw = D + 2u;
+    unsigned long long *const wide = ubg_lds;                       // wide[2 * cell] hits above D, wide[2 * cell + 1] all hits
+    uint32_t *const bins = (uint32_t *)(ubg_lds + 2u * cells);
+    for (uint32_t i = threadIdx.x; i < 2u * cells; i += 256u) wide[i] = 0ull;
+    for (uint32_t i = threadIdx.x; i < cells * cw; i += 256u) bins[i] = 0u;
+    __syncthreads();
+    const uint32_t live = ns >= 32u ? 0xFFFFFFFFu : (1u << ns) - 1u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < nslots; i0 += stride) {       // (uniform: every lane makes the ballots below)
+        const uint64_t i = i0 + threadIdx.x;
+        uint2 m = make_uint2(0u, 0u);
+        uint32_t v = 0u;
+        if (i < nslots) {
+            const sk_u4 e = slots[i];
+            if (sk_slot_key(e) != SK_EMPTY64 && e.z < nrows) { m = umask[e.z]; m.x &= live; v = ucol[e.z]; }
+        }
+        if (COUNT_KEYS)
+            for (uint32_t s = 0; s < ns; s++) {
+                const bool has = (m.x >> s) & 1u, inf = (m.y >> s) & 1u;
+                const unsigned long long bi = __ballot(has && inf), bb = __ballot(has && !inf);
+                if (lane == 0u) {
+                    if (bi) atomicAdd(&bins[(s * 2u) * cw], (uint32_t)__popcll(bi));
+                    if (bb) atomicAdd(&bins[(s * 2u + 1u) * cw], (uint32_t)__popcll(bb));
+                }
+            }
+        if (!v) continue;
+        for (uint32_t x = m.x; x; x &= x - 1u) {
+            const uint32_t s = (uint32_t)__builtin_ctz(x), cell = s * 2u + (((m.y >> s) & 1u) ? 0u : 1u);
+            atomicAdd(&bins[cell * cw + (v <= D ? v : D + 1u)], 1u);
+            if (v > D) atomicAdd(&wide[2u * cell], (unsigned long long)v);
+            atomicAdd(&wide[2u * cell + 1u], (unsigned long long)v);
+        }
+    }
+    __syncthreads();
+    const uint32_t words = 2u * (5u + D + 1u), cwords = 5u + D + 1u;      // (SK_BACKGROUND_WORDS, SK_BACKGROUND_CLASS_WORDS)
+    for (uint32_t i = threadIdx.x; i < cells * cw; i += 256u) {
+        const uint32_t n = bins[i];
+        if (!n) continue;
+        const uint32_t cell = i / cw, d = i - cell * cw;
+        unsigned long long *const o = out + (size_t)(cell >> 1) * words + (size_t)(cell & 1u) * cwords;
+        if (d == 0u) { if (COUNT_KEYS) atomicAdd(keys + cell, (unsigned long long)n); }
+        else if (d <= D) atomicAdd(o + 5u + d, (unsigned long long)n);
+        else atomicAdd(o + 3u, (unsigned long long)n);
+    }
+    for (uint32_t i = threadIdx.x; i < 2u * cells; i += 256u) {
+        const unsigned long long n = wide[i];
+        if (!n) continue;
+        const uint32_t cell = i >> 1;
+        unsigned long long *const o = out + (size_t)(cell >> 1) * words + (size_t)(cell & 1u) * cwords;
+        atomicAdd(o + ((i & 1u) ? 2u : 4u), n);
+    }
+}

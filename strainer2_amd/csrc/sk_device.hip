@@ -804,7 +804,7 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
     memset(&sink, 0, sizeof sink);
     if (tally_sink) sink = *tally_sink;
     else {
-        c->infbits_ok = false;                                 // (a column is about to change)
+        if (col == c->infbits_col) c->infbits_ok = false;      // (the column the bitmap was made from is about to change)
         sink.counts = c->d_counts + (size_t)col * c->nrows;
         sink.diff = c->d_diff;
         if (tv.text2 && c->diff_col != (int)col) {            // the difference array serves one column at a time
@@ -1260,6 +1260,9 @@ struct sk_union {
     std::vector<sk_ctx *> mem;
     std::vector<uint32_t> base;
     uint32_t *d_canon;               // [rows] NULL until count columns were set up
+    // sk_union_background_finish: the rows of every (member, class), counted by its first call (the masks are a snapshot)
+    uint64_t  bg_keys[2 * SK_UNION_MAX];
+    bool      bg_keys_ok;
 };
 
 extern "C" void sk_union_destroy(sk_union *u)
@@ -1300,6 +1303,7 @@ extern "C" int sk_union_create(sk_ctx *const *members, uint32_t n, uint32_t type
     if (!u) return SK_E_NOMEM;
     u->uc = NULL; u->n = n; u->d_ukeys = NULL; u->d_umask = NULL; u->d_members = NULL;
     u->d_tally = u->d_flag = u->d_raw = NULL; u->tally_cap = u->flag_cap = u->raw_cap = 0; u->d_cnt = NULL; u->d_canon = NULL;
+    u->bg_keys_ok = false;
     int rc = sk_ctx_create(&u->uc, first->device);
     if (rc != SK_OK) { delete u; return rc; }
     sk_ctx *c = u->uc;
@@ -1665,6 +1669,94 @@ extern "C" int sk_union_share(sk_union *a, sk_union *b, uint64_t *out)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d_out);
     if (e != hipSuccess) { (void)hipGetLastError(); return sk_fail(c, SK_E_HIP, "sk_union_share failed: %s", hipGetErrorString(e)); }
+    return SK_OK;
+}
+
+// The background of step 4's numbers for every member of a union (include/strainer_kmer.h has the rule): the counts of column ucol
+// gathered on the keys' slot rows (sk_union_fold_canon, as sk_union_counts_fold begins), ONE sweep over the slots, the column
+// zeroed.  Nothing here is proportional to members x rows: no member column is touched.  The device result is allocated for the
+// call and freed again, as sk_union_share does.
+extern "C" int sk_union_background_finish(sk_union *u, uint32_t ucol, uint32_t max_depth, uint64_t *out)
+{
+    if (!u || !out) return SK_E_ARG;
+    sk_ctx *c = u->uc;
+    if (!c->d_counts || !u->d_canon) return sk_fail(c, SK_E_STATE, "the union has no count columns (sk_union_count_enable)");
+    if (ucol >= c->ncols) return sk_fail(c, SK_E_ARG, "union column %u out of range", ucol);
+    if (max_depth > SK_BACKGROUND_MAX_DEPTH) return sk_fail(c, SK_E_ARG, "depth %u above %u", max_depth, SK_BACKGROUND_MAX_DEPTH);
+    SK_HIP(c, hipSetDevice(c->device));
+    { int rc = sk_diff_flush(c); if (rc) return rc; }
+    const uint32_t D = max_depth, ns = u->n, nrows = c->nrows, words = SK_BACKGROUND_WORDS(D), cwords = SK_BACKGROUND_CLASS_WORDS(D);
+    const size_t nout = (size_t)ns * words, nall = nout + 2u * SK_UNION_MAX;          // the members' blocks, then keys[member * 2 + class]
+    const size_t lds = (size_t)ns * 2u * 2u * sizeof(unsigned long long) + (size_t)ns * 2u * (D + 2u) * sizeof(uint32_t);
+    const bool count_keys = !u->bg_keys_ok;
+    const void *fn = count_keys ? (const void *)sk_union_background_sweep<true> : (const void *)sk_union_background_sweep<false>;
+    SK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    std::vector<unsigned long long> h(nall);
+    unsigned long long *d_out = NULL;
+    SK_UNION_MALLOC(c, hipMalloc((void **)&d_out, nall * sizeof(unsigned long long)));
+    uint32_t *const uc = c->d_counts + (size_t)ucol * nrows;
+    const uint64_t nslots = (uint64_t)1 << c->slots_log2;
+    uint64_t gx = (nslots + 255u) / 256u;
+    if (gx > SK_UBG_BLOCKS) gx = SK_UBG_BLOCKS;
+    hipError_t e = hipMemsetAsync(d_out, 0, nall * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) {
+        if (nrows) hipLaunchKernelGGL(sk_union_fold_canon, dim3((nrows + 255) / 256), dim3(256), 0, c->stream, uc, (const uint32_t *)u->d_canon, nrows);
+        if (count_keys)
+            hipLaunchKernelGGL(sk_union_background_sweep<true>, dim3((unsigned)gx), dim3(256), lds, c->stream, (const sk_u4 *)c->d_keys, nslots,
+                               (const uint2 *)u->d_umask, (const uint32_t *)uc, nrows, ns, D, d_out, d_out + nout);
+        else
+            hipLaunchKernelGGL(sk_union_background_sweep<false>, dim3((unsigned)gx), dim3(256), lds, c->stream, (const sk_u4 *)c->d_keys, nslots,
+                               (const uint2 *)u->d_umask, (const uint32_t *)uc, nrows, ns, D, d_out, d_out + nout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(uc, 0, (size_t)nrows * 4, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, nall * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) { (void)hipGetLastError(); return sk_fail(c, SK_E_HIP, "sk_union_background_finish failed: %s", hipGetErrorString(e)); }
+    if (count_keys) {
+        for (uint32_t i = 0; i < 2u * SK_UNION_MAX; i++) u->bg_keys[i] = h[nout + i];
+        u->bg_keys_ok = true;
+    }
+    for (uint32_t cell = 0; cell < 2u * ns; cell++) {         // what the sweep leaves to the host: a class's rows, and those at depth 0
+        unsigned long long *const o = h.data() + (size_t)(cell >> 1) * words + (size_t)(cell & 1u) * cwords;
+        unsigned long long covered = o[3];
+        for (uint32_t d = 1; d <= D; d++) covered += o[SK_BACKGROUND_HEAD + d];
+        o[0] = u->bg_keys[cell]; o[1] = covered; o[SK_BACKGROUND_HEAD] = o[0] - covered;
+    }
+    for (size_t i = 0; i < nout; i++) out[i] = h[i];
+    return SK_OK;
+}
+
+// A COUNT scan of a batch as it lies on the device (include/strainer_kmer.h): the kernels sk_scan_device[_packed] launch, behind the
+// batch's upload, on the context's stream -- where the TALLY launch on the same batch runs, so that whatever waits for the one
+// (sk_tally_collect*, sk_sync) has waited for the other before the batch is refilled.  sk_launch_scan gets what sk_scan_device[_packed]
+// pass but for ONE argument: lane_scan stays false.  Those two let back-to-back scans take the context's two lanes in turn; a scan
+// on lane 1 would run beside the context's stream, not behind the batch's `ready` event and the TALLY launch that were put there.
+extern "C" int sk_scan_batch(sk_ctx *c, const sk_batch *b, uint32_t col)
+{
+    if (!c || !b) return SK_E_ARG;
+    if (!c->d_keys) return sk_fail(c, SK_E_STATE, "no table loaded");
+    if (!c->d_counts) return sk_fail(c, SK_E_STATE, "no count columns (a union's context needs sk_union_count_enable)");
+    if (col >= c->ncols) return sk_fail(c, SK_E_ARG, "column %u out of range", col);
+    if (b->owner->device != c->device) return sk_fail(c, SK_E_ARG, "batch lives on another device");
+    if (b->nrec == 0) return sk_fail(c, SK_E_STATE, "empty batch");
+    SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }
+    SK_HIP(c, hipStreamWaitEvent(c->stream, b->ready, 0));
+    return sk_launch_scan(c, (const uint8_t *)b->d_stream, b->nbytes, 0, col, NULL,
+                          b->packed ? (const uint8_t *)b->d_stream + ((b->nbytes + 15u) >> 4) * 4u : NULL);
+}
+
+extern "C" int sk_background_view_(sk_ctx *c, uint32_t col, uint32_t type_col, sk_background_view *v)
+{
+    if (!c || !v) return SK_E_ARG;
+    if (!c->d_counts || col >= c->ncols || type_col >= c->ncols) return sk_fail(c, SK_E_ARG, "bad column");
+    if (col == type_col) return sk_fail(c, SK_E_ARG, "the count column is the type column");
+    SK_HIP(c, hipSetDevice(c->device));
+    { int rc = sk_diff_flush(c); if (rc) return rc; }
+    v->device = c->device; v->stream = (void *)c->stream; v->nrows = c->nrows;
+    v->d_col = c->d_counts + (size_t)col * c->nrows; v->d_type = c->d_counts + (size_t)type_col * c->nrows;
     return SK_OK;
 }
 

@@ -2486,6 +2486,12 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
         argv[j++] = argv[c];
     }
     argc = j;
+    for (c = 1; c < detect_argc; c++)                 /* (before anything is read: the resident table has no column for it) */
+        if (!strncmp(detect_argv[c], "--coverage-background", 21) && (detect_argv[c][21] == 0 || detect_argv[c][21] == '=')) {
+            fprintf(err, "kmer_scrub_count: --coverage-background does not go behind --detect: the resident table is loaded without its count column; "
+                         "run strain_detect on its own for it\n");
+            return 1;
+        }
     {   /* a list of fractions and --coverage-scrub-sweep behind --detect go together: step 3 reads the class file step 2 writes */
         int want_sw = 0;
         for (c = 1; c < detect_argc; c++)

@@ -306,6 +306,12 @@ static int sm_check_detect(int argc, char **argv, int *want_cov, int *want_sw, F
     const char *th_list = NULL;
     if (!v) return 1;
     for (c = 0; c < argc; c++) {
+        if (c > 0 && !strncmp(argv[c], "--coverage-background", 21) && (argv[c][21] == 0 || argv[c][21] == '=')) {
+            fprintf(err, "kmer_scrub_count: --coverage-background does not go behind --detect: the resident tables are loaded without its count column; "
+                         "run strain_detect on its own for it\n");
+            free(v);
+            return 1;
+        }
         if (c > 0 && !strncmp(argv[c], "--coverage-depth", 16) && (argv[c][16] == 0 || argv[c][16] == '=')) {
             if (argv[c][16] == '=') {
                 fprintf(err, "kmer_scrub_count: with -S, --coverage-depth takes no file name (each strain's table goes next to its hit list)\n");

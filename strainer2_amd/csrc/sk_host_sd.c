@@ -103,6 +103,7 @@ typedef struct {
     skh_regions rg; uint32_t *row_region; uint64_t *reg_inf; char *rg_path;
     char *sp_path;                             /* --coverage-spectrum: the table's path */
     char *rc_path, *rp_path;                   /* --coverage-recurrence, --recurrence-pairs: the tables' paths */
+    char *bg_path, *bgs_path; skb_table *bg;   /* --coverage-background, --background-spectrum: the tables' paths, the targets' blocks */
 } sd_prog;
 
 /* ---------------------------------------------------------------------------------------------
@@ -1471,6 +1472,30 @@ static void lanes_stop(void)
     L->n = 0;
 }
 
+/* --coverage-background [--background-spectrum] [--background-max D] (include/strainer_kmer.h has the rule): every table above slices
+ * the strain's INFORMATIVE k-mers; this one counts all of them.  With the flag a strain's table has one more column, SD_BGCOUNT, and
+ * every batch of every file of a target is COUNT-scanned as it lies on the device (sk_scan_batch) right behind its TALLY launch, on
+ * the same stream -- into that column strain by strain, or ONCE per union table into a count column of the union's own context.  The
+ * TALLY scan cannot give this: it keeps the "all hits" count per read, not per row.  Where a target ends one sweep per strain or per
+ * union (sk_background_finish, sk_union_background_finish) turns the column into the target's block and leaves it zero.  The entries
+ * are weak, as the accumulators' are: the host-only test builds link this file without them, and there the flag fails the run. */
+#pragma weak sk_scan_batch
+#pragma weak sk_scan_timing
+#pragma weak sk_union_scan_timing
+#pragma weak sk_background_finish
+#pragma weak sk_union_background_finish
+#pragma weak sk_union_count_enable
+#pragma weak sk_union_context
+#pragma weak skb_create
+#pragma weak skb_destroy
+#pragma weak skb_add
+#pragma weak skb_write
+#pragma weak skb_write_spectrum
+enum { SD_BGCOUNT = SD_NCOLS };
+static struct { int on; uint32_t max; int failed; double ms_sweep; uint64_t scans; } sd_bg;
+static uint32_t sd_ncols(void) { return sd_bg.on ? SD_NCOLS + 1u : SD_NCOLS; }
+static const char *sd_bg_error;            /* the text of the context (a strain's, a union's) whose sweep failed */
+
 /* Many strains on one device: one union table per group of up to SK_UNION_MAX strains (sk_union_*), so that a batch is
  * scanned once per group instead of once per strain (BASELINE configs[4]: 32 strains per GPU).  Built by sd_run when the
  * strains are open and flagged; a strain the union cannot hold (byte-string keys, no text stage), SK_SD_NO_UNION=1, or a
@@ -1509,6 +1534,7 @@ static void sd_unions_open(sd_prog *p, uint32_t ns)
         int rc;
         for (k = 0; k < n; k++) m[k] = p[a + k].ctx;
         rc = sk_union_create(m, n, SD_TYPE, SD_INFORMATIVE, &sd_un.u[g]);
+        if (rc == SK_OK && sd_bg.on && (rc = sk_union_count_enable(sd_un.u[g], 1)) != SK_OK) { sk_union_destroy(sd_un.u[g]); sd_un.u[g] = NULL; }
         if (rc != SK_OK) {
             if (getenv("SK_SD_TIMING")) fprintf(p[0].err, "strain_detect: no union table (%s: %s): strain by strain\n", sk_strerror(rc), sk_last_error(m[0]));
             sd_un.n = g;
@@ -1987,21 +2013,37 @@ static int co_materialise(sd_prog *p, uint32_t ns, sd_chunk *c)
 }
 
 /* start the scans of one uploaded chunk: against every union table, or strain by strain (they overlap on the devices) */
+/* --coverage-background: the COUNT scans of the chunk, each on the stream of the TALLY launch just made on the same batch and so
+ * done when that launch has been collected -- before the batch is refilled.  Made once per chunk, here and nowhere else: a launch
+ * that is repeated with more room for its log (sd_collect, co_collect) counts nothing again.  A failure stays: a chunk whose count
+ * scans started only in part is never launched again as if nothing had been counted. */
+static int sd_background_scans(sd_prog *p, uint32_t ns, sk_batch **batches)
+{
+    uint32_t g, s;
+    if (sd_bg.failed) return sd_bg.failed;
+    for (g = 0; g < sd_un.n && !sd_bg.failed; g++, sd_bg.scans++)
+        sd_bg.failed = sk_scan_batch(sk_union_context(sd_un.u[g]), batches[sd_dev_of_strain(g * sd_group)], 0);
+    for (s = 0; !sd_un.n && s < ns && !sd_bg.failed; s++, sd_bg.scans++)
+        sd_bg.failed = sk_scan_batch(p[s].ctx, batches[sd_dev_of_strain(s)], SD_BGCOUNT);
+    return sd_bg.failed;
+}
+
 static int sd_launch(sd_prog *p, uint32_t ns, sk_batch **batches)
 {
     uint32_t g, s;
     int rc;
+    if (sd_bg.on && sd_bg.failed) return sd_bg.failed;
     if (sd_un.n) {
         for (g = 0; g < sd_un.n; g++)
             if ((rc = sd_co.acc ? sk_union_tally_launch_ex(sd_un.u[g], batches[sd_dev_of_strain(g * sd_group)], sd_un.hcap[g], 1)
                                 : sk_union_tally_launch(sd_un.u[g], batches[sd_dev_of_strain(g * sd_group)], sd_un.hcap[g])) != SK_OK) return rc;
-        return SK_OK;
+        return sd_bg.on ? sd_background_scans(p, ns, batches) : SK_OK;
     }
     for (s = 0; s < ns; s++) {
         if (p[s].hitcap == 0) { p[s].hitcap = 1u << 16; p[s].hitbuf = (sk_hit *)malloc((size_t)p[s].hitcap * sizeof(sk_hit)); }
         if ((rc = sk_tally_launch(p[s].ctx, batches[sd_dev_of_strain(s)], SD_TYPE, SD_INFORMATIVE, p[s].hitcap)) != SK_OK) return rc;
     }
-    return SK_OK;
+    return sd_bg.on ? sd_background_scans(p, ns, batches) : SK_OK;
 }
 
 /* room for n more records and m more log entries in the chunk's own result arrays */
@@ -2458,6 +2500,35 @@ static int post_replay(const char *f1, sd_chunk *ca, uint32_t a0, sd_chunk *cb, 
  * tallies, the totals and the "PE2 ended early" failure -- are the same for all strains and are handled
  * here, run by run; the per-strain part is sd_replay_run.  A read shorter than k refreshes nothing, so it
  * re-uses (and may re-emit) the previous read's tallies and sequence, as in the reference. */
+/* --coverage-background, where a target ends: the count column(s) of every strain or union, swept into the target's block per
+ * strain and left zero for the next target.  Every batch of the target has been collected by now, so every count scan is done. */
+static int sd_background_target(sd_prog *p, uint32_t ns, const char *f1)
+{
+    const uint32_t words = SK_BACKGROUND_WORDS(sd_bg.max);
+    uint64_t *blk = (uint64_t *)malloc((size_t)SK_UNION_MAX * words * sizeof *blk);
+    const double t0 = now_s();
+    uint32_t g, s, m;
+    int rc = blk ? SK_OK : SK_E_NOMEM;
+    sd_bg_error = NULL;
+    if (rc == SK_OK && sd_bg.failed) rc = sd_bg.failed;
+    pthread_mutex_lock(&sd_dev_mu);
+    for (g = 0; g < sd_un.n && rc == SK_OK; g++) {
+        const uint32_t a = g * sd_group, n = sk_union_members(sd_un.u[g]);
+        rc = sk_union_background_finish(sd_un.u[g], 0, sd_bg.max, blk);
+        if (rc != SK_OK) sd_bg_error = sk_union_last_error(sd_un.u[g]);
+        for (m = 0; m < n && rc == SK_OK; m++) if (skb_add(p[a + m].bg, f1, blk + (size_t)m * words)) rc = SK_E_NOMEM;
+    }
+    for (s = 0; !sd_un.n && s < ns && rc == SK_OK; s++) {
+        rc = sk_background_finish(p[s].ctx, SD_BGCOUNT, SD_TYPE, SD_INFORMATIVE, sd_bg.max, blk);
+        if (rc != SK_OK) sd_bg_error = sk_last_error(p[s].ctx);
+        if (rc == SK_OK && skb_add(p[s].bg, f1, blk)) rc = SK_E_NOMEM;
+    }
+    pthread_mutex_unlock(&sd_dev_mu);
+    free(blk);
+    sd_bg.ms_sweep += 1e3 * (now_s() - t0);
+    return rc;
+}
+
 static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, const char *f1, const char *f2, int mode)
 {
     sd_stream A, B;
@@ -2547,6 +2618,12 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
             A.ci += n * astep;
             if (mode == SD_PE && cb) B.ci += n;
         }
+    }
+    /* --coverage-background counts every record of every file of the target, paired or not: what PE2 holds beyond PE1's last read
+     * is scanned as well (its tallies go nowhere: no run is replayed over it) */
+    while (sd_bg.on && mode == SD_PE && got == 0 && (rc = stream_fill(&B, p, ns, batch, pool)) != 0) {
+        if (rc < 0) { got = rc; break; }
+        B.ci = B.c->nrec;
     }
     {   /* the lanes run dry before anything is said about the file: the trailer lines follow the last hit line, and a strain's error
          * state is read only here */
@@ -2640,6 +2717,10 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
             if (!(sd_rec.name[sd_rec.next] = strdup(f1))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
             sd_rec.next++;
         }
+    }
+    if (sd_bg.on && (got = sd_background_target(p, ns, f1)) != SK_OK) {
+        fprintf(err, "strain_detect: --coverage-background: %s on %s (%s)\n", sk_strerror(got), f1, sd_bg_error ? sd_bg_error : "");
+        goto done;
     }
     if (__atomic_load_n(&sd_sup.failed, __ATOMIC_RELAXED)) { fprintf(err, "strain_detect: --coverage-support: out of memory\n"); goto done; }
     for (s = 0; s < ns; s++) {
@@ -2836,7 +2917,7 @@ static int sd_keyset(sd_prog *p, const char *r, int device)
     if (!getenv("SK_SD_HOST_KEYSET")) {
         if (!p->ctx && !p->ctx_rc) p->ctx_rc = sk_ctx_create(&p->ctx, device);
         if (p->ctx) {
-            const int rc = skh_keyset_build_on_device(&p->ks, p->ctx, r, SD_NCOLS, SD_PLAIN);
+            const int rc = skh_keyset_build_on_device(&p->ks, p->ctx, r, sd_ncols(), SD_PLAIN);
             if (rc == SK_OK) { p->table_on_device = 1; return SK_OK; }
             skh_keyset_free(&p->ks);
             if (rc != SK_E_UNSUPPORTED && rc != SK_E_OPEN) return rc;      /* (an unreadable file: the host's builder says so in the reference's words) */
@@ -2911,7 +2992,7 @@ static int sd_strain_finish(sd_prog *p, int ks_rc, const char *r, const char *a,
         rc = p->ctx ? SK_OK : (p->ctx_rc ? p->ctx_rc : sk_ctx_create(&p->ctx, device));
         if (rc != SK_OK) { fprintf(err, "strain_detect: cannot use HIP device %d: %s\n", device, sk_strerror(rc)); return 1; }
         t1 = now_s();
-        rc = p->table_on_device ? SK_OK : skh_keyset_load(p->ctx, &p->ks, SD_NCOLS);
+        rc = p->table_on_device ? SK_OK : skh_keyset_load(p->ctx, &p->ks, sd_ncols());
         if (rc != SK_OK) { fprintf(err, "strain_detect: table load failed: %s (%s)\n", sk_strerror(rc), sk_last_error(p->ctx)); return 1; }
         t2 = now_s();
         frc = sd_strain_flags(p, a, g, o);
@@ -3018,6 +3099,24 @@ static char *sd_table_path(const char *o_path, const char *explicit_path, const 
     if (n >= 13 && !strcmp(t + n - 13, ".kmer_hits.gz")) t[n - 13] = 0;
     strcat(t, suffix);
     return t;
+}
+
+/* --coverage-background, --background-spectrum: the tables of strain p */
+static int sd_background_write(sd_prog *p)
+{
+    char *name = sd_strain_name(p->o_path);
+    FILE *f = name ? fopen(p->bg_path, "w") : NULL;
+    int rc = f ? skb_write(p->bg, name, f) : -1;
+    const char *bad = p->bg_path;
+    if (f) fclose(f);
+    if (!rc && p->bgs_path) {
+        bad = p->bgs_path;
+        rc = (f = fopen(p->bgs_path, "w")) ? skb_write_spectrum(p->bg, name, f) : -1;
+        if (f) fclose(f);
+    }
+    free(name);
+    if (rc) { fprintf(p->err, "strain_detect: could not write %s\n", bad); return 1; }
+    return 0;
 }
 
 /* --coverage-support: every strain's table, and with --support-pairs the panel's one file */
@@ -3282,6 +3381,8 @@ static void sd_strain_close(sd_prog *p)
     if (skh_regions_free) skh_regions_free(&p->rg);
     free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->th_path); free(p->su_path); free(p->rc_path); free(p->rp_path);
     free(p->sw_path); free(p->sw_rows); free(p->row_class);
+    free(p->bg_path); free(p->bgs_path);
+    if (p->bg && skb_destroy) skb_destroy(p->bg);
     skc_classes_free(&p->sw_c);
     memset(p, 0, sizeof *p);
 }
@@ -3404,6 +3505,15 @@ static int sd_run(sd_prog *p, uint32_t ns, const char *B, const char *b, const c
     pool_stop(&pool);
     sd_unmap_wait();
     sd_batch_cache_close();
+    if (getenv("SK_SD_SCAN_TIMING") && sk_scan_timing && sk_union_scan_timing) {   /* (opt-in: what --coverage-background's count scans add is read off two runs) */
+        double ms = 0, one;
+        uint64_t n = 0, k;
+        uint32_t g, s;
+        for (g = 0; g < sd_un.n; g++) if (sk_union_scan_timing(sd_un.u[g], &one, &k, 0) == SK_OK) { ms += one; n += k; }
+        for (s = 0; !sd_un.n && s < ns; s++) if (sk_scan_timing(p[s].ctx, &one, &k, 0) == SK_OK) { ms += one; n += k; }
+        fprintf(err, "strain_detect timing: scan kernels on the device: %.3f ms in %llu launches (TALLY%s)\n", ms, (unsigned long long)n,
+                sd_bg.on ? " and the background's COUNT scans" : "");
+    }
     if (!bad && sd_rec.r) bad = sd_recurrence_finish(p, err);
     co_close();
     if (getenv("SK_LEAK_AT_EXIT") && strcmp(getenv("SK_LEAK_AT_EXIT"), "0")) return bad;     /* (the process is about to end: see sd_strain_close) */
@@ -3532,6 +3642,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL, *th_file = NULL, *th_list = NULL;
     int want_th = 0, want_sw = 0, want_su = 0, want_sq = 0;
     const char *su_file = NULL, *sq_file = NULL;
+    int want_bg = 0, want_bgs = 0;
+    const char *bg_file = NULL, *bgs_file = NULL, *bg_max = NULL;
     const char *sw_file = NULL, *sw_classes = NULL;
     skc_classes *swc = NULL;
     uint32_t nswc = 0;
@@ -3637,6 +3749,22 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             sq_file = argv[c][15] ? argv[c] + 16 : NULL;
             continue;
         }
+        /* "--coverage-background[=FILE] [--background-spectrum[=FILE]] [--background-max D]": next to either table, how much of ALL the
+         * strain's k-mers each target holds and how deep, per class (informative, background); with the spectrum, per depth 0..D and
+         * above (default D 63, at most 255); default FILEs = outfile with ".kmer_hits.gz" replaced by ".coverage_background" and
+         * ".coverage_background_spectrum" */
+        if (!strncmp(argv[c], "--coverage-background", 21) && (argv[c][21] == 0 || argv[c][21] == '=')) {
+            want_bg = 1;
+            bg_file = argv[c][21] ? argv[c] + 22 : NULL;
+            continue;
+        }
+        if (!strncmp(argv[c], "--background-spectrum", 21) && (argv[c][21] == 0 || argv[c][21] == '=')) {
+            want_bgs = 1;
+            bgs_file = argv[c][21] ? argv[c] + 22 : NULL;
+            continue;
+        }
+        if (!strcmp(argv[c], "--background-max") && c + 1 < argc) { bg_max = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--background-max=", 17)) { bg_max = argv[c] + 17; continue; }
         if (!strcmp(argv[c], "--min-kmer-hits") && c + 1 < argc) { cov_min = atoll(argv[++c]); continue; }
         if (!strcmp(argv[c], "--target-cache") && c + 1 < argc) { tc_dir = argv[++c]; continue; }       /* (extension: the target cache, see sd_tc) */
         if (!strncmp(argv[c], "--target-cache=", 15)) { tc_dir = argv[c] + 15; continue; }
@@ -3651,6 +3779,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_co.on = 0;
     sd_ps.path = NULL;
     sd_sup.on = 0; sd_sup.pairs_path = NULL;
+    memset(&sd_bg, 0, sizeof sd_bg);
     if (cov_only && want_cov) { fputs("strain_detect: --coverage-only and --coverage-depth exclude each other (the table is the same; only one writes the hit list)\n", err); return sd_drop(p, ns); }
 
     optind = 1;
@@ -3766,6 +3895,49 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             if (getenv("SK_SD_NO_UNION")) { fputs("strain_detect: --support-pairs compares the strains of a union table and SK_SD_NO_UNION is set: no pairs of the panel\n", err); return sd_drop(p, ns); }
         }
     }
+    if (want_bg || want_bgs || bg_max) {
+        const int several = (S && !a && !o && !r) || (ad && ad->o);
+        long long d = 63;
+        char *end = NULL;
+        if (!want_bg) { fprintf(err, "strain_detect: %s goes with --coverage-background\n", want_bgs ? "--background-spectrum" : "--background-max"); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-background goes with --coverage-depth or --coverage-only: it is the denominator their table's numbers are read against\n", err); return sd_drop(p, ns); }
+        if ((bg_file || bgs_file) && several) { fputs("strain_detect: --coverage-background=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        if (bg_max) {
+            errno = 0;
+            d = strtoll(bg_max, &end, 10);
+            if (end == bg_max || *end || errno || d < 1 || d > (long long)SK_BACKGROUND_MAX_DEPTH) { fprintf(err, "strain_detect: --background-max %s: a depth from 1 to %u\n", bg_max, SK_BACKGROUND_MAX_DEPTH); return sd_drop(p, ns); }
+        }
+        if (ad) { fputs("strain_detect: --coverage-background does not go behind kmer_scrub_count --detect: the resident tables were loaded without its count column\n", err); return sd_drop(p, ns); }
+        if (!sk_scan_batch || !sk_background_finish || !sk_union_background_finish || !sk_union_count_enable || !sk_union_context || !skb_create || !skb_destroy ||
+            !skb_add || !skb_write || !skb_write_spectrum) { fputs("strain_detect: --coverage-background: this build has no background sweep\n", err); return sd_drop(p, ns); }
+        if (B) {                                             /* breadth is not additive, and the device column is swept per target */
+            FILE *fp = fopen(B, "r");
+            char *line = NULL, **seen = NULL;
+            size_t cap = 0;
+            uint32_t nseen = 0, k;
+            int shared = 0;
+            while (fp && !shared && getline(&line, &cap, fp) != -1) {
+                char *tok, *f1, *f2, **grown;
+                int m;
+                if (sd_list_line(line, &m, &tok, &f1, &f2) != SD_LL_TARGET) continue;
+                if (strrchr(f1, '/')) f1 = strrchr(f1, '/') + 1;
+                for (k = 0; k < nseen; k++) if (!strcmp(seen[k], f1)) shared = 1;
+                if (!(grown = (char **)realloc(seen, ((size_t)nseen + 1) * sizeof *seen))) break;
+                seen = grown;
+                if (!(seen[nseen] = strdup(f1))) break;
+                nseen++;
+            }
+            for (k = 0; k < nseen; k++) free(seen[k]);
+            free(seen); free(line);
+            if (fp) fclose(fp);
+            if (shared) {
+                fprintf(err, "strain_detect: --coverage-background: two targets of %s share a file name, the tables count them as one sample, and the "
+                             "k-mers two files cover do not add up: run them apart\n", B);
+                return sd_drop(p, ns);
+            }
+        }
+        sd_bg.max = (uint32_t)d;
+    }
     if (want_ps) {
         const char *ws = getenv("SK_WORLD_SIZE") ? getenv("SK_WORLD_SIZE") : getenv("WORLD_SIZE");
         if (!ps_file || !*ps_file) { fputs("strain_detect: --panel-share=FILE needs a file name: the table is one file for the whole panel\n", err); return sd_drop(p, ns); }
@@ -3821,6 +3993,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_ps.path = want_ps ? ps_file : NULL;
     sd_ps.ms = 0; sd_ps.calls = 0;
     sd_sup.on = want_su; sd_sup.pairs_path = want_sq ? sq_file : NULL; sd_sup.acc = NULL; sd_sup.ms_take = sd_sup.ms_finish = 0;
+    sd_bg.on = want_bg;
     sd_co.flush_rows = (env = getenv("SK_SD_CO_FLUSH_ROWS")) != NULL && atoll(env) >= 1 ? (uint64_t)atoll(env) : 1u << 20;
     sd_res_bytes = 0;
     sd_tc_open(tc_dir, err);
@@ -3930,9 +4103,18 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (!(p[s].su_path = sd_table_path(p[s].o_path, S || (ad && ad->o) ? NULL : su_file, ".coverage_support"))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
     for (s = 0; want_rc && s < ns; s++)
         if (sd_recurrence_open(&p[s], S || (ad && ad->o) ? NULL : rc_file, S || (ad && ad->o) ? NULL : rp_file)) goto done;
+    for (s = 0; want_bg && s < ns; s++) {
+        const int own = S || (ad && ad->o);
+        p[s].bg_path = sd_table_path(p[s].o_path, own ? NULL : bg_file, ".coverage_background");
+        p[s].bgs_path = want_bgs ? sd_table_path(p[s].o_path, own ? NULL : bgs_file, ".coverage_background_spectrum") : NULL;
+        p[s].bg = skb_create(sd_bg.max);
+        if (!p[s].bg_path || (want_bgs && !p[s].bgs_path) || !p[s].bg) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
+    }
     if ((c = sd_run(p, ns, B, b, b2, mode, out, err)) != 0) { if (c == SK_E_CACHE) status = SK_E_CACHE; goto done; }
     for (s = 0; s < ns; s++)
         if (sd_coverage_write(&p[s])) goto done;
+    for (s = 0; want_bg && s < ns; s++)
+        if (sd_background_write(&p[s])) goto done;
     if (sd_sup.acc && sd_support_write(p, ns)) goto done;
     status = 0;
 done:
@@ -4006,6 +4188,9 @@ done:
                 sd_rec.ms_mark, sd_rec.T, sd_rec.ms_hist, sd_rec.ms_gram);
     if (getenv("SK_SD_TIMING") && cov_only && want_su)
         fprintf(err, "strain_detect timing: support on the device: takes %.3f ms (inside the folds above), finishes %.3f ms\n", sd_sup.ms_take, sd_sup.ms_finish);
+    if (getenv("SK_SD_TIMING") && want_bg)
+        fprintf(err, "strain_detect timing: background: %llu count scans beside the TALLY launches, finishing sweeps %.3f ms (wall time of the calls)\n",
+                (unsigned long long)sd_bg.scans, sd_bg.ms_sweep);
     if (getenv("SK_SD_TIMING") && want_ps)
         fprintf(err, "strain_detect timing: panel share %.3f ms, %u call(s) of sk_union_share\n", sd_ps.ms, sd_ps.calls);
     if (getenv("SK_SD_RESULT_BYTES"))
@@ -4021,6 +4206,7 @@ done:
     sd_sw.on = 0;
     sd_rec.on = 0;
     sd_ps.path = NULL;
+    sd_bg.on = 0;
     if (sd_sup.acc) sks_destroy(sd_sup.acc);
     sd_sup.acc = NULL; sd_sup.on = 0; sd_sup.pairs_path = NULL;
     sd_sweep_drop(swc, nswc);

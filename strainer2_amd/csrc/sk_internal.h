@@ -136,6 +136,24 @@ typedef struct sk_tally_view {
     const uint32_t *d_rec_start; uint32_t nrec;
 } sk_tally_view;
 int sk_tally_view_(sk_ctx *ctx, sk_union *u, sk_tally_view *out);
+/* the background tables on the host (sk_host_background.c): one strain's blocks as sk_background_finish / sk_union_background_finish
+ * returned them, one per target in run order (skb_add copies SK_BACKGROUND_WORDS(max_depth) u64 and keeps the target's basename), and
+ * the two tables; every call returns 0, or -1 (out of memory, a write that failed, a NULL) */
+typedef struct skb_table skb_table;
+skb_table *skb_create(uint32_t max_depth);
+void skb_destroy(skb_table *t);
+int skb_add(skb_table *t, const char *metagenome, const uint64_t *block);
+uint32_t skb_targets(const skb_table *t);
+int skb_write(const skb_table *t, const char *strain_name, FILE *f);
+int skb_write_spectrum(const skb_table *t, const char *strain_name, FILE *f);
+/* A count column and the type column beside it, as they lie on the device (both in the counters' own order, so row i of one is row i
+ * of the other), for the background sweep (sk_background.hip).  Pending increments are folded in and both scan lanes joined before
+ * this returns; the sweep runs on `stream` and leaves the column zero. */
+typedef struct sk_background_view {
+    int device; void *stream;              /* hipStream_t */
+    uint32_t *d_col; const uint32_t *d_type; uint32_t nrows;
+} sk_background_view;
+int sk_background_view_(sk_ctx *ctx, uint32_t col, uint32_t type_col, sk_background_view *out);
 /* the accumulator's device time (events around every fold and every target sweep): on != 0 starts the clocks, ms_fold / ms_sweep
  * (NULL: not wanted) are the sums so far.  Off unless asked for: strain_detect asks under SK_SD_TIMING. */
 int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *ms_sweep);

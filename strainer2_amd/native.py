@@ -77,6 +77,7 @@ ABI_SYMBOLS = [
     "sk_filter_classes_joint", "sk_filter_classes_above", "skh_scrub_filter_resident_sweep",
     "sk_covacc_set_classes", "sk_covacc_finish_target_classes", "sk_distinct_classes",
     "sk_covacc_set_support", "sk_covacc_finish_target_support",
+    "sk_scan_batch", "sk_background_finish", "sk_union_background_finish",
 ]
 
 
@@ -259,6 +260,11 @@ lib.sk_union_members.restype = C.c_uint32
 lib.sk_union_rows.argtypes = [C.c_void_p]
 lib.sk_union_rows.restype = C.c_uint32
 lib.sk_union_share.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+SK_BACKGROUND_MAX_DEPTH = 255
+SK_BACKGROUND_HEAD = 5
+lib.sk_scan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+lib.sk_background_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+lib.sk_union_background_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
 
 _libc = C.CDLL(None)
 _libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
@@ -453,6 +459,19 @@ class KmerContext:
             self._ck(lib.sk_scan_stream(self._h, stream.ctypes.data, stream.size, col))
         else:
             self._ck(lib.sk_scan_stream(self._h, stream, len(stream), col))
+
+    def scan_batch(self, batch, col):
+        """sk_scan_batch: a COUNT scan of a filled TallyBatch, as it lies on the device, into column col (returns at once; sync()
+        before the batch is refilled)"""
+        self._ck(lib.sk_scan_batch(self._h, batch._h, col))
+
+    def background_finish(self, col, type_col=0, informative_value=2, max_depth=63):
+        """sk_background_finish: uint64[2, 5 + max_depth + 1] -- row 0 the informative rows, row 1 the background rows; columns
+        kmers, covered_kmers, total_hits, rows above max_depth, hits above max_depth, then the rows at depth 0..max_depth.  Column
+        col is zero afterwards."""
+        out = np.zeros((2, SK_BACKGROUND_HEAD + max_depth + 1), dtype=np.uint64)
+        self._ck(lib.sk_background_finish(self._h, col, type_col, informative_value, max_depth, out.ctypes.data))
+        return out
 
     def tally_batch(self, stream: bytes, rec_start, type_col=0, informative_value=2):
         """Per-record tallies (strain_detect): returns (tally[nrec, 2], hits[n, 2] sorted by position)."""
@@ -1090,6 +1109,20 @@ class KmerUnion:
         if member_mask is None:
             member_mask = (1 << len(self._members)) - 1
         self._uck(lib.sk_union_counts_fold(self._h, ucol, member_col, member_mask & 0xFFFFFFFF, int(bool(subtract))))
+
+    def scan_batch(self, batch, col=0):
+        """sk_scan_batch on the union's context: ONE count scan of a filled TallyBatch into union column col"""
+        self._uck(lib.sk_scan_batch(lib.sk_union_context(self._h), batch._h, col))
+
+    def sync(self):
+        self._uck(lib.sk_sync(lib.sk_union_context(self._h)))
+
+    def background_finish(self, ucol=0, max_depth=63):
+        """sk_union_background_finish: uint64[members, 2, 5 + max_depth + 1], each member's block as KmerContext.background_finish
+        returns it; union column ucol is zero afterwards"""
+        out = np.zeros((len(self._members), 2, SK_BACKGROUND_HEAD + max_depth + 1), dtype=np.uint64)
+        self._uck(lib.sk_union_background_finish(self._h, ucol, max_depth, out.ctypes.data))
+        return out
 
     def share(self, other=None):
         """sk_union_share: (shared, informative_in_other, informative_both), three uint64 arrays [members of self, members of

@@ -30,10 +30,15 @@ apart.
     python tools/coverage_only_bench.py --thresholds [--threshold-list 0,1,2] --rounds 3 --parent-exe PATH [--out profiles/coverage_thresholds_bench.txt]
     python tools/coverage_only_bench.py --scrub-sweep --rounds 3 --parent-exe PATH [--out profiles/coverage_scrub_sweep_bench.txt]
     python tools/coverage_only_bench.py --support [--pairs] --rounds 3 --parent-exe PATH [--out profiles/coverage_support_bench.txt]
+    python tools/coverage_only_bench.py --background --rounds 3 --parent-exe PATH [--out profiles/coverage_background_bench.txt]
 
 --support measures --coverage-support (--pairs: with --support-pairs=FILE) like --thresholds: the parent's plain --coverage-only runs in
 turn with this build's plain runs and its runs with the flag; each line with the flag also carries the device time of the takes (a
 part of the folds) and of the finishes.
+
+--background measures --coverage-background --background-spectrum like --thresholds; every run of this build also reports the scan
+kernels' summed device time (SK_SD_SCAN_TIMING=1: TALLY alone without the flag, TALLY and the COUNT scans with it -- the difference is
+what the count scans add), and each line with the flag the finishing sweeps of all targets (wall time of the calls).
 
 --scrub-sweep measures --coverage-scrub-sweep like --thresholds (class files of 8 fractions are made up for the strains' lists: the
 class pass does not care where the classes come from), then step 2 alone at 8 fractions against 1 (kmer_scrub_filter over one
@@ -66,6 +71,8 @@ ACC = re.compile(rb"coverage accumulators on the device: folds ([0-9.]+) ms, tar
 REC = re.compile(rb"recurrence on the device: marks ([0-9.]+) ms \((\d+) targets\), finish: histogram ([0-9.]+) ms, pairs ([0-9.]+) ms")
 THR = re.compile(rb"thresholds on the device: (\d+) thresholds, finishing passes ([0-9.]+) ms")
 SUPT = re.compile(rb"support on the device: takes ([0-9.]+) ms \(inside the folds above\), finishes ([0-9.]+) ms")
+BGT = re.compile(rb"background: (\d+) count scans beside the TALLY launches, finishing sweeps ([0-9.]+) ms")
+SCN = re.compile(rb"scan kernels on the device: ([0-9.]+) ms in (\d+) launches")
 SWP = re.compile(rb"scrub sweep on the device: class passes ([0-9.]+) ms")
 SWEEP_LIST = "0.5,0.4,0.3,0.2,0.1,0.05,0.02,0.01"
 BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
@@ -87,7 +94,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     for s in range(ns):
         for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum",
                   f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs", f"out{s}.gz.coverage_thresholds",
-                  f"out{s}.gz.coverage_scrub_sweep", f"out{s}.gz.coverage_support"):
+                  f"out{s}.gz.coverage_scrub_sweep", f"out{s}.gz.coverage_support", f"out{s}.gz.coverage_background", f"out{s}.gz.coverage_background_spectrum"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -108,7 +115,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             h.update(f.read())
     hr = hashlib.md5()
     for s in range(ns):
-        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds", "coverage_scrub_sweep", "coverage_support"):    # (the table beside the coverage table, whichever the run wrote)
+        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds", "coverage_scrub_sweep", "coverage_support", "coverage_background", "coverage_background_spectrum"):    # (the table beside the coverage table, whichever the run wrote)
             if os.path.exists(os.path.join(cwd, f"out{s}.gz.{ext}")):
                 with open(os.path.join(cwd, f"out{s}.gz.{ext}"), "rb") as f:
                     hr.update(f.read())
@@ -119,7 +126,11 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     th = THR.search(p.stderr)
     sw = SWP.search(p.stderr)
     su = SUPT.search(p.stderr)
-    return dict(take=float(su.group(1)) if su else float("nan"), supfin=float(su.group(2)) if su else float("nan"), cls=float(sw.group(1)) if sw else float("nan"), thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
+    bg = BGT.search(p.stderr)
+    sc = SCN.search(p.stderr)
+    return dict(bgscans=int(bg.group(1)) if bg else -1, bgsweep=float(bg.group(2)) if bg else float("nan"), scan=float(sc.group(1)) if sc else float("nan"),
+                launches=int(sc.group(2)) if sc else -1,
+                take=float(su.group(1)) if su else float("nan"), supfin=float(su.group(2)) if su else float("nan"), cls=float(sw.group(1)) if sw else float("nan"), thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
                 fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
                 passed=float(m.group(2)) - float(m.group(1)) if m else float("nan"),
                 d2h=int(b.group(1)) if b else -1, dev=int(b.group(2)) if b else -1, replayed=int(b.group(3)) if b else -1)
@@ -157,7 +168,7 @@ def regions_case(say, args, env, tmp, ns, kind, argv):
         say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
-def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False, sweep=False, support=False):
+def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False, sweep=False, support=False, background=False):
     """--coverage-only without and with --coverage-spectrum (recurrence: --coverage-recurrence --recurrence-pairs; thresholds:
     --coverage-thresholds [--threshold-list ..]), alternating; the parent build's plain --coverage-only behind them -- with
     thresholds: in turn with them, round by round -- and the new build's medians set against the parent's"""
@@ -177,6 +188,11 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
         with_sp = ["--coverage-only", "--coverage-support"] + (["--support-pairs=" + os.path.join(tmp, "support_pairs.tsv")] if args.pairs else [])
         word, label = "support", "... --coverage-support" + (" --support-pairs=FILE" if args.pairs else "")
         thresholds = True
+    if background:                                           # (measured like the thresholds: the parent's runs in turn, folds compared too)
+        with_sp = ["--coverage-only", "--coverage-background", "--background-spectrum"]
+        word, label = "background", "... --coverage-background --background-spectrum"
+        thresholds = True
+        env = dict(env, SK_SD_SCAN_TIMING="1")
     res = {"plain": [], "spectrum": [], "parent": []}
     md5 = md5s = None
     for rnd in range(args.rounds):
@@ -204,7 +220,10 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
         if rs:
             say(f"    {names[tag]}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s; accumulators on the device: folds "
                 f"{row(rs, 'fold', '.2f')} ms, target sweeps {row(rs, 'sweep', '.3f')} ms; runs on the device {rs[0]['dev']}, replayed {rs[0]['replayed']}")
-            if support and tag == "spectrum":
+            if background and tag != "parent":
+                say(f"        scan kernels on the device: {row(rs, 'scan', '.3f')} ms in {rs[0]['launches']} launches" +
+                    (f"; background: {rs[0]['bgscans']} count scans, finishing sweeps of all targets {row(rs, 'bgsweep', '.3f')} ms" if tag == "spectrum" else ""))
+            elif support and tag == "spectrum":
                 say(f"        support on the device: takes of all folds {row(rs, 'take', '.3f')} ms (a part of the folds above), finishes of all targets "
                     f"{row(rs, 'supfin', '.3f')} ms")
             elif sweep and tag == "spectrum":
@@ -218,6 +237,11 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
     med = {t: {k: statistics.median(r[k] for r in rs) for k in keys} for t, rs in res.items() if rs}
     say(f"    with the {word} / without at the medians: pass %.2f, wall %.2f, folds %.2f, target sweeps %.2f" %
         tuple(med["spectrum"][k] / med["plain"][k] if med["plain"][k] else float("nan") for k in keys))
+    if background:
+        ms = {t: statistics.median(r["scan"] for r in res[t]) for t in ("plain", "spectrum")}
+        extra = res["spectrum"][0]["launches"] - res["plain"][0]["launches"]
+        say(f"    the count scans add {ms['spectrum'] - ms['plain']:.3f} ms of scan kernel time at the medians ({ms['plain']:.3f} -> {ms['spectrum']:.3f} ms) in "
+            f"{extra} launches: {1e3 * (ms['spectrum'] - ms['plain']) / extra if extra else float('nan'):.1f} us per count scan")
     if res["parent"]:                                        # the yardstick: the parent's medians; the margin: its own spread
         for k, unit in (("passed", "s"), ("fold", "ms"), ("sweep", "ms")) if thresholds else (("passed", "s"), ("sweep", "ms")):
             spread = max(r[k] for r in res["parent"]) - min(r[k] for r in res["parent"])
@@ -298,6 +322,7 @@ def main():
     ap.add_argument("--threshold-list", default=None, help="... with this --threshold-list (default: the program's)")
     ap.add_argument("--scrub-sweep", action="store_true", help="measure --coverage-scrub-sweep, step 2 at 8 fractions and the fused form")
     ap.add_argument("--support", action="store_true", help="measure --coverage-support, the parent build's runs in turn with this build's")
+    ap.add_argument("--background", action="store_true", help="measure --coverage-background --background-spectrum, the parent build's runs in turn with this build's")
     ap.add_argument("--pairs", action="store_true", help="... with --support-pairs=FILE as well")
     ap.add_argument("--stderr-dir", default=None, help="keep every run's stderr (the SK_SD_TIMING lines) in this directory")
     ap.add_argument("--out", default=None)
@@ -363,8 +388,8 @@ def main():
             for ns in counts:
                 for kind, lst in lists.items():
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
-                    if args.spectrum is not None or args.recurrence or args.thresholds or args.scrub_sweep or args.support:
-                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds, args.scrub_sweep, args.support)
+                    if args.spectrum is not None or args.recurrence or args.thresholds or args.scrub_sweep or args.support or args.background:
+                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds, args.scrub_sweep, args.support, args.background)
                         continue
                     if args.regions is not None:
                         regions_case(say, args, env, tmp, ns, kind, argv)
