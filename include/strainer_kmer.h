@@ -993,6 +993,80 @@ int  sk_covacc_set_support(sk_covacc *a, int on);
 int  sk_covacc_finish_target_support(sk_covacc *a, uint64_t *out_pairs /* nmembers */, uint64_t *out_lines /* nmembers */,
                                      uint64_t *out_both /* nmembers */, uint64_t *out_shared /* nmembers x nmembers */,
                                      uint64_t *out_lines_a /* nmembers x nmembers */);
+/* RAREFACTION (new): step 4's two numbers at nested subsamples of a target's read pairs, from the one pass -- how the distinct
+ * informative k-mers grow with the number of pairs, which says whether a negative or borderline call was sequenced deeply enough.
+ * With the reference this takes a subsample of the FASTQ and a rerun of steps 3 and 4 at every depth.  The rule:
+ *   pair ordinal  i = the pair's 0-based position in the target in file order: -t PE the record index in the mate-1 file, -t PEI
+ *             record index / 2, single-end the record index.  Every record counts, whatever its content: shorter than k, with N, or
+ *             missing a mate.
+ *   draw      x = (uint32)i ^ ((uint32)(i >> 32) * 0x9E3779B9u) ^ seed;
+ *             x ^= x >> 16; x *= 0x85EBCA6Bu;  x ^= x >> 13; x *= 0xC2B2AE35u;  x ^= x >> 16;  u(i) = x   (all in 32 bits)
+ *             seed is a u32, default 0 (--rarefaction-seed S).
+ *   fractions 1 to SK_COVACC_RAREFACTION_MAX = 16 decimal fractions f0,f1,... with 0 < f <= 1, strictly descending
+ *             (--rarefaction-list; default 1,0.5,0.25,0.125,0.0625,0.03125).  T[q] = (uint64)floor(strtod(f_q) * 4294967296.0): a
+ *             double times 2^32 is exact, and int(float(s) * 4294967296.0) in Python gives the same value.  An empty field, a field
+ *             that is no plain decimal number (digits, '.', an exponent), a value outside (0, 1], an order that does not descend, two
+ *             fractions with equal T, more than 16 entries or a field of more than 39 characters is refused.
+ *   subsample q   holds pair i iff u(i) < T[q].  The class of a pair is the number of q that hold it; the list descends, so the pair
+ *             is in subsamples 0 .. class - 1, and the subsamples are nested.
+ *   pairs[q]  the pairs of the target in subsample q.
+ *   total[q]  the hit lines of step 3 that pass the run's --min-kmer-hits and whose pair is in subsample q.
+ *   unique[q] the rows (informative k-mers) with at least one such line.
+ *             A line belongs to the pair that printed it.  For a target whose records all have k bases or more and whose mates are
+ *             all there, these are exactly step 4's two numbers for a run of the same program on a file that holds only the
+ *             subsample's pairs, in order.  A record shorter than k, and a read without its mate, re-use the tallies (and a short
+ *             PE1 read the rows) of the record before them (src/strain_detect.c:444), which in a subsample's file is another
+ *             record: at such records a rerun can differ.  With f0 = 1, unique[0] and total[0] are the main table's numbers and
+ *             pairs[0] is the target's pair count.
+ *   table     strain_detect --coverage-rarefaction[=FILE] [--rarefaction-list ...] [--rarefaction-seed S] (with --coverage-depth or
+ *             --coverage-only; default FILE the -o path with ".kmer_hits.gz" replaced by ".coverage_rarefaction"): a header line,
+ *             then per target (its basename), in the run's order, one line per fraction in the list's order, zeros included, numbers
+ *             integers, `fraction` the user's text; with -S every line begins with a column strain_name:
+ *               metagenome<TAB>fraction<TAB>pairs<TAB>unique_kmers<TAB>total_hits
+ * The accumulator keeps the counted lines per (member, class) and every row's highest class, as for the thresholds: one u32 per
+ * accumulator row from the first sk_covacc_set_rarefaction on, whatever the list's length, plus [nmembers x 17] line bins, as many
+ * row bins and 17 pair bins.
+ *   sk_covacc_set_rarefaction: n = 0 turns rarefaction off (the state after create: nothing of it is allocated and no fold or sweep
+ *   launches a kernel it did not launch before).  Otherwise T[0] > T[1] > ... and T[0] <= 2^32, at most 16 (SK_E_ARG).  It may be
+ *   called between targets; whatever was classified since the last finish is discarded.
+ *   sk_covacc_set_pair_base: the ordinal of pair 0 of the next sk_covacc_add's run (it stays until set again; 0 after create).
+ *   sk_covacc_add with rarefaction on also classifies, in a pass of its own over each side's log, every entry whose pair's total
+ *   exceeds min_kmer_hits by the class of pair first_pair + j, and counts the run's npairs pairs by class, once per run.  It writes
+ *   no depth counter: the main counters, the thresholds and support are what they are without it.
+ *   sk_covacc_add_rows_hits_pairs: sk_covacc_add_rows_hits, and each of the n unfiltered hits also carries its pair's ordinal and is
+ *   classified by the same rule.  sk_covacc_add_pairs: pairs first .. first + n - 1 of the target counted by class (the pairs of
+ *   replayed runs, which sk_covacc_add does not see).  Every pair of a target is to be counted exactly once.  Both are SK_E_STATE
+ *   with rarefaction off.
+ *   sk_covacc_finish_target_rarefaction: out_pairs[q], out_unique[m * n + q], out_total[m * n + q] for the list's n fractions.  A
+ *   pass of its own in front of whichever sweep ends the target: it changes no depth counter; the rarefaction state is zero
+ *   afterwards (a second call returns zeros).  SK_E_STATE with rarefaction off.
+ * The host side (sk_host_rarefaction.c): skh_rarefaction_parse reads a list (NULL: the default) into T[] and keeps each field's
+ * text; skh_rarefaction_draw and skh_rarefaction_class are the rule above; skh_rarefaction_fold is the table of one strain and
+ * target from its hit lines as (pair ordinal, row < nrows, pair total) triples and the target's pairs first_pair .. first_pair +
+ * npairs - 1 (SK_E_ARG for a row out of range); skh_rarefaction_write prints the header (metagenome NULL) or a sample's lines.
+ * coverage_depth has no flag for this table: a hit list carries no pair ordinal. */
+#define SK_COVACC_RAREFACTION_MAX 16u
+#define SKH_RAREFACTION_DEFAULT "1,0.5,0.25,0.125,0.0625,0.03125"
+typedef struct skh_rarefaction {
+    uint32_t n, seed;
+    uint64_t T[SK_COVACC_RAREFACTION_MAX];
+    char     text[SK_COVACC_RAREFACTION_MAX][40];
+} skh_rarefaction;
+int  sk_covacc_set_rarefaction(sk_covacc *a, const uint64_t *T, uint32_t n, uint32_t seed);
+int  sk_covacc_set_pair_base(sk_covacc *a, uint64_t first_pair);
+int  sk_covacc_add_pairs(sk_covacc *a, uint64_t first, uint64_t n);
+int  sk_covacc_add_rows_hits_pairs(sk_covacc *a, uint32_t member, const uint32_t *rows, const uint32_t *total_hits,
+                                   const uint64_t *pair_ordinal, uint64_t n);
+int  sk_covacc_finish_target_rarefaction(sk_covacc *a, uint64_t *out_pairs /* n */, uint64_t *out_unique /* nmembers x n */,
+                                         uint64_t *out_total /* nmembers x n */);
+int  skh_rarefaction_parse(const char *list_or_null, uint32_t seed, skh_rarefaction *out);
+uint32_t skh_rarefaction_draw(uint64_t pair, uint32_t seed);
+uint32_t skh_rarefaction_class(const skh_rarefaction *r, uint64_t pair);
+int  skh_rarefaction_fold(const skh_rarefaction *r, int64_t min_kmer_hits, uint32_t nrows, const uint64_t *pair, const uint32_t *row,
+                          const uint32_t *total_hits, uint64_t n, uint64_t first_pair, uint64_t npairs,
+                          uint64_t *out_pairs /* r->n */, uint64_t *out_unique /* r->n */, uint64_t *out_total /* r->n */);
+int  skh_rarefaction_write(FILE *f, const skh_rarefaction *r, const char *strain_or_null, const char *metagenome_or_null,
+                           const uint64_t *pairs, const uint64_t *unique, const uint64_t *total);
 /* The script's command line (-k/--kmer_hits_file, -m/--min_kmer_hits, -b/--background_metagenomes_file):
  * same stdout bytes and exit status.  New: --scrub-classes FILE --scrub-sweep[=FILE] also writes the scrub sweep table (above) to
  * FILE, default the hits file's path with a trailing ".kmer_hits.gz" replaced by ".coverage_scrub_sweep"; stdout is unchanged; a hit

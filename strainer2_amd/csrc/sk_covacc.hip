@@ -24,6 +24,9 @@
 // that also sums each (pair, member)'s informative tallies and marks the pair's word, and the pass between the scatter and the clearing
 // scatter in which one lane per marked pair adds the pair's supporters to per-workgroup LDS tables.  A run with support off launches
 // neither and allocates nothing of them.
+// covacc_rar_hits / covacc_rar_pairs / covacc_rows_rar are rarefaction (step 4's numbers at nested subsamples of the read pairs): a
+// classifying pass of its own over each side's log between the scatters and the clearing scatters, the run's pairs binned once per
+// run, and covacc_thr_finish again over the rows' highest classes.  A run that never sets a list launches and allocates none of it.
 // Every kernel is a grid-stride loop over n items with the bounds of every index it forms checked against the sizes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -698,6 +701,120 @@ __global__ void __launch_bounds__(256) covacc_take(const uint32_t *__restrict__ 
         atomicAdd(acc + (size_t)member0 * 3u + threadIdx.x, s_mem[threadIdx.x]);
 }
 
+// ---- rarefaction: step 4's numbers at nested subsamples of the read pairs, from one pass (include/strainer_kmer.h has the rule) ----
+// Pair i of the target draws u(i), a function of its ordinal and the seed alone; it is in subsample q iff u(i) < T[q], and its class is
+// the number of listed q that hold it (T descends, so those are q = 0 .. class - 1).  The structure is the thresholds': every counted
+// line of a pair of class c >= 1 adds to rar_cnt[member][c] (LDS bins, cov_bin_add) and raises rar_max[row] to c; covacc_thr_finish --
+// the same 17 bins -- turns rar_max[] into rows per class, and the host takes suffix sums.  covacc_rar_hits is a pass of its own over a
+// side's log, between the scatters and the clearing scatter: it writes no depth counter, so it stands behind covacc_hits,
+// covacc_hits_thr and the support take alike, and a run with rarefaction off launches none of this.  covacc_rar_pairs bins the run's
+// pairs themselves, once per run.
+#define COV_RAR_CLASSES (SK_COVACC_RAREFACTION_MAX + 1u)
+static_assert(COV_RAR_CLASSES == COV_THR_CLASSES, "covacc_thr_finish bins both tables' row classes");
+struct cov_rar { unsigned long long t[SK_COVACC_RAREFACTION_MAX]; uint32_t n, seed; };
+
+__device__ __forceinline__ uint32_t cov_rar_draw(unsigned long long i, uint32_t seed)
+{
+    uint32_t x = (uint32_t)i ^ ((uint32_t)(i >> 32) * 0x9E3779B9u) ^ seed;
+    x ^= x >> 16; x *= 0x85EBCA6Bu;
+    x ^= x >> 13; x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
+__device__ __forceinline__ uint32_t cov_rar_class(const cov_rar &rf, unsigned long long pair)
+{
+    const unsigned long long u = cov_rar_draw(pair, rf.seed);
+    const uint32_t n = rf.n < SK_COVACC_RAREFACTION_MAX ? rf.n : SK_COVACC_RAREFACTION_MAX;
+    uint32_t c = 0;
+    for (uint32_t q = 0; q < n; q++) c += u < rf.t[q] ? 1u : 0u;
+    return c;
+}
+
+// every log entry of a side whose pair's total passes: the pair's class to rar_max[row] and to the (member, class) bin.  An entry no
+// table row stands behind is left out here; the fold in front of this pass has reported it.
+__global__ void __launch_bounds__(256) covacc_rar_hits(const sk_hit *__restrict__ hits, uint64_t n, const uint32_t *__restrict__ rec_start,
+                                                       uint32_t nrec, uint32_t ns, int is_union, uint32_t r0, uint32_t step, uint32_t npairs,
+                                                       const uint32_t *__restrict__ tot, long long min_hits,
+                                                       const uint64_t *__restrict__ row_base, const uint32_t *__restrict__ nrows,
+                                                       cov_rar rf, unsigned long long pair_base, uint32_t *__restrict__ rar_max,
+                                                       unsigned long long *__restrict__ rar_cnt)
+{
+    __shared__ unsigned long long s_bin[COV_THR_LDS_MEMBERS * COV_RAR_CLASSES];
+    const bool in_lds = ns <= COV_THR_LDS_MEMBERS;
+    const uint32_t nbins = in_lds ? ns * COV_RAR_CLASSES : 0u;
+    for (uint32_t b = threadIdx.x; b < nbins; b += 256u) s_bin[b] = 0ull;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < n; i0 += stride) {      // (i0 is the workgroup's: every wave stays whole)
+        const uint64_t i = i0 + threadIdx.x;
+        uint32_t bin = 0xFFFFFFFFu;
+        if (i < n) {
+            const sk_hit e = hits[i];
+            uint32_t lo = 0, hi = nrec;
+            while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (rec_start[mid] <= e.pos) lo = mid; else hi = mid; }
+            const uint32_t m = is_union ? e.row >> SK_UNION_ROW_BITS : 0u;
+            const uint32_t row = is_union ? e.row & ((1u << SK_UNION_ROW_BITS) - 1u) : e.row;
+            if (rec_start[lo] <= e.pos && m < ns && row < nrows[m]) {
+                const uint32_t j = cov_pair(lo, r0, step, npairs);
+                if (j < npairs && (long long)tot[(size_t)j * ns + m] > min_hits) {
+                    const uint32_t c = cov_rar_class(rf, pair_base + j);
+                    if (c) {
+                        atomicMax(rar_max + row_base[m] + row, c);
+                        if (in_lds) bin = m * COV_RAR_CLASSES + c;
+                        else atomicAdd(rar_cnt + (size_t)m * COV_RAR_CLASSES + c, 1ull);
+                    }
+                }
+            }
+        }
+        if (in_lds) cov_bin_add(s_bin, nbins, bin);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < nbins; b += 256u)
+        if (s_bin[b]) atomicAdd(rar_cnt + b, s_bin[b]);
+}
+
+// pairs first .. first + n - 1 of the target, binned by class into pair_cnt[COV_RAR_CLASSES]
+__global__ void __launch_bounds__(256) covacc_rar_pairs(unsigned long long first, uint64_t n, cov_rar rf, unsigned long long *__restrict__ pair_cnt)
+{
+    __shared__ unsigned long long s_bin[COV_RAR_CLASSES];
+    if (threadIdx.x < COV_RAR_CLASSES) s_bin[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < n; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        uint32_t bin = 0xFFFFFFFFu;
+        if (i < n) { const uint32_t c = cov_rar_class(rf, first + i); if (c) bin = c; }
+        cov_bin_add(s_bin, COV_RAR_CLASSES, bin);
+    }
+    __syncthreads();
+    if (threadIdx.x < COV_RAR_CLASSES && s_bin[threadIdx.x]) atomicAdd(pair_cnt + threadIdx.x, s_bin[threadIdx.x]);
+}
+
+// host-replayed entries of one member, unfiltered, each with its pair's total and its pair's ordinal: the classification only
+// (covacc_rows_hits in front of it has the counters); rar_max is the member's, rar_cnt its COV_RAR_CLASSES bins
+__global__ void __launch_bounds__(256) covacc_rows_rar(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ totals,
+                                                       const unsigned long long *__restrict__ pairs, uint64_t n, uint32_t nrows,
+                                                       long long min_hits, cov_rar rf, uint32_t *__restrict__ rar_max,
+                                                       unsigned long long *__restrict__ rar_cnt)
+{
+    __shared__ unsigned long long s_bin[COV_RAR_CLASSES];
+    if (threadIdx.x < COV_RAR_CLASSES) s_bin[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < n; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        uint32_t bin = 0xFFFFFFFFu;
+        if (i < n && rows[i] < nrows && (long long)totals[i] > min_hits) {
+            const uint32_t c = cov_rar_class(rf, pairs[i]);
+            if (c) { atomicMax(rar_max + rows[i], c); bin = c; }
+        }
+        cov_bin_add(s_bin, COV_RAR_CLASSES, bin);
+    }
+    __syncthreads();
+    if (threadIdx.x < COV_RAR_CLASSES && s_bin[threadIdx.x]) atomicAdd(rar_cnt + threadIdx.x, s_bin[threadIdx.x]);
+}
+
 struct sk_covacc {
     sk_ctx *ctx; int device;
     hipStream_t stream;
@@ -746,6 +863,14 @@ struct sk_covacc {
     unsigned long long *d_sword; size_t sword_cap;          // [pairs] PE1 members | PE2 members << 32; all zero between folds
     unsigned long long *d_sup; size_t sup_cells;            // the target's accumulators (covacc_take has the layout); zero after a finish
     hipEvent_t ev2, ev3; bool sup_timed; double ms_take, ms_supfin;   // the takes' and the finishes' device time
+    // rarefaction: nothing of it exists until sk_covacc_set_rarefaction is called with a list
+    cov_rar rar;                                            // rar.n = 0: off
+    unsigned long long pair_base;                           // the ordinal of pair 0 of the next sk_covacc_add's run
+    uint32_t *d_rar_max;                                    // [total_rows] each row's highest class since the last finish
+    unsigned long long *d_rar_cnt;                          // [nm x COV_RAR_CLASSES] lines per class, as many: rows per class, then [COV_RAR_CLASSES] pairs
+    unsigned long long *d_pairs; size_t pairs_cap;          // sk_covacc_add_rows_hits_pairs' upload of the ordinals
+    bool rar_dirty;                                         // something was classified or counted since the last finish
+    hipEvent_t ev4, ev5; bool rar_timed; double ms_rar, ms_rarfin;    // the classifying passes' and the finishing passes' device time
 };
 
 static void cov_t0(sk_covacc *a) { if (a->timed) (void)hipEventRecord(a->ev0, a->stream); }
@@ -798,6 +923,15 @@ extern "C" int sk_covacc_support_timing_(sk_covacc *a, double *ms_take, double *
     return SK_OK;
 }
 
+// ms_class: the classifying passes' device time inside the folds (pair counts included); ms_finish: the finishing passes'.  Both
+// are kept only while sk_covacc_timing_ is on.
+extern "C" int sk_covacc_rarefaction_timing_(sk_covacc *a, double *ms_class, double *ms_finish)
+{
+    if (!a || !ms_class || !ms_finish) return SK_E_ARG;
+    *ms_class = a->ms_rar; *ms_finish = a->ms_rarfin;
+    return SK_OK;
+}
+
 #define CA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sk_fail_(a->ctx, SK_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 static unsigned cov_grid(uint64_t n) { const uint64_t g = (n + 255u) / 256u; return (unsigned)(g < 1u ? 1u : g > 4096u ? 4096u : g); }
@@ -827,6 +961,8 @@ extern "C" void sk_covacc_destroy(sk_covacc *a)
     (void)hipFree(a->d_thr_max); (void)hipFree(a->d_thr_cnt); (void)hipFree(a->d_tots);
     (void)hipFree(a->d_cls); (void)hipFree(a->d_ncls); (void)hipFree(a->d_cls_up); (void)hipFree(a->d_cls_out);
     (void)hipFree(a->d_sinf); (void)hipFree(a->d_sword); (void)hipFree(a->d_sup);
+    (void)hipFree(a->d_rar_max); (void)hipFree(a->d_rar_cnt); (void)hipFree(a->d_pairs);
+    if (a->rar_timed) { (void)hipEventDestroy(a->ev4); (void)hipEventDestroy(a->ev5); }
     if (a->sup_timed) { (void)hipEventDestroy(a->ev2); (void)hipEventDestroy(a->ev3); }
     if (a->timed) { (void)hipEventDestroy(a->ev0); (void)hipEventDestroy(a->ev1); }
     if (a->h_bad) (void)hipHostFree(a->h_bad);
@@ -991,6 +1127,12 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
             a->sup_timed = true;
         }
     }
+    const bool rar = a->rar.n != 0u;
+    if (rar && a->timed && !a->rar_timed) {
+        CA_HIP(hipEventCreate(&a->ev4));
+        if (hipEventCreate(&a->ev5) != hipSuccess) { (void)hipEventDestroy(a->ev4); return sk_fail_(a->ctx, SK_E_HIP, "no event for the classifying pass"); }
+        a->rar_timed = true;
+    }
     cov_t0(a);
     for (int clear = 0; clear < 2; clear++) {
         for (uint32_t k = 0; k < nsides; k++)
@@ -1024,6 +1166,23 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
                                    side[k].rec_start, side[k].nrec, ns, members ? 1 : 0, side[k].r0, side[k].step, npairs,
                                    (const uint32_t *)a->d_tot, a->min_hits, a->d_depth, (const uint64_t *)a->d_base + member0,
                                    (const uint32_t *)a->d_nrows + member0, a->d_bad);
+        if (rar && !clear) {                                  // the classifying pass: behind the scatters, in front of the clearing ones
+            if (a->rar_timed) (void)hipEventRecord(a->ev4, a->stream);
+            for (uint32_t k = 0; k < nsides; k++)
+                if (side[k].nhits)
+                    hipLaunchKernelGGL(covacc_rar_hits, dim3(cov_grid(side[k].nhits)), dim3(256), 0, a->stream, side[k].hits, side[k].nhits,
+                                       side[k].rec_start, side[k].nrec, ns, members ? 1 : 0, side[k].r0, side[k].step, npairs,
+                                       (const uint32_t *)a->d_tot, a->min_hits, (const uint64_t *)a->d_base + member0,
+                                       (const uint32_t *)a->d_nrows + member0, a->rar, a->pair_base, a->d_rar_max,
+                                       a->d_rar_cnt + (size_t)member0 * COV_RAR_CLASSES);
+            {   // the run's pairs, once per run
+                const unsigned g = cov_grid(npairs);
+                hipLaunchKernelGGL(covacc_rar_pairs, dim3(g > 256u ? 256u : g), dim3(256), 0, a->stream, a->pair_base, (uint64_t)npairs,
+                                   a->rar, a->d_rar_cnt + (size_t)a->nm * COV_RAR_CLASSES * 2u);
+            }
+            if (a->rar_timed) (void)hipEventRecord(a->ev5, a->stream);
+            a->rar_dirty = true;
+        }
     }
     {   // a fold that fails half way leaves tot[] (and support's cells and words) as they must be between folds: all zero
         hipError_t e = hipGetLastError();
@@ -1037,6 +1196,7 @@ extern "C" int sk_covacc_add(sk_covacc *a, sk_ctx *ctx, sk_union *u, uint32_t me
     }
     cov_t1(a, &a->ms_fold);
     if (sup && a->sup_timed) { float ms = 0.f; if (hipEventElapsedTime(&ms, a->ev2, a->ev3) == hipSuccess) a->ms_take += (double)ms; }
+    if (rar && a->rar_timed) { float ms = 0.f; if (hipEventElapsedTime(&ms, a->ev4, a->ev5) == hipSuccess) a->ms_rar += (double)ms; }
     if (mate && mate->held) a->held = false;
     if (*(volatile uint32_t *)a->h_bad) { *a->h_bad = 0u; return sk_fail_(a->ctx, SK_E_STATE, "a hit log entry names no row of its member"); }
     return SK_OK;
@@ -1528,5 +1688,118 @@ extern "C" int sk_covacc_finish_target_classes(sk_covacc *a, uint64_t *out_uniqu
         }
     }
     *out_stray = h[ncell];
+    return SK_OK;
+}
+
+// ---- rarefaction ----
+static int cov_rar_clear(sk_covacc *a)
+{
+    if (a->d_rar_max && a->rar_dirty) {
+        CA_HIP(hipMemsetAsync(a->d_rar_max, 0, (size_t)(a->total_rows ? a->total_rows : 1u) * 4u, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_rar_cnt, 0, ((size_t)a->nm * 2u + 1u) * COV_RAR_CLASSES * 8u, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+    }
+    a->rar_dirty = false;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_set_rarefaction(sk_covacc *a, const uint64_t *T, uint32_t n, uint32_t seed)
+{
+    if (!a || n > SK_COVACC_RAREFACTION_MAX || (n && !T)) return SK_E_ARG;
+    for (uint32_t q = 0; q < n; q++)
+        if (T[q] > 0x100000000ull || (q && T[q] >= T[q - 1])) return SK_E_ARG;   // (T = 0, a fraction below 2^-32, holds no pair)
+    CA_HIP(hipSetDevice(a->device));
+    if (n && !a->d_rar_max) {                             // all zero: no row has a line of any class, no pair was counted
+        const size_t bytes = (size_t)(a->total_rows ? a->total_rows : 1u) * 4u, cb = ((size_t)a->nm * 2u + 1u) * COV_RAR_CLASSES * 8u;
+        uint32_t *p = NULL; unsigned long long *c = NULL;
+        CA_HIP(hipMalloc((void **)&p, bytes));
+        if (hipMalloc((void **)&c, cb) != hipSuccess) { (void)hipFree(p); return sk_fail_(a->ctx, SK_E_HIP, "no room for the class counts"); }
+        a->d_rar_max = p; a->d_rar_cnt = c;
+        CA_HIP(hipMemsetAsync(a->d_rar_max, 0, bytes, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_rar_cnt, 0, cb, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+        a->rar_dirty = false;
+    }
+    const int rc = cov_rar_clear(a);                      // (whatever was classified under the old list is gone)
+    if (rc != SK_OK) return rc;
+    memset(&a->rar, 0, sizeof a->rar);
+    for (uint32_t q = 0; q < n; q++) a->rar.t[q] = (unsigned long long)T[q];
+    a->rar.n = n; a->rar.seed = seed;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_set_pair_base(sk_covacc *a, uint64_t first_pair)
+{
+    if (!a) return SK_E_ARG;
+    a->pair_base = (unsigned long long)first_pair;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_add_pairs(sk_covacc *a, uint64_t first, uint64_t n)
+{
+    if (!a) return SK_E_ARG;
+    if (!a->rar.n) return sk_fail_(a->ctx, SK_E_STATE, "rarefaction is off (sk_covacc_set_rarefaction)");
+    if (!n) return SK_OK;
+    CA_HIP(hipSetDevice(a->device));
+    const unsigned g = cov_grid(n);
+    hipLaunchKernelGGL(covacc_rar_pairs, dim3(g > 256u ? 256u : g), dim3(256), 0, a->stream, (unsigned long long)first, n, a->rar,
+                       a->d_rar_cnt + (size_t)a->nm * COV_RAR_CLASSES * 2u);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipStreamSynchronize(a->stream));
+    a->rar_dirty = true;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_add_rows_hits_pairs(sk_covacc *a, uint32_t member, const uint32_t *rows, const uint32_t *total_hits,
+                                             const uint64_t *pair_ordinal, uint64_t n)
+{
+    if (!a || (n && (!rows || !total_hits || !pair_ordinal))) return SK_E_ARG;
+    if (!a->rar.n) return sk_fail_(a->ctx, SK_E_STATE, "rarefaction is off (sk_covacc_set_rarefaction)");
+    int rc = sk_covacc_add_rows_hits(a, member, rows, total_hits, n);     // (the counters and the thresholds, every argument checked)
+    if (rc != SK_OK || !n) return rc;
+    if ((rc = cov_room(a, (void **)&a->d_pairs, &a->pairs_cap, (size_t)n * 8u, false)) != SK_OK) return rc;
+    cov_t0(a);
+    CA_HIP(hipMemcpyAsync(a->d_pairs, pair_ordinal, (size_t)n * 8u, hipMemcpyHostToDevice, a->stream));
+    hipLaunchKernelGGL(covacc_rows_rar, dim3(cov_grid(n)), dim3(256), 0, a->stream, (const uint32_t *)a->d_rows, (const uint32_t *)a->d_tots,
+                       (const unsigned long long *)a->d_pairs, n, a->nrows[member], a->min_hits, a->rar, a->d_rar_max + a->base[member],
+                       a->d_rar_cnt + (size_t)member * COV_RAR_CLASSES);
+    CA_HIP(hipGetLastError());
+    CA_HIP(hipStreamSynchronize(a->stream));
+    cov_t1(a, &a->ms_fold);
+    a->rar_dirty = true;
+    return SK_OK;
+}
+
+extern "C" int sk_covacc_finish_target_rarefaction(sk_covacc *a, uint64_t *out_pairs, uint64_t *out_unique, uint64_t *out_total)
+{
+    if (!a || !out_pairs || !out_unique || !out_total) return SK_E_ARG;
+    if (!a->rar.n) return sk_fail_(a->ctx, SK_E_STATE, "rarefaction is off (sk_covacc_set_rarefaction)");
+    CA_HIP(hipSetDevice(a->device));
+    const size_t ncell = (size_t)a->nm * COV_RAR_CLASSES, nall = ncell * 2u + COV_RAR_CLASSES;
+    std::vector<unsigned long long> h(nall, 0ull);
+    if (a->rar_dirty) {                                   // (nothing classified since the last finish: every number is zero)
+        cov_t0(a);
+        unsigned gx = (a->max_rows + 255u) / 256u;
+        gx = gx < 1u ? 1u : gx > 256u ? 256u : gx;
+        hipLaunchKernelGGL(covacc_thr_finish, dim3(gx, a->nm), dim3(256), 0, a->stream, a->d_rar_max, (const uint64_t *)a->d_base,
+                           (const uint32_t *)a->d_nrows, a->d_rar_cnt + ncell);
+        CA_HIP(hipGetLastError());
+        CA_HIP(hipMemcpyAsync(h.data(), a->d_rar_cnt, nall * 8u, hipMemcpyDeviceToHost, a->stream));
+        CA_HIP(hipMemsetAsync(a->d_rar_cnt, 0, nall * 8u, a->stream));
+        CA_HIP(hipStreamSynchronize(a->stream));
+        cov_t1(a, &a->ms_rarfin);
+        a->rar_dirty = false;
+    }
+    const uint32_t nq = a->rar.n;
+    unsigned long long np = 0;
+    for (uint32_t q = nq; q-- > 0u; ) { np += h[ncell * 2u + q + 1u]; out_pairs[q] = np; }
+    for (uint32_t m = 0; m < a->nm; m++) {                // class c counts for the subsamples 0 .. c - 1: suffix sums
+        unsigned long long u = 0, t = 0;
+        for (uint32_t q = nq; q-- > 0u; ) {
+            t += h[(size_t)m * COV_RAR_CLASSES + q + 1u];
+            u += h[ncell + (size_t)m * COV_RAR_CLASSES + q + 1u];
+            out_unique[(size_t)m * nq + q] = u; out_total[(size_t)m * nq + q] = t;
+        }
+    }
     return SK_OK;
 }

@@ -95,6 +95,12 @@ typedef struct {
     uint32_t   *co_rows; uint64_t co_n, co_cap;   /* --coverage-only: rows of host-replayed passing hits on their way to the device's counters */
     uint32_t   *co_tot;                        /* --coverage-thresholds: beside every such row its pair's h1 + h2 (the rows then pass min(--min-kmer-hits, t[0])) */
     char *th_path;                             /* --coverage-thresholds: the table's path */
+    /* --coverage-rarefaction: the table's path and its text so far; beside every row on its way to the device its pair's ordinal; the
+     * pair the replay is at; and, where the lines are counted on the host, every row's highest class and the lines per class of the
+     * target being read */
+    char *ra_path, *ra_buf; size_t ra_len; FILE *ra_f;
+    uint64_t *co_pair, rar_pair;
+    uint8_t *rar_best; uint64_t rar_lines[SK_COVACC_RAREFACTION_MAX + 1];
     char *su_path;                             /* --coverage-support: the table's path */
     /* --coverage-scrub-sweep: the table's path, the strain's class file, its k-mers' rows and classes (the device's sparse list), and
      * every row's class (the host fold's) */
@@ -117,6 +123,7 @@ typedef struct sd_chunk {
     uint32_t *pstart, *prec; uint32_t np, pcap;   /* those records: offset in buf, index in len[] */
     uint64_t *len; uint32_t nrec, rcap;      /* every record, length as the reference sees it */
     int       last, end_kind; size_t end_len;/* last chunk of the file: how the parser ended */
+    uint64_t  rec0, co_base;                 /* the file's records in front of the chunk; a folded chunk: the target's ordinal of its run's pair 0 (--coverage-rarefaction) */
     /* per strain, filled by sd_tally_chunk: the records that hit the strain at all, ascending -- their tallies and their
      * informative rows (CSR).  Nothing here is proportional to records x strains: against a metagenome nearly every
      * (read, strain) pair is a blank */
@@ -175,6 +182,7 @@ typedef struct {
     sd_chunk   *pre;                         /* the queued chunk whose bytes are already in bat[bcur ^ 1] */
     sd_chunk   *ahead;                       /* ... and whose scan has been launched as well (solo streams: see sd_launch_ahead) */
     uint32_t    co_next;                     /* --coverage-only, PEI: the next chunk's co_a0 */
+    uint64_t    nrec_seen;                   /* records of the chunks taken so far */
     int         solo;                        /* the only stream that uses the tables now (SE, PEI): its next chunk may be scanned while this one is replayed */
     /* the target cache (sd_tc): a file that is served has a serving thread in the decode thread's place; one that is filled has a writer */
     int         serving, cache_failed;
@@ -1270,6 +1278,7 @@ typedef struct sd_job {
     uint32_t a0, b0, astep, n, first_valid;
     int have_copy;
     int mute;                                  /* REPLAY: nothing is emitted, only the carried state moves on (a run the device counted) */
+    uint64_t pair_base;                        /* REPLAY: the target's ordinal of the run's pair 0 (--coverage-rarefaction) */
     int pending;                               /* lanes that still have it (atomic) */
     sks_list *sup; int sup_sample;             /* REPLAY with --coverage-support: the run's emissions, a list per strain, and the target's sample */
 } sd_job;
@@ -1293,7 +1302,7 @@ static pthread_mutex_t sd_dev_mu = PTHREAD_MUTEX_INITIALIZER;
 static double t_lane_busy, t_lane_backpressure, t_lane_drain;
 
 static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk *ca, uint32_t a0, const sd_chunk *cb, uint32_t b0,
-                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute, sks_list *sup);
+                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute, sks_list *sup, uint64_t pair_base);
 
 /* --coverage-support[=FILE] [--support-pairs=FILE] (include/strainer_kmer.h has the rule): the read pairs behind the table's numbers.
  * A run the device folds is counted there (sk_covacc_set_support; the numbers come home at the target's end beside the sweep's);
@@ -1362,7 +1371,7 @@ static void *lane_main(void *arg)
                 sd_prog *p = &L->p[s];
                 if (j->kind == SD_JOB_TALLY) tally_one(p, j->ca, s);
                 else if (j->kind == SD_JOB_REPLAY && p->job_rc == SK_OK)
-                    sd_replay_run(p, s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute, j->sup ? &j->sup[s] : NULL);
+                    sd_replay_run(p, s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute, j->sup ? &j->sup[s] : NULL, j->pair_base);
             }
             ln->busy += now_s() - t0;
         }
@@ -1409,7 +1418,7 @@ static void lanes_post(sd_job *j)
             for (s = ln->id; s < L->ns; s += L->n) {
                 if (j->kind == SD_JOB_TALLY) tally_one(&L->p[s], j->ca, s);
                 else if (j->kind == SD_JOB_REPLAY && L->p[s].job_rc == SK_OK)
-                    sd_replay_run(&L->p[s], s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute, j->sup ? &j->sup[s] : NULL);
+                    sd_replay_run(&L->p[s], s, j->f1, j->ca, j->a0, j->cb, j->b0, j->astep, j->n, j->have_copy, j->first_valid, j->mute, j->sup ? &j->sup[s] : NULL, j->pair_base);
             }
             lane_job_done(L, j);
             continue;
@@ -1707,6 +1716,29 @@ static struct { int on; uint32_t n; int64_t t[SK_COVACC_THRESHOLDS_MAX]; double 
  * accumulators on the device the classes go up once as one byte per row (sk_covacc_set_classes) and a pass of its own in front of the
  * target's sweep bins the non-zero rows by class (sk_covacc_finish_target_classes); with --coverage-depth, and where --coverage-only
  * counts on the host, skc_report_classes folds the host accumulator's list. */
+/* --coverage-rarefaction [--rarefaction-list f0,f1,...] [--rarefaction-seed S] (include/strainer_kmer.h has the rule): every read pair
+ * draws a number from its ordinal in the target, and the table gives step 4's numbers over the pairs below each listed fraction.  The
+ * main loop of sd_quantify knows every run's first ordinal (the pairs of the runs before it); a chunk folded on the device gets the same
+ * number from the records in front of it (co_collect), and the two are compared.  Folded runs are classified and their pairs counted on
+ * the device (sk_covacc_set_pair_base in front of sk_covacc_add); a replayed run's lines travel with their ordinals
+ * (sk_covacc_add_rows_hits_pairs) and its pairs are counted here; with --coverage-depth, and where --coverage-only counts on the host,
+ * every strain keeps its rows' highest classes of the target being read.  sk_host_rarefaction.c has the parser, the class and the
+ * table's lines. */
+#pragma weak sk_covacc_set_rarefaction
+#pragma weak sk_covacc_set_pair_base
+#pragma weak sk_covacc_add_rows_hits_pairs
+#pragma weak sk_covacc_finish_target_rarefaction
+#pragma weak sk_covacc_rarefaction_timing_
+#pragma weak skh_rarefaction_parse
+#pragma weak skh_rarefaction_class
+#pragma weak skh_rarefaction_write
+static struct {
+    int on, named;                              /* the flag; the lines begin with the strain's name (-S) */
+    long long min;                              /* --min-kmer-hits */
+    skh_rarefaction r;
+    uint64_t host_pairs[SK_COVACC_RAREFACTION_MAX + 1];    /* the pairs of the target's replayed runs, by class */
+    double ms_class, ms_finish;                 /* SK_SD_TIMING */
+} sd_rar;
 #pragma weak sk_covacc_set_classes
 #pragma weak sk_covacc_finish_target_classes
 #pragma weak sk_covacc_classes_timing_
@@ -1775,6 +1807,7 @@ static void co_close(void)
         if (sd_thr.on && sk_covacc_thresholds_timing_ && sd_co.acc[k] && sk_covacc_thresholds_timing_(sd_co.acc[k], &f) == SK_OK) sd_thr.ms_finish += f;
         if (sd_sw.on && sk_covacc_classes_timing_ && sd_co.acc[k] && sk_covacc_classes_timing_(sd_co.acc[k], &f) == SK_OK) sd_sw.ms_cls += f;
         if (sd_sup.on && sk_covacc_support_timing_ && sd_co.acc[k] && sk_covacc_support_timing_(sd_co.acc[k], &f, &w) == SK_OK) { sd_sup.ms_take += f; sd_sup.ms_finish += w; }
+        if (sd_rar.on && sk_covacc_rarefaction_timing_ && sd_co.acc[k] && sk_covacc_rarefaction_timing_(sd_co.acc[k], &f, &w) == SK_OK) { sd_rar.ms_class += f; sd_rar.ms_finish += w; }
         if (sk_covacc_destroy) sk_covacc_destroy(sd_co.acc[k]);
     }
     for (k = 0; k < sd_rec.nr; k++) {
@@ -1800,6 +1833,7 @@ static int co_open(sd_prog *p, uint32_t ns)
         (sd_thr.on && (!sk_covacc_set_thresholds || !sk_covacc_add_rows_hits || !sk_covacc_finish_target_thresholds)) ||
         (sd_sw.on && (!sk_covacc_set_classes || !sk_covacc_finish_target_classes)) ||
         (sd_sup.on && (!sk_covacc_set_support || !sk_covacc_finish_target_support)) ||
+        (sd_rar.on && (!sk_covacc_set_rarefaction || !sk_covacc_set_pair_base || !sk_covacc_add_rows_hits_pairs || !sk_covacc_finish_target_rarefaction)) ||
         (sd_rec.on && (!sk_recur_create || !sk_recur_finish || !sk_covacc_set_recurrence || !sk_covacc_mark_target))) {
         fprintf(p[0].err, "strain_detect: --coverage-only: this build has no coverage accumulator on the device: this run is counted on the host\n");
         sd_co.host = 1;
@@ -1824,6 +1858,7 @@ static int co_open(sd_prog *p, uint32_t ns)
         if (sd_spec.on && (rc = sk_covacc_set_spectrum(sd_co.acc[k], sd_spec.max)) != SK_OK) { co_close(); return rc; }
         if (sd_thr.on && (rc = sk_covacc_set_thresholds(sd_co.acc[k], sd_thr.t, sd_thr.n)) != SK_OK) { co_close(); return rc; }
         if (sd_sup.on && (rc = sk_covacc_set_support(sd_co.acc[k], 1)) != SK_OK) { co_close(); return rc; }
+        if (sd_rar.on && (rc = sk_covacc_set_rarefaction(sd_co.acc[k], sd_rar.r.T, sd_rar.r.n, sd_rar.r.seed)) != SK_OK) { co_close(); return rc; }
         for (m = 0; m < n && sd_sw.on; m++) {             /* every member's class bytes, from its class file's k-mers */
             const sd_prog *q = &p[a + m];
             uint8_t one = 0;
@@ -1878,7 +1913,8 @@ static void co_flush(sd_prog *p, uint32_t s)
     int rc;
     if (!p->co_n) return;
     pthread_mutex_lock(&sd_dev_mu);
-    rc = sd_thr.on ? sk_covacc_add_rows_hits(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_tot, p->co_n)
+    rc = sd_rar.on ? sk_covacc_add_rows_hits_pairs(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_tot, p->co_pair, p->co_n) :
+         sd_thr.on ? sk_covacc_add_rows_hits(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_tot, p->co_n)
                    : sk_covacc_add_rows(sd_co.acc[unit], s - co_unit_first(unit), p->co_rows, p->co_n);
     pthread_mutex_unlock(&sd_dev_mu);
     p->co_n = 0;
@@ -1975,6 +2011,11 @@ static int co_collect(sd_prog *p, uint32_t ns, sk_batch **batches, sd_chunk *c, 
             if (!u) p[a].hitbuf = (sk_hit *)realloc(p[a].hitbuf, (size_t)p[a].hitcap * sizeof(sk_hit));
             rc = u ? sk_union_tally_launch_ex(u, batches[sd_dev_of_strain(a)], *cap, 1) : sk_tally_launch(ctx, batches[sd_dev_of_strain(a)], SD_TYPE, SD_INFORMATIVE, *cap);
             if (rc != SK_OK) return rc;
+        }
+        if (sd_rar.on && plan != CO_PLAN_HOLD) {             /* the ordinal of the run's pair 0: PE the PE1 chunk's first record, PEI two records a pair */
+            c->co_base = plan == CO_PLAN_MATE ? sd_co.pe_a->c->rec0 : sd_co.mode == SD_PEI ? (c->rec0 + c->co_a0) / 2 : c->rec0;
+            if (plan == CO_PLAN_MATE) sd_co.pe_a->c->co_base = c->co_base;
+            if ((rc = sk_covacc_set_pair_base(sd_co.acc[k], c->co_base)) != SK_OK) return rc;
         }
         if (plan == CO_PLAN_HOLD) rc = sk_covacc_hold(sd_co.acc[k], ctx, u);
         else if (plan == CO_PLAN_MATE) {
@@ -2305,6 +2346,7 @@ static int stream_fill(sd_stream *st, sd_prog *p, uint32_t ns, sk_batch *batch, 
                 if (rc == 0) { sd_text_decline(st, c); chunk_free(c); t_tally += now_s() - t0; continue; }      /* the host parser's chunks follow */
                 uploaded = 1;                              /* (the batch holds it) */
             }
+            c->rec0 = st->nrec_seen; st->nrec_seen += c->nrec;
             if (sd_co.acc && sd_co.mode == SD_PEI) {       /* (interleaved pairs: is the chunk's first record the last chunk's last record's mate?) */
                 c->co_a0 = c->nrec ? st->co_next : 0;
                 if (c->nrec) st->co_next = (c->nrec - c->co_a0) & 1u;
@@ -2341,25 +2383,41 @@ static unsigned char *put_int(unsigned char *w, int v)
 
 /* the hit lines of one read: "<file>\t<hits PE1>\t<informative PE1>\t<hits PE2>\t<informative PE2>\t<k-mer>\n"
  * (src/strain_detect.c:567,608), formatted straight into the output block */
+/* --coverage-rarefaction where the lines are counted on the host: the lines of the pair the replay is at, by the pair's class */
+static void rar_host_lines(sd_prog *p, const uint32_t *rows, uint32_t n)
+{
+    uint32_t j, c;
+    if (!sd_rar.on || !n || !p->rar_best || !((long long)p->h1 + p->h2 > sd_rar.min)) return;
+    c = skh_rarefaction_class(&sd_rar.r, p->rar_pair);
+    p->rar_lines[c] += n;
+    for (j = 0; j < n; j++) if (rows[j] < p->ks.nrows && c > p->rar_best[rows[j]]) p->rar_best[rows[j]] = (uint8_t)c;
+}
+
 static void emit_rows(sd_prog *p, const uint32_t *rows, uint32_t n, const char *name)
 {
     const size_t nl = strlen(name);
     uint32_t j;
     char key[32];
     if (sd_co.on) {                                        /* --coverage-only: no line, only what the script would count of it */
-        if (!sd_co.acc) { for (j = 0; j < n; j++) skc_add_hit(p->cov, name, p->h1, p->h2, rows[j]); return; }
+        if (!sd_co.acc) { for (j = 0; j < n; j++) skc_add_hit(p->cov, name, p->h1, p->h2, rows[j]); rar_host_lines(p, rows, n); return; }
         if (!n || !((long long)p->h1 + p->h2 > (sd_thr.on && sd_thr.t[0] < sd_co.min ? (long long)sd_thr.t[0] : sd_co.min))) return;
         if (p->co_n + n > p->co_cap) {
             p->co_cap = (p->co_n + n) * 2 + 1024;
             p->co_rows = (uint32_t *)realloc(p->co_rows, (size_t)p->co_cap * sizeof *p->co_rows);
-            if (p->co_rows && sd_thr.on) {
+            if (p->co_rows && (sd_thr.on || sd_rar.on)) {
                 uint32_t *t2 = (uint32_t *)realloc(p->co_tot, (size_t)p->co_cap * sizeof *p->co_tot);
                 if (t2) p->co_tot = t2;
                 else { free(p->co_rows); p->co_rows = NULL; }
             }
+            if (p->co_rows && sd_rar.on) {
+                uint64_t *o2 = (uint64_t *)realloc(p->co_pair, (size_t)p->co_cap * sizeof *p->co_pair);
+                if (o2) p->co_pair = o2;
+                else { free(p->co_rows); p->co_rows = NULL; }
+            }
             if (!p->co_rows) { p->co_cap = p->co_n = 0; p->job_rc = SK_E_NOMEM; return; }
         }
-        if (sd_thr.on) {                                   /* (unfiltered: the device applies --min-kmer-hits and the list to the total) */
+        for (j = 0; j < n && sd_rar.on; j++) p->co_pair[p->co_n + j] = p->rar_pair;
+        if (sd_thr.on || sd_rar.on) {                      /* (unfiltered: the device applies --min-kmer-hits and the list to the total) */
             const long long tot = (long long)p->h1 + p->h2;
             for (j = 0; j < n; j++) p->co_tot[p->co_n + j] = tot > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)tot;
         }
@@ -2400,6 +2458,7 @@ static void emit_rows(sd_prog *p, const uint32_t *rows, uint32_t n, const char *
         }
         if (p->cov) skc_add_hit(p->cov, name, p->h1, p->h2, rows[j]);
     }
+    if (p->cov) rar_host_lines(p, rows, n);
 }
 
 static void emit_trailer(sd_prog *p, const char *f1, const char *what, long long v)
@@ -2429,7 +2488,7 @@ static uint32_t sp_lower(const sd_sp *q, uint32_t rec)
  * not all zero (a read shorter than k refreshes nothing, :444, so it re-emits what the read before it left).  A pair without
  * hits met with all-zero tallies leaves them all zero and emits nothing: skipped. */
 static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk *ca, uint32_t a0, const sd_chunk *cb, uint32_t b0,
-                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute, sks_list *sup)
+                          uint32_t astep, uint32_t n, int have_copy_in, uint32_t first_valid, int mute, sks_list *sup, uint64_t pair_base)
 {
     const sd_sp *A = &ca->sp[s], *B = cb ? &cb->sp[s] : NULL;
     const uint64_t a_end = (uint64_t)a0 + (uint64_t)n * astep, b_end = (uint64_t)b0 + (uint64_t)n * astep;
@@ -2468,6 +2527,7 @@ static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk
         }
         if (!mute && p->h1 + p->h2 >= 1 && p->i1 + p->i2 >= 1) {
             uint32_t la = 0, lb = 0;
+            p->rar_pair = pair_base + j;
             if (have_copy_in || first_valid <= j) { emit_rows(p, p->copy_rows, p->copy_n, f1); la = p->copy_n; }
             if (b_valid == 1) { lb = B->hbeg[ib + 1] - B->hbeg[ib]; emit_rows(p, B->rows + B->hbeg[ib], lb, f1); }
             /* support: the emission, by the run's own --min-kmer-hits whatever emit_rows lets through for a threshold list */
@@ -2480,10 +2540,12 @@ static void sd_replay_run(sd_prog *p, uint32_t s, const char *f1, const sd_chunk
 
 /* Post one run to the lanes (they replay it strain by strain, behind the runs posted before); returns the (strain-independent)
  * have_copy afterwards.  The job holds the two chunks until every lane is through with it. */
-static int post_replay(const char *f1, sd_chunk *ca, uint32_t a0, sd_chunk *cb, uint32_t b0, uint32_t astep, uint32_t n, int have_copy)
+static int post_replay(const char *f1, sd_chunk *ca, uint32_t a0, sd_chunk *cb, uint32_t b0, uint32_t astep, uint32_t n, int have_copy,
+                       uint64_t pair_base)
 {
     sd_job *j = job_new(SD_JOB_REPLAY, ca, cb);
     uint32_t k;
+    j->pair_base = pair_base;
     j->f1 = f1; j->a0 = a0; j->b0 = b0; j->astep = astep; j->n = n; j->have_copy = have_copy;
     for (k = 0; k < n && ca->len[a0 + k * astep] < SK_K; k++) { }
     j->first_valid = k;
@@ -2529,11 +2591,22 @@ static int sd_background_target(sd_prog *p, uint32_t ns, const char *f1)
     return rc;
 }
 
+/* --coverage-rarefaction: a target's lines of strain p's table */
+static int sd_rarefaction_line(sd_prog *p, const char *f1, const uint64_t *pairs, const uint64_t *unique, const uint64_t *total)
+{
+    const char *base = strrchr(f1, '/') ? strrchr(f1, '/') + 1 : f1;
+    char *name = sd_rar.named ? sd_strain_name(p->o_path) : NULL;
+    int rc = !p->ra_f || (sd_rar.named && !name) ? SK_E_NOMEM : skh_rarefaction_write(p->ra_f, &sd_rar.r, name, base, pairs, unique, total);
+    free(name);
+    return rc;
+}
+
 static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, const char *f1, const char *f2, int mode)
 {
     sd_stream A, B;
     uint32_t s, j;
     int have_copy = 0, rc, got, status = 1;
+    uint64_t pairs_done = 0;                             /* the target's pairs in front of the run at hand: its pair 0's ordinal */
     double t_mark;
     unsigned long long evaluated = 0, reads = 0;
     FILE *err = p[0].err;
@@ -2553,6 +2626,15 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
     t_sopen += now_s() - t_mark;
     sd_co.mode = mode; sd_co.pe_a = mode == SD_PE ? &A : NULL;
     A.co_next = 0;
+    A.nrec_seen = 0; B.nrec_seen = 0;
+    if (sd_rar.on) {                                     /* nothing of the target before is left */
+        memset(sd_rar.host_pairs, 0, sizeof sd_rar.host_pairs);
+        for (s = 0; s < ns; s++) {
+            memset(p[s].rar_lines, 0, sizeof p[s].rar_lines);
+            if (!p[s].rar_best && !sd_co.acc && !(p[s].rar_best = (uint8_t *)malloc(p[s].ks.nrows ? p[s].ks.nrows : 1u))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
+            if (p[s].rar_best) memset(p[s].rar_best, 0, p[s].ks.nrows ? p[s].ks.nrows : 1u);
+        }
+    }
     if (sd_co.on && !sd_co.acc) sd_co_hostacc++;
     A.solo = mode != SD_PE;                              /* (two streams take turns at the tables: no scan ahead of the replay) */
 
@@ -2603,15 +2685,19 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
         if (sd_co.acc && n && ca->co == SD_CO_FOLDED &&
             (mode == SD_SE ? !cb : mode == SD_PEI ? cb == ca : cb && cb != ca && cb->co == SD_CO_FOLDED)) {
             /* the run was counted on the device: only the state its last pair leaves behind is replayed, and nothing is emitted */
-            sd_job *jb = job_new(SD_JOB_REPLAY, ca, cb);
+            sd_job *jb;
+            if (sd_rar.on && ca->co_base != pairs_done) { got = SK_E_STATE; break; }      /* (never: the fold numbered its pairs otherwise) */
+            jb = job_new(SD_JOB_REPLAY, ca, cb);
             jb->f1 = f1; jb->a0 = a0 + (n - 1) * astep; jb->b0 = b0 + (n - 1) * astep; jb->astep = astep; jb->n = 1; jb->have_copy = 1; jb->mute = 1;
             lanes_post(jb);
             have_copy = 1;
             sd_co_dev++;
         } else {
-            have_copy = post_replay(f1, ca, a0, cb, b0, astep, n, have_copy);
+            have_copy = post_replay(f1, ca, a0, cb, b0, astep, n, have_copy, pairs_done);
             if (sd_co.on) sd_co_replayed++;
+            for (j = 0; j < n && sd_rar.on; j++) sd_rar.host_pairs[skh_rarefaction_class(&sd_rar.r, pairs_done + j)]++;
         }
+        pairs_done += n;
         t_replay += now_s() - t_mark;
         if (held) { chunk_free(held); if (cb) A.ci++; }  /* PEI across a chunk boundary: the mate was A's next record */
         else {
@@ -2691,6 +2777,15 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
                     if (skc_add_class_counts(p[a + m].cov, f1, cu + (size_t)m * F, ct + (size_t)m * F, p[a + m].sw_c.F)) rc = SK_E_NOMEM;
                 if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
             }
+            if (sd_rar.on) {                                 /* the numbers per fraction: a pass of its own that changes no counter */
+                uint64_t rp[SK_COVACC_RAREFACTION_MAX], ru2[SK_UNION_MAX * SK_COVACC_RAREFACTION_MAX], rt2[SK_UNION_MAX * SK_COVACC_RAREFACTION_MAX], hp = 0;
+                uint32_t q;
+                rc = sk_covacc_finish_target_rarefaction(sd_co.acc[k], rp, ru2, rt2);
+                for (q = sd_rar.r.n; rc == SK_OK && q-- > 0u; ) { hp += sd_rar.host_pairs[q + 1]; rp[q] += hp; }     /* (the replayed runs' pairs) */
+                for (m = 0; m < n && rc == SK_OK; m++)
+                    rc = sd_rarefaction_line(&p[a + m], f1, rp, ru2 + (size_t)m * sd_rar.r.n, rt2 + (size_t)m * sd_rar.r.n);
+                if (rc != SK_OK) { pthread_mutex_unlock(&sd_dev_mu); free(ru); free(sp); got = rc; break; }
+            }
             if (sd_sup.acc) {                                /* the pairs behind the numbers, of the runs folded on the device */
                 uint64_t *sm = (uint64_t *)malloc(((size_t)3 * n + (size_t)2 * n * n) * sizeof *sm);
                 rc = sm ? sk_covacc_finish_target_support(sd_co.acc[k], sm, sm + n, sm + 2 * n, sm + 3 * n, sm + 3 * n + (size_t)n * n) : SK_E_NOMEM;
@@ -2716,6 +2811,20 @@ static int sd_quantify(sd_prog *p, uint32_t ns, sk_batch *batch, sd_pool *pool, 
         if (sd_rec.r) {                                      /* the host remembers ordinal -> sample name */
             if (!(sd_rec.name[sd_rec.next] = strdup(f1))) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
             sd_rec.next++;
+        }
+    }
+    if (sd_rar.on && !sd_co.acc) {                       /* counted on the host: every strain's rows by their highest class */
+        uint64_t rp[SK_COVACC_RAREFACTION_MAX], ru2[SK_COVACC_RAREFACTION_MAX], rt2[SK_COVACC_RAREFACTION_MAX];
+        for (s = 0; s < ns; s++) {
+            uint64_t rows[SK_COVACC_RAREFACTION_MAX + 1], hp = 0, hu = 0, ht = 0, i;
+            uint32_t q;
+            memset(rows, 0, sizeof rows);
+            for (i = 0; p[s].rar_best && i < p[s].ks.nrows; i++) rows[p[s].rar_best[i]]++;
+            for (q = sd_rar.r.n; q-- > 0u; ) {
+                hp += sd_rar.host_pairs[q + 1]; hu += rows[q + 1]; ht += p[s].rar_lines[q + 1];
+                rp[q] = hp; ru2[q] = hu; rt2[q] = ht;
+            }
+            if ((rc = sd_rarefaction_line(&p[s], f1, rp, ru2, rt2)) != SK_OK) { fprintf(err, "strain_detect: --coverage-rarefaction: %s on %s\n", sk_strerror(rc), f1); goto done; }
         }
     }
     if (sd_bg.on && (got = sd_background_target(p, ns, f1)) != SK_OK) {
@@ -3072,6 +3181,13 @@ static int sd_coverage_write(sd_prog *p)
         rc = skc_report_thresholds(p->cov, p->o_path, f, p->err);
         fclose(f);
     }
+    if (!rc && sd_rar.on && p->ra_f) {
+        if (fclose(p->ra_f)) rc = 1;
+        p->ra_f = NULL;
+        if (!rc && !(f = fopen(p->ra_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->ra_path); return 1; }
+        if (!rc) { rc = fwrite(p->ra_buf, 1, p->ra_len, f) != p->ra_len; if (fclose(f)) rc = 1; }
+        if (rc) fprintf(p->err, "strain_detect: error writing %s\n", p->ra_path);
+    }
     if (!rc && sd_sw.on) {
         if (!(f = fopen(p->sw_path, "w"))) { fprintf(p->err, "strain_detect: could not write %s\n", p->sw_path); return 1; }
         rc = skc_report_classes(p->cov, p->o_path, p->row_class, (uint32_t)p->ks.nrows, f, p->err);
@@ -3377,6 +3493,8 @@ static void sd_strain_close(sd_prog *p)
     if (p->ctx) { skh_pack_cache_set(p->ctx, NULL, NULL); sk_ctx_destroy(p->ctx); }
     skh_keyset_free(&p->ks);
     free(p->type); free(p->copy_rows); free(p->hitbuf); free(p->tallybuf); free(p->cov_path); free(p->o_path); free(p->co_rows); free(p->co_tot);
+    if (p->ra_f) fclose(p->ra_f);
+    free(p->ra_path); free(p->ra_buf); free(p->co_pair); free(p->rar_best);
     skc_destroy(p->cov);
     if (skh_regions_free) skh_regions_free(&p->rg);
     free(p->row_region); free(p->reg_inf); free(p->rg_path); free(p->sp_path); free(p->th_path); free(p->su_path); free(p->rc_path); free(p->rp_path);
@@ -3641,6 +3759,8 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     const char *rc_file = NULL, *rp_file = NULL;
     const char *sp_file = NULL, *sp_max = NULL, *ps_file = NULL, *th_file = NULL, *th_list = NULL;
     int want_th = 0, want_sw = 0, want_su = 0, want_sq = 0;
+    const char *ra_file = NULL, *ra_list = NULL, *ra_seed = NULL;
+    int want_ra = 0;
     const char *su_file = NULL, *sq_file = NULL;
     int want_bg = 0, want_bgs = 0;
     const char *bg_file = NULL, *bgs_file = NULL, *bg_max = NULL;
@@ -3704,6 +3824,18 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             th_file = argv[c][21] ? argv[c] + 22 : NULL;
             continue;
         }
+        /* "--coverage-rarefaction[=FILE] [--rarefaction-list f0,f1,...] [--rarefaction-seed S]": next to either table, the target's pairs
+         * and its two numbers over nested subsamples of its read pairs, from the one pass (default list 1,0.5,0.25,0.125,0.0625,0.03125,
+         * default seed 0), default FILE = outfile with ".kmer_hits.gz" replaced by ".coverage_rarefaction" */
+        if (!strncmp(argv[c], "--coverage-rarefaction", 22) && (argv[c][22] == 0 || argv[c][22] == '=')) {
+            want_ra = 1;
+            ra_file = argv[c][22] ? argv[c] + 23 : NULL;
+            continue;
+        }
+        if (!strcmp(argv[c], "--rarefaction-list") && c + 1 < argc) { ra_list = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--rarefaction-list=", 19)) { ra_list = argv[c] + 19; continue; }
+        if (!strcmp(argv[c], "--rarefaction-seed") && c + 1 < argc) { ra_seed = argv[++c]; continue; }
+        if (!strncmp(argv[c], "--rarefaction-seed=", 19)) { ra_seed = argv[c] + 19; continue; }
         if (!strcmp(argv[c], "--threshold-list") && c + 1 < argc) { th_list = argv[++c]; continue; }
         if (!strncmp(argv[c], "--threshold-list=", 17)) { th_list = argv[c] + 17; continue; }
         /* "--coverage-scrub-sweep[=FILE] [--scrub-classes FILE]": next to either table, its numbers at every min_fraction of the strain's
@@ -3774,6 +3906,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_rg.on = 0; sd_rg.genomes = NULL; sd_rg.ngenomes = 0;
     sd_spec.on = 0;
     sd_thr.on = 0;
+    sd_rar.on = 0;
     sd_sw.on = 0;
     sd_rec.on = 0;
     sd_co.on = 0;
@@ -3840,6 +3973,24 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
             if (end == sp_max || *end || errno || d < 1 || d > (long long)SK_COVACC_SPECTRUM_MAX) { fprintf(err, "strain_detect: --spectrum-max %s: a depth from 1 to %u\n", sp_max, SK_COVACC_SPECTRUM_MAX); return sd_drop(p, ns); }
         }
         sd_spec.max = (uint32_t)d;
+    }
+    if (want_ra || ra_list || ra_seed) {
+        unsigned long long seed = 0;
+        char *end = NULL;
+        if (!want_ra) { fprintf(err, "strain_detect: %s goes with --coverage-rarefaction\n", ra_list ? "--rarefaction-list" : "--rarefaction-seed"); return sd_drop(p, ns); }
+        if (!want_cov) { fputs("strain_detect: --coverage-rarefaction goes with --coverage-depth or --coverage-only: it gives their table's two numbers over nested subsamples of the read pairs\n", err); return sd_drop(p, ns); }
+        if (ra_file && ((S && !a && !o && !r) || (ad && ad->o))) { fputs("strain_detect: --coverage-rarefaction=FILE names one file; with several strains each table goes to its default path\n", err); return sd_drop(p, ns); }
+        if (ad) { fputs("strain_detect: --coverage-rarefaction does not go behind kmer_scrub_count --detect\n", err); return sd_drop(p, ns); }
+        if (!skh_rarefaction_parse || !skh_rarefaction_class || !skh_rarefaction_write) { fputs("strain_detect: --coverage-rarefaction: this build has no rarefaction table\n", err); return sd_drop(p, ns); }
+        if (ra_seed) {
+            errno = 0;
+            seed = strtoull(ra_seed, &end, 10);
+            if (end == ra_seed || *end || errno || seed > 0xFFFFFFFFull || ra_seed[0] == '-' || ra_seed[0] == '+' || ra_seed[0] == ' ') { fprintf(err, "strain_detect: --rarefaction-seed %s: an integer from 0 to 4294967295\n", ra_seed); return sd_drop(p, ns); }
+        }
+        if (skh_rarefaction_parse(ra_list, (uint32_t)seed, &sd_rar.r) != SK_OK) {
+            fprintf(err, "strain_detect: --rarefaction-list %s: 1 to %u decimal fractions, 0 < f <= 1, strictly descending, no two of them equal in 32 bits\n", ra_list, SK_COVACC_RAREFACTION_MAX);
+            return sd_drop(p, ns);
+        }
     }
     if (want_th || th_list) {
         static const int64_t dflt[8] = { 0, 1, 2, 3, 5, 10, 20, 50 };
@@ -3987,6 +4138,7 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
     sd_rg.on = want_rg;
     sd_spec.on = want_sp;
     sd_thr.on = want_th; sd_thr.ms_finish = 0;
+    sd_rar.on = want_ra; sd_rar.named = S != NULL; sd_rar.min = cov_min; sd_rar.ms_class = sd_rar.ms_finish = 0;
     sd_sw.on = want_sw; sd_sw.ms_cls = 0;
     sd_rec.on = want_rc; sd_rec.pairs = want_rp; sd_rec.next = 0;
     sd_rec.ms_mark = sd_rec.ms_hist = sd_rec.ms_gram = 0;
@@ -4097,6 +4249,11 @@ static int sd_main_impl(int argc, char **argv, FILE *out, FILE *err, const sd_ad
         if (sd_spectrum_open(&p[s], S || (ad && ad->o) ? NULL : sp_file)) goto done;
     for (s = 0; want_th && s < ns; s++)
         if (sd_thresholds_open(&p[s], S || (ad && ad->o) ? NULL : th_file)) goto done;
+    for (s = 0; want_ra && s < ns; s++) {
+        p[s].ra_path = sd_table_path(p[s].o_path, S || (ad && ad->o) ? NULL : ra_file, ".coverage_rarefaction");
+        p[s].ra_f = p[s].ra_path ? open_memstream(&p[s].ra_buf, &p[s].ra_len) : NULL;
+        if (!p[s].ra_f || skh_rarefaction_write(p[s].ra_f, &sd_rar.r, S ? "" : NULL, NULL, NULL, NULL, NULL) != SK_OK) { fprintf(err, "strain_detect: out of memory\n"); goto done; }
+    }
     for (s = 0; want_sw && s < ns; s++)
         if (sd_sweep_open(&p[s], &swc[s], S || (ad && ad->o) ? NULL : sw_file)) goto done;
     for (s = 0; want_su && s < ns; s++)
@@ -4181,6 +4338,9 @@ done:
     if (getenv("SK_SD_TIMING") && cov_only && want_th)
         fprintf(err, "strain_detect timing: thresholds on the device: %u thresholds, finishing passes %.3f ms (the folds above classify as well)\n",
                 sd_thr.n, sd_thr.ms_finish);
+    if (getenv("SK_SD_TIMING") && cov_only && want_ra)
+        fprintf(err, "strain_detect timing: rarefaction on the device: %u fractions, classifying passes %.3f ms (inside the folds above), finishing passes %.3f ms\n",
+                sd_rar.r.n, sd_rar.ms_class, sd_rar.ms_finish);
     if (getenv("SK_SD_TIMING") && cov_only && want_sw)
         fprintf(err, "strain_detect timing: scrub sweep on the device: class passes %.3f ms\n", sd_sw.ms_cls);
     if (getenv("SK_SD_TIMING") && cov_only && want_rc)
@@ -4203,6 +4363,7 @@ done:
     sd_rg.on = 0;
     sd_spec.on = 0;
     sd_thr.on = 0;
+    sd_rar.on = 0;
     sd_sw.on = 0;
     sd_rec.on = 0;
     sd_ps.path = NULL;

@@ -165,6 +165,8 @@ int sk_covacc_thresholds_timing_(sk_covacc *a, double *ms_thr);
 int sk_covacc_classes_timing_(sk_covacc *a, double *ms_cls);
 /* ... and of support: the takes inside the folds (a part of ms_fold) and the copies home (sk_covacc_finish_target_support) */
 int sk_covacc_support_timing_(sk_covacc *a, double *ms_take, double *ms_finish);
+/* ... and of rarefaction: the classifying passes and pair counts inside the folds (a part of ms_fold) and the finishing passes */
+int sk_covacc_rarefaction_timing_(sk_covacc *a, double *ms_class, double *ms_finish);
 /* The recurrence engine's planes (sk_recur.hip), for the feeders that set bits with kernels of their own (sk_covacc.hip,
  * sk_cover.hip): plane `sample` of member m begins at d_planes + sample * words + word_base[m] and holds (nbits[m] + 63) / 64
  * words; a feeder sets no bit at or above nbits[m] and synchronises before the engine's next call. */

@@ -78,6 +78,9 @@ ABI_SYMBOLS = [
     "sk_covacc_set_classes", "sk_covacc_finish_target_classes", "sk_distinct_classes",
     "sk_covacc_set_support", "sk_covacc_finish_target_support",
     "sk_scan_batch", "sk_background_finish", "sk_union_background_finish",
+    "sk_covacc_set_rarefaction", "sk_covacc_set_pair_base", "sk_covacc_add_pairs", "sk_covacc_add_rows_hits_pairs",
+    "sk_covacc_finish_target_rarefaction", "skh_rarefaction_parse", "skh_rarefaction_draw", "skh_rarefaction_class",
+    "skh_rarefaction_fold", "skh_rarefaction_write",
 ]
 
 
@@ -877,6 +880,40 @@ lib.sk_distinct_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void
 SK_COVACC_SUPPORT_MEMBERS_MAX = 1024
 lib.sk_covacc_set_support.argtypes = [C.c_void_p, C.c_int]
 lib.sk_covacc_finish_target_support.argtypes = [C.c_void_p] * 6
+SK_COVACC_RAREFACTION_MAX = 16
+DEFAULT_RAREFACTION = "1,0.5,0.25,0.125,0.0625,0.03125"
+lib.sk_covacc_set_rarefaction.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+lib.sk_covacc_set_pair_base.argtypes = [C.c_void_p, C.c_uint64]
+lib.sk_covacc_add_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+lib.sk_covacc_add_rows_hits_pairs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+lib.sk_covacc_finish_target_rarefaction.argtypes = [C.c_void_p] * 4
+lib.sk_covacc_rarefaction_timing_.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+
+
+class RarefactionList(C.Structure):
+    """skh_rarefaction: the parsed --rarefaction-list"""
+    _fields_ = [("n", C.c_uint32), ("seed", C.c_uint32), ("T", C.c_uint64 * 16), ("text", (C.c_char * 40) * 16)]
+
+
+lib.skh_rarefaction_parse.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(RarefactionList)]
+lib.skh_rarefaction_draw.argtypes = [C.c_uint64, C.c_uint32]
+lib.skh_rarefaction_draw.restype = C.c_uint32
+lib.skh_rarefaction_class.argtypes = [C.POINTER(RarefactionList), C.c_uint64]
+lib.skh_rarefaction_class.restype = C.c_uint32
+lib.skh_rarefaction_fold.argtypes = [C.POINTER(RarefactionList), C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def rarefaction_parse(text=None, seed=0):
+    """skh_rarefaction_parse: (T list, the fields' texts) of a --rarefaction-list (None: the default); SKError(SK_E_ARG) for a list
+    the rule refuses"""
+    r = RarefactionList()
+    rc = lib.skh_rarefaction_parse(None if text is None else text.encode(), seed, C.byref(r))
+    if rc != SK_OK:
+        raise SKError(rc, "rarefaction list %r" % (text,))
+    return [int(r.T[q]) for q in range(r.n)], [r.text[q].value.decode() for q in range(r.n)]
+
+
 lib.sk_covacc_timing_.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
 lib.sk_covacc_support_timing_.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
 
@@ -1236,6 +1273,46 @@ class CoverageAcc:
         tot = np.zeros_like(uq)
         self._ctx._ck(lib.sk_covacc_finish_target_thresholds(self._h, uq.ctypes.data, tot.ctypes.data))
         return uq[:, :nt], tot[:, :nt]
+
+    def set_rarefaction(self, T, seed=0):
+        """sk_covacc_set_rarefaction: an empty list turns rarefaction off; otherwise 1..SK_COVACC_RAREFACTION_MAX strictly descending
+        T[q] = floor(fraction * 2^32).  Whatever was classified since the last finish is discarded."""
+        t = np.ascontiguousarray(T, dtype=np.uint64).reshape(-1)
+        self._ctx._ck(lib.sk_covacc_set_rarefaction(self._h, t.ctypes.data if len(t) else None, len(t), int(seed) & 0xFFFFFFFF))
+        self._rar_n = len(t)
+
+    def set_pair_base(self, first_pair):
+        """sk_covacc_set_pair_base: the target's ordinal of pair 0 of the next add()'s run"""
+        self._ctx._ck(lib.sk_covacc_set_pair_base(self._h, int(first_pair)))
+
+    def add_pairs(self, first, n):
+        """sk_covacc_add_pairs: pairs first .. first + n - 1 of the target counted by class (replayed runs' pairs)"""
+        self._ctx._ck(lib.sk_covacc_add_pairs(self._h, int(first), int(n)))
+
+    def add_rows_hits_pairs(self, member, rows, total_hits, pair_ordinal):
+        """sk_covacc_add_rows_hits_pairs: add_rows_hits, each hit also with its pair's ordinal in the target (u64)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        total_hits = np.ascontiguousarray(total_hits, dtype=np.uint32)
+        pair_ordinal = np.ascontiguousarray(pair_ordinal, dtype=np.uint64)
+        assert len(rows) == len(total_hits) == len(pair_ordinal)
+        self._ctx._ck(lib.sk_covacc_add_rows_hits_pairs(self._h, member, rows.ctypes.data, total_hits.ctypes.data,
+                                                        pair_ordinal.ctypes.data, len(rows)))
+
+    def finish_target_rarefaction(self):
+        """sk_covacc_finish_target_rarefaction: (pairs[nq], unique[nmembers, nq], total[nmembers, nq]); the depth counters are not
+        touched, the rarefaction state is zero afterwards.  Call it before the sweep that ends the target."""
+        nq = getattr(self, "_rar_n", 0)
+        pairs = np.zeros(max(nq, 1), dtype=np.uint64)
+        uq = np.zeros((len(self.nrows), max(nq, 1)), dtype=np.uint64)
+        tot = np.zeros_like(uq)
+        self._ctx._ck(lib.sk_covacc_finish_target_rarefaction(self._h, pairs.ctypes.data, uq.ctypes.data, tot.ctypes.data))
+        return pairs[:nq], uq[:, :nq], tot[:, :nq]
+
+    def rarefaction_timing(self):
+        """(classifying passes ms, finishing passes ms) summed while timing() is on"""
+        a, b = C.c_double(0), C.c_double(0)
+        self._ctx._ck(lib.sk_covacc_rarefaction_timing_(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def set_classes(self, member, rows, cls, ncls):
         """sk_covacc_set_classes: member's rows[i] gets the scrub class cls[i] (1..ncls), every other row class 0; ncls = 0 (and no

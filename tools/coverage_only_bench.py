@@ -31,6 +31,12 @@ apart.
     python tools/coverage_only_bench.py --scrub-sweep --rounds 3 --parent-exe PATH [--out profiles/coverage_scrub_sweep_bench.txt]
     python tools/coverage_only_bench.py --support [--pairs] --rounds 3 --parent-exe PATH [--out profiles/coverage_support_bench.txt]
     python tools/coverage_only_bench.py --background --rounds 3 --parent-exe PATH [--out profiles/coverage_background_bench.txt]
+    python tools/coverage_only_bench.py --rarefaction --rounds 3 --parent-exe PATH [--out profiles/coverage_rarefaction_bench.txt]
+
+--rarefaction measures --coverage-rarefaction (the default list of six fractions) like --thresholds; each line with the flag also
+carries the device time of the classifying passes and pair counts (a part of the folds), the same per fold in microseconds (a fold: one
+unit's share of one run counted on the device) and the finishing passes of all targets.
+--kinds plain (or gz) keeps one kind of target: a second measurement of one case over more rounds.
 
 --support measures --coverage-support (--pairs: with --support-pairs=FILE) like --thresholds: the parent's plain --coverage-only runs in
 turn with this build's plain runs and its runs with the flag; each line with the flag also carries the device time of the takes (a
@@ -73,6 +79,7 @@ THR = re.compile(rb"thresholds on the device: (\d+) thresholds, finishing passes
 SUPT = re.compile(rb"support on the device: takes ([0-9.]+) ms \(inside the folds above\), finishes ([0-9.]+) ms")
 BGT = re.compile(rb"background: (\d+) count scans beside the TALLY launches, finishing sweeps ([0-9.]+) ms")
 SCN = re.compile(rb"scan kernels on the device: ([0-9.]+) ms in (\d+) launches")
+RAR = re.compile(rb"rarefaction on the device: (\d+) fractions, classifying passes ([0-9.]+) ms \(inside the folds above\), finishing passes ([0-9.]+) ms")
 SWP = re.compile(rb"scrub sweep on the device: class passes ([0-9.]+) ms")
 SWEEP_LIST = "0.5,0.4,0.3,0.2,0.1,0.05,0.02,0.01"
 BYTES = re.compile(rb"scan results copied from the device: (\d+) bytes; --coverage-only: (\d+) runs counted on the device, (\d+) replayed")
@@ -94,7 +101,8 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     for s in range(ns):
         for f in (f"out{s}.gz", f"out{s}.gz.coverage_depth", f"out{s}.gz.coverage_regions", f"out{s}.gz.coverage_spectrum",
                   f"out{s}.gz.coverage_recurrence", f"out{s}.gz.coverage_recurrence_pairs", f"out{s}.gz.coverage_thresholds",
-                  f"out{s}.gz.coverage_scrub_sweep", f"out{s}.gz.coverage_support", f"out{s}.gz.coverage_background", f"out{s}.gz.coverage_background_spectrum"):
+                  f"out{s}.gz.coverage_scrub_sweep", f"out{s}.gz.coverage_support", f"out{s}.gz.coverage_background", f"out{s}.gz.coverage_background_spectrum",
+                  f"out{s}.gz.coverage_rarefaction"):
             if os.path.exists(os.path.join(cwd, f)):
                 os.remove(os.path.join(cwd, f))
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
@@ -115,7 +123,7 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
             h.update(f.read())
     hr = hashlib.md5()
     for s in range(ns):
-        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds", "coverage_scrub_sweep", "coverage_support", "coverage_background", "coverage_background_spectrum"):    # (the table beside the coverage table, whichever the run wrote)
+        for ext in ("coverage_regions", "coverage_spectrum", "coverage_recurrence", "coverage_recurrence_pairs", "coverage_thresholds", "coverage_scrub_sweep", "coverage_support", "coverage_background", "coverage_background_spectrum", "coverage_rarefaction"):    # (the table beside the coverage table, whichever the run wrote)
             if os.path.exists(os.path.join(cwd, f"out{s}.gz.{ext}")):
                 with open(os.path.join(cwd, f"out{s}.gz.{ext}"), "rb") as f:
                     hr.update(f.read())
@@ -128,7 +136,9 @@ def step(exe, argv, env, limit, cwd, ns, hit_lists):
     su = SUPT.search(p.stderr)
     bg = BGT.search(p.stderr)
     sc = SCN.search(p.stderr)
-    return dict(bgscans=int(bg.group(1)) if bg else -1, bgsweep=float(bg.group(2)) if bg else float("nan"), scan=float(sc.group(1)) if sc else float("nan"),
+    ra = RAR.search(p.stderr)
+    return dict(rarcls=float(ra.group(2)) if ra else float("nan"), rarfin=float(ra.group(3)) if ra else float("nan"),
+                bgscans=int(bg.group(1)) if bg else -1, bgsweep=float(bg.group(2)) if bg else float("nan"), scan=float(sc.group(1)) if sc else float("nan"),
                 launches=int(sc.group(2)) if sc else -1,
                 take=float(su.group(1)) if su else float("nan"), supfin=float(su.group(2)) if su else float("nan"), cls=float(sw.group(1)) if sw else float("nan"), thr=float(th.group(2)) if th else float("nan"), mark=float(rc.group(1)) if rc else float("nan"), hist=float(rc.group(3)) if rc else float("nan"), gram=float(rc.group(4)) if rc else float("nan"),
                 fold=float(a.group(1)) if a else float("nan"), sweep=float(a.group(2)) if a else float("nan"), md5r=hr.hexdigest(), wall=wall, cpu=(r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime), md5=h.hexdigest(),
@@ -168,7 +178,8 @@ def regions_case(say, args, env, tmp, ns, kind, argv):
         say(f"    parent build, --coverage-only x{args.rounds}: pass {row(rs, 'passed', '.2f')} s; wall {row(rs, 'wall', '.2f')} s (same tables)")
 
 
-def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False, sweep=False, support=False, background=False):
+def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresholds=False, sweep=False, support=False, background=False,
+                  rarefaction=False):
     """--coverage-only without and with --coverage-spectrum (recurrence: --coverage-recurrence --recurrence-pairs; thresholds:
     --coverage-thresholds [--threshold-list ..]), alternating; the parent build's plain --coverage-only behind them -- with
     thresholds: in turn with them, round by round -- and the new build's medians set against the parent's"""
@@ -193,6 +204,10 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
         word, label = "background", "... --coverage-background --background-spectrum"
         thresholds = True
         env = dict(env, SK_SD_SCAN_TIMING="1")
+    if rarefaction:                                          # (measured like the thresholds: the parent's runs in turn, folds compared too)
+        with_sp = ["--coverage-only", "--coverage-rarefaction"]
+        word, label = "rarefaction", "... --coverage-rarefaction"
+        thresholds = True
     res = {"plain": [], "spectrum": [], "parent": []}
     md5 = md5s = None
     for rnd in range(args.rounds):
@@ -223,6 +238,11 @@ def spectrum_case(say, args, env, tmp, ns, kind, argv, recurrence=False, thresho
             if background and tag != "parent":
                 say(f"        scan kernels on the device: {row(rs, 'scan', '.3f')} ms in {rs[0]['launches']} launches" +
                     (f"; background: {rs[0]['bgscans']} count scans, finishing sweeps of all targets {row(rs, 'bgsweep', '.3f')} ms" if tag == "spectrum" else ""))
+            elif rarefaction and tag == "spectrum":
+                folds = rs[0]["dev"] * ((ns + 31) // 32)
+                say(f"        rarefaction on the device: classifying passes and pair counts of all folds {row(rs, 'rarcls', '.3f')} ms (a part of the folds "
+                    f"above): {' '.join(format(1e3 * r['rarcls'] / folds if folds else float('nan'), '.1f') for r in rs)} us per fold over {folds} folds; "
+                    f"finishing passes of all targets {row(rs, 'rarfin', '.3f')} ms")
             elif support and tag == "spectrum":
                 say(f"        support on the device: takes of all folds {row(rs, 'take', '.3f')} ms (a part of the folds above), finishes of all targets "
                     f"{row(rs, 'supfin', '.3f')} ms")
@@ -323,6 +343,8 @@ def main():
     ap.add_argument("--scrub-sweep", action="store_true", help="measure --coverage-scrub-sweep, step 2 at 8 fractions and the fused form")
     ap.add_argument("--support", action="store_true", help="measure --coverage-support, the parent build's runs in turn with this build's")
     ap.add_argument("--background", action="store_true", help="measure --coverage-background --background-spectrum, the parent build's runs in turn with this build's")
+    ap.add_argument("--rarefaction", action="store_true", help="measure --coverage-rarefaction, the parent build's runs in turn with this build's")
+    ap.add_argument("--kinds", default="plain,gz", help="the targets' kinds to measure: plain, gz or both")
     ap.add_argument("--pairs", action="store_true", help="... with --support-pairs=FILE as well")
     ap.add_argument("--stderr-dir", default=None, help="keep every run's stderr (the SK_SD_TIMING lines) in this directory")
     ap.add_argument("--out", default=None)
@@ -387,9 +409,12 @@ def main():
         try:
             for ns in counts:
                 for kind, lst in lists.items():
+                    if ("gz" if kind.endswith(".gz") else "plain") not in args.kinds.split(","):
+                        continue
                     argv = ["-S", f"S{ns}.txt", "-B", lst]
-                    if args.spectrum is not None or args.recurrence or args.thresholds or args.scrub_sweep or args.support or args.background:
-                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds, args.scrub_sweep, args.support, args.background)
+                    if args.spectrum is not None or args.recurrence or args.thresholds or args.scrub_sweep or args.support or args.background or args.rarefaction:
+                        spectrum_case(say, args, env, tmp, ns, kind, argv, args.recurrence, args.thresholds, args.scrub_sweep, args.support, args.background,
+                                      args.rarefaction)
                         continue
                     if args.regions is not None:
                         regions_case(say, args, env, tmp, ns, kind, argv)
