@@ -381,6 +381,33 @@ int  sk_background_finish(sk_ctx *ctx, uint32_t col, uint32_t type_col, uint32_t
                           uint64_t *out /* SK_BACKGROUND_WORDS(max_depth) */);
 int  sk_union_background_finish(sk_union *u, uint32_t ucol, uint32_t max_depth, uint64_t *out /* members x SK_BACKGROUND_WORDS(max_depth) */);
 
+/* PREVALENCE: in how many items of a list a k-mer occurs (new: kmer_scrub_count --prevalence; the reference has no counterpart).
+ * Step 1 adds every file of a list into ONE number per key -- the reference's count[vec_column] += 1 for every window of every
+ * file, src/genome_compare.c:220-223 -- and step 2 ranks by that sum, which a few deep samples or one sample that holds the strain
+ * decide.  Here the same sum is split per item: for list item j, v_j[row] = the windows of item j alone whose canonical 31-mer is
+ * the row's key (the COUNT scan's window rules, unchanged), so that
+ *   count[row]      = sum over j of v_j[row]              (mod 2^32: bit for bit the column step 1 always made)
+ *   prevalence[row] = the items j with v_j[row] >= min_count
+ * and per item j the record {kmers_present = rows with v_j >= min_count, kmer_hits = sum over rows of v_j} (u64 each).
+ * sk_item_slots: nslots pairs {scratch column u32[nrows], difference array u32[nrows + 2]} of the loaded table, all zero, and one
+ *   block-sums buffer; 0 frees them; a call replaces what an earlier call made.  At most SK_ITEM_SLOTS_MAX.  SK_E_NOMEM / SK_E_HIP
+ *   when they do not fit: nothing is kept and no HIP error is left behind.  SK_E_STATE without a table with count columns.  Loading
+ *   another table frees the slots.  Nothing is allocated unless this is called.
+ * sk_item_slot: from now on every COUNT scan of the context (sk_scan_stream, sk_scan_pinned[_packed][_many],
+ *   sk_scan_pinned_pack_many, sk_scan_text_pinned[_many], sk_scan_device[_packed], sk_scan_batch) adds into that slot, whatever
+ *   column it names; -1: into the column it names, as ever.  The column's own pending increments are left alone and stay pending.
+ *   TALLY launches ignore the slot.  The state is the context's: callers that scan from several threads set it under the lock
+ *   that orders their submits.
+ * sk_item_fold: behind every scan of the slot on either lane, on the context's stream: per row v = the slot's value;
+ *   counts[count_col][row] += v; counts[prev_col][row] += (v >= min_count); the slot is zero again; d_item_record[0] += the rows
+ *   with v >= min_count, d_item_record[1] += the sum of v.  d_item_record: two u64 in DEVICE memory (sk_dev_alloc; 8-byte aligned;
+ *   NULL: no record), zeroed by the caller, fetched when the caller likes after a sk_sync.  Asynchronous.  min_count >= 1 and
+ *   count_col != prev_col, else SK_E_ARG.  Folding an empty slot changes nothing. */
+#define SK_ITEM_SLOTS_MAX 256u
+int  sk_item_slots(sk_ctx *ctx, uint32_t nslots);
+int  sk_item_slot(sk_ctx *ctx, int slot);
+int  sk_item_fold(sk_ctx *ctx, uint32_t slot, uint32_t count_col, uint32_t prev_col, uint32_t min_count, uint64_t *d_item_record);
+
 /* Wait for all queued work of the context. */
 int sk_sync(sk_ctx *ctx);
 
@@ -419,7 +446,8 @@ int  sk_comm_sum_u32(sk_ctx *ctx, uint32_t value, uint32_t *sum);
 /* *agree = 1 iff every rank passed the same value (one max all-reduce of {v, ~v}); without a communicator: 1.
  * skh_scan_list uses it to compare the ranks' work plans before any of them scans. */
 int  sk_comm_agree_u64(sk_ctx *ctx, uint64_t value, int *agree);
-/* vals[i] = the maximum of vals[i] over all ranks, i < n <= 8 (one all-reduce); without a communicator: unchanged.  The list
+/* vals[i] = the maximum of vals[i] over all ranks, i < n (one all-reduce; above eight values through a device buffer made for the call: the items'
+ * records of a list walk with prevalence); without a communicator: unchanged.  The list
  * walk's two agreements per list are built on it (skh_scan_list below): whatever happens to a rank locally, every rank issues
  * the same sequence of collectives.  sk_comm_world: ranks of the context's communicator, 0 without one. */
 int  sk_comm_max_u64(sk_ctx *ctx, uint64_t *vals, uint32_t n);
@@ -513,6 +541,27 @@ int skh_scan_list(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t
  * scan_list_sharded).  skh_scan_list_uncut = skh_scan_list over the plan without byte-range pieces (SK_NO_SPLIT=1). */
 int skh_scan_list_uncut(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col,
                         FILE *progress, FILE *err, uint32_t rank, uint32_t world, uint64_t *bases);
+/* skh_scan_list with PREVALENCE (new: kmer_scrub_count --prevalence; the rule is at sk_item_fold): column `col` ends bit for bit as
+ * skh_scan_list leaves it, column `prev_col` gets, per row, the ITEMS of the list in which the row was seen at least min_count
+ * times, and *items_out one record per item in list order.  An ITEM is a list line whose file was opened: the line equal to
+ * `skip` is none (skipped with skh_scan_list's message), a file that cannot be opened fails the scan as it always did (SK_E_OPEN:
+ * nothing is handed out); a line listed twice is two items; an empty file is an item of no bases.  items_out->n is the
+ * denominator of the column.
+ * How: the list is planned UNCUT (skh_scan_list_uncut's plan, whatever the world: an item is whole on one rank); every decode
+ * thread owns an item slot (sk_item_slots: as many as the walk has threads), names it before each of its submits -- its helper
+ * threads of a split .gz item, the cache-served path, the pack-cache fill and the device text path included -- and enqueues the
+ * item's sk_item_fold when the item ends, whether it was served, parsed or failed part-way.  With several ranks the prevalence
+ * columns ride sk_counts_allreduce like any column; the items' records are merged by ONE sk_comm_max_u64 per list (a cell is
+ * non-zero on its owner only), issued by every rank behind the agreement that closes the scan.  The setting enters the plan
+ * hash: ranks that disagree about it, about prev_col or about min_count leave with SK_E_PLAN.
+ * SK_E_ARG: min_count 0, col == prev_col, no items_out.  SK_E_STATE: a build whose device layer has no item slots.
+ * skh_prev_items_free releases what a call handed out (and zeroes the struct). */
+typedef struct { uint32_t line;            /* 1-based line of the list file */
+                 char *path; uint64_t bases, kmers_present, kmer_hits; } skh_prev_item;
+typedef struct { skh_prev_item *item; uint32_t n; } skh_prev_items;
+int  skh_scan_list_prevalence(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, uint32_t prev_col, uint32_t min_count,
+                              skh_prev_items *items_out, FILE *progress, FILE *err, uint32_t rank, uint32_t world, uint64_t *bases);
+void skh_prev_items_free(skh_prev_items *items);
 /* skh_scan_list into n contexts on one device over ONE decode of the list (new: kmer_scrub_count -S feeds every resident union
  * from one walk): each chunk goes up once and is scanned into column `col` of every ctx[i] (sk_scan_pinned[_packed]_many; packed
  * or bytes is decided once per chunk, for all of them).  A cut that does not hold puts back the column of EVERY context before the
@@ -671,6 +720,10 @@ int skh_scrub_filter_main(int argc, char **argv, FILE *out, FILE *err);
  * computed from the resident counters (columns 1, 2 and, with_drug_column, 3). */
 int skh_scrub_filter_resident(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, double min_fraction,
                               int independent, FILE *out, FILE *err);
+/* ... from three other columns {pangenome, metagenome, drug} of the resident table (new: kmer_scrub_count --scrub-by prevalence
+ * hands in the prevalence columns): what the script would print for a table with those columns in place of the counts */
+int skh_scrub_filter_resident_cols(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, const uint32_t cols[3], double min_fraction,
+                                   int independent, FILE *out, FILE *err);
 /* ... at a list of fractions "f0,f1,..." (the scrub sweep above): the run at f0, and the class file to classes_path; 1 for a bad list */
 int skh_scrub_filter_resident_sweep(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, const char *fraction_list,
                                     int independent, const char *classes_path, FILE *out, FILE *err);

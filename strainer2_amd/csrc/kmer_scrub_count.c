@@ -4,6 +4,8 @@
  * Extension: -S <strains file> WITHOUT -r counts many strains over one pass of the lists
  * (skh_kmer_scrub_count_multi_main), and with --scrub .. --detect takes them on through steps 2-3 (and 4); with -r, -S is what
  * the reference makes of it (usage, ignored).
+ * Extension: --prevalence[=FILE] [--prevalence-min-count m] [--prevalence-items=FILE] [--scrub-by prevalence] (with -r): in how
+ * many items of each list a k-mer occurs, beside the counts.
  * All of the work happens in libstrainer_kmer.so (host layer in C, scan in HIP on gfx950). */
 #include <stdio.h>
 #include <string.h>

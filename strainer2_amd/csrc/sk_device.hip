@@ -95,6 +95,12 @@ struct sk_ctx {
     uint32_t     infbits_col, infbits_val; bool infbits_ok;
     uint32_t    *d_diff, *d_diff_sums;// difference array of the column being scanned [nrows + 1] and its block sums
     int          diff_col;            // the column d_diff belongs to, -1 = nothing pending
+    // item slots (sk_item_slots): per slot a scratch column [nrows] and a difference array [nrows + 2] of its own, one allocation;
+    // while item_slot >= 0 every COUNT scan adds into that slot and sk_item_fold (sk_prevalence.hip) moves it into the columns
+    uint32_t    *d_item, *d_item_sums;
+    uint32_t     item_nslots;
+    size_t       item_stride;         // u32 words from one slot to the next (a multiple of 4)
+    int          item_slot;           // the slot COUNT scans go into, -1 = the column they name
     std::vector<uint32_t> h_perm;     // host copy of the permutation (empty = identity)
     // wide keys
     char        *d_wide_keys;
@@ -214,6 +220,7 @@ extern "C" int sk_ctx_create(sk_ctx **out, int device)
     c->table_load_pct = 50;
     c->grid_kib = -1;
     c->diff_col = -1;
+    c->item_slot = -1;
     c->err[0] = 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return SK_E_NODEVICE; }
     if (hipMalloc((void **)&c->d_flags, 32 * sizeof(uint32_t)) != hipSuccess) { delete c; return SK_E_NOMEM; }   // (words 16..31: scratch of the small collectives)
@@ -354,6 +361,9 @@ static void sk_table_release(sk_ctx *c)
     hipFree(c->d_diff); c->d_diff = NULL;
     hipFree(c->d_diff_sums); c->d_diff_sums = NULL;
     c->diff_col = -1;
+    hipFree(c->d_item); c->d_item = NULL;
+    hipFree(c->d_item_sums); c->d_item_sums = NULL;
+    c->item_nslots = 0; c->item_slot = -1;
     hipFree(c->d_infbits); c->d_infbits = NULL; c->infbits_ok = false;
     hipFree(c->d_wide_keys); c->d_wide_keys = NULL;
     hipFree(c->d_wide_rows); c->d_wide_rows = NULL;
@@ -760,6 +770,75 @@ static int sk_diff_flush(sk_ctx *c)
 
 static int sk_scratch(sk_ctx *c, void **p, size_t *cap, size_t need);
 
+// ---- item slots: a list item's scans kept apart until the item ends (kmer_scrub_count --prevalence; include/strainer_kmer.h) ----
+static inline size_t sk_item_diff_at(uint32_t nrows) { return ((size_t)nrows + 3u) & ~(size_t)3u; }       // the difference array behind the scratch column
+static int sk_item_release(sk_ctx *c)
+{
+    if (c->d_item || c->d_item_sums) {                        // (a scan of either lane may still add to them)
+        int jrc = sk_lanes_join(c);
+        if (jrc) return jrc;
+        SK_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    hipFree(c->d_item); c->d_item = NULL;
+    hipFree(c->d_item_sums); c->d_item_sums = NULL;
+    c->item_nslots = 0; c->item_slot = -1;
+    return SK_OK;
+}
+extern "C" int sk_item_slots(sk_ctx *c, uint32_t nslots)
+{
+    if (!c) return SK_E_ARG;
+    if (nslots > SK_ITEM_SLOTS_MAX) return sk_fail(c, SK_E_ARG, "%u item slots (at most %u)", nslots, SK_ITEM_SLOTS_MAX);
+    SK_HIP(c, hipSetDevice(c->device));
+    { int rc = sk_item_release(c); if (rc) return rc; }
+    if (!nslots) return SK_OK;
+    if (!c->d_keys || !c->d_counts) return sk_fail(c, SK_E_STATE, "item slots need a table with count columns");
+    const size_t stride = (sk_item_diff_at(c->nrows) + (size_t)c->nrows + 2u + 3u) & ~(size_t)3u;
+    const size_t bytes = stride * nslots * 4;
+    hipError_t e = hipMalloc((void **)&c->d_item, bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_item_sums, ((size_t)c->nrows / SK_DIFF_PER_BLOCK + 2) * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_item, 0, bytes, c->stream);
+    if (e != hipSuccess) {                                    // (no error left behind for a later hipGetLastError: the caller may go on without slots)
+        (void)hipGetLastError();
+        hipFree(c->d_item); c->d_item = NULL;
+        hipFree(c->d_item_sums); c->d_item_sums = NULL;
+        (void)hipGetLastError();
+        return sk_fail(c, e == hipErrorOutOfMemory ? SK_E_NOMEM : SK_E_HIP, "sk_item_slots: %u slots of %zu bytes: %s", nslots, stride * 4, hipGetErrorString(e));
+    }
+    c->item_nslots = nslots; c->item_stride = stride;
+    c->lane1_behind = true;                                   // (lane 1's next scan waits for the zeroing)
+    return SK_OK;
+}
+extern "C" int sk_item_slot(sk_ctx *c, int slot)
+{
+    if (!c) return SK_E_ARG;
+    if (slot < -1 || (slot >= 0 && (uint32_t)slot >= c->item_nslots)) return sk_fail(c, SK_E_ARG, "item slot %d of %u", slot, c->item_nslots);
+    c->item_slot = slot;
+    return SK_OK;
+}
+extern "C" int sk_item_view_(sk_ctx *c, uint32_t slot, uint32_t count_col, uint32_t prev_col, sk_item_view *v)
+{
+    if (!c || !v) return SK_E_ARG;
+    if (slot >= c->item_nslots) return sk_fail(c, SK_E_ARG, "item slot %u of %u", slot, c->item_nslots);
+    if (!c->d_counts || count_col >= c->ncols || prev_col >= c->ncols || count_col == prev_col) return sk_fail(c, SK_E_ARG, "bad column");
+    SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }       // (both lanes add to the slot; lane 1's next scan waits for the fold)
+    if (c->infbits_col == count_col || c->infbits_col == prev_col) c->infbits_ok = false;
+    v->device = c->device; v->stream = (void *)c->stream; v->nrows = c->nrows;
+    v->d_scratch = c->d_item + (size_t)slot * c->item_stride; v->d_diff = v->d_scratch + sk_item_diff_at(c->nrows);
+    v->d_sums = c->d_item_sums;
+    v->d_count = c->d_counts + (size_t)count_col * c->nrows; v->d_prev = c->d_counts + (size_t)prev_col * c->nrows;
+    return SK_OK;
+}
+// block sums of a difference array of n entries and their exclusive scan, on the context's stream
+extern "C" int sk_diff_sums_(sk_ctx *c, const uint32_t *d_diff, uint32_t n, uint32_t *d_sums)
+{
+    const uint32_t nb = (n + SK_DIFF_PER_BLOCK - 1u) / SK_DIFF_PER_BLOCK;
+    hipLaunchKernelGGL(sk_diff_block_sums, dim3(nb), dim3(256), 0, c->stream, d_diff, n, d_sums);
+    hipLaunchKernelGGL(sk_diff_scan_sums, dim3(1), dim3(1024), 0, c->stream, d_sums, nb);
+    SK_HIP(c, hipGetLastError());
+    return SK_OK;
+}
+
 // The forms of the two scan kernels that exist, by the facts of the launch: the hit goes to the per-record tallies (`tally`) or to
 // the column's counters, the table is a union of strains (`un`: TALLY only -- a sink with strains IS a tally sink), the stream is
 // read through the partitioned pipeline's candidate map (`cand`) or came packed by the host (`packed`).  Eight forms of the grid
@@ -807,6 +886,10 @@ static int sk_launch_scan(sk_ctx *c, const uint8_t *d_stream, uint64_t nbytes, u
         if (col == c->infbits_col) c->infbits_ok = false;      // (the column the bitmap was made from is about to change)
         sink.counts = c->d_counts + (size_t)col * c->nrows;
         sink.diff = c->d_diff;
+        if (c->item_slot >= 0) {                              // an item's scans: into the slot's own pair, d_diff and diff_col left alone
+            sink.counts = c->d_item + (size_t)c->item_slot * c->item_stride;
+            sink.diff = sink.counts + sk_item_diff_at(c->nrows);
+        } else
         if (tv.text2 && c->diff_col != (int)col) {            // the difference array serves one column at a time
             int rc = sk_diff_flush(c);
             if (rc) return rc;
@@ -2309,9 +2392,21 @@ extern "C" int sk_comm_sum_u32(sk_ctx *c, uint32_t value, uint32_t *sum)
 // sequence of these whatever happens to it locally).  No communicator: the values stay as they are.
 extern "C" int sk_comm_max_u64(sk_ctx *c, uint64_t *vals, uint32_t n)
 {
-    if (!vals || n == 0 || n > 8) return SK_E_ARG;
+    if (!vals || n == 0) return SK_E_ARG;
     if (!c || !c->comm) return SK_OK;
     SK_HIP(c, hipSetDevice(c->device));
+    if (n > 8) {                                      // (the items' records of a list with prevalence: a buffer of its own for the call)
+        uint64_t *d = NULL;
+        SK_UNION_MALLOC(c, hipMalloc((void **)&d, 8u * (size_t)n));
+        const int ncclUint64 = 5, ncclMax = 2;
+        hipError_t e = hipMemcpyAsync(d, vals, 8u * (size_t)n, hipMemcpyHostToDevice, c->stream);
+        const bool sent = e == hipSuccess && g_rccl.allreduce(d, d, n, ncclUint64, ncclMax, c->comm, c->stream) == 0;
+        if (sent) e = hipMemcpyAsync(vals, d, 8u * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d);
+        if (e != hipSuccess) return sk_fail(c, SK_E_HIP, "sk_comm_max_u64 failed: %s", hipGetErrorString(e));
+        return sent ? SK_OK : sk_fail(c, SK_E_RCCL, "ncclAllReduce failed");
+    }
     uint64_t *d = (uint64_t *)(c->d_flags + 16);      // scratch words of the flag block (64 bytes in: 8-byte aligned)
     SK_HIP(c, hipMemcpyAsync(d, vals, 8u * n, hipMemcpyHostToDevice, c->stream));
     const int ncclUint64 = 5, ncclMax = 2;            // rccl.h: ncclDataType_t / ncclRedOp_t

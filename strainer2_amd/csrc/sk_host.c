@@ -846,7 +846,7 @@ static int parse_from(const char *path, uint64_t off, rec_fn fn, void *user, int
  * caller's text buffer (NULL at first; made here, grown here when a piece must grow; the caller gives it back with sk_pinned_free when
  * its walk is over -- that call drains the context, so it is not made per file). */
 static int text_scan(sk_ctx *const *ctxs, uint32_t nctx, pthread_mutex_t *mu, const char *path, uint32_t col, uint64_t *bases,
-                     int64_t *nrecords, uint64_t *resume, uint8_t **tbuf, uint64_t *tcap)
+                     int64_t *nrecords, uint64_t *resume, uint8_t **tbuf, uint64_t *tcap, int slot /* the item's slot, named before every scan; -1: none */)
 {
     sk_ctx *const ctx = ctxs[0];
     const int fd = open(path, O_RDONLY);
@@ -874,6 +874,7 @@ static int text_scan(sk_ctx *const *ctxs, uint32_t nctx, pthread_mutex_t *mu, co
         if (off + have >= (uint64_t)st.st_size) eof = 1;
         if (!have) break;
         if (mu) pthread_mutex_lock(mu);
+        if (slot >= 0) (void)sk_item_slot(ctx, slot);
         rc = sk_scan_text_pinned_many(ctxs, nctx, buf, have, eof, col, &info);
         if (mu) pthread_mutex_unlock(mu);
         if (rc != SK_OK) break;
@@ -1040,7 +1041,7 @@ int skh_scan_file(sk_ctx *ctx, const char *path, uint32_t col, uint64_t *bases)
         uint64_t resume = TEXT_WHOLE, b = 0, tcap = 0;
         uint8_t *tbuf = NULL;
         int64_t nrec = 0;
-        int trc = text_scan(&ctx, 1, NULL, path, col, &b, &nrec, &resume, &tbuf, &tcap);
+        int trc = text_scan(&ctx, 1, NULL, path, col, &b, &nrec, &resume, &tbuf, &tcap, -1);
         if (tbuf) sk_pinned_free(ctx, tbuf);
         if (trc != TEXT_NOT_TAKEN) {
             if (trc == SK_OK && resume != TEXT_WHOLE) {
@@ -1118,7 +1119,27 @@ typedef struct {
     double          pc_t_sum, pc_t_read, pc_t_write;               /* ... seconds summed over the threads: checksums, reading, writing */
     uint64_t        pc_bytes;                                      /* ... cache bytes read or written */
     int             pc_rw;                                         /* ... the directory may be written */
+    /* prevalence (skh_scan_list_prevalence): every decode thread's index is its item slot, named under submit_mu before each submit;
+     * an item's fold is enqueued when it ends, its record cell is that of its list line */
+    int             prev;
+    uint32_t        prev_col, prev_min;
+    uint64_t       *d_rec;             /* device: {kmers_present, kmer_hits} per list line */
+    uint64_t       *line_bases;        /* host: the bases of each list line's item (under queue_mu) */
 } scan_pool;
+
+/* The host-only test builds link this file against device doubles without item slots (a walk with prevalence is refused there) */
+#pragma weak sk_item_slots
+#pragma weak sk_item_slot
+#pragma weak sk_item_fold
+#pragma weak sk_dev_alloc
+#pragma weak sk_dev_free
+#pragma weak sk_dev_upload
+#pragma weak sk_dev_download
+#pragma weak skh_scrub_filter_resident_cols
+#pragma weak sk_item_fold_timing_
+
+/* under submit_mu, just before a submit: the scans that follow belong to this slot's item */
+static inline void pool_slot(const scan_pool *p, int slot) { if (p->prev) (void)sk_item_slot(p->ctx, slot); }
 
 /* The progress file gets a list line when a decode thread TAKES the line's (first) item, and every line before it that is
  * not there yet -- the reference writes the line, then opens the file.  Called under queue_mu (or from the one thread). */
@@ -1157,6 +1178,7 @@ typedef struct {
     uint8_t   *fill_tmp;               /* the host's pack of a chunk that went up as bytes (builds without the device pack) */
     int        pend, pend_i; const uint8_t *pend_chunk; uint64_t pend_n;
     double     t_pc_sum, t_pc_read; uint64_t pc_bytes;
+    int        slot;                   /* prevalence: this thread's item slot (a split .gz item's helpers: their parent's) */
 } scan_worker;
 
 /* size of a worker's chunk buffer: SK_CHUNK_BYTES (4096 .. 63 MiB; tests use small ones: many flushes per file), default 32 MiB */
@@ -1232,6 +1254,7 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
             if (!odd) {
                 pthread_mutex_lock(&w->pool->submit_mu);
                 t1 = w->pool->timing ? now_s() : 0.0;
+                pool_slot(w->pool, w->slot);
                 rc = pool_submit(w->pool, w->pk[i], nbytes, 1, &w->pk_ticket[i]);
                 pthread_mutex_unlock(&w->pool->submit_mu);
                 if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; w->npacked++; }
@@ -1254,6 +1277,7 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
             if (w->pool->timing) { t1 = now_s(); w->t_ticket += t1 - t0; t0 = t1; }
             pthread_mutex_lock(&w->pool->submit_mu);
             t1 = w->pool->timing ? now_s() : 0.0;
+            pool_slot(w->pool, w->slot);
             rc = sk_scan_pinned_pack_many(w->pool->ctxs, w->pool->nctx, chunk, nbytes, w->pool->col, w->pk[i], &w->pkodd[i], &w->pk_ticket[i]);
             pthread_mutex_unlock(&w->pool->submit_mu);
             if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; }
@@ -1266,6 +1290,7 @@ static int worker_sink(void *user, const uint8_t *chunk, uint64_t nbytes)
     }
     pthread_mutex_lock(&w->pool->submit_mu);
     t1 = w->pool->timing ? now_s() : 0.0;
+    pool_slot(w->pool, w->slot);
     rc = pool_submit(w->pool, chunk, nbytes, 0, &w->ticket[w->cur]);
     pthread_mutex_unlock(&w->pool->submit_mu);
     if (w->pool->timing) { w->t_submit_wait += t1 - t0; w->t_submit += now_s() - t1; w->nchunks++; }
@@ -1410,6 +1435,7 @@ typedef struct {
     int nq, done, stop, rc;
     uint64_t bases; int64_t nrec;
     skpc_writer *fill;                 /* the item's cache file being written (or NULL): every helper's chunks go there */
+    int slot;                          /* the item's slot (prevalence): the helpers' chunks are their parent's item's */
 } gz_split;
 
 static void *gz_split_worker(void *arg)
@@ -1418,6 +1444,7 @@ static void *gz_split_worker(void *arg)
     scan_worker w;
     worker_init(&w, g->pool);
     w.fill = g->fill;
+    w.slot = g->slot;
     for (;;) {
         gz_seg *sg;
         int stop;
@@ -1492,6 +1519,7 @@ static int64_t parse_gz_split(scan_worker *w, const scan_item *it, uint64_t *bas
     memset(&g, 0, sizeof g);
     g.pool = w->pool;
     g.fill = w->fill;
+    g.slot = w->slot;
     pthread_mutex_init(&g.mu, NULL);
     pthread_cond_init(&g.cv, NULL);
     for (i = 0; i < npar; i++) if (pthread_create(&th[nth], NULL, gz_split_worker, &g) == 0) nth++;
@@ -1616,7 +1644,7 @@ static int64_t worker_item_parse(scan_worker *w, const scan_item *it, uint64_t *
 #endif
     if (!it->ranged && w->pool->text) {
         uint64_t resume = TEXT_WHOLE;
-        rc = text_scan(w->pool->ctxs, w->pool->nctx, &w->pool->submit_mu, it->path, w->pool->col, bases, &nrec, &resume, &w->tbuf, &w->tcap);
+        rc = text_scan(w->pool->ctxs, w->pool->nctx, &w->pool->submit_mu, it->path, w->pool->col, bases, &nrec, &resume, &w->tbuf, &w->tcap, w->pool->prev ? w->slot : -1);
         if (rc != TEXT_NOT_TAKEN) {
             if (rc != SK_OK) return rc;
             if (resume == TEXT_WHOLE) return nrec;
@@ -1675,6 +1703,7 @@ static int64_t worker_serve(scan_worker *w, const scan_item *it, uint64_t *bases
             pthread_mutex_lock(&p->submit_mu);
             {
                 const double t2 = p->timing ? now_s() : 0.0;
+                pool_slot(p, w->slot);
                 rc = pool_submit(p, w->pk[i], sg.stream_len, 1, &w->pk_ticket[i]);
                 pthread_mutex_unlock(&p->submit_mu);
                 if (p->timing) { w->t_submit_wait += t2 - t1; w->t_submit += now_s() - t2; w->nchunks++; w->npacked++; }
@@ -1691,6 +1720,7 @@ static int64_t worker_serve(scan_worker *w, const scan_item *it, uint64_t *bases
             pthread_mutex_lock(&p->submit_mu);
             {
                 const double t2 = p->timing ? now_s() : 0.0;
+                pool_slot(p, w->slot);
                 rc = pool_submit(p, buf, sg.stream_len, 0, &w->ticket[w->cur]);
                 pthread_mutex_unlock(&p->submit_mu);
                 if (p->timing) { w->t_submit_wait += t2 - t1; w->t_submit += now_s() - t2; w->nchunks++; }
@@ -1793,6 +1823,19 @@ static int scan_file_cached(sk_ctx *ctx, const char *path, uint32_t col, uint64_
     return r < 0 ? (int)r : SK_OK;
 }
 
+/* prevalence: where an item ends -- served, parsed or failed part-way -- its slot is folded into the two columns and its record
+ * cell; what was scanned does not stay in the slot.  Returns the item's status (a fold that fails makes a good item fail). */
+static int64_t worker_item_end(scan_worker *w, const scan_item *it, int64_t rc)
+{
+    scan_pool *const p = w->pool;
+    int frc;
+    if (!p->prev) return rc;
+    pthread_mutex_lock(&p->submit_mu);
+    frc = sk_item_fold(p->ctx, (uint32_t)w->slot, p->col, p->prev_col, p->prev_min, p->d_rec + 2u * (size_t)it->line);
+    pthread_mutex_unlock(&p->submit_mu);
+    return rc >= 0 && frc != SK_OK ? (int64_t)frc : rc;
+}
+
 static void *pool_worker(void *arg)
 {
     scan_pool *p = (scan_pool *)arg;
@@ -1800,6 +1843,7 @@ static void *pool_worker(void *arg)
     int wrc = worker_init(&w, p);
     pthread_setname_np(pthread_self(), "sk-decode");
     pthread_mutex_lock(&p->queue_mu);
+    w.slot = p->worker_ids;
     w.dev_ok = p->worker_ids++ < p->dev_workers;
     pthread_mutex_unlock(&p->queue_mu);
     for (;;) {
@@ -1815,7 +1859,9 @@ static void *pool_worker(void *arg)
         {
             const double t0 = p->timing ? now_s() : 0.0;
             rc = wrc != SK_OK ? wrc : worker_item(&w, &p->item[i], &bases);
+            rc = worker_item_end(&w, &p->item[i], rc);
             pthread_mutex_lock(&p->queue_mu);
+            if (p->prev) p->line_bases[p->item[i].line] = bases;
             if (p->timing) p->t_item += now_s() - t0;
         }
         p->bases += bases;
@@ -1912,9 +1958,12 @@ typedef struct { uint32_t **snap; uint32_t nsnap; long prog_at; int armed; } spl
 #define LIST_FAIL_OPEN  1u    /* agreement before the scan: this rank could not read the list itself */
 #define LIST_FAIL_GUARD 2u    /*                            ... could not copy its column (no memory, device error) */
 
+/* prevalence (skh_scan_list_prevalence): the second column, the threshold, and where the items' records go */
+typedef struct { uint32_t prev_col, min_count; skh_prev_items *items; } prev_opts;
+
 static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                           FILE *err, uint32_t rank, uint32_t world, uint64_t *bases, int plan_only, const plan_report *report,
-                          int no_split, split_guard *guard)
+                          int no_split, split_guard *guard, const prev_opts *pv)
 {
     sk_ctx *const ctx = ctxs ? ctxs[0] : NULL;       /* (plan only: no context) */
     FILE *fp = fopen(list_path, "r");
@@ -1932,6 +1981,7 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
     int any_ranged = 0, coordinated, by_other = 0;
     char *pc_dir = NULL;                        /* the packed input cache's directory for this scan (NULL: none) */
     int pc_mode = SKPC_RW, pc_asked = 0;
+    int prev_failed = 0;                        /* prevalence: the slots or the record array could not be made */
     if (world == 0) world = 1;
     /* several ranks act together only when all of them are in the library's communicator */
     coordinated = world <= 1 || (ctx && (uint32_t)sk_comm_world(ctx) == world);
@@ -2067,6 +2117,10 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
     owner = (uint32_t *)malloc(((size_t)nall + 1) * sizeof *owner);
     plan_owners(all, est, nall, world, owner);
     plan_hash = plan_digest(all, owner, nall, world);
+    if (pv) {                                             /* the uncut plan with prevalence is another plan than the uncut plan */
+        const uint32_t w[4] = {0x76657270u, pv->prev_col, pv->min_count, nline};
+        plan_hash = fnv_bytes(plan_hash, w, sizeof w);
+    }
     if (report && report->hash) *report->hash = plan_hash;
     if (report && report->nlines) *report->nlines = nline;
     if (report && report->owner) {                        /* who scans which list line (SKH_PLAN_SKIPPED / SKH_PLAN_SHARED) */
@@ -2151,7 +2205,32 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
         }
 #endif
     }
-    if (plan_only) {
+    if (pv && !plan_only && pool.nitem) {
+        /* a slot per decode thread, a record cell per list line (the cells of lines this rank does not own stay zero) */
+        const uint32_t nslots = nthreads == 1 ? 1u : (uint32_t)nthreads > pool.nitem ? pool.nitem : (uint32_t)nthreads;
+        const size_t rbytes = (size_t)nline * 2u * sizeof(uint64_t);
+        int prc;
+        pool.prev_col = pv->prev_col; pool.prev_min = pv->min_count;
+        pool.line_bases = (uint64_t *)calloc((size_t)nline + 1, sizeof *pool.line_bases);
+        prc = pool.line_bases ? sk_item_slots(ctx, nslots) : SK_E_NOMEM;
+        if (prc == SK_OK) prc = sk_dev_alloc(ctx, (void **)&pool.d_rec, rbytes);
+        if (prc == SK_OK) {
+            uint64_t *z = (uint64_t *)calloc((size_t)nline * 2u + 1, sizeof *z);
+            prc = z ? sk_dev_upload(ctx, pool.d_rec, z, rbytes) : SK_E_NOMEM;
+            free(z);
+        }
+        if (prc != SK_OK) {
+            if (err) fprintf(err, "kmer_scrub_count: no room for %u item slots (--prevalence): %s (%s)\n", nslots, sk_strerror(prc), sk_last_error(ctx));
+            pool.rc = prc; pool.rc_index = 0; prev_failed = 1;
+        } else {
+            pool.prev = 1;
+            if (pool.timing && sk_item_fold_timing_) (void)sk_item_fold_timing_(ctx, 1, NULL, NULL);
+            if (pool.timing && err)
+                fprintf(err, "kmer_scrub_count timing: prevalence: %s: %u item slots take %.1f MB of HBM\n", list_path, nslots,
+                        1e-6 * (double)nslots * (2.0 * (double)sk_table_rows(ctx) + 8.0) * 4.0);
+        }
+    }
+    if (plan_only || prev_failed) {
         /* nothing is scanned */
     } else if (nthreads == 1) {                               /* strict sequence, as the reference */
         scan_worker seq;
@@ -2162,6 +2241,8 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
             int64_t rc;
             progress_upto(&pool, pool.item[i].line);
             rc = seq_rc != SK_OK ? seq_rc : worker_item(&seq, &pool.item[i], &b);
+            if (seq_rc == SK_OK) rc = worker_item_end(&seq, &pool.item[i], rc);
+            if (pool.prev) pool.line_bases[pool.item[i].line] = b;
             pool.bases += b;
             if (rc < 0) { pool.rc = (int)rc; pool.rc_index = i; break; }
         }
@@ -2206,6 +2287,49 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
             if (pool.rc != SK_E_SPLIT) by_other = 1;
             pool.rc = SK_E_SPLIT;
         }
+    }
+    if (pv && !plan_only && ctx && nline) {
+        /* The items' records: every rank hands in its own lines' cells {kmers_present, kmer_hits, bases}, one max all-reduce makes them
+         * everybody's -- issued here by every rank whatever failed where (a rank that scanned nothing hands in zeros). */
+        uint64_t *v = (uint64_t *)calloc((size_t)nline * 3u + 1, sizeof *v), *r2 = (uint64_t *)calloc((size_t)nline * 2u + 1, sizeof *r2);
+        int rrc = v && r2 ? SK_OK : SK_E_NOMEM, arc;
+        if (pool.prev) {
+            (void)sk_item_slot(ctx, -1);
+            if (rrc == SK_OK) rrc = sk_dev_download(ctx, r2, pool.d_rec, (size_t)nline * 2u * sizeof(uint64_t));      /* (waits for the folds) */
+            if (pool.timing && sk_item_fold_timing_) {
+                double fms = 0.0;
+                uint64_t nf = 0;
+                (void)sk_item_fold_timing_(ctx, 0, &fms, &nf);
+                if (err) fprintf(err, "kmer_scrub_count timing: prevalence: %s: %llu item folds, %.3f ms on the device (%.1f us each)\n", list_path,
+                                 (unsigned long long)nf, fms, nf ? 1e3 * fms / (double)nf : 0.0);
+            }
+            for (i = 0; rrc == SK_OK && i < nline; i++) { v[3u * i] = r2[2u * i]; v[3u * i + 1] = r2[2u * i + 1]; v[3u * i + 2] = pool.line_bases[i]; }
+        }
+        arc = v ? sk_comm_max_u64(ctx, v, nline * 3u) : SK_OK;
+        if (rrc == SK_OK && arc != SK_OK) rrc = arc;
+        if (rrc != SK_OK && pool.rc == SK_OK) {
+            if (err) fprintf(err, "kmer_scrub_count: the items' records could not be fetched: %s (%s)\n", sk_strerror(rrc), sk_last_error(ctx));
+            pool.rc = rrc; by_other = 1;
+        }
+        if (pool.rc == SK_OK && pv->items) {                  /* one record per item: per list line that was not skipped */
+            skh_prev_items *const o = pv->items;
+            o->item = (skh_prev_item *)calloc((size_t)nline + 1, sizeof *o->item);
+            o->n = 0;
+            for (i = 0; o->item && i < nline; i++) {
+                skh_prev_item *const t = &o->item[o->n];
+                if (pool.ll[i].skipped) continue;
+                t->line = i + 1; t->path = strdup(pool.ll[i].text);
+                t->kmers_present = v[3u * i]; t->kmer_hits = v[3u * i + 1]; t->bases = v[3u * i + 2];
+                o->n++;
+            }
+            if (!o->item) pool.rc = SK_E_NOMEM;
+        }
+        free(v); free(r2);
+    }
+    if (pv && ctx && !plan_only) {
+        if (pool.d_rec) (void)sk_dev_free(ctx, pool.d_rec);
+        if (pool.prev || prev_failed) (void)sk_item_slots(ctx, 0);
+        free(pool.line_bases);
     }
     if (!plan_only) {
         /* What the reference has said by now.  All went well: every progress line, every skip message.  A file could not be
@@ -2261,11 +2385,12 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
 }
 
 static int scan_list_impl(sk_ctx *const *ctxs, uint32_t nctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
-                          FILE *err, uint32_t rank, uint32_t world, uint64_t *bases, int plan_only, const plan_report *report, int no_split)
+                          FILE *err, uint32_t rank, uint32_t world, uint64_t *bases, int plan_only, const plan_report *report, int no_split,
+                          const prev_opts *pv)
 {
     split_guard guard = {NULL, 0, -1, 0};
     uint32_t c;
-    int rc = scan_list_once(ctxs, nctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, no_split, &guard);
+    int rc = scan_list_once(ctxs, nctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, no_split, &guard, pv);
     if (rc == SK_E_SPLIT && guard.armed) {               /* (armed on every rank of a coordinated run, or on none) */
         rc = SK_OK;
         for (c = 0; rc == SK_OK && c < guard.nsnap; c++)  /* every context's column back */
@@ -2275,7 +2400,7 @@ static int scan_list_impl(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
             fseek(progress, guard.prog_at, SEEK_SET);
         if (getenv("SK_TIMING") && err && rc == SK_OK) fprintf(err, "kmer_scrub_count timing: a cut of %s did not hold; the list is scanned again uncut\n", list_path);
         /* the second scan opens with an agreement too: a rank whose restore failed says so there and everybody leaves */
-        rc = scan_list_once(ctxs, nctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, rc == SK_OK ? 1 : 2, NULL);
+        rc = scan_list_once(ctxs, nctx, list_path, skip, col, progress, err, rank, world, bases, plan_only, report, rc == SK_OK ? 1 : 2, NULL, pv);
     }
     for (c = 0; c < guard.nsnap; c++) free(guard.snap[c]);
     free(guard.snap);
@@ -2285,7 +2410,7 @@ static int scan_list_impl(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
 int skh_scan_list(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                   FILE *err, uint32_t rank, uint32_t world, uint64_t *bases)
 {
-    return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 0);
+    return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 0, NULL);
 }
 
 int skh_scan_list_many(sk_ctx *const *ctx, uint32_t n, const char *list_path, const char *skip, uint32_t col, FILE *progress,
@@ -2293,27 +2418,47 @@ int skh_scan_list_many(sk_ctx *const *ctx, uint32_t n, const char *list_path, co
 {
     if (!ctx || n < 1) return SK_E_ARG;
     if (n > 1 && (!sk_scan_pinned_many || !sk_scan_pinned_packed_many)) return SK_E_STATE;
-    return scan_list_impl(ctx, n, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 0);
+    return scan_list_impl(ctx, n, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 0, NULL);
 }
 
 int skh_scan_list_uncut(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                         FILE *err, uint32_t rank, uint32_t world, uint64_t *bases)
 {
-    return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 1);
+    return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 1, NULL);
+}
+
+int skh_scan_list_prevalence(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, uint32_t prev_col, uint32_t min_count,
+                             skh_prev_items *items_out, FILE *progress, FILE *err, uint32_t rank, uint32_t world, uint64_t *bases)
+{
+    prev_opts pv;
+    if (!ctx || !list_path || !items_out || min_count < 1 || col == prev_col) return SK_E_ARG;
+    if (!sk_item_slots || !sk_item_slot || !sk_item_fold || !sk_dev_alloc || !sk_dev_free || !sk_dev_upload || !sk_dev_download) return SK_E_STATE;
+    items_out->item = NULL; items_out->n = 0;
+    pv.prev_col = prev_col; pv.min_count = min_count; pv.items = items_out;
+    return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 1, &pv);
+}
+
+void skh_prev_items_free(skh_prev_items *items)
+{
+    uint32_t i;
+    if (!items) return;
+    for (i = 0; items->item && i < items->n; i++) free(items->item[i].path);
+    free(items->item);
+    items->item = NULL; items->n = 0;
 }
 
 int skh_list_plan_hash(const char *list_path, const char *skip, uint32_t world, uint64_t *hash)
 {
     plan_report rp = {hash, NULL, 0, NULL};
     if (!list_path || !hash) return SK_E_ARG;
-    return scan_list_impl(NULL, 0, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0);
+    return scan_list_impl(NULL, 0, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0, NULL);
 }
 
 int skh_list_plan_owners(const char *list_path, const char *skip, uint32_t world, uint32_t *owner, uint32_t cap, uint32_t *nlines)
 {
     plan_report rp = {NULL, owner, cap, nlines};
     if (!list_path || !nlines || (cap && !owner)) return SK_E_ARG;
-    return scan_list_impl(NULL, 0, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0);
+    return scan_list_impl(NULL, 0, list_path, skip, 0, NULL, NULL, 0, world ? world : 1, NULL, 1, &rp, 0, NULL);
 }
 
 /* =========================================================================================
@@ -2333,7 +2478,8 @@ static char *put_i32(char *p, int32_t v)             /* "%d" of an unsigned coun
 
 static int cmp_u64(const void *a, const void *b) { const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b; return x < y ? -1 : x > y; }
 
-int skh_print_counts(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug_column)
+/* the table from any four columns of the counters (from[c]: the column printed as field c + 1), `extra` behind the header line */
+static int print_table(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug_column, const uint32_t from[4], const char *extra)
 {
     const uint32_t ncols = with_drug_column ? 4 : 3, n = ks->nrows;
     uint32_t *cols[4] = {NULL, NULL, NULL, NULL};
@@ -2341,10 +2487,11 @@ int skh_print_counts(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug
     char *buf, *p;
     int rc = SK_OK;
     const size_t BUF = 1 << 20;
-    if (sk_table_cols(ctx) < ncols || sk_table_rows(ctx) != n) return SK_E_STATE;
+    if (sk_table_rows(ctx) != n) return SK_E_STATE;
+    for (c = 0; c < ncols; c++) if (sk_table_cols(ctx) <= from[c]) return SK_E_STATE;
     for (c = 0; c < ncols && rc == SK_OK; c++) {
         cols[c] = (uint32_t *)malloc((size_t)(n ? n : 1) * sizeof(uint32_t));
-        rc = sk_counts_fetch(ctx, c, cols[c]);
+        rc = sk_counts_fetch(ctx, from[c], cols[c]);
     }
     /* wide keys in ascending row order (an IUPAC-riddled strain has hundreds of thousands: sort, not insert) */
     worder = (uint32_t *)malloc((size_t)(ks->nwide ? ks->nwide : 1) * sizeof(uint32_t));
@@ -2359,6 +2506,7 @@ int skh_print_counts(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug
         buf = (char *)malloc(BUF + 256);
         p = buf;
         fputs("#kmer\treference_count\tpangenome_count\tmetagenome_count\tdrug_count\n", out);
+        if (extra) fputs(extra, out);
         for (r = 0; r < n; r++) {
             if (ks->packed[r] != SK_KEY_NONE) { decode_key(ks->packed[r], p); p += SK_K; }
             else {
@@ -2377,6 +2525,12 @@ int skh_print_counts(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug
     for (c = 0; c < 4; c++) free(cols[c]);
     free(worder);
     return rc;
+}
+
+int skh_print_counts(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug_column)
+{
+    static const uint32_t from[4] = {0, 1, 2, 3};
+    return print_table(ctx, ks, out, with_drug_column, from, NULL);
 }
 
 /* =========================================================================================
@@ -2439,6 +2593,13 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
     const char *scrub_out = NULL;                    /* --scrub-out FILE: the filter's result goes there instead of stdout */
     int detect_argc = 0;                             /* --detect ...: strain_detect's arguments, run on the resident table */
     char **detect_argv = NULL;
+    /* --prevalence[=FILE] [--prevalence-min-count m] [--prevalence-items=FILE] [--scrub-by prevalence] (extension; the rule is in
+     * include/strainer_kmer.h at sk_item_fold): three more columns behind the table's own, a second table of the count table's shape */
+    int prevalence = 0, scrub_by_prev = 0;
+    const char *prev_file = NULL, *prev_items_file = NULL, *prev_min_text = NULL, *scrub_by = NULL;
+    uint32_t prev_min = 1, prev_base = 4;
+    skh_prev_items prev_items[3];
+    char prev_path[4200] = "";
 
     /* Extension (not in the reference): "--scrub <min_fraction>" [--independent] runs step 2 of the
      * workflow (scripts/kmer_scrub_filter.py -s <table> -m <min_fraction> [-i]) on the counters while
@@ -2464,6 +2625,23 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
             if (!dir[0]) { fprintf(err, "kmer_scrub_count: --pack-cache needs a directory\n"); return 1; }
             skh_pack_cache_set(NULL, dir, m && !strcmp(m, "ro") ? "ro" : "rw");
             *pack_cache_word_out = 1;
+            continue;
+        }
+        if (!strncmp(argv[c], "--prevalence-min-count", 22) && (argv[c][22] == 0 || argv[c][22] == '=')) {
+            prev_min_text = argv[c][22] ? argv[c] + 23 : (c + 1 < argc ? argv[++c] : "");
+            continue;
+        }
+        if (!strncmp(argv[c], "--prevalence-items", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            prev_items_file = argv[c][18] ? argv[c] + 19 : (c + 1 < argc ? argv[++c] : "");
+            continue;
+        }
+        if (!strncmp(argv[c], "--prevalence", 12) && (argv[c][12] == 0 || argv[c][12] == '=')) {
+            prevalence = 1;
+            if (argv[c][12]) prev_file = argv[c] + 13;
+            continue;
+        }
+        if (!strncmp(argv[c], "--scrub-by", 10) && (argv[c][10] == 0 || argv[c][10] == '=')) {
+            scrub_by = argv[c][10] ? argv[c] + 11 : (c + 1 < argc ? argv[++c] : "");
             continue;
         }
         if (!strncmp(argv[c], "--scrub", 7) && (argv[c][7] == 0 || argv[c][7] == '=')) {
@@ -2511,6 +2689,45 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
         if (scrub_list && !skh_scrub_filter_resident_sweep) { fprintf(err, "kmer_scrub_count: this build has no scrub sweep\n"); return 1; }
     }
 
+    memset(prev_items, 0, sizeof prev_items);
+    {   /* the prevalence words, before anything is read */
+        if (scrub_by && strcmp(scrub_by, "prevalence") && strcmp(scrub_by, "count")) {
+            fprintf(err, "kmer_scrub_count: --scrub-by takes count or prevalence\n");
+            return 1;
+        }
+        scrub_by_prev = scrub_by && !strcmp(scrub_by, "prevalence");
+        if (scrub_by_prev && !prevalence) { fprintf(err, "kmer_scrub_count: --scrub-by prevalence needs --prevalence\n"); return 1; }
+        if (scrub_by && scrub_fraction < 0.0) { fprintf(err, "kmer_scrub_count: --scrub-by needs --scrub <min_fraction>\n"); return 1; }
+        if (scrub_by_prev && scrub_list) {
+            fprintf(err, "kmer_scrub_count: --scrub-by prevalence does not go with a list of fractions (the scrub sweep ranks by count)\n");
+            return 1;
+        }
+        if ((prev_min_text || prev_items_file) && !prevalence) {
+            fprintf(err, "kmer_scrub_count: --prevalence-min-count and --prevalence-items need --prevalence\n");
+            return 1;
+        }
+        if (prev_min_text) {
+            char *e;
+            const unsigned long long m = strtoull(prev_min_text, &e, 10);
+            if (e == prev_min_text || *e || prev_min_text[0] == '-' || prev_min_text[0] == '+' || m < 1 || m > 0xFFFFFFFFull) {
+                fprintf(err, "kmer_scrub_count: --prevalence-min-count needs an integer of at least 1\n");
+                return 1;
+            }
+            prev_min = (uint32_t)m;
+        }
+        if (prevalence && ((prev_file && !prev_file[0]) || (prev_items_file && !prev_items_file[0]))) {
+            fprintf(err, "kmer_scrub_count: --prevalence=FILE and --prevalence-items=FILE need a file name\n");
+            return 1;
+        }
+        if (prevalence) {                             /* (-S with --prevalence is refused by the -S program: skh_kmer_scrub_count_multi_main) */
+            if (!sk_item_slots || !sk_item_slot || !sk_item_fold || !sk_dev_alloc || !sk_dev_free || !sk_dev_upload || !sk_dev_download ||
+                (scrub_by_prev && !skh_scrub_filter_resident_cols)) {
+                fprintf(err, "kmer_scrub_count: this build has no prevalence\n");
+                return 1;
+            }
+        }
+    }
+
     optind = 1;
     while ((c = getopt(argc, argv, "A:B:C:r:p:Hhud")) != -1) {
         switch (c) {
@@ -2529,6 +2746,15 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
         return 1;
     }
     if (world < 1 || rank < 0 || rank >= world) { fprintf(err, "kmer_scrub_count: bad rank %d of %d\n", rank, world); return 1; }
+    if (prevalence) {                                 /* the prevalence table's name: FILE, else <progress file>.prevalence.tsv, else kmer_scrub_count.prevalence.tsv */
+        if (prev_file ? strlen(prev_file) + 1 > sizeof prev_path : (P ? strlen(P) : 16) + 16 > sizeof prev_path) {
+            fprintf(err, "kmer_scrub_count: the prevalence file's path is too long\n");
+            return 1;
+        }
+        if (prev_file) snprintf(prev_path, sizeof prev_path, "%s", prev_file);
+        else snprintf(prev_path, sizeof prev_path, "%s.prevalence.tsv", P ? P : "kmer_scrub_count");
+        prev_base = detect_argv ? 6 : 4;
+    }
     if (P && rank == 0) {
         progress = fopen(P, "w");
         if (!progress) { fprintf(err, "could not open progress file %s\n", P); return 1; }
@@ -2576,7 +2802,7 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
             if (rc != SK_OK) goto done;
         } else if (setup_failed) goto done;
     }
-    rc = skh_keyset_load(ctx, &ks, detect_argv ? 6 : 4);        /* (strain_detect's table has six columns) */
+    rc = skh_keyset_load(ctx, &ks, (detect_argv ? 6u : 4u) + (prevalence ? 3u : 0u));        /* (strain_detect's table has six columns; the prevalence columns lie behind) */
     t3 = now_s();
     if (rc != SK_OK) { fprintf(err, "kmer_scrub_count: table load failed: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx)); failed = 1; }
     if (rc == SK_OK && world > 1) rc = sk_counts_zero(ctx, 0);      /* column 0 must not be summed world times: keep it on rank 0 */
@@ -2596,9 +2822,15 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
             goto done;
         }
     }
-    if (!failed && skh_scan_list(ctx, A, NULL, 1, progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
-    if (!failed && skh_scan_list(ctx, B, NULL, 2, progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
-    if (!failed && C && skh_scan_list(ctx, C, R, 3, progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
+    if (prevalence) {
+        if (!failed && skh_scan_list_prevalence(ctx, A, NULL, 1, prev_base, prev_min, &prev_items[0], progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
+        if (!failed && skh_scan_list_prevalence(ctx, B, NULL, 2, prev_base + 1, prev_min, &prev_items[1], progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
+        if (!failed && C && skh_scan_list_prevalence(ctx, C, R, 3, prev_base + 2, prev_min, &prev_items[2], progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
+    } else {
+        if (!failed && skh_scan_list(ctx, A, NULL, 1, progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
+        if (!failed && skh_scan_list(ctx, B, NULL, 2, progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
+        if (!failed && C && skh_scan_list(ctx, C, R, 3, progress, err, (uint32_t)rank, (uint32_t)world, NULL) != SK_OK) failed = 1;
+    }
     if (use_comm) {
         /* agree once more (the lists' own agreements have made `failed` the same everywhere: a belt to those braces) */
         rc = sk_comm_sum_u32(ctx, (uint32_t)failed, &nfailed);
@@ -2607,6 +2839,30 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
         rc = sk_counts_allreduce(ctx, NULL);
         if (rc != SK_OK) { fprintf(err, "kmer_scrub_count: all-reduce failed: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx)); goto done; }
     } else if (failed) goto done;
+    if (prevalence && rank == 0) {
+        /* the prevalence table: the count table's shape, the items of each list that hold the k-mer in place of its counts; and the
+         * items' own records */
+        const uint32_t from[4] = {0, prev_base, prev_base + 1, prev_base + 2};
+        char extra[160];
+        FILE *pf = fopen(prev_path, "w");
+        if (!pf) { fprintf(err, "kmer_scrub_count: cannot write %s\n", prev_path); goto done; }
+        snprintf(extra, sizeof extra, "#items\t%u\t%u\t%u\n#min_count\t%u\n", prev_items[0].n, prev_items[1].n, prev_items[2].n, prev_min);
+        rc = print_table(ctx, &ks, pf, C != NULL, from, extra);
+        if (fclose(pf) != 0 && rc == SK_OK) rc = SK_E_OPEN;
+        if (rc != SK_OK) { fprintf(err, "kmer_scrub_count: %s: %s (%s)\n", prev_path, sk_strerror(rc), sk_last_error(ctx)); goto done; }
+        if (prev_items_file) {
+            uint32_t l, k;
+            if (!(pf = fopen(prev_items_file, "w"))) { fprintf(err, "kmer_scrub_count: cannot write %s\n", prev_items_file); goto done; }
+            fputs("#list\tline\tfile\tbases\tkmers_present\tkmer_hits\n", pf);
+            for (l = 0; l < 3; l++)
+                for (k = 0; k < prev_items[l].n; k++) {
+                    const skh_prev_item *t = &prev_items[l].item[k];
+                    fprintf(pf, "%c\t%u\t%s\t%llu\t%llu\t%llu\n", "ABC"[l], t->line, t->path, (unsigned long long)t->bases,
+                            (unsigned long long)t->kmers_present, (unsigned long long)t->kmer_hits);
+                }
+            if (fclose(pf) != 0) { fprintf(err, "kmer_scrub_count: cannot write %s\n", prev_items_file); goto done; }
+        }
+    }
     t4 = now_s();
     if (rank == 0 && scrub_fraction >= 0.0) {
         FILE *so = out;
@@ -2625,6 +2881,9 @@ static int ksc_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache
             if (strlen(list_path) + 9 > sizeof cls_path) { fprintf(err, "kmer_scrub_count: %s: the path is too long\n", list_path); fclose(so); goto done; }
             snprintf(cls_path, sizeof cls_path, "%s.classes", list_path);
             status = skh_scrub_filter_resident_sweep(ctx, &ks, C != NULL, scrub_list, scrub_independent, cls_path, so, err);
+        } else if (scrub_by_prev) {
+            const uint32_t pcols[3] = {prev_base, prev_base + 1, prev_base + 2};
+            status = skh_scrub_filter_resident_cols(ctx, &ks, C != NULL, pcols, scrub_fraction, scrub_independent, so, err);
         } else
             status = skh_scrub_filter_resident(ctx, &ks, C != NULL, scrub_fraction, scrub_independent, so, err);
         if (so != out) fclose(so);
@@ -2663,5 +2922,6 @@ done:
     if (ctx) sk_ctx_destroy(ctx);
     skh_keyset_free(&ks);
     if (progress) fclose(progress);
+    for (c = 0; c < 3; c++) skh_prev_items_free(&prev_items[c]);
     return status;
 }

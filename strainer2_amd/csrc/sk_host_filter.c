@@ -601,13 +601,14 @@ static const char *keyset_key_of(void *user, uint64_t row, char tmp[32])
 }
 
 static int resident_impl(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, double min_fraction, int independent, FILE *out, FILE *err,
-                         const skw_list *sw, const char *classes_path)
+                         const skw_list *sw, const char *classes_path, const uint32_t *cols /* pangenome, metagenome, drug; NULL: 1, 2, 3 */)
 {
+    static const uint32_t count_cols[3] = {1, 2, 3};
     sk_filter *flt = NULL;
     uint64_t n_gone = 0;
     int rc, status;
     if (!ctx || !ks || min_fraction < 0.0 || min_fraction > 1.0) return 1;
-    if ((rc = sk_filter_create(ctx, &flt)) != SK_OK || (rc = sk_filter_load_counts(flt, 1, 2, with_drug_column ? 3 : -1)) != SK_OK ||
+    if ((rc = sk_filter_create(ctx, &flt)) != SK_OK || (rc = sk_filter_load_counts(flt, (cols ? cols : count_cols)[0], (cols ? cols : count_cols)[1], with_drug_column ? (int32_t)(cols ? cols : count_cols)[2] : -1)) != SK_OK ||
         (rc = sk_filter_sums(flt, NULL, NULL, NULL, NULL, &n_gone)) != SK_OK) {
         fprintf(err, "kmer_scrub_filter: %s (%s)\n", sk_strerror(rc), sk_last_error(ctx));
         sk_filter_destroy(flt);
@@ -625,7 +626,15 @@ static int resident_impl(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column
 int skh_scrub_filter_resident(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, double min_fraction,
                               int independent, FILE *out, FILE *err)
 {
-    return resident_impl(ctx, ks, with_drug_column, min_fraction, independent, out, err, NULL, NULL);
+    return resident_impl(ctx, ks, with_drug_column, min_fraction, independent, out, err, NULL, NULL, NULL);
+}
+
+/* ... from three other columns of the resident table (kmer_scrub_count --scrub-by prevalence: the prevalence columns) */
+int skh_scrub_filter_resident_cols(sk_ctx *ctx, const skh_keyset *ks, int with_drug_column, const uint32_t cols[3], double min_fraction,
+                                   int independent, FILE *out, FILE *err)
+{
+    if (!cols) return 1;
+    return resident_impl(ctx, ks, with_drug_column, min_fraction, independent, out, err, NULL, NULL, cols);
 }
 
 /* ... at a list of fractions (the scrub sweep): the run at the list's first, and the class file to classes_path */
@@ -636,5 +645,5 @@ int skh_scrub_filter_resident_sweep(sk_ctx *ctx, const skh_keyset *ks, int with_
     char why[160];
     if (!fraction_list || !classes_path || !*classes_path) { fprintf(err, "kmer_scrub_filter: the scrub sweep needs a list of fractions and a class file's path\n"); return 1; }
     if (skw_parse_list(fraction_list, &sw, why, sizeof why)) { fprintf(err, "kmer_scrub_filter: fraction list %s: %s\n", fraction_list, why); return 1; }
-    return resident_impl(ctx, ks, with_drug_column, sw.f[0], independent, out, err, &sw, classes_path);
+    return resident_impl(ctx, ks, with_drug_column, sw.f[0], independent, out, err, &sw, classes_path, NULL);
 }

@@ -532,6 +532,11 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
      * not take them: the informative lists alone are the single-strain program's */
     for (c = 1; c < argc; c++)
         if (!strcmp(argv[c], "--detect")) { detect_argv = argv + c; detect_argc = argc - c; argc = c; break; }
+    for (c = 1; c < argc; c++)                        /* (before anything is read, and before --scrub-by could pass for --scrub) */
+        if (!strncmp(argv[c], "--prevalence", 12) || !strncmp(argv[c], "--scrub-by", 10)) {
+            fprintf(err, "kmer_scrub_count: --prevalence does not go with -S: a union's per-key fold and its subtracting -C pass have no per-item form yet\n");
+            return 1;
+        }
     for (c = 1; !detect_argv && c < argc; c++)
         if (!strncmp(argv[c], "--scrub", 7) || !strcmp(argv[c], "--independent")) {
             fprintf(err, "kmer_scrub_count: -S does not go with --scrub/--detect (run the strains one by one for those)\n");

@@ -154,6 +154,20 @@ typedef struct sk_background_view {
     uint32_t *d_col; const uint32_t *d_type; uint32_t nrows;
 } sk_background_view;
 int sk_background_view_(sk_ctx *ctx, uint32_t col, uint32_t type_col, sk_background_view *out);
+/* An item slot and the two columns its fold adds to, as they lie on the device (all four in the counters' own order), for
+ * sk_item_fold (sk_prevalence.hip).  Both scan lanes are joined before this returns and lane 1's next scan waits for what the caller
+ * puts on `stream`.  d_diff holds nrows + 1 live entries, d_sums room for the block sums of that many (sk_diff_sums_). */
+typedef struct sk_item_view {
+    int device; void *stream;              /* hipStream_t */
+    uint32_t *d_scratch, *d_diff, *d_sums, *d_count, *d_prev; uint32_t nrows;
+} sk_item_view;
+int sk_item_view_(sk_ctx *ctx, uint32_t slot, uint32_t count_col, uint32_t prev_col, sk_item_view *out);
+/* the block sums (one per 4096 entries) of a difference array of n entries and their exclusive scan in place, on ctx's stream */
+int sk_diff_sums_(sk_ctx *ctx, const uint32_t *d_diff, uint32_t n, uint32_t *d_sums);
+/* the device time of the item folds (sk_item_fold), from an event pair around each while the clocks are on: the call hands out the
+ * sum and the number of the folds since the last call (ms / folds NULL: not wanted) and sets the clocks (on != 0: running).  Off
+ * unless asked for: the list walk asks under SK_TIMING. */
+int sk_item_fold_timing_(sk_ctx *ctx, int on, double *ms, uint64_t *folds);
 /* the accumulator's device time (events around every fold and every target sweep): on != 0 starts the clocks, ms_fold / ms_sweep
  * (NULL: not wanted) are the sums so far.  Off unless asked for: strain_detect asks under SK_SD_TIMING. */
 int sk_covacc_timing_(sk_covacc *a, int on, double *ms_fold, double *ms_sweep);

@@ -81,6 +81,7 @@ ABI_SYMBOLS = [
     "sk_covacc_set_rarefaction", "sk_covacc_set_pair_base", "sk_covacc_add_pairs", "sk_covacc_add_rows_hits_pairs",
     "sk_covacc_finish_target_rarefaction", "skh_rarefaction_parse", "skh_rarefaction_draw", "skh_rarefaction_class",
     "skh_rarefaction_fold", "skh_rarefaction_write",
+    "sk_item_slots", "sk_item_slot", "sk_item_fold", "skh_scan_list_prevalence", "skh_prev_items_free", "skh_scrub_filter_resident_cols",
 ]
 
 
@@ -152,6 +153,9 @@ lib.sk_text_release.restype = None
 lib.sk_text_option.argtypes = [C.c_void_p, C.c_int]
 lib.sk_text_enabled.argtypes = [C.c_void_p]
 lib.sk_text_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+lib.sk_item_slots.argtypes = [C.c_void_p, C.c_uint32]
+lib.sk_item_slot.argtypes = [C.c_void_p, C.c_int]
+lib.sk_item_fold.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
 lib.sk_counts_fetch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_counts_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_counts_set_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -475,6 +479,20 @@ class KmerContext:
         out = np.zeros((2, SK_BACKGROUND_HEAD + max_depth + 1), dtype=np.uint64)
         self._ck(lib.sk_background_finish(self._h, col, type_col, informative_value, max_depth, out.ctypes.data))
         return out
+
+    def item_slots(self, nslots):
+        """sk_item_slots: nslots item slots (a scratch column and a difference array each) for the loaded table; 0 frees them"""
+        self._ck(lib.sk_item_slots(self._h, nslots))
+
+    def item_slot(self, slot):
+        """sk_item_slot: every COUNT scan from now on adds into item slot `slot`, whatever column it names; -1: into its column"""
+        self._ck(lib.sk_item_slot(self._h, slot))
+
+    def item_fold(self, slot, count_col, prev_col, min_count=1, record=None):
+        """sk_item_fold: the slot's values v go into counts[count_col] += v and counts[prev_col] += (v >= min_count), the slot is
+        zero again; record: a device pointer (dev_alloc) to two u64 that {rows with v >= min_count, sum of v} are added to.
+        Asynchronous."""
+        self._ck(lib.sk_item_fold(self._h, slot, count_col, prev_col, min_count, record))
 
     def tally_batch(self, stream: bytes, rec_start, type_col=0, informative_value=2):
         """Per-record tallies (strain_detect): returns (tally[nrec, 2], hits[n, 2] sorted by position)."""
