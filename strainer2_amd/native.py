@@ -214,6 +214,7 @@ lib.skh_scrub_filter_main.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p
 lib.skh_scrub_filter_resident.argtypes = [C.c_void_p, C.POINTER(_KeysetStruct), C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
 
 lib.sk_distinct_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.sk_first_seen_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.skh_coverage_depth_main.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
 
 lib.sk_batch_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -752,6 +753,18 @@ class KmerContext:
         total = np.zeros(nsamples, dtype=np.uint64)
         self._ck(lib.sk_distinct_count(self._h, keys.ctypes.data, sample.ctypes.data, len(keys), nsamples,
                                        uniq.ctypes.data, total.ctypes.data))
+        return uniq, total
+
+    def first_seen_count(self, ids, sample, nids, nsamples):
+        """sk_first_seen_count: (unique[nsamples], total[nsamples]) -- every line counts for its sample; an id (< nids) counts once, for
+        the sample of the first line that shows it"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32)
+        assert len(ids) == len(sample)
+        uniq = np.zeros(nsamples, dtype=np.uint64)
+        total = np.zeros(nsamples, dtype=np.uint64)
+        self._ck(lib.sk_first_seen_count(self._h, ids.ctypes.data, sample.ctypes.data, len(ids), nids, nsamples,
+                                         uniq.ctypes.data, total.ctypes.data))
         return uniq, total
 
     def distinct_spectrum(self, keys, sample, nsamples, max_depth):
