@@ -402,11 +402,28 @@ int  sk_union_background_finish(sk_union *u, uint32_t ucol, uint32_t max_depth, 
  *   counts[count_col][row] += v; counts[prev_col][row] += (v >= min_count); the slot is zero again; d_item_record[0] += the rows
  *   with v >= min_count, d_item_record[1] += the sum of v.  d_item_record: two u64 in DEVICE memory (sk_dev_alloc; 8-byte aligned;
  *   NULL: no record), zeroed by the caller, fetched when the caller likes after a sk_sync.  Asynchronous.  min_count >= 1 and
- *   count_col != prev_col, else SK_E_ARG.  Folding an empty slot changes nothing. */
+ *   count_col != prev_col, else SK_E_ARG.  Folding an empty slot changes nothing.
+ * On a UNION (many strains over one pass of a list): sk_item_slots / sk_item_slot on sk_union_context(u), after
+ *   sk_union_count_enable, send the union's COUNT scans into a slot of GLOBAL rows (8 bytes x sk_union_rows(u) a slot), and
+ * sk_union_item_fold hands the slot to the members.  All arithmetic mod 2^32.  Per global row g, v_g = the slot's value; per
+ *   distinct key, with w its slot row, V_w = the sum of v_g over the rows g of that key (the scan may credit any member's row of a
+ *   key several members hold).  For every member s of member_mask and every row i of s, with V the V_w of that row's key:
+ *   counts_s[count_col][i] += V; counts_s[prev_col][i] += (V >= min_count); d_records[2 s] += (V >= min_count);
+ *   d_records[2 s + 1] += V.  Each such member's columns and record end exactly as sk_item_fold would leave them had the item been
+ *   scanned into a slot of that member alone.  Members outside the mask are untouched, their records too; the whole slot is zero
+ *   afterwards, also with member_mask 0 (an item that counts for nobody: a -C line equal to every member's genome).  The union's own
+ *   count columns and its pending increments are left alone.  d_records: sk_union_members(u) x 2 u64 in DEVICE memory (8-byte
+ *   aligned; NULL: no records), zeroed by the caller.  Asynchronous on the union's stream, behind every scan of the slot on either
+ *   lane, and the host waits for nothing: five launches whatever the number of members.  While folds are in flight only the
+ *   union's stream may touch the members' columns; the caller calls sk_sync(sk_union_context(u)) once where the list ends.
+ *   SK_E_STATE without sk_union_count_enable; SK_E_ARG: no such slot, min_count 0, count_col == prev_col, a mask bit beyond the
+ *   members, a masked member without the two columns. */
 #define SK_ITEM_SLOTS_MAX 256u
 int  sk_item_slots(sk_ctx *ctx, uint32_t nslots);
 int  sk_item_slot(sk_ctx *ctx, int slot);
 int  sk_item_fold(sk_ctx *ctx, uint32_t slot, uint32_t count_col, uint32_t prev_col, uint32_t min_count, uint64_t *d_item_record);
+int  sk_union_item_fold(sk_union *u, uint32_t slot, uint32_t count_col, uint32_t prev_col, uint32_t member_mask, uint32_t min_count,
+                        uint64_t *d_records /* [members][2] u64 in device memory, or NULL */);
 
 /* Wait for all queued work of the context. */
 int sk_sync(sk_ctx *ctx);
@@ -562,6 +579,21 @@ typedef struct { skh_prev_item *item; uint32_t n; } skh_prev_items;
 int  skh_scan_list_prevalence(sk_ctx *ctx, const char *list_path, const char *skip, uint32_t col, uint32_t prev_col, uint32_t min_count,
                               skh_prev_items *items_out, FILE *progress, FILE *err, uint32_t rank, uint32_t world, uint64_t *bases);
 void skh_prev_items_free(skh_prev_items *items);
+/* PREVALENCE over n contexts on one device from ONE decode of the list (new: kmer_scrub_count -S --prevalence=SUFFIX; the contexts
+ * are the resident unions' own, sk_union_context).  skh_scan_list_many's walk with skh_scan_list_prevalence's slots, and the folds
+ * left to the caller, so that this layer never names a union: every ctx[i] has `nslots` item slots already (sk_item_slots, made
+ * once for all the lists); the list is planned uncut; under the lock that orders the submits a decode thread names its slot on
+ * EVERY context before each of its submits -- on all the paths skh_scan_list_prevalence names --, and where its item ends, served,
+ * parsed or failed part-way, it calls fold(user, slot, line) under the same lock: line is the item's 0-based list line, and the
+ * caller enqueues each context's fold of that slot there (sk_union_item_fold: asynchronous) into record cells of its own.  At most
+ * nslots decode threads run: a thread owns a slot, so with fewer slots than SK_THREADS the other items wait for one.  Every line
+ * is an item (the per-strain -C rule is the caller's fold mask).  When the call returns the folds are enqueued, not done: the
+ * caller waits for each context once (sk_sync).  *items_out: one entry per line in list order with line, path and bases;
+ * kmers_present and kmer_hits are 0 (they are in the caller's cells).  A hook that fails makes its item fail with what it returned
+ * (a negative SK_E_*).  SK_E_ARG: no hook, no slots, no items_out; SK_E_STATE: a device layer without item slots. */
+typedef int (*skh_item_fold_fn)(void *user, uint32_t slot, uint32_t line);
+int  skh_scan_list_many_prevalence(sk_ctx *const *ctx, uint32_t n, const char *list_path, uint32_t col, uint32_t nslots,
+                                   skh_item_fold_fn fold, void *user, skh_prev_items *items_out, FILE *progress, FILE *err, uint64_t *bases);
 /* skh_scan_list into n contexts on one device over ONE decode of the list (new: kmer_scrub_count -S feeds every resident union
  * from one walk): each chunk goes up once and is scanned into column `col` of every ctx[i] (sk_scan_pinned[_packed]_many; packed
  * or bytes is decided once per chunk, for all of them).  A cut that does not hold puts back the column of EVERY context before the
@@ -626,7 +658,15 @@ int skh_kmer_scrub_count_main(int argc, char **argv, FILE *out, FILE *err);
  * with WORLD_SIZE/RANK the strain lines are dealt to the ranks round-robin (no collective).  With "--scrub <min_fraction> [--independent] --detect <strain_detect arguments>" a line is
  * <genome> TAB <informative outfile> TAB <hits outfile> [TAB <-g list>]: the informative outfile gets what `-r <genome> ...
  * --scrub f [--independent]` prints (step 2 on the resident counts), and the strains go on into step 3 (and 4) together through
- * skh_strain_detect_resident_many.  --scrub without --detect is refused.  Returns the exit status. */
+ * skh_strain_detect_resident_many.  --scrub without --detect is refused.
+ * With "--prevalence=SUFFIX [--prevalence-items=SUFFIX] [--prevalence-min-count m]" every strain also gets, from the same decode,
+ * its prevalence table at <its outfile><SUFFIX> and its item records at <its outfile><items SUFFIX>: byte for byte what `-r <genome>
+ * .. --prevalence=F --prevalence-items=G --prevalence-min-count m` writes to F and G (the rule is at sk_item_fold).  The union's
+ * scans go into item slots of its own context, made once per decode, and sk_union_item_fold hands each item to the members; a -C
+ * line equal to a strain's genome is masked out of that strain's fold (no item of that strain), so nothing is rescanned and taken
+ * back.  "--scrub f --scrub-by prevalence --detect .." ranks step 2 by the prevalence columns.  The bare --prevalence stays refused
+ * (one file name cannot serve many strains), as are output names that coincide once the suffixes are applied.  Everything the run
+ * wrote without the words stays the same bytes.  Returns the exit status. */
 int skh_kmer_scrub_count_multi_main(int argc, char **argv, FILE *out, FILE *err);
 
 /* The whole strain_detect program with the reference's argv contract (src/strain_detect.c:61-158):

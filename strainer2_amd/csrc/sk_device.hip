@@ -1716,6 +1716,45 @@ extern "C" int sk_union_counts_fold(sk_union *u, uint32_t ucol, uint32_t member_
     return SK_OK;
 }
 
+// what sk_union_item_fold (sk_prevalence.hip) needs of an item slot of the union's context and of the members' columns
+extern "C" int sk_union_item_view_(sk_union *u, uint32_t slot, uint32_t count_col, uint32_t prev_col, uint32_t member_mask, sk_union_item_view *v)
+{
+    if (!u || !v) return SK_E_ARG;
+    sk_ctx *c = u->uc;
+    if (!c->d_counts || !u->d_canon) return sk_fail(c, SK_E_STATE, "the union has no count columns (sk_union_count_enable)");
+    if (slot >= c->item_nslots) return sk_fail(c, SK_E_ARG, "item slot %u of %u", slot, c->item_nslots);
+    if (count_col == prev_col) return sk_fail(c, SK_E_ARG, "bad column");
+    if (u->n < 32u && (member_mask >> u->n) != 0u) return sk_fail(c, SK_E_ARG, "member mask 0x%x names no member of %u", member_mask, u->n);
+    for (uint32_t s = 0; s < u->n; s++)
+        if (((member_mask >> s) & 1u) && (!u->mem[s]->d_counts || count_col >= u->mem[s]->ncols || prev_col >= u->mem[s]->ncols))
+            return sk_fail(c, SK_E_ARG, "member %u has no columns %u and %u", s, count_col, prev_col);
+    SK_HIP(c, hipSetDevice(c->device));
+    { int jrc = sk_lanes_join(c); if (jrc) return jrc; }       // (both lanes add to the slot; lane 1's next scan waits for the fold)
+    v->uc = c; v->device = c->device; v->stream = (void *)c->stream; v->nrows = c->nrows; v->members = u->n;
+    v->d_scratch = c->d_item + (size_t)slot * c->item_stride; v->d_diff = v->d_scratch + sk_item_diff_at(c->nrows);
+    v->d_sums = c->d_item_sums; v->d_canon = u->d_canon;
+    for (uint32_t s = 0; s <= SK_UNION_MAX; s++) v->base[s] = s < u->n ? u->base[s] : c->nrows;
+    for (uint32_t s = 0; s < SK_UNION_MAX; s++) {
+        v->d_count[s] = v->d_prev[s] = NULL;
+        if (s >= u->n || !((member_mask >> s) & 1u)) continue;
+        sk_ctx *m = u->mem[s];
+        if (m->diff_col >= 0 || m->lane1_busy) {              // the member's own increments of a column: folded in on its stream, and the
+            int rc = sk_diff_flush(m);                        // union's stream waits for that on the device
+            if (rc) return sk_fail(c, rc, "member %u: %s", s, m->err);
+            hipEvent_t ev = NULL;
+            SK_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            hipError_t e = hipEventRecord(ev, m->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
+            (void)hipEventDestroy(ev);
+            SK_HIP(c, e);
+        }
+        if (m->infbits_col == count_col || m->infbits_col == prev_col) m->infbits_ok = false;
+        v->d_count[s] = m->d_counts + (size_t)count_col * m->nrows;
+        v->d_prev[s] = m->d_counts + (size_t)prev_col * m->nrows;
+    }
+    return SK_OK;
+}
+
 extern "C" int sk_union_scan_timing(sk_union *u, double *total_ms, uint64_t *launches, int reset)
 {
     return u ? sk_scan_timing(u->uc, total_ms, launches, reset) : SK_E_ARG;

@@ -874,7 +874,7 @@ static int text_scan(sk_ctx *const *ctxs, uint32_t nctx, pthread_mutex_t *mu, co
         if (off + have >= (uint64_t)st.st_size) eof = 1;
         if (!have) break;
         if (mu) pthread_mutex_lock(mu);
-        if (slot >= 0) (void)sk_item_slot(ctx, slot);
+        if (slot >= 0) { uint32_t c; for (c = 0; c < nctx; c++) (void)sk_item_slot(ctxs[c], slot); }
         rc = sk_scan_text_pinned_many(ctxs, nctx, buf, have, eof, col, &info);
         if (mu) pthread_mutex_unlock(mu);
         if (rc != SK_OK) break;
@@ -1119,9 +1119,12 @@ typedef struct {
     double          pc_t_sum, pc_t_read, pc_t_write;               /* ... seconds summed over the threads: checksums, reading, writing */
     uint64_t        pc_bytes;                                      /* ... cache bytes read or written */
     int             pc_rw;                                         /* ... the directory may be written */
-    /* prevalence (skh_scan_list_prevalence): every decode thread's index is its item slot, named under submit_mu before each submit;
-     * an item's fold is enqueued when it ends, its record cell is that of its list line */
+    /* prevalence (skh_scan_list_prevalence): every decode thread's index is its item slot, named under submit_mu before each submit
+     * on EVERY context of the walk; an item's fold is enqueued when it ends, its record cell is that of its list line.  With a fold
+     * hook (skh_scan_list_many_prevalence) the slots, the folds and the records are the caller's: the hook is called where
+     * sk_item_fold would be, under submit_mu */
     int             prev;
+    skh_item_fold_fn fold; void *fold_user;
     uint32_t        prev_col, prev_min;
     uint64_t       *d_rec;             /* device: {kmers_present, kmer_hits} per list line */
     uint64_t       *line_bases;        /* host: the bases of each list line's item (under queue_mu) */
@@ -1139,7 +1142,11 @@ typedef struct {
 #pragma weak sk_item_fold_timing_
 
 /* under submit_mu, just before a submit: the scans that follow belong to this slot's item */
-static inline void pool_slot(const scan_pool *p, int slot) { if (p->prev) (void)sk_item_slot(p->ctx, slot); }
+static inline void pool_slot(const scan_pool *p, int slot)
+{
+    uint32_t c;
+    if (p->prev) for (c = 0; c < p->nctx; c++) (void)sk_item_slot(p->ctxs[c], slot);
+}
 
 /* The progress file gets a list line when a decode thread TAKES the line's (first) item, and every line before it that is
  * not there yet -- the reference writes the line, then opens the file.  Called under queue_mu (or from the one thread). */
@@ -1831,7 +1838,8 @@ static int64_t worker_item_end(scan_worker *w, const scan_item *it, int64_t rc)
     int frc;
     if (!p->prev) return rc;
     pthread_mutex_lock(&p->submit_mu);
-    frc = sk_item_fold(p->ctx, (uint32_t)w->slot, p->col, p->prev_col, p->prev_min, p->d_rec + 2u * (size_t)it->line);
+    frc = p->fold ? p->fold(p->fold_user, (uint32_t)w->slot, it->line)
+                  : sk_item_fold(p->ctx, (uint32_t)w->slot, p->col, p->prev_col, p->prev_min, p->d_rec + 2u * (size_t)it->line);
     pthread_mutex_unlock(&p->submit_mu);
     return rc >= 0 && frc != SK_OK ? (int64_t)frc : rc;
 }
@@ -1958,8 +1966,11 @@ typedef struct { uint32_t **snap; uint32_t nsnap; long prog_at; int armed; } spl
 #define LIST_FAIL_OPEN  1u    /* agreement before the scan: this rank could not read the list itself */
 #define LIST_FAIL_GUARD 2u    /*                            ... could not copy its column (no memory, device error) */
 
-/* prevalence (skh_scan_list_prevalence): the second column, the threshold, and where the items' records go */
-typedef struct { uint32_t prev_col, min_count; skh_prev_items *items; } prev_opts;
+/* prevalence (skh_scan_list_prevalence): the second column, the threshold, and where the items' records go.  With `fold`
+ * (skh_scan_list_many_prevalence) the walk makes no slots, no folds and no records of its own: every context has `nslots` item slots
+ * already, at most that many decode threads run -- a thread owns a slot, so the others' items wait for one --, the hook is called
+ * where an item ends, and the items handed out carry their bases alone */
+typedef struct { uint32_t prev_col, min_count; skh_prev_items *items; skh_item_fold_fn fold; void *fold_user; uint32_t nslots; } prev_opts;
 
 static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_path, const char *skip, uint32_t col, FILE *progress,
                           FILE *err, uint32_t rank, uint32_t world, uint64_t *bases, int plan_only, const plan_report *report,
@@ -2205,6 +2216,12 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
         }
 #endif
     }
+    if (pv && pv->fold && !plan_only && pool.nitem) {       /* the caller's slots and folds: a decode thread per slot at the most */
+        if ((uint32_t)nthreads > pv->nslots) { nthreads = (int)pv->nslots; if (nthreads == 1) pool.pipe = 0; }
+        pool.line_bases = (uint64_t *)calloc((size_t)nline + 1, sizeof *pool.line_bases);
+        if (!pool.line_bases) { pool.rc = SK_E_NOMEM; pool.rc_index = 0; prev_failed = 1; }
+        else { pool.prev = 1; pool.fold = pv->fold; pool.fold_user = pv->fold_user; }
+    } else
     if (pv && !plan_only && pool.nitem) {
         /* a slot per decode thread, a record cell per list line (the cells of lines this rank does not own stay zero) */
         const uint32_t nslots = nthreads == 1 ? 1u : (uint32_t)nthreads > pool.nitem ? pool.nitem : (uint32_t)nthreads;
@@ -2293,6 +2310,11 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
          * everybody's -- issued here by every rank whatever failed where (a rank that scanned nothing hands in zeros). */
         uint64_t *v = (uint64_t *)calloc((size_t)nline * 3u + 1, sizeof *v), *r2 = (uint64_t *)calloc((size_t)nline * 2u + 1, sizeof *r2);
         int rrc = v && r2 ? SK_OK : SK_E_NOMEM, arc;
+        if (pool.prev && pool.fold) {
+            uint32_t c;
+            for (c = 0; c < nctx; c++) (void)sk_item_slot(ctxs[c], -1);
+            for (i = 0; rrc == SK_OK && i < nline; i++) v[3u * i + 2] = pool.line_bases[i];
+        } else
         if (pool.prev) {
             (void)sk_item_slot(ctx, -1);
             if (rrc == SK_OK) rrc = sk_dev_download(ctx, r2, pool.d_rec, (size_t)nline * 2u * sizeof(uint64_t));      /* (waits for the folds) */
@@ -2328,7 +2350,7 @@ static int scan_list_once(sk_ctx *const *ctxs, uint32_t nctx, const char *list_p
     }
     if (pv && ctx && !plan_only) {
         if (pool.d_rec) (void)sk_dev_free(ctx, pool.d_rec);
-        if (pool.prev || prev_failed) (void)sk_item_slots(ctx, 0);
+        if (!pv->fold && (pool.prev || prev_failed)) (void)sk_item_slots(ctx, 0);
         free(pool.line_bases);
     }
     if (!plan_only) {
@@ -2434,8 +2456,21 @@ int skh_scan_list_prevalence(sk_ctx *ctx, const char *list_path, const char *ski
     if (!ctx || !list_path || !items_out || min_count < 1 || col == prev_col) return SK_E_ARG;
     if (!sk_item_slots || !sk_item_slot || !sk_item_fold || !sk_dev_alloc || !sk_dev_free || !sk_dev_upload || !sk_dev_download) return SK_E_STATE;
     items_out->item = NULL; items_out->n = 0;
+    memset(&pv, 0, sizeof pv);
     pv.prev_col = prev_col; pv.min_count = min_count; pv.items = items_out;
     return scan_list_impl(&ctx, 1, list_path, skip, col, progress, err, rank, world, bases, 0, NULL, 1, &pv);
+}
+
+int skh_scan_list_many_prevalence(sk_ctx *const *ctx, uint32_t n, const char *list_path, uint32_t col, uint32_t nslots,
+                                  skh_item_fold_fn fold, void *user, skh_prev_items *items_out, FILE *progress, FILE *err, uint64_t *bases)
+{
+    prev_opts pv;
+    if (!ctx || n < 1 || !list_path || !items_out || !fold || nslots < 1) return SK_E_ARG;
+    if (!sk_item_slot || (n > 1 && (!sk_scan_pinned_many || !sk_scan_pinned_packed_many))) return SK_E_STATE;
+    items_out->item = NULL; items_out->n = 0;
+    memset(&pv, 0, sizeof pv);
+    pv.items = items_out; pv.fold = fold; pv.fold_user = user; pv.nslots = nslots;
+    return scan_list_impl(ctx, n, list_path, NULL, col, progress, err, 0, 1, bases, 0, NULL, 1, &pv);
 }
 
 void skh_prev_items_free(skh_prev_items *items)
@@ -2525,6 +2560,13 @@ static int print_table(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_dr
     for (c = 0; c < 4; c++) free(cols[c]);
     free(worder);
     return rc;
+}
+
+/* the count table's shape from any four columns, with comment lines behind the header (kmer_scrub_count -S writes each strain's
+ * prevalence table with it) */
+int skh_print_table_cols_(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug_column, const uint32_t from[4], const char *extra)
+{
+    return print_table(ctx, ks, out, with_drug_column, from, extra);
 }
 
 int skh_print_counts(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug_column)

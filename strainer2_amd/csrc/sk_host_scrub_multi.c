@@ -22,6 +22,14 @@
  * strain_detect -S's machinery with the tables of step 1 taken over instead of rebuilt.  --scrub without --detect stays refused,
  * as before this mode existed (run the strains one by one for the informative lists alone).
  *
+ * With --prevalence=SUFFIX [--prevalence-items=SUFFIX] [--prevalence-min-count m] every strain also gets its prevalence table and
+ * item records beside its outfile (<outfile><SUFFIX>), byte for byte the single-strain program's: the members are loaded with three
+ * more columns behind their own, every resident union gets its item slots ONCE per decode (sk_item_slots on its context, kept
+ * across -A, -B, -C), the walk (skh_scan_list_many_prevalence) names a slot on every union before each submit, and where an item ends
+ * sm_item_fold_hook enqueues every union's sk_union_item_fold.  The per-strain -C rule is that fold's member mask, so sm_union_skips'
+ * rescans are not run with the flag on -- only its "skipping" lines are printed, at their place.  A strain the union cannot hold
+ * takes skh_scan_list_prevalence on its own context.  --scrub f --scrub-by prevalence --detect .. ranks step 2 by those columns.
+ *
  * Kept in a translation unit of its own: the host tests link sk_host.c, sk_host_sd.c and sk_host_cov.c against a device
  * double that has none of the union's COUNT entry points. */
 #define _GNU_SOURCE
@@ -51,7 +59,9 @@ typedef struct {
     int        print_rc;
     char      *err_buf;            /* --scrub: what the filter said, replayed in list order */
     size_t     err_len;
-    unsigned   made;               /* the files this run created: 1 outfile, 2 hits, 4 coverage table */
+    unsigned   made;               /* the files this run created: 1 outfile, 2 hits, 4 coverage table, 8 prevalence table, 16 item records */
+    char      *prev_path, *items_path;     /* --prevalence=SUFFIX, --prevalence-items=SUFFIX: <outfile><SUFFIX> (or NULL)        */
+    skh_prev_items pitems[3];      /* ... this strain's items of -A, -B, -C (a -C line equal to its genome is none)              */
 } sm_strain;
 
 typedef struct {
@@ -61,6 +71,8 @@ typedef struct {
     double     scrub_fraction;     /* >= 0: step 2 instead of the table */
     const char *scrub_list;        /* --scrub f0,f1,...: the scrub sweep -- each strain's class file goes to <informative outfile>.classes */
     int        independent;
+    int        prev, scrub_by_prev;/* --prevalence=SUFFIX: the three prevalence columns lie behind the table's own, from prev_base */
+    uint32_t   prev_base, prev_min;
     uint32_t   next;               /* pool: the next strain to take */
     pthread_mutex_t mu;
 } sm_job;
@@ -128,6 +140,38 @@ static ssize_t sm_gz_write(void *cookie, const char *buf, size_t n)
     return (ssize_t)n;
 }
 
+#define SM_PREV_WRITE_FAILED  2     /* (print_rc of a strain whose prevalence table could not be written ...) */
+#define SM_ITEMS_WRITE_FAILED 3     /* (... or its item records) */
+
+/* a strain's prevalence table and its items' records, the bytes `-r <genome> --prevalence=F --prevalence-items=G` writes to F and G
+ * (skh_kmer_scrub_count_main) */
+static int sm_print_prevalence(const sm_job *j, sm_strain *s)
+{
+    const uint32_t from[4] = {0, j->prev_base, j->prev_base + 1, j->prev_base + 2};
+    char extra[160];
+    FILE *pf = fopen(s->prev_path, "w");
+    int rc;
+    if (!pf) return SM_PREV_WRITE_FAILED;
+    setvbuf(pf, NULL, _IOFBF, 1 << 20);
+    snprintf(extra, sizeof extra, "#items\t%u\t%u\t%u\n#min_count\t%u\n", s->pitems[0].n, s->pitems[1].n, s->pitems[2].n, j->prev_min);
+    rc = skh_print_table_cols_(s->ctx, &s->ks, pf, j->with_drug, from, extra);
+    if (fclose(pf) != 0 && rc == SK_OK) rc = SM_PREV_WRITE_FAILED;
+    if (rc != SK_OK) return rc;
+    if (s->items_path) {
+        uint32_t l, k;
+        if (!(pf = fopen(s->items_path, "w"))) return SM_ITEMS_WRITE_FAILED;
+        fputs("#list\tline\tfile\tbases\tkmers_present\tkmer_hits\n", pf);
+        for (l = 0; l < 3; l++)
+            for (k = 0; k < s->pitems[l].n; k++) {
+                const skh_prev_item *t = &s->pitems[l].item[k];
+                fprintf(pf, "%c\t%u\t%s\t%llu\t%llu\t%llu\n", "ABC"[l], t->line, t->path, (unsigned long long)t->bases,
+                        (unsigned long long)t->kmers_present, (unsigned long long)t->kmer_hits);
+            }
+        if (fclose(pf) != 0) return SM_ITEMS_WRITE_FAILED;
+    }
+    return SK_OK;
+}
+
 static void *sm_print_worker(void *arg)
 {
     sm_job *j = (sm_job *)arg;
@@ -144,7 +188,9 @@ static void *sm_print_worker(void *arg)
             FILE *me = open_memstream(&s->err_buf, &s->err_len);
             char *cp = j->scrub_list ? (char *)malloc(strlen(s->outfile) + 9) : NULL;
             if (cp) { strcpy(cp, s->outfile); strcat(cp, ".classes"); }
+            const uint32_t pcols[3] = {j->prev_base, j->prev_base + 1, j->prev_base + 2};
             s->print_rc = (j->scrub_list ? (!cp || skh_scrub_filter_resident_sweep(s->ctx, &s->ks, j->with_drug, j->scrub_list, j->independent, cp, f, me ? me : stderr))
+                           : j->scrub_by_prev ? skh_scrub_filter_resident_cols(s->ctx, &s->ks, j->with_drug, pcols, j->scrub_fraction, j->independent, f, me ? me : stderr)
                                          : skh_scrub_filter_resident(s->ctx, &s->ks, j->with_drug, j->scrub_fraction, j->independent, f, me ? me : stderr))
                               ? SM_FILTER_FAILED : SK_OK;
             free(cp);
@@ -152,13 +198,25 @@ static void *sm_print_worker(void *arg)
         } else s->print_rc = skh_print_counts(s->ctx, &s->ks, f, j->with_drug);
         if (s->zo) { if (fclose(f) != 0 && s->print_rc == SK_OK) s->print_rc = SK_E_OPEN; }
         else if (fflush(f) != 0 && s->print_rc == SK_OK) s->print_rc = SK_E_OPEN;
+        if (j->prev && s->print_rc == SK_OK) s->print_rc = sm_print_prevalence(j, s);
     }
     return NULL;
 }
 
+/* --prevalence=SUFFIX for the passes: the first of the three prevalence columns, the threshold, the item slots every resident
+ * union of a decode has (made once per decode, kept across -A, -B, -C), and what SK_TIMING reports of them */
+typedef struct { uint32_t base, min, nslots; int timing; double slot_mb, fold_ms; uint64_t folds; } sm_prev;
+
 /* one strain, its own pass: what the single-strain program does (src/kmer_scrub_count.c:87-99) */
-static int sm_single_pass(sm_strain *s, const char *A, const char *B, const char *C, FILE *progress, FILE *err, uint64_t *bases)
+static int sm_single_pass(sm_strain *s, const char *A, const char *B, const char *C, FILE *progress, FILE *err, uint64_t *bases,
+                          const sm_prev *pv)
 {
+    if (pv) {                                        /* (with prevalence: the single-strain program's walk, on this strain's own context) */
+        if (skh_scan_list_prevalence(s->ctx, A, NULL, 1, pv->base, pv->min, &s->pitems[0], progress, err, 0, 1, bases) != SK_OK) return 1;
+        if (skh_scan_list_prevalence(s->ctx, B, NULL, 2, pv->base + 1, pv->min, &s->pitems[1], progress, err, 0, 1, bases) != SK_OK) return 1;
+        if (C && skh_scan_list_prevalence(s->ctx, C, s->genome, 3, pv->base + 2, pv->min, &s->pitems[2], progress, err, 0, 1, bases) != SK_OK) return 1;
+        return 0;
+    }
     if (skh_scan_list(s->ctx, A, NULL, 1, progress, err, 0, 1, bases) != SK_OK) return 1;
     if (skh_scan_list(s->ctx, B, NULL, 2, progress, err, 0, 1, bases) != SK_OK) return 1;
     if (C && skh_scan_list(s->ctx, C, s->genome, 3, progress, err, 0, 1, bases) != SK_OK) return 1;
@@ -183,20 +241,20 @@ static uint32_t sm_all(uint32_t n) { return n >= 32 ? 0xFFFFFFFFu : (1u << n) - 
 /* What a union of these strains will hold in HBM (sk_union_create + sk_union_count_enable): slots at half
  * load, keys, masks, the row map, the count column and its difference array, the two filter levels, the texts and their rank maps,
  * and the staging ring of its -C rescans.  An estimate from the layout, not a measurement. */
-static uint64_t sm_union_bytes(sm_strain *const *g, uint32_t n)
+static uint64_t sm_union_bytes(sm_strain *const *g, uint32_t n, uint32_t item_slots)
 {
     uint64_t rows = 0, bases = 0, slots = 1024, g2 = 4096;
     uint32_t k;
     for (k = 0; k < n; k++) { rows += g[k]->ks.nrows; bases += ((uint64_t)g[k]->ks.text_bases + 63u) / 64u * 64u + 64u; }
     while (slots < 2 * rows) slots <<= 1;
     while (g2 < rows * 32) g2 <<= 1;
-    return slots * 16 + rows * 33 + g2 / 8 + bases / 2 + (128ull << 20);
+    return slots * 16 + rows * 33 + g2 / 8 + bases / 2 + (128ull << 20) + (uint64_t)item_slots * rows * 8;     /* (item slots: --prevalence=SUFFIX) */
 }
 
 /* the union of one group with its count column.  SM_FALLBACK: a member it cannot hold (SK_E_STATE) -- the caller runs the strains
  * one by one.  SM_LATER: it did not fit next to the unions already made (`others`): nothing is lost, no list has been scanned into
  * them yet -- the caller decodes the lists for those and makes this one again afterwards */
-static int sm_union_make(sm_strain **g, uint32_t n, int others, sk_union **out, FILE *err)
+static int sm_union_make(sm_strain **g, uint32_t n, int others, sk_union **out, FILE *err, uint32_t *item_slots)
 {
     sk_ctx *m[SK_UNION_MAX];
     sk_union *u = NULL;
@@ -215,6 +273,19 @@ static int sm_union_make(sm_strain **g, uint32_t n, int others, sk_union **out, 
         if (!others) fprintf(err, "kmer_scrub_count: union count column failed: %s (%s)\n", sk_strerror(rc), sk_union_last_error(u));
         sk_union_destroy(u);
         return others ? SM_LATER : 1;
+    }
+    if (item_slots) {
+        /* the item slots, ONCE for all the lists of the decode (8 bytes x global rows each): as many as the walk has threads, or the
+         * most that fit -- with fewer, a decode thread owns a slot and the other items wait; a union without room for one closes the
+         * set as a failed count column does (sk_item_slots leaves no HIP error behind) */
+        uint32_t want = *item_slots;
+        while (want >= 1 && (rc = sk_item_slots(sk_union_context(u), want)) == SK_E_NOMEM) want /= 2;
+        if (rc != SK_OK || want < 1) {
+            if (!others) fprintf(err, "kmer_scrub_count: no room for an item slot of the union (--prevalence): %s (%s)\n", sk_strerror(rc), sk_union_last_error(u));
+            sk_union_destroy(u);
+            return others ? SM_LATER : 1;
+        }
+        *item_slots = want;
     }
     *out = u;
     return 0;
@@ -269,6 +340,145 @@ static int sm_decode(const sm_union *r, uint32_t nr, const char *A, const char *
     if (l < 3 && list[l]) return 1;
     for (i = 0; C && i < nr; i++) if (sm_union_skips(&r[i], C, err)) return 1;
     return 0;
+}
+
+/* ---- the decode with --prevalence=SUFFIX.  Every scan of the walk goes into an item slot of every union
+ * (skh_scan_list_many_prevalence), and where an item ends every union folds that slot into its members (sk_union_item_fold):
+ * the count column, the prevalence column and the record cell of (line, union, member).  The -C rule is the fold's member mask: a
+ * line equal to a member's genome is folded into everybody but that member, so it is no item of that strain -- no record, not in
+ * its nC, nothing in either column.  The count column is still the flag-off column bit for bit: there the line is added to every
+ * member and taken back from the one (sm_union_skips), and in integer adds mod 2^32 "never added" equals "added and taken back". */
+typedef struct {
+    const sm_union *r; uint32_t nr;
+    uint32_t col, prev_col, min;
+    char **line; uint32_t nline; int is_c;
+    uint64_t **d_rec;                   /* per union, device: [line][member] {kmers_present, kmer_hits} */
+    FILE *err;
+} sm_fold_job;
+
+static int sm_item_fold_hook(void *user, uint32_t slot, uint32_t line)
+{
+    const sm_fold_job *j = (const sm_fold_job *)user;
+    uint32_t i, k;
+    if (line >= j->nline) return SK_E_ARG;           /* (the walk read more lines than this run did: the list changed under it) */
+    for (i = 0; i < j->nr; i++) {
+        const sm_union *r = &j->r[i];
+        uint32_t mask = sm_all(r->n);
+        int rc;
+        for (k = 0; j->is_c && k < r->n; k++) if (strcmp(r->g[k]->genome, j->line[line]) == 0) mask &= ~(1u << k);
+        rc = sk_union_item_fold(r->u, slot, j->col, j->prev_col, mask, j->min, j->d_rec[i] + ((size_t)line * r->n) * 2u);
+        if (rc != SK_OK) return rc;
+    }
+    return SK_OK;
+}
+
+static void sm_lines_free(char **line, uint32_t n)
+{
+    uint32_t t;
+    for (t = 0; line && t < n; t++) free(line[t]);
+    free(line);
+}
+
+/* the list's lines as the walk reads them.  NULL with *oom 0: not readable (the walk says so); NULL with *oom 1: out of memory */
+static char **sm_list_lines(const char *path, uint32_t *n, int *oom)
+{
+    FILE *fp = fopen(path, "r");
+    char **out = (char **)malloc(sizeof *out), *line = NULL, *nl;
+    size_t cap = 0;
+    *n = 0; *oom = 0;
+    if (!fp || !out) { *oom = fp != NULL; if (fp) fclose(fp); free(out); return NULL; }
+    while (getline(&line, &cap, fp) != -1) {
+        char **grown = (char **)realloc(out, ((size_t)*n + 2) * sizeof *out);
+        if (grown) out = grown;
+        if ((nl = strchr(line, '\n')) != NULL) *nl = '\0';
+        if (!grown || !(out[*n] = strdup(line))) { *oom = 1; break; }
+        (*n)++;
+    }
+    free(line);
+    fclose(fp);
+    if (*oom) { sm_lines_free(out, *n); *n = 0; return NULL; }
+    return out;
+}
+
+static int sm_decode_prev(const sm_union *r, uint32_t nr, const char *A, const char *B, const char *C, FILE *progress, FILE *err,
+                          uint64_t *bases, sm_prev *pv)
+{
+    sk_ctx **uc = (sk_ctx **)malloc((size_t)nr * sizeof *uc);
+    const char *list[3] = {A, B, C};
+    uint32_t i, k, l, t, c_nline = 0;
+    char **c_line = NULL;                            /* -C's lines, kept for the "skipping" lines: the list is read ONCE */
+    int failed = 0;
+    if (!uc) { fprintf(err, "kmer_scrub_count: out of memory\n"); return 1; }
+    for (i = 0; i < nr; i++) uc[i] = sk_union_context(r[i].u);
+    if (pv->timing) (void)sk_item_fold_timing_(uc[0], 1, NULL, NULL);
+    for (l = 0; l < 3 && list[l] && !failed; l++) {
+        sm_fold_job j;
+        skh_prev_items walked = {NULL, 0};
+        uint64_t **h_rec = (uint64_t **)calloc(nr, sizeof *h_rec);
+        int rc = SK_OK, oom = 0;
+        memset(&j, 0, sizeof j);
+        j.r = r; j.nr = nr; j.col = l + 1; j.prev_col = pv->base + l; j.min = pv->min; j.is_c = l == 2; j.err = err;
+        j.line = sm_list_lines(list[l], &j.nline, &oom);
+        j.d_rec = (uint64_t **)calloc(nr, sizeof *j.d_rec);
+        if (!h_rec || !j.d_rec || oom) rc = SK_E_NOMEM;
+        for (i = 0; rc == SK_OK && j.line && i < nr; i++) {      /* the record cells, zeroed */
+            const size_t bytes = ((size_t)j.nline * r[i].n + 1) * 2u * sizeof(uint64_t);
+            if (!(h_rec[i] = (uint64_t *)calloc(1, bytes))) { rc = SK_E_NOMEM; break; }
+            if ((rc = sk_dev_alloc(uc[i], (void **)&j.d_rec[i], bytes)) == SK_OK) rc = sk_dev_upload(uc[i], j.d_rec[i], h_rec[i], bytes);
+        }
+        if (rc != SK_OK) fprintf(err, "kmer_scrub_count: no room for the items' records (--prevalence): %s\n", sk_strerror(rc));
+        else rc = skh_scan_list_many_prevalence(uc, nr, list[l], 0, pv->nslots, sm_item_fold_hook, &j, &walked, progress, err, bases);
+        failed = rc != SK_OK;
+        if (!failed) {                                           /* the walk's lines are the lines the masks and cells were made from */
+            int same = walked.n == j.nline;
+            for (t = 0; same && t < walked.n; t++) same = walked.item[t].line == t + 1 && !strcmp(walked.item[t].path, j.line[t]);
+            if (!same) { fprintf(err, "kmer_scrub_count: %s changed while it was read\n", list[l]); failed = 1; }
+        }
+        for (i = 0; i < nr; i++) {                               /* where the list ends: ONE wait per union, then its cells come home */
+            const size_t bytes = ((size_t)j.nline * r[i].n + 1) * 2u * sizeof(uint64_t);
+            int src = sk_sync(uc[i]);
+            if (src == SK_OK && !failed && j.d_rec && j.d_rec[i]) src = sk_dev_download(uc[i], h_rec[i], j.d_rec[i], bytes);
+            if (src != SK_OK && !failed) {
+                fprintf(err, "kmer_scrub_count: the items' records could not be fetched: %s (%s)\n", sk_strerror(src), sk_last_error(uc[i]));
+                failed = 1;
+            }
+            if (j.d_rec && j.d_rec[i]) (void)sk_dev_free(uc[i], j.d_rec[i]);
+        }
+        for (i = 0; !failed && i < nr; i++)                      /* every member's items of this list */
+            for (k = 0; k < r[i].n; k++) {
+                skh_prev_items *o = &r[i].g[k]->pitems[l];
+                o->item = (skh_prev_item *)calloc((size_t)walked.n + 1, sizeof *o->item);
+                o->n = 0;
+                if (!o->item) { fprintf(err, "kmer_scrub_count: out of memory\n"); failed = 1; break; }
+                for (t = 0; t < walked.n; t++) {
+                    const skh_prev_item *w = &walked.item[t];
+                    const uint64_t *cell = h_rec[i] + ((size_t)(w->line - 1) * r[i].n + k) * 2u;
+                    skh_prev_item *it = &o->item[o->n];
+                    if (j.is_c && strcmp(r[i].g[k]->genome, w->path) == 0) continue;
+                    it->line = w->line; it->path = strdup(w->path); it->bases = w->bases;
+                    it->kmers_present = cell[0]; it->kmer_hits = cell[1];
+                    o->n++;
+                }
+            }
+        skh_prev_items_free(&walked);
+        for (i = 0; i < nr; i++) if (h_rec) free(h_rec[i]);
+        free(h_rec); free(j.d_rec);
+        if (l == 2 && !failed) { c_line = j.line; c_nline = j.nline; }
+        else sm_lines_free(j.line, j.nline);
+    }
+    if (pv->timing) {
+        double ms = 0.0;
+        uint64_t nf = 0;
+        (void)sk_item_fold_timing_(uc[0], 0, &ms, &nf);
+        pv->fold_ms += ms; pv->folds += nf;
+    }
+    free(uc);
+    /* the lines a member would have skipped: said where and in the order one pass per union said them (sm_union_skips) */
+    for (i = 0; !failed && i < nr; i++)
+        for (t = 0; t < c_nline; t++)
+            for (k = 0; k < r[i].n; k++) if (strcmp(r[i].g[k]->genome, c_line[t]) == 0) fprintf(err, "skipping %s (identical match)\n", c_line[t]);
+    sm_lines_free(c_line, c_nline);
+    return failed;
 }
 
 static int sm_is_gz(const char *p)
@@ -526,17 +736,75 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
     int independent = 0, detect_argc = 0, want_sw = 0;
     const char *scrub_list = NULL;                   /* --scrub f0,f1,...: the scrub sweep (scrub_fraction is f0) */
     char **detect_argv = NULL;                       /* --detect ...: strain_detect's arguments (step 3 for all the strains) */
+    /* --prevalence=SUFFIX [--prevalence-items=SUFFIX] [--prevalence-min-count m] [--scrub-by prevalence]: each strain's prevalence
+     * table (and item records) beside its outfile, from the same pass (the rule is in include/strainer_kmer.h at sk_item_fold) */
+    const char *prev_sfx = NULL, *items_sfx = NULL, *prev_min_text = NULL, *scrub_by = NULL;
+    uint32_t prev_min = 1;
+    int scrub_by_prev = 0;
+    sm_prev pvs, *pv = NULL;
+    char **allname = NULL;                           /* ... every output name of every strain line, whichever rank writes it */
+    uint32_t nall = 0;
 
     /* the words of the single-strain program's extensions (skh_kmer_scrub_count_main): everything behind --detect is
      * strain_detect's command line; --scrub and --independent are taken out of argv before getopt.  Without --detect, -S does
      * not take them: the informative lists alone are the single-strain program's */
     for (c = 1; c < argc; c++)
         if (!strcmp(argv[c], "--detect")) { detect_argv = argv + c; detect_argc = argc - c; argc = c; break; }
-    for (c = 1; c < argc; c++)                        /* (before anything is read, and before --scrub-by could pass for --scrub) */
-        if (!strncmp(argv[c], "--prevalence", 12) || !strncmp(argv[c], "--scrub-by", 10)) {
-            fprintf(err, "kmer_scrub_count: --prevalence does not go with -S: a union's per-key fold and its subtracting -C pass have no per-item form yet\n");
+    /* the prevalence words (before anything is read, and before --scrub-by could pass for --scrub): under -S they take a SUFFIX --
+     * each strain's table goes to <its outfile><SUFFIX> --, because one file name cannot serve many strains */
+    for (c = 1, j = 1; c < argc; c++) {
+        if (!strncmp(argv[c], "--prevalence-min-count", 22) && (argv[c][22] == 0 || argv[c][22] == '=')) {
+            prev_min_text = argv[c][22] ? argv[c] + 23 : (c + 1 < argc ? argv[++c] : "");
+            continue;
+        }
+        if (!strncmp(argv[c], "--prevalence-items", 18) && (argv[c][18] == 0 || argv[c][18] == '=')) {
+            if (argv[c][18] == 0 || argv[c][19] == 0) {
+                fprintf(err, "kmer_scrub_count: with -S, --prevalence-items takes a suffix: give --prevalence-items=SUFFIX (each strain's records go to <its outfile><SUFFIX>)\n");
+                return 1;
+            }
+            items_sfx = argv[c] + 19;
+            continue;
+        }
+        if (!strncmp(argv[c], "--prevalence", 12)) {
+            if (argv[c][12] != '=' || argv[c][13] == 0) {
+                fprintf(err, "kmer_scrub_count: --prevalence does not go with -S as it stands: one file name cannot serve many strains; "
+                             "give --prevalence=SUFFIX (each strain's table goes to <its outfile><SUFFIX>)\n");
+                return 1;
+            }
+            prev_sfx = argv[c] + 13;
+            continue;
+        }
+        if (!strncmp(argv[c], "--scrub-by", 10) && (argv[c][10] == 0 || argv[c][10] == '=')) {
+            scrub_by = argv[c][10] ? argv[c] + 11 : (c + 1 < argc ? argv[++c] : "");
+            continue;
+        }
+        argv[j++] = argv[c];
+    }
+    argc = j;
+    if (scrub_by && strcmp(scrub_by, "prevalence") && strcmp(scrub_by, "count")) {
+        fprintf(err, "kmer_scrub_count: --scrub-by takes count or prevalence\n");
+        return 1;
+    }
+    scrub_by_prev = scrub_by && !strcmp(scrub_by, "prevalence");
+    if ((prev_min_text || items_sfx) && !prev_sfx) {
+        fprintf(err, "kmer_scrub_count: --prevalence-min-count and --prevalence-items need --prevalence=SUFFIX\n");
+        return 1;
+    }
+    if (scrub_by_prev && !prev_sfx) { fprintf(err, "kmer_scrub_count: --scrub-by prevalence needs --prevalence=SUFFIX\n"); return 1; }
+    if (prev_min_text) {
+        char *e;
+        const unsigned long long m = strtoull(prev_min_text, &e, 10);
+        if (e == prev_min_text || *e || prev_min_text[0] == '-' || prev_min_text[0] == '+' || m < 1 || m > 0xFFFFFFFFull) {
+            fprintf(err, "kmer_scrub_count: --prevalence-min-count needs an integer of at least 1\n");
             return 1;
         }
+        prev_min = (uint32_t)m;
+    }
+    if (scrub_by) {                                   /* (--scrub-by needs --scrub, whatever else the line holds) */
+        int has_scrub = 0;
+        for (c = 1; c < argc; c++) if (!strncmp(argv[c], "--scrub", 7) && (argv[c][7] == 0 || argv[c][7] == '=')) has_scrub = 1;
+        if (!has_scrub) { fprintf(err, "kmer_scrub_count: --scrub-by needs --scrub <min_fraction>\n"); return 1; }
+    }
     for (c = 1; !detect_argv && c < argc; c++)
         if (!strncmp(argv[c], "--scrub", 7) || !strcmp(argv[c], "--independent")) {
             fprintf(err, "kmer_scrub_count: -S does not go with --scrub/--detect (run the strains one by one for those)\n");
@@ -599,6 +867,10 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
         fprintf(err, "kmer_scrub_count: --detect needs --scrub <min_fraction> and a single process\n");
         return 1;
     }
+    if (scrub_by_prev && scrub_list) {
+        fprintf(err, "kmer_scrub_count: --scrub-by prevalence does not go with a list of fractions (the scrub sweep ranks by count)\n");
+        return 1;
+    }
     if (detect_argv && sm_check_detect(detect_argc, detect_argv, &want_cov, &want_sw, err)) return 1;
     if (scrub_list && !want_sw) {
         fprintf(err, "kmer_scrub_count: --scrub %s: a list of fractions goes with --detect ... --coverage-scrub-sweep\n", scrub_list);
@@ -641,6 +913,21 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
                 free(line); fclose(fp);
                 goto done;
             }
+            if (prev_sfx) {
+                /* the names this line's strain will write, on whichever rank: compared below over ALL the lines, before the deal --
+                 * the ranks write into the same directories */
+                char **grown = (char **)realloc(allname, ((size_t)nall + 6) * sizeof *allname), *cat;
+                const char *sfx[3];
+                int q;
+                if (!grown) { fprintf(err, "kmer_scrub_count: out of memory\n"); free(line); fclose(fp); goto done; }
+                allname = grown;
+                sfx[0] = prev_sfx; sfx[1] = items_sfx; sfx[2] = scrub_list ? ".classes" : NULL;
+                allname[nall++] = strdup(fo);
+                for (q = 0; q < 3; q++)
+                    if (sfx[q] && (cat = (char *)malloc(strlen(fo) + strlen(sfx[q]) + 1)) != NULL) { strcpy(cat, fo); strcat(cat, sfx[q]); allname[nall++] = cat; }
+                if (fh && !(want_cov & 2)) allname[nall++] = strdup(fh);
+                if (fh && want_cov) allname[nall++] = sm_cov_path(fh);
+            }
             if (world > 1 && (int)(lineno++ % (unsigned)world) != rank) continue;     /* strains are dealt to the ranks; no collective */
             st = (sm_strain *)realloc(st, ((size_t)ns + 1) * sizeof *st);
             memset(&st[ns], 0, sizeof st[ns]);
@@ -654,19 +941,43 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
         free(line);
         fclose(fp);
     }
+    if (prev_sfx) {
+        /* each strain's prevalence files: its outfile's name with the suffix behind it.  No two names of the run may coincide --
+         * outfiles x and x.p with the suffix .p -- or one file would end up holding another's bytes */
+        uint32_t a2, b2;
+        for (a2 = 0; a2 < nall; a2++)
+            for (b2 = a2 + 1; b2 <= nall; b2++) {
+                const char *other = b2 < nall ? allname[b2] : P;
+                if (allname[a2] && other && !strcmp(allname[a2], other)) {
+                    fprintf(err, "kmer_scrub_count: two outputs of this run would be the one file %s (the suffixes of --prevalence / --prevalence-items go behind each outfile's name)\n", other);
+                    goto done;
+                }
+            }
+        for (k = 0; k < ns; k++) {
+            st[k].prev_path = (char *)malloc(strlen(st[k].outfile) + strlen(prev_sfx) + 1);
+            if (st[k].prev_path) { strcpy(st[k].prev_path, st[k].outfile); strcat(st[k].prev_path, prev_sfx); }
+            if (items_sfx && (st[k].items_path = (char *)malloc(strlen(st[k].outfile) + strlen(items_sfx) + 1)) != NULL) {
+                strcpy(st[k].items_path, st[k].outfile); strcat(st[k].items_path, items_sfx);
+            }
+            if (!st[k].prev_path || (items_sfx && !st[k].items_path)) { fprintf(err, "kmer_scrub_count: out of memory\n"); goto done; }
+        }
+        memset(&pvs, 0, sizeof pvs);
+        pvs.base = detect_argv ? 6u : 4u; pvs.min = prev_min; pvs.timing = getenv("SK_TIMING") != NULL;
+        pv = &pvs;
+    }
     /* every outfile is created before anything is scanned: a run that cannot write its results does not start (the hit lists
      * and coverage tables are written by step 3, which opens them again) */
     for (k = 0; k < ns; k++) any_gz |= sm_is_gz(st[k].outfile);
     if (any_gz) { skzo_pool_start(&zpool, sm_threads()); zpool_on = 1; }
     for (k = 0; k < ns; k++) {
-        const char *more[2];
+        const char *more[4];
         int m;
         if (sm_is_gz(st[k].outfile)) st[k].zo = skzo_open(&zpool, st[k].outfile);
         else st[k].fp = fopen(st[k].outfile, "w");
         if (!st[k].zo && !st[k].fp) { fprintf(err, "kmer_scrub_count: cannot write %s\n", st[k].outfile); goto done; }
         st[k].made |= 1u;
-        more[0] = (want_cov & 2) ? NULL : st[k].hits; more[1] = st[k].cov;
-        for (m = 0; m < 2; m++) {
+        more[0] = (want_cov & 2) ? NULL : st[k].hits; more[1] = st[k].cov; more[2] = st[k].prev_path; more[3] = st[k].items_path;
+        for (m = 0; m < 4; m++) {
             FILE *f;
             if (!more[m]) continue;
             if (!(f = fopen(more[m], "w"))) { fprintf(err, "kmer_scrub_count: cannot write %s\n", more[m]); goto done; }
@@ -683,7 +994,7 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
     {   /* the strains are opened on worker threads; what went wrong is said here, in list order, up to the first failure */
         sm_job j;
         memset(&j, 0, sizeof j);
-        j.st = st; j.n = ns; j.device = device; j.ncols = detect_argv ? 6 : 4;
+        j.st = st; j.n = ns; j.device = device; j.ncols = (detect_argv ? 6 : 4) + (pv ? 3 : 0);    /* (the prevalence columns lie behind the table's own) */
         sm_pool_run(&j, sm_threads(), sm_open_worker);
         for (k = 0; k < ns; k++) {
             sm_strain *s = &st[k];
@@ -726,9 +1037,10 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
             uint64_t used = 0;
             while (a < nu && nr < max_unions) {                /* make this decode's unions */
                 const uint32_t n = nu - a < group ? nu - a : group;
-                const uint64_t est = sm_union_bytes(uni + a, n);
+                uint32_t slots = pv ? (uint32_t)sm_threads() : 0;
+                const uint64_t est = sm_union_bytes(uni + a, n, slots);
                 if (nr && used + est > budget) break;
-                rc = sm_union_make(uni + a, n, nr > 0, &res[nr].u, err);
+                rc = sm_union_make(uni + a, n, nr > 0, &res[nr].u, err, pv ? &slots : NULL);
                 if (rc == SM_FALLBACK) {                       /* (nothing was scanned) */
                     for (k = 0; k < n; k++) solo[nsolo++] = uni[a + k];
                     a += n;
@@ -738,9 +1050,25 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
                 if (rc == SM_LATER) { rc = 0; break; }         /* (made again for the next decode) */
                 if (rc != 0) break;
                 res[nr].g = uni + a; res[nr].n = n;
+                if (pv) {                                      /* (every union of a decode is walked with the fewest slots any of them has) */
+                    uint64_t rows = 0;
+                    for (k = 0; k < n; k++) rows += uni[a + k]->ks.nrows;
+                    if (!nr || slots < pv->nslots) pv->nslots = slots;
+                    if (!nr) pv->slot_mb = 0.0;
+                    pv->slot_mb += 1e-6 * (double)slots * 8.0 * (double)rows;
+                }
                 nr++; used += est; a += n;
             }
             if (rc == 0 && nr) {
+                if (pv) {
+                    const uint64_t f0 = pv->folds;
+                    const double m0 = pv->fold_ms;
+                    rc = sm_decode_prev(res, nr, A, B, C, progress, err, &list_bases, pv);
+                    if (pv->timing)
+                        fprintf(err, "kmer_scrub_count -S timing: prevalence: %u union(s) with %u item slot(s) each take %.1f MB of HBM; %llu union folds, "
+                                     "%.3f ms on the device (%.1f us each)\n", nr, pv->nslots, pv->slot_mb, (unsigned long long)(pv->folds - f0),
+                                pv->fold_ms - m0, pv->folds > f0 ? 1e3 * (pv->fold_ms - m0) / (double)(pv->folds - f0) : 0.0);
+                } else
                 rc = sm_decode(res, nr, A, B, C, progress, err, &fold_ms, &list_bases);
                 ndecode++;
                 if (rc == 0) nunion += nr;
@@ -749,7 +1077,7 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
             for (k = 0; k < nr; k++) { skh_pack_cache_set(sk_union_context(res[k].u), NULL, NULL); sk_union_destroy(res[k].u); res[k].u = NULL; }
         }
         for (k = 0; rc == 0 && k < nsolo; k++) {
-            rc = sm_single_pass(solo[k], A, B, C, progress, err, &list_bases);
+            rc = sm_single_pass(solo[k], A, B, C, progress, err, &list_bases, pv);
             nsingle++;
             ndecode++;
             if (progress) { fclose(progress); progress = NULL; }
@@ -766,11 +1094,16 @@ static int sm_main(int argc, char **argv, FILE *out, FILE *err, int *pack_cache_
         sm_job j;
         memset(&j, 0, sizeof j);
         j.st = st; j.n = ns; j.with_drug = C != NULL; j.scrub_fraction = scrub_fraction; j.scrub_list = scrub_list; j.independent = independent;
+        j.prev = pv != NULL; j.scrub_by_prev = scrub_by_prev; j.prev_base = pv ? pv->base : 0; j.prev_min = prev_min;
         sm_pool_run(&j, sm_threads(), sm_print_worker);
         for (k = 0; k < ns; k++) {
             int wrc = st[k].print_rc;
             if (st[k].err_buf && st[k].err_len) fwrite(st[k].err_buf, 1, st[k].err_len, err);
             if (wrc == SM_FILTER_FAILED) goto done;
+            if (wrc == SM_PREV_WRITE_FAILED || wrc == SM_ITEMS_WRITE_FAILED) {
+                fprintf(err, "kmer_scrub_count: cannot write %s\n", wrc == SM_PREV_WRITE_FAILED ? st[k].prev_path : st[k].items_path);
+                goto done;
+            }
             if (st[k].zo) { if (skzo_close(st[k].zo) && wrc == SK_OK) wrc = SK_E_OPEN; st[k].zo = NULL; }
             if (st[k].fp) { if (fclose(st[k].fp) != 0 && wrc == SK_OK) wrc = SK_E_OPEN; st[k].fp = NULL; }
             if (wrc == SK_E_OPEN) { fprintf(err, "kmer_scrub_count: error writing %s\n", st[k].outfile); goto done; }
@@ -817,6 +1150,8 @@ done:
             if (st[k].made & 1u) unlink(st[k].outfile);
             if (st[k].made & 2u) unlink(st[k].hits);
             if (st[k].made & 4u) unlink(st[k].cov);
+            if (st[k].made & 8u) unlink(st[k].prev_path);
+            if (st[k].made & 16u) unlink(st[k].items_path);
         }
         if (st[k].ctx) { skh_pack_cache_set(st[k].ctx, NULL, NULL); sk_ctx_destroy(st[k].ctx); }
         skh_keyset_free(&st[k].ks);
@@ -824,8 +1159,12 @@ done:
         free(st[k].outfile);
         free(st[k].hits); free(st[k].glist); free(st[k].cov);
         free(st[k].err_buf);
+        free(st[k].prev_path); free(st[k].items_path);
+        for (c = 0; c < 3; c++) skh_prev_items_free(&st[k].pitems[c]);
     }
     free(st);
+    for (k = 0; k < nall; k++) free(allname[k]);
+    free(allname);
     if (progress) fclose(progress);
     if (zpool_on) skzo_pool_stop(&zpool);
     return status;

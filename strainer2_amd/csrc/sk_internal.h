@@ -162,6 +162,22 @@ typedef struct sk_item_view {
     uint32_t *d_scratch, *d_diff, *d_sums, *d_count, *d_prev; uint32_t nrows;
 } sk_item_view;
 int sk_item_view_(sk_ctx *ctx, uint32_t slot, uint32_t count_col, uint32_t prev_col, sk_item_view *out);
+/* An item slot of a union's context and what its fold needs of the union and its members, as they lie on the device, for
+ * sk_union_item_fold (sk_prevalence.hip): the slot's pair and the block sums as in sk_item_view (global rows), canon[] (every global
+ * row's key slot row), the members' first global rows (base[members] = nrows) and, for the members of member_mask, their two
+ * columns (the others' are NULL).  Both scan lanes of the union's context are joined before this returns and lane 1's next scan
+ * waits for what the caller puts on `stream`; a masked member's pending increments are flushed on its own stream and `stream`
+ * waits for them on the device -- the host waits for nothing. */
+typedef struct sk_union_item_view {
+    sk_ctx *uc; int device; void *stream;  /* the union's context; hipStream_t */
+    uint32_t *d_scratch, *d_diff, *d_sums; const uint32_t *d_canon; uint32_t nrows, members;
+    uint32_t base[SK_UNION_MAX + 1];
+    uint32_t *d_count[SK_UNION_MAX], *d_prev[SK_UNION_MAX];
+} sk_union_item_view;
+int sk_union_item_view_(sk_union *u, uint32_t slot, uint32_t count_col, uint32_t prev_col, uint32_t member_mask, sk_union_item_view *out);
+/* skh_print_counts' table from columns from[0..3] of ctx (from[0]: the reference_count column), `extra` (or NULL) written behind
+ * the header line: the prevalence table of kmer_scrub_count --prevalence */
+int skh_print_table_cols_(sk_ctx *ctx, const skh_keyset *ks, FILE *out, int with_drug_column, const uint32_t from[4], const char *extra);
 /* the block sums (one per 4096 entries) of a difference array of n entries and their exclusive scan in place, on ctx's stream */
 int sk_diff_sums_(sk_ctx *ctx, const uint32_t *d_diff, uint32_t n, uint32_t *d_sums);
 /* the device time of the item folds (sk_item_fold), from an event pair around each while the clocks are on: the call hands out the

@@ -82,6 +82,7 @@ ABI_SYMBOLS = [
     "sk_covacc_finish_target_rarefaction", "skh_rarefaction_parse", "skh_rarefaction_draw", "skh_rarefaction_class",
     "skh_rarefaction_fold", "skh_rarefaction_write",
     "sk_item_slots", "sk_item_slot", "sk_item_fold", "skh_scan_list_prevalence", "skh_prev_items_free", "skh_scrub_filter_resident_cols",
+    "sk_union_item_fold", "skh_scan_list_many_prevalence",
 ]
 
 
@@ -156,6 +157,7 @@ lib.sk_text_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 lib.sk_item_slots.argtypes = [C.c_void_p, C.c_uint32]
 lib.sk_item_slot.argtypes = [C.c_void_p, C.c_int]
 lib.sk_item_fold.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+lib.sk_union_item_fold.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
 lib.sk_counts_fetch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_counts_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 lib.sk_counts_set_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -1177,6 +1179,22 @@ class KmerUnion:
         if member_mask is None:
             member_mask = (1 << len(self._members)) - 1
         self._uck(lib.sk_union_counts_fold(self._h, ucol, member_col, member_mask & 0xFFFFFFFF, int(bool(subtract))))
+
+    def item_slots(self, nslots):
+        """sk_item_slots on the union's context: nslots item slots of global rows (8 bytes x rows each); 0 frees them"""
+        self._uck(lib.sk_item_slots(lib.sk_union_context(self._h), nslots))
+
+    def item_slot(self, slot):
+        """sk_item_slot on the union's context: its COUNT scans add into item slot `slot` from now on; -1: into the column they name"""
+        self._uck(lib.sk_item_slot(lib.sk_union_context(self._h), slot))
+
+    def item_fold(self, slot, count_col, prev_col, member_mask=None, min_count=1, records=None):
+        """sk_union_item_fold: with V a key's count in the slot, every member of member_mask (default: all) gets
+        counts[count_col] += V and counts[prev_col] += (V >= min_count) on its rows, the slot is zero again; records: a device
+        pointer to [members][2] u64 that {rows with V >= min_count, sum of V} of each such member are added to.  Asynchronous."""
+        if member_mask is None:
+            member_mask = (1 << len(self._members)) - 1
+        self._uck(lib.sk_union_item_fold(self._h, slot, count_col, prev_col, member_mask & 0xFFFFFFFF, min_count, records))
 
     def scan_batch(self, batch, col=0):
         """sk_scan_batch on the union's context: ONE count scan of a filled TallyBatch into union column col"""
